@@ -4,7 +4,9 @@
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`.  For N > 1 the driver launches it under
 torch.distributed.run with one rank per GPU (RCCL); when it is started directly with --gpus N > 1 and no WORLD_SIZE it starts
 those N ranks itself as a child `python -m torch.distributed.run ...` (decided before anything touches the GPU; never re-execs)
-and fails loudly when the box has fewer than N GPUs or fewer than N ranks join.  Rank 0 prints ONE JSON line.
+and fails loudly when the box has fewer than N GPUs or fewer than N ranks join.  Rank 0 prints ONE JSON line; its `ms_per_step` is
+the time of one of the K timed steps of the main workload.  `--dump-outputs DIR` writes what the last of them computed (dump_outputs):
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Workload (BASELINE.json: "molecules/s (ELBO fwd+bwd+step) ... batch 1024, 1/2/4/8 MI355X"): a "step" is train.py:95-104 on one
 synthetic minibatch: idx = randint(0, 35, (b, 120)), one-hot target, MolecularVAE(i=120, o=292, c=35) with the reference's default
@@ -41,7 +43,7 @@ sys.path.insert(0, ROOT)
 
 L_SEQ, VOCAB, LATENT = 120, 35, 292
 H_DEC, NL_DEC = 1024, 4
-BF16_DENSE_PEAK_TFLOPS = 2500.0      # /opt/skills/guides/MI355X_MICROARCH.md, Peak BF16 MFMA dense
+BF16_DENSE_PEAK_TFLOPS = 2500.0      # MI355X peak dense BF16 MFMA
 F32_MFMA_PEAK_TFLOPS = 157.3
 HBM_PEAK_GBS = 8000.0
 
@@ -139,6 +141,8 @@ def parse_args():
                                                               "N-rank step anyway (GradSync(force=True)); prints `comm` for the one GPU at hand")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl == RCCL; gloo only to rehearse the multi-rank "
                                                        "path on a box with fewer GPUs than ranks)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (loss, "
+                                                                         "updated parameters, gradients) as DIR/<name>.npy, 64 MB at most")
     return ap.parse_args()
 
 
@@ -310,8 +314,43 @@ def make_workload(model, B, dtype, dev, rank, sync, L=L_SEQ, C=VOCAB, noise="dev
     return Models2dWorkload(B, dtype, dev, rank, sync)
 
 
-def measure(model, B, dtype, steps, warmup, dev, rank, world, sync, label, L=L_SEQ, C=VOCAB, pipeline=False, noise="device"):
-    """W untimed warm-up steps, then exactly `steps` steps between barrier + synchronize on both sides; MAX over ranks."""
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(wl, loss, out_dir, budget=DUMP_BYTES - (1 << 20)):
+    """--dump-outputs: what the last timed step hands its caller -- the loss (float64), every parameter after the update and every gradient
+    of that step (float32) -- one DIR/<name>.npy each.  Arrays are written whole while all of them fit in `budget` bytes (1 MB is left for the
+    .npy headers); otherwise every array above a common element cap keeps that many elements, flattened, at positions drawn by
+    numpy.random.RandomState(0) from its size alone, so two runs or two builds with the same arguments write comparable files."""
+    import numpy as np
+    import torch
+    arrays = {"loss": loss.detach().double().reshape(())}
+    for name, p in wl.model.named_parameters():
+        arrays["param." + name] = p.detach()
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad.detach()
+    cap, left = None, budget // 4 - 2
+    sizes = sorted(a.numel() for a in arrays.values())
+    for i, n in enumerate(sizes):                 # the largest cap that keeps the total within the budget
+        if n * (len(sizes) - i) > left:
+            cap = left // (len(sizes) - i)
+            break
+        left -= n
+    os.makedirs(out_dir, exist_ok=True)
+    sampled, positions = 0, {}
+    for name, a in arrays.items():
+        if cap is not None and a.numel() > cap:
+            if a.numel() not in positions:
+                positions[a.numel()] = torch.from_numpy(np.sort(np.random.RandomState(0).choice(a.numel(), cap, replace=False)))
+            a = a.reshape(-1)[positions[a.numel()].to(a.device)]
+            sampled += 1
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy() if name == "loss" else a.float().cpu().numpy())
+    log(f"dumped {len(arrays)} arrays to {out_dir}" + (f" ({sampled} sampled to {cap} elements each)" if sampled else ""))
+
+
+def measure(model, B, dtype, steps, warmup, dev, rank, world, sync, label, L=L_SEQ, C=VOCAB, pipeline=False, noise="device", dump_dir=None):
+    """W untimed warm-up steps, then exactly `steps` steps between barrier + synchronize on both sides; MAX over ranks.
+    dump_dir: rank 0 writes the last timed step's outputs there (dump_outputs)."""
     import torch
     import torch.distributed as dist
     from molecular_vae_amd import ops
@@ -362,6 +401,8 @@ def measure(model, B, dtype, steps, warmup, dev, rank, world, sync, label, L=L_S
         sched["per_rank"] = [dict(zip(("persist_fwd", "persist_bwd", "rowres_pipe", "failures", "skipped_steps"), [int(v) for v in x.tolist()])) for x in alls]
     ms = 1e3 * dt / steps
     log(f"[{label}] timed region done: {ms:.2f} ms/step")
+    if dump_dir is not None and rank == 0:
+        dump_outputs(wl, loss, dump_dir)
     tag_ms = {k: sum(s.elapsed_time(e) for s, e in v) / steps for k, v in prof.items()}      # per STEP (a tag may be recorded several times in one)
     roof = wl.roofline(tag_ms, dtype)
     roof["phase_ms"] = {k: round(v, 3) for k, v in tag_ms.items()}
@@ -457,6 +498,8 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         die("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        die("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args)                                           # never returns
     rank = int(os.environ.get("RANK", 0)); world = int(os.environ.get("WORLD_SIZE", 1))
@@ -498,7 +541,7 @@ def main():
         B, scaling = args.global_batch // world, "strong"
 
     main_res = measure(args.model, B, args.dtype, args.steps, args.warmup, dev, rank, world, sync, "main", args.seq_len, args.vocab,
-                       pipeline=(world == 1 and not force and args.model == "molvae" and not args.no_secondary))
+                       pipeline=(world == 1 and not force and args.model == "molvae" and not args.no_secondary), dump_dir=args.dump_outputs)
     metric = {"molvae": "molecules/s (ELBO fwd+bwd+step)", "moses": "molecules/s (mosesvae.VAE KL+CE fwd+bwd+step)",
               "models2d": "molecules/s (models2d.VAE ELBO fwd+bwd+step)"}[args.model]
     cfg = main_res["config"]; cfg["final_loss"] = main_res["final_loss"]

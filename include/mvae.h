@@ -4,7 +4,7 @@
  * surface of models.py / mosesvae.py and the loop body of train.py:94-104, and all arithmetic is delegated
  * to torch.nn primitives.  This header is therefore the boundary the build defines *beneath* that surface
  * (SURVEY.md section 8b): one entry point per fused op x {fwd,bwd}; each comment names the reference call
- * site (file:line under /root/reference) whose torch primitive it replaces.
+ * site (file:line in the reference) whose torch primitive it replaces.
  *
  * Conventions
  *  - raw DEVICE pointers, caller-owned (the library never allocates or frees caller memory);

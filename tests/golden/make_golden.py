@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Generate the golden fixtures in this directory FROM THE REFERENCE ITSELF.
 
-Runs only in the build container (needs /root/reference on disk).  It imports the
+Needs a checkout of the reference (aclyde11/molecular-VAE), named by REFERENCE_DIR.  It imports the
 reference's ``models.py`` / ``mosesvae.py`` / ``vocab.py`` as they lie there, loads
 weights from the build-owned seeded initialiser (oracle/initparams.py), feeds
 seeded inputs and records inputs + expected outputs.  Only DATA is written here
 (.npz); no reference source text is copied.
 
-    python tests/golden/make_golden.py            # writes g1..g5 *.npz next to this file
+    REFERENCE_DIR=<checkout> python tests/golden/make_golden.py     # writes g1..g7 *.npz next to this file
 
 Fixtures:
   g1_small.npz   reduced dims, B=3: every stage, recon/mu/logvar, loss, all parameter grads
@@ -27,7 +27,9 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, "/root/reference")
+if not os.path.isfile(os.path.join(os.environ.get("REFERENCE_DIR", ""), "models.py")):
+    sys.exit("make_golden.py: set REFERENCE_DIR to a checkout of the reference (the directory holding models.py)")
+sys.path.insert(0, os.environ["REFERENCE_DIR"])
 
 import models as ref_models          # noqa: E402  (reference, read-only)
 import mosesvae as ref_moses         # noqa: E402

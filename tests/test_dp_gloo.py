@@ -18,6 +18,12 @@ def _free_port():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
 
 
+def _barrier():
+    """dist.barrier() asks torch for the machine's accelerator, which opens the GPU where there is one; these ranks must leave it alone
+    (eight of them at once exceed what a shared GPU admits), so they meet in a collective on a CPU tensor instead."""
+    dist.all_reduce(torch.zeros(1))
+
+
 def _worker(rank, world, port, out_dir):
     os.environ["MASTER_ADDR"] = "127.0.0.1"; os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -67,7 +73,7 @@ def _worker(rank, world, port, out_dir):
         ref = np.concatenate([full["grads"][k].reshape(-1) for k in names])
         err = float(np.abs(flat.numpy() - ref).max() / np.abs(ref).max())
         np.save(os.path.join(out_dir, "result.npy"), np.array([err, abs(float(loss) - full["loss"]) / abs(full["loss"])]))
-    dist.barrier()
+    _barrier()
     dist.destroy_process_group()
 
 
@@ -151,7 +157,7 @@ def _worker8(rank, world, port, out_dir):
     assert len(set(seeds)) == world, seeds
     if rank == 0:
         np.save(os.path.join(out_dir, "ok8.npy"), np.array([1.0]))
-    dist.barrier()
+    _barrier()
     dist.destroy_process_group()
 
 

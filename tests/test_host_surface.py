@@ -233,6 +233,35 @@ def test_bench_refuses_world_size_mismatch_and_tuning_variables():
     assert r.returncode != 0 and "MVAE_DBG" in r.stderr and not r.stdout.strip()
 
 
+def test_bench_dump_outputs_writes_the_step_outputs_within_the_budget(tmp_path):
+    """--dump-outputs: loss (float64), every parameter and gradient (float32) as <name>.npy; small sets whole, large ones sampled under the
+    byte budget at the same positions on every call."""
+    import bench
+    torch.manual_seed(0)
+    wl = type("W", (), {})()
+    wl.model = torch.nn.Sequential(torch.nn.Linear(400, 300), torch.nn.Linear(300, 5))
+    wl.model(torch.randn(7, 400)).square().sum().backward()
+    loss = torch.tensor(1.25)
+    whole = str(tmp_path / "whole")
+    bench.dump_outputs(wl, loss, whole)
+    names = sorted(f for f in os.listdir(whole))
+    assert names == sorted(["loss.npy"] + [f"{k}.{n}.npy" for k in ("grad", "param") for n, _ in wl.model.named_parameters()])
+    assert np.load(os.path.join(whole, "loss.npy")).dtype == np.float64 and float(np.load(os.path.join(whole, "loss.npy"))) == 1.25
+    for n, p in wl.model.named_parameters():
+        assert np.array_equal(np.load(os.path.join(whole, f"param.{n}.npy")), p.detach().numpy())
+        assert np.array_equal(np.load(os.path.join(whole, f"grad.{n}.npy")), p.grad.numpy())
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    for d in (a, b):
+        bench.dump_outputs(wl, loss, d, budget=200_000)
+    assert sum(os.path.getsize(os.path.join(a, f)) for f in os.listdir(a)) <= 200_000 + 128 * len(os.listdir(a))
+    w = np.load(os.path.join(a, "param.0.weight.npy"))
+    assert w.dtype == np.float32 and w.ndim == 1 and w.size < 400 * 300
+    assert np.isin(w, wl.model[0].weight.detach().numpy()).all()
+    assert np.array_equal(np.load(os.path.join(a, "param.1.bias.npy")), wl.model[1].bias.detach().numpy())       # small arrays stay whole
+    for f in os.listdir(a):
+        assert np.array_equal(np.load(os.path.join(a, f)), np.load(os.path.join(b, f))), f
+
+
 def test_graft_entry_build_hook_runs():
     """The driver's "does it build" hook: compiles every HIP source for gfx950 and loads the library (no GPU needed)."""
     import __graft_entry__ as ge
