@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MVAE_ABI_VERSION 10
+#define MVAE_ABI_VERSION 11
 
 #define MVAE_OK 0
 #define MVAE_ERR_INVALID (-1)     /* bad argument (null pointer, bad size, misaligned leading dimension) */
@@ -478,6 +478,25 @@ int mvae_sumsq(int64_t n, const float* g, float* partial, void* stream);
 int mvae_clip_adam(int64_t n, float* p, const float* g, float* m, float* v, const float* partial, int64_t npartial,
                    float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps, int step,
                    float* norm_out, int norm_out_len, float* poison_reset, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * The same clip followed by torch.optim.SGD.step() (train_distributed.py:73,91) on a FLAT fp32 parameter / gradient /
+ * momentum buffer.  Reads the partial sums of mvae_sumsq exactly as mvae_clip_adam does (same norm, same coef, same
+ * skip of a step whose norm is not finite, same norm_out / poison_reset), then per element, in torch's order:
+ *   d = g * coef + weight_decay * p
+ *   momentum != 0: buf = initialised ? momentum * buf + (1 - dampening) * d : d;   d = nesterov ? d + momentum * buf : buf
+ *   p -= lr * d
+ * momentum == 0: buf and initialised are not touched (may be NULL): 12 bytes per element instead of 20.
+ * initialised [2] (momentum != 0): torch's "momentum_buffer is not None", as a device word double-buffered by the host's step
+ * parity: the launch reads initialised[parity] and writes initialised[parity ^ 1] (1 after an update; a skipped step copies the
+ * word it read), so no block of a launch reads what another block of the same launch writes.  The caller alternates parity
+ * step by step, and sets both words when it loads a state.
+ * Rejected (MVAE_ERR_INVALID, before anything is enqueued): n < 0, npartial < 1, momentum < 0, nesterov with momentum <= 0 or
+ * dampening != 0, parity not 0 / 1, a NULL buffer that the arguments need.
+ */
+int mvae_clip_sgd(int64_t n, float* p, const float* g, float* buf, const float* partial, int64_t npartial, float grad_scale,
+                  float max_norm, float lr, float momentum, float dampening, float weight_decay, int nesterov, int32_t* initialised,
+                  int parity, float* norm_out, int norm_out_len, float* poison_reset, void* stream);
 
 #ifdef __cplusplus
 }

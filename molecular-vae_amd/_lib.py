@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = ((os.environ.get("MVAE_LIB") if os.environ.get("MVAE_TUNING", "0") not in ("", "0") else None)
             or os.path.join(_HERE, "libmvae_hip.so"))      # MVAE_LIB too is honoured only under MVAE_TUNING=1
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 MVAE_F32, MVAE_BF16, MVAE_F32X3 = 0, 1, 2
 CONV_BWD_X3 = 0x100
 ACT_NONE, ACT_SELU, ACT_RELU = 0, 1, 2
@@ -153,6 +153,7 @@ SIGNATURES = {
     "mvae_sumsq_workspace": (_sz, [_i64]),
     "mvae_sumsq": (_i, [_i64, _vp, _vp, _vp]),
     "mvae_clip_adam": (_i, [_i64, _vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _i, _vp, _i, _vp, _vp]),
+    "mvae_clip_sgd": (_i, [_i64, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _i, _vp, _i, _vp, _i, _vp, _vp]),
 }
 
 _lib = None

@@ -1,6 +1,6 @@
 // HBM-bound helper kernels of the SMILES-VAE training path (gfx950): casts/transposes, embedding-table gather and
 // its deterministic scatter, SELU derivative, reparameterisation, softmax head, ELBO, reductions,
-// gradient-norm + Adam.  All reductions use fixed orders (wave shuffle -> LDS -> serial over blocks) so results
+// gradient-norm + Adam / SGD.  All reductions use fixed orders (wave shuffle -> LDS -> serial over blocks) so results
 // are bitwise reproducible run to run.
 #include <atomic>
 #include "common.hpp"
@@ -929,6 +929,72 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(long n, float* p, const 
   }
 }
 
+// torch.optim.SGD.step() behind the same clip (mvae_clip_sgd in include/mvae.h).  HBM-bound: 20 B per element with momentum (p r/w, g r,
+// buf r/w), 12 B without.  The aligned body moves 16 bytes per access (n4 float4 items); the elements behind it (and everything when a
+// pointer is not 16-byte aligned: n4 == 0) go through the scalar tail.
+// Explicit fmaf: the vector body and the scalar tail must round alike (the sharded optimiser moves an element from one to the other and
+// must still match the all-reduce form bit for bit), which implicit contraction does not promise.
+template <bool MOM>
+__device__ __forceinline__ float sgd_elem(float p, float g, float& b, float coef, float lr, float mom, float damp1, float wd, bool nest, bool init) {
+  float d = fmaf(wd, p, g * coef);
+  if (MOM) {
+    b = init ? fmaf(damp1, d, mom * b) : d;
+    d = nest ? fmaf(mom, b, d) : b;
+  }
+  return fmaf(-lr, d, p);
+}
+template <bool MOM>
+__global__ __launch_bounds__(256) void clip_sgd_kernel(long n, long n4, float* p, const float* g, float* buf, const float* partial, long npartial,
+                                                       float grad_scale, float max_norm, float lr, float mom, float damp1, float wd, int nesterov,
+                                                       int32_t* initialised, int parity, float* norm_out, int norm_out_len, float* poison_reset) {
+  __shared__ float red[4];
+  __shared__ float s_coef;
+  // the norm, the clip coefficient and the skip decision exactly as clip_adam_kernel forms them
+  float a = 0.f;
+  for (long i = threadIdx.x; i < npartial; i += 256) a += partial[i];
+  a = block_sum_256(a, red);
+  // "momentum_buffer is not None": every block reads the word of this step's parity; only block 0 writes, and only the OTHER word (read by
+  // the next launch, which the stream orders behind this one) -- no block can see a value written during this launch
+  const bool init = MOM ? (initialised[parity] != 0) : false;
+  if (threadIdx.x == 0) {
+    const float norm = sqrtf(a) * grad_scale;
+    float coef = 1.f;
+    if (max_norm > 0.f) { coef = max_norm / (norm + 1e-6f); if (coef > 1.f) coef = 1.f; }
+    const bool finite = norm < __builtin_huge_valf() && norm == norm;
+    s_coef = finite ? coef * grad_scale : __builtin_nanf("");
+    if (blockIdx.x == 0) {
+      if (norm_out) { norm_out[0] = norm; if (!finite && norm_out_len >= 2) norm_out[1] += 1.f; }
+      if (poison_reset) *poison_reset = 0.f;
+      if (MOM) initialised[parity ^ 1] = finite ? 1 : (init ? 1 : 0);      // a skipped step leaves the buffer (and its state) as it was
+    }
+  }
+  __syncthreads();
+  const float coef = s_coef;
+  if (!(coef == coef)) return;
+  const bool nest = nesterov != 0;
+  const long stride = (long)gridDim.x * 256;
+  float4* p4 = reinterpret_cast<float4*>(p);
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  float4* b4 = reinterpret_cast<float4*>(buf);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    float4 pv = p4[i];
+    const float4 gv = g4[i];
+    float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (MOM) bv = b4[i];
+    pv.x = sgd_elem<MOM>(pv.x, gv.x, bv.x, coef, lr, mom, damp1, wd, nest, init);
+    pv.y = sgd_elem<MOM>(pv.y, gv.y, bv.y, coef, lr, mom, damp1, wd, nest, init);
+    pv.z = sgd_elem<MOM>(pv.z, gv.z, bv.z, coef, lr, mom, damp1, wd, nest, init);
+    pv.w = sgd_elem<MOM>(pv.w, gv.w, bv.w, coef, lr, mom, damp1, wd, nest, init);
+    p4[i] = pv;
+    if (MOM) b4[i] = bv;
+  }
+  for (long i = 4 * n4 + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    float bi = MOM ? buf[i] : 0.f;
+    p[i] = sgd_elem<MOM>(p[i], g[i], bi, coef, lr, mom, damp1, wd, nest, init);
+    if (MOM) buf[i] = bi;
+  }
+}
+
 // ------------------------------------------------------------------------------------------- device-side input pipeline
 // rows[b] selects a molecule of the uint8 index store [N, L] resident in HBM; emits what MoleLoader.__getitem__ + the default collate
 // yield (data_loader.py:26-31): int64 indices [B, L] and the float one-hot [B, L, C].
@@ -1478,6 +1544,29 @@ int mvae_clip_adam(int64_t n, float* p, const float* g, float* m, float* v, cons
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
   hipLaunchKernelGGL(clip_adam_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, (long)n, p, g, m, v, partial,
                      (long)npartial, grad_scale, max_norm, lr, beta1, beta2, eps, (float)bc1, (float)sqrt(bc2), norm_out, norm_out_len, poison_reset);
+  MVAE_CHECK_HIP(hipGetLastError());
+  return MVAE_OK;
+}
+
+int mvae_clip_sgd(int64_t n, float* p, const float* g, float* buf, const float* partial, int64_t npartial, float grad_scale, float max_norm,
+                  float lr, float momentum, float dampening, float weight_decay, int nesterov, int32_t* initialised, int parity, float* norm_out,
+                  int norm_out_len, float* poison_reset, void* stream) {
+  if (n < 0 || npartial < 1 || !(momentum >= 0.f) || (parity != 0 && parity != 1)) return MVAE_ERR_INVALID;
+  if (nesterov && (momentum <= 0.f || dampening != 0.f)) return MVAE_ERR_INVALID;
+  const bool mom = momentum != 0.f;
+  if (!partial || (n > 0 && (!p || !g)) || (mom && (!initialised || (n > 0 && !buf)))) return MVAE_ERR_INVALID;
+  const bool aligned = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | (mom ? reinterpret_cast<uintptr_t>(buf) : 0)) & 15) == 0;
+  const long n4 = aligned ? (long)(n / 4) : 0;
+  // one block at least: the norm, the skip count, the poison slot and the state word are written even when this slice is empty
+  const int grid = grid_for(n4 > 0 ? n4 : n, 256, 4096);
+  if (mom)
+    hipLaunchKernelGGL(clip_sgd_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (long)n, n4, p, g, buf, partial, (long)npartial,
+                       grad_scale, max_norm, lr, momentum, 1.f - dampening, weight_decay, nesterov, initialised, parity, norm_out, norm_out_len,
+                       poison_reset);
+  else
+    hipLaunchKernelGGL(clip_sgd_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (long)n, n4, p, g, (float*)nullptr, partial,
+                       (long)npartial, grad_scale, max_norm, lr, 0.f, 1.f, weight_decay, 0, (int32_t*)nullptr, 0, norm_out, norm_out_len,
+                       poison_reset);
   MVAE_CHECK_HIP(hipGetLastError());
   return MVAE_OK;
 }

@@ -929,3 +929,13 @@ def clip_adam(p, g, m, v, partial, grad_scale, max_norm, lr, b1, b2, eps, step, 
     check(L.load().mvae_clip_adam(p.numel(), ptr(p), ptr(g), ptr(m), ptr(v), ptr(partial), partial.numel(), float(grad_scale),
                                   float(max_norm), float(lr), float(b1), float(b2), float(eps), int(step), ptr(norm_out), norm_out.numel(),
                                   ptr(poison_reset), stream_ptr()), "mvae_clip_adam")
+
+
+def clip_sgd(p, g, buf, partial, grad_scale, max_norm, lr, momentum, dampening, weight_decay, nesterov, initialised, parity, norm_out=None,
+             poison_reset=None):
+    """torch.optim.SGD.step() behind the global-norm clip (mvae_clip_sgd).  buf / initialised (int32 [2]) are used only with momentum != 0;
+    parity: the host step's parity (which word of `initialised` this launch reads).  norm_out / poison_reset as in clip_adam."""
+    check(L.load().mvae_clip_sgd(p.numel(), ptr(p), ptr(g), ptr(buf), ptr(partial), partial.numel(), float(grad_scale), float(max_norm),
+                                 float(lr), float(momentum), float(dampening), float(weight_decay), int(bool(nesterov)), ptr(initialised),
+                                 int(parity), ptr(norm_out), norm_out.numel() if norm_out is not None else 0, ptr(poison_reset), stream_ptr()),
+          "mvae_clip_sgd")

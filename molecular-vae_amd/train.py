@@ -1,9 +1,12 @@
-"""Training-loop surface of train.py:81-104 / train_distributed.py:72-73, MI355X-native.
+"""Training-loop surface of train.py:81-104 / train_distributed.py:72-91, MI355X-native.
 
   * ``loss_function`` -- the reference's ELBO (train.py:31-38) as one fused HIP forward/backward pair.
   * ``FusedAdam``     -- ``clip_grad_norm_(params, max_norm)`` (train.py:102) + ``optim.Adam.step()`` (train.py:81,104)
                          as two HIP kernels over one flat fp32 buffer; a ``torch.optim.Optimizer`` so LR schedulers
                          (``ReduceLROnPlateau``, train.py:83) and ``state_dict()`` (train.py:173) keep working.
+  * ``FusedSGD``      -- ``clip_grad_norm_(params, max_norm)`` + ``optim.SGD(momentum=...).step()`` (train_distributed.py:73,91) on the
+                         same flat buffers and data-parallel path as FusedAdam (two HIP kernels, one gradient norm over every
+                         param group); ``state_dict()`` in ``torch.optim.SGD``'s layout (train_distributed.py:145-151).
   * ``GradSync``      -- data parallelism: one process per GPU, bucketed all-reduce(SUM) of the flat gradient over RCCL
                          (backend "nccl" on ROCm) / gloo on CPU, replacing ``nn.DataParallel`` (train_distributed.py:72).
   * ``shard_batch`` / ``ShardedSampler`` -- contiguous per-rank shards (the commented-out DistributedSampler of
@@ -353,6 +356,227 @@ class FusedAdam(torch.optim.Optimizer):
                     self.state[p]["step"] = torch.as_tensor(float(st["step"]))
                     f["step"] = int(float(st["step"]))
                 idx += 1
+
+
+class FusedSGD(torch.optim.Optimizer):
+    """SGD with momentum (train_distributed.py:73) with the global-norm clip of train_distributed.py:91 fused in.
+
+    The layout of ``FusedAdam``: one fp32 flat parameter / gradient / momentum buffer per param group (each ``p.data`` a view of it, the
+    poison slot at ``g[n]``, gradient sinks registered), the same ``GradSync`` data parallelism (early ranges from backward, bf16 wire,
+    sharded form), and ``step()`` = ``mvae_sumsq`` + ``mvae_clip_sgd`` with no host synchronisation.  Unlike FusedAdam the gradient norm is
+    ONE norm over every group, as ``clip_grad_norm_(model.parameters())`` forms it: each group's partial sums fill a slice of one shared
+    array that every group's update reads, so a poisoned or non-finite gradient anywhere skips the update of every group, and
+    ``skipped_steps`` counts steps.  ``state_dict()`` has ``torch.optim.SGD``'s layout (a ``momentum_buffer`` per parameter once the first
+    update has run, none before) and loads into it and back.
+    """
+
+    # torch.optim.SGD's remaining hyper-parameters at their inert values: kept in every param_group so that ``state_dict()`` has SGD's layout
+    _SGD_INERT = dict(maximize=False, foreach=None, differentiable=False, fused=None)
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, max_grad_norm=0.0, grad_sync=None,
+                 shard_optimizer=False, *, maximize=False, foreach=None, differentiable=False, fused=None):
+        """shard_optimizer (needs a GradSync with world > 1, one param group): reduce-scatter of the gradient, clip + SGD on this rank's
+        1/world slice of the flat buffers (the momentum buffer of the other slices stays old until `gather_state()`), all-gather of the
+        parameters; the norm is formed from the same 64K-element partial sums in the same order as the all-reduce form, so both forms give
+        bit-identical parameters."""
+        asked = dict(maximize=maximize, foreach=foreach, differentiable=differentiable, fused=fused)
+        for k, v in asked.items():
+            if v != self._SGD_INERT[k]:
+                raise ValueError(f"FusedSGD: {k}={v!r} is not supported (it runs one fused HIP kernel; {k} must stay {self._SGD_INERT[k]!r})")
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, max_grad_norm=max_grad_norm,
+                        **self._SGD_INERT)
+        self._check_hyper(defaults)
+        super().__init__(params, defaults)
+        for group in self.param_groups:
+            self._check_hyper(group)
+        self.grad_sync = grad_sync
+        self.shard = bool(shard_optimizer) and grad_sync is not None and grad_sync.active
+        self._moments_stale = False
+        if self.shard:
+            if len(self.param_groups) > 1:
+                raise ValueError("FusedSGD(shard_optimizer=True) takes one param group")
+            if grad_sync.compress is not None:
+                raise ValueError("GradSync(compress=...) applies to the all-reduce form only: the reduce-scatter of shard_optimizer=True sends fp32")
+            grad_sync.allow_early = False
+        world = grad_sync.world if self.shard else 1
+        chunk = 1 << 16
+        groups = [[p for p in g["params"] if p.requires_grad] for g in self.param_groups]
+        devs = {ps[0].device for ps in groups if ps}
+        if len(devs) > 1:
+            raise ValueError("FusedSGD: every param group must live on one device (the groups share one gradient norm)")
+        dev = devs.pop() if devs else torch.device("cpu")
+        sizes = []
+        for ps in groups:
+            n = sum(p.numel() for p in ps)
+            # (n + 1: the poison slot, see FusedAdam)  sharded form: equal slices on whole 64K-element chunks of the partial sums
+            shard_elems = ((n + 1 + world * chunk - 1) // (world * chunk)) * chunk if self.shard else n + 1
+            sizes.append((n, shard_elems, shard_elems * world))
+        # ONE partial-sum array for all groups (group k's chunks at [part_off[k], part_off[k] + nparts_k)) and one norm / skip counter
+        nparts = [(n_alloc + chunk - 1) >> 16 if ps else 0 for ps, (_, _, n_alloc) in zip(groups, sizes)]
+        self._partial = torch.zeros(max(1, sum(nparts)), dtype=torch.float32, device=dev)
+        self._norm = torch.zeros(2, dtype=torch.float32, device=dev)
+        self._flat, self._buf_view = [], {}
+        part_off = 0
+        for ps, (n, shard_elems, n_alloc), npart in zip(groups, sizes, nparts):
+            if not ps:
+                self._flat.append(None)
+                continue
+            pflat = torch.zeros(n_alloc, dtype=torch.float32, device=dev)
+            g = torch.zeros_like(pflat); buf = torch.zeros_like(pflat)
+            off = 0
+            for p in ps:
+                k = p.numel()
+                with torch.no_grad():
+                    pflat[off:off + k].copy_(p.data.reshape(-1))
+                    p.data = pflat[off:off + k].view(p.shape)
+                self._buf_view[p] = buf[off:off + k].view(p.shape)
+                off += k
+            # init: torch's "momentum_buffer is not None" for this group, double-buffered by the parity of `step` (mvae_clip_sgd)
+            self._flat.append(dict(params=ps, p=pflat, g=g, buf=buf, partial=self._partial[part_off:part_off + npart], norm=self._norm,
+                                   init=torch.zeros(2, dtype=torch.int32, device=dev), step=0, n=n, shard_elems=shard_elems,
+                                   poison=g[n:n + 1]))
+            part_off += npart
+            off = 0
+            for p in ps:
+                L.register_grad_sink(p, self, g, off, poison=g[n:n + 1])
+                off += p.numel()
+        L.PARAM_EPOCH[0] += 1
+
+    @staticmethod
+    def _check_hyper(group):
+        """What torch.optim.SGD's constructor refuses."""
+        if group["lr"] < 0.0:
+            raise ValueError(f"Invalid learning rate: {group['lr']}")
+        if group["momentum"] < 0.0:
+            raise ValueError(f"Invalid momentum value: {group['momentum']}")
+        if group["weight_decay"] < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {group['weight_decay']}")
+        if group["nesterov"] and (group["momentum"] <= 0 or group["dampening"] != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        for k, v in FusedSGD._SGD_INERT.items():
+            if group.get(k, v) != v:
+                raise ValueError(f"FusedSGD: {k}={group[k]!r} is not supported")
+
+    @property
+    def last_grad_norm(self):
+        """Device tensor holding the pre-clip global gradient norm (over every group) of the last step."""
+        return self._norm[:1]
+
+    @property
+    def skipped_steps(self):
+        """Device tensor: how many step() calls were no-ops because the global gradient norm was not finite (poisoned or diverged)."""
+        return self._norm[1:2]
+
+    gather_grads = FusedAdam.gather_grads        # the same flat gradient buffers, the same sinks
+
+    @torch.no_grad()
+    @ops.traced("fused_sgd_step")
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        ops.persist_check()            # see FusedAdam.step: a poisoned step is skipped on the device, nothing waits here
+        ops.join_pending()
+        flats = self.gather_grads()
+        sync = self.grad_sync
+        if sync is not None and not self.shard:
+            with ops._Timed("dp_allreduce_exposed" if sync.active else None):
+                for g in flats:
+                    sync.start_rest(g)
+                sync.wait()
+        scale = sync.grad_scale() if sync is not None else 1.0
+        live = [(group, f) for group, f in zip(self.param_groups, self._flat) if f is not None]
+        for group, f in live:
+            self._check_hyper(group)
+            if f["p"].device.type != "cuda":
+                raise L.MvaeError("FusedSGD.step runs on the MI355X only (no CPU fallback)")
+        if self.shard:
+            group, f = live[0]
+            S, r = f["shard_elems"], dist.get_rank(sync.group)
+            with ops._Timed("dp_allreduce_exposed"):
+                gs = sync.reduce_scatter(f["g"], S)
+            sl = slice(r * S, (r + 1) * S)
+            cps = S >> 16
+            with ops._Timed("hbm_sumsq_clip_sgd"):
+                self._partial.zero_()
+                ops.sumsq(gs, self._partial[r * cps:(r + 1) * cps])
+                dist.all_reduce(self._partial, group=sync.group)
+                self._clip_sgd(group, f, f["p"][sl], gs, f["buf"][sl], scale, first=True)
+            with ops._Timed("dp_allreduce_exposed"):
+                sync.all_gather(f["p"], S)
+            self._moments_stale = True
+        else:
+            with ops._Timed("hbm_sumsq_clip_sgd"):
+                for _, f in live:                   # every group's partial sums first: each update below reads all of them
+                    ops.sumsq(f["g"], f["partial"])
+                for k, (group, f) in enumerate(live):
+                    self._clip_sgd(group, f, f["p"], f["g"], f["buf"], scale, first=(k == 0))
+        L.PARAM_EPOCH[0] += 1
+        return loss
+
+    def _clip_sgd(self, group, f, p, g, buf, scale, first):
+        # norm_out for the first group only: the norm is the same for all, and the skip counter counts steps, not groups
+        ops.clip_sgd(p, g, buf, self._partial, scale, group["max_grad_norm"], group["lr"], group["momentum"], group["dampening"],
+                     group["weight_decay"], group["nesterov"], f["init"], f["step"] & 1, norm_out=(self._norm if first else None),
+                     poison_reset=f["poison"])
+        f["step"] += 1
+
+    def gather_state(self):
+        """Sharded form: collect every rank's slice of the momentum buffer (a collective; call it on every rank before ``state_dict()``)."""
+        if not self.shard:
+            return
+        for f in self._flat:
+            if f is not None:
+                self.grad_sync.all_gather(f["buf"], f["shard_elems"])
+        self._moments_stale = False
+
+    def _initialised(self, group, f):
+        return f is not None and group["momentum"] != 0 and int(f["init"][f["step"] & 1]) != 0      # reads a device word: synchronises
+
+    def state_dict(self):
+        """torch.optim.SGD's layout: ``state[i] = {"momentum_buffer": tensor}`` for every parameter once the group has taken an update with
+        momentum, nothing before.  Reads a device word (a checkpoint call).  Sharded form: refused until every rank ran ``gather_state()``."""
+        if self.shard and self._moments_stale:
+            raise L.MvaeError("FusedSGD(shard_optimizer=True).state_dict(): the momentum buffers of the other ranks' slices are stale; call "
+                              "optimizer.gather_state() on every rank first (a collective), then save")
+        for group, f in zip(self.param_groups, self._flat):
+            init = self._initialised(group, f)
+            for p in group["params"]:
+                if init and p in self._buf_view:
+                    self.state[p]["momentum_buffer"] = self._buf_view[p]
+                else:
+                    self.state.pop(p, None)
+        return super().state_dict()
+
+    def load_state_dict(self, state_dict):
+        """Accepts a FusedSGD or a ``torch.optim.SGD`` state dict (train_distributed.py:145-151 ``optimizer_state_dict``); hyper-parameters
+        present in the dict override ours.  A group whose entries carry a ``momentum_buffer`` (absent / None ones count as zero) continues
+        from it; a group without any starts as torch does at its first step (``buf = d``)."""
+        sd_groups = state_dict["param_groups"]
+        if len(sd_groups) != len(self.param_groups):
+            raise ValueError("loaded state dict has a different number of parameter groups")
+        for group, sg in zip(self.param_groups, sd_groups):
+            if len(sg["params"]) != len(group["params"]):
+                raise ValueError("loaded state dict contains a parameter group that doesn't match the size of optimizer's group")
+        for group, sg in zip(self.param_groups, sd_groups):
+            for k in ("lr", "momentum", "dampening", "weight_decay", "nesterov", "max_grad_norm", "initial_lr"):
+                if k in sg:
+                    group[k] = sg[k]
+            self._check_hyper(group)
+        idx = 0
+        for group, f in zip(self.param_groups, self._flat):
+            any_buf = False
+            for p in group["params"]:
+                st = state_dict["state"].get(idx)
+                b = st.get("momentum_buffer") if st is not None else None
+                if p in self._buf_view:
+                    if b is not None:
+                        self._buf_view[p].copy_(b); any_buf = True
+                    else:
+                        self._buf_view[p].zero_()
+                idx += 1
+            if f is not None:
+                f["init"].fill_(1 if any_buf else 0)           # both words: whichever parity the next step reads
+            for p in group["params"]:
+                self.state.pop(p, None)
 
 
 class CosineAnnealingLRWithRestart:
