@@ -228,21 +228,22 @@ def dt_code(dtype):
     raise MvaeError(f"unsupported dtype {dtype}")
 
 
-# Bumped by in-place parameter updates that bypass torch's version counters (FusedAdam.step, load_state_dict) so that the packed
+# Bumped by in-place parameter updates that bypass torch's version counters (the optimisers' step, load_state_dict) so that the packed
 # (bf16 / transposed) weight shadows are refreshed.  Code that edits parameter storage by hand (``p.data[...] = ...`` through a view
 # torch does not track) must do ``_lib.PARAM_EPOCH[0] += 1`` itself.
 PARAM_EPOCH = [0]
 
-# Gradient sinks.  train.FusedAdam registers, ON each parameter object (attribute ``_mvae_sink``), where that parameter's gradient
-# lives inside the optimiser's flat fp32 gradient buffer: (weakref(optimizer), flat, offset, numel).  The modules' backward passes
-# then write parameter gradients straight into that buffer (no gather copy) and can start the data-parallel all-reduce of a finished
-# range while the rest of backward is still running.  The entry dies with the parameter; a dead optimiser's entry is dropped on sight.
+# Gradient sinks.  train._FlatOptimizer (the base of FusedAdam and FusedSGD) registers, ON each parameter object (attribute
+# ``_mvae_sink``), where that parameter's gradient lives inside the optimiser's flat fp32 gradient buffer: (weakref(optimizer), flat,
+# offset, numel).  The modules' backward passes then write parameter gradients straight into that buffer (no gather copy) and can start
+# the data-parallel all-reduce of a finished range while the rest of backward is still running.  The entry dies with the parameter; a
+# dead optimiser's entry is dropped on sight.
 _SINK_ATTR = "_mvae_sink"
 
 
 def register_grad_sink(p, owner, flat, off, poison=None):
-    """poison: the spare fp32 slot behind the flat gradient buffer (FusedAdam): a persistent launch that gives up stores a NaN there, which
-    makes mvae_clip_adam skip the step (mvae_rnn_*_desc.poison)."""
+    """poison: the spare fp32 slot behind the flat gradient buffer (train._FlatOptimizer): a persistent launch that gives up stores a NaN
+    there, which makes the optimiser kernel skip the step (mvae_rnn_*_desc.poison)."""
     setattr(p, _SINK_ATTR, (weakref.ref(owner), flat, off, p.numel(), poison))
 
 

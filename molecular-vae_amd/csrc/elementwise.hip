@@ -893,12 +893,15 @@ __global__ __launch_bounds__(256) void sumsq_kernel(long n, const float* g, floa
   a = block_sum_256(a, red);
   if (threadIdx.x == 0) partial[blockIdx.x] = a;
 }
-__global__ __launch_bounds__(256) void clip_adam_kernel(long n, float* p, const float* g, float* m, float* v, const float* partial, long npartial,
-                                                        float grad_scale, float max_norm, float lr, float b1, float b2, float eps,
-                                                        float bc1, float bc2_sqrt, float* norm_out, int norm_out_len, float* poison_reset) {
+// The prologue of clip_adam_kernel and clip_sgd_kernel: the gradient norm from mvae_sumsq's partial sums and the scale to apply to every
+// gradient element (clip coefficient x grad_scale), the same value in every thread.  NaN: the norm is not finite (a poisoned step:
+// mvae_rnn_*_desc.poison, or genuinely diverged gradients) and the whole update is skipped.  Every block re-derives the norm from the
+// partials in the same fixed order, so every block (and, in the sharded form, every rank) takes the same decision.  Block 0 writes the
+// norm and counts a skipped step into norm_out, and resets the poison slot.
+__device__ __forceinline__ float clip_coef(const float* partial, long npartial, float grad_scale, float max_norm, float* norm_out,
+                                           int norm_out_len, float* poison_reset) {
   __shared__ float red[4];
   __shared__ float s_coef;
-  // every block re-derives the global norm from the partials in the same fixed order
   float a = 0.f;
   for (long i = threadIdx.x; i < npartial; i += 256) a += partial[i];
   a = block_sum_256(a, red);
@@ -906,8 +909,6 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(long n, float* p, const 
     const float norm = sqrtf(a) * grad_scale;
     float coef = 1.f;
     if (max_norm > 0.f) { coef = max_norm / (norm + 1e-6f); if (coef > 1.f) coef = 1.f; }
-    // a norm that is not finite (a poisoned step: mvae_rnn_*_desc.poison, or genuinely diverged gradients): skip the whole update -- every
-    // block takes the same decision from the same partials
     const bool finite = norm < __builtin_huge_valf() && norm == norm;
     s_coef = finite ? coef * grad_scale : __builtin_nanf("");
     if (blockIdx.x == 0) {
@@ -916,7 +917,12 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(long n, float* p, const 
     }
   }
   __syncthreads();
-  const float coef = s_coef;
+  return s_coef;
+}
+__global__ __launch_bounds__(256) void clip_adam_kernel(long n, float* p, const float* g, float* m, float* v, const float* partial, long npartial,
+                                                        float grad_scale, float max_norm, float lr, float b1, float b2, float eps,
+                                                        float bc1, float bc2_sqrt, float* norm_out, int norm_out_len, float* poison_reset) {
+  const float coef = clip_coef(partial, npartial, grad_scale, max_norm, norm_out, norm_out_len, poison_reset);
   if (!(coef == coef)) return;
   const float step_size = lr / bc1;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
@@ -947,30 +953,14 @@ template <bool MOM>
 __global__ __launch_bounds__(256) void clip_sgd_kernel(long n, long n4, float* p, const float* g, float* buf, const float* partial, long npartial,
                                                        float grad_scale, float max_norm, float lr, float mom, float damp1, float wd, int nesterov,
                                                        int32_t* initialised, int parity, float* norm_out, int norm_out_len, float* poison_reset) {
-  __shared__ float red[4];
-  __shared__ float s_coef;
-  // the norm, the clip coefficient and the skip decision exactly as clip_adam_kernel forms them
-  float a = 0.f;
-  for (long i = threadIdx.x; i < npartial; i += 256) a += partial[i];
-  a = block_sum_256(a, red);
   // "momentum_buffer is not None": every block reads the word of this step's parity; only block 0 writes, and only the OTHER word (read by
   // the next launch, which the stream orders behind this one) -- no block can see a value written during this launch
   const bool init = MOM ? (initialised[parity] != 0) : false;
-  if (threadIdx.x == 0) {
-    const float norm = sqrtf(a) * grad_scale;
-    float coef = 1.f;
-    if (max_norm > 0.f) { coef = max_norm / (norm + 1e-6f); if (coef > 1.f) coef = 1.f; }
-    const bool finite = norm < __builtin_huge_valf() && norm == norm;
-    s_coef = finite ? coef * grad_scale : __builtin_nanf("");
-    if (blockIdx.x == 0) {
-      if (norm_out) { norm_out[0] = norm; if (!finite && norm_out_len >= 2) norm_out[1] += 1.f; }
-      if (poison_reset) *poison_reset = 0.f;
-      if (MOM) initialised[parity ^ 1] = finite ? 1 : (init ? 1 : 0);      // a skipped step leaves the buffer (and its state) as it was
-    }
-  }
-  __syncthreads();
-  const float coef = s_coef;
-  if (!(coef == coef)) return;
+  const float coef = clip_coef(partial, npartial, grad_scale, max_norm, norm_out, norm_out_len, poison_reset);
+  const bool skip = !(coef == coef);
+  // a skipped step leaves the buffer (and its state) as it was
+  if (MOM && blockIdx.x == 0 && threadIdx.x == 0) initialised[parity ^ 1] = (!skip || init) ? 1 : 0;
+  if (skip) return;
   const bool nest = nesterov != 0;
   const long stride = (long)gridDim.x * 256;
   float4* p4 = reinterpret_cast<float4*>(p);

@@ -1,12 +1,15 @@
 """Training-loop surface of train.py:81-104 / train_distributed.py:72-91, MI355X-native.
 
   * ``loss_function`` -- the reference's ELBO (train.py:31-38) as one fused HIP forward/backward pair.
+  * ``_FlatOptimizer`` -- the base of both optimisers below: one flat fp32 buffer per param group (parameters, gradient, poison slot,
+                         optimiser state), the gradient sinks, the gradient-norm partial sums and both data-parallel forms of
+                         ``step()``; a ``torch.optim.Optimizer`` so LR schedulers (``ReduceLROnPlateau``, train.py:83) and
+                         ``state_dict()`` (train.py:173) keep working.
   * ``FusedAdam``     -- ``clip_grad_norm_(params, max_norm)`` (train.py:102) + ``optim.Adam.step()`` (train.py:81,104)
-                         as two HIP kernels over one flat fp32 buffer; a ``torch.optim.Optimizer`` so LR schedulers
-                         (``ReduceLROnPlateau``, train.py:83) and ``state_dict()`` (train.py:173) keep working.
-  * ``FusedSGD``      -- ``clip_grad_norm_(params, max_norm)`` + ``optim.SGD(momentum=...).step()`` (train_distributed.py:73,91) on the
-                         same flat buffers and data-parallel path as FusedAdam (two HIP kernels, one gradient norm over every
-                         param group); ``state_dict()`` in ``torch.optim.SGD``'s layout (train_distributed.py:145-151).
+                         as two HIP kernels (a gradient norm per param group).
+  * ``FusedSGD``      -- ``clip_grad_norm_(params, max_norm)`` + ``optim.SGD(momentum=...).step()`` (train_distributed.py:73,91) as two
+                         HIP kernels (one gradient norm over every param group); ``state_dict()`` in ``torch.optim.SGD``'s layout
+                         (train_distributed.py:145-151).
   * ``GradSync``      -- data parallelism: one process per GPU, bucketed all-reduce(SUM) of the flat gradient over RCCL
                          (backend "nccl" on ROCm) / gloo on CPU, replacing ``nn.DataParallel`` (train_distributed.py:72).
   * ``shard_batch`` / ``ShardedSampler`` -- contiguous per-rank shards (the commented-out DistributedSampler of
@@ -163,82 +166,87 @@ class ShardedSampler(torch.utils.data.Sampler):
 
 
 # ------------------------------------------------------------------------------------------------ optimiser
-class FusedAdam(torch.optim.Optimizer):
-    """Adam (no weight decay / amsgrad, as train.py:81) with the global-norm clip of train.py:102 fused in.
+class _FlatOptimizer(torch.optim.Optimizer):
+    """What FusedAdam and FusedSGD share: the flat buffers, the gradient sinks, the poison slot, the gradient-norm partial sums and both
+    data-parallel forms of ``step()``.
 
-    Parameters are flattened into one fp32 buffer (each ``p.data`` becomes a view of it); ``exp_avg`` / ``exp_avg_sq``
-    are views of flat buffers too, so ``state_dict()`` has torch.optim.Adam's layout.  ``step()`` gathers the
-    gradients into a flat buffer, all-reduces it when a process group is active, then runs
-    ``mvae_sumsq`` + ``mvae_clip_adam`` -- no host synchronisation anywhere.
+    Each param group's parameters live in one fp32 flat buffer (each ``p.data`` becomes a view of it), beside a flat gradient buffer and the
+    flat state buffers the subclass names in ``_STATE``.  ``step()`` gathers the gradients into the flat buffer, all-reduces it when a
+    process group is active, then runs ``mvae_sumsq`` + the subclass's fused clip-and-update kernel -- no host synchronisation anywhere.
+    Every group's partial sums fill a slice of ONE array, so a kernel may read its own group's slice (a norm per group) or all of it (one
+    norm over every group).  A subclass supplies ``_check_hyper``, ``_new_group``, ``_update``, ``_load_hyper`` and ``_load_state``, and
+    may override ``_check_groups`` and ``_export_state``.
     """
 
-    # torch.optim.Adam's remaining hyper-parameters at their inert values: kept in every param_group so that ``state_dict()`` loads into
-    # ``torch.optim.Adam`` (train.py:81,173) and the reverse; step() refuses any other value.
-    _ADAM_INERT = dict(weight_decay=0, amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None,
-                       decoupled_weight_decay=False)
+    _STATE = ()          # flat state buffers beside p and g, e.g. ("m", "v"): same layout, sharded alike, collected by gather_state()
+    _STATE_WHAT = ""     # what they hold, for the stale state_dict() refusal
+    _TRACE = _TIMER = None
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0, grad_sync=None, shard_optimizer=False):
-        """shard_optimizer (needs a GradSync with world > 1): the gradient is reduce-SCATTERED, every rank runs the clip + Adam update on its
-        1/world slice of the flat buffers only (exp_avg / exp_avg_sq of the other slices stay untouched: `gather_state()` collects them
-        before a checkpoint), and the updated parameters are all-gathered -- half the collective bytes of the all-reduce form and 1/world
-        of the 7 x 4 x P bytes of optimiser traffic.  The global gradient norm is formed from the same 64K-element partial sums in the same
-        order as the all-reduce form, so both forms give bit-identical parameters.  No early (in-backward) ranges in this form."""
-        defaults = dict(lr=lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm, **self._ADAM_INERT)
+    def __init__(self, params, defaults, grad_sync, shard_optimizer):
         super().__init__(params, defaults)
         self.grad_sync = grad_sync
         self.shard = bool(shard_optimizer) and grad_sync is not None and grad_sync.active
-        self._moments_stale = False      # sharded form: True from step() until gather_state() -- the other ranks' slices of exp_avg / exp_avg_sq are old
+        self._moments_stale = False      # sharded form: True from step() until gather_state() -- the other ranks' slices of the state are old
+        self._check_groups()
         if self.shard:
             if grad_sync.compress is not None:
                 raise ValueError("GradSync(compress=...) applies to the all-reduce form only: the reduce-scatter of shard_optimizer=True sends fp32")
             grad_sync.allow_early = False
         world = grad_sync.world if self.shard else 1
-        self._flat = []
-        for group in self.param_groups:
-            ps = [p for p in group["params"] if p.requires_grad]
+        chunk = 1 << 16
+        groups = [[p for p in g["params"] if p.requires_grad] for g in self.param_groups]
+        devs = {ps[0].device for ps in groups if ps}
+        if len(devs) > 1:
+            raise ValueError(f"{type(self).__name__}: every param group must live on one device (the groups share one partial-sum array)")
+        dev = devs.pop() if devs else torch.device("cpu")
+        # One spare element behind the parameters in every flat buffer: the POISON slot.  A persistent launch that gives up stores a NaN into
+        # g[n] (mvae_rnn_*_desc.poison); mvae_sumsq covers the slot, so the norm becomes NaN and the update kernel skips the whole update -- in
+        # data parallel on EVERY rank, because the slot travels with the last gradient bucket of the all-reduce (sharded form: with the
+        # all-reduced partial sums).  It is zero otherwise (p[n] and the state never leave zero) and adds nothing to the norm.
+        # sharded form: equal slices whose boundaries fall on the 64K-element chunks of the gradient-norm partial sums (zero padding)
+        sizes = [sum(p.numel() for p in ps) for ps in groups]
+        shard_elems = [((n + 1 + world * chunk - 1) // (world * chunk)) * chunk if self.shard else n + 1 for n in sizes]
+        nparts = [(S * world + chunk - 1) >> 16 if ps else 0 for ps, S in zip(groups, shard_elems)]
+        self._partial = torch.zeros(max(1, sum(nparts)), dtype=torch.float32, device=dev)   # group k's chunks follow group k-1's
+        self._norm = torch.zeros(2, dtype=torch.float32, device=dev)    # [0] the norm of the last step, [1] the skip counter
+        self._flat, self._views = [], {}
+        part_off = 0
+        for ps, n, S, npart in zip(groups, sizes, shard_elems, nparts):
             if not ps:
                 self._flat.append(None)
                 continue
-            dev = ps[0].device
-            n = sum(p.numel() for p in ps)
-            # One spare element behind the parameters in all four flat buffers: the POISON slot.  A persistent launch that gives up stores a
-            # NaN into g[n] (mvae_rnn_*_desc.poison); mvae_sumsq covers the slot, so the norm becomes NaN and mvae_clip_adam skips the whole
-            # update -- in data parallel on EVERY rank, because the slot travels with the last gradient bucket of the all-reduce (sharded
-            # form: with the all-reduced partial sums).  It is zero otherwise (p[n], m[n], v[n] never leave zero) and adds nothing to the norm.
-            # sharded form: equal slices whose boundaries fall on the 64K-element chunks of the gradient-norm partial sums (zero padding)
-            chunk = 1 << 16
-            shard_elems = ((n + 1 + world * chunk - 1) // (world * chunk)) * chunk if self.shard else n + 1
-            n_alloc = shard_elems * world
-            pflat = torch.zeros(n_alloc, dtype=torch.float32, device=dev)
-            m = torch.zeros_like(pflat); v = torch.zeros_like(pflat); g = torch.zeros_like(pflat)
+            pflat = torch.zeros(S * world, dtype=torch.float32, device=dev)
+            f = dict(params=ps, p=pflat, g=torch.zeros_like(pflat), **{s: torch.zeros_like(pflat) for s in self._STATE},
+                     partial=self._partial[part_off:part_off + npart], step=0, n=n, shard_elems=S)
+            f["poison"] = f["g"][n:n + 1]
+            part_off += npart
             off = 0
             for p in ps:
                 k = p.numel()
                 with torch.no_grad():
                     pflat[off:off + k].copy_(p.data.reshape(-1))
                     p.data = pflat[off:off + k].view(p.shape)
-                self.state[p] = dict(step=torch.tensor(0.0), exp_avg=m[off:off + k].view(p.shape),
-                                     exp_avg_sq=v[off:off + k].view(p.shape))
+                self._views[p] = {s: f[s][off:off + k].view(p.shape) for s in self._STATE}
+                L.register_grad_sink(p, self, f["g"], off, poison=f["poison"])   # modules may write their gradients straight into g
                 off += k
-            nparts = (n_alloc + (1 << 16) - 1) >> 16
-            self._flat.append(dict(params=ps, p=pflat, m=m, v=v, g=g, partial=torch.zeros(nparts, device=dev),
-                                   norm=torch.zeros(2, device=dev), step=0, n=n, shard_elems=shard_elems, poison=g[n:n + 1]))
-            off = 0
-            for p in ps:                 # modules may write their gradients straight into g (see _lib.register_grad_sink)
-                L.register_grad_sink(p, self, g, off, poison=g[n:n + 1])
-                off += p.numel()
+            self._new_group(f, first=all(x is None for x in self._flat))
+            self._flat.append(f)
         L.PARAM_EPOCH[0] += 1
+
+    def _check_groups(self):
+        """Constructor hook, run before any buffer is built: refuse what the subclass does not support."""
 
     @property
     def last_grad_norm(self):
-        """Device tensor holding the pre-clip global gradient norm of the last step (train.py:102's return value)."""
-        return self._flat[0]["norm"][:1]
+        """Device tensor holding the pre-clip gradient norm of the last step (train.py:102's return value): FusedAdam's first param group's,
+        FusedSGD's over every group."""
+        return self._norm[:1]
 
     @property
     def skipped_steps(self):
-        """Device tensor: how many step() calls the optimiser kernel turned into no-ops because the global gradient norm was not finite (a
-        persistent launch gave up and poisoned the step, or the gradients diverged).  Reading it synchronises; nothing in step() does."""
-        return self._flat[0]["norm"][1:2]
+        """Device tensor: how many step() calls the optimiser kernel turned into no-ops because the gradient norm was not finite (a persistent
+        launch gave up and poisoned the step, or the gradients diverged).  Reading it synchronises; nothing in step() does."""
+        return self._norm[1:2]
 
     def gather_grads(self):
         """Copy every ``p.grad`` into the flat gradient buffer (missing grads count as zero); returns the flats."""
@@ -267,111 +275,165 @@ class FusedAdam(torch.optim.Optimizer):
         return outs
 
     @torch.no_grad()
-    @ops.traced("fused_adam_step")
     def step(self, closure=None):
-        loss = closure() if closure is not None else None
-        # A launch with bounded spins that gave up during this step has poisoned the gradient buffer's spare slot ON THE DEVICE: the kernels below
-        # then skip the update by themselves, on every rank -- no host wait here.  persist_check only reports what has already arrived.
-        ops.persist_check()
-        ops.join_pending()             # gradients produced on a side stream (decoder weight-gradient GEMMs)
-        flats = self.gather_grads()
-        sync = self.grad_sync
-        if sync is not None and not self.shard:
-            with ops._Timed("dp_allreduce_exposed" if sync.active else None):   # bench.py: what the overlap with backward did not hide
-                for g in flats:
-                    sync.start_rest(g)
-                sync.wait()
-        scale = sync.grad_scale() if sync is not None else 1.0
-        for group, f in zip(self.param_groups, self._flat):
-            if f is None:
-                continue
-            f["step"] += 1
-            b1, b2 = group["betas"]
-            if group.get("weight_decay", 0) or group.get("amsgrad", False) or group.get("maximize", False):
-                raise L.MvaeError("FusedAdam implements plain Adam (train.py:81): weight_decay / amsgrad / maximize are not supported")
-            if f["p"].device.type != "cuda":
-                raise L.MvaeError("FusedAdam.step runs on the MI355X only (no CPU fallback)")
+        with ops.trace_range(self._TRACE):
+            loss = closure() if closure is not None else None
+            # A launch with bounded spins that gave up during this step has poisoned the gradient buffer's spare slot ON THE DEVICE: the
+            # kernels below then skip the update by themselves, on every rank -- no host wait here.  persist_check only reports what has
+            # already arrived.
+            ops.persist_check()
+            ops.join_pending()             # gradients produced on a side stream (decoder weight-gradient GEMMs)
+            flats = self.gather_grads()
+            sync = self.grad_sync
+            if sync is not None and not self.shard:
+                with ops._Timed("dp_allreduce_exposed" if sync.active else None):   # bench.py: what the overlap with backward did not hide
+                    for g in flats:
+                        sync.start_rest(g)
+                    sync.wait()
+            scale = sync.grad_scale() if sync is not None else 1.0
+            live = [(group, f) for group, f in zip(self.param_groups, self._flat) if f is not None]
+            for group, f in live:
+                self._check_hyper(group)
+                if f["p"].device.type != "cuda":
+                    raise L.MvaeError(f"{type(self).__name__}.step runs on the MI355X only (no CPU fallback)")
             if self.shard:
-                S, r = f["shard_elems"], dist.get_rank(sync.group)
-                with ops._Timed("dp_allreduce_exposed"):
-                    gs = sync.reduce_scatter(f["g"], S)
-                sl = slice(r * S, (r + 1) * S)
-                cps = S >> 16                                         # 64K-element chunks per shard: this rank's slice of the partial sums
-                with ops._Timed("hbm_sumsq_clip_adam"):
-                    f["partial"].zero_()
-                    ops.sumsq(gs, f["partial"][r * cps:(r + 1) * cps])
-                    dist.all_reduce(f["partial"], group=sync.group)    # disjoint slices + zeros: a gather, a few KB; same values on every rank
-                    ops.clip_adam(f["p"][sl], gs, f["m"][sl], f["v"][sl], f["partial"], scale, group["max_grad_norm"], group["lr"], b1, b2,
-                                  group["eps"], f["step"], f["norm"], poison_reset=f["poison"])
-                with ops._Timed("dp_allreduce_exposed"):
-                    sync.all_gather(f["p"], S)
-                self._moments_stale = True
+                r = dist.get_rank(sync.group)
+                for k, (group, f) in enumerate(live):
+                    S = f["shard_elems"]
+                    with ops._Timed("dp_allreduce_exposed"):
+                        gs = sync.reduce_scatter(f["g"], S)
+                    cps = S >> 16                                      # 64K-element chunks per shard: this rank's slice of the partial sums
+                    with ops._Timed(self._TIMER):
+                        f["partial"].zero_()
+                        ops.sumsq(gs, f["partial"][r * cps:(r + 1) * cps])
+                        dist.all_reduce(f["partial"], group=sync.group)   # disjoint slices + zeros: a gather, a few KB; same values on every rank
+                        self._update(group, f, slice(r * S, (r + 1) * S), gs, scale, first=(k == 0))
+                    with ops._Timed("dp_allreduce_exposed"):
+                        sync.all_gather(f["p"], S)
+                    self._moments_stale = True
             else:
-                with ops._Timed("hbm_sumsq_clip_adam"):
-                    ops.sumsq(f["g"], f["partial"])
-                    ops.clip_adam(f["p"], f["g"], f["m"], f["v"], f["partial"], scale, group["max_grad_norm"], group["lr"], b1, b2,
-                                  group["eps"], f["step"], f["norm"], poison_reset=f["poison"])
-            for p in f["params"]:
-                self.state[p]["step"] += 1
-        L.PARAM_EPOCH[0] += 1      # packed bf16 / transposed weight shadows must be refreshed
-        return loss
+                with ops._Timed(self._TIMER):
+                    for _, f in live:              # every group's partial sums first: an update may read all of them
+                        ops.sumsq(f["g"], f["partial"])
+                    for k, (group, f) in enumerate(live):
+                        self._update(group, f, slice(None), f["g"], scale, first=(k == 0))
+            L.PARAM_EPOCH[0] += 1      # packed bf16 / transposed weight shadows must be refreshed
+            return loss
 
     def gather_state(self):
-        """Sharded form: every rank holds the Adam moments of its own slice only; collect all of them (before ``state_dict()`` / a checkpoint)."""
+        """Sharded form: every rank holds the optimiser state of its own slice only; collect all of it (a collective: call it on every rank
+        before ``state_dict()`` / a checkpoint)."""
         if not self.shard:
             return
         for f in self._flat:
             if f is not None:
-                self.grad_sync.all_gather(f["m"], f["shard_elems"])
-                self.grad_sync.all_gather(f["v"], f["shard_elems"])
+                for s in self._STATE:
+                    self.grad_sync.all_gather(f[s], f["shard_elems"])
         self._moments_stale = False
 
     def state_dict(self):
-        """torch.optim.Adam's layout.  Sharded form: after a step() this rank holds current moments for its own 1/world slice only, so the
+        """The torch optimiser's layout.  Sharded form: after a step() this rank holds current state for its own 1/world slice only, so the
         dictionary would be silently wrong for the rest -- refuse until EVERY rank has called ``gather_state()`` (a collective: call it on all
         ranks, then save on rank 0)."""
         if self.shard and self._moments_stale:
-            raise L.MvaeError("FusedAdam(shard_optimizer=True).state_dict(): the Adam moments of the other ranks' slices are stale; call "
-                              "optimizer.gather_state() on every rank first (a collective), then save")
+            raise L.MvaeError(f"{type(self).__name__}(shard_optimizer=True).state_dict(): the {self._STATE_WHAT} of the other ranks' slices "
+                              "are stale; call optimizer.gather_state() on every rank first (a collective), then save")
+        self._export_state()
         return super().state_dict()
 
+    def _export_state(self):
+        """Hook: bring ``self.state`` into the torch optimiser's layout before ``state_dict()`` reads it."""
+
     def load_state_dict(self, state_dict):
-        """Accepts a FusedAdam or a ``torch.optim.Adam`` state dict (train.py:173 ``optimizer_state_dict``): same ``state`` layout
-        (``step`` / ``exp_avg`` / ``exp_avg_sq`` per parameter index); hyper-parameters present in the dict override ours."""
+        """Accepts this optimiser's or the matching torch optimiser's state dict; hyper-parameters present in the dict override ours."""
         sd_groups = state_dict["param_groups"]
         if len(sd_groups) != len(self.param_groups):
             raise ValueError("loaded state dict has a different number of parameter groups")
         for group, sg in zip(self.param_groups, sd_groups):
             if len(sg["params"]) != len(group["params"]):
                 raise ValueError("loaded state dict contains a parameter group that doesn't match the size of optimizer's group")
-            for k in ("lr", "betas", "eps", "max_grad_norm", "initial_lr"):
-                if k in sg:
-                    group[k] = tuple(sg[k]) if k == "betas" else sg[k]
+        for group, sg in zip(self.param_groups, sd_groups):
+            self._load_hyper(group, sg)
         idx = 0
         for group, f in zip(self.param_groups, self._flat):
-            for p in group["params"]:
-                st = state_dict["state"].get(idx)
-                if st is not None and f is not None and p in self.state:
-                    self.state[p]["exp_avg"].copy_(st["exp_avg"]); self.state[p]["exp_avg_sq"].copy_(st["exp_avg_sq"])
-                    self.state[p]["step"] = torch.as_tensor(float(st["step"]))
-                    f["step"] = int(float(st["step"]))
-                idx += 1
+            n = len(group["params"])
+            self._load_state(group, f, [state_dict["state"].get(i) for i in range(idx, idx + n)])
+            idx += n
 
 
-class FusedSGD(torch.optim.Optimizer):
-    """SGD with momentum (train_distributed.py:73) with the global-norm clip of train_distributed.py:91 fused in.
+class FusedAdam(_FlatOptimizer):
+    """Adam (no weight decay / amsgrad, as train.py:81) with the global-norm clip of train.py:102 fused in: ``mvae_sumsq`` +
+    ``mvae_clip_adam`` over the flat buffers of ``_FlatOptimizer``.
 
-    The layout of ``FusedAdam``: one fp32 flat parameter / gradient / momentum buffer per param group (each ``p.data`` a view of it, the
-    poison slot at ``g[n]``, gradient sinks registered), the same ``GradSync`` data parallelism (early ranges from backward, bf16 wire,
-    sharded form), and ``step()`` = ``mvae_sumsq`` + ``mvae_clip_sgd`` with no host synchronisation.  Unlike FusedAdam the gradient norm is
-    ONE norm over every group, as ``clip_grad_norm_(model.parameters())`` forms it: each group's partial sums fill a slice of one shared
-    array that every group's update reads, so a poisoned or non-finite gradient anywhere skips the update of every group, and
-    ``skipped_steps`` counts steps.  ``state_dict()`` has ``torch.optim.SGD``'s layout (a ``momentum_buffer`` per parameter once the first
-    update has run, none before) and loads into it and back.
+    ``exp_avg`` / ``exp_avg_sq`` are views of the flat state buffers, so ``state_dict()`` has torch.optim.Adam's layout.  Each param group
+    has its own gradient norm and skip counter; ``last_grad_norm`` / ``skipped_steps`` read the first group's.
+    """
+
+    # torch.optim.Adam's remaining hyper-parameters at their inert values: kept in every param_group so that ``state_dict()`` loads into
+    # ``torch.optim.Adam`` (train.py:81,173) and the reverse; step() refuses any other value.
+    _ADAM_INERT = dict(weight_decay=0, amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None,
+                       decoupled_weight_decay=False)
+    _STATE, _STATE_WHAT = ("m", "v"), "Adam moments"
+    _TRACE, _TIMER = "fused_adam_step", "hbm_sumsq_clip_adam"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=0.0, grad_sync=None, shard_optimizer=False):
+        """shard_optimizer (needs a GradSync with world > 1): the gradient is reduce-SCATTERED, every rank runs the clip + Adam update on its
+        1/world slice of the flat buffers only (exp_avg / exp_avg_sq of the other slices stay untouched: `gather_state()` collects them
+        before a checkpoint), and the updated parameters are all-gathered -- half the collective bytes of the all-reduce form and 1/world
+        of the 7 x 4 x P bytes of optimiser traffic.  The global gradient norm is formed from the same 64K-element partial sums in the same
+        order as the all-reduce form, so both forms give bit-identical parameters.  No early (in-backward) ranges in this form."""
+        defaults = dict(lr=lr, betas=betas, eps=eps, max_grad_norm=max_grad_norm, **self._ADAM_INERT)
+        super().__init__(params, defaults, grad_sync, shard_optimizer)
+
+    def _new_group(self, f, first):
+        f["norm"] = self._norm if first else torch.zeros_like(self._norm)
+        for p in f["params"]:
+            v = self._views[p]
+            self.state[p] = dict(step=torch.tensor(0.0), exp_avg=v["m"], exp_avg_sq=v["v"])
+
+    @staticmethod
+    def _check_hyper(group):
+        if group.get("weight_decay", 0) or group.get("amsgrad", False) or group.get("maximize", False):
+            raise L.MvaeError("FusedAdam implements plain Adam (train.py:81): weight_decay / amsgrad / maximize are not supported")
+
+    def _update(self, group, f, sl, g, scale, first):
+        """clip + Adam on f's elements `sl` (g: their gradient), normed over this group's partial sums."""
+        f["step"] += 1
+        b1, b2 = group["betas"]
+        ops.clip_adam(f["p"][sl], g, f["m"][sl], f["v"][sl], f["partial"], scale, group["max_grad_norm"], group["lr"], b1, b2, group["eps"],
+                      f["step"], f["norm"], poison_reset=f["poison"])
+        for p in f["params"]:
+            self.state[p]["step"] += 1
+
+    def _load_hyper(self, group, sg):
+        for k in ("lr", "betas", "eps", "max_grad_norm", "initial_lr"):
+            if k in sg:
+                group[k] = tuple(sg[k]) if k == "betas" else sg[k]
+
+    def _load_state(self, group, f, states):
+        """A FusedAdam or ``torch.optim.Adam`` state dict (train.py:173 ``optimizer_state_dict``): ``step`` / ``exp_avg`` / ``exp_avg_sq``
+        per parameter index."""
+        for p, st in zip(group["params"], states):
+            if st is not None and f is not None and p in self.state:
+                self.state[p]["exp_avg"].copy_(st["exp_avg"]); self.state[p]["exp_avg_sq"].copy_(st["exp_avg_sq"])
+                self.state[p]["step"] = torch.as_tensor(float(st["step"]))
+                f["step"] = int(float(st["step"]))
+
+
+class FusedSGD(_FlatOptimizer):
+    """SGD with momentum (train_distributed.py:73) with the global-norm clip of train_distributed.py:91 fused in: ``mvae_sumsq`` +
+    ``mvae_clip_sgd`` over the flat buffers of ``_FlatOptimizer`` (one momentum buffer per param group).
+
+    Unlike FusedAdam the gradient norm is ONE norm over every group, as ``clip_grad_norm_(model.parameters())`` forms it: every group's update
+    reads the whole partial-sum array, so a poisoned or non-finite gradient anywhere skips the update of every group, and ``skipped_steps``
+    counts steps.  ``state_dict()`` has ``torch.optim.SGD``'s layout (a ``momentum_buffer`` per parameter once the first update has run, none
+    before) and loads into it and back.
     """
 
     # torch.optim.SGD's remaining hyper-parameters at their inert values: kept in every param_group so that ``state_dict()`` has SGD's layout
     _SGD_INERT = dict(maximize=False, foreach=None, differentiable=False, fused=None)
+    _STATE, _STATE_WHAT = ("buf",), "momentum buffers"
+    _TRACE, _TIMER = "fused_sgd_step", "hbm_sumsq_clip_sgd"
 
     def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, max_grad_norm=0.0, grad_sync=None,
                  shard_optimizer=False, *, maximize=False, foreach=None, differentiable=False, fused=None):
@@ -386,61 +448,18 @@ class FusedSGD(torch.optim.Optimizer):
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, max_grad_norm=max_grad_norm,
                         **self._SGD_INERT)
         self._check_hyper(defaults)
-        super().__init__(params, defaults)
+        super().__init__(params, defaults, grad_sync, shard_optimizer)
+
+    def _check_groups(self):
         for group in self.param_groups:
             self._check_hyper(group)
-        self.grad_sync = grad_sync
-        self.shard = bool(shard_optimizer) and grad_sync is not None and grad_sync.active
-        self._moments_stale = False
-        if self.shard:
-            if len(self.param_groups) > 1:
-                raise ValueError("FusedSGD(shard_optimizer=True) takes one param group")
-            if grad_sync.compress is not None:
-                raise ValueError("GradSync(compress=...) applies to the all-reduce form only: the reduce-scatter of shard_optimizer=True sends fp32")
-            grad_sync.allow_early = False
-        world = grad_sync.world if self.shard else 1
-        chunk = 1 << 16
-        groups = [[p for p in g["params"] if p.requires_grad] for g in self.param_groups]
-        devs = {ps[0].device for ps in groups if ps}
-        if len(devs) > 1:
-            raise ValueError("FusedSGD: every param group must live on one device (the groups share one gradient norm)")
-        dev = devs.pop() if devs else torch.device("cpu")
-        sizes = []
-        for ps in groups:
-            n = sum(p.numel() for p in ps)
-            # (n + 1: the poison slot, see FusedAdam)  sharded form: equal slices on whole 64K-element chunks of the partial sums
-            shard_elems = ((n + 1 + world * chunk - 1) // (world * chunk)) * chunk if self.shard else n + 1
-            sizes.append((n, shard_elems, shard_elems * world))
-        # ONE partial-sum array for all groups (group k's chunks at [part_off[k], part_off[k] + nparts_k)) and one norm / skip counter
-        nparts = [(n_alloc + chunk - 1) >> 16 if ps else 0 for ps, (_, _, n_alloc) in zip(groups, sizes)]
-        self._partial = torch.zeros(max(1, sum(nparts)), dtype=torch.float32, device=dev)
-        self._norm = torch.zeros(2, dtype=torch.float32, device=dev)
-        self._flat, self._buf_view = [], {}
-        part_off = 0
-        for ps, (n, shard_elems, n_alloc), npart in zip(groups, sizes, nparts):
-            if not ps:
-                self._flat.append(None)
-                continue
-            pflat = torch.zeros(n_alloc, dtype=torch.float32, device=dev)
-            g = torch.zeros_like(pflat); buf = torch.zeros_like(pflat)
-            off = 0
-            for p in ps:
-                k = p.numel()
-                with torch.no_grad():
-                    pflat[off:off + k].copy_(p.data.reshape(-1))
-                    p.data = pflat[off:off + k].view(p.shape)
-                self._buf_view[p] = buf[off:off + k].view(p.shape)
-                off += k
-            # init: torch's "momentum_buffer is not None" for this group, double-buffered by the parity of `step` (mvae_clip_sgd)
-            self._flat.append(dict(params=ps, p=pflat, g=g, buf=buf, partial=self._partial[part_off:part_off + npart], norm=self._norm,
-                                   init=torch.zeros(2, dtype=torch.int32, device=dev), step=0, n=n, shard_elems=shard_elems,
-                                   poison=g[n:n + 1]))
-            part_off += npart
-            off = 0
-            for p in ps:
-                L.register_grad_sink(p, self, g, off, poison=g[n:n + 1])
-                off += p.numel()
-        L.PARAM_EPOCH[0] += 1
+        if self.shard and len(self.param_groups) > 1:
+            raise ValueError("FusedSGD(shard_optimizer=True) takes one param group")
+
+    def _new_group(self, f, first):
+        f["norm"] = self._norm
+        # init: torch's "momentum_buffer is not None" for this group, double-buffered by the parity of `step` (mvae_clip_sgd)
+        f["init"] = torch.zeros(2, dtype=torch.int32, device=self._norm.device)
 
     @staticmethod
     def _check_hyper(group):
@@ -457,126 +476,47 @@ class FusedSGD(torch.optim.Optimizer):
             if group.get(k, v) != v:
                 raise ValueError(f"FusedSGD: {k}={group[k]!r} is not supported")
 
-    @property
-    def last_grad_norm(self):
-        """Device tensor holding the pre-clip global gradient norm (over every group) of the last step."""
-        return self._norm[:1]
-
-    @property
-    def skipped_steps(self):
-        """Device tensor: how many step() calls were no-ops because the global gradient norm was not finite (poisoned or diverged)."""
-        return self._norm[1:2]
-
-    gather_grads = FusedAdam.gather_grads        # the same flat gradient buffers, the same sinks
-
-    @torch.no_grad()
-    @ops.traced("fused_sgd_step")
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
-        ops.persist_check()            # see FusedAdam.step: a poisoned step is skipped on the device, nothing waits here
-        ops.join_pending()
-        flats = self.gather_grads()
-        sync = self.grad_sync
-        if sync is not None and not self.shard:
-            with ops._Timed("dp_allreduce_exposed" if sync.active else None):
-                for g in flats:
-                    sync.start_rest(g)
-                sync.wait()
-        scale = sync.grad_scale() if sync is not None else 1.0
-        live = [(group, f) for group, f in zip(self.param_groups, self._flat) if f is not None]
-        for group, f in live:
-            self._check_hyper(group)
-            if f["p"].device.type != "cuda":
-                raise L.MvaeError("FusedSGD.step runs on the MI355X only (no CPU fallback)")
-        if self.shard:
-            group, f = live[0]
-            S, r = f["shard_elems"], dist.get_rank(sync.group)
-            with ops._Timed("dp_allreduce_exposed"):
-                gs = sync.reduce_scatter(f["g"], S)
-            sl = slice(r * S, (r + 1) * S)
-            cps = S >> 16
-            with ops._Timed("hbm_sumsq_clip_sgd"):
-                self._partial.zero_()
-                ops.sumsq(gs, self._partial[r * cps:(r + 1) * cps])
-                dist.all_reduce(self._partial, group=sync.group)
-                self._clip_sgd(group, f, f["p"][sl], gs, f["buf"][sl], scale, first=True)
-            with ops._Timed("dp_allreduce_exposed"):
-                sync.all_gather(f["p"], S)
-            self._moments_stale = True
-        else:
-            with ops._Timed("hbm_sumsq_clip_sgd"):
-                for _, f in live:                   # every group's partial sums first: each update below reads all of them
-                    ops.sumsq(f["g"], f["partial"])
-                for k, (group, f) in enumerate(live):
-                    self._clip_sgd(group, f, f["p"], f["g"], f["buf"], scale, first=(k == 0))
-        L.PARAM_EPOCH[0] += 1
-        return loss
-
-    def _clip_sgd(self, group, f, p, g, buf, scale, first):
-        # norm_out for the first group only: the norm is the same for all, and the skip counter counts steps, not groups
-        ops.clip_sgd(p, g, buf, self._partial, scale, group["max_grad_norm"], group["lr"], group["momentum"], group["dampening"],
-                     group["weight_decay"], group["nesterov"], f["init"], f["step"] & 1, norm_out=(self._norm if first else None),
-                     poison_reset=f["poison"])
+    def _update(self, group, f, sl, g, scale, first):
+        """clip + SGD on f's elements `sl` (g: their gradient), normed over every group's partial sums.  norm_out for the first group only:
+        the norm is the same for all, and the skip counter counts steps, not groups."""
+        ops.clip_sgd(f["p"][sl], g, f["buf"][sl], self._partial, scale, group["max_grad_norm"], group["lr"], group["momentum"],
+                     group["dampening"], group["weight_decay"], group["nesterov"], f["init"], f["step"] & 1,
+                     norm_out=(self._norm if first else None), poison_reset=f["poison"])
         f["step"] += 1
 
-    def gather_state(self):
-        """Sharded form: collect every rank's slice of the momentum buffer (a collective; call it on every rank before ``state_dict()``)."""
-        if not self.shard:
-            return
-        for f in self._flat:
-            if f is not None:
-                self.grad_sync.all_gather(f["buf"], f["shard_elems"])
-        self._moments_stale = False
-
-    def _initialised(self, group, f):
-        return f is not None and group["momentum"] != 0 and int(f["init"][f["step"] & 1]) != 0      # reads a device word: synchronises
-
-    def state_dict(self):
+    def _export_state(self):
         """torch.optim.SGD's layout: ``state[i] = {"momentum_buffer": tensor}`` for every parameter once the group has taken an update with
-        momentum, nothing before.  Reads a device word (a checkpoint call).  Sharded form: refused until every rank ran ``gather_state()``."""
-        if self.shard and self._moments_stale:
-            raise L.MvaeError("FusedSGD(shard_optimizer=True).state_dict(): the momentum buffers of the other ranks' slices are stale; call "
-                              "optimizer.gather_state() on every rank first (a collective), then save")
+        momentum, nothing before.  Reads a device word (a checkpoint call)."""
         for group, f in zip(self.param_groups, self._flat):
-            init = self._initialised(group, f)
+            init = f is not None and group["momentum"] != 0 and int(f["init"][f["step"] & 1]) != 0      # reads a device word: synchronises
             for p in group["params"]:
-                if init and p in self._buf_view:
-                    self.state[p]["momentum_buffer"] = self._buf_view[p]
+                if init and p in self._views:
+                    self.state[p]["momentum_buffer"] = self._views[p]["buf"]
                 else:
                     self.state.pop(p, None)
-        return super().state_dict()
 
-    def load_state_dict(self, state_dict):
-        """Accepts a FusedSGD or a ``torch.optim.SGD`` state dict (train_distributed.py:145-151 ``optimizer_state_dict``); hyper-parameters
-        present in the dict override ours.  A group whose entries carry a ``momentum_buffer`` (absent / None ones count as zero) continues
-        from it; a group without any starts as torch does at its first step (``buf = d``)."""
-        sd_groups = state_dict["param_groups"]
-        if len(sd_groups) != len(self.param_groups):
-            raise ValueError("loaded state dict has a different number of parameter groups")
-        for group, sg in zip(self.param_groups, sd_groups):
-            if len(sg["params"]) != len(group["params"]):
-                raise ValueError("loaded state dict contains a parameter group that doesn't match the size of optimizer's group")
-        for group, sg in zip(self.param_groups, sd_groups):
-            for k in ("lr", "momentum", "dampening", "weight_decay", "nesterov", "max_grad_norm", "initial_lr"):
-                if k in sg:
-                    group[k] = sg[k]
-            self._check_hyper(group)
-        idx = 0
-        for group, f in zip(self.param_groups, self._flat):
-            any_buf = False
-            for p in group["params"]:
-                st = state_dict["state"].get(idx)
-                b = st.get("momentum_buffer") if st is not None else None
-                if p in self._buf_view:
-                    if b is not None:
-                        self._buf_view[p].copy_(b); any_buf = True
-                    else:
-                        self._buf_view[p].zero_()
-                idx += 1
-            if f is not None:
-                f["init"].fill_(1 if any_buf else 0)           # both words: whichever parity the next step reads
-            for p in group["params"]:
-                self.state.pop(p, None)
+    def _load_hyper(self, group, sg):
+        for k in ("lr", "momentum", "dampening", "weight_decay", "nesterov", "max_grad_norm", "initial_lr"):
+            if k in sg:
+                group[k] = sg[k]
+        self._check_hyper(group)
+
+    def _load_state(self, group, f, states):
+        """A FusedSGD or ``torch.optim.SGD`` state dict (train_distributed.py:145-151 ``optimizer_state_dict``).  A group whose entries carry
+        a ``momentum_buffer`` (absent / None ones count as zero) continues from it; a group without any starts as torch does at its first
+        step (``buf = d``)."""
+        any_buf = False
+        for p, st in zip(group["params"], states):
+            b = st.get("momentum_buffer") if st is not None else None
+            if p in self._views:
+                if b is not None:
+                    self._views[p]["buf"].copy_(b); any_buf = True
+                else:
+                    self._views[p]["buf"].zero_()
+        if f is not None:
+            f["init"].fill_(1 if any_buf else 0)           # both words: whichever parity the next step reads
+        for p in group["params"]:
+            self.state.pop(p, None)
 
 
 class CosineAnnealingLRWithRestart:

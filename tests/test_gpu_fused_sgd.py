@@ -352,7 +352,7 @@ def _port():
 
 def _two_ranks(out, *extra):
     _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-          "--master-port", str(_port()), os.path.join(ROOT, "tests", "dp_sgd_equiv.py"), "--out", out] + list(extra))
+          "--master-port", str(_port()), os.path.join(ROOT, "tests", "dp_equiv.py"), "--optim", "sgd", "--out", out] + list(extra))
     return json.load(open(out))
 
 
@@ -360,7 +360,7 @@ def test_two_rank_fused_sgd_equals_single_process(tmp_path):
     """One process at 2b against two ranks at b each (gloo, sharing this GPU) with the early all-reduce from backward: losses, parameter sums
     and gradient norms within the f32 tolerance of test_two_rank_data_parallel_equals_single_process."""
     a = os.path.join(str(tmp_path), "one.json")
-    _run([sys.executable, os.path.join(ROOT, "tests", "dp_sgd_equiv.py"), "--out", a, "--b", "32", "--steps", "4"])
+    _run([sys.executable, os.path.join(ROOT, "tests", "dp_equiv.py"), "--optim", "sgd", "--out", a, "--b", "32", "--steps", "4"])
     ra = json.load(open(a))
     rb = _two_ranks(os.path.join(str(tmp_path), "two.json"), "--b", "32", "--steps", "4")
     assert rb["world"] == 2 and rb["early_ranges"] == 4 * 4
