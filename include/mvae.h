@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MVAE_ABI_VERSION 11
+#define MVAE_ABI_VERSION 12
 
 #define MVAE_OK 0
 #define MVAE_ERR_INVALID (-1)     /* bad argument (null pointer, bad size, misaligned leading dimension) */
@@ -417,6 +417,24 @@ int mvae_bce_kl_loss_fwd(int64_t n_recon, const float* recon, const float* targe
 int mvae_bce_kl_loss_bwd(int64_t n_recon, const float* recon, const float* target, int64_t n_latent, const float* mu,
                          const float* logvar, float max_len, const float* grad_out, float* drecon, float* dmu,
                          float* dlogvar, void* stream);
+
+/* The same ELBO from the head's TIME-MAJOR logits [(t*B+b), ldl] fp32 and the int64 index targets idx [B, L] (batch-major): the softmax over
+ * C, the BCE against the implied one-hot (-log p_y - sum_{c != y} log(1 - p_c), each log clamped at -100), the mean over B*L*C times
+ * max_len, and the KL term above -- without the [B, L, C] probabilities, the float one-hot or drecon.  C <= 128 (else MVAE_ERR_UNSUPPORTED);
+ * n_latent = the element count of mu / logvar.
+ *   fwd: loss_out[3] as mvae_bce_kl_loss_fwd (one launch, the same deterministic ticket reduction; ws >= mvae_bce_kl_logits_workspace()
+ *   bytes with the same zero-ticket contract).  pred_out (optional) int64 [B, L]: the arg-max of each row's probabilities, first index on
+ *   ties (recon.argmax(2)).  An index outside [0, C) is never dereferenced: it makes the loss NaN.
+ *   bwd: dl = softmax_bwd(p, drecon) with drecon = g*(max_len/n)*(p - onehot)/max(p(1-p),1e-12), p recomputed from the logits, written in
+ *   dtype to dl [(t*B+b), ldd] (columns C .. ldd-1 are not touched: the caller keeps them zero) and, when dlT != NULL, to dlT [C][ldT]
+ *   (column t*B+b, ldT >= B*L); dmu / dlogvar of the KL term come from the same launch.  g = *grad_out, or 1 when NULL.
+ */
+size_t mvae_bce_kl_logits_workspace(int B, int L);
+int mvae_bce_kl_logits_fwd(int B, int L, int C, const float* logits, int64_t ldl, const int64_t* idx, int64_t n_latent, const float* mu,
+                           const float* logvar, float max_len, float* loss_out, int64_t* pred_out, void* ws, size_t ws_bytes, void* stream);
+int mvae_bce_kl_logits_bwd(int dtype, int B, int L, int C, const float* logits, int64_t ldl, const int64_t* idx, int64_t n_latent,
+                           const float* mu, const float* logvar, float max_len, const float* grad_out, void* dl, int64_t ldd, void* dlT,
+                           int64_t ldT, float* dmu, float* dlogvar, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Device-side input pipeline: the encoded data set lives in HBM as uint8 indices [N, L]; a batch is the

@@ -746,23 +746,9 @@ __device__ __forceinline__ float bce_term(float p, float t) {
 // a fixed order (bitwise reproducible) and writes the three loss values.  `ticket` lives behind the partials in the caller's workspace: zero
 // before the first call, reset to zero by the finishing block (so zero again before the next).  Hand-off across XCDs (per-XCD L2s are not
 // coherent): every handed-off value is a device-scope (sc1) store drained with vmcnt(0) before the ticket, and a device-scope load after it.
-__global__ __launch_bounds__(256) void bce_kl_fused_kernel(long n, const float* recon, const float* target, long m, const float* mu,
-                                                           const float* logvar, float max_len, float* partial, unsigned int* ticket, float* out) {
-  __shared__ float red[4];
-  __shared__ int s_last;
-  float a = 0.f, k = 0.f;
-  const long n4 = ((reinterpret_cast<uintptr_t>(recon) | reinterpret_cast<uintptr_t>(target)) & 15) ? 0 : n / 4;    // 16-byte vector part
-  const float4* r4 = reinterpret_cast<const float4*>(recon);
-  const float4* t4 = reinterpret_cast<const float4*>(target);
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-    const float4 p = r4[i], t = t4[i];
-    a -= (bce_term(p.x, t.x) + bce_term(p.y, t.y)) + (bce_term(p.z, t.z) + bce_term(p.w, t.w));
-  }
-  for (long i = 4 * n4 + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) a -= bce_term(recon[i], target[i]);
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < m; i += (long)gridDim.x * 256) {
-    const float u = mu[i], v = logvar[i];
-    k += 1.f + u - v * v - expf(u);                                             // mu / logvar swapped, as train.py:36-37
-  }
+// a = -(sum of this thread's BCE terms), k = this thread's sum of KL terms; n / m: the element counts of the two means.
+__device__ __forceinline__ void loss_ticket_finish(float a, float k, long n, long m, float max_len, float* partial, unsigned int* ticket,
+                                                   float* out, float* red, int* s_last) {
   a = block_sum_256(a, red);
   k = block_sum_256(k, red);
   if (threadIdx.x == 0) {
@@ -771,10 +757,10 @@ __global__ __launch_bounds__(256) void bce_kl_fused_kernel(long n, const float* 
     __hip_atomic_store(partial + 2 * blockIdx.x, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(partial + 2 * blockIdx.x + 1, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    s_last = (__hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) ? 1 : 0;
+    *s_last = (__hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1) ? 1 : 0;
   }
   __syncthreads();
-  if (!s_last) return;
+  if (!*s_last) return;
   float sa = 0.f, sk = 0.f;
   for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) {                     // device-scope (sc1) loads: past this CU's L1 and this XCD's L2
     sa += __hip_atomic_load(partial + 2 * i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -789,6 +775,23 @@ __global__ __launch_bounds__(256) void bce_kl_fused_kernel(long n, const float* 
     __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next call (stream order)
   }
 }
+__device__ __forceinline__ float kl_term(float u, float v) { return 1.f + u - v * v - expf(u); }    // mu / logvar swapped, as train.py:36-37
+__global__ __launch_bounds__(256) void bce_kl_fused_kernel(long n, const float* recon, const float* target, long m, const float* mu,
+                                                           const float* logvar, float max_len, float* partial, unsigned int* ticket, float* out) {
+  __shared__ float red[4];
+  __shared__ int s_last;
+  float a = 0.f, k = 0.f;
+  const long n4 = ((reinterpret_cast<uintptr_t>(recon) | reinterpret_cast<uintptr_t>(target)) & 15) ? 0 : n / 4;    // 16-byte vector part
+  const float4* r4 = reinterpret_cast<const float4*>(recon);
+  const float4* t4 = reinterpret_cast<const float4*>(target);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    const float4 p = r4[i], t = t4[i];
+    a -= (bce_term(p.x, t.x) + bce_term(p.y, t.y)) + (bce_term(p.z, t.z) + bce_term(p.w, t.w));
+  }
+  for (long i = 4 * n4 + (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) a -= bce_term(recon[i], target[i]);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < m; i += (long)gridDim.x * 256) k += kl_term(mu[i], logvar[i]);
+  loss_ticket_finish(a, k, n, m, max_len, partial, ticket, out, red, &s_last);
+}
 __global__ __launch_bounds__(256) void bce_kl_bwd_kernel(long n, const float* recon, const float* target, long m, const float* mu,
                                                          const float* logvar, float max_len, const float* grad_out, float* drecon,
                                                          float* dmu, float* dlogvar) {
@@ -802,6 +805,156 @@ __global__ __launch_bounds__(256) void bce_kl_bwd_kernel(long n, const float* re
     if (dmu) dmu[i] = sl * (1.f - expf(mu[i]));
     if (dlogvar) dlogvar[i] = sl * (-2.f * logvar[i]);
   }
+}
+
+// ---- the same ELBO straight from the head's TIME-MAJOR logits (row t*B + b, leading dimension ldl) and the int64 index targets
+// idx [B, L]: no [B, L, C] probabilities, no float one-hot, no drecon.  A group of LPR lanes owns a row, column c = j + LPR * kk (kk < 4, so
+// C <= 4 * LPR; consecutive lanes read consecutive floats of the row); EL_RPT rows per group are loaded before the first reduction.  Rows of a
+// block are consecutive (groups g, g + 1 read adjacent rows).  p = softmax(row) (softmax_tb_fwd's e / s); the BCE against onehot(y),
+// y = idx[b*L + t], is -log p_y - sum_{c != y} log(1 - p_c), each log clamped at -100 (bce_term with t = 1 / 0).  An index outside [0, C)
+// matches no column (nothing is ever read through it) and adds a NaN to the sum: the loss turns NaN and the optimiser skips the step.
+constexpr int EL_RPT = 2, EL_CPL = 4;
+template <int LPR>
+__device__ __forceinline__ void elbo_rows_load(int B, int L, int C, const float* __restrict__ logits, long ldl, const int64_t* __restrict__ idx,
+                                               long c0, int g, int j, float (&x)[EL_RPT][EL_CPL], int64_t (&y)[EL_RPT]) {
+  const long rows = (long)B * L;
+#pragma unroll
+  for (int r = 0; r < EL_RPT; ++r) {
+    const long row = c0 + r * (256 / LPR) + g;
+    const bool ok = row < rows;
+    const long t = row / B, b = row - t * B;
+    y[r] = ok ? idx[b * L + t] : 0;
+#pragma unroll
+    for (int kk = 0; kk < EL_CPL; ++kk) {
+      const int c = j + LPR * kk;
+      x[r][kk] = (ok && c < C) ? logits[row * ldl + c] : -INFINITY;
+    }
+  }
+}
+// p[kk] = softmax of the row (0 in the columns >= C and in rows past the end); wave-uniform: every lane of the wave calls it
+template <int LPR>
+__device__ __forceinline__ void elbo_row_softmax(int C, bool ok, int j, const float (&x)[EL_CPL], float (&p)[EL_CPL]) {
+  float mx = x[0];
+#pragma unroll
+  for (int kk = 1; kk < EL_CPL; ++kk) mx = fmaxf(mx, x[kk]);
+  mx = group_max<LPR>(mx);
+  float s = 0.f;
+#pragma unroll
+  for (int kk = 0; kk < EL_CPL; ++kk) { p[kk] = (ok && j + LPR * kk < C) ? expf(x[kk] - mx) : 0.f; s += p[kk]; }
+  s = group_sum<LPR>(s);
+#pragma unroll
+  for (int kk = 0; kk < EL_CPL; ++kk) p[kk] = ok ? p[kk] / s : 0.f;
+}
+template <int LPR>
+__global__ __launch_bounds__(256) void bce_kl_logits_fwd_kernel(int B, int L, int C, const float* __restrict__ logits, long ldl,
+                                                                const int64_t* __restrict__ idx, long m, const float* mu, const float* logvar,
+                                                                float max_len, int64_t* pred, float* partial, unsigned int* ticket, float* out) {
+  constexpr int GPB = 256 / LPR;                                  // row groups per block
+  __shared__ float red[4];
+  __shared__ int s_last;
+  const long rows = (long)B * L;
+  const int g = threadIdx.x / LPR, j = threadIdx.x - g * LPR;
+  float a = 0.f, k = 0.f;
+  for (long c0 = (long)blockIdx.x * GPB * EL_RPT; c0 < rows; c0 += (long)gridDim.x * GPB * EL_RPT) {     // block-uniform trip count
+    float x[EL_RPT][EL_CPL];
+    int64_t y[EL_RPT];
+    elbo_rows_load<LPR>(B, L, C, logits, ldl, idx, c0, g, j, x, y);
+#pragma unroll
+    for (int r = 0; r < EL_RPT; ++r) {
+      const long row = c0 + r * GPB + g;
+      const bool ok = row < rows;
+      float p[EL_CPL];
+      elbo_row_softmax<LPR>(C, ok, j, x[r], p);
+      if (ok) {
+#pragma unroll
+        for (int kk = 0; kk < EL_CPL; ++kk) {
+          const int c = j + LPR * kk;
+          if (c < C) a -= (c == y[r]) ? fmaxf(fast_log(p[kk]), -100.f) : fmaxf(fast_log1m(p[kk]), -100.f);
+        }
+        if (j == 0 && (uint64_t)y[r] >= (uint64_t)C) a += __builtin_nanf("");
+      }
+      if (pred) {                                                 // argmax of the probabilities, first index on ties (recon.argmax(2))
+        float bv = -1.f;
+        int bi = 0;
+#pragma unroll
+        for (int kk = 0; kk < EL_CPL; ++kk)
+          if (j + LPR * kk < C && p[kk] > bv) { bv = p[kk]; bi = j + LPR * kk; }
+#pragma unroll
+        for (int o = LPR / 2; o > 0; o >>= 1) {
+          const float ov = __shfl_xor(bv, o, 64);
+          const int oi = __shfl_xor(bi, o, 64);
+          if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+        }
+        if (ok && j == 0) {
+          const long t = row / B, b = row - t * B;
+          pred[b * L + t] = bi;
+        }
+      }
+    }
+  }
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < m; i += (long)gridDim.x * 256) k += kl_term(mu[i], logvar[i]);
+  loss_ticket_finish(a, k, rows * C, m, max_len, partial, ticket, out, red, &s_last);
+}
+// dl = softmax_bwd(p, drecon) with drecon = g*(max_len/n)*(p - onehot(y))/max(p(1-p), 1e-12) (bce_kl_bwd_kernel) kept in registers:
+// dl[c] = p[c] * (d[c] - sum_c' d[c'] p[c']), written in T to dl [(t*B+b), ldd] (columns C .. ldd-1 untouched) and, when dlT != NULL, to
+// dlT [C][ldT] (column t*B+b).  The KL gradients (dmu, dlogvar) come from the same launch.  One pass, no loop over rows: the grid covers them.
+template <int LPR, typename T>
+__global__ __launch_bounds__(256) void bce_kl_logits_bwd_kernel(int B, int L, int C, const float* __restrict__ logits, long ldl,
+                                                                const int64_t* __restrict__ idx, long m, const float* mu, const float* logvar,
+                                                                float max_len, const float* grad_out, T* __restrict__ dl, long ldd, T* dlT,
+                                                                long ldT, float* dmu, float* dlogvar) {
+  constexpr int GPB = 256 / LPR;
+  const long rows = (long)B * L;
+  const float gs = grad_out ? grad_out[0] : 1.f;
+  const float sr = gs * max_len / (float)(rows * C), sl = gs * (-0.5f) / (float)m;
+  const int g = threadIdx.x / LPR, j = threadIdx.x - g * LPR;
+  const long c0 = (long)blockIdx.x * GPB * EL_RPT;
+  if (c0 < rows) {                                                // block-uniform
+    float x[EL_RPT][EL_CPL];
+    int64_t y[EL_RPT];
+    elbo_rows_load<LPR>(B, L, C, logits, ldl, idx, c0, g, j, x, y);
+#pragma unroll
+    for (int r = 0; r < EL_RPT; ++r) {
+      const long row = c0 + r * GPB + g;
+      const bool ok = row < rows;
+      float p[EL_CPL], d[EL_CPL], sd = 0.f;
+      elbo_row_softmax<LPR>(C, ok, j, x[r], p);
+#pragma unroll
+      for (int kk = 0; kk < EL_CPL; ++kk) {
+        const int c = j + LPR * kk;
+        d[kk] = (ok && c < C) ? sr * (p[kk] - (c == y[r] ? 1.f : 0.f)) / fmaxf((1.f - p[kk]) * p[kk], 1e-12f) : 0.f;
+        sd += d[kk] * p[kk];
+      }
+      sd = group_sum<LPR>(sd);
+      if (ok) {
+#pragma unroll
+        for (int kk = 0; kk < EL_CPL; ++kk) {
+          const int c = j + LPR * kk;
+          if (c < C) {
+            const float v = p[kk] * (d[kk] - sd);
+            TT<T>::st(dl + row * ldd + c, v);
+            if (dlT) TT<T>::st(dlT + (long)c * ldT + row, v);
+          }
+        }
+      }
+    }
+  }
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < m; i += (long)gridDim.x * 256) {
+    dmu[i] = sl * (1.f - expf(mu[i]));
+    dlogvar[i] = sl * (-2.f * logvar[i]);
+  }
+}
+
+// lanes per row of the logits-ELBO kernels: 4 columns per lane, C <= 128
+static int elbo_lpr(int C) { return C <= 16 ? 4 : C <= 32 ? 8 : C <= 64 ? 16 : C <= 128 ? 32 : 0; }
+template <typename T>
+static void elbo_bwd_launch(int lpr, dim3 grid, hipStream_t st, int B, int L, int C, const float* logits, long ldl, const int64_t* idx, long m,
+                            const float* mu, const float* logvar, float max_len, const float* grad_out, void* dl, long ldd, void* dlT, long ldT,
+                            float* dmu, float* dlogvar) {
+#define ELBO_BWD(LPR) hipLaunchKernelGGL((bce_kl_logits_bwd_kernel<LPR, T>), grid, dim3(256), 0, st, B, L, C, logits, ldl, idx, m, mu, logvar, \
+                                         max_len, grad_out, (T*)dl, ldd, (T*)dlT, ldT, dmu, dlogvar)
+  if (lpr == 4) ELBO_BWD(4); else if (lpr == 8) ELBO_BWD(8); else if (lpr == 16) ELBO_BWD(16); else ELBO_BWD(32);
+#undef ELBO_BWD
 }
 
 // ------------------------------------------------------------------------------------------- autoregressive sampling step (mosesvae.py:236-253)
@@ -1484,6 +1637,49 @@ int mvae_bce_kl_loss_bwd(int64_t n, const float* recon, const float* target, int
   if (!recon || !target || !mu || !logvar || !drecon || n < 1 || m < 1) return MVAE_ERR_INVALID;
   hipLaunchKernelGGL(bce_kl_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (long)n, recon, target, (long)m, mu, logvar, max_len,
                      grad_out, drecon, dmu, dlogvar);
+  MVAE_CHECK_HIP(hipGetLastError());
+  return MVAE_OK;
+}
+size_t mvae_bce_kl_logits_workspace(int, int) { return (size_t)LOSS_BLOCKS * 2 * sizeof(float) + 16; }
+int mvae_bce_kl_logits_fwd(int B, int L, int C, const float* logits, int64_t ldl, const int64_t* idx, int64_t m, const float* mu,
+                           const float* logvar, float max_len, float* loss_out, int64_t* pred_out, void* ws, size_t ws_bytes, void* stream) {
+  if (!logits || !idx || !mu || !logvar || !loss_out || B < 1 || L < 1 || C < 1 || ldl < C || m < 1) return MVAE_ERR_INVALID;
+  const int lpr = elbo_lpr(C);
+  if (!lpr) return MVAE_ERR_UNSUPPORTED;
+  if (!ws || ws_bytes < mvae_bce_kl_logits_workspace(B, L) || (reinterpret_cast<uintptr_t>(ws) & 3)) return MVAE_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const long rows = (long)B * L, per_block = (long)(256 / lpr) * EL_RPT;
+  long want = (rows + per_block - 1) / per_block;                // one pass over the rows where that fits; the cap as in mvae_bce_kl_loss_fwd
+  const int blocks = (int)(want > 1024 ? 1024 : want);
+  float* partial = reinterpret_cast<float*>(ws);
+  unsigned int* ticket = reinterpret_cast<unsigned int*>(partial + 2 * LOSS_BLOCKS);
+#define ELBO_FWD(LPR) hipLaunchKernelGGL((bce_kl_logits_fwd_kernel<LPR>), dim3(blocks), dim3(256), 0, st, B, L, C, logits, (long)ldl, idx, (long)m, \
+                                         mu, logvar, max_len, pred_out, partial, ticket, loss_out)
+  if (lpr == 4) ELBO_FWD(4); else if (lpr == 8) ELBO_FWD(8); else if (lpr == 16) ELBO_FWD(16); else ELBO_FWD(32);
+#undef ELBO_FWD
+  MVAE_CHECK_HIP(hipGetLastError());
+  return MVAE_OK;
+}
+int mvae_bce_kl_logits_bwd(int dtype, int B, int L, int C, const float* logits, int64_t ldl, const int64_t* idx, int64_t m, const float* mu,
+                           const float* logvar, float max_len, const float* grad_out, void* dl, int64_t ldd, void* dlT, int64_t ldT, float* dmu,
+                           float* dlogvar, void* stream) {
+  if (!logits || !idx || !mu || !logvar || !dl || !dmu || !dlogvar || B < 1 || L < 1 || C < 1 || ldl < C || ldd < C || m < 1) return MVAE_ERR_INVALID;
+  const long rows = (long)B * L;
+  if (dlT && ldT < rows) return MVAE_ERR_INVALID;
+  if (dtype != MVAE_F32 && dtype != MVAE_BF16) return MVAE_ERR_INVALID;
+  const int lpr = elbo_lpr(C);
+  if (!lpr) return MVAE_ERR_UNSUPPORTED;
+  const long per_block = (long)(256 / lpr) * EL_RPT;
+  long nb = (rows + per_block - 1) / per_block;
+  const long nm = (m + 255) / 256;                               // the KL gradients: grid-stride, but never fewer blocks than 2048 of them need
+  if (nb < nm && nb < 2048) nb = nm < 2048 ? nm : 2048;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MVAE_F32)
+    elbo_bwd_launch<float>(lpr, dim3((unsigned)nb), st, B, L, C, logits, (long)ldl, idx, (long)m, mu, logvar, max_len, grad_out, dl, (long)ldd,
+                           dlT, (long)ldT, dmu, dlogvar);
+  else
+    elbo_bwd_launch<bf16_t>(lpr, dim3((unsigned)nb), st, B, L, C, logits, (long)ldl, idx, (long)m, mu, logvar, max_len, grad_out, dl, (long)ldd,
+                            dlT, (long)ldT, dmu, dlogvar);
   MVAE_CHECK_HIP(hipGetLastError());
   return MVAE_OK;
 }

@@ -46,6 +46,14 @@ def make_loss_function(max_len):
     return loss_function
 
 
+def decoder_elbo(decoder, z, idx, mu, logvar, max_len):
+    """The ELBO of train.py:31-38 for a separately built MolDecoder: decode `z` and score it against the int64 index targets idx [B, L]
+    (the one-hot is implied) in one fused HIP pass over the head's logits -- ``bce_kl_loss(decoder(z), one_hot(idx), mu, logvar, max_len)``
+    without the [B, L, C] reconstruction.  Returns the scalar loss (gradients reach z, mu and logvar); ``decoder.elbo_parts`` holds
+    (total, xent, kl) on device."""
+    return decoder.elbo(z, idx, mu, logvar, max_len=max_len)
+
+
 class _LambdaFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mod, x, eps, wm, bm, wv, bv):

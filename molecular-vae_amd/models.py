@@ -224,6 +224,13 @@ def _require_cuda(dev, what):
         raise L.MvaeError(f"{what} runs on the MI355X only (no CPU fallback); move the module and inputs to cuda")
 
 
+def _check_index_batch(idx, B, Lq, what):
+    """idx: the int64 [B, L] index targets of an ELBO (a wrong shape or dtype is refused before anything runs)."""
+    if not torch.is_tensor(idx) or idx.dtype != torch.int64 or idx.dim() != 2 or (B is not None and idx.shape[0] != B) or idx.shape[1] != Lq:
+        got = f"{idx.dtype} {tuple(idx.shape)}" if torch.is_tensor(idx) else type(idx).__name__
+        raise L.MvaeError(f"{what}: the targets must be an int64 [B{'' if B is None else '=' + str(B)}, L={Lq}] index tensor, got {got}")
+
+
 def _grad_buffer(params, dev):
     """Zeroed flat fp32 buffer for the gradients of `params` (in order): the optimiser's own flat gradient range when the
     parameters are registered with a FusedAdam and no gradient is pending accumulation, else a fresh tensor."""
@@ -717,6 +724,7 @@ class MolDecoder(nn.Module, _SavedState):
         self.__dict__["_z_from_peer"] = False  # True only inside MolecularVAE.forward: z is that encoder's output
         self.__dict__["_side"] = None
         self.overlap_weight_grads = True       # run the weight-gradient GEMMs on a side stream under the encoder's backward
+        self.__dict__["elbo_parts"] = None     # (total, xent, kl) of the last `elbo`, on device
 
     apply = _apply_and_mark
 
@@ -727,6 +735,26 @@ class MolDecoder(nn.Module, _SavedState):
         # under no_grad (evaluation, train.py:120-153 / sampling from a latent, train_sample.py:32) nothing is saved for backward
         infer = not torch.is_grad_enabled()
         return _DecoderFn.apply(self, x, infer, *list(self.parameters()))
+
+    def elbo(self, z, idx, mu, logvar, max_len=None, pred_out=None):
+        """Decode `z` and return the ELBO of train.py:31-38 against the int64 index targets idx [B, L] (the one-hot is implied), as a scalar
+        that backpropagates into z, mu and logvar -- without the [B, L, C] reconstruction.  max_len defaults to L.  The (total, xent, kl)
+        parts stay on device in `self.elbo_parts`.  pred_out (optional, int64 [B, L], cuda): receives recon.argmax(2).  Under no_grad
+        nothing is saved for backward."""
+        B, Lq = z.shape[0], self.repeat_vector.rep
+        _check_index_batch(idx, B, Lq, "MolDecoder.elbo")
+        if mu.shape != logvar.shape or mu.dim() != 2 or mu.shape[0] != B:
+            raise L.MvaeError(f"MolDecoder.elbo: mu / logvar must both be [B={B}, latent], got {tuple(mu.shape)} / {tuple(logvar.shape)}")
+        _require_cuda(z.device, "MolDecoder.elbo")
+        for what, t in (("idx", idx), ("mu", mu), ("logvar", logvar), ("pred_out", pred_out)):
+            if t is not None and t.device != z.device:
+                raise L.MvaeError(f"MolDecoder.elbo: {what} is on {t.device}, z on {z.device}")
+        if pred_out is not None:
+            if pred_out.dtype != torch.int64 or tuple(pred_out.shape) != (B, Lq) or not pred_out.is_contiguous():
+                raise L.MvaeError(f"MolDecoder.elbo: pred_out must be a contiguous int64 [{B}, {Lq}] tensor")
+        infer = not torch.is_grad_enabled()
+        return _DecoderElboFn.apply(self, z, idx.contiguous(), mu, logvar, float(Lq if max_len is None else max_len), infer, pred_out,
+                                    *list(self.parameters()))
 
     def _pack(self, dev):
         params = list(self.parameters())
@@ -778,203 +806,263 @@ class MolDecoder(nn.Module, _SavedState):
         self.__dict__["_pack_list"] = pl
 
 
+def _decoder_fwd_logits(ctx, mod, z, infer, params):
+    """The decoder's forward up to the output head: returns (z as fp32, logits) with logits the time-major [L*B, C] fp32 head output
+    (row t*B + b) in the forward's saved-state workspace.  Records on ctx what _decoder_bwd_tail reads (a forward under no_grad -- `infer` --
+    saves nothing: its generation -1 makes a backward refuse)."""
+    dev = z.device
+    _require_cuda(dev, "MolDecoder")
+    z = z.contiguous().float()
+    g, dt = mod.gru, mod.compute_dtype
+    H, NL, o = g.hidden_size, g.num_layers, g.input_size
+    B = z.shape[0]
+    Lq = mod.repeat_vector.rep
+    om = mod.decoded_mean.module[0]
+    Cv = om.out_features
+    G4, TB = 4 * H, Lq * B
+    P = mod._pack(dev)
+    slot, ws = mod._next_saved_ws()
+    f32 = torch.float32
+    li_mod = mod.latent_input[0]
+    # K6: latent projection + SELU; layer-0 input is time-invariant -> its gate pre-activation is computed ONCE
+    li = ws.get("li", (B, o), f32, dev)
+    ops.gemm_nt(z, li_mod.weight, li, B, o, o, bias=li_mod.bias, act=L.ACT_SELU)
+    gx0 = ws.get("gx0", (B, G4), f32, dev)
+    ops.gemm_nt(li, g.weight_ih_l0, gx0, B, G4, o, bias=P["bias"][0])
+    # K7: 4-layer LSTM wavefront
+    ldh = H + _LDPAD
+    hs = [ws.get(f"hs{l}", (Lq, B, ldh), dt, dev) for l in range(NL)]
+    cs = [None if infer else ws.get(f"cs{l}", (Lq, B, H), dt, dev) for l in range(NL)]
+    gates = [None if infer else ws.get(f"gates{l}", (Lq, B, G4), dt, dev) for l in range(NL)]
+    cstate = [ws.get(f"cstate{l}", (2, B, H), f32, dev) for l in range(NL)]
+    ops.rnn_fwd(L.CELL_LSTM, dt, Lq, B, H, gx0, 0, P["Wih"], [P["ldw"]] * NL, P["Whh"], [P["ldw"]] * NL, [None] + P["bias"][1:],
+                hs, ldh, cs, gates, cstate, tag="dec_lstm_fwd", poison=(None if infer else L.grad_poison(params)))
+    # K8: output head (the softmax and the loss are the caller's)
+    logits = ws.get("logits", (TB, Cv), f32, dev)
+    ops.gemm_nt(hs[-1].view(TB, ldh), P["Wout"], logits, TB, Cv, H, bias=om.bias)
+    ctx.mod, ctx.slot, ctx.gen, ctx.z = mod, slot, (-1 if infer else ws.generation), z     # a forward-only pass saved nothing: backward refuses
+    ctx.from_peer = bool(mod.__dict__.get("_z_from_peer", False))
+    return z, logits
+
+
+def _decoder_bwd_tail(ctx, fill_dl):
+    """The decoder's backward from the logit gradients on: `fill_dl(ws, dl, dlT)` writes dlogits into the head's dl buffer [L*B, ldd] (dtype
+    of the module, pad columns zero) and, for fp32 modules, its transpose dlT [C, ldT]; everything after that -- the recurrent backward, the
+    weight-gradient parts (forked to the side stream, data-parallel early ranges), the latent projection -- is shared by every head.
+    Returns (dz, the parameter gradients: a tuple for autograd, all None when they were handed over by assignment)."""
+    mod, z = ctx.mod, ctx.z
+    ws = mod._saved_ws(ctx.slot, ctx.gen, "MolDecoder")
+    dev = z.device
+    f32 = torch.float32
+    g, dt = mod.gru, mod.compute_dtype
+    H, NL, o = g.hidden_size, g.num_layers, g.input_size
+    B = z.shape[0]
+    Lq = mod.repeat_vector.rep
+    om = mod.decoded_mean.module[0]
+    Cv = om.out_features
+    G4, TB = 4 * H, Lq * B
+    Cp = _pad(Cv, 8)
+    Bp = _pad(B, 4)
+    P = mod._packed
+    params = list(mod.parameters())
+    names = [n for n, _ in mod.named_parameters()]
+    gflat, sink = _grad_buffer(params, dev)
+    grads, off, offs = {}, 0, {}
+    for n, p in zip(names, params):
+        grads[n] = gflat[off:off + p.numel()].view(p.shape)
+        offs[n] = off
+        off += p.numel()
+    W = lambda name, shape, d=f32: ws.get(name, shape, d, dev)
+    ldh, ldg = H + _LDPAD, G4 + _LDPAD
+    hs = [W(f"hs{l}", (Lq, B, ldh), dt) for l in range(NL)]
+    cs = [W(f"cs{l}", (Lq, B, H), dt) for l in range(NL)]
+    gates = [W(f"gates{l}", (Lq, B, G4), dt) for l in range(NL)]
+    # K8 backward
+    # bf16 (and a hidden size the LDS-direct loop serves): the top LSTM cell contracts dl . W_out itself (no [T, B, H] fp32 dy tensor)
+    # The weights-resident dataflow backward (rnn_persist_bwd.hip: the per-rank shape of the 8-GPU configuration) wants dy as a tensor: one
+    # [T*B, H] GEMM in front of it instead of the fused segment.
+    fuse_ok = dt == torch.bfloat16 and (4 * H) % 64 == 0
+    use_pb = fuse_ok and ops.rnn_bwd_persist_wanted(L.CELL_LSTM, dt, NL, B, H, ldg, dev)
+    fuse_dy = fuse_ok and not use_pb
+    ldl = _dyk(Cv) if fuse_ok else Cp           # pad columns are allocated zero and never written
+    dl = W("dl", (TB + 8, ldl), dt)[:TB]        # +8 rows: the TN tile reads 256-byte row segments past the last row
+    dlT = None
+    if dt != torch.bfloat16:
+        ldT = _pad(TB, 8) + 8
+        dlT = W("dlT", (Cv, ldT), dt)
+    fill_dl(ws, dl, dlT)
+    dy = None
+    if not fuse_dy:
+        dy = W("dy", (TB, H))
+        ops.gemm_nt(dl, P["WoutT"], dy, TB, H, ldl if fuse_ok else Cp)
+    # K7 backward
+    dG = [W(f"dG{l}", (Lq, B, ldg), dt) for l in range(NL)]
+    dstate = [W(f"dstate{l}", (2, B, H)) for l in range(NL)]
+    ops.rnn_bwd(L.CELL_LSTM, dt, Lq, B, H, P["WhhT"], [P["ldwT"]] * NL, P["WihT"], [P["ldwT"]] * NL, dy, H, hs, ldh, cs, gates,
+                dG, dstate, ldg=ldg, tag="dec_lstm_bwd", dy_a=(dl if fuse_dy else None), dy_w=(P["WoutT"] if fuse_dy else None),
+                dy_k=(_dyk(Cv) if fuse_dy else 0), poison=L.grad_poison(params))
+
+    # Everything that only produces parameter gradients (nothing on the path to dz) -- the output head + the LSTM weights -- is cut into
+    # PARTS, each a set of layers whose gradients are one contiguous range of the flat gradient buffer, produced (and, in DP, all-reduced)
+    # in reverse layer order.  Default: two parts (head + the upper layers | the two lowest layers: 256 / 192 tiles of the grouped GEMM, one
+    # round of workgroups each).  Data parallel (an optimiser with a GradSync that takes early ranges): ONE PART PER LAYER, so that layer
+    # 3's range is on the links while layers 2, 1, 0 are still being contracted and the encoder's backward runs -- four early ranges
+    # instead of two (at the per-rank batch of a DP job the 128-tile launches cost little: K = T * b is short).
+    gsync = getattr(sink[0], "grad_sync", None) if sink is not None else None
+    dp_early = gsync is not None and gsync.active and gsync.allow_early
+    # two parts (upper layers + head, lower layers) where the peer releases them at two points of its backward; ONE part at the small per-GPU
+    # batches whose GEMMs are released at once on a capped grid (round 5, b = 128: 5.50 -> 5.37 ms per step with 160 workgroups -- the gap
+    # between two grouped launches, ~0.1 ms of bias / column-sum launches, closes, and the main stream keeps 96 compute units)
+    nlow = min(int(L.knob("MVAE_DEFER_LAYERS", "0" if TB <= int(L.knob("MVAE_WGRAD_LATE_TB", 32768)) else "2")), NL - 1)
+    per_layer = L.knob("MVAE_WGRAD_PER_LAYER", "1" if dp_early else "0") == "1"
+    if per_layer:
+        parts = [[l] for l in range(NL - 1, -1, -1)]
+    else:
+        parts = [list(range(nlow, NL))] + ([list(range(nlow))] if nlow >= 1 else [])
+    first_name = lambda l: f"gru.weight_ih_l{l}" if l >= 1 else "gru.weight_hh_l0"
+
+    wg_cap = [0]             # workgroup cap of the grouped weight-gradient launches (0: one per tile), see the fork below
+
+    def weight_grads(k):
+        """part k of `parts` (None: everything at once, on the current stream)."""
+        with ops._Timed("dec_lstm_wgrad" if (k is None or k == 0) else "dec_lstm_wgrad_deferred"):
+            if k is None or k == 0:
+                if dt == torch.bfloat16:
+                    ops.gemm_tn(dl, hs[-1].view(TB, ldh), grads["decoded_mean.module.0.weight"], Cv, H, TB, lda=ldl, ldb=ldh)
+                    dbp = W("dbout_p", (Cp,))
+                    ops.colsum_t(dl, TB, Cp, dbp, ldx=ldl)
+                    grads["decoded_mean.module.0.bias"].copy_(dbp[:Cv])
+                else:
+                    hsT = W("wg_hsT_out", (H, ldT), dt)
+                    ops.cast_transpose(hs[-1].view(TB, ldh), TB, H, dstT=hsT, lds=ldh)
+                    ops.gemm_nt(dlT, hsT, grads["decoded_mean.module.0.weight"], Cv, H, TB, lda=ldT, ldb=ldT)
+                    ops.rowsum(dlT, Cv, TB, grads["decoded_mean.module.0.bias"])
+            layers = range(NL) if k is None else parts[k]
+            caps_big = [int(c) for c in L.knob("MVAE_WGRAD_CAPS", WGRAD_CAPS_BIG).split(":")]       # per part, the two-part schedule of large batches
+            mw = wg_cap[0] if (wg_cap[0] or k is None) else caps_big[min(k, len(caps_big) - 1)]
+            _lstm_weight_grads(ws, grads, "gru", dt, dev, NL, Lq, B, H, dG, ldg, hs, ldh, layers=layers, max_workgroups=mw)
+            if k is not None and dp_early:
+                # What this part produced is final on this stream: all-reduce it now -- [first parameter of its lowest layer, start of
+                # the previous part) (part 0: to the end of our range, i.e. with the head).  weight_ih_l0 / latent_input, produced on
+                # the main stream later, go with the rest in step().  Fork path only: there the gradients are handed over by ASSIGNMENT
+                # (p.grad = view of the flat buffer), so what step() sees is the reduced buffer; through autograd's AccumulateGrad a
+                # clone could hide it (FusedAdam.gather_grads)
+                lo = sink[2] + offs[first_name(min(parts[k]))]
+                hi = sink[3] if k == 0 else sink[2] + offs[first_name(min(parts[k - 1]))]
+                gsync.start_early(sink[1], lo, hi)
+
+    # Fork: the weight-gradient GEMMs are throughput-bound and independent of dz, while the encoder's backward that follows is a
+    # latency-bound chain of small launches -> run them concurrently.  Only when our MolecularVAE peer will join the side stream
+    # (its backward ends with ForkState.join) and no gradient accumulation is pending (p.grad is assigned, never added to).
+    # The later parts are parked (ops.ForkState): the peer releases them right before its row-resident LSTM backward,
+    # whose 128 workgroups leave half the CUs idle -- the GEMMs fill them instead of running alone later.
+    peer = mod.__dict__["_peer"]() if mod.__dict__["_peer"] is not None else None
+    fork = bool(mod.overlap_weight_grads and peer is not None and ctx.from_peer and ctx.needs_input_grad[1] and
+                all(p.grad is None for p in params))
+    if fork:
+        side = mod._side_stream(dev)
+        gflat.record_stream(side)
+        fstate = peer.__dict__["_fork"]                               # the model's own fork state (ops.ForkState), kept by the peer
+        # first half of the parts: released by the peer after its head section; the rest next to its row-resident LSTM backward.  At small
+        # per-GPU batches (K = T * B short: a group of GEMMs is a few hundred microseconds) EVERYTHING waits for that second point: released
+        # earlier, the chip-filling 256 x 256 tiles only starve the peer's conv / dense backward (a 5 us bias column sum sat 308 us behind
+        # them at b = 128), while next to the 32-workgroup row-resident kernel (0.7 ms) they are hidden completely.
+        late_all = TB <= int(L.knob("MVAE_WGRAD_LATE_TB", 32768))      # round 3: b = 128 8.38 -> 8.22 ms / step, B = 256 +0.13; with the capped grid below B = 256 gains too (9.84 -> 9.72)
+        # ... or, at those batches, released AT ONCE but with a capped grid (mvae_gemm_tn_grouped_capped: `cap` workgroups looping over the
+        # tiles): the compute units left over serve the peer's dependent small launches without queueing behind chip-filling tiles
+        cap = int(L.knob("MVAE_WGRAD_CAP", WGRAD_CAP)) if late_all else 0
+        if cap > 0:
+            wg_cap[0] = cap
+            for k in range(len(parts)):
+                fstate.park(side, (lambda kk=k: weight_grads(kk)), -1)
+            fstate.run_deferred(stage=-1)
+        else:
+            for k in range(len(parts)):
+                fstate.park(side, (lambda kk=k: weight_grads(kk)), 1 if (late_all or 2 * k >= len(parts)) else 0)
+    else:
+        weight_grads(None)
+    # layer-0 input is time-invariant: its gradient is the time sum of dG[0]
+    dgx0 = W("dgx0", (B, ldg))           # pad columns of dG are zero, so the padded time sum is too
+    ops.timesum(dG[0], Lq, B, ldg, dgx0)
+    li = W("li", (B, o))
+    ops.gemm_tn(dgx0, li, grads["gru.weight_ih_l0"], G4, o, B, lda=ldg)
+    dli = W("dli", (B, o))
+    ops.gemm_nt(dgx0, P["Wih0T"], dli, B, o, G4)
+    # K6 backward
+    ops.selu_bwd(dli, li)
+    ops.gemm_tn_f32_colsum(dli, z, grads["latent_input.0.weight"], grads["latent_input.0.bias"], o, o, B)
+    dz = torch.empty(B, o, dtype=f32, device=dev)
+    ops.gemm_nt(dli, P["WliT"], dz, B, o, o, ldb=P["WliT"].stride(0))
+    if fork:
+        # gradients are still being written on the side stream: hand them over by assignment (autograd must not touch them)
+        for n, p in zip(names, params):
+            p.grad = grads[n]
+        return dz, (None,) * len(names)
+    return dz, tuple(grads[n] for n in names)
+
+
 class _DecoderFn(torch.autograd.Function):
     @staticmethod
     @ops.traced("molvae_decoder_fwd")
     def forward(ctx, mod, z, infer, *params):
-        dev = z.device
-        _require_cuda(dev, "MolDecoder")
-        z = z.contiguous().float()
-        g, dt = mod.gru, mod.compute_dtype
-        H, NL, o = g.hidden_size, g.num_layers, g.input_size
-        B = z.shape[0]
-        Lq = mod.repeat_vector.rep
-        om = mod.decoded_mean.module[0]
-        Cv = om.out_features
-        G4, TB = 4 * H, Lq * B
-        P = mod._pack(dev)
-        slot, ws = mod._next_saved_ws()
-        f32 = torch.float32
-        li_mod = mod.latent_input[0]
-        # K6: latent projection + SELU; layer-0 input is time-invariant -> its gate pre-activation is computed ONCE
-        li = ws.get("li", (B, o), f32, dev)
-        ops.gemm_nt(z, li_mod.weight, li, B, o, o, bias=li_mod.bias, act=L.ACT_SELU)
-        gx0 = ws.get("gx0", (B, G4), f32, dev)
-        ops.gemm_nt(li, g.weight_ih_l0, gx0, B, G4, o, bias=P["bias"][0])
-        # K7: 4-layer LSTM wavefront
-        ldh = H + _LDPAD
-        hs = [ws.get(f"hs{l}", (Lq, B, ldh), dt, dev) for l in range(NL)]
-        cs = [None if infer else ws.get(f"cs{l}", (Lq, B, H), dt, dev) for l in range(NL)]
-        gates = [None if infer else ws.get(f"gates{l}", (Lq, B, G4), dt, dev) for l in range(NL)]
-        cstate = [ws.get(f"cstate{l}", (2, B, H), f32, dev) for l in range(NL)]
-        ops.rnn_fwd(L.CELL_LSTM, dt, Lq, B, H, gx0, 0, P["Wih"], [P["ldw"]] * NL, P["Whh"], [P["ldw"]] * NL, [None] + P["bias"][1:],
-                    hs, ldh, cs, gates, cstate, tag="dec_lstm_fwd", poison=(None if infer else L.grad_poison(params)))
-        # K8: output head + softmax over the class axis
-        logits = ws.get("logits", (TB, Cv), f32, dev)
-        ops.gemm_nt(hs[-1].view(TB, ldh), P["Wout"], logits, TB, Cv, H, bias=om.bias)
-        recon = torch.empty(B, Lq, Cv, dtype=f32, device=dev)
+        z, logits = _decoder_fwd_logits(ctx, mod, z, infer, params)
+        B, Lq, Cv = z.shape[0], mod.repeat_vector.rep, mod.decoded_mean.module[0].out_features
+        # K8: softmax over the class axis
+        recon = torch.empty(B, Lq, Cv, dtype=torch.float32, device=z.device)
         with ops._Timed("hbm_softmax_fwd"):
             ops.softmax_tb_fwd(logits, Cv, recon, B, Lq, Cv)
-        ctx.mod, ctx.slot, ctx.gen, ctx.z = mod, slot, (-1 if infer else ws.generation), z     # a forward-only pass saved nothing: backward refuses
-        ctx.from_peer = bool(mod.__dict__.get("_z_from_peer", False))
         ctx.save_for_backward(recon)
         return recon
 
     @staticmethod
     @ops.traced("molvae_decoder_bwd")
     def backward(ctx, drecon):
-        mod, z = ctx.mod, ctx.z
         (recon,) = ctx.saved_tensors
-        ws = mod._saved_ws(ctx.slot, ctx.gen, "MolDecoder")
-        dev = z.device
-        f32 = torch.float32
-        g, dt = mod.gru, mod.compute_dtype
-        H, NL, o = g.hidden_size, g.num_layers, g.input_size
-        B = z.shape[0]
-        Lq = mod.repeat_vector.rep
-        om = mod.decoded_mean.module[0]
-        Cv = om.out_features
-        G4, TB = 4 * H, Lq * B
-        Cp = _pad(Cv, 8)
-        Bp = _pad(B, 4)
-        P = mod._packed
-        params = list(mod.parameters())
-        names = [n for n, _ in mod.named_parameters()]
-        gflat, sink = _grad_buffer(params, dev)
-        grads, off, offs = {}, 0, {}
-        for n, p in zip(names, params):
-            grads[n] = gflat[off:off + p.numel()].view(p.shape)
-            offs[n] = off
-            off += p.numel()
         drecon = drecon.contiguous().float()
-        W = lambda name, shape, d=f32: ws.get(name, shape, d, dev)
-        ldh, ldg = H + _LDPAD, G4 + _LDPAD
-        hs = [W(f"hs{l}", (Lq, B, ldh), dt) for l in range(NL)]
-        cs = [W(f"cs{l}", (Lq, B, H), dt) for l in range(NL)]
-        gates = [W(f"gates{l}", (Lq, B, G4), dt) for l in range(NL)]
-        # K8 backward
-        # bf16 (and a hidden size the LDS-direct loop serves): the top LSTM cell contracts dl . W_out itself (no [T, B, H] fp32 dy tensor)
-        # The weights-resident dataflow backward (rnn_persist_bwd.hip: the per-rank shape of the 8-GPU configuration) wants dy as a tensor: one
-        # [T*B, H] GEMM in front of it instead of the fused segment.
-        fuse_ok = dt == torch.bfloat16 and (4 * H) % 64 == 0
-        use_pb = fuse_ok and ops.rnn_bwd_persist_wanted(L.CELL_LSTM, dt, NL, B, H, ldg, dev)
-        fuse_dy = fuse_ok and not use_pb
-        ldl = _dyk(Cv) if fuse_ok else Cp           # pad columns are allocated zero and never written
-        dl = W("dl", (TB + 8, ldl), dt)[:TB]        # +8 rows: the TN tile reads 256-byte row segments past the last row
-        dlT = None
-        if dt != torch.bfloat16:
-            ldT = _pad(TB, 8) + 8
-            dlT = W("dlT", (Cv, ldT), dt)
-        with ops._Timed("hbm_softmax_bwd"):
-            ops.softmax_tb_bwd(recon, drecon, dl, dlT, B, Lq, Cv)
-        dy = None
-        if not fuse_dy:
-            dy = W("dy", (TB, H))
-            ops.gemm_nt(dl, P["WoutT"], dy, TB, H, ldl if fuse_ok else Cp)
-        # K7 backward
-        dG = [W(f"dG{l}", (Lq, B, ldg), dt) for l in range(NL)]
-        dstate = [W(f"dstate{l}", (2, B, H)) for l in range(NL)]
-        ops.rnn_bwd(L.CELL_LSTM, dt, Lq, B, H, P["WhhT"], [P["ldwT"]] * NL, P["WihT"], [P["ldwT"]] * NL, dy, H, hs, ldh, cs, gates,
-                    dG, dstate, ldg=ldg, tag="dec_lstm_bwd", dy_a=(dl if fuse_dy else None), dy_w=(P["WoutT"] if fuse_dy else None),
-                    dy_k=(_dyk(Cv) if fuse_dy else 0), poison=L.grad_poison(params))
+        B, Lq, Cv = recon.shape
 
-        # Everything that only produces parameter gradients (nothing on the path to dz) -- the output head + the LSTM weights -- is cut into
-        # PARTS, each a set of layers whose gradients are one contiguous range of the flat gradient buffer, produced (and, in DP, all-reduced)
-        # in reverse layer order.  Default: two parts (head + the upper layers | the two lowest layers: 256 / 192 tiles of the grouped GEMM, one
-        # round of workgroups each).  Data parallel (an optimiser with a GradSync that takes early ranges): ONE PART PER LAYER, so that layer
-        # 3's range is on the links while layers 2, 1, 0 are still being contracted and the encoder's backward runs -- four early ranges
-        # instead of two (at the per-rank batch of a DP job the 128-tile launches cost little: K = T * b is short).
-        gsync = getattr(sink[0], "grad_sync", None) if sink is not None else None
-        dp_early = gsync is not None and gsync.active and gsync.allow_early
-        # two parts (upper layers + head, lower layers) where the peer releases them at two points of its backward; ONE part at the small per-GPU
-        # batches whose GEMMs are released at once on a capped grid (round 5, b = 128: 5.50 -> 5.37 ms per step with 160 workgroups -- the gap
-        # between two grouped launches, ~0.1 ms of bias / column-sum launches, closes, and the main stream keeps 96 compute units)
-        nlow = min(int(L.knob("MVAE_DEFER_LAYERS", "0" if TB <= int(L.knob("MVAE_WGRAD_LATE_TB", 32768)) else "2")), NL - 1)
-        per_layer = L.knob("MVAE_WGRAD_PER_LAYER", "1" if dp_early else "0") == "1"
-        if per_layer:
-            parts = [[l] for l in range(NL - 1, -1, -1)]
-        else:
-            parts = [list(range(nlow, NL))] + ([list(range(nlow))] if nlow >= 1 else [])
-        first_name = lambda l: f"gru.weight_ih_l{l}" if l >= 1 else "gru.weight_hh_l0"
+        def fill_dl(ws, dl, dlT):
+            with ops._Timed("hbm_softmax_bwd"):
+                ops.softmax_tb_bwd(recon, drecon, dl, dlT, B, Lq, Cv)
+        dz, pgrads = _decoder_bwd_tail(ctx, fill_dl)
+        return (None, dz, None) + pgrads
 
-        wg_cap = [0]             # workgroup cap of the grouped weight-gradient launches (0: one per tile), see the fork below
 
-        def weight_grads(k):
-            """part k of `parts` (None: everything at once, on the current stream)."""
-            with ops._Timed("dec_lstm_wgrad" if (k is None or k == 0) else "dec_lstm_wgrad_deferred"):
-                if k is None or k == 0:
-                    if dt == torch.bfloat16:
-                        ops.gemm_tn(dl, hs[-1].view(TB, ldh), grads["decoded_mean.module.0.weight"], Cv, H, TB, lda=ldl, ldb=ldh)
-                        dbp = W("dbout_p", (Cp,))
-                        ops.colsum_t(dl, TB, Cp, dbp, ldx=ldl)
-                        grads["decoded_mean.module.0.bias"].copy_(dbp[:Cv])
-                    else:
-                        hsT = W("wg_hsT_out", (H, ldT), dt)
-                        ops.cast_transpose(hs[-1].view(TB, ldh), TB, H, dstT=hsT, lds=ldh)
-                        ops.gemm_nt(dlT, hsT, grads["decoded_mean.module.0.weight"], Cv, H, TB, lda=ldT, ldb=ldT)
-                        ops.rowsum(dlT, Cv, TB, grads["decoded_mean.module.0.bias"])
-                layers = range(NL) if k is None else parts[k]
-                caps_big = [int(c) for c in L.knob("MVAE_WGRAD_CAPS", WGRAD_CAPS_BIG).split(":")]       # per part, the two-part schedule of large batches
-                mw = wg_cap[0] if (wg_cap[0] or k is None) else caps_big[min(k, len(caps_big) - 1)]
-                _lstm_weight_grads(ws, grads, "gru", dt, dev, NL, Lq, B, H, dG, ldg, hs, ldh, layers=layers, max_workgroups=mw)
-                if k is not None and dp_early:
-                    # What this part produced is final on this stream: all-reduce it now -- [first parameter of its lowest layer, start of
-                    # the previous part) (part 0: to the end of our range, i.e. with the head).  weight_ih_l0 / latent_input, produced on
-                    # the main stream later, go with the rest in step().  Fork path only: there the gradients are handed over by ASSIGNMENT
-                    # (p.grad = view of the flat buffer), so what step() sees is the reduced buffer; through autograd's AccumulateGrad a
-                    # clone could hide it (FusedAdam.gather_grads)
-                    lo = sink[2] + offs[first_name(min(parts[k]))]
-                    hi = sink[3] if k == 0 else sink[2] + offs[first_name(min(parts[k - 1]))]
-                    gsync.start_early(sink[1], lo, hi)
+class _DecoderElboFn(torch.autograd.Function):
+    """The decoder ending in the ELBO (train.py:31-38) on index targets: the head's logits go straight into mvae_bce_kl_logits_fwd / _bwd --
+    no [B, L, C] probabilities, float one-hot or drecon is allocated, and nothing of that size is saved (the logits live in the forward's
+    saved-state workspace).  Returns the scalar loss; the [3] parts (total, xent, kl) are left on the module as `elbo_parts`."""
 
-        # Fork: the weight-gradient GEMMs are throughput-bound and independent of dz, while the encoder's backward that follows is a
-        # latency-bound chain of small launches -> run them concurrently.  Only when our MolecularVAE peer will join the side stream
-        # (its backward ends with ForkState.join) and no gradient accumulation is pending (p.grad is assigned, never added to).
-        # The later parts are parked (ops.ForkState): the peer releases them right before its row-resident LSTM backward,
-        # whose 128 workgroups leave half the CUs idle -- the GEMMs fill them instead of running alone later.
-        peer = mod.__dict__["_peer"]() if mod.__dict__["_peer"] is not None else None
-        fork = bool(mod.overlap_weight_grads and peer is not None and ctx.from_peer and ctx.needs_input_grad[1] and
-                    all(p.grad is None for p in params))
-        if fork:
-            side = mod._side_stream(dev)
-            gflat.record_stream(side)
-            fstate = peer.__dict__["_fork"]                               # the model's own fork state (ops.ForkState), kept by the peer
-            # first half of the parts: released by the peer after its head section; the rest next to its row-resident LSTM backward.  At small
-            # per-GPU batches (K = T * B short: a group of GEMMs is a few hundred microseconds) EVERYTHING waits for that second point: released
-            # earlier, the chip-filling 256 x 256 tiles only starve the peer's conv / dense backward (a 5 us bias column sum sat 308 us behind
-            # them at b = 128), while next to the 32-workgroup row-resident kernel (0.7 ms) they are hidden completely.
-            late_all = TB <= int(L.knob("MVAE_WGRAD_LATE_TB", 32768))      # round 3: b = 128 8.38 -> 8.22 ms / step, B = 256 +0.13; with the capped grid below B = 256 gains too (9.84 -> 9.72)
-            # ... or, at those batches, released AT ONCE but with a capped grid (mvae_gemm_tn_grouped_capped: `cap` workgroups looping over the
-            # tiles): the compute units left over serve the peer's dependent small launches without queueing behind chip-filling tiles
-            cap = int(L.knob("MVAE_WGRAD_CAP", WGRAD_CAP)) if late_all else 0
-            if cap > 0:
-                wg_cap[0] = cap
-                for k in range(len(parts)):
-                    fstate.park(side, (lambda kk=k: weight_grads(kk)), -1)
-                fstate.run_deferred(stage=-1)
-            else:
-                for k in range(len(parts)):
-                    fstate.park(side, (lambda kk=k: weight_grads(kk)), 1 if (late_all or 2 * k >= len(parts)) else 0)
-        else:
-            weight_grads(None)
-        # layer-0 input is time-invariant: its gradient is the time sum of dG[0]
-        dgx0 = W("dgx0", (B, ldg))           # pad columns of dG are zero, so the padded time sum is too
-        ops.timesum(dG[0], Lq, B, ldg, dgx0)
-        li = W("li", (B, o))
-        ops.gemm_tn(dgx0, li, grads["gru.weight_ih_l0"], G4, o, B, lda=ldg)
-        dli = W("dli", (B, o))
-        ops.gemm_nt(dgx0, P["Wih0T"], dli, B, o, G4)
-        # K6 backward
-        ops.selu_bwd(dli, li)
-        ops.gemm_tn_f32_colsum(dli, z, grads["latent_input.0.weight"], grads["latent_input.0.bias"], o, o, B)
-        dz = torch.empty(B, o, dtype=f32, device=dev)
-        ops.gemm_nt(dli, P["WliT"], dz, B, o, o, ldb=P["WliT"].stride(0))
-        if fork:
-            # gradients are still being written on the side stream: hand them over by assignment (autograd must not touch them)
-            for n, p in zip(names, params):
-                p.grad = grads[n]
-            return (None, dz, None) + (None,) * len(names)
-        return (None, dz, None) + tuple(grads[n] for n in names)
+    @staticmethod
+    @ops.traced("molvae_decoder_elbo_fwd")
+    def forward(ctx, mod, z, idx, mu, logvar, max_len, infer, pred_out, *params):
+        z, logits = _decoder_fwd_logits(ctx, mod, z, infer, params)
+        B, Lq, Cv = z.shape[0], mod.repeat_vector.rep, mod.decoded_mean.module[0].out_features
+        mu, logvar = mu.contiguous().float(), logvar.contiguous().float()
+        out = torch.empty(3, dtype=torch.float32, device=z.device)
+        with ops._Timed("hbm_elbo_fwd"):
+            ops.bce_kl_logits_fwd(logits, Cv, idx, mu, logvar, max_len, out, B, Lq, Cv, pred_out=pred_out)
+        mod.__dict__["elbo_parts"] = out
+        ctx.max_len = max_len
+        if not infer:
+            ctx.save_for_backward(idx, mu, logvar)
+        return out[0].clone()
+
+    @staticmethod
+    @ops.traced("molvae_decoder_elbo_bwd")
+    def backward(ctx, grad_loss):
+        idx, mu, logvar = ctx.saved_tensors
+        g = grad_loss.contiguous().float().reshape(1)
+        dmu, dlogvar = torch.empty_like(mu), torch.empty_like(logvar)
+        mod = ctx.mod
+        B, Lq, Cv = mu.shape[0], mod.repeat_vector.rep, mod.decoded_mean.module[0].out_features
+
+        def fill_dl(ws, dl, dlT):
+            logits = ws.get("logits", (Lq * B, Cv), torch.float32, mu.device)
+            with ops._Timed("hbm_elbo_bwd"):
+                ops.bce_kl_logits_bwd(logits, Cv, idx, mu, logvar, ctx.max_len, g, dl, dlT, dmu, dlogvar, B, Lq, Cv)
+        dz, pgrads = _decoder_bwd_tail(ctx, fill_dl)
+        return (None, dz, None, dmu, dlogvar, None, None, None) + pgrads
 
 
 # ----------------------------------------------------------------------------------------------- VAE
@@ -998,7 +1086,7 @@ class MolecularVAE(nn.Module):
 
     apply = _apply_and_mark
 
-    def forward(self, x, eps=None):
+    def _encode(self, x, eps):
         ev = None
         if x.is_cuda and self.prepack_decoder and L.knob("MVAE_PREPACK", "1") != "0":
             # the decoder's weight shadows (8 bf16 cast / transposes of 4096 x 1024) are independent of the encoder's forward: refresh them
@@ -1008,11 +1096,35 @@ class MolecularVAE(nn.Module):
             with torch.cuda.stream(side):
                 self.decoder._pack(x.device)
                 ev = torch.cuda.Event(); ev.record()
-        x, mu, logvar = self.encoder(x, eps) if eps is not None else self.encoder(x)
+        z, mu, logvar = self.encoder(x, eps) if eps is not None else self.encoder(x)
         if ev is not None:
             torch.cuda.current_stream().wait_event(ev)
+        return z, mu, logvar
+
+    def forward(self, x, eps=None):
+        x, mu, logvar = self._encode(x, eps)
         self.decoder.__dict__["_z_from_peer"] = True       # this forward's z comes from our encoder: its backward will join / release side work
         try:
             return self.decoder(x), mu, logvar
         finally:
             self.decoder.__dict__["_z_from_peer"] = False
+
+    def elbo(self, x, eps=None, max_len=None, pred_out=None):
+        """The training loss straight from the int64 token indices x [B, L]: ``loss_function(*model(x), ...)`` with the one-hot implied
+        (train.py:31-38), without allocating or writing the [B, L, C] reconstruction, the float one-hot or their gradients.  Returns
+        ``(loss, mu, logvar)``; ``self.elbo_parts`` holds (total, xent, kl) on device.  max_len defaults to L; eps / noise as in forward;
+        pred_out: optional int64 [B, L] tensor that receives the arg-max reconstruction (recon.argmax(2))."""
+        _check_index_batch(x, None, self.decoder.repeat_vector.rep, "MolecularVAE.elbo")
+        _require_cuda(x.device, "MolecularVAE.elbo")
+        z, mu, logvar = self._encode(x, eps)
+        self.decoder.__dict__["_z_from_peer"] = True
+        try:
+            loss = self.decoder.elbo(z, x, mu, logvar, max_len=max_len, pred_out=pred_out)
+        finally:
+            self.decoder.__dict__["_z_from_peer"] = False
+        return loss, mu, logvar
+
+    @property
+    def elbo_parts(self):
+        """(total, xent, kl) of the last `elbo` call, a device tensor [3] (reading it is the caller's host sync)."""
+        return self.decoder.__dict__.get("elbo_parts")

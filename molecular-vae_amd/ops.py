@@ -665,6 +665,22 @@ def bce_kl_loss_bwd(recon, target, mu, logvar, max_len, grad_out, drecon, dmu, d
                                         ptr(grad_out), ptr(drecon), ptr(dmu), ptr(dlogvar), stream_ptr()), "mvae_bce_kl_loss_bwd")
 
 
+def bce_kl_logits_fwd(logits, ldl, idx, mu, logvar, max_len, out3, B, Lq, C_, pred_out=None):
+    """ELBO from time-major logits and int64 index targets (mvae_bce_kl_logits_fwd); pred_out: optional int64 [B, Lq] arg-max."""
+    lib = L.load()
+    need = lib.mvae_bce_kl_logits_workspace(B, Lq)
+    ws = Scratch.get(need, logits.device, tag="elbo_ticket", zeroed=True)        # the kernel's ticket counter lives in its last 16 bytes
+    check(lib.mvae_bce_kl_logits_fwd(B, Lq, C_, ptr(logits), ldl, ptr(idx), mu.numel(), ptr(mu), ptr(logvar), float(max_len), ptr(out3),
+                                     ptr(pred_out), ptr(ws), need, stream_ptr()), "mvae_bce_kl_logits_fwd")
+
+
+def bce_kl_logits_bwd(logits, ldl, idx, mu, logvar, max_len, grad_out, dl, dlT, dmu, dlogvar, B, Lq, C_):
+    check(L.load().mvae_bce_kl_logits_bwd(dt_code(dl.dtype), B, Lq, C_, ptr(logits), ldl, ptr(idx), mu.numel(), ptr(mu), ptr(logvar),
+                                          float(max_len), ptr(grad_out), ptr(dl), dl.stride(0), ptr(dlT),
+                                          dlT.stride(0) if dlT is not None else 0, ptr(dmu), ptr(dlogvar), stream_ptr()),
+          "mvae_bce_kl_logits_bwd")
+
+
 def _fill(arr, tensors):
     for i, t in enumerate(tensors):
         arr[i] = t.data_ptr() if t is not None else None

@@ -565,6 +565,17 @@ def train_step(model, optimizer, loss_function, data, ohe, eps=None):
     return loss.detach()
 
 
+def elbo_train_step(model, optimizer, data, eps=None, max_len=None):
+    """train_step on the index targets alone: the loss comes from ``model.elbo(data)`` (the head's logits and the int64 indices, one fused
+    HIP pass each way), so neither the [B, L, C] reconstruction nor the float one-hot is needed.  max_len defaults to L.  Returns the loss
+    as a device tensor."""
+    optimizer.zero_grad(set_to_none=True)
+    loss, _, _ = model.elbo(data, eps=eps, max_len=max_len)
+    loss.backward()
+    optimizer.step()
+    return loss.detach()
+
+
 def exact_match_accuracy(recon_batch, data):
     """train.py:109-113: fraction of sequences whose arg-max reconstruction equals the input, computed on device."""
     preds = recon_batch.argmax(dim=2)
@@ -602,6 +613,28 @@ def evaluate(model, loss_function, batches):
         recon, mu, logvar = model(data)
         loss = loss_function(recon, ohe, mu, logvar)
         acc = (recon.argmax(dim=2) == data).all(dim=1).sum()
+        total = loss if total is None else total + loss
+        right = acc if right is None else right + acc
+        n_seq += data.shape[0]; n += 1
+    model.train(was_training)
+    if n == 0:
+        return float("nan"), float("nan")
+    return float(total) / n, float(right) / n_seq
+
+
+@torch.no_grad()
+def evaluate_elbo(model, batches, max_len=None):
+    """``evaluate`` on index targets: `batches` yields ``idx`` or ``(idx, anything)`` pairs (``DeviceDataset.batches(want_onehot=False)``);
+    the loss comes from ``model.elbo`` and the exact-match accuracy from the arg-max the same launch writes, so no [B, L, C] tensor is
+    made.  Returns ``(mean loss per batch, exact-match accuracy over all sequences)`` as Python floats (one host sync at the end)."""
+    was_training = model.training
+    model.eval()
+    total, right, n_seq, n = None, None, 0, 0
+    for item in batches:
+        data = item[0] if isinstance(item, (tuple, list)) else item
+        pred = torch.empty_like(data)
+        loss, _, _ = model.elbo(data, max_len=max_len, pred_out=pred)
+        acc = (pred == data).all(dim=1).sum()
         total = loss if total is None else total + loss
         right = acc if right is None else right + acc
         n_seq += data.shape[0]; n += 1
