@@ -476,6 +476,28 @@ int mvae_permute102(int T, int B, int V, const float* in, float* out, void* stre
 int mvae_moses_sample_step(int dtype, int B, int V, int H, const void* h_top, int64_t ldh, const void* w_fc, int64_t ldw, const float* bias, float temp,
                            uint32_t seed, int step, int eos_id, const float* table, int W, const float* base, float* add_out, int64_t* x, int64_t x_ld,
                            int64_t* end_pads, uint8_t* eos_mask, int64_t* w_out, void* stream);
+/* Beam-search decoding (an addition beyond the reference, which only samples): R = B * K rows, molecule m owning rows m*K .. m*K + K-1.
+ * mvae_moses_beam_step: one launch per generated token behind the GRU step.  logp = log_softmax(decoder_fc(h_top)) (w_fc [V, ldw] dtype,
+ *   V <= 64 else MVAE_ERR_UNSUPPORTED; 1 <= K <= min(16, V) else MVAE_ERR_INVALID).  An active beam proposes its top-K tokens at
+ *   score + logp, a finished beam (fin != 0) proposes itself once (token pad_id, score unchanged); per molecule the best K candidates
+ *   survive in the order (score desc, parent beam asc, token asc), a NaN counting as -inf.  Per new beam r it writes score[r], fin[r],
+ *   ends[r] (step + 1 at the first <eos>, unchanged otherwise: initialise ends to max_len), the backpointer record hist_tok / hist_par
+ *   [max_len, R] int32 at row `step` (token; parent beam 0..K-1 of the same molecule), the next step's layer-0 addend row
+ *   add_out[r] = table[token] + base[r] (fp32 [*, W], 16-byte aligned), and reorders the recurrent state: state (dtype) holds, per layer l
+ *   (offset l * layer_stride elements), half 0 = the state the GRU step read as h0 and half 1 (offset half_stride) = the state it wrote,
+ *   rows of ldh elements; the parent's half-1 row is copied into row r of half 0 for every layer.  h_top is half 1 of the last layer.
+ *   Initial state: score 0 for beam 0 and -inf for beams 1..K-1 of every molecule, fin 0, ends max_len.
+ * mvae_moses_beam_finalize: ids [B, K, max_len] int64 from the backpointers (bos_id first, pad after each end), in score order (the beams
+ *   are kept sorted by mvae_moses_beam_step); ends_out [B*K] / score_out [B*K] (optional) copy ends / score.
+ * mvae_ce_rows_fwd: out[b] = log p(x[b] | z) = sum over t of log_softmax(logits row t*B+b)[x[b, t+1]] for x[b, t+1] != pad -- the targets of
+ *   mvae_ce_loss_fwd, one float per sequence, summed in t order (bitwise deterministic); an id outside [0, V) gives NaN. */
+int mvae_moses_beam_step(int dtype, int B, int K, int V, int H, int layers, void* state, int64_t layer_stride, int64_t half_stride, int64_t ldh,
+                         const void* w_fc, int64_t ldw, const float* bias, int step, int eos_id, int pad_id, const float* table, int W,
+                         const float* base, float* add_out, float* score, uint8_t* fin, int64_t* ends, int32_t* hist_tok, int32_t* hist_par,
+                         void* stream);
+int mvae_moses_beam_finalize(int B, int K, int max_len, int bos_id, const int32_t* hist_tok, const int32_t* hist_par, const int64_t* ends,
+                             const float* score, int64_t* ids, int64_t* ends_out, float* score_out, void* stream);
+int mvae_ce_rows_fwd(int B, int T, int V, const float* logits, int64_t ldl, const int64_t* x, int pad, float* out, void* stream);
 int mvae_relu_bwd(int64_t n, float* dy, const float* y, void* stream);
 int mvae_mask_rows_tb(int dtype, int T, int B, int64_t ld, const int32_t* lengths, void* buf, void* stream);
 

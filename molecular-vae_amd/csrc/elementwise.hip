@@ -1013,6 +1013,175 @@ __global__ __launch_bounds__(256) void moses_sample_step_kernel(int B, int V, in
   }
 }
 
+// ------------------------------------------------------------------------------------------- beam-search decoding step (no reference counterpart)
+// ONE launch per generated token for everything behind the GRU step, for R = B * K rows (molecule m owns rows m*K .. m*K + K-1, beam k of it
+// being row m*K + k):  logp = log_softmax(decoder_fc(h_top));  an active beam r proposes its own top-K tokens at score[r] + logp, a finished
+// beam proposes itself once (token pad, score unchanged);  per molecule the best K of those candidates survive, in the total order
+// (score desc, parent beam asc, token asc) -- so the K beams of a molecule stay sorted by score.  A NaN candidate counts as -inf.
+// A workgroup owns whole molecules (G = max(1, 4 / K) of them per pass, one wave per row), striding over them as the sampler strides over
+// rows, so the V x H head is loaded into LDS once per workgroup and each merge stays in LDS.  The launch then writes, per new beam, the
+// backpointer record (token, parent) of this step, the new score / finished flag / end (end = step + 1 at the first <eos>, unchanged
+// otherwise), the next step's layer-0 addend row table[token] + base[r], and reorders the recurrent state: for every layer, the parent's row
+// of the state the GRU step just wrote (half 1 of `state`) is copied into row r of half 0, which that step has already consumed and which
+// the next step reads as its h0.  Parents are rows of the same molecule, so a workgroup touches only its own rows.
+constexpr int BEAM_KMAX = 16;
+template <typename T>
+__global__ __launch_bounds__(256) void moses_beam_step_kernel(int B, int K, int V, int H, int NL, T* __restrict__ state, long layer_stride,
+                                                              long half_stride, long ldh, const T* __restrict__ wfc, long ldw,
+                                                              const float* __restrict__ bias, int step, int eos_id, int pad_id,
+                                                              const float* __restrict__ table, int W, const float* __restrict__ base,
+                                                              float* __restrict__ add_out, float* __restrict__ score, uint8_t* __restrict__ fin,
+                                                              int64_t* __restrict__ ends, int32_t* __restrict__ hist_tok, int32_t* __restrict__ hist_par) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  T* ws = reinterpret_cast<T*>(smem_raw);                    // [V][H]
+  __shared__ float cand_s[BEAM_KMAX * BEAM_KMAX];            // [row of the pass][rank within the row]
+  __shared__ int cand_t[BEAM_KMAX * BEAM_KMAX];
+  __shared__ int cand_n[BEAM_KMAX];
+  __shared__ float old_s[BEAM_KMAX];
+  __shared__ int old_f[BEAM_KMAX];
+  __shared__ long old_e[BEAM_KMAX];
+  __shared__ float sel_s[BEAM_KMAX];
+  __shared__ int sel_p[BEAM_KMAX], sel_t[BEAM_KMAX];
+  for (int i = threadIdx.x; i < V * H; i += 256) ws[i] = wfc[(long)(i / H) * ldw + (i % H)];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int G = K >= 4 ? 1 : 4 / K;                         // molecules per pass: G * K <= 16 rows
+  const long R = (long)B * K;
+  const T* htop = state + (long)(NL - 1) * layer_stride + half_stride;
+  for (int m0 = blockIdx.x * G; m0 < B; m0 += gridDim.x * G) {
+    const int nm = (B - m0 < G) ? B - m0 : G, nr = nm * K;
+    const long r0 = (long)m0 * K;
+    // 1. each row's candidates, sorted by (score desc, token asc)
+    for (int lr = wave; lr < nr; lr += 4) {
+      const long r = r0 + lr;
+      float s = score[r];
+      if (s != s) s = -INFINITY;
+      const bool done = fin[r] != 0;
+      if (lane == 0) { old_s[lr] = s; old_f[lr] = done; old_e[lr] = (long)ends[r]; }
+      if (done) {
+        if (lane == 0) { cand_s[lr * K] = s; cand_t[lr * K] = pad_id; cand_n[lr] = 1; }
+        continue;                                            // wave-uniform
+      }
+      float mine = -INFINITY;
+      for (int v = 0; v < V; ++v) {
+        float a = 0.f;
+        for (int k = lane; k < H; k += 64) a += TT<T>::ld(htop + r * ldh + k) * TT<T>::ld(ws + (long)v * H + k);
+        a = wave_sum(a);
+        if (lane == v) mine = a + (bias ? bias[v] : 0.f);
+      }
+      const float mx = wave_max(mine);
+      const float se = wave_sum(lane < V ? expf(mine - mx) : 0.f);
+      float c = s + (mine - (mx + logf(se)));
+      if (c != c) c = -INFINITY;
+      bool avail = lane < V;
+      for (int j = 0; j < K; ++j) {                          // K <= V: an available class is always left
+        const float best = wave_max(avail ? c : -INFINITY);
+        const unsigned long long hit = __ballot(avail && c == best);
+        const int v = hit ? (int)__builtin_ctzll(hit) : 0;
+        if (lane == v) avail = false;
+        if (lane == 0) { cand_s[lr * K + j] = best; cand_t[lr * K + j] = v; }
+      }
+      if (lane == 0) cand_n[lr] = K;
+    }
+    __syncthreads();
+    // 2. per molecule, a K-way merge of its K sorted candidate lists (lane p = the head of parent p's list): the best K survive
+    if (wave < nm) {
+      const int g = wave;
+      int ptr = 0;
+      for (int j = 0; j < K; ++j) {
+        const bool valid = lane < K && ptr < cand_n[g * K + lane];
+        const int ci = (g * K + (lane < K ? lane : 0)) * K + (ptr < K ? ptr : 0);
+        const float key = valid ? cand_s[ci] : -INFINITY;
+        const int tk = valid ? cand_t[ci] : pad_id;
+        const float best = wave_max(key);
+        const unsigned long long hit = __ballot(valid && key == best);   // at least K candidates exist: never empty
+        const int p = hit ? (int)__builtin_ctzll(hit) : 0;
+        const int tok = __shfl(tk, p, 64);
+        if (lane == p) ++ptr;
+        if (lane == 0) { sel_s[g * K + j] = best; sel_p[g * K + j] = p; sel_t[g * K + j] = hit ? tok : pad_id; }
+      }
+    }
+    __syncthreads();
+    // 3. the new beams: bookkeeping, backpointers, next input rows, recurrent state reordered from the parents
+    for (int lr = wave; lr < nr; lr += 4) {
+      const long r = r0 + lr;
+      const int p = sel_p[lr], lp = (lr / K) * K + p;
+      const bool pdone = old_f[lp] != 0;
+      const int tok = pdone ? pad_id : sel_t[lr];
+      if (lane == 0) {
+        score[r] = sel_s[lr];
+        fin[r] = (pdone || tok == eos_id) ? 1 : 0;
+        ends[r] = (!pdone && tok == eos_id) ? (int64_t)(step + 1) : (int64_t)old_e[lp];
+        hist_tok[(long)step * R + r] = tok;
+        hist_par[(long)step * R + r] = p;
+      }
+      const float* trow = table + (long)tok * W;
+      const float* brow = base + r * W;
+      float* orow = add_out + r * W;
+      for (int cidx = lane * 4; cidx < W; cidx += 256) {
+        const float4 tv = *reinterpret_cast<const float4*>(trow + cidx), bv = *reinterpret_cast<const float4*>(brow + cidx);
+        *reinterpret_cast<float4*>(orow + cidx) = make_float4(tv.x + bv.x, tv.y + bv.y, tv.z + bv.z, tv.w + bv.w);
+      }
+      const long src_row = r0 + lp;
+      for (int l = 0; l < NL; ++l) {
+        const T* src = state + (long)l * layer_stride + half_stride + src_row * ldh;
+        T* dst = state + (long)l * layer_stride + r * ldh;
+        if (((H * (int)sizeof(T)) & 15) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0) {
+          const int n16 = H * (int)sizeof(T) / 16;
+          for (int i = lane; i < n16; i += 64) reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(src)[i];
+        } else {
+          for (int i = lane; i < H; i += 64) dst[i] = src[i];
+        }
+      }
+    }
+    __syncthreads();                                         // LDS is reused by the next pass
+  }
+}
+// The K hypotheses of every molecule from the backpointer record, already in score order: ids [B, K, max_len] int64 (bos first, the
+// chosen tokens after it -- pad after each end, as finished beams only ever append pad).  One thread per (molecule, beam).
+__global__ __launch_bounds__(256) void moses_beam_finalize_kernel(int B, int K, int max_len, int bos_id, const int32_t* __restrict__ hist_tok,
+                                                                  const int32_t* __restrict__ hist_par, const int64_t* __restrict__ ends,
+                                                                  const float* __restrict__ score, int64_t* __restrict__ ids,
+                                                                  int64_t* __restrict__ ends_out, float* __restrict__ score_out) {
+  const long R = (long)B * K;
+  for (long r = (long)blockIdx.x * 256 + threadIdx.x; r < R; r += (long)gridDim.x * 256) {
+    const long m0 = (r / K) * K;
+    int k = (int)(r - m0);
+    int64_t* out = ids + r * max_len;
+    for (int t = max_len - 1; t >= 1; --t) {
+      const long i = (long)t * R + m0 + k;
+      out[t] = hist_tok[i];
+      k = hist_par[i];
+    }
+    out[0] = bos_id;
+    if (ends_out) ends_out[r] = ends[r];
+    if (score_out) score_out[r] = score[r];
+  }
+}
+// log p(x[b] | z) per sequence from the TIME-MAJOR logits of the teacher-forced decoder: the targets of mvae_ce_loss_fwd (row t*B+b predicts
+// x[b, t+1], pad targets ignored), one float per sequence.  One wave per sequence walks t in order: bitwise deterministic.
+__global__ __launch_bounds__(256) void ce_rows_fwd_kernel(int B, int T_, int V, const float* __restrict__ logits, long ldl,
+                                                          const int64_t* __restrict__ x, int pad, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  for (long b = (long)blockIdx.x * 4 + (threadIdx.x >> 6); b < B; b += (long)gridDim.x * 4) {
+    float acc = 0.f;
+    for (int t = 0; t + 1 < T_; ++t) {
+      const long tgt = x[b * T_ + t + 1];
+      if (tgt == pad) continue;
+      if (tgt < 0 || tgt >= V) { acc = NAN; break; }         // an id outside the vocabulary: NaN, never read through
+      const float* l = logits + ((long)t * B + b) * ldl;
+      float mx = -INFINITY;
+      for (int v = lane; v < V; v += 64) mx = fmaxf(mx, l[v]);
+      mx = wave_max(mx);
+      float s = 0.f;
+      for (int v = lane; v < V; v += 64) s += expf(l[v] - mx);
+      s = wave_sum(s);
+      acc += l[tgt] - (mx + logf(s));
+    }
+    if (lane == 0) out[b] = acc;
+  }
+}
+
 // ------------------------------------------------------------------------------------------- grad-norm + Adam
 constexpr int SUMSQ_CHUNK = 1 << 16;   // elements per partial
 __global__ __launch_bounds__(256) void sumsq_kernel(long n, const float* g, float* partial) {
@@ -1710,6 +1879,62 @@ int mvae_moses_sample_step(int dtype, int B, int V, int H, const void* h_top, in
     hipLaunchKernelGGL((moses_sample_step_kernel<float>), dim3(blocks), dim3(256), lds, st, B, V, H, (const float*)h_top, (long)ldh, (const float*)w_fc, (long)ldw,
                        bias, 1.f / temp, seed, step, eos_id, table, W, base, add_out, x, (long)x_ld, end_pads, eos_mask, w_out);
   else return MVAE_ERR_INVALID;
+  MVAE_CHECK_HIP(hipGetLastError());
+  return MVAE_OK;
+}
+
+int mvae_moses_beam_step(int dtype, int B, int K, int V, int H, int layers, void* state, int64_t layer_stride, int64_t half_stride, int64_t ldh,
+                         const void* w_fc, int64_t ldw, const float* bias, int step, int eos_id, int pad_id, const float* table, int W,
+                         const float* base, float* add_out, float* score, uint8_t* fin, int64_t* ends, int32_t* hist_tok, int32_t* hist_par,
+                         void* stream) {
+  if (!state || !w_fc || !table || !base || !add_out || !score || !fin || !ends || !hist_tok || !hist_par) return MVAE_ERR_INVALID;
+  if (dtype != MVAE_F32 && dtype != MVAE_BF16) return MVAE_ERR_INVALID;
+  if (B < 1 || V < 1 || H < 1 || layers < 1 || layers > MVAE_MAX_LAYERS || ldh < H || ldw < H || (W & 3) || W < 4 || step < 1) return MVAE_ERR_INVALID;
+  if (K < 1 || K > BEAM_KMAX || K > V) return MVAE_ERR_INVALID;
+  if (eos_id < 0 || eos_id >= V || pad_id < 0 || pad_id >= V) return MVAE_ERR_INVALID;
+  if ((reinterpret_cast<uintptr_t>(table) | reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(add_out)) & 15) return MVAE_ERR_INVALID;
+  if (V > 64) return MVAE_ERR_UNSUPPORTED;                           // one class per lane
+  const size_t lds = (size_t)V * H * (dtype == MVAE_BF16 ? 2 : 4);
+  constexpr size_t lds_cap = 156 * 1024;                             // the CU's 160 KB less the kernel's static candidate arrays
+  if (lds > lds_cap) return MVAE_ERR_UNSUPPORTED;
+  if (lds > 64 * 1024) {                                              // above the default dynamic-LDS limit: opt in, as the sampler does
+    static std::atomic<bool> attr[64];
+    int dev_id = 0;
+    MVAE_CHECK_HIP(hipGetDevice(&dev_id));
+    if (dev_id < 0 || dev_id >= 64 || !attr[dev_id].load(std::memory_order_acquire)) {
+      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(moses_beam_step_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
+      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(moses_beam_step_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
+      if (dev_id >= 0 && dev_id < 64) attr[dev_id].store(true, std::memory_order_release);
+    }
+  }
+  const int G = K >= 4 ? 1 : 4 / K;
+  int blocks = (B + G - 1) / G; if (blocks > 1024) blocks = 1024;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MVAE_BF16)
+    hipLaunchKernelGGL((moses_beam_step_kernel<bf16_t>), dim3(blocks), dim3(256), lds, st, B, K, V, H, layers, (bf16_t*)state, (long)layer_stride,
+                       (long)half_stride, (long)ldh, (const bf16_t*)w_fc, (long)ldw, bias, step, eos_id, pad_id, table, W, base, add_out, score, fin,
+                       ends, hist_tok, hist_par);
+  else
+    hipLaunchKernelGGL((moses_beam_step_kernel<float>), dim3(blocks), dim3(256), lds, st, B, K, V, H, layers, (float*)state, (long)layer_stride,
+                       (long)half_stride, (long)ldh, (const float*)w_fc, (long)ldw, bias, step, eos_id, pad_id, table, W, base, add_out, score, fin,
+                       ends, hist_tok, hist_par);
+  MVAE_CHECK_HIP(hipGetLastError());
+  return MVAE_OK;
+}
+
+int mvae_moses_beam_finalize(int B, int K, int max_len, int bos_id, const int32_t* hist_tok, const int32_t* hist_par, const int64_t* ends,
+                             const float* score, int64_t* ids, int64_t* ends_out, float* score_out, void* stream) {
+  if (!hist_tok || !hist_par || !ends || !score || !ids || B < 1 || K < 1 || K > BEAM_KMAX || max_len < 1) return MVAE_ERR_INVALID;
+  hipLaunchKernelGGL(moses_beam_finalize_kernel, dim3(grid_for((long)B * K)), dim3(256), 0, (hipStream_t)stream, B, K, max_len, bos_id, hist_tok,
+                     hist_par, ends, score, ids, ends_out, score_out);
+  MVAE_CHECK_HIP(hipGetLastError());
+  return MVAE_OK;
+}
+
+int mvae_ce_rows_fwd(int B, int T, int V, const float* logits, int64_t ldl, const int64_t* x, int pad, float* out, void* stream) {
+  if (!logits || !x || !out || B < 1 || T < 1 || V < 1 || ldl < V) return MVAE_ERR_INVALID;
+  int blocks = (B + 3) / 4; if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(ce_rows_fwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, B, T, V, logits, (long)ldl, x, pad, out);
   MVAE_CHECK_HIP(hipGetLastError());
   return MVAE_OK;
 }

@@ -248,7 +248,100 @@ class VAE(nn.Module, _SavedState):
             return [xs[b, :ends[b]] for b in range(B)], z
         return [self.tensor2string(xs[b, :ends[b]]) for b in range(B)], z
 
-    # -- packed shadows: ONE multi-tensor pack launch (ops.PackList) instead of ~60 few-microsecond launches per optimiser step
+    @torch.no_grad()
+    def decode(self, z, beam_width=1, max_len=100, return_tokens=False):
+        """Deterministic decoding of the latents z [B, d_z] by beam search (an addition: the reference only samples); beam_width=1 is greedy
+        decoding.  The `sample()` loop with the beam launch in place of the sampling launch: per generated token one wavefront pass of the
+        3-layer stack (T = 1) and ONE mvae_moses_beam_step launch, which also reorders the recurrent state to the surviving beams -- 4 launches
+        per token, no torch arithmetic and no host synchronisation in the loop; it runs to max_len as `sample` does.  A hypothesis' score is
+        its raw summed log-probability log p(tokens 1..end | z) (no length normalisation; the `pad` steps after <eos> add nothing); ties
+        are broken by (parent beam, token id), so a decode is deterministic.  Dropout is never applied.
+        Returns (best string per molecule, scores [B]); return_tokens=True: (per molecule, its beam_width id tensors cut at their ends --
+        bos first, <eos> last when it came -- best first, scores [B, beam_width])."""
+        ids, ends, scores = self._beam_search(z, beam_width, max_len)
+        xs, es = ids.cpu(), ends.cpu()
+        B, K = es.shape
+        if return_tokens:
+            return [[xs[b, k, :es[b, k]] for k in range(K)] for b in range(B)], scores
+        best, n = xs[:, 0].tolist(), es[:, 0].tolist()        # Python lists: per-row tensor indexing costs ~10 us a molecule
+        return [self.vocabulary.ids2string(best[b][:n[b]], rem_bos=True, rem_eos=True) for b in range(B)], scores[:, 0]
+
+    def _beam_search(self, z, beam_width, max_len):
+        """decode() without the host side: (ids [B, K, max_len] int64, ends [B, K] int64, scores [B, K] fp32) on the device, best first."""
+        V, dz = self.x_emb.num_embeddings, self.d_z
+        K = int(beam_width)
+        if not (1 <= K <= 16) or K > V:
+            raise ValueError(f"decode: beam_width must be in [1, min(16, V = {V})], got {beam_width}")
+        if int(max_len) < 1:
+            raise ValueError(f"decode: max_len must be >= 1, got {max_len}")
+        if z.dim() != 2 or z.shape[1] != dz or z.shape[0] < 1:
+            raise ValueError(f"decode: z must be [B, {dz}], got {tuple(z.shape)}")
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.decode")
+        max_len = int(max_len)
+        P = self._pack(dev)
+        ws, dt, f32 = self._ws, self.compute_dtype, torch.float32
+        B = z.shape[0]; R = B * K
+        zr = z.to(dev).float().repeat_interleave(K, 0).contiguous()              # beams of molecule m: rows m*K .. m*K + K-1
+        pd = P["dec"]; Hd = pd["H"]; NL = self.decoder_rnn.num_layers
+        Vp, ldh = _pad(V, 4), Hd + _LDPAD
+        W = lambda name, shape, d=f32: ws.get("bm_" + name, shape, d, dev)
+        h0 = W("h0", (R, Hd)); ops.gemm_nt(zr, self.decoder_lat.weight, h0, R, Hd, dz, bias=self.decoder_lat.bias)
+        tbl3 = W("tbl3", (V, 3 * Hd)); ops.gemm_nt(P["E_p"], pd["Wx_p"], tbl3, V, 3 * Hd, Vp)
+        tbl4 = W("tbl4", (V, 4 * Hd)); tbl4[:, :3 * Hd].copy_(tbl3)
+        zp3 = W("zp3", (R, 3 * Hd)); ops.gemm_nt(zr, P["Wz"], zp3, R, 3 * Hd, dz)
+        zp4 = W("zp4", (R, 4 * Hd)); zp4[:, :3 * Hd].copy_(zp3)
+        state = W("state", (NL, 2, R, ldh), dt)            # [l][0] = the state the next GRU step reads, [l][1] = the state it writes
+        for l in range(NL):
+            ops.cast_transpose(h0, R, Hd, dst=state[l][0])
+        gates = [W(f"gates{l}", (1, R, 4 * Hd), dt) for l in range(NL)]
+        hstate = [W(f"hstate{l}", (2, R, Hd)) for l in range(NL)]
+        add = W("add", (1, R, 4 * Hd))
+        score = torch.full((B, K), float("-inf"), device=dev); score[:, 0] = 0.0    # beams 1..K-1 start dead: no duplicates at step 1
+        score = score.view(R)
+        fin = torch.zeros(R, dtype=torch.uint8, device=dev)
+        ends = torch.full((R,), max_len, dtype=torch.long, device=dev)
+        hist_tok = torch.empty((max_len, R), dtype=torch.int32, device=dev)          # row 0 (bos) is never read
+        hist_par = torch.empty((max_len, R), dtype=torch.int32, device=dev)
+        w = torch.full((R, 1), self.bos, dtype=torch.long, device=dev)
+        ops.gather_rows_tb(w, tbl4, add, R, 1, V, 4 * Hd, base=zp4)     # the <bos> input rows; later ones come out of the beam launch
+        h_out, h_in, ldws = [state[l][1:2] for l in range(NL)], [state[l][0] for l in range(NL)], [pd["ldw"]] * NL    # fixed: no swap
+        for i in range(1, max_len):
+            ops.rnn_fwd(L.CELL_GRU, dt, 1, R, Hd, add, 0, pd["Wih"], ldws, pd["Whh"], ldws, pd["bias"], h_out, ldh, None, gates, hstate,
+                        h0=h_in, ldh0=ldh, persist=False)
+            ops.moses_beam_step(state, ldh, P["Wfc"], self.decoder_fc.bias, i, self.eos, self.pad, tbl4, zp4, add, score, fin, ends,
+                                hist_tok, hist_par, B, K, V, Hd)
+        ids = torch.empty((B, K, max_len), dtype=torch.long, device=dev)
+        ends_out = torch.empty((B, K), dtype=torch.long, device=dev)
+        scores = torch.empty((B, K), device=dev)
+        ops.moses_beam_finalize(hist_tok, hist_par, ends, score, ids, ends_out, scores, self.bos, B, K, max_len)
+        return ids, ends_out, scores
+
+    @torch.no_grad()
+    def score(self, x, z):
+        """log p(x | z) per molecule: the teacher-forced decoder (no dropout) on the latents z [B, d_z], followed by mvae_ce_rows_fwd -- the
+        raw summed log-probability of tokens 1 .. end of each sequence (the targets of the mean reconstruction loss).  x: a list of id
+        tensors (bos first) or strings, in any order.  Returns a float32 [B] device tensor; no gradients."""
+        seqs = [self.string2tensor(s, device="cpu") if isinstance(s, str) else torch.as_tensor(s, dtype=torch.long) for s in x]
+        B = len(seqs)
+        if B < 1 or z.dim() != 2 or tuple(z.shape) != (B, self.d_z):
+            raise ValueError(f"score: z must be [{B}, {self.d_z}], got {tuple(z.shape)}")
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.score")
+        order = sorted(range(B), key=lambda b: -int(seqs[b].numel()))          # the decoder's packed layout wants lengths descending
+        perm = torch.tensor(order, dtype=torch.long, device=dev)
+        x_pad, len_t = self._batch([seqs[b].to(dev) for b in order])
+        T, V = x_pad.shape[1], self.x_emb.num_embeddings
+        # a workspace of its own: a pending forward_decoder's saved state (self._ws) stays intact
+        ws = self.__dict__.setdefault("_score_ws", _Workspace())
+        y_tb = _dec_forward(self, ws, self._pack(dev), x_pad, len_t, z.to(dev).float()[perm].contiguous(), None, heads=False)
+        lp = torch.empty(B, device=dev)
+        ops.ce_rows(y_tb, V, x_pad, self.pad, lp, B, T, V)
+        out = torch.empty_like(lp)
+        out[perm] = lp
+        return out
+
+    # -- packed shadows: ONE multi-tensor pack launch    # -- packed shadows: ONE multi-tensor pack launch (ops.PackList) instead of ~60 few-microsecond launches per optimiser step
     def _pack(self, dev):
         params = self._plist()
         key = _params_key(params) + (self.compute_dtype,)
@@ -367,7 +460,8 @@ def _enc_forward(mod, ws, P, x_pad, lengths, eps):
     return z, kl, lv, eps
 
 
-def _dec_forward(mod, ws, P, x_pad, lengths, z, drop):
+def _dec_forward(mod, ws, P, x_pad, lengths, z, drop, heads=True):
+    """heads=False: return the time-major logits y_tb [T*B, V] alone (no `y` permute, no mean cross-entropy; VAE.score)."""
     dev, dt, f32 = x_pad.device, mod.compute_dtype, torch.float32
     B, T = x_pad.shape
     V, dz = mod.x_emb.num_embeddings, mod.d_z
@@ -397,6 +491,8 @@ def _dec_forward(mod, ws, P, x_pad, lengths, z, drop):
     TB = T * B
     y_tb = W("y_tb", (TB, V))
     ops.gemm_nt(hsx_d[-1][1:].reshape(TB, ldh_d), P["Wfc"], y_tb, TB, V, Hd, bias=mod.decoder_fc.bias)
+    if not heads:
+        return y_tb
     y = torch.empty(B, T, V, device=dev); ops.permute102(y_tb, y, T, B, V)
     loss2 = W("loss2", (2,)); ops.ce_loss_fwd(y_tb, V, x_pad, mod.pad, loss2, B, T, V)
     return loss2[0].clone(), y, loss2[1].clone()

@@ -477,6 +477,27 @@ def moses_sample_step(h_top, ldh, w_fc, bias, temp, seed, step, eos_id, table, b
                                           ptr(x), x.stride(0), ptr(end_pads), ptr(eos_mask), ptr(w_out), stream_ptr()), "mvae_moses_sample_step")
 
 
+
+def moses_beam_step(state, ldh, w_fc, bias, step, eos_id, pad_id, table, base, add_out, score, fin, ends, hist_tok, hist_par, B, K, V, H):
+    """One beam-search token behind the GRU step: head GEMV, log-softmax, per-beam top-K, per-molecule merge, backpointers and the next
+    step's layer-0 addend rows, and the recurrent state reordered from state[:, 1] (just written) into state[:, 0] (the next h0) -- one
+    launch (mvae_moses_beam_step).  state: [layers, 2, B*K, ldh] in the compute dtype."""
+    check(L.load().mvae_moses_beam_step(dt_code(state.dtype), B, K, V, H, state.shape[0], ptr(state), state.stride(0), state.stride(1), ldh,
+                                        ptr(w_fc), w_fc.stride(0), ptr(bias), int(step), int(eos_id), int(pad_id), ptr(table), table.shape[1],
+                                        ptr(base), ptr(add_out), ptr(score), ptr(fin), ptr(ends), ptr(hist_tok), ptr(hist_par), stream_ptr()),
+          "mvae_moses_beam_step")
+
+
+def moses_beam_finalize(hist_tok, hist_par, ends, score, ids, ends_out, score_out, bos_id, B, K, max_len):
+    """ids [B, K, max_len] int64 from the beam search's backpointers, in score order; ends / scores copied out (mvae_moses_beam_finalize)."""
+    check(L.load().mvae_moses_beam_finalize(B, K, max_len, int(bos_id), ptr(hist_tok), ptr(hist_par), ptr(ends), ptr(score), ptr(ids),
+                                            ptr(ends_out), ptr(score_out), stream_ptr()), "mvae_moses_beam_finalize")
+
+
+def ce_rows(logits, ldl, x, pad, out, B, T, V):
+    """out[b] = log p(x[b] | z) from time-major teacher-forced logits, pad targets ignored (mvae_ce_rows_fwd)."""
+    check(L.load().mvae_ce_rows_fwd(B, T, V, ptr(logits), ldl, ptr(x), pad, ptr(out), stream_ptr()), "mvae_ce_rows_fwd")
+
 def sample_uniform(seed, step, B):
     """Host restatement of the sampling step's uniforms u(b) = hash(seed, step * B + b) / 2^32 (tests)."""
     import numpy as np

@@ -733,3 +733,32 @@ def moses_train_epoch(model, epoch, batches, kl_weight, optimizer=None, log_ever
     lr = optimizer.param_groups[0]["lr"] if optimizer is not None else None
     return {"epoch": epoch, "kl_weight": kl_weight, "lr": lr, "kl_loss": mean[1], "recon_loss": mean[2], "loss": mean[0],
             "mode": "Eval" if optimizer is None else "Train"}
+
+
+@torch.no_grad()
+def moses_reconstruction(model, batches, beam_width=1, max_len=100):
+    """Reconstruction of a ``mosesvae.VAE`` (an addition: the reference only reports teacher-forced token accuracy): every batch (a list of
+    id tensors, bos first, or a PaddedBatch) is encoded with eps = 0 (z = mu), decoded deterministically (``VAE.decode(z, beam_width,
+    max_len)``, best hypothesis) and compared as a string with its input; ``VAE.score(x, mu)`` gives each molecule's log p(x | mu).
+    Returns (exact-match fraction, mean per-molecule log p(x | mu)) as Python floats; the host waits once, at the end."""
+    from .vocab import PaddedBatch
+    dev = model.device
+    lp_sum, n = torch.zeros((), dtype=torch.float64, device=dev), 0
+    kept = []
+    for batch in batches:
+        if isinstance(batch, PaddedBatch):
+            seqs = [batch.x_pad[b, :int(batch.lengths[b])] for b in range(batch.x_pad.shape[0])]
+        else:
+            seqs = list(batch)
+        B = len(seqs)
+        mu, _, _ = model.forward_encoder(batch, eps=torch.zeros(B, model.d_z, device=dev))
+        ids, ends, _ = model._beam_search(mu, beam_width, max_len)
+        lp_sum += model.score(seqs, mu).double().sum()
+        kept.append((seqs, ids[:, 0], ends[:, 0]))
+        n += B
+    hits = 0
+    for seqs, ids, ends in kept:
+        ids, ends = ids.tolist(), ends.tolist()
+        hits += sum(model.vocabulary.ids2string(ids[b][:ends[b]], rem_bos=True, rem_eos=True) == model.tensor2string(seqs[b].cpu())
+                    for b in range(len(seqs)))
+    return hits / max(n, 1), float(lp_sum) / max(n, 1)
