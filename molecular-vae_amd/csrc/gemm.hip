@@ -128,8 +128,9 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(GemmArgs p) {
 }
 
 // C[M,N] = A^T . B with A [K][lda], B [K][ldb] (bf16, K-major): the weight-gradient contraction (see tile_pipe.hpp, TN form).
-template <int NBUF, int MI, bool WS>
-__global__ __launch_bounds__(WS ? 512 : 256) void gemm_tn_bf16_kernel(GemmArgs p) {
+// 512 threads: waves 0-3 compute, waves 4-7 only load (tile_gemm_ws_tn).
+template <int NBUF, int MI>
+__global__ __launch_bounds__(512) void gemm_tn_bf16_kernel(GemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int BM = 32 * MI;
   const int tid = threadIdx.x, lane = tid & 63, wave = (tid >> 6) & 3, wm = wave >> 1, wn = wave & 1;
@@ -148,12 +149,8 @@ __global__ __launch_bounds__(WS ? 512 : 256) void gemm_tn_bf16_kernel(GemmArgs p
   PipeSegTN<MI> s;
   pipe_seg_tn_init<MI>(s, reinterpret_cast<const bf16_t*>(p.A) + kbeg * p.lda, p.lda, m0, reinterpret_cast<const bf16_t*>(p.B) + kbeg * p.ldb,
                        p.ldb, n0, (int)(kend - kbeg), tid & 255);
-  if constexpr (WS) {
-    tile_gemm_ws_tn<NBUF, MI>(smem, s, wm, wn, acc, tid);
-    if (tid >= 256) return;                       // loader waves own no accumulators
-  } else {
-    tile_gemm_pipe_tn<NBUF, MI>(smem, s, wm, wn, acc, tid);
-  }
+  tile_gemm_ws_tn<NBUF, MI>(smem, s, wm, wn, acc, tid);
+  if (tid >= 256) return;                         // loader waves own no accumulators
   const int lr = lane & 15, lq = lane >> 4;
 #pragma unroll
   for (int i = 0; i < MI; ++i)
@@ -515,36 +512,18 @@ int launch_gemm_tn_bf16_colsum(int M, int N, int K, const void* A, long lda, con
   dim3 grid(pl.tiles_m * pl.tiles_n, pl.splits);
   static bool attr_set = false;
   if (!attr_set) {
-    MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_bf16_kernel<4, 4, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_bf16_kernel<3, 8, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_bf16_kernel<4, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_bf16_kernel<3, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_bf16_kernel<4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_bf16_kernel<3, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_bf16_256_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_bf16_256_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr_set = true;
   }
-  const char* we = mvae_knob("MVAE_TN_WS");
-  const bool wspec = we ? atoi(we) != 0 : true;      // loader / consumer wave specialisation (512-thread workgroups)
   if (pl.bm == 512) {
     if (colsum_out) hipLaunchKernelGGL(gemm_tn_bf16_256_kernel<true>, grid, dim3(512), 2 * 65536, st, p);
     else hipLaunchKernelGGL(gemm_tn_bf16_256_kernel<false>, grid, dim3(512), 2 * 65536, st, p);
   }
-  else if (wspec) {
-    if (pl.bm == 256) hipLaunchKernelGGL((gemm_tn_bf16_kernel<3, 8, true>), grid, dim3(512), 3 * (32768 + 16384), st, p);
-    else {
-      const char* ne = mvae_knob("MVAE_NBUF_TN");
-      const int nb = ne ? atoi(ne) : 4;
-      if (nb == 3) hipLaunchKernelGGL((gemm_tn_bf16_kernel<3, 4, true>), grid, dim3(512), 3 * 32768, st, p);
-      else if (nb == 5) {
-        static bool a5 = false;
-        if (!a5) { MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_bf16_kernel<5, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); a5 = true; }
-        hipLaunchKernelGGL((gemm_tn_bf16_kernel<5, 4, true>), grid, dim3(512), 5 * 32768, st, p);
-      } else hipLaunchKernelGGL((gemm_tn_bf16_kernel<4, 4, true>), grid, dim3(512), 4 * 32768, st, p);
-    }
-  } else {
-    if (pl.bm == 256) hipLaunchKernelGGL((gemm_tn_bf16_kernel<3, 8, false>), grid, dim3(256), 3 * (32768 + 16384), st, p);   // 144 KiB ring
-    else hipLaunchKernelGGL((gemm_tn_bf16_kernel<4, 4, false>), grid, dim3(256), 4 * 32768, st, p);
-  }
+  else if (pl.bm == 256) hipLaunchKernelGGL((gemm_tn_bf16_kernel<3, 8>), grid, dim3(512), 3 * (32768 + 16384), st, p);   // 144 KiB ring
+  else hipLaunchKernelGGL((gemm_tn_bf16_kernel<4, 4>), grid, dim3(512), 4 * 32768, st, p);
   MVAE_CHECK_HIP(hipGetLastError());
   if (pl.splits > 1) {
     long n = (long)M * N;

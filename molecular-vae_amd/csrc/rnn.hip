@@ -368,7 +368,7 @@ __global__ __launch_bounds__(WS ? 512 : 256) void lstm_step_fwd_kernel(StepArgsF
 // WS (32-unit tiles only): 512 threads, waves 4-7 only issue the LDS-DMA pieces (tile_gemm_ws).  The small-batch tile's K-step is 16
 // MFMAs per wave against 6 DMA pieces of 60-180 issue cycles each: with every wave doing both jobs the pieces, not the MFMAs, set the pace
 // (~950 cycles per K-step for 256 cycles of MFMA at b = 128).
-template <int BMW, int BNB, int NBUF, int MODE = 2, bool WS = false>
+template <int BMW, int BNB, int NBUF, bool WS = false>
 __global__ __launch_bounds__(WS ? 512 : BMW * 2) void lstm_step_fwd_gm_kernel(StepArgsF p) {
   using T = bf16_t;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -460,7 +460,7 @@ __global__ __launch_bounds__(WS ? 512 : BMW * 2) void lstm_step_fwd_gm_kernel(St
       if (q.A1 == nullptr) s1.nk = 0;
     }
     if constexpr (WS) tile_gemm_ws<T, BMW, BNB, MI, NI, NBUF, NI, 0>(smem, s0, s1, 0, wn * (16 * NI), acc, tid);
-    else tile_gemm_pipe_all<T, BMW, BNB, MI, NI, NBUF, NT, MODE>(smem, s0, s1, wm * 128, wn * (16 * NI), acc, tid);
+    else tile_gemm_pipe_all<T, BMW, BNB, MI, NI, NBUF, NT>(smem, s0, s1, wm * 128, wn * (16 * NI), acc, tid);
   }
   if constexpr (WS) { if (tid >= 256) return; }          // loader waves own no accumulators
 #ifdef MVAE_TUNING
@@ -562,7 +562,7 @@ struct StepTaskB {
   const uint8_t* dmask;               // [B, H] injected keep mask of this cell's OUTPUT (nullptr: hash)
   uint32_t didx0;
 };
-struct StepArgsB { StepTaskB t[MVAE_MAX_LAYERS]; const int* lengths; float* partial; int ntask, B, H, tiles_m, tiles_n, dbg, vec, cell, split, gru3, tailpref; DropArgs drop; };
+struct StepArgsB { StepTaskB t[MVAE_MAX_LAYERS]; const int* lengths; float* partial; int ntask, B, H, tiles_m, tiles_n, dbg, vec, cell, split, gru3; DropArgs drop; };
 
 // Gate-derivative math of one (batch row, 8 hidden units) group, given dh = sum of the two contractions (fp32): the general form (any n,
 // scalar or vector accesses, operands requested where they are used).  The element-wise launch of the split forms and ragged tiles use it.
@@ -915,7 +915,7 @@ __global__ __launch_bounds__(WS ? 512 : 256) void lstm_step_bwd_kernel(StepArgsB
       // LSTM cells (a fixed number of operand loads per group): the loads go out BEHIND the last ring stage -- in front of the first they
       // delayed the whole main loop by their HBM latency (6 us of the launch, tune build) -- and land under the last three K-steps
       constexpr int NTAIL = NIT * (HAS_DY ? 10 : 8);
-      const bool tail_form = p.cell == MVAE_CELL_LSTM && nk >= NBUF && run_main && p.tailpref;
+      const bool tail_form = p.cell == MVAE_CELL_LSTM && nk >= NBUF && run_main;
       if (tail_form) {
         tile_gemm_ws_loader_tail<T, BM, BN, NBUF, NTAIL>(smem, s0, s1, wv - 4, [&]() {
 #pragma unroll
@@ -1165,7 +1165,7 @@ __global__ __launch_bounds__(256) void lstm_bwd_epi_kernel(StepArgsB p) {
   } while (0)
 
 // Schedule knobs (read per call; every setting computes the same results -- the GPU tests force each tile variant through them):
-// MVAE_NBUF_FWD / MVAE_NBUF_BWD = LDS ring depth, MVAE_BM / MVAE_BJ = tile, MVAE_BWD_SPLIT, MVAE_ROWRES.  MVAE_DBG (skip parts of a
+// MVAE_NBUF_FWD / MVAE_NBUF_BWD = LDS ring depth, MVAE_BM / MVAE_BJ / MVAE_FWD_GM = tile, MVAE_BWD_SPLIT.  MVAE_DBG (skip parts of a
 // kernel, results WRONG) exists only in the diagnostic build (-DMVAE_TUNING); the product library ignores it.
 static int tune_int(const char* name, int dflt) {
   const char* v = mvae_knob(name);
@@ -1210,12 +1210,12 @@ int rnn_fwd_impl(const mvae_rnn_fwd_desc* d, hipStream_t st) {
     for (int l = 0; l + 1 < NL; ++l) if (!d->hdrop[l]) return MVAE_ERR_INVALID;
   }
   // narrow f32 stacks (the encoder): row-resident schedule, one launch per layer instead of one per wavefront step
-  if (!drop && tune_int("MVAE_ROWRES", 1)) {
+  if (!drop) {
     const int rc = rnn_rowres_fwd(d, st);
     if (rc != MVAE_ERR_UNSUPPORTED) return rc;
   }
   // one-layer bf16 GRU(256) over a token table (the MOSES encoder): row-resident as well, ONE launch for the whole sequence
-  if (!drop && tune_int("MVAE_GRU_ROWRES", 1)) {
+  if (!drop) {
     const int rc = rnn_gru_rowres_fwd(d, st);
     if (rc != MVAE_ERR_UNSUPPORTED) return rc;
   }
@@ -1276,7 +1276,7 @@ int rnn_fwd_impl(const mvae_rnn_fwd_desc* d, hipStream_t st) {
   a.drop.scale = drop ? 1.f / (1.f - d->drop_p) : 1.f;
   a.drop.thresh = drop ? (uint32_t)((double)d->drop_p * 4294967296.0) : 0u;
   a.drop.seed = d->drop_seed;
-  a.gru3 = (gru && tune_int("MVAE_GRU3", 1)) ? 1 : 0;       // GRU: never fetch the zero gate-slot block of either segment
+  a.gru3 = gru ? 1 : 0;       // GRU: never fetch the zero gate-slot block of either segment
 #ifdef MVAE_TUNING
   a.dbg = tune_int("MVAE_DBG", 0);
 #else
@@ -1333,21 +1333,11 @@ int rnn_fwd_impl(const mvae_rnn_fwd_desc* d, hipStream_t st) {
       block = dim3(BMW * 2);
       if (BMW == 256 && BNB == 256) {
         lds = 2 * (256 + 256) * KB;
-#ifdef MVAE_TUNING
-        const int mode = tune_int("MVAE_GM_MODE", 2);
-        if (mode == 0) { MVAE_STEP_LAUNCH((lstm_step_fwd_gm_kernel<256, 256, 2, 0>)); continue; }
-        if (mode == 1) { MVAE_STEP_LAUNCH((lstm_step_fwd_gm_kernel<256, 256, 2, 1>)); continue; }
-        if (mode == 3) { MVAE_STEP_LAUNCH((lstm_step_fwd_gm_kernel<256, 256, 2, 3>)); continue; }
-#endif
         MVAE_STEP_LAUNCH((lstm_step_fwd_gm_kernel<256, 256, 2>));
       }
       else if (BMW == 256) { lds = 3 * (256 + 128) * KB; MVAE_STEP_LAUNCH((lstm_step_fwd_gm_kernel<256, 128, 3>)); }
       else if (BNB == 128) { lds = 4 * (128 + 128) * KB; MVAE_STEP_LAUNCH((lstm_step_fwd_gm_kernel<128, 128, 4>)); }
-      else {
-        lds = 4 * (128 + 64) * KB;
-        if (tune_int("MVAE_FWD_GM_WS", 1)) { block = dim3(512); MVAE_STEP_LAUNCH((lstm_step_fwd_gm_kernel<128, 64, 4, 2, true>)); }
-        else MVAE_STEP_LAUNCH((lstm_step_fwd_gm_kernel<128, 64, 4>));
-      }
+      else { lds = 4 * (128 + 64) * KB; block = dim3(512); MVAE_STEP_LAUNCH((lstm_step_fwd_gm_kernel<128, 64, 4, true>)); }
       continue;
     }
 #define FWD_CASE(TT_, BM_, NB_) if (BJ == 32 && BM == BM_ && nbuf == NB_) { MVAE_STEP_LAUNCH((lstm_step_fwd_kernel<TT_, BM_, 32, NB_>)); continue; }
@@ -1402,11 +1392,11 @@ int rnn_bwd_impl(const mvae_rnn_bwd_desc* d, hipStream_t st) {
   if (ldg < 4L * H || ldg % epc) return MVAE_ERR_INVALID;
   const bool drop = d->drop_p > 0.f;
   if (drop && d->drop_p >= 1.f) return MVAE_ERR_INVALID;
-  if (!drop && tune_int("MVAE_ROWRES", 1)) {
+  if (!drop) {
     const int rc = rnn_rowres_bwd(d, st);
     if (rc != MVAE_ERR_UNSUPPORTED) return rc;
   }
-  if (!drop && tune_int("MVAE_GRU_ROWRES", 1)) {             // one-layer bf16 GRU(256): row-resident, one launch (rnn_rowres.hip)
+  if (!drop) {                                               // one-layer bf16 GRU(256): row-resident, one launch (rnn_rowres.hip)
     const int rc = rnn_gru_rowres_bwd(d, st);
     if (rc != MVAE_ERR_UNSUPPORTED) return rc;
   }
@@ -1445,12 +1435,11 @@ int rnn_bwd_impl(const mvae_rnn_bwd_desc* d, hipStream_t st) {
     // (128 x 64, 1) = the same fused kernel on half-width tiles: B = 512 at 4 x 1024 is 256 of them -- one launch of 3 MB per CU instead of the
     // (128 x 128, 2) GEMM + element-wise pair (MVAE_BWD_SPLIT=641 forces it)
     // (256 x 128, 1) = the fused kernel on 256-row tiles (a quarter fewer operand bytes and LDS reads per FLOP than 128 x 128): only where it
-    // still gives a workgroup per CU -- B >= 2048 at 4 x 1024 (BASELINE configs[4]); MVAE_BWD_SPLIT=2561 forces it (tests), MVAE_BWD_256=0 keeps it out
+    // still gives a workgroup per CU -- B >= 2048 at 4 x 1024 (BASELINE configs[4]); MVAE_BWD_SPLIT=2561 forces it (tests)
     static const Cand cand[7] = {{256, 128, 1, 2561}, {128, 128, 1, 1281}, {128, 64, 1, 641}, {256, 128, 2, 2562}, {128, 128, 2, 2}, {128, 128, 4, 1284}, {128, 64, 4, 644}};
     for (int c = 0; c < 7 && !nsplit; ++c) {
       if (B % cand[c].bm || (cand[c].ns == 4 && (4 * H) % (2 * ke))) continue;
       if (drop && cand[c].ns == 1) continue;      // the unsplit wave-specialised instantiation carries no dropout factor (DROP = false): never with a mask
-      if (cand[c].key == 2561 && split_knob != 2561 && !tune_int("MVAE_BWD_256", 1)) continue;
       const long wgs = (long)(B / cand[c].bm) * (H / cand[c].bn) * cand[c].ns * NL;
       if (split_knob == cand[c].key || (split_knob == 1 && wgs >= (cand[c].ns == 1 ? 256 : 192))) { BM = cand[c].bm; BN = cand[c].bn; nsplit = cand[c].ns; }
     }
@@ -1462,7 +1451,7 @@ int rnn_bwd_impl(const mvae_rnn_bwd_desc* d, hipStream_t st) {
     // B = 512 5.58 -> 5.10 ms / step (B <= 256: 4.43 vs 4.48, the split pair stays); 4 x 1024 (8H = 8192 columns, 2 MB per tile) never.
     if (split_knob == 1 && nsplit > 1) {
       const long fused_tiles = (long)((B + 63) / 64) * ((H + 63) / 64) * NL;
-      const long kcols = (gru && tune_int("MVAE_GRU3", 1) ? 6L : 8L) * H;
+      const long kcols = (gru ? 6L : 8L) * H;
       if (fused_tiles >= 192 && 128 * kcols * sz <= (1L << 20)) { nsplit = 0; BM = 64; BN = 64; }
       // A ONE-layer stack (the MOSES encoder GRU(256)): a cell is a few hundred KB of operands either way, and every time step of the
       // split form is two dependent launches (GEMM + element-wise) of ~7 us each, i.e. launch latency twice: the fused single launch wins
@@ -1480,8 +1469,7 @@ int rnn_bwd_impl(const mvae_rnn_bwd_desc* d, hipStream_t st) {
   a.drop.seed = d->drop_seed;
   // GRU: skip the zero gate-slot block of each contraction (k in [2H,3H) of dG . W_hh^T, k >= 3H of dG_up . W_ih^T); the skipped ranges
   // must start on whole K-steps (and the 4-way split's half of 3H as well)
-  a.tailpref = tune_int("MVAE_BWD_TAILPREF", 1);      // fused prefetching form: the loader waves' operand loads behind the last ring stage (A/B knob)
-  a.gru3 = (gru && tune_int("MVAE_GRU3", 1) && H % ke == 0 && (nsplit != 4 || (3 * H / 2) % ke == 0)) ? 1 : 0;
+  a.gru3 = (gru && H % ke == 0 && (nsplit != 4 || (3 * H / 2) % ke == 0)) ? 1 : 0;
   a.B = B; a.H = H; a.tiles_m = (B + BM - 1) / BM; a.tiles_n = (H + BN - 1) / BN; a.vec = vec ? 1 : 0;
 #ifdef MVAE_TUNING
   a.dbg = tune_int("MVAE_DBG", 0);
@@ -1489,7 +1477,6 @@ int rnn_bwd_impl(const mvae_rnn_bwd_desc* d, hipStream_t st) {
   a.dbg = 0;
 #endif
   const int nbuf = pipe ? (drop ? 4 : tune_int("MVAE_NBUF_BWD", 4)) : 0;
-  const bool ws = tune_int("MVAE_WS_BWD", 1) != 0;      // loader / consumer wave specialisation of the split-mode GEMM kernel
   size_t lds = (size_t)(split ? (BM == 256 ? 3 : 4) : big_fused ? (BM == 256 ? 3 : 4) : (nbuf > 0 ? nbuf : 2)) * (BM + BN) * KB;
   const size_t stage_bytes = (size_t)BM * (BN + 4) * sizeof(float);
   if (lds < stage_bytes) lds = stage_bytes;
@@ -1542,7 +1529,6 @@ int rnn_bwd_impl(const mvae_rnn_bwd_desc* d, hipStream_t st) {
     if (big_fused && drop) return MVAE_ERR_UNSUPPORTED;      // (excluded above; an unhandled combination must never run silently)
     if (big_fused) {
       block = dim3(512);
-      const int pref = tune_int("MVAE_BWD_PREF", 1);           // 0: the round-2 form (operands requested inside the epilogue), A/B knob
       if (BM == 256) {              // (the round-2 form of the fused epilogue: the prefetching forms are written out for a ring of four)
         MVAE_STEP_LAUNCH((lstm_step_bwd_kernel<bf16_t, 256, 128, 3, true, false, 0>));
         continue;
@@ -1552,16 +1538,14 @@ int rnn_bwd_impl(const mvae_rnn_bwd_desc* d, hipStream_t st) {
         else MVAE_STEP_LAUNCH((lstm_step_bwd_kernel<bf16_t, 128, 64, 4, true, false, 0, 2>));
         continue;
       }
-      if (!pref) MVAE_STEP_LAUNCH((lstm_step_bwd_kernel<bf16_t, 128, 128, 4, true, false, 0>));
-      else if (d->dy) MVAE_STEP_LAUNCH((lstm_step_bwd_kernel<bf16_t, 128, 128, 4, true, false, 0, 1>));
+      if (d->dy) MVAE_STEP_LAUNCH((lstm_step_bwd_kernel<bf16_t, 128, 128, 4, true, false, 0, 1>));
       else MVAE_STEP_LAUNCH((lstm_step_bwd_kernel<bf16_t, 128, 128, 4, true, false, 0, 2>));
       continue;
     }
     if (split) {
       if (BM == 256) { block = dim3(512); MVAE_STEP_LAUNCH((lstm_step_bwd_kernel<bf16_t, 256, 128, 3, true, false, 1>)); block = dim3(256); }
       else if (BN == 64) { block = dim3(512); MVAE_STEP_LAUNCH((lstm_step_bwd_kernel<bf16_t, 128, 64, 4, true, false, 1>)); block = dim3(256); }
-      else if (ws) { block = dim3(512); MVAE_STEP_LAUNCH((lstm_step_bwd_kernel<bf16_t, 128, 128, 4, true, false, 1>)); block = dim3(256); }
-      else MVAE_STEP_LAUNCH((lstm_step_bwd_kernel<bf16_t, 128, 128, 4, false, false, 1>));
+      else { block = dim3(512); MVAE_STEP_LAUNCH((lstm_step_bwd_kernel<bf16_t, 128, 128, 4, true, false, 1>)); block = dim3(256); }
       const long groups = (long)n * B * (H / 8);
       hipLaunchKernelGGL((lstm_bwd_epi_kernel<bf16_t>), dim3((unsigned)((groups + 255) / 256)), block, 0, st, a);
       continue;

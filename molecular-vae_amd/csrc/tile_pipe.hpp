@@ -223,31 +223,6 @@ __device__ __forceinline__ void tile_gemm_pipe(char* smem, const PipeSeg<BM, BN>
 }
 
 
-// Pieces [LO, HI) of the LPS = (BM + BN) * 8 / NT LDS-DMA pieces a thread issues per stage (A pieces first).
-template <int BM, int BN, int NBUF, int NT, int LO, int HI>
-__device__ __forceinline__ void pipe_issue_part(char* smem, const PipeSeg<BM, BN, NT>& s0, const PipeSeg<BM, BN, NT>& s1, int st, int wave) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  constexpr int NA = BM * 8 / NT, NB = BN * 8 / NT;
-  char* stage = smem + (st % NBUF) * ((BM + BN) * KB);
-  const bool first = st < s0.nk;
-  const PipeSeg<BM, BN, NT>& s = first ? s0 : s1;
-  const int ls = first ? st : st - s0.nk;
-  const uint32_t kbyte = (uint32_t)ls * KB + (ls >= s.hole_st ? s.hole_bytes : 0u);
-#pragma unroll
-  for (int i = 0; i < NA; ++i) {
-    if (i < LO || i >= HI) continue;
-    lds_void_t* dst = (lds_void_t*)(stage + (i * NT + wave * 64) * 16);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(s.ra, dst, 16, s.offA[i] + kbyte, 0, 0, 0);
-  }
-#pragma unroll
-  for (int i = 0; i < NB; ++i) {
-    if (NA + i < LO || NA + i >= HI) continue;
-    lds_void_t* dst = (lds_void_t*)(stage + BM * KB + (i * NT + wave * 64) * 16);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(s.rb, dst, 16, s.offB[i] + kbyte, 0, 0, 0);
-  }
-#endif
-}
-
 __device__ __forceinline__ void SB() { __builtin_amdgcn_sched_barrier(0); }     // pins the DMA / MFMA interleave as written
 
 // MFMAs of fragment rows [M0, M1) of one K-half
@@ -269,45 +244,20 @@ __device__ __forceinline__ void mma_rows(const u32x4 (&a)[MI], const u32x4 (&b)[
 //   holds everything it needs of stage kt-1 in registers -> stage kt is readable, the buffer of stage kt-1 is free and is refilled with
 //   stage kt+NBUF-1.
 // The refill's DMA pieces cost their issuing wave ~100 cycles each, during which it issues no MFMA, and the two waves of a SIMD run
-// this loop in lockstep (same barrier).  So (MODE bit 0) the pieces are spread over the rows of an MFMA block instead of issued as one
-// burst, and (MODE bit 1) they are STAGGERED between the SIMD partners: waves 0..NT/128-1 interleave them with block 3 right behind the
-// barrier, the other half of the waves with block 0 of the NEXT K-step -- while one partner issues DMA the other issues MFMAs.  (The
-// counted vmcnt is the same for both: the deferred pieces are issued before the next wait.)
+// this loop in lockstep (same barrier).  So at NT = 512 the pieces are STAGGERED between the SIMD partners: waves 0..NT/128-1 issue them
+// beside block 3 right behind the barrier, the other half of the waves beside block 0 of the NEXT K-step -- while one partner issues DMA
+// the other issues MFMAs.  (The counted vmcnt is the same for both: the deferred pieces are issued before the next wait.)
 // One MFMA block (fragment rows M0 .. M0+GA-1 of one K-half) with the refill of stage `st` issued beside it when `refill` (wave-uniform)
 // is set.  Only the DMA issue sits under the branch, never an MFMA: the accumulators stay in one straight-line live range.
-template <typename T, int BM, int BN, int NBUF, int NT, int MI, int NI, int GA, bool SPREAD, int M0>
+template <typename T, int BM, int BN, int NBUF, int NT, int MI, int NI, int GA, int M0>
 __device__ __forceinline__ void pipe_block_with_refill(char* smem, const PipeSeg<BM, BN, NT>& s0, const PipeSeg<BM, BN, NT>& s1, bool refill, int st,
                                                        int wave, const u32x4 (&a)[GA], const u32x4 (&b)[NI], f32x4 (&acc)[MI][NI]) {
-  constexpr int LPS = (BM + BN) * 8 / NT;
-  if constexpr (SPREAD && GA == 4 && LPS % 4 == 0) {
-    constexpr int Q = LPS / 4;
-    if (refill) pipe_issue_part<BM, BN, NBUF, NT, 0, Q>(smem, s0, s1, st, wave);
-    SB();
+  if (refill) pipe_issue_stage<BM, BN, NBUF, NT>(smem, s0, s1, st, wave);
+  SB();
 #pragma unroll
-    for (int ni = 0; ni < NI; ++ni) mma16<T>(__builtin_bit_cast(uint4, a[0]), __builtin_bit_cast(uint4, b[ni]), acc[M0 + 0][ni]);
-    SB();
-    if (refill) pipe_issue_part<BM, BN, NBUF, NT, Q, 2 * Q>(smem, s0, s1, st, wave);
-    SB();
+  for (int r = 0; r < GA; ++r)
 #pragma unroll
-    for (int ni = 0; ni < NI; ++ni) mma16<T>(__builtin_bit_cast(uint4, a[1]), __builtin_bit_cast(uint4, b[ni]), acc[M0 + 1][ni]);
-    SB();
-    if (refill) pipe_issue_part<BM, BN, NBUF, NT, 2 * Q, 3 * Q>(smem, s0, s1, st, wave);
-    SB();
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni) mma16<T>(__builtin_bit_cast(uint4, a[2]), __builtin_bit_cast(uint4, b[ni]), acc[M0 + 2][ni]);
-    SB();
-    if (refill) pipe_issue_part<BM, BN, NBUF, NT, 3 * Q, LPS>(smem, s0, s1, st, wave);
-    SB();
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni) mma16<T>(__builtin_bit_cast(uint4, a[3]), __builtin_bit_cast(uint4, b[ni]), acc[M0 + 3][ni]);
-  } else {
-    if (refill) pipe_issue_stage<BM, BN, NBUF, NT>(smem, s0, s1, st, wave);
-    SB();
-#pragma unroll
-    for (int r = 0; r < GA; ++r)
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni) mma16<T>(__builtin_bit_cast(uint4, a[r]), __builtin_bit_cast(uint4, b[ni]), acc[M0 + r][ni]);
-  }
+    for (int ni = 0; ni < NI; ++ni) mma16<T>(__builtin_bit_cast(uint4, a[r]), __builtin_bit_cast(uint4, b[ni]), acc[M0 + r][ni]);
 }
 template <typename T, int MI, int NI, int GA, int M0>
 __device__ __forceinline__ void pipe_block(const u32x4 (&a)[GA], const u32x4 (&b)[NI], f32x4 (&acc)[MI][NI]) {
@@ -317,13 +267,13 @@ __device__ __forceinline__ void pipe_block(const u32x4 (&a)[GA], const u32x4 (&b
     for (int ni = 0; ni < NI; ++ni) mma16<T>(__builtin_bit_cast(uint4, a[r]), __builtin_bit_cast(uint4, b[ni]), acc[M0 + r][ni]);
 }
 
-template <typename T, int BM, int BN, int MI, int NI, int NBUF, int NT, int MODE = 3>
+template <typename T, int BM, int BN, int MI, int NI, int NBUF, int NT>
 __device__ __forceinline__ void tile_gemm_pipe_all(char* smem, const PipeSeg<BM, BN, NT>& s0, const PipeSeg<BM, BN, NT>& s1, int arow0,
                                                    int brow0, f32x4 (&acc)[MI][NI], int tid) {
   constexpr int STAGE = (BM + BN) * KB;
   constexpr int LPS = (BM + BN) * 8 / NT;
   constexpr int GA = MI / 2;
-  constexpr bool SPREAD = (MODE & 1) != 0, STAGGER = (MODE & 2) != 0 && NT == 512;
+  constexpr bool STAGGER = NT == 512;
   static_assert(MI % 2 == 0 && NBUF >= 2 && (NBUF - 2) * LPS < 64, "vmcnt range");
   static_assert(GA + NI <= 15, "lgkmcnt range");
   static_assert(BM * 8 % NT == 0 && BN * 8 % NT == 0, "whole LDS-DMA pieces per thread");
@@ -357,7 +307,7 @@ __device__ __forceinline__ void tile_gemm_pipe_all(char* smem, const PipeSeg<BM,
     FragReadB<0, NI, NI, 0>::run(bh1, st + b_lane[1]);                   // (h1)
     wait_lgkmcnt<GA + NI>();                                              // aX, bh0 arrived
     if constexpr (STAGGER) {                                              // block 0 (+ the staggered waves' refill)
-      pipe_block_with_refill<T, BM, BN, NBUF, NT, MI, NI, GA, SPREAD, 0>(smem, s0, s1, late && pend >= 0, pend, wave, aX, bh0, acc);
+      pipe_block_with_refill<T, BM, BN, NBUF, NT, MI, NI, GA, 0>(smem, s0, s1, late && pend >= 0, pend, wave, aX, bh0, acc);
       if (late) pend = -1;
     } else pipe_block<T, MI, NI, GA, 0>(aX, bh0, acc);
     SB();
@@ -377,7 +327,7 @@ __device__ __forceinline__ void tile_gemm_pipe_all(char* smem, const PipeSeg<BM,
       FragRead<0, GA, 16 * KB>::run(aX, sn + a_lane[0]);
       FragReadB<0, NI, NI, 0>::run(bh0, sn + b_lane[0]);
     }
-    pipe_block_with_refill<T, BM, BN, NBUF, NT, MI, NI, GA, SPREAD, GA>(smem, s0, s1, !late && pend >= 0, pend, wave, aY, bh1, acc);   // block 3
+    pipe_block_with_refill<T, BM, BN, NBUF, NT, MI, NI, GA, GA>(smem, s0, s1, !late && pend >= 0, pend, wave, aY, bh1, acc);   // block 3
     if (!late) pend = -1;
     SB();
   }
@@ -475,55 +425,6 @@ template <int I, int N, int ROWB> struct FragReadTN {
 template <int N, int ROWB> struct FragReadTN<N, N, ROWB> {
   template <int KOFF> static __device__ __forceinline__ void run(u32x4 (&)[N], const uint32_t (&)[N], uint32_t) {}
 };
-
-// smem: NBUF * (4096*MI + 16384) bytes.
-template <int NBUF, int MI>
-__device__ __forceinline__ void tile_gemm_pipe_tn(char* smem, const PipeSegTN<MI>& s, int wm, int wn, f32x4 (&acc)[MI][4], int tid) {
-  constexpr int LPS = MI + 4;
-  constexpr int RA = 64 * MI, ABYTES = 64 * RA, STAGE = ABYTES + 16384;
-  static_assert((NBUF - 2) * LPS < 64, "vmcnt range");
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nk = s.nk;
-  if (nk <= 0) return;
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_void_t*)smem;
-  const int g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
-  const uint32_t f = (uint32_t)(q | ((g & 1) << 2));
-  uint32_t addrA[MI], addrB[4];
-#pragma unroll
-  for (int i = 0; i < MI; ++i) addrA[i] = (uint32_t)(8 * g + q) * (uint32_t)RA + ((((uint32_t)(wm * MI + i)) ^ f) << 5) + (uint32_t)pp * 8u;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) addrB[i] = (uint32_t)(8 * g + q) * 256u + ((((uint32_t)(wn * 4 + i)) ^ f) << 5) + (uint32_t)pp * 8u + (uint32_t)ABYTES;
-#pragma unroll
-  for (int st = 0; st < NBUF - 1; ++st)
-    if (st < nk) pipe_tn_issue<NBUF, MI>(smem, s, st, wave);
-  for (int kt = 0; kt < nk; ++kt) {
-    if (kt + NBUF - 2 < nk) wait_vmcnt<(NBUF - 2) * LPS>();
-    else wait_vmcnt<0>();
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (kt + NBUF - 1 < nk) pipe_tn_issue<NBUF, MI>(smem, s, kt + NBUF - 1, wave);
-    const uint32_t st = lds0 + (uint32_t)((kt % NBUF) * STAGE);
-    u32x4 a0[MI], b0[4], a1[MI], b1[4];
-    FragReadTN<0, MI, RA>::template run<0>(a0, addrA, st);          // k rows 0..31 of the stage
-    FragReadTN<0, 4, 256>::template run<0>(b0, addrB, st);
-    wait_lgkmcnt<0>();
-    FragReadTN<0, MI, RA>::template run<32 * RA>(a1, addrA, st);    // k rows 32..63: in flight under the first MFMAs
-    FragReadTN<0, 4, 256>::template run<32 * 256>(b1, addrB, st);
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-        mma16<bf16_t>(__builtin_bit_cast(uint4, a0[mi]), __builtin_bit_cast(uint4, b0[ni]), acc[mi][ni]);
-    wait_lgkmcnt<0>();
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-        mma16<bf16_t>(__builtin_bit_cast(uint4, a1[mi]), __builtin_bit_cast(uint4, b1[ni]), acc[mi][ni]);
-  }
-  __builtin_amdgcn_s_barrier();
-}
 
 // =====================================================================================================================
 // Wave-specialised main loops (512-thread workgroups): waves 0-3 are CONSUMERS (fragment reads + MFMA only), waves 4-7 are

@@ -246,9 +246,8 @@ def _params_key(params):
     return (L.PARAM_EPOCH[0],) + tuple((p.data_ptr(), p._version) for p in params)
 
 
-DW_KSPLIT = "1"      # K-chunks of the grouped decoder weight-gradient launches (see _lstm_weight_grads)
-WGRAD_CAPS_BIG = "0:0"   # workgroup caps of the two parts of the large-batch schedule (0: one workgroup per tile)
-WGRAD_CAP = "160"      # workgroups of the grouped weight-gradient launches at small per-GPU batches (0: one per tile, released next to the encoder LSTM backward)
+WGRAD_LATE_TB = 32768   # T*B up to which every weight-gradient launch is released late, next to the encoder LSTM backward
+WGRAD_CAP = 160         # workgroups of those late grouped weight-gradient launches
 
 
 def _lstm_weight_grads(ws, grads, prefix, dt, dev, NL, Lq, B, H, dG, ldg, hs, ldh, layers=None, max_workgroups=0, batch=None):
@@ -261,13 +260,10 @@ def _lstm_weight_grads(ws, grads, prefix, dt, dev, NL, Lq, B, H, dG, ldg, hs, ld
     # accumulate -- the grouped full-K kernel then serves them too (round 5; before, that size fell back to one split-K GEMM per matrix: 0.81 PFLOP/s)
     ks_auto = max(1, -(-(TB * max(ldg, ldh) * 2) // ((1 << 31) - (1 << 24))))
     k_chunk = TB - B if ks_auto == 1 else ((TB // ks_auto + B - 1) // B) * B
-    if dt == torch.bfloat16 and Lq > 1 and ops.gemm_tn_grouped_supported(dG[0], G4, H, k_chunk, ldg, ldh) and H == 1024 and L.knob("MVAE_DW_GROUPED", "1") != "0":
+    if dt == torch.bfloat16 and Lq > 1 and ops.gemm_tn_grouped_supported(dG[0], G4, H, k_chunk, ldg, ldh) and H == 1024:
         # ONE grouped launch for every dW_ih / dW_hh of the requested layers (64 tiles of 256 x 256 each, accumulated over the full K = T*B in
         # registers: no split-K slabs, no reduction launch); the bias gradient (column sums of dG) rides along one GEMM per layer.
-        # K-chunks (MVAE_DW_KSPLIT, default 1): the same tiles as `ks` shorter launches that accumulate -- a 256 x 256 tile owns its CU for
-        # its whole K (3.1 ms at B = 1024), so shorter launches give the dispatcher points at which the other stream's kernels get CUs
-        ks = max(ks_auto, int(L.knob("MVAE_DW_KSPLIT", DW_KSPLIT)))
-        step = ((TB // ks + B - 1) // B) * B if ks > 1 else TB            # whole time steps per chunk
+        step = k_chunk if ks_auto > 1 else TB                             # whole time steps per chunk
         for k0 in range(0, TB, step):
             k1 = min(TB, k0 + step)
             first = k0 == 0
@@ -624,9 +620,8 @@ class _EncoderFn(torch.autograd.Function):
         # left on the way are the input-gradient chain.  MVAE_ENC_DW_BATCH=0: one launch each, where it stands (A/B, tests).
         # (measured, ms per step: b = 128 5.47 -> 5.35, B = 512 17.14 -> 16.99; B = 1024 28.28 -> 28.66 -- there each of these GEMMs is big enough to
         # fill its launch and, issued where it stands, runs under the decoder's weight-gradient launches instead of behind the LSTM backward)
-        bmode = L.knob("MVAE_ENC_DW_BATCH", "1" if B * Lq <= 65536 else "0")      # "2": only the LSTM stack's products + the table gradient (the tail)
-        lstm_batch = ops.TnF32Batch(dev) if bmode != "0" else None
-        batch = lstm_batch if bmode == "1" else None
+        bmode = L.knob("MVAE_ENC_DW_BATCH", "1" if B * Lq <= 65536 else "0")
+        batch = ops.TnF32Batch(dev) if bmode != "0" else None
         for k, nm in enumerate(("lmbd.z_mean", "lmbd.z_log_var")):
             if batch is not None:
                 batch.add(dmulv[:, k * o:(k + 1) * o], d, grads[nm + ".weight"], o, 512, B, lda=2 * o, ldb=512, colsum_out=grads[nm + ".bias"])
@@ -658,8 +653,8 @@ class _EncoderFn(torch.autograd.Function):
         x1, y1, y2, y3 = W("x1", (B * Hp, L1)), W("y1", (B * W1, O1)), W("y2", (B * W2, O2)), W("y3", (B * W3, C3))
         dy2, dy1, dx1 = W("dy2", (B * W2, O2)), W("dy1", (B * W1, O1)), W("dx1", (B * H, L1))
         dzp3, dzp2, dzp1 = W("dzp3", (B * (W3 + 2 * k - 2), C3)), W("dzp2", (B * (W2 + 2 * k - 2), O2)), W("dzp1", (B * (W1 + 2 * k - 2), O1))
-        # bf16 training mode: input-gradient GEMMs as 3 x bf16 products (forward conv stays exact fp32); MVAE_CONV_X3=0: A/B knob
-        x3 = bool(mod.fast_grad_gemms) and L.knob("MVAE_CONV_X3", "1") != "0"
+        # bf16 training mode: input-gradient GEMMs as 3 x bf16 products (forward conv stays exact fp32)
+        x3 = bool(mod.fast_grad_gemms)
         for (n, Wi, Ci, ldx_, xbs, Co, ldo_, dy_, y_, x_, dzp_, dx_, lddx_) in (
                 ("3", W2, c3.in_channels, O2, W2 * O2, C3, C3, dy3, y3, y2, dzp3, dy2, O2),
                 ("2", W1, c2.in_channels, O1, W1 * O1, c2.out_channels, O2, dy2, y2, y1, dzp2, dy1, O1),
@@ -681,7 +676,6 @@ class _EncoderFn(torch.autograd.Function):
         fork.run_deferred(1)      # the decoder's remaining weight-gradient GEMMs: they fill the CUs the row-resident backward leaves idle
         ops.rnn_bwd(L.CELL_LSTM, f32, Lq, B, H, P["WhhT"], [G4] * NL, P["WihT"], [G4] * NL, dhs, H, hs, Hp, cs, gates,
                     dG, dstate, tag="enc_lstm_bwd", poison=L.grad_poison(params))
-        batch = lstm_batch
         _lstm_weight_grads(ws, grads, "gru", f32, dev, NL, Lq, B, H, dG, G4, hs, Hp, batch=batch)
         # K1 backward: table gradient, then embedding / W_ih0
         dtbl = W("dtbl", (Cv, G4))
@@ -913,9 +907,9 @@ def _decoder_bwd_tail(ctx, fill_dl):
     # two parts (upper layers + head, lower layers) where the peer releases them at two points of its backward; ONE part at the small per-GPU
     # batches whose GEMMs are released at once on a capped grid (round 5, b = 128: 5.50 -> 5.37 ms per step with 160 workgroups -- the gap
     # between two grouped launches, ~0.1 ms of bias / column-sum launches, closes, and the main stream keeps 96 compute units)
-    nlow = min(int(L.knob("MVAE_DEFER_LAYERS", "0" if TB <= int(L.knob("MVAE_WGRAD_LATE_TB", 32768)) else "2")), NL - 1)
-    per_layer = L.knob("MVAE_WGRAD_PER_LAYER", "1" if dp_early else "0") == "1"
-    if per_layer:
+    late_all = TB <= WGRAD_LATE_TB
+    nlow = 0 if late_all else min(2, NL - 1)
+    if dp_early:
         parts = [[l] for l in range(NL - 1, -1, -1)]
     else:
         parts = [list(range(nlow, NL))] + ([list(range(nlow))] if nlow >= 1 else [])
@@ -938,9 +932,7 @@ def _decoder_bwd_tail(ctx, fill_dl):
                     ops.gemm_nt(dlT, hsT, grads["decoded_mean.module.0.weight"], Cv, H, TB, lda=ldT, ldb=ldT)
                     ops.rowsum(dlT, Cv, TB, grads["decoded_mean.module.0.bias"])
             layers = range(NL) if k is None else parts[k]
-            caps_big = [int(c) for c in L.knob("MVAE_WGRAD_CAPS", WGRAD_CAPS_BIG).split(":")]       # per part, the two-part schedule of large batches
-            mw = wg_cap[0] if (wg_cap[0] or k is None) else caps_big[min(k, len(caps_big) - 1)]
-            _lstm_weight_grads(ws, grads, "gru", dt, dev, NL, Lq, B, H, dG, ldg, hs, ldh, layers=layers, max_workgroups=mw)
+            _lstm_weight_grads(ws, grads, "gru", dt, dev, NL, Lq, B, H, dG, ldg, hs, ldh, layers=layers, max_workgroups=wg_cap[0])
             if k is not None and dp_early:
                 # What this part produced is final on this stream: all-reduce it now -- [first parameter of its lowest layer, start of
                 # the previous part) (part 0: to the end of our range, i.e. with the head).  weight_ih_l0 / latent_input, produced on
@@ -966,19 +958,18 @@ def _decoder_bwd_tail(ctx, fill_dl):
         # first half of the parts: released by the peer after its head section; the rest next to its row-resident LSTM backward.  At small
         # per-GPU batches (K = T * B short: a group of GEMMs is a few hundred microseconds) EVERYTHING waits for that second point: released
         # earlier, the chip-filling 256 x 256 tiles only starve the peer's conv / dense backward (a 5 us bias column sum sat 308 us behind
-        # them at b = 128), while next to the 32-workgroup row-resident kernel (0.7 ms) they are hidden completely.
-        late_all = TB <= int(L.knob("MVAE_WGRAD_LATE_TB", 32768))      # round 3: b = 128 8.38 -> 8.22 ms / step, B = 256 +0.13; with the capped grid below B = 256 gains too (9.84 -> 9.72)
-        # ... or, at those batches, released AT ONCE but with a capped grid (mvae_gemm_tn_grouped_capped: `cap` workgroups looping over the
-        # tiles): the compute units left over serve the peer's dependent small launches without queueing behind chip-filling tiles
-        cap = int(L.knob("MVAE_WGRAD_CAP", WGRAD_CAP)) if late_all else 0
-        if cap > 0:
-            wg_cap[0] = cap
+        # them at b = 128), while next to the 32-workgroup row-resident kernel (0.7 ms) they are hidden completely (round 3: b = 128 8.38 ->
+        # 8.22 ms / step).  There they are released AT ONCE but with a capped grid (mvae_gemm_tn_grouped_capped: WGRAD_CAP workgroups looping
+        # over the tiles): the compute units left over serve the peer's dependent small launches without queueing behind chip-filling tiles
+        # (B = 256: 9.84 -> 9.72 ms / step)
+        if late_all:
+            wg_cap[0] = WGRAD_CAP
             for k in range(len(parts)):
                 fstate.park(side, (lambda kk=k: weight_grads(kk)), -1)
             fstate.run_deferred(stage=-1)
         else:
             for k in range(len(parts)):
-                fstate.park(side, (lambda kk=k: weight_grads(kk)), 1 if (late_all or 2 * k >= len(parts)) else 0)
+                fstate.park(side, (lambda kk=k: weight_grads(kk)), 1 if 2 * k >= len(parts) else 0)
     else:
         weight_grads(None)
     # layer-0 input is time-invariant: its gradient is the time sum of dG[0]
@@ -1088,7 +1079,7 @@ class MolecularVAE(nn.Module):
 
     def _encode(self, x, eps):
         ev = None
-        if x.is_cuda and self.prepack_decoder and L.knob("MVAE_PREPACK", "1") != "0":
+        if x.is_cuda and self.prepack_decoder:
             # the decoder's weight shadows (8 bf16 cast / transposes of 4096 x 1024) are independent of the encoder's forward: refresh them
             # on the side stream beside it (after everything issued so far: the optimiser update they read)
             side = self.decoder._side_stream(x.device)

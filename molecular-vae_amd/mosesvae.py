@@ -589,25 +589,17 @@ def _dec_backward(mod, ws, P, grads, x_pad, lengths, drop, drecon, dy_ext, dz_ex
             grads[f"decoder_rnn.bias_hh_l{l}"][:2 * Hd].copy_(s4[:2 * Hd]); grads[f"decoder_rnn.bias_hh_l{l}"][2 * Hd:].copy_(s4[3 * Hd:])
 
     def dec_weight_grads():
-        # the 3 x (dW_hh[r, z], dW_hh[n], dW_ih) contractions of the stack, one split-K TN GEMM each.  MVAE_MOSES_DW_GROUPED=1: ONE grouped launch of
-        # full-K 256 x 256 tiles instead (8 problems, 66 tiles) -- measured in round 5 and NOT kept: 5.46 vs 5.18 ms per step at B = 1024 (66
-        # workgroups with K = 62 k each run longer than the whole tail they sit beside; the chip-wide split-K launches finish sooner)
-        probs = []
+        # the 3 x (dW_hh[r, z], dW_hh[n], dW_ih) contractions of the stack, one split-K TN GEMM each (one grouped launch of full-K 256 x 256
+        # tiles measured slower in round 5: 5.46 vs 5.18 ms per step at B = 1024)
         for l in range(NL):
             a = dG_d[l].view(TB, ldg_d)
             hprev = hsx_d[l][:T].reshape(TB, ldh_d)                  # h_{t-1} for every t (slot 0 = h_0)
             gw = grads[f"decoder_rnn.weight_hh_l{l}"]
-            probs.append(dict(A=a, B=hprev, out=gw[:2 * Hd], M=2 * Hd, N=Hd, K=TB, lda=ldg_d, ldb=ldh_d, tag="dwhh_rz"))
-            probs.append(dict(A=a[:, 3 * Hd:], B=hprev, out=gw[2 * Hd:], M=Hd, N=Hd, K=TB, lda=ldg_d, ldb=ldh_d, tag="dwhh_n"))
+            _kmajor_gemm(ws, "dwhh_rz", a, ldg_d, 2 * Hd, hprev, ldh_d, Hd, TB, gw[:2 * Hd], dev)
+            _kmajor_gemm(ws, "dwhh_n", a[:, 3 * Hd:], ldg_d, Hd, hprev, ldh_d, Hd, TB, gw[2 * Hd:], dev)
             if l > 0:                                                 # the layer's input: the output of layer l-1 (after its dropout in train mode)
                 xin = hd[l - 1].view(TB, ldh_d) if hd is not None else hsx_d[l - 1][1:].reshape(TB, ldh_d)
-                probs.append(dict(A=a, B=xin, out=grads[f"decoder_rnn.weight_ih_l{l}"], M=3 * Hd, N=Hd, K=TB, lda=ldg_d, ldb=ldh_d, tag="dwih"))
-        if (L.knob("MVAE_MOSES_DW_GROUPED", "0") != "0" and dt == torch.bfloat16
-                and all(ops.gemm_tn_grouped_supported(q["A"], q["M"], q["N"], q["K"], q["lda"], q["ldb"]) for q in probs)):
-            ops.gemm_tn_grouped(probs)
-        else:
-            for q in probs:
-                _kmajor_gemm(ws, q["tag"], q["A"], q["lda"], q["M"], q["B"], q["ldb"], q["N"], q["K"], q["out"], dev)
+                _kmajor_gemm(ws, "dwih", a, ldg_d, 3 * Hd, xin, ldh_d, Hd, TB, grads[f"decoder_rnn.weight_ih_l{l}"], dev)
         # layer-0 input = [emb(x_t), z]: table gradient for the embedding part (the z part is on the path to the encoder: main stream)
         dtbl3 = W("dec_dtbl3", (V, 3 * Hd))
         if onehot is not None:
@@ -725,10 +717,6 @@ def _grad_views(mod, ws, names, params, dev):
     return grads
 
 
-def _fork_allowed(dy_ext):
-    return L.knob("MVAE_MOSES_FORK", "1") != "0" and dy_ext is None      # MVAE_MOSES_FORK=0: one stream (A/B knob)
-
-
 class _MosesFn(torch.autograd.Function):
     """mosesvae.VAE.forward (mosesvae.py:126-140): both halves in ONE autograd node."""
 
@@ -760,7 +748,7 @@ class _MosesFn(torch.autograd.Function):
         names = [n for n, _ in mod.named_parameters()]
         grads = _grad_views(mod, ws, names, params, dev)
         onehot = _onehot(mod, ws, x_pad)
-        dz_tot, finish = _dec_backward(mod, dws, P, grads, x_pad, lengths, drop, drecon, dy_ext, dz_ext, _fork_allowed(dy_ext), onehot)
+        dz_tot, finish = _dec_backward(mod, dws, P, grads, x_pad, lengths, drop, drecon, dy_ext, dz_ext, dy_ext is None, onehot)
         _enc_backward(mod, ws, P, grads, x_pad, lengths, eps, dz_tot, dkl, dlv_ext, onehot)
         finish()
         ge = grads["x_emb.weight"]; torch.add(grads["_dE_dec"], grads["_dE_enc"], out=ge)
@@ -825,7 +813,7 @@ class _MosesDecFn(torch.autograd.Function):
         names, params = mod._half_params("dec")
         grads = _grad_views(mod, ws, names, params, dev)
         onehot = _onehot(mod, ws, x_pad)
-        dz_tot, finish = _dec_backward(mod, ws, mod._packed, grads, x_pad, lengths, drop, drecon, dy_ext, None, _fork_allowed(dy_ext), onehot)
+        dz_tot, finish = _dec_backward(mod, ws, mod._packed, grads, x_pad, lengths, drop, drecon, dy_ext, None, dy_ext is None, onehot)
         finish()
         ge = grads["x_emb.weight"]; ge.copy_(grads["_dE_dec"])
         ge[mod.pad].zero_()

@@ -852,7 +852,7 @@ def rnn_fwd(cell, dtype, T, B, H, add0, add0_tstride, w_ih, ldw_ih, w_hh, ldw_hh
         if drop_mask is not None:
             _fill(d.drop_mask, drop_mask)
         d.drop_p, d.drop_seed = float(drop_p), int(drop_seed) & 0xFFFFFFFF
-    use_p = ((L.knob("MVAE_PERSIST", PERSIST_DEFAULT) != "0") if persist is None else bool(persist)) and not PERSIST_STATS["disabled"]
+    use_p = ((PERSIST_DEFAULT != "0") if persist is None else bool(persist)) and not PERSIST_STATS["disabled"]
     pws = None
     if use_p:
         persist_check()
