@@ -173,7 +173,8 @@ size_t mvae_scatter_rows_tb_workspace(int B, int L, int nrows, int W);
  * With it the scatter above is the TN contraction  dtable = out^T . d  (mvae_gemm_tn, M = nrows): the bf16 gradient sequence is read
  * once at GEMM streaming rate and summed in fp32 by the MFMAs. */
 int mvae_onehot_tb(const int64_t* idx, int B, int L, int nrows, void* out, int64_t ld, void* stream);
-/* fp32 form, rows in the order of idx itself: out[r, c] = (idx[r] == c) for r < n, c < ld (ld >= nrows, ld % 4 == 0).  The exact-f32 table gradient
+/* fp32 form, rows in the order of idx itself: out[r, c] = (idx[r] == c) for r < n, c < ld (ld >= nrows, ld % 4 == 0; ids clamped to
+ * [0, nrows) as in the gather).  The exact-f32 table gradient
  * of the encoder (models.py:116 Embedding folded into the LSTM's layer-0 projection) is then one problem of mvae_gemm_tn_f32_multi: A = out,
  * B = the layer-0 pre-activation gradients addressed through row groups (row b * L + t of B = dG[t][b]). */
 int mvae_onehot_f32(const int64_t* idx, int64_t n, int nrows, float* out, int64_t ld, void* stream);
@@ -450,6 +451,8 @@ int mvae_expand_indices(const uint8_t* store, const int64_t* rows, int B, int L,
  *   mvae_ce_loss_*: F.cross_entropy(y[:, :-1], x[:, 1:], ignore_index=pad) (mosesvae.py:193-197) on TIME-MAJOR logits
  *     (row t*B+b, leading dimension ldl); loss2[0] = loss, loss2[1] = number of counted tokens.  Backward writes dlogits in
  *     `dtype` with zero-padded columns V..ldd-1 (the next GEMM's K), adding an optional external dy given in [B,T,V] layout.
+ *     A target outside [0, V) that is not pad is never read through: it makes loss2[0] NaN and is not counted in loss2[1], and its
+ *     row's cross-entropy gradient is zero (the external dy is still added), so dlogits stays finite.
  *   mvae_permute102: [T,B,V] -> [B,T,V] (the `y` return value); mvae_relu_bwd: dy *= (y > 0) in place.
  *   mvae_mask_rows_tb: rows (t*B + b) with t >= lengths[b] of a time-major [T*B, ld] buffer := 0 (ld * sizeof(dtype) a multiple of 16).
  *     pad_packed_sequence (mosesvae.py:189) emits zeros at finished positions, so no gradient reaches h there: when an external gradient

@@ -1373,6 +1373,7 @@ __global__ __launch_bounds__(256) void moses_latent_bwd_kernel(int B, int dz, co
   }
 }
 // token cross-entropy of mosesvae.py:193-197: logits row (t*B+b) predicts x[b, t+1]; targets == pad are ignored; mean over the rest.
+// A target outside [0, V) (and not pad) makes the loss NaN, is not counted and is never used as an address (as ce_rows_fwd_kernel).
 // a block = 64 consecutive (t, b) rows, 16 per wave; per-BLOCK partial sums (nll, count), added up in a fixed order by the final kernel.
 // (One partial per row made the final kernel a 66 us serial walk over T * B * 2 floats by one block.)
 constexpr int CE_RPB = 64;
@@ -1389,6 +1390,7 @@ __global__ __launch_bounds__(256) void ce_tb_fwd_kernel(int B, int T_, int V, co
     if (t + 1 >= T_) continue;
     const long tgt = x[(long)b * T_ + t + 1];
     if (tgt == pad) continue;
+    if (tgt < 0 || tgt >= V) { out = NAN; continue; }       // an id outside the vocabulary: NaN, never read through
     const float* l = logits + row * ldl;
     float mx = -INFINITY;
     for (int v = lane; v < V; v += 64) mx = fmaxf(mx, l[v]);
@@ -1412,7 +1414,8 @@ __global__ __launch_bounds__(256) void ce_tb_final_kernel(long nparts, const flo
   c = block_sum_256(c, red);
   if (threadIdx.x == 0) { out2[0] = a / c; out2[1] = c; }
 }
-// dlogits[(t*B+b), :] = g * (softmax - onehot(target)) / ntok for counted rows, 0 otherwise (+ optional external dy in [B,T,V] layout)
+// dlogits[(t*B+b), :] = g * (softmax - onehot(target)) / ntok for counted rows, 0 otherwise (+ optional external dy in [B,T,V] layout);
+// a row whose target is outside [0, V) is not counted: its CE term is 0 (the forward's loss is NaN)
 template <typename T>
 __global__ __launch_bounds__(256) void ce_tb_bwd_kernel(int B, int T_, int V, const float* logits, long ldl, const int64_t* x, int pad,
                                                         const float* loss2, const float* g, const float* dy_ext, T* dl, long ldd) {
@@ -1422,7 +1425,7 @@ __global__ __launch_bounds__(256) void ce_tb_bwd_kernel(int B, int T_, int V, co
   const int t = (int)(row / B), b = (int)(row - (long)t * B);
   const float scale = (g ? g[0] : 1.f) / loss2[1];
   bool on = false; long tgt = 0;
-  if (t + 1 < T_) { tgt = x[(long)b * T_ + t + 1]; on = tgt != pad; }
+  if (t + 1 < T_) { tgt = x[(long)b * T_ + t + 1]; on = tgt != pad && tgt >= 0 && tgt < V; }
   const float* l = logits + row * ldl;
   float mx = -INFINITY, s = 1.f;
   if (on) {

@@ -249,6 +249,52 @@ def test_c_abi_rejects_bad_arguments_before_touching_the_device():
     assert lib.mvae_relu_bwd(8, None, p, None) == INV
 
 
+def test_helper_launchers_reject_bad_arguments_and_count_pack_blocks():
+    """Status codes of the helper launchers (MOSES cross-entropy, row mask, cast / transpose, multi-job pack) from their argument checks
+    alone, and the block counts the pack table is built from: nothing here reaches the device."""
+    import ctypes as C
+    lib = L.load()
+    INV, WSP = -1, -2
+    buf = (C.c_float * 4096)()
+    p = C.cast(buf, C.c_void_p)
+    B, T, V = 4, 6, 30
+    assert lib.mvae_ce_loss_bwd(L.MVAE_F32, B, T, V, p, V, p, 0, p, None, None, p, V - 1, None) == INV      # ldd < V
+    assert lib.mvae_ce_loss_bwd(L.MVAE_BF16, B, T, V, p, V, p, 0, p, None, None, p, V - 2, None) == INV
+    assert lib.mvae_ce_loss_bwd(7, B, T, V, p, V, p, 0, p, None, None, p, V, None) == INV                 # unknown dtype
+    need = lib.mvae_ce_loss_workspace(B, T)
+    assert need >= 2 * ((B * T + 63) // 64) * 4
+    assert lib.mvae_ce_loss_fwd(B, T, V, p, V, p, 0, p, p, need - 1, None) == WSP                           # short workspace
+    assert lib.mvae_ce_loss_fwd(B, T, V, p, V, p, 0, p, None, need, None) == WSP
+    assert lib.mvae_ce_loss_fwd(B, T, V, None, V, p, 0, p, p, need, None) == INV
+    # mask_rows_tb: the row pitch in bytes must be a multiple of 16
+    assert lib.mvae_mask_rows_tb(L.MVAE_F32, T, B, 6, p, p, None) == INV          # 24 bytes
+    assert lib.mvae_mask_rows_tb(L.MVAE_BF16, T, B, 12, p, p, None) == INV        # 24 bytes
+    assert lib.mvae_mask_rows_tb(L.MVAE_F32, T, B, 3, p, p, None) == INV          # 12 bytes
+    assert lib.mvae_mask_rows_tb(5, T, B, 8, p, p, None) == INV                   # unknown dtype
+    # cast_transpose: a destination narrower than the block
+    assert lib.mvae_cast_transpose(L.MVAE_F32, L.MVAE_BF16, 8, 33, p, 33, p, 32, None, 0, None) == INV    # ldd < C
+    assert lib.mvae_cast_transpose(L.MVAE_F32, L.MVAE_F32, 9, 8, p, 8, None, 0, p, 8, None) == INV        # ldt < R
+    assert lib.mvae_cast_transpose(L.MVAE_F32, L.MVAE_F32, 8, 8, p, 8, None, 0, None, 0, None) == INV     # no destination
+    assert lib.mvae_cast_transpose(L.MVAE_F32, 7, 8, 8, p, 8, p, 8, None, 0, None) == INV                 # unknown dtype
+    assert lib.mvae_cast_transpose(L.MVAE_F32, L.MVAE_F32, 0, 8, None, 8, None, 0, None, 0, None) == 0    # empty: nothing to do
+    # pack_multi: an empty launch is refused
+    assert lib.mvae_pack_multi(3, p, 0, None) == INV
+    assert lib.mvae_pack_multi(0, p, 4, None) == INV
+    assert lib.mvae_pack_multi(3, None, 4, None) == INV
+
+    def blocks(kind, R, C_):
+        j = L.PackJob()
+        j.kind, j.R, j.C = kind, R, C_
+        return lib.mvae_pack_job_blocks(C.byref(j))
+
+    assert blocks(0, 33, 100) == 2 * 4 and blocks(0, 32, 32) == 1 and blocks(0, 1, 1) == 1 and blocks(0, 100, 33) == 4 * 2   # 32 x 32 tiles
+    assert blocks(1, 1, 2500) == 3 and blocks(1, 1, 1024) == 1 and blocks(1, 2, 513) == 2                                   # 1024 elements
+    assert blocks(2, 31, 40) == 2 and blocks(2, 64, 65) == 2 * 3                                                           # 32 x 32 tiles
+    for kind in (0, 1, 2):                                                                                                  # zero-size jobs
+        assert blocks(kind, 0, 8) == 0 and blocks(kind, 8, 0) == 0 and blocks(kind, 1, 0) == 0
+    assert lib.mvae_pack_job_blocks(None) == 0
+
+
 def test_gru_rowres_time_loops_issue_exactly_the_counted_memory_operations(tmp_path):
     """the counted s_waitcnt vmcnt(N) of gru_rowres_fwd / _bwd (NLD / NST in rnn_rowres.hip) are right only while the compiler
     emits exactly that many vector-memory instructions per time step -- no merged, split or predicated-away access, no scratch traffic.
