@@ -148,17 +148,61 @@ class _Workspace:
         return b
 
 
+def _apply_and_mark(self, fn):
+    """nn.Module.apply, then invalidate the packed weight shadows: initialisation hooks often write through ``p.data`` (``m.bias.data.fill_``,
+    moses_train_distrib_logp.py:51), which torch's version counters do not see."""
+    out = nn.Module.apply(self, fn)
+    L.PARAM_EPOCH[0] += 1
+    return out
+
+
+def _params_key(params):
+    return (L.PARAM_EPOCH[0],) + tuple((p.data_ptr(), p._version) for p in params)
+
+
 class _SavedState:
-    """Mixin: where a module's forward keeps what its backward reads.  By default ONE workspace (`_ws`, which also holds the packed weight
+    """Mixin (list it before nn.Module: it overrides `apply`) for the modules that drive the kernels: their workspaces and packed weights.
+
+    Saved state: where a module's forward keeps what its backward reads.  By default ONE workspace (`_ws`, which also holds the packed weight
     shadows): a forward overwrites the previous forward's saved state, so `fwd, fwd, bwd(first)` raises -- at that backward, because only
     then is it known that the first forward is still wanted (train.py:120-153 runs forward after forward with gradients enabled and never
     calls backward).  `saved_state_depth = n` keeps a ring of n workspaces (n x the activation memory): up to n forward passes of the SAME
-    module may be outstanding, backpropagated in any order (micro-batches interleaved by hand, two losses from two forwards)."""
+    module may be outstanding, backpropagated in any order (micro-batches interleaved by hand, two losses from two forwards).
+
+    Packed weight shadows: the bf16 / transposed / padded copies of the parameters the kernels read, refreshed by `_pack` when any parameter
+    changed -- ONE multi-tensor pack launch (ops.PackList) plus the module's conv-weight packs, if it has convolutions.  `_build_pack(dev)` is
+    the per-module part: it allocates the shadows in `_ws` (zeroed: padding is never written) and records `_packed` (name -> shadow),
+    `_pack_list` (the jobs that fill them, each straight from a parameter) and `_conv_packs` (ops.conv1d_pack_weights argument tuples)."""
+
+    apply = _apply_and_mark
 
     def _init_saved_state(self):
         self._ws = _Workspace()
         self.__dict__["_ring"] = [self._ws]
         self.__dict__["_turn"] = 0
+        self._pack_key, self._packed = None, {}
+
+    def _pack(self, dev):
+        params = list(self.parameters())
+        dt = getattr(self, "compute_dtype", None)
+        key = _params_key(params) + (dt,)
+        if key == self._pack_key:
+            return self._packed
+        ptrs = (dev, dt) + tuple((id(p), p.data_ptr()) for p in params)     # id: a deepcopy must rebuild its own job table
+        if self.__dict__.get("_pack_ptrs") != ptrs:
+            with torch.no_grad():                      # the job table keeps plain (non-autograd) views of the parameters
+                self._build_pack(dev)
+            self.__dict__["_pack_ptrs"] = ptrs
+        with torch.no_grad():
+            self.__dict__["_pack_list"].run()
+            for args in self.__dict__["_conv_packs"]:
+                ops.conv1d_pack_weights(*args)
+        self._pack_key = key
+        return self._packed
+
+    def _set_pack(self, P, pl, conv_packs=()):
+        self._packed = P
+        self.__dict__["_pack_list"], self.__dict__["_conv_packs"] = pl, list(conv_packs)
 
     @property
     def saved_state_depth(self):
@@ -211,14 +255,6 @@ def _dyk(n_out):
     return _pad(n_out, 128)
 
 
-def _apply_and_mark(self, fn):
-    """nn.Module.apply, then invalidate the packed weight shadows: initialisation hooks often write through ``p.data`` (``m.bias.data.fill_``,
-    moses_train_distrib_logp.py:51), which torch's version counters do not see."""
-    out = nn.Module.apply(self, fn)
-    L.PARAM_EPOCH[0] += 1
-    return out
-
-
 def _require_cuda(dev, what):
     if dev.type != "cuda":
         raise L.MvaeError(f"{what} runs on the MI355X only (no CPU fallback); move the module and inputs to cuda")
@@ -242,8 +278,99 @@ def _grad_buffer(params, dev):
     return torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=dev), None
 
 
-def _params_key(params):
-    return (L.PARAM_EPOCH[0],) + tuple((p.data_ptr(), p._version) for p in params)
+def _grad_views(names, params, dev):
+    """Zeroed flat fp32 gradient buffer for `params` (in order) and a view of it per name; "_flat": [the buffer]."""
+    gflat = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=dev)
+    grads, off = {"_flat": [gflat]}, 0
+    for n, p in zip(names, params):
+        grads[n] = gflat[off:off + p.numel()].view(p.shape); off += p.numel()
+    return grads
+
+
+def _kmajor_gemm(ws, tag, A, lda, M, Bm, ldb, N, K, out, dev):
+    """out[M,N] = A[:K,:M]^T . Bm[:K,:N] for K-major operands: TN kernel for bf16, transposes + NT for f32 (into workspace buffers named by
+    `tag`: work that may run concurrently on one workspace needs distinct tags)."""
+    if A.dtype == torch.bfloat16:
+        ops.gemm_tn(A, Bm, out, M, N, K, lda=lda, ldb=ldb)
+        return
+    ldT = _pad(K, 8) + 8
+    AT = ws.get(tag + "_AT", (M, ldT), torch.float32, dev); BT = ws.get(tag + "_BT", (N, ldT), torch.float32, dev)
+    ops.cast_transpose(A, K, M, dstT=AT, lds=lda); ops.cast_transpose(Bm, K, N, dstT=BT, lds=ldb)
+    ops.gemm_nt(AT, BT, out, M, N, ldT, lda=ldT, ldb=ldT)
+
+
+# ----------------------------------------------------------------------------------------------- RNN stacks
+# The recurrent kernels read every stack in 4 gate slots of Hp rows.  LSTM: torch's own gate order (i, f, g, o), Hp = H.  GRU: torch's
+# (r, z, n) rows go to slots (r, z, n, 0) in W_ih and (r, z, 0, n) in W_hh, the bias to (b_ir + b_hr, b_iz + b_hz, b_in, b_hn); a slot may
+# be zero-padded from H to Hp rows (models2d: 501 -> 512), and so are the K columns of the recurrent matrices.
+def _gru_slot_runs(H, Hp, n_slot=None):
+    """Where torch's GRU gate rows (r, z, n) go in the 4-slot layout, n in slot `n_slot` (None: r and z alone), as (gate row, slot row,
+    rows) runs -- gates that stay adjacent (no padding) in one run."""
+    runs = []
+    for g, s in ((0, 0), (1, 1)) + (((2, n_slot),) if n_slot is not None else ()):
+        if runs and runs[-1][1] + runs[-1][2] == s * Hp:
+            runs[-1] = (runs[-1][0], runs[-1][1], runs[-1][2] + H)
+        else:
+            runs.append((g * H, s * Hp, H))
+    return runs
+
+
+def _pack_rnn_stack(pl, ws, rnn, prefix, dt, dev, ldw, ldwT, Hp=None):
+    """Record in PackList `pl` the shadows of an RNN stack (RNNWeights) the recurrent kernels read: W_hh / W_hh^T of every layer, W_ih / W_ih^T
+    of layers >= 1 (layer 0's input weights are model-specific) in `dt` -- workspace buffers `{prefix}Whh{l}` [4Hp, ldw], `{prefix}WhhT{l}`
+    [Hp, ldwT], `{prefix}Wih{l}`, `{prefix}WihT{l}` -- and the fp32 bias `{prefix}bias{l}` [4Hp], in the slot layout above (Hp: default H).
+    Returns dict(Whh, WhhT, Wih, WihT, bias) of per-layer lists (Wih / WihT: None at layer 0)."""
+    H, f32 = rnn.hidden_size, torch.float32
+    Hp = Hp or H
+    gru = rnn.mode == "GRU"
+    S = dict(Whh=[], WhhT=[], Wih=[None], WihT=[None], bias=[])
+    for l in range(rnn.num_layers):
+        bi, bh = getattr(rnn, f"bias_ih_l{l}"), getattr(rnn, f"bias_hh_l{l}")
+        b = ws.get(f"{prefix}bias{l}", (4 * Hp,), f32, dev)
+        for g, s, n in _gru_slot_runs(H, Hp) if gru else [(0, 0, 4 * H)]:
+            pl.add(bi[g:g + n], bh[g:g + n], b[s:s + n])
+        if gru:
+            pl.copy(bi[2 * H:], b[2 * Hp:2 * Hp + H]); pl.copy(bh[2 * H:], b[3 * Hp:3 * Hp + H])
+        S["bias"].append(b)
+        for k, n_slot in (("hh", 3), ("ih", 2)) if l > 0 else (("hh", 3),):
+            w = getattr(rnn, f"weight_{k}_l{l}")
+            W, WT = ws.get(f"{prefix}W{k}{l}", (4 * Hp, ldw), dt, dev), ws.get(f"{prefix}W{k}T{l}", (Hp, ldwT), dt, dev)
+            for g, s, n in _gru_slot_runs(H, Hp, n_slot) if gru else [(0, 0, 4 * H)]:
+                pl.cast_transpose(w[g:g + n], n, H, dst=W[s:s + n], dstT=WT[:H, s:s + n])
+            S[f"W{k}"].append(W); S[f"W{k}T"].append(WT)
+    return S
+
+
+def _gru_unslot(src, dst, H, Hp, n_slot):
+    """dst (torch's gate rows (r, z, n); [3H] or [3H, K]) := its rows of the 4-slot `src` (n in slot `n_slot`), cut to dst's columns."""
+    for g, s, n in _gru_slot_runs(H, Hp, n_slot):
+        dst[g:g + n].copy_(src[s:s + n] if dst.dim() == 1 else src[s:s + n, :dst.shape[1]])
+
+
+def _gru_param_grads(ws, tag, grads, prefix, l, a, ldg, hprev, xin, ldh, Hp, TB, dev, s4=None):
+    """Parameter gradients of layer l of the GRU stack `prefix` (gradient views grads[f"{prefix}.weight_hh_l{l}"], ...) from the K-major
+    operands of its backward: a = dG [T*B, 4Hp] in the slot layout (ld ldg), hprev = the h_{t-1} rows and xin = the input rows (layers >= 1,
+    else None), both [T*B, Hp] (ld ldh).  dW_hh (r, z | n) and dW_ih (r, z, n) go straight into the gradient views when Hp == H, through a
+    [4Hp, Hp] workspace temporary cut back to H otherwise; hprev None: no weight gradients.  s4 (a [4Hp] fp32 buffer): also b_ih / b_hh from
+    the column sums of dG.  `tag` prefixes the workspace names of the f32 path's transposes (_kmajor_gemm)."""
+    H = grads[f"{prefix}.weight_hh_l{l}"].shape[1]
+    if hprev is not None:
+        tmp = ws.get(tag + "dw_gru", (4 * Hp, Hp), torch.float32, dev) if Hp > H else None
+        gw = grads[f"{prefix}.weight_hh_l{l}"]
+        out = gw if tmp is None else tmp
+        _kmajor_gemm(ws, tag + "dwhh_rz", a, ldg, 2 * Hp, hprev, ldh, Hp, TB, out[:2 * Hp], dev)                    # slots r, z
+        _kmajor_gemm(ws, tag + "dwhh_n", a[:, 3 * Hp:], ldg, Hp, hprev, ldh, Hp, TB, out[(2 if tmp is None else 3) * Hp:], dev)  # slot n_h
+        if tmp is not None:
+            _gru_unslot(tmp, gw, H, Hp, 3)
+        if xin is not None:
+            gw = grads[f"{prefix}.weight_ih_l{l}"]
+            _kmajor_gemm(ws, tag + "dwih", a, ldg, 3 * Hp, xin, ldh, Hp, TB, (gw if tmp is None else tmp)[:3 * Hp], dev)   # slots r, z, n_x
+            if tmp is not None:
+                _gru_unslot(tmp, gw, H, Hp, 2)
+    if s4 is not None:
+        ops.colsum_t(a, TB, 4 * Hp, s4, ldx=ldg)
+        _gru_unslot(s4, grads[f"{prefix}.bias_ih_l{l}"], H, Hp, 2)
+        _gru_unslot(s4, grads[f"{prefix}.bias_hh_l{l}"], H, Hp, 3)
 
 
 WGRAD_LATE_TB = 32768   # T*B up to which every weight-gradient launch is released late, next to the encoder LSTM backward
@@ -406,7 +533,7 @@ class Lambda(nn.Module):
 
 
 # ----------------------------------------------------------------------------------------------- encoder
-class MolEncoder(nn.Module, _SavedState):
+class MolEncoder(_SavedState, nn.Module):
     """models.py:109-135: Embedding -> LSTM(30->72, 3 layers) -> 3 x (Conv1d k=18 + SELU) -> Linear+SELU -> Lambda."""
 
     def __init__(self, i=120, o=292, c=35, word_embedding_size=30, h_size=72, num_lstm=3):
@@ -422,10 +549,6 @@ class MolEncoder(nn.Module, _SavedState):
         self._init_saved_state()
         self.__dict__["_fork"] = ops.ForkState()   # side-stream work of the decoder paired with us (MolecularVAE shares one object between the two)
         self.fast_grad_gemms = False      # set by MolecularVAE in bf16 mode (conv input-gradient GEMMs as 3 x bf16 products)
-        self._pack_key = None
-        self._packed = {}
-
-    apply = _apply_and_mark
 
     def forward(self, x, eps=None):
         B = x.shape[0]
@@ -439,29 +562,9 @@ class MolEncoder(nn.Module, _SavedState):
         self.lmbd.mu, self.lmbd.log_v = mu, logv
         return z, mu, logv
 
-    # -- packed weight shadows (refreshed when any parameter changed): ONE multi-tensor pack launch (ops.PackList) + the three conv packs
-    def _pack(self, dev):
-        params = list(self.parameters())
-        key = _params_key(params)
-        if key == self._pack_key:
-            return self._packed
-        ptrs = (dev,) + tuple((id(p), p.data_ptr()) for p in params)     # id: a deepcopy must rebuild its own job table
-        if self.__dict__.get("_pack_ptrs") != ptrs:
-            with torch.no_grad():                      # the job table keeps plain (non-autograd) views of the parameters
-                self._build_pack(dev)
-            self.__dict__["_pack_ptrs"] = ptrs
-        with torch.no_grad():
-            self.__dict__["_pack_list"].run()
-            for n, conv in (("c1", self.conv_1[0]), ("c2", self.conv_2[0]), ("c3", self.conv_3[0])):
-                Ci, Co, k = conv.in_channels, conv.out_channels, conv.kernel_size
-                ops.conv1d_pack_weights(conv.weight, Ci, Co, k, _pad(Ci, 32), self._packed[n + "_wp"], _pad(Co, 32), self._packed[n + "_wq"])
-        self._pack_key = key
-        return self._packed
-
     def _build_pack(self, dev):
-        """Allocate the shadows (zeroed: padding is never written) and record the jobs that fill them, each straight from a parameter."""
         g, ws = self.gru, self._ws
-        H, NL, E, Cv = g.hidden_size, g.num_layers, g.input_size, self.embedding.num_embeddings
+        H, E, Cv = g.hidden_size, g.input_size, self.embedding.num_embeddings
         P, pl = {}, ops.PackList()
         Ep = _pad(E, 4)
         P["E_p"] = ws.get("E_p", (Cv, Ep), torch.float32, dev)
@@ -470,30 +573,16 @@ class MolEncoder(nn.Module, _SavedState):
         P["Wih0_p"] = ws.get("Wih0_p", (4 * H, Ep), torch.float32, dev)
         P["Wih0T"] = ws.get("Wih0T", (E, 4 * H), torch.float32, dev)
         pl.cast_transpose(g.weight_ih_l0, 4 * H, E, dst=P["Wih0_p"], dstT=P["Wih0T"])
-        P["bias"] = []
-        P["WihT"], P["WhhT"] = [None], []
-        Hp = _pad(H, 32)                       # whole 128-byte K-steps (f32): zero-padded shadows -> LDS-direct main loop
-        P["Hp"] = Hp
-        P["Wih"], P["Whh"] = [None], []
-        for l in range(NL):
-            b = ws.get(f"bias{l}", (4 * H,), torch.float32, dev)
-            pl.add(getattr(g, f"bias_ih_l{l}"), getattr(g, f"bias_hh_l{l}"), b)
-            P["bias"].append(b)
-            w = ws.get(f"Whh{l}", (4 * H, Hp), torch.float32, dev)
-            t = ws.get(f"WhhT{l}", (H, 4 * H), torch.float32, dev)
-            pl.cast_transpose(getattr(g, f"weight_hh_l{l}"), 4 * H, H, dst=w, dstT=t)
-            P["Whh"].append(w); P["WhhT"].append(t)
-            if l > 0:
-                w = ws.get(f"Wih{l}", (4 * H, Hp), torch.float32, dev)
-                t = ws.get(f"WihT{l}", (H, 4 * H), torch.float32, dev)
-                pl.cast_transpose(getattr(g, f"weight_ih_l{l}"), 4 * H, H, dst=w, dstT=t)
-                P["Wih"].append(w); P["WihT"].append(t)
+        P["Hp"] = Hp = _pad(H, 32)            # whole 128-byte K-steps (f32): zero-padded shadows -> LDS-direct main loop
+        P.update(_pack_rnn_stack(pl, ws, g, "", torch.float32, dev, Hp, 4 * H))
         # conv stack, channels-last with channel counts padded to whole K-steps: packed weights for the sliding-window GEMMs
+        convs = []
         for n, conv in (("c1", self.conv_1[0]), ("c2", self.conv_2[0]), ("c3", self.conv_3[0])):
             Ci, Co, k = conv.in_channels, conv.out_channels, conv.kernel_size
             ldx, ldo = _pad(Ci, 32), _pad(Co, 32)
             P[n + "_wp"] = ws.get(n + "_wp", (Co, k * ldx), torch.float32, dev)
             P[n + "_wq"] = ws.get(n + "_wq", (Ci, k * ldo), torch.float32, dev)
+            convs.append((conv.weight, Ci, Co, k, ldx, P[n + "_wp"], ldo, P[n + "_wq"]))
         d1 = self.dense_1[0]
         P["W1T"] = ws.get("W1T", (d1.in_features, d1.out_features), torch.float32, dev)
         pl.cast_transpose(d1.weight, d1.out_features, d1.in_features, dstT=P["W1T"])
@@ -504,8 +593,7 @@ class MolEncoder(nn.Module, _SavedState):
         for k, lin in enumerate((self.lmbd.z_mean, self.lmbd.z_log_var)):           # the stacked mu | logvar head and its transpose, each from the parameter
             pl.cast_transpose(lin.weight, o, 512, dst=P["Wml"][k * o:(k + 1) * o], dstT=P["WmlT"][:, k * o:(k + 1) * o])
             pl.copy(lin.bias, P["bml"][k * o:(k + 1) * o])
-        self._packed = P
-        self.__dict__["_pack_list"] = pl
+        self._set_pack(P, pl, convs)
 
 
 class _EncoderFn(torch.autograd.Function):
@@ -701,7 +789,7 @@ class _EncoderFn(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------------------------- decoder
-class MolDecoder(nn.Module, _SavedState):
+class MolDecoder(_SavedState, nn.Module):
     """models.py:148-165: Linear+SELU -> repeat L -> LSTM(292->1024, 4 layers) -> Linear(1024,C) -> softmax over C."""
 
     def __init__(self, i=292, o=120, c=35, num_gru=4, h_size=1024, dtype=torch.bfloat16):
@@ -712,15 +800,11 @@ class MolDecoder(nn.Module, _SavedState):
         self.decoded_mean = TimeDistributed(nn.Sequential(LinearWeights(h_size, c), Softmax()))
         self.compute_dtype = dtype
         self._init_saved_state()
-        self._pack_key = None
-        self._packed = {}
         self.__dict__["_peer"] = None          # weakref to the encoder whose backward runs after ours (set by MolecularVAE)
         self.__dict__["_z_from_peer"] = False  # True only inside MolecularVAE.forward: z is that encoder's output
         self.__dict__["_side"] = None
         self.overlap_weight_grads = True       # run the weight-gradient GEMMs on a side stream under the encoder's backward
         self.__dict__["elbo_parts"] = None     # (total, xent, kl) of the last `elbo`, on device
-
-    apply = _apply_and_mark
 
     def _side_stream(self, dev):
         return ops.side_stream(dev)       # process-wide, probed not to share a hardware queue with the main stream (stream priorities: no effect)
@@ -750,45 +834,19 @@ class MolDecoder(nn.Module, _SavedState):
         return _DecoderElboFn.apply(self, z, idx.contiguous(), mu, logvar, float(Lq if max_len is None else max_len), infer, pred_out,
                                     *list(self.parameters()))
 
-    def _pack(self, dev):
-        params = list(self.parameters())
-        key = _params_key(params) + (self.compute_dtype,)
-        if key == self._pack_key:
-            return self._packed
-        ptrs = (dev, self.compute_dtype) + tuple((id(p), p.data_ptr()) for p in params)     # id: a deepcopy must rebuild its own job table
-        if self.__dict__.get("_pack_ptrs") != ptrs:
-            with torch.no_grad():                      # the job table keeps plain (non-autograd) views of the parameters
-                self._build_pack(dev)
-            self.__dict__["_pack_ptrs"] = ptrs
-        with torch.no_grad():
-            self.__dict__["_pack_list"].run()          # every shadow in ONE launch (ops.PackList)
-        self._pack_key = key
-        return self._packed
-
     def _build_pack(self, dev):
         g, ws, dt = self.gru, self._ws, self.compute_dtype
-        H, NL, o = g.hidden_size, g.num_layers, g.input_size
+        H, o = g.hidden_size, g.input_size
         G4 = 4 * H
         f32 = torch.float32
         ldw, ldwT = H + _LDPAD, G4 + _LDPAD       # leading dimensions kept off powers of two (L2 / MALL set conflicts)
-        P = {"Wih": [None], "WihT": [None], "Whh": [], "WhhT": [], "bias": [], "ldw": ldw, "ldwT": ldwT}
         pl = ops.PackList()
+        P = {"ldw": ldw, "ldwT": ldwT, **_pack_rnn_stack(pl, ws, g, "", dt, dev, ldw, ldwT)}
         li = self.latent_input[0]
         P["WliT"] = ws.get("WliT", (o, _pad(o, 4)), f32, dev)
         pl.cast_transpose(li.weight, o, o, dstT=P["WliT"])
         P["Wih0T"] = ws.get("Wih0T", (o, G4), f32, dev)
         pl.cast_transpose(g.weight_ih_l0, G4, o, dstT=P["Wih0T"])
-        for l in range(NL):
-            b = ws.get(f"bias{l}", (G4,), f32, dev)
-            pl.add(getattr(g, f"bias_ih_l{l}"), getattr(g, f"bias_hh_l{l}"), b)
-            P["bias"].append(b)
-            w = ws.get(f"Whh{l}", (G4, ldw), dt, dev); wT = ws.get(f"WhhT{l}", (H, ldwT), dt, dev)
-            pl.cast_transpose(getattr(g, f"weight_hh_l{l}"), G4, H, dst=w, dstT=wT)
-            P["Whh"].append(w); P["WhhT"].append(wT)
-            if l > 0:
-                w = ws.get(f"Wih{l}", (G4, ldw), dt, dev); wT = ws.get(f"WihT{l}", (H, ldwT), dt, dev)
-                pl.cast_transpose(getattr(g, f"weight_ih_l{l}"), G4, H, dst=w, dstT=wT)
-                P["Wih"].append(w); P["WihT"].append(wT)
         om = self.decoded_mean.module[0]
         Cv = om.out_features
         Cp = _pad(Cv, 8)
@@ -796,8 +854,7 @@ class MolDecoder(nn.Module, _SavedState):
         # bf16: W_out^T zero-padded to _dyk(C) columns -- the backward contracts the logit gradients with it inside the top LSTM cell
         P["WoutT"] = ws.get("WoutT", (H, _dyk(Cv) if dt == torch.bfloat16 else Cp), dt, dev)
         pl.cast_transpose(om.weight, Cv, H, dst=P["Wout"], dstT=P["WoutT"])
-        self._packed = P
-        self.__dict__["_pack_list"] = pl
+        self._set_pack(P, pl)
 
 
 def _decoder_fwd_logits(ctx, mod, z, infer, params):

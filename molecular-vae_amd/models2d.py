@@ -20,24 +20,13 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
-from .models import LinearWeights, Conv1dWeights, RNNWeights, _Workspace, _SavedState, _params_key, _pad, _require_cuda, _LDPAD, _dyk
-from .mosesvae import _kmajor_gemm
+from .models import (LinearWeights, Conv1dWeights, RNNWeights, _SavedState, _pad, _require_cuda, _LDPAD, _dyk, _grad_views, _kmajor_gemm,
+                     _gru_slot_runs, _pack_rnn_stack, _gru_unslot, _gru_param_grads)
 
 SEQ, VOCAB, HID, HP, NLAY = 120, 35, 501, 512, 3
 
 
-def _slots4p(w3, H, Hp, Kp, order):
-    """[3H, K] GRU gate rows (r, z, n) -> [4Hp, Kp] slot rows, zero padded; order 'x' = (r, z, n, 0) for W_ih, 'h' = (r, z, 0, n) for W_hh."""
-    K = w3.shape[1]
-    out = torch.zeros(4 * Hp, Kp, dtype=w3.dtype, device=w3.device)
-    out[0:H, :K] = w3[0:H]
-    out[Hp:Hp + H, :K] = w3[H:2 * H]
-    s = 2 if order == "x" else 3
-    out[s * Hp:s * Hp + H, :K] = w3[2 * H:3 * H]
-    return out
-
-
-class VAE(nn.Module, _SavedState):
+class VAE(_SavedState, nn.Module):
     def __init__(self, dtype=torch.bfloat16):
         super().__init__()
         self.conv1d1 = Conv1dWeights(SEQ, 9, 9)          # models2d.py:12-21, same construction order (same RNG stream under manual_seed)
@@ -52,7 +41,6 @@ class VAE(nn.Module, _SavedState):
         self.compute_dtype = dtype
         self.__dict__["noise_stream"] = ops.NoiseStream()           # (seed, counter) of the reparameterisation draws made inside mvae_lambda_fwd
         self._init_saved_state()
-        self._pack_key, self._packed = None, {}
 
     # -- the reference's method surface
     def forward(self, x, eps=None):
@@ -84,54 +72,33 @@ class VAE(nn.Module, _SavedState):
         with torch.no_grad():
             return _decode_only(self, z.contiguous().float())
 
-    # -- packed shadows
-    def _pack(self, dev):
-        params = list(self.parameters())
-        key = _params_key(params) + (self.compute_dtype,)
-        if key == self._pack_key:
-            return self._packed
+    # -- packed shadows (_SavedState._pack)
+    def _build_pack(self, dev):
         ws, dt, f32 = self._ws, self.compute_dtype, torch.float32
-        P = {}
-        with torch.no_grad():
-            for n, conv, ldx, ldo, want_q in (("c1", self.conv1d1, SEQ, 12, False), ("c2", self.conv1d2, 12, 12, True), ("c3", self.conv1d3, 12, 12, True)):
-                Ci, Co, k = conv.in_channels, conv.out_channels, conv.kernel_size
-                P[n + "_wp"] = ws.get(n + "_wp", (Co, k * ldx), f32, dev)
-                P[n + "_wq"] = ws.get(n + "_wq", (Ci, k * ldo), f32, dev) if want_q else None
-                ops.conv1d_pack_weights(conv.weight, Ci, Co, k, ldx, P[n + "_wp"], ldo if want_q else 0, P[n + "_wq"])
-            P["W0p"] = ws.get("W0p", (435, 92), f32, dev); P["W0p"][:, :90].copy_(self.fc0.weight)
-            P["W0T"] = ws.get("W0T", (92, 436), f32, dev); ops.cast_transpose(P["W0p"], 435, 92, dstT=P["W0T"])
-            P["Wml"] = ws.get("Wml", (4, 436), f32, dev); P["Wml"][:2, :435].copy_(self.fc11.weight); P["Wml"][2:, :435].copy_(self.fc12.weight)
-            P["bml"] = ws.get("bml", (4,), f32, dev); P["bml"][:2].copy_(self.fc11.bias); P["bml"][2:].copy_(self.fc12.bias)
-            P["WmlT"] = ws.get("WmlT", (436, 4), f32, dev); ops.cast_transpose(P["Wml"], 4, 436, dstT=P["WmlT"])
-            P["W2p"] = ws.get("W2p", (2, 4), f32, dev); P["W2p"][:, :2].copy_(self.fc2.weight)
-            P["W2T"] = ws.get("W2T", (4, 4), f32, dev); P["W2T"][:2, :2].copy_(self.fc2.weight.t())
-            g = self.gru
-            ldw, ldwT = HP + _LDPAD, 4 * HP + _LDPAD
-            P.update(ldw=ldw, ldwT=ldwT, Whh=[], WhhT=[], Wih=[None], WihT=[None], bias=[])
-            for l in range(NLAY):
-                whh4 = _slots4p(getattr(g, f"weight_hh_l{l}"), HID, HP, HP, "h")
-                w = ws.get(f"Whh{l}", (4 * HP, ldw), dt, dev); wT = ws.get(f"WhhT{l}", (HP, ldwT), dt, dev)
-                ops.cast_transpose(whh4, 4 * HP, HP, dst=w, dstT=wT)
-                P["Whh"].append(w); P["WhhT"].append(wT)
-                if l > 0:
-                    wih4 = _slots4p(getattr(g, f"weight_ih_l{l}"), HID, HP, HP, "x")
-                    w = ws.get(f"Wih{l}", (4 * HP, ldw), dt, dev); wT = ws.get(f"WihT{l}", (HP, ldwT), dt, dev)
-                    ops.cast_transpose(wih4, 4 * HP, HP, dst=w, dstT=wT)
-                    P["Wih"].append(w); P["WihT"].append(wT)
-                bi, bh = getattr(g, f"bias_ih_l{l}"), getattr(g, f"bias_hh_l{l}")
-                b4 = ws.get(f"bias{l}", (4 * HP,), f32, dev)
-                b4.zero_()
-                b4[0:HID] = bi[0:HID] + bh[0:HID]; b4[HP:HP + HID] = bi[HID:2 * HID] + bh[HID:2 * HID]
-                b4[2 * HP:2 * HP + HID] = bi[2 * HID:]; b4[3 * HP:3 * HP + HID] = bh[2 * HID:]
-                P["bias"].append(b4)
-            P["Wx0"] = ws.get("Wx0", (4 * HP, 4), f32, dev); P["Wx0"].copy_(_slots4p(g.weight_ih_l0, HID, HP, 4, "x"))
-            P["Wx0T"] = ws.get("Wx0T", (4, 4 * HP), f32, dev); ops.cast_transpose(P["Wx0"], 4 * HP, 4, dstT=P["Wx0T"])
-            Cp = _pad(VOCAB, 8)
-            w3p = torch.zeros(VOCAB, HP, device=dev); w3p[:, :HID].copy_(self.fc3.weight)
-            P["Wfc"] = ws.get("Wfc", (VOCAB, ldw), dt, dev); P["WfcT"] = ws.get("WfcT", (HP, _dyk(VOCAB) if dt == torch.bfloat16 else Cp), dt, dev)
-            ops.cast_transpose(w3p, VOCAB, HP, dst=P["Wfc"], dstT=P["WfcT"])
-        self._pack_key, self._packed = key, P
-        return P
+        P, pl, convs = {}, ops.PackList(), []
+        for n, conv, ldx, ldo, want_q in (("c1", self.conv1d1, SEQ, 12, False), ("c2", self.conv1d2, 12, 12, True), ("c3", self.conv1d3, 12, 12, True)):
+            Ci, Co, k = conv.in_channels, conv.out_channels, conv.kernel_size
+            P[n + "_wp"] = ws.get(n + "_wp", (Co, k * ldx), f32, dev)
+            P[n + "_wq"] = ws.get(n + "_wq", (Ci, k * ldo), f32, dev) if want_q else None
+            convs.append((conv.weight, Ci, Co, k, ldx, P[n + "_wp"], ldo if want_q else 0, P[n + "_wq"]))
+        P["W0p"] = ws.get("W0p", (435, 92), f32, dev); P["W0T"] = ws.get("W0T", (92, 436), f32, dev)
+        pl.cast_transpose(self.fc0.weight, 435, 90, dst=P["W0p"], dstT=P["W0T"])
+        P["Wml"] = ws.get("Wml", (4, 436), f32, dev); P["bml"] = ws.get("bml", (4,), f32, dev); P["WmlT"] = ws.get("WmlT", (436, 4), f32, dev)
+        for k, lin in enumerate((self.fc11, self.fc12)):                       # the stacked mu | logvar head and its transpose
+            pl.cast_transpose(lin.weight, 2, 435, dst=P["Wml"][2 * k:2 * k + 2], dstT=P["WmlT"][:, 2 * k:2 * k + 2])
+            pl.copy(lin.bias, P["bml"][2 * k:2 * k + 2])
+        P["W2p"] = ws.get("W2p", (2, 4), f32, dev); P["W2T"] = ws.get("W2T", (4, 4), f32, dev)
+        pl.cast_transpose(self.fc2.weight, 2, 2, dst=P["W2p"], dstT=P["W2T"])
+        g = self.gru
+        ldw, ldwT = HP + _LDPAD, 4 * HP + _LDPAD
+        P.update(ldw=ldw, ldwT=ldwT, **_pack_rnn_stack(pl, ws, g, "", dt, dev, ldw, ldwT, Hp=HP))
+        P["Wx0"] = ws.get("Wx0", (4 * HP, 4), f32, dev); P["Wx0T"] = ws.get("Wx0T", (4, 4 * HP), f32, dev)
+        for r, s, n in _gru_slot_runs(HID, HP, 2):                             # layer-0 input weights [3H, 2] in the W_ih slots, padded
+            pl.cast_transpose(g.weight_ih_l0[r:r + n], n, 2, dst=P["Wx0"][s:s + n], dstT=P["Wx0T"][:, s:s + n])
+        Cp = _pad(VOCAB, 8)
+        P["Wfc"] = ws.get("Wfc", (VOCAB, ldw), dt, dev); P["WfcT"] = ws.get("WfcT", (HP, _dyk(VOCAB) if dt == torch.bfloat16 else Cp), dt, dev)
+        pl.cast_transpose(self.fc3.weight, VOCAB, HID, dst=P["Wfc"], dstT=P["WfcT"])
+        self._set_pack(P, pl, convs)
 
 
 def _decoder_forward(mod, P, W, zp, B, dev, infer):
@@ -208,12 +175,8 @@ class _Models2dFn(torch.autograd.Function):
         dev = recon.device
         P, dt, f32 = mod._packed, mod.compute_dtype, torch.float32
         W = lambda name, shape, d=f32: ws.get(name, shape, d, dev)
-        params = list(mod.parameters())
         names = [n for n, _ in mod.named_parameters()]
-        gflat = torch.zeros(sum(p.numel() for p in params), dtype=f32, device=dev)
-        grads, off = {}, 0
-        for n, p in zip(names, params):
-            grads[n] = gflat[off:off + p.numel()].view(p.shape); off += p.numel()
+        grads = _grad_views(names, list(mod.parameters()), dev)
         Bp, TB, Cp = _pad(B, 4), SEQ * B, _pad(VOCAB, 8)
         ldh, ldg = HP + _LDPAD, 4 * HP + _LDPAD
 
@@ -249,31 +212,17 @@ class _Models2dFn(torch.autograd.Function):
                     [h[1:] for h in hsx], ldh, None, gates, dG, dstate, ldg=ldg, h0=[h[0] for h in hsx], ldh0=ldh, tag="m2d_gru_bwd",
                     dy_a=(dl if fuse_dy else None), dy_w=(P["WfcT"] if fuse_dy else None), dy_k=(_dyk(VOCAB) if fuse_dy else 0))
         s4 = W("s4", (4 * HP,))
-        tmp = W("dw_gru", (4 * HP, HP))
         for l in range(NLAY):
-            a = dG[l].view(TB, ldg)
             hprev = hsx[l][:SEQ].reshape(TB, ldh)                        # h_{t-1} for every t (slot 0 = 0)
-            _kmajor_gemm(ws, "dwhh_rz", a, ldg, 2 * HP, hprev, ldh, HP, TB, tmp[:2 * HP], dev)          # slots r, z
-            _kmajor_gemm(ws, "dwhh_n", a[:, 3 * HP:], ldg, HP, hprev, ldh, HP, TB, tmp[3 * HP:], dev)    # slot n_h (slot n_x has no W_hh rows)
-            gw = grads[f"gru.weight_hh_l{l}"]
-            gw[0:HID].copy_(tmp[0:HID, :HID]); gw[HID:2 * HID].copy_(tmp[HP:HP + HID, :HID]); gw[2 * HID:].copy_(tmp[3 * HP:3 * HP + HID, :HID])
-            if l > 0:
-                _kmajor_gemm(ws, "dwih", a, ldg, 3 * HP, hsx[l - 1][1:].reshape(TB, ldh), ldh, HP, TB, tmp[:3 * HP], dev)   # slots r, z, n_x
-                gw = grads[f"gru.weight_ih_l{l}"]
-                gw[0:HID].copy_(tmp[0:HID, :HID]); gw[HID:2 * HID].copy_(tmp[HP:HP + HID, :HID]); gw[2 * HID:].copy_(tmp[2 * HP:2 * HP + HID, :HID])
-            ops.colsum_t(a, TB, 4 * HP, s4, ldx=ldg)
-            gb = grads[f"gru.bias_ih_l{l}"]
-            gb[0:HID].copy_(s4[0:HID]); gb[HID:2 * HID].copy_(s4[HP:HP + HID]); gb[2 * HID:].copy_(s4[2 * HP:2 * HP + HID])
-            gb = grads[f"gru.bias_hh_l{l}"]
-            gb[0:HID].copy_(s4[0:HID]); gb[HID:2 * HID].copy_(s4[HP:HP + HID]); gb[2 * HID:].copy_(s4[3 * HP:3 * HP + HID])
+            xin = hsx[l - 1][1:].reshape(TB, ldh) if l > 0 else None
+            _gru_param_grads(ws, "", grads, "gru", l, dG[l].view(TB, ldg), ldg, hprev, xin, ldh, HP, TB, dev, s4=s4)
         # layer 0: the input is time-invariant -> its gradient is the time sum of dG[0]
         dgx0 = W("dgx0", (B, ldg)); ops.timesum(dG[0], SEQ, B, ldg, dgx0)
         d2p, zp = W("d2p", (B, 4)), W("zp", (B, 4))
         dgT, d2T = W("dgx0T", (4 * HP, Bp)), W("d2T", (4, Bp))
         ops.cast_transpose(dgx0, B, 4 * HP, dstT=dgT, lds=ldg); ops.cast_transpose(d2p, B, 4, dstT=d2T)
         dwx = W("dwx0", (4 * HP, 4)); ops.gemm_nt(dgT, d2T, dwx, 4 * HP, 4, Bp)
-        gw = grads["gru.weight_ih_l0"]
-        gw[0:HID].copy_(dwx[0:HID, :2]); gw[HID:2 * HID].copy_(dwx[HP:HP + HID, :2]); gw[2 * HID:].copy_(dwx[2 * HP:2 * HP + HID, :2])
+        _gru_unslot(dwx, grads["gru.weight_ih_l0"], HID, HP, 2)
         dd2 = W("dd2", (B, 4)); ops.gemm_nt(dgx0, P["Wx0T"], dd2, B, 4, 4 * HP, lda=ldg)
         ops.selu_bwd(dd2, d2p)
         lin_grads("fc2", dd2, 4, 2, zp, 4, 2, grads["fc2.weight"], grads["fc2.bias"])

@@ -23,8 +23,8 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
-from .models import (LinearWeights, EmbeddingWeights, RNNWeights, _Workspace, _SavedState, _params_key, _pad, _require_cuda, _LDPAD, _dyk,
-                     _apply_and_mark)
+from .models import (LinearWeights, EmbeddingWeights, RNNWeights, _Workspace, _SavedState, _pad, _require_cuda, _LDPAD, _dyk, _grad_views, _kmajor_gemm,
+                     _pack_rnn_stack, _gru_param_grads)
 from .vocab import PaddedBatch, pad_batch
 
 
@@ -32,18 +32,7 @@ class ReLU(nn.Module):
     """Marker (fused into the producing GEMM's epilogue)."""
 
 
-def _slots4(w3, H, order):
-    """[3H, K] gate rows (r, z, n) -> [4H, K] slot rows; order 'x' = (r, z, n, 0) for W_ih, 'h' = (r, z, 0, n) for W_hh."""
-    out = torch.zeros(4 * H, *w3.shape[1:], dtype=w3.dtype, device=w3.device)
-    out[:2 * H] = w3[:2 * H]
-    if order == "x":
-        out[2 * H:3 * H] = w3[2 * H:]
-    else:
-        out[3 * H:] = w3[2 * H:]
-    return out
-
-
-class VAE(nn.Module, _SavedState):
+class VAE(_SavedState, nn.Module):
     def __init__(self, vocab, dtype=torch.bfloat16):
         super().__init__()
         q_d_h, q_n_layers, d_n_layers, d_dropout, d_z, d_d_h = 256, 1, 3, 0.2, 160, 512     # mosesvae.py:31-40
@@ -77,10 +66,7 @@ class VAE(nn.Module, _SavedState):
         self.noise = "device"                # reparameterisation noise: "device" = drawn by the library inside the latent launch; "torch" = torch.randn on the device generator
         self.__dict__["noise_stream"] = ops.NoiseStream()
         self._init_saved_state()
-        self._pack_key, self._packed = None, {}
         self.__dict__["_side"] = None
-
-    apply = _apply_and_mark
 
     def _side_stream(self, dev):
         return ops.side_stream(dev)
@@ -341,25 +327,7 @@ class VAE(nn.Module, _SavedState):
         out[perm] = lp
         return out
 
-    # -- packed shadows: ONE multi-tensor pack launch    # -- packed shadows: ONE multi-tensor pack launch (ops.PackList) instead of ~60 few-microsecond launches per optimiser step
-    def _pack(self, dev):
-        params = self._plist()
-        key = _params_key(params) + (self.compute_dtype,)
-        if key == self._pack_key:
-            return self._packed
-        ptrs = (dev, self.compute_dtype) + tuple((id(p), p.data_ptr()) for p in params)     # id: a deepcopy must rebuild its own job table
-        if self.__dict__.get("_pack_ptrs") != ptrs:
-            with torch.no_grad():                      # the job table keeps plain (non-autograd) views of the parameters
-                self._build_pack(dev)
-            self.__dict__["_pack_ptrs"] = ptrs
-        with torch.no_grad():
-            self.__dict__["_pack_list"].run()
-        self._pack_key = key
-        return self._packed
-
     def _build_pack(self, dev):
-        """Allocate the shadows (zeroed: the empty gate slot of every 4-slot matrix and all padding are never written) and record the jobs
-        that fill them, each straight from a parameter (jobs of one launch must not depend on each other)."""
         ws, dt, f32 = self._ws, self.compute_dtype, torch.float32
         V = self.x_emb.num_embeddings
         Vp = _pad(V, 4)
@@ -367,26 +335,10 @@ class VAE(nn.Module, _SavedState):
         E = self.x_emb.weight
         P["E_p"] = ws.get("E_p", (V, Vp), f32, dev); P["ET_p"] = ws.get("ET_p", (V, Vp), f32, dev)
         pl.cast_transpose(E, V, V, dst=P["E_p"], dstT=P["ET_p"])
-        for name, rnn, nl in (("enc", self.encoder_rnn, 1), ("dec", self.decoder_rnn, self.decoder_rnn.num_layers)):
+        for name, rnn in (("enc", self.encoder_rnn), ("dec", self.decoder_rnn)):
             H = rnn.hidden_size
             ldw, ldwT = H + _LDPAD, 4 * H + _LDPAD
-            P[name] = dict(H=H, ldw=ldw, ldwT=ldwT, Whh=[], WhhT=[], Wih=[None], WihT=[None], bias=[])
-            for l in range(nl):
-                # gate rows (r, z, n) -> slots: W_hh (r, z, 0, n), W_ih (r, z, n, 0)
-                whh = getattr(rnn, f"weight_hh_l{l}")
-                w = ws.get(f"{name}_Whh{l}", (4 * H, ldw), dt, dev); wT = ws.get(f"{name}_WhhT{l}", (H, ldwT), dt, dev)
-                pl.cast_transpose(whh[:2 * H], 2 * H, H, dst=w[:2 * H], dstT=wT[:, :2 * H])
-                pl.cast_transpose(whh[2 * H:], H, H, dst=w[3 * H:], dstT=wT[:, 3 * H:4 * H])
-                P[name]["Whh"].append(w); P[name]["WhhT"].append(wT)
-                if l > 0:
-                    wih = getattr(rnn, f"weight_ih_l{l}")
-                    w = ws.get(f"{name}_Wih{l}", (4 * H, ldw), dt, dev); wT = ws.get(f"{name}_WihT{l}", (H, ldwT), dt, dev)
-                    pl.cast_transpose(wih, 3 * H, H, dst=w[:3 * H], dstT=wT[:, :3 * H])
-                    P[name]["Wih"].append(w); P[name]["WihT"].append(wT)
-                bi, bh = getattr(rnn, f"bias_ih_l{l}"), getattr(rnn, f"bias_hh_l{l}")
-                b4 = ws.get(f"{name}_bias{l}", (4 * H,), f32, dev)
-                pl.add(bi[:2 * H], bh[:2 * H], b4[:2 * H]); pl.copy(bi[2 * H:], b4[2 * H:3 * H]); pl.copy(bh[2 * H:], b4[3 * H:])
-                P[name]["bias"].append(b4)
+            P[name] = dict(H=H, ldw=ldw, ldwT=ldwT, **_pack_rnn_stack(pl, ws, rnn, name + "_", dt, dev, ldw, ldwT))
             # layer-0 input weights: the embedding part becomes a table, the z part (decoder) a dense projection
             w0 = getattr(rnn, "weight_ih_l0")
             wx = ws.get(f"{name}_Wx_p", (3 * H, Vp), f32, dev); wxT = ws.get(f"{name}_WxT", (V, 3 * H), f32, dev)
@@ -406,19 +358,7 @@ class VAE(nn.Module, _SavedState):
         Vp8 = _pad(V, 8)
         P["Wfc"] = ws.get("Wfc", (V, Hd + _LDPAD), dt, dev); P["WfcT"] = ws.get("WfcT", (Hd, _dyk(V) if dt == torch.bfloat16 else Vp8), dt, dev)
         pl.cast_transpose(self.decoder_fc.weight, V, Hd, dst=P["Wfc"], dstT=P["WfcT"])
-        self._packed = P
-        self.__dict__["_pack_list"] = pl
-
-
-def _kmajor_gemm(ws, tag, A, lda, M, Bm, ldb, N, K, out, dev):
-    """out[M,N] = A[:K,:M]^T . Bm[:K,:N] for K-major operands: TN kernel for bf16, transposes + NT for f32."""
-    if A.dtype == torch.bfloat16:
-        ops.gemm_tn(A, Bm, out, M, N, K, lda=lda, ldb=ldb)
-        return
-    ldT = _pad(K, 8) + 8
-    AT = ws.get(tag + "_AT", (M, ldT), torch.float32, dev); BT = ws.get(tag + "_BT", (N, ldT), torch.float32, dev)
-    ops.cast_transpose(A, K, M, dstT=AT, lds=lda); ops.cast_transpose(Bm, K, N, dstT=BT, lds=ldb)
-    ops.gemm_nt(AT, BT, out, M, N, ldT, lda=ldT, ldb=ldT)
+        self._set_pack(P, pl)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -584,22 +524,17 @@ def _dec_backward(mod, ws, P, grads, x_pad, lengths, drop, drecon, dy_ext, dz_ex
         # stream's compute-bound weight-gradient GEMMs -- the side stream is the longer of the two chains since the encoder's backward is one launch
         s4 = W("dec_s4", (4 * Hd,))
         for l in range(NL):
-            ops.colsum_t(dG_d[l].view(TB, ldg_d), TB, 4 * Hd, s4, ldx=ldg_d)
-            grads[f"decoder_rnn.bias_ih_l{l}"].copy_(s4[:3 * Hd])
-            grads[f"decoder_rnn.bias_hh_l{l}"][:2 * Hd].copy_(s4[:2 * Hd]); grads[f"decoder_rnn.bias_hh_l{l}"][2 * Hd:].copy_(s4[3 * Hd:])
+            _gru_param_grads(ws, "", grads, "decoder_rnn", l, dG_d[l].view(TB, ldg_d), ldg_d, None, None, ldh_d, Hd, TB, dev, s4=s4)
 
     def dec_weight_grads():
         # the 3 x (dW_hh[r, z], dW_hh[n], dW_ih) contractions of the stack, one split-K TN GEMM each (one grouped launch of full-K 256 x 256
         # tiles measured slower in round 5: 5.46 vs 5.18 ms per step at B = 1024)
         for l in range(NL):
-            a = dG_d[l].view(TB, ldg_d)
             hprev = hsx_d[l][:T].reshape(TB, ldh_d)                  # h_{t-1} for every t (slot 0 = h_0)
-            gw = grads[f"decoder_rnn.weight_hh_l{l}"]
-            _kmajor_gemm(ws, "dwhh_rz", a, ldg_d, 2 * Hd, hprev, ldh_d, Hd, TB, gw[:2 * Hd], dev)
-            _kmajor_gemm(ws, "dwhh_n", a[:, 3 * Hd:], ldg_d, Hd, hprev, ldh_d, Hd, TB, gw[2 * Hd:], dev)
-            if l > 0:                                                 # the layer's input: the output of layer l-1 (after its dropout in train mode)
+            xin = None                                                # the layer's input: the output of layer l-1 (after its dropout in train mode)
+            if l > 0:
                 xin = hd[l - 1].view(TB, ldh_d) if hd is not None else hsx_d[l - 1][1:].reshape(TB, ldh_d)
-                _kmajor_gemm(ws, "dwih", a, ldg_d, 3 * Hd, xin, ldh_d, Hd, TB, grads[f"decoder_rnn.weight_ih_l{l}"], dev)
+            _gru_param_grads(ws, "", grads, "decoder_rnn", l, dG_d[l].view(TB, ldg_d), ldg_d, hprev, xin, ldh_d, Hd, TB, dev)
         # layer-0 input = [emb(x_t), z]: table gradient for the embedding part (the z part is on the path to the encoder: main stream)
         dtbl3 = W("dec_dtbl3", (V, 3 * Hd))
         if onehot is not None:
@@ -687,13 +622,8 @@ def _enc_backward(mod, ws, P, grads, x_pad, lengths, eps, dz_tot, dkl, dlv_ext, 
                 [hsx_e[0][1:]], ldh_e, None, gates_e, dG_e, dstate_e, ldg=ldg_e, h0=[hsx_e[0][0]], ldh0=ldh_e,
                 lengths=lengths, dh_last=[dhq_tot], tag="moses_enc_bwd")
     a = dG_e[0].view(TB, ldg_e)
-    hprev = hsx_e[0][:T].reshape(TB, ldh_e)
-    gw = grads["encoder_rnn.weight_hh_l0"]
-    _kmajor_gemm(ws, "e_dwhh_rz", a, ldg_e, 2 * Hq, hprev, ldh_e, Hq, TB, gw[:2 * Hq], dev)
-    _kmajor_gemm(ws, "e_dwhh_n", a[:, 3 * Hq:], ldg_e, Hq, hprev, ldh_e, Hq, TB, gw[2 * Hq:], dev)
-    s4e = W("enc_s4", (4 * Hq,)); ops.colsum_t(a, TB, 4 * Hq, s4e, ldx=ldg_e)
-    grads["encoder_rnn.bias_ih_l0"].copy_(s4e[:3 * Hq])
-    grads["encoder_rnn.bias_hh_l0"][:2 * Hq].copy_(s4e[:2 * Hq]); grads["encoder_rnn.bias_hh_l0"][2 * Hq:].copy_(s4e[3 * Hq:])
+    # "e_": the decoder's weight gradients may still run on the side stream in this workspace (_MosesFn, saved_state_depth 1)
+    _gru_param_grads(ws, "e_", grads, "encoder_rnn", 0, a, ldg_e, hsx_e[0][:T].reshape(TB, ldh_e), None, ldh_e, Hq, TB, dev, s4=W("enc_s4", (4 * Hq,)))
     etbl3 = W("enc_dtbl3", (V, 3 * Hq))
     if onehot is not None:
         ops.gemm_tn(onehot, a, etbl3, V, 3 * Hq, TB, lda=Vp8, ldb=ldg_e)
@@ -705,12 +635,9 @@ def _enc_backward(mod, ws, P, grads, x_pad, lengths, eps, dz_tot, dkl, dlv_ext, 
     ops.gemm_nt(etblT, P["ET_p"], grads["encoder_rnn.weight_ih_l0"], 3 * Hq, V, Vp)
 
 
-def _grad_views(mod, ws, names, params, dev):
-    """Zeroed flat fp32 buffer + per-parameter views for `names`, plus the two halves' scratch shares of the embedding gradient."""
-    gflat = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=dev)
-    grads, off = {"_flat": [gflat]}, 0
-    for n, p in zip(names, params):
-        grads[n] = gflat[off:off + p.numel()].view(p.shape); off += p.numel()
+def _moses_grad_views(mod, ws, names, params, dev):
+    """_grad_views plus the two halves' scratch shares of the embedding gradient."""
+    grads = _grad_views(names, params, dev)
     V = mod.x_emb.num_embeddings
     grads["_dE_dec"] = ws.get("dE", (V, V), torch.float32, dev)
     grads["_dE_enc"] = ws.get("dE2", (V, V), torch.float32, dev)
@@ -746,7 +673,7 @@ class _MosesFn(torch.autograd.Function):
         P = mod._packed
         params = mod._plist()
         names = [n for n, _ in mod.named_parameters()]
-        grads = _grad_views(mod, ws, names, params, dev)
+        grads = _moses_grad_views(mod, ws, names, params, dev)
         onehot = _onehot(mod, ws, x_pad)
         dz_tot, finish = _dec_backward(mod, dws, P, grads, x_pad, lengths, drop, drecon, dy_ext, dz_ext, dy_ext is None, onehot)
         _enc_backward(mod, ws, P, grads, x_pad, lengths, eps, dz_tot, dkl, dlv_ext, onehot)
@@ -778,7 +705,7 @@ class _MosesEncFn(torch.autograd.Function):
         ws = mod._saved_ws(ctx.slot, ctx.gen, "mosesvae.VAE.forward_encoder", "enc")
         dev = x_pad.device
         names, params = mod._half_params("enc")
-        grads = _grad_views(mod, ws, names, params, dev)
+        grads = _moses_grad_views(mod, ws, names, params, dev)
         onehot = _onehot(mod, ws, x_pad)
         dz = dz_ext.contiguous().float() if dz_ext is not None else None
         _enc_backward(mod, ws, mod._packed, grads, x_pad, lengths, eps, dz, dkl, dlv_ext, onehot)
@@ -811,7 +738,7 @@ class _MosesDecFn(torch.autograd.Function):
         ws = mod._saved_ws(ctx.dslot, ctx.dgen, "mosesvae.VAE.forward_decoder", "dec")
         dev = x_pad.device
         names, params = mod._half_params("dec")
-        grads = _grad_views(mod, ws, names, params, dev)
+        grads = _moses_grad_views(mod, ws, names, params, dev)
         onehot = _onehot(mod, ws, x_pad)
         dz_tot, finish = _dec_backward(mod, ws, mod._packed, grads, x_pad, lengths, drop, drecon, dy_ext, None, dy_ext is None, onehot)
         finish()

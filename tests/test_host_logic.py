@@ -131,9 +131,8 @@ def test_product_path_refuses_cpu():
         mv.bce_kl_loss(torch.rand(2, 3, 4), torch.rand(2, 3, 4), torch.rand(2, 5), torch.rand(2, 5), 3)
 
 
-def test_forward_backward_bookkeeping_with_stubbed_kernels(monkeypatch):
-    """Runs the whole host-side orchestration on CPU tensors with every kernel launch replaced by a no-op:
-    checks argument bookkeeping (shapes, workspace names, gradient slots), not arithmetic."""
+def _stub_kernels(monkeypatch):
+    """Replace every kernel launch the modules make by a no-op that records its name (the returned list) and let them run on CPU tensors."""
     calls = []
 
     def stub(name):
@@ -142,12 +141,21 @@ def test_forward_backward_bookkeeping_with_stubbed_kernels(monkeypatch):
         return f
     for name in ("gemm_nt", "gemm_tn", "gemm_tn_f32_colsum", "colsum_t", "cast_transpose", "permute021", "gather_rows_tb", "scatter_rows_tb", "onehot_f32", "rowsum", "timesum", "colsum",
                  "selu_bwd", "conv1d_pack_weights", "conv1d_selu_fwd", "conv1d_selu_bwd", "lambda_fwd", "lambda_bwd", "softmax_tb_fwd", "softmax_tb_bwd",
-                 "rnn_fwd", "rnn_bwd"):
+                 "rnn_fwd", "rnn_bwd", "moses_latent_fwd", "moses_latent_bwd", "permute102", "ce_loss_fwd", "ce_loss_bwd", "mask_rows_tb", "onehot_tb",
+                 "relu_bwd"):
         monkeypatch.setattr(ops, name, stub(name))
     monkeypatch.setattr(ops.PackList, "run", lambda self: calls.append("pack_multi"))      # the multi-tensor pack launch
     monkeypatch.setattr(ops.TnF32Batch, "run", lambda self: calls.append(f"tn_f32_multi[{len(self.probs)}]"))       # the encoder's parameter-gradient GEMMs: ONE launch
     monkeypatch.setattr(ops.TnF32Batch, "add_conv_dw", lambda self, *a, **k: self.probs.append("conv"))
-    monkeypatch.setattr(M, "_require_cuda", lambda dev, what: None)
+    for mod in (M, mv.mosesvae, mv.models2d):
+        monkeypatch.setattr(mod, "_require_cuda", lambda dev, what: None)
+    return calls
+
+
+def test_forward_backward_bookkeeping_with_stubbed_kernels(monkeypatch):
+    """Runs the whole host-side orchestration on CPU tensors with every kernel launch replaced by a no-op:
+    checks argument bookkeeping (shapes, workspace names, gradient slots), not arithmetic."""
+    calls = _stub_kernels(monkeypatch)
     enc = mv.MolEncoder(i=24, o=16, c=12, h_size=56, num_lstm=2)
     dec = mv.MolDecoder(i=16, o=24, c=12, num_gru=2, h_size=32, dtype=torch.float32)
     idx = torch.zeros(3, 24, dtype=torch.long)
@@ -166,6 +174,36 @@ def test_forward_backward_bookkeeping_with_stubbed_kernels(monkeypatch):
     z3, _, _ = enc(idx, torch.zeros(3, 16))
     with pytest.raises(L.MvaeError):
         z2.sum().backward()
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+def test_models2d_and_moses_bookkeeping_with_stubbed_kernels(monkeypatch, dt):
+    """models2d.VAE and mosesvae.VAE through the same stubs: one pack launch per pack (models2d: no per-matrix cast_transpose in it, the three
+    conv packs beside it), a gradient of the right shape for every parameter."""
+    calls = _stub_kernels(monkeypatch)
+    m2 = mv.models2d.VAE(dtype=dt)
+    m2._pack(torch.device("cpu"))
+    assert calls == ["pack_multi"] + ["conv1d_pack_weights"] * 3
+    m2._pack(torch.device("cpu"))
+    assert len(calls) == 4                                          # nothing changed: no launch
+    recon, mu, logvar = m2(torch.zeros(3, 120, 35))
+    assert recon.shape == (3, 120, 35) and mu.shape == logvar.shape == (3, 2)
+    (recon.sum() + mu.sum() + logvar.sum()).backward()
+    assert calls.count("pack_multi") == 1 and calls.count("rnn_bwd") == 1
+    for n, p in m2.named_parameters():
+        assert p.grad is not None and p.grad.shape == p.shape, n
+    del calls[:]
+    moses = mv.mosesvae.VAE(mv.vocab.OneHotVocab(set("CNO()=c1")), dtype=dt)
+    x = [moses.string2tensor(s, device="cpu") for s in ("CC(=O)N", "c1ccO1", "CN")]
+    kl, recon, z, logvar, _, y = moses(x)
+    (kl + recon + z.sum() + logvar.sum() + y.sum()).backward()     # a gradient w.r.t. y: the decoder's weight gradients stay on the main stream
+    assert calls.count("pack_multi") == 1 and calls.count("rnn_fwd") == 2 and calls.count("rnn_bwd") == 2
+    for n, p in moses.named_parameters():
+        assert p.grad is not None and p.grad.shape == p.shape, n
+    moses.zero_grad(set_to_none=True)
+    kl, recon, _, _, _, y = moses(x)
+    (kl + recon + y.sum()).backward()
+    assert calls.count("pack_multi") == 1                           # parameters unchanged: the shadows are not repacked
 
 
 def test_shard_helpers():
