@@ -505,6 +505,27 @@ int mvae_relu_bwd(int64_t n, float* dy, const float* y, void* stream);
 int mvae_mask_rows_tb(int dtype, int T, int B, int64_t ld, const int32_t* lengths, void* buf, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Latent diagnostics of mosesvae.VAE (an addition: the reference's trainer has no evaluation of its latent code): the importance-weighted
+ * log-likelihood, the mutual information I(x; z) under the encoder (He et al. 2019, calc_mi, over the whole evaluated set) and, on the host,
+ * the active units.  fp32 throughout; every reduction runs in a fixed order without atomics (two runs are bitwise equal).  Sizes < 1,
+ * a leading dimension < dz or a NULL pointer an argument needs give MVAE_ERR_INVALID before anything is enqueued.
+ * mvae_gauss_iw_draw: K draws per molecule from q(z | x) = N(mu_b, exp(logvar_b)) (mu, logvar [B, ld]): row r = b*K + k of z_out [B*K, dz]
+ *   is z = mu_b + exp(logvar_b / 2) * eps_r and logw_out[r] = 0.5 * sum_d (eps^2 + logvar - z^2) = log N(z; 0, I) - log N(z; mu, sigma^2).
+ *   eps == NULL: eps_rd = n(seed, offset + r*dz + d), the counter normal of mvae_lambda_fwd; else eps is read from [B*K, dz].
+ * mvae_group_logmeanexp: per group g of K values v_k = a[gK + k] + b[gK + k] (b may be NULL): lme_out[g] = m + log sum_k exp(v_k - m) - log K
+ *   with m = max_k v_k, and mean_out[g] = sum_k v_k / K.  A NaN makes its own group's lme NaN; an all -inf group gives -inf.
+ * mvae_gauss_pairwise_lse: out[i] = logsumexp_j log N(z_i; mu_j, exp(logvar_j)) over Nx diagonal Gaussians (mu, logvar [Nx, ldp]) for Nz
+ *   points (z [Nz, ldz]) -- a direct difference per (pair, dimension), not an expanded square.  dz <= 192 (else MVAE_ERR_UNSUPPORTED).
+ *   Workspace: mvae_gauss_pairwise_lse_workspace(Nz, Nx, dz) bytes (8-byte aligned; 0: none needed), else MVAE_ERR_WORKSPACE.
+ */
+int mvae_gauss_iw_draw(int B, int K, int dz, const float* mu, const float* logvar, int64_t ld, const float* eps, uint32_t seed, uint64_t offset,
+                       float* z_out, float* logw_out, void* stream);
+int mvae_group_logmeanexp(int G, int K, const float* a, const float* b, float* lme_out, float* mean_out, void* stream);
+size_t mvae_gauss_pairwise_lse_workspace(int Nz, int Nx, int dz);
+int mvae_gauss_pairwise_lse(int Nz, int Nx, int dz, const float* z, int64_t ldz, const float* mu, const float* logvar, int64_t ldp, float* out,
+                            void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Optimiser surface (K14 + K15): torch.nn.utils.clip_grad_norm_(params, max_norm) (train.py:102) followed by
  * torch.optim.Adam.step() (train.py:81,104) on a FLAT fp32 parameter / gradient / m / v buffer.
  *   mvae_sumsq: partial[i] = sum of squares of chunk i (deterministic); norm_out[0] = sqrt(total) is

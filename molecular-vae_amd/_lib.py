@@ -161,6 +161,10 @@ SIGNATURES = {
     "mvae_sumsq": (_i, [_i64, _vp, _vp, _vp]),
     "mvae_clip_adam": (_i, [_i64, _vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _i, _vp, _i, _vp, _vp]),
     "mvae_clip_sgd": (_i, [_i64, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "mvae_gauss_iw_draw": (_i, [_i, _i, _i, _vp, _vp, _i64, _vp, C.c_uint32, C.c_uint64, _vp, _vp, _vp]),
+    "mvae_group_logmeanexp": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mvae_gauss_pairwise_lse_workspace": (_sz, [_i, _i, _i]),
+    "mvae_gauss_pairwise_lse": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -15,6 +15,7 @@ gradients enabled) takes the token mean of the reconstruction loss (mosesvae.py:
 (``dp_global_token_mean``, one 4-byte all-reduce on ``dp_group``), so that the all-reduced gradient equals the single-process gradient of
 the global batch; eval / no_grad forwards never communicate.
 """
+import math
 import os
 
 import torch
@@ -26,6 +27,23 @@ from . import ops
 from .models import (LinearWeights, EmbeddingWeights, RNNWeights, _Workspace, _SavedState, _pad, _require_cuda, _LDPAD, _dyk, _grad_views, _kmajor_gemm,
                      _pack_rnn_stack, _gru_param_grads)
 from .vocab import PaddedBatch, pad_batch
+
+
+class _RowsWorkspace(_Workspace):
+    """A _Workspace whose buffers are views of grow-only flat allocations, one per (name, row width, dtype, device): the passes of
+    iw_log_likelihood, whose (rows, T) change from pass to pass, reuse one set of decoder buffers instead of allocating and zero-filling a
+    new set per shape.  Every buffer of the teacher-forced decoder (_dec_forward) is an array of rows of a fixed width, and the columns
+    that must stay zero (a leading dimension's padding, the unused gate slot of a [*, 4H] addend) are never written, so they stay zero
+    under any row count; the rows themselves are written before they are read in every pass.  (Not for the encoder half: it reads slot 0
+    of its hidden-state buffer as the zero initial state without writing it.)"""
+
+    def get(self, name, shape, dtype, device):
+        key, n = (name, shape[-1], dtype, device), math.prod(shape)
+        b = self.bufs.get(key)
+        if b is None or b.numel() < n:
+            self.bufs[key] = None                                          # the smaller buffer goes before the larger one is allocated
+            b = self.bufs[key] = torch.zeros(n, dtype=dtype, device=device)
+        return b[:n].view(shape)
 
 
 class ReLU(nn.Module):
@@ -326,6 +344,72 @@ class VAE(_SavedState, nn.Module):
         out = torch.empty_like(lp)
         out[perm] = lp
         return out
+
+    _IW_ROWS = 4096         # decoder rows per teacher-forced pass of iw_log_likelihood (bounds its workspace, not its result)
+
+    @torch.no_grad()
+    def iw_log_likelihood(self, x, n_samples=500, eps=None, seed=None):
+        """Importance-weighted log-likelihood (Burda et al.; He et al. 2019 evaluate with K = 500): per molecule, the encoder's
+        q(z | x) = N(mu, exp(logvar)) (eps = 0, as forward_encoder(x, eps=0)), K draws z_k = mu + exp(logvar / 2) * eps_k and
+        log w_k = log p(x | z_k) + log N(z_k; 0, I) - log N(z_k; mu, sigma^2), log p(x | z_k) as `score` gives it.  Returns
+        (log_px, elbo), fp32 [B] device tensors in input order: log_px = logsumexp_k log w_k - log K (-log_px is the NLL estimate) and
+        elbo = mean_k log w_k over the same draws (log_px >= elbo).  x: id tensors (bos first) or strings, in any order.  eps [B, K, d_z]
+        (input order) injects the noise; else it is drawn from self.noise_stream, or from a fresh stream of `seed`, molecule by molecule in
+        the length-sorted order the decoder runs (a stable sort: molecules of equal length keep their input order).  So with drawn noise,
+        a permutation of x permutes the result only when it keeps the relative order of molecules of equal length; two molecules of the
+        same length that swap places also swap their draws.  No gradients, no dropout."""
+        seqs = [self.string2tensor(s, device="cpu") if isinstance(s, str) else torch.as_tensor(s, dtype=torch.long) for s in x]
+        stream = ops.NoiseStream(seed) if seed is not None else self.noise_stream
+        log_px, elbo, _, _ = self._iw(seqs, n_samples, eps, stream)
+        return log_px, elbo
+
+    def _iw(self, seqs, n_samples, eps, stream):
+        """iw_log_likelihood on a list of id tensors; also returns the encoder's (mu, logvar) [B, d_z] in input order."""
+        B, K, dz = len(seqs), int(n_samples), self.d_z
+        if B < 1 or K < 1:
+            raise ValueError(f"iw_log_likelihood: needs at least one molecule and n_samples >= 1, got {B} and {n_samples}")
+        if eps is not None and tuple(eps.shape) != (B, K, dz):
+            raise ValueError(f"iw_log_likelihood: eps must be [{B}, {K}, {dz}], got {tuple(eps.shape)}")
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.iw_log_likelihood")
+        order = sorted(range(B), key=lambda b: -int(seqs[b].numel()))          # the GRUs' packed layout wants lengths descending
+        lens = [int(seqs[b].numel()) for b in order]
+        perm = torch.tensor(order, dtype=torch.long, device=dev)
+        x_pad, len_t = self._batch([seqs[b].to(dev) for b in order])
+        V, f32 = self.x_emb.num_embeddings, torch.float32
+        P = self._pack(dev)
+        # workspaces of their own: a pending forward's saved state (self._ws) stays intact
+        ws_e = self.__dict__.setdefault("_iw_enc_ws", _Workspace())
+        mu, _, lv, _ = _enc_forward(self, ws_e, P, x_pad, len_t, torch.zeros(B, dz, device=dev))      # eps = 0: z = mu
+        lv = lv.clone()
+        if eps is None:
+            seed_, off = stream.take(B * K * dz)
+            eps_s = None
+        else:
+            seed_, off = 0, 0
+            eps_s = eps.to(dev).float()[perm].reshape(B * K, dz).contiguous()
+        lp, logw = torch.empty(B * K, device=dev), torch.empty(B * K, device=dev)
+        ws = self.__dict__.setdefault("_iw_ws", _RowsWorkspace())      # one set of decoder buffers for passes of every (rows, T)
+        R = self._IW_ROWS
+        if K <= R:                                                       # whole molecules per pass
+            chunks = [(b0, min(b0 + R // K, B), 0, K) for b0 in range(0, B, R // K)]
+        else:                                                            # one molecule's draws over several passes
+            chunks = [(b, b + 1, k0, min(k0 + R, K)) for b in range(B) for k0 in range(0, K, R)]
+        for b0, b1, k0, k1 in chunks:
+            nb, nk = b1 - b0, k1 - k0
+            r0, rows, T = b0 * K + k0, nb * nk, lens[b0]
+            z = ws.get("iw_z", (rows, dz), f32, dev)
+            ops.gauss_iw_draw(mu[b0:b1], lv[b0:b1], z, logw[r0:r0 + rows], nb, nk, dz,
+                              eps=None if eps_s is None else eps_s[r0:r0 + rows], seed=seed_, offset=off + r0 * dz)
+            xc = x_pad[b0:b1, :T].repeat_interleave(nk, 0).contiguous()          # molecule-major: lengths stay descending
+            y_tb = _dec_forward(self, ws, P, xc, len_t[b0:b1].repeat_interleave(nk, 0), z, None, heads=False)
+            ops.ce_rows(y_tb, V, xc, self.pad, lp[r0:r0 + rows], rows, T, V)
+        lme, mean = torch.empty(B, device=dev), torch.empty(B, device=dev)
+        ops.group_logmeanexp(lp, lme, mean, B, K, b=logw)
+        out = [torch.empty_like(t) for t in (lme, mean, mu, lv)]
+        for o, t in zip(out, (lme, mean, mu, lv)):
+            o[perm] = t
+        return tuple(out)
 
     def _build_pack(self, dev):
         ws, dt, f32 = self._ws, self.compute_dtype, torch.float32

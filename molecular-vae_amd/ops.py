@@ -498,6 +498,27 @@ def ce_rows(logits, ldl, x, pad, out, B, T, V):
     """out[b] = log p(x[b] | z) from time-major teacher-forced logits, pad targets ignored (mvae_ce_rows_fwd)."""
     check(L.load().mvae_ce_rows_fwd(B, T, V, ptr(logits), ldl, ptr(x), pad, ptr(out), stream_ptr()), "mvae_ce_rows_fwd")
 
+def gauss_iw_draw(mu, logvar, z_out, logw_out, B, K, dz, eps=None, seed=0, offset=0, ld=None):
+    """K draws per molecule from N(mu_b, exp(logvar_b)): z_out [B*K, dz] (row b*K + k), logw_out [B*K] = log N(z; 0, I) - log N(z; mu, sigma^2);
+    eps [B*K, dz] injected, or None: the counter normal n(seed, offset + row*dz + d) (mvae_gauss_iw_draw)."""
+    check(L.load().mvae_gauss_iw_draw(B, K, dz, ptr(mu), ptr(logvar), ld or dz, ptr(eps), int(seed) & 0xFFFFFFFF, int(offset), ptr(z_out),
+                                      ptr(logw_out), stream_ptr()), "mvae_gauss_iw_draw")
+
+
+def group_logmeanexp(a, lme_out, mean_out, G, K, b=None):
+    """Per group of K values v = a (+ b): lme_out[g] = log mean_k exp(v), mean_out[g] = mean_k v (mvae_group_logmeanexp)."""
+    check(L.load().mvae_group_logmeanexp(G, K, ptr(a), ptr(b), ptr(lme_out), ptr(mean_out), stream_ptr()), "mvae_group_logmeanexp")
+
+
+def gauss_pairwise_lse(z, mu, logvar, out, Nz, Nx, dz, ldz=None, ldp=None):
+    """out[i] = logsumexp_j log N(z_i; mu_j, exp(logvar_j)) (mvae_gauss_pairwise_lse; its workspace comes from Scratch)."""
+    lib = L.load()
+    nb = lib.mvae_gauss_pairwise_lse_workspace(Nz, Nx, dz)
+    ws = Scratch.get(nb, out.device, "pairwise_lse") if nb else None
+    check(lib.mvae_gauss_pairwise_lse(Nz, Nx, dz, ptr(z), ldz or dz, ptr(mu), ptr(logvar), ldp or dz, ptr(out), ptr(ws), nb, stream_ptr()),
+          "mvae_gauss_pairwise_lse")
+
+
 def sample_uniform(seed, step, B):
     """Host restatement of the sampling step's uniforms u(b) = hash(seed, step * B + b) / 2^32 (tests)."""
     import numpy as np

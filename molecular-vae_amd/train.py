@@ -747,7 +747,7 @@ def moses_reconstruction(model, batches, beam_width=1, max_len=100):
     kept = []
     for batch in batches:
         if isinstance(batch, PaddedBatch):
-            seqs = [batch.x_pad[b, :int(batch.lengths[b])] for b in range(batch.x_pad.shape[0])]
+            seqs = [batch.x_pad[b, :n] for b, n in enumerate(batch.lengths.tolist())]
         else:
             seqs = list(batch)
         B = len(seqs)
@@ -762,3 +762,62 @@ def moses_reconstruction(model, batches, beam_width=1, max_len=100):
         hits += sum(model.vocabulary.ids2string(ids[b][:ends[b]], rem_bos=True, rem_eos=True) == model.tensor2string(seqs[b].cpu())
                     for b in range(len(seqs)))
     return hits / max(n, 1), float(lp_sum) / max(n, 1)
+
+
+def active_units(mu, delta=0.01):
+    """Active units of a latent code (Burda et al.; He et al.'s calc_au): the number of dimensions d whose sample variance over the set
+    (divided by N - 1) of mu[:, d] exceeds `delta`, computed in float64, as a 0-d tensor on mu's device (0 for fewer than two rows)."""
+    mu = mu.double()
+    if mu.shape[0] < 2:
+        return torch.zeros((), dtype=torch.int64, device=mu.device)
+    return (mu.var(0, unbiased=True) > delta).sum()
+
+
+def moses_latent_diagnostics(model, batches, n_samples=500, seed=None):
+    """Whether a ``mosesvae.VAE`` uses its latent code (an addition; the measures of He et al. 2019, *Lagging Inference Networks and
+    Posterior Collapse in VAEs*), over every molecule of `batches` (lists of id tensors, bos first, or strings, or PaddedBatches):
+      nll    mean over molecules of -log p(x), the importance-weighted estimate of ``VAE.iw_log_likelihood`` with K = n_samples;
+      nll_per_token / ppl   sum of those NLLs over the tokens ``VAE.score`` counts (len - 1 per molecule) / exp of it;
+      elbo   mean of elbo_K (the same draws); kl   mean analytic KL(q(z | x) || N(0, I));
+      mi     I(x; z) under the encoder as He et al.'s calc_mi, but over the whole set (one draw z_i per molecule, log q(z_i) the log-mean of
+             q(z_i | x_j) over all j: mvae_gauss_pairwise_lse), where a per-batch average is biased low at small batches;
+      au     dimensions whose mu varies across the set by more than 0.01 (sample variance, Burda et al.).
+    Draws come from model.noise_stream, or a fresh stream of `seed`: the IW draws of each batch in turn, then one per molecule for mi.
+    au is computed by `active_units`.  Returns a dict of Python floats (n_molecules, n_tokens, nll, nll_per_token, ppl, elbo, kl, mi, au);
+    the host waits once, at the end (and once per PaddedBatch whose lengths are on the device, to read them), and the model's train /
+    eval mode is restored."""
+    from .vocab import PaddedBatch
+    dev, dz = model.device, model.d_z
+    was_training = model.training
+    model.eval()
+    try:
+        stream = ops.NoiseStream(seed) if seed is not None else model.noise_stream
+        nll, elbo, mus, lvs, n_tok = [], [], [], [], 0
+        for batch in batches:
+            if isinstance(batch, PaddedBatch):                  # its lengths in one copy (a wait when they live on the device)
+                seqs = [batch.x_pad[b, :n] for b, n in enumerate(batch.lengths.tolist())]
+            else:
+                seqs = [model.string2tensor(s, device="cpu") if isinstance(s, str) else torch.as_tensor(s, dtype=torch.long) for s in batch]
+            log_px, el, mu, lv = model._iw(seqs, n_samples, None, stream)
+            n_tok += sum(int(s.numel()) - 1 for s in seqs)
+            nll.append(-log_px); elbo.append(el); mus.append(mu); lvs.append(lv)
+        if not mus:
+            raise ValueError("moses_latent_diagnostics: no molecules")
+        mu, lv = torch.cat(mus), torch.cat(lvs)
+        N = mu.shape[0]
+        seed_, off = stream.take(N * dz)
+        z, logw, lse = torch.empty(N, dz, device=dev), torch.empty(N, device=dev), torch.empty(N, device=dev)
+        ops.gauss_iw_draw(mu, lv, z, logw, N, 1, dz, seed=seed_, offset=off)
+        ops.gauss_pairwise_lse(z, mu, lv, lse, N, N, dz)
+        mu64, lv64 = mu.double(), lv.double()
+        neg_entropy = (-0.5 * dz * math.log(2 * math.pi) - 0.5 * (1 + lv64).sum(1)).mean()
+        mi = neg_entropy - (lse.double() - math.log(N)).mean()
+        kl = (0.5 * (lv64.exp() + mu64 ** 2 - 1 - lv64).sum(1)).mean()
+        au = active_units(mu64).double()
+        nll_sum = torch.cat(nll).double().sum()
+        vals = torch.stack([nll_sum, torch.cat(elbo).double().mean(), kl, mi, au]).tolist()
+    finally:
+        model.train(was_training)
+    nll_sum, elbo_m, kl, mi, au = vals
+    return dict(n_molecules=float(N), n_tokens=float(n_tok), nll=nll_sum / N, nll_per_token=nll_sum / n_tok, ppl=math.exp(nll_sum / n_tok),
+                elbo=elbo_m, kl=kl, mi=mi, au=au)
