@@ -1,0 +1,89 @@
+#!/usr/bin/env python3
+"""The MOSES generation run (hugesample.py's surface: sample in batches of 8192, hash, count unique / valid / total, log a
+``time,unique,valid,total`` CSV and samples per second) on the MI355X path.  The reference moves every sampled string to a hasher process;
+here ``mv.moses_generate`` hashes the token rows inside the sampling launches and deduplicates them on the device, so only sequences not
+seen before in their round reach the host; the rounds are merged in a dictionary.  Checkpoint and vocabulary as ``examples/train_moses.py``
+writes them (without them: a seeded random model over a synthetic corpus' vocabulary, which exercises the path but generates noise).
+``valid`` needs rdkit (``Chem.MolFromSmiles``); without it the column is left empty.
+
+    python examples/sample_moses.py --ckpt trained_save.pt --vocab vocab.pkl --rounds 10 --top_p 0.95
+"""
+import argparse
+import os
+import pickle
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import molecular_vae_amd as mv                          # noqa: E402
+from molecular_vae_amd import data as D, mosesvae as MV, vocab as VC   # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--ckpt", default=None)
+ap.add_argument("--vocab", default=None)
+ap.add_argument("-b", "--batch_size", default=8192, type=int)                # hugesample.py:113
+ap.add_argument("--batches_per_round", default=4, type=int)
+ap.add_argument("--rounds", default=5, type=int)
+ap.add_argument("--max_len", default=100, type=int)
+ap.add_argument("--temp", default=1.0, type=float)
+ap.add_argument("--top_k", default=None, type=int)
+ap.add_argument("--top_p", default=None, type=float)
+ap.add_argument("--prior", default="normal", choices=["normal", "zeros"], help="zeros = sample_z_prior as the reference is written")
+ap.add_argument("--seed", default=0, type=int)
+ap.add_argument("--log", default="log_small.csv")
+ap.add_argument("--out", default=None, help="write the unique strings with their counts here (tab separated)")
+args = ap.parse_args()
+
+try:
+    from rdkit import Chem, rdBase
+    rdBase.DisableLog("rdApp.error")
+except ImportError:
+    Chem = None
+
+dev = torch.device("cuda", 0)
+if args.vocab:
+    with open(args.vocab, "rb") as f:
+        vocab = pickle.load(f)
+else:
+    vocab = VC.OneHotVocab.from_data(D.synthetic_smiles(2048, seed=0))
+torch.manual_seed(42)
+model = MV.VAE(vocab)
+if args.ckpt:
+    model.load_state_dict(mv.strip_module_prefix(torch.load(args.ckpt, map_location="cpu")))
+model = model.to(dev).eval()
+model.prior = args.prior
+model.seed_noise(args.seed)
+
+
+def is_valid(s):
+    try:
+        return Chem.MolFromSmiles(s) is not None
+    except Exception:
+        return False
+
+
+seen, total, valid = {}, 0, 0
+per_round = args.batch_size * args.batches_per_round
+start = time.time()
+with open(args.log, "w", buffering=1) as f:
+    f.write("time,unique,valid,total\n")
+    for r in range(args.rounds):
+        res = mv.moses_generate(model, per_round, batch_size=args.batch_size, max_len=args.max_len, temp=args.temp, top_k=args.top_k,
+                                top_p=args.top_p, seed=args.seed + r * args.batches_per_round)
+        total += res["total"]
+        for s, c in zip(res["strings"], res["counts"]):
+            if s not in seen:
+                seen[s] = 0
+                if Chem is not None and is_valid(s):
+                    valid += 1
+            seen[s] += c
+        now = time.time()
+        f.write("{0},{1},{2},{3}\n".format(now, len(seen), valid if Chem is not None else "", total))
+        print(f"round {r}: unique {len(seen)} ({len(seen) / total:.3f}), sampled {total}, samples per second {total / (now - start):.0f}, "
+              f"unique per second {len(seen) / (now - start):.0f}" + (f", valid unique {valid}" if Chem is not None else ""), flush=True)
+if args.out:
+    with open(args.out, "w") as f:
+        for s, c in sorted(seen.items(), key=lambda kv: -kv[1]):
+            f.write(f"{s}\t{c}\n")

@@ -479,6 +479,26 @@ int mvae_permute102(int T, int B, int V, const float* in, float* out, void* stre
 int mvae_moses_sample_step(int dtype, int B, int V, int H, const void* h_top, int64_t ldh, const void* w_fc, int64_t ldw, const float* bias, float temp,
                            uint32_t seed, int step, int eos_id, const float* table, int W, const float* base, float* add_out, int64_t* x, int64_t x_ld,
                            int64_t* end_pads, uint8_t* eos_mask, int64_t* w_out, void* stream);
+/* The filtered sibling of mvae_moses_sample_step (an addition: the reference samples from the full softmax only): top-k and nucleus (top-p)
+ * truncation, the sample's log-probability under the distribution it was drawn from, and a running hash of the row's tokens.  Same shape
+ * and constraints (V <= 64, the head must fit the LDS, bf16 and f32), one launch per generated token.  Per row b:
+ *   1. p = softmax(decoder_fc(h_top[b]) / temp), with the fp32 arithmetic of mvae_moses_sample_step in the same order.
+ *   2. The classes are ranked in the total order (p descending, class id ascending); before(v) = sum of p_u over the classes ranked before v.
+ *   3. Keep set = {rank < top_k} (top_k == 0: off; valid 0 .. V) intersected with {before(v) < top_p * sum(p)}, i.e. the shortest rank
+ *      prefix whose mass reaches top_p, the rank-0 class always kept (top_p >= 1: off; valid (0, 1], larger values mean off).  Both
+ *      filters look at the unfiltered p: there is no renormalisation between them.
+ *   4. q_v = keep_v ? p_v : 0; the sample w is the first kept class, in class-id order, with cumsum(q)_v > u * sum(q), u as in
+ *      mvae_moses_sample_step.  With both filters off the tokens are bitwise those of mvae_moses_sample_step.
+ *   5. Bookkeeping (x, end_pads, eos_mask), w_out and the next step's add_out row exactly as mvae_moses_sample_step.
+ *   6. If the row had not ended before this step (the <eos> step itself counts): logq[b] += log(q_w / sum(q)) (fp32, exact logf) and
+ *      hash[b] = (hash[b] ^ w) * 0x100000001b3 mod 2^64 -- 64-bit FNV-1a over the token ids x[b, 1 : end], one "byte" per id (<bos> is not
+ *      hashed, <eos> is).  The caller initialises logq to 0 and hash to the FNV offset basis 0xcbf29ce484222325.  Either may be NULL.
+ * Refused before anything is enqueued: what mvae_moses_sample_step refuses, with its codes, a dtype other than f32 / bf16, top_k outside
+ * 0 .. V and top_p <= 0 or NaN (MVAE_ERR_INVALID). */
+int mvae_moses_sample_filtered_step(int dtype, int B, int V, int H, const void* h_top, int64_t ldh, const void* w_fc, int64_t ldw, const float* bias,
+                                    float temp, int top_k, float top_p, uint32_t seed, int step, int eos_id, const float* table, int W,
+                                    const float* base, float* add_out, int64_t* x, int64_t x_ld, int64_t* end_pads, uint8_t* eos_mask,
+                                    int64_t* w_out, float* logq /* [B] or NULL */, int64_t* hash /* [B] or NULL */, void* stream);
 /* Beam-search decoding (an addition beyond the reference, which only samples): R = B * K rows, molecule m owning rows m*K .. m*K + K-1.
  * mvae_moses_beam_step: one launch per generated token behind the GRU step.  logp = log_softmax(decoder_fc(h_top)) (w_fc [V, ldw] dtype,
  *   V <= 64 else MVAE_ERR_UNSUPPORTED; 1 <= K <= min(16, V) else MVAE_ERR_INVALID).  An active beam proposes its top-K tokens at

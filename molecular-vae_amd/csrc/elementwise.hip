@@ -1013,6 +1013,82 @@ __global__ __launch_bounds__(256) void moses_sample_step_kernel(int B, int V, in
   }
 }
 
+// The filtered sibling of moses_sample_step_kernel (top-k / nucleus truncation, the sample's log-probability, a running FNV-1a hash of the
+// row's tokens; no reference counterpart).  Same shape, and the same fp32 arithmetic in the same order up to the prefix sum of e.  Class v
+// lives in lane v, so its rank in the order (p desc, id asc) and the mass ranked before it come out of one pass over u = 0 .. V-1 of
+// "read lane u (uniform index), compare, add".  keep = (rank < top_k, 0: off) and (before < top_p * sum(p) or rank 0; top_p >= 1: off), both
+// on the unfiltered p;  q = keep ? e : 0;  the draw is the first KEPT class with cumsum(q) > u * sum(q).  With both filters off q == e and
+// the draw is the existing one.  A row that had not ended before this step adds log(q_w / sum q) to logq[b] and folds w into hash[b].
+template <typename T>
+__global__ __launch_bounds__(256) void moses_sample_filtered_step_kernel(int B, int V, int H, const T* __restrict__ h, long ldh, const T* __restrict__ wfc,
+                                                                         long ldw, const float* __restrict__ bias, float inv_temp, int top_k, float top_p,
+                                                                         uint32_t seed, int step, int eos_id, const float* __restrict__ table, int W,
+                                                                         const float* __restrict__ base, float* __restrict__ add_out,
+                                                                         int64_t* __restrict__ x, long x_ld, int64_t* __restrict__ end_pads,
+                                                                         uint8_t* __restrict__ eos_mask, int64_t* __restrict__ w_out,
+                                                                         float* __restrict__ logq, int64_t* __restrict__ hash) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  T* ws = reinterpret_cast<T*>(smem_raw);                    // [V][H]
+  for (int i = threadIdx.x; i < V * H; i += 256) ws[i] = wfc[(long)(i / H) * ldw + (i % H)];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool filtered = top_k > 0 || top_p < 1.f;            // kernel-uniform
+  for (int b = blockIdx.x * 4 + wave; b < B; b += gridDim.x * 4) {
+    float mine = -INFINITY;
+    for (int v = 0; v < V; ++v) {
+      float a = 0.f;
+      for (int k = lane; k < H; k += 64) a += TT<T>::ld(h + (long)b * ldh + k) * TT<T>::ld(ws + (long)v * H + k);
+      a = wave_sum(a);
+      if (lane == v) mine = (a + (bias ? bias[v] : 0.f)) * inv_temp;
+    }
+    const float mx = wave_max(mine);
+    const float e = (lane < V) ? __expf(mine - mx) : 0.f;
+    float c = e;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const float up = __shfl_up(c, o, 64); if (lane >= o) c += up; }
+    float tot = __shfl(c, 63, 64);
+    bool keep = lane < V;
+    float q = e;
+    if (filtered) {
+      int rank = 0;
+      float before = 0.f;
+      for (int u = 0; u < V; ++u) {                          // uniform index: a lane read, not a permute
+        const float eu = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e), u));
+        if (eu > e || (eu == e && u < lane)) { ++rank; before += eu; }
+      }
+      keep = keep && (top_k == 0 || rank < top_k) && (!(top_p < 1.f) || rank == 0 || before < top_p * tot);
+      q = keep ? e : 0.f;
+      c = q;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) { const float up = __shfl_up(c, o, 64); if (lane >= o) c += up; }
+      tot = __shfl(c, 63, 64);
+    }
+    const uint32_t hsh = drop_hash_u32(seed, (uint32_t)((long)step * B + b));
+    const float u = (float)hsh * (1.0f / 4294967296.0f) * tot;
+    const unsigned long long kept = __ballot(keep);          // never empty: the rank-0 class is kept
+    const unsigned long long above = __ballot(keep && c > u);
+    const int w = above ? (int)__builtin_ctzll(above) : (kept ? 63 - (int)__builtin_clzll(kept) : V - 1);   // (u rounds up to tot: the last kept class)
+    const float qw = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q), w));
+    if (lane == 0) {
+      const bool done = eos_mask[b] != 0;
+      if (!done) {
+        x[(long)b * x_ld + step] = w;
+        if (w == eos_id) { end_pads[b] = step + 1; eos_mask[b] = 1; }
+        if (logq) logq[b] += logf(qw / tot);
+        if (hash) hash[b] = (int64_t)(((uint64_t)hash[b] ^ (uint64_t)w) * 0x100000001b3ULL);
+      }
+      w_out[b] = w;
+    }
+    const float* trow = table + (long)w * W;
+    const float* brow = base + (long)b * W;
+    float* orow = add_out + (long)b * W;
+    for (int cidx = lane * 4; cidx < W; cidx += 256) {
+      const float4 tv = *reinterpret_cast<const float4*>(trow + cidx), bv = *reinterpret_cast<const float4*>(brow + cidx);
+      *reinterpret_cast<float4*>(orow + cidx) = make_float4(tv.x + bv.x, tv.y + bv.y, tv.z + bv.z, tv.w + bv.w);
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------- beam-search decoding step (no reference counterpart)
 // ONE launch per generated token for everything behind the GRU step, for R = B * K rows (molecule m owns rows m*K .. m*K + K-1, beam k of it
 // being row m*K + k):  logp = log_softmax(decoder_fc(h_top));  an active beam r proposes its own top-K tokens at score[r] + logp, a finished
@@ -1882,6 +1958,41 @@ int mvae_moses_sample_step(int dtype, int B, int V, int H, const void* h_top, in
     hipLaunchKernelGGL((moses_sample_step_kernel<float>), dim3(blocks), dim3(256), lds, st, B, V, H, (const float*)h_top, (long)ldh, (const float*)w_fc, (long)ldw,
                        bias, 1.f / temp, seed, step, eos_id, table, W, base, add_out, x, (long)x_ld, end_pads, eos_mask, w_out);
   else return MVAE_ERR_INVALID;
+  MVAE_CHECK_HIP(hipGetLastError());
+  return MVAE_OK;
+}
+
+int mvae_moses_sample_filtered_step(int dtype, int B, int V, int H, const void* h_top, int64_t ldh, const void* w_fc, int64_t ldw, const float* bias,
+                                    float temp, int top_k, float top_p, uint32_t seed, int step, int eos_id, const float* table, int W,
+                                    const float* base, float* add_out, int64_t* x, int64_t x_ld, int64_t* end_pads, uint8_t* eos_mask,
+                                    int64_t* w_out, float* logq, int64_t* hash, void* stream) {
+  if (!h_top || !w_fc || !table || !base || !add_out || !x || !end_pads || !eos_mask || !w_out) return MVAE_ERR_INVALID;
+  if (dtype != MVAE_F32 && dtype != MVAE_BF16) return MVAE_ERR_INVALID;
+  if (B < 1 || V < 1 || V > 64 || H < 1 || (W & 3) || W < 4 || !(temp > 0.f) || step < 0) return MVAE_ERR_INVALID;
+  if (top_k < 0 || top_k > V || !(top_p > 0.f)) return MVAE_ERR_INVALID;     // (a NaN top_p fails the comparison)
+  const size_t lds = (size_t)V * H * (dtype == MVAE_BF16 ? 2 : 4);
+  if (lds > 160 * 1024) return MVAE_ERR_UNSUPPORTED;                 // the head must fit the CU's LDS, as in mvae_moses_sample_step
+  if (lds > 64 * 1024) {                                              // above the default dynamic-LDS limit: opt in
+    static std::atomic<bool> attr[64];
+    int dev_id = 0;
+    MVAE_CHECK_HIP(hipGetDevice(&dev_id));
+    if (dev_id < 0 || dev_id >= 64 || !attr[dev_id].load(std::memory_order_acquire)) {
+      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(moses_sample_filtered_step_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(moses_sample_filtered_step_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      if (dev_id >= 0 && dev_id < 64) attr[dev_id].store(true, std::memory_order_release);
+    }
+  }
+  if (top_p > 1.f) top_p = 1.f;                                       // larger values mean off
+  int blocks = (B + 3) / 4; if (blocks > 1024) blocks = 1024;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MVAE_BF16)
+    hipLaunchKernelGGL((moses_sample_filtered_step_kernel<bf16_t>), dim3(blocks), dim3(256), lds, st, B, V, H, (const bf16_t*)h_top, (long)ldh,
+                       (const bf16_t*)w_fc, (long)ldw, bias, 1.f / temp, top_k, top_p, seed, step, eos_id, table, W, base, add_out, x, (long)x_ld,
+                       end_pads, eos_mask, w_out, logq, hash);
+  else
+    hipLaunchKernelGGL((moses_sample_filtered_step_kernel<float>), dim3(blocks), dim3(256), lds, st, B, V, H, (const float*)h_top, (long)ldh,
+                       (const float*)w_fc, (long)ldw, bias, 1.f / temp, top_k, top_p, seed, step, eos_id, table, W, base, add_out, x, (long)x_ld,
+                       end_pads, eos_mask, w_out, logq, hash);
   MVAE_CHECK_HIP(hipGetLastError());
   return MVAE_OK;
 }

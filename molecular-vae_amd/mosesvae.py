@@ -204,22 +204,67 @@ class VAE(_SavedState, nn.Module):
         return torch.randn(n_batch, self.d_z, device=self.device)
 
     @torch.no_grad()
-    def sample(self, n_batch, max_len=100, z=None, temp=1.0, return_tokens=False, seed=None):
+    def sample(self, n_batch, max_len=100, z=None, temp=1.0, return_tokens=False, seed=None, top_k=None, top_p=None, return_logp=False):
         """mosesvae.py:214-262 (autoregressive decoding, multinomial sampling at temperature `temp`) on the GRU step kernels: per generated token
         one wavefront pass of the 3-layer stack (T = 1) and ONE sampling launch (head GEMV + softmax + multinomial + eos / end-pad bookkeeping +
         the next token's input rows: mvae_moses_sample_step) -- 4 launches per token, no torch arithmetic in the loop.  Randomness is explicit:
         `seed` (default: drawn from torch's CPU generator, so torch.manual_seed makes a run reproducible) feeds a counter hash of (step, row).
-        Upstream bugs fixed: boolean masks, a real d_z.  Returns (list of strings, z)."""
+        Upstream bugs fixed: boolean masks, a real d_z.  Returns (list of strings, z).
+        Additions beyond the reference: `top_k` keeps the k most probable tokens of each step, `top_p` the shortest most-probable-first prefix
+        whose probability reaches top_p (ties by token id; both look at the unfiltered softmax(y / temp), and the draw is from their
+        intersection, renormalised); None, top_k >= V and top_p >= 1 switch a filter off.  `return_logp=True` appends a third return value
+        logq, float32 [B] on the device: the summed log-probability of tokens 1 .. end under the distribution they were drawn from,
+        temperature and truncation included (at temp = 1 with the filters off that is log p(x | z) as `decode` reports it: an emitted `pad`
+        token counts, unlike in `score`).  With a filter or return_logp the sampling launch is mvae_moses_sample_filtered_step (still 4
+        launches per token); without them the method runs the launches it always ran.  The same seed gives the same tokens either way."""
+        top_k, top_p = self._check_filters(top_k, top_p)
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.sample")
+        if z is None:
+            z = self.sample_z_prior(n_batch)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)))
+        filtered = top_k > 0 or top_p < 1.0 or return_logp
+        x, end_pads, logq, _ = self._sample_tokens(z[:n_batch], max_len, temp, seed, top_k, top_p, filtered=filtered)
+        xs, ends = x.cpu(), end_pads.cpu()
+        if return_tokens:                                                # raw id tensors (specials included), for tests / downstream scoring
+            out = [xs[b, :ends[b]] for b in range(n_batch)]
+        else:
+            out = [self.tensor2string(xs[b, :ends[b]]) for b in range(n_batch)]
+        z = z.to(dev).float().contiguous()
+        return (out, z, logq) if return_logp else (out, z)
+
+    def _check_filters(self, top_k, top_p):
+        """sample()'s top_k / top_p as the kernel takes them: (top_k, 0 = off; top_p, 1.0 = off).  ValueError for top_k < 1, top_p <= 0 / NaN."""
+        V = self.x_emb.num_embeddings
+        if top_k is None:
+            k = 0
+        else:
+            k = int(top_k)
+            if k < 1 or k != top_k:
+                raise ValueError(f"sample: top_k must be an integer >= 1 (or None), got {top_k}")
+            k = 0 if k >= V else k
+        if top_p is None:
+            p = 1.0
+        else:
+            p = float(top_p)
+            if not p > 0.0:
+                raise ValueError(f"sample: top_p must be in (0, 1] (or None), got {top_p}")
+            p = min(p, 1.0)
+        return k, p
+
+    _FNV_BASIS = -3750763034362895579       # 0xcbf29ce484222325, the 64-bit FNV-1a offset basis, as an int64
+
+    def _sample_tokens(self, z, max_len, temp, seed, top_k=0, top_p=1.0, filtered=True):
+        """The sampling loop without the host side: (x [B, max_len] int64 -- bos first, pad after each end --, ends [B] int64, logq [B] fp32,
+        hash [B] int64: FNV-1a over x[b, 1 : end]) on the device.  top_k (0: off) / top_p (1.0: off) as _check_filters returns them.
+        filtered=False issues mvae_moses_sample_step instead (sample()'s default path) and returns None for logq and hash."""
         dev = self.device
         _require_cuda(dev, "mosesvae.VAE.sample")
         P = self._pack(dev)
         ws, dt, f32 = self._ws, self.compute_dtype, torch.float32
-        if z is None:
-            z = self.sample_z_prior(n_batch)
         z = z.to(dev).float().contiguous()
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)))
-        B, V, dz = n_batch, self.x_emb.num_embeddings, self.d_z
+        B, V, dz = z.shape[0], self.x_emb.num_embeddings, self.d_z
         pd = P["dec"]; Hd = pd["H"]; NL = self.decoder_rnn.num_layers
         Vp, ldh = _pad(V, 4), Hd + _LDPAD
         W = lambda name, shape, d=f32: ws.get("smp_" + name, shape, d, dev)
@@ -239,18 +284,23 @@ class VAE(_SavedState, nn.Module):
         x[:, 0] = self.bos
         end_pads = torch.full((B,), max_len, dtype=torch.long, device=dev)
         eos_mask = torch.zeros(B, dtype=torch.uint8, device=dev)
+        logq = hsh = None
+        if filtered:
+            logq = torch.zeros(B, dtype=f32, device=dev)
+            hsh = torch.full((B,), self._FNV_BASIS, dtype=torch.long, device=dev)
         ops.gather_rows_tb(w.view(B, 1), tbl4, add, B, 1, V, 4 * Hd, base=zp4)      # the <bos> input rows; later ones come out of the sampling launch
         cur = 0
         for i in range(1, max_len):
             ops.rnn_fwd(L.CELL_GRU, dt, 1, B, Hd, add, 0, pd["Wih"], [pd["ldw"]] * NL, pd["Whh"], [pd["ldw"]] * NL, pd["bias"],
                         [h[1 - cur:2 - cur] for h in hbuf], ldh, None, gates, hstate, h0=[h[cur] for h in hbuf], ldh0=ldh, persist=False)
-            ops.moses_sample_step(hbuf[-1][1 - cur], ldh, P["Wfc"], self.decoder_fc.bias, temp, seed, i, self.eos, tbl4, zp4, add, x, end_pads,
-                                  eos_mask, w, B, V, Hd)
+            if filtered:
+                ops.moses_sample_filtered_step(hbuf[-1][1 - cur], ldh, P["Wfc"], self.decoder_fc.bias, temp, top_k, top_p, seed, i, self.eos, tbl4,
+                                               zp4, add, x, end_pads, eos_mask, w, B, V, Hd, logq=logq, hash=hsh)
+            else:
+                ops.moses_sample_step(hbuf[-1][1 - cur], ldh, P["Wfc"], self.decoder_fc.bias, temp, seed, i, self.eos, tbl4, zp4, add, x, end_pads,
+                                      eos_mask, w, B, V, Hd)
             cur = 1 - cur
-        xs, ends = x.cpu(), end_pads.cpu()
-        if return_tokens:                                                # raw id tensors (specials included), for tests / downstream scoring
-            return [xs[b, :ends[b]] for b in range(B)], z
-        return [self.tensor2string(xs[b, :ends[b]]) for b in range(B)], z
+        return x, end_pads, logq, hsh
 
     @torch.no_grad()
     def decode(self, z, beam_width=1, max_len=100, return_tokens=False):

@@ -477,6 +477,17 @@ def moses_sample_step(h_top, ldh, w_fc, bias, temp, seed, step, eos_id, table, b
                                           ptr(x), x.stride(0), ptr(end_pads), ptr(eos_mask), ptr(w_out), stream_ptr()), "mvae_moses_sample_step")
 
 
+def moses_sample_filtered_step(h_top, ldh, w_fc, bias, temp, top_k, top_p, seed, step, eos_id, table, base, add_out, x, end_pads, eos_mask, w_out,
+                               B, V, H, logq=None, hash=None):
+    """moses_sample_step with top-k (0: off) / top-p (>= 1: off) truncation; logq [B] fp32 accumulates the drawn token's log-probability
+    under the truncated distribution and hash [B] int64 the FNV-1a hash of the row's tokens, for the rows that had not ended -- one launch
+    (mvae_moses_sample_filtered_step)."""
+    check(L.load().mvae_moses_sample_filtered_step(dt_code(h_top.dtype), B, V, H, ptr(h_top), ldh, ptr(w_fc), w_fc.stride(0), ptr(bias), float(temp),
+                                                   int(top_k), float(top_p), int(seed) & 0xFFFFFFFF, int(step), int(eos_id), ptr(table),
+                                                   table.shape[1], ptr(base), ptr(add_out), ptr(x), x.stride(0), ptr(end_pads), ptr(eos_mask),
+                                                   ptr(w_out), ptr(logq), ptr(hash), stream_ptr()), "mvae_moses_sample_filtered_step")
+
+
 
 def moses_beam_step(state, ldh, w_fc, bias, step, eos_id, pad_id, table, base, add_out, score, fin, ends, hist_tok, hist_par, B, K, V, H):
     """One beam-search token behind the GRU step: head GEMV, log-softmax, per-beam top-K, per-molecule merge, backpointers and the next

@@ -764,6 +764,82 @@ def moses_reconstruction(model, batches, beam_width=1, max_len=100):
     return hits / max(n, 1), float(lp_sum) / max(n, 1)
 
 
+@torch.no_grad()
+def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top_k=None, top_p=None, seed=0, z=None):
+    """The reference's generation pipeline (``hugesample.py``: sample in batches, hash the strings, count unique / total) with the hashing
+    and the deduplication on the device: ``n_samples`` sequences from a ``mosesvae.VAE`` in batches of ``batch_size`` (the last one shorter),
+    batch j with seed ``seed + j`` and ``temp`` / ``top_k`` / ``top_p`` as ``VAE.sample`` takes them.  ``z`` None draws each batch's latents
+    with ``model.sample_z_prior`` (so ``model.prior`` decides, as in ``sample``); a tensor [n_samples, d_z] is consumed batch by batch.
+    Every sequence carries the 64-bit FNV-1a hash of its token ids (bos excluded, <eos> included), computed by the sampling launches; each
+    batch's hashes are deduplicated on the device, within the batch and against every hash seen so far, and only the first occurrence of a
+    NEW hash has its token row copied to the host and turned into a string.  The host waits once per batch (for the number of new rows);
+    the rows themselves arrive asynchronously and are converted while the next batch runs.
+    Returns {"total": n_samples, "unique": number of distinct hashes, "strings": their strings in first-seen order, "counts": how often
+    each was drawn, "logq": the log-probability of each one's first occurrence under the distribution it was drawn from (VAE.sample's
+    return_logp)}.  Equality is decided by the hash alone: n distinct sequences collide with probability about n^2 / 2^65 (3e-8 at a
+    million), in which case the later sequence is counted as the earlier one.  The hash is over token ids, so two sequences that differ
+    only in how they end (<eos> against the max_len cut) are distinct entries with equal strings."""
+    n_samples, batch_size, max_len = int(n_samples), int(batch_size), int(max_len)
+    if n_samples < 1 or batch_size < 1 or max_len < 1:
+        raise ValueError(f"moses_generate: n_samples, batch_size and max_len must be >= 1, got {n_samples}, {batch_size}, {max_len}")
+    k, p = model._check_filters(top_k, top_p)
+    if z is not None and tuple(z.shape) != (n_samples, model.d_z):
+        raise ValueError(f"moses_generate: z must be [{n_samples}, {model.d_z}], got {tuple(z.shape)}")
+    dev = model.device
+    i64 = torch.long
+    seen_h = torch.empty(0, dtype=i64, device=dev)             # the hashes seen so far, sorted, and the first-seen index of each
+    seen_g = torch.empty(0, dtype=i64, device=dev)
+    counts = torch.empty(0, dtype=i64, device=dev)             # in first-seen order
+    logqs, strings = [], []
+    stage = [None, None]                                        # pinned staging rows [batch_size, max_len + 1] (ids, end), alternating
+    pending = None
+
+    def convert(job):
+        rows, n_new = job
+        ids = rows[:n_new].tolist()
+        v = model.vocabulary
+        strings.extend(v.ids2string(r[:r[max_len]], rem_bos=True, rem_eos=True) for r in ids)
+
+    for j, b0 in enumerate(range(0, n_samples, batch_size)):
+        n = min(batch_size, n_samples - b0)
+        zb = model.sample_z_prior(n) if z is None else z[b0:b0 + n]
+        x, ends, logq, h = model._sample_tokens(zb, max_len, temp, int(seed) + j, k, p)
+        hs, order = torch.sort(h, stable=True)                  # equal hashes: ascending row, so a run starts at its first occurrence
+        first = torch.ones(n, dtype=torch.bool, device=dev)
+        first[1:] = hs[1:] != hs[:-1]
+        run = torch.cumsum(first, 0) - 1
+        cnt = torch.zeros(n, dtype=i64, device=dev).index_add_(0, run, torch.ones(n, dtype=i64, device=dev))[run]
+        if seen_h.numel():
+            pos = torch.searchsorted(seen_h, hs).clamp_(max=seen_h.numel() - 1)
+            hit = seen_h[pos] == hs
+            counts.index_add_(0, seen_g[pos], torch.where(hit & first, cnt, torch.zeros_like(cnt)))
+            new = first & ~hit
+        else:
+            new = first
+        key, ord2 = torch.sort(torch.where(new, order, torch.full_like(order, n)))     # the new rows first, in first-seen order
+        n_new = int(new.sum())                                   # the batch's one host wait (the copy queued last round has landed too)
+        if pending is not None:
+            convert(pending)
+            pending = None
+        if n_new:
+            sel, src = key[:n_new], ord2[:n_new]
+            if stage[j & 1] is None:
+                stage[j & 1] = torch.empty((batch_size, max_len + 1), dtype=i64, pin_memory=True)
+            rows = stage[j & 1]
+            rows[:n_new].copy_(torch.cat([x[sel], ends[sel, None]], 1), non_blocking=True)
+            pending = (rows, n_new)
+            logqs.append(logq[sel])
+            g0 = counts.numel()
+            counts = torch.cat([counts, cnt[src]])
+            seen_h, perm = torch.sort(torch.cat([seen_h, hs[src]]))
+            seen_g = torch.cat([seen_g, torch.arange(g0, g0 + n_new, device=dev)])[perm]
+    torch.cuda.current_stream(dev).synchronize()
+    if pending is not None:
+        convert(pending)
+    return {"total": n_samples, "unique": len(strings), "strings": strings, "counts": counts.tolist(),
+            "logq": torch.cat(logqs).tolist() if logqs else []}
+
+
 def active_units(mu, delta=0.01):
     """Active units of a latent code (Burda et al.; He et al.'s calc_au): the number of dimensions d whose sample variance over the set
     (divided by N - 1) of mu[:, d] exceeds `delta`, computed in float64, as a 0-d tensor on mu's device (0 for fewer than two rows)."""
