@@ -284,7 +284,7 @@ typedef struct {
   const void* cs[MVAE_MAX_LAYERS];
   const void* gates[MVAE_MAX_LAYERS];
   void* dG[MVAE_MAX_LAYERS]; int64_t ldg;                                  /* row stride of dG (>= G*H; pad it off powers of two) */
-  void* dGh[MVAE_MAX_LAYERS];                                              /* GRU only: W_hh-side gradient rows */
+  void* dGh[MVAE_MAX_LAYERS];                                              /* RESERVED, ignored: no kernel reads or writes it (the W_hh-side rows are dG's slots r, z, n*r); kept for the struct layout */
   float* dstate[MVAE_MAX_LAYERS];                                         /* fp32 [2][B][H] ping-pong: LSTM dc, GRU dh carry */
   float* dh0[MVAE_MAX_LAYERS];                                            /* optional out: gradient w.r.t. h0 (GRU decoder_lat path) */
   void* split_ws; size_t split_ws_bytes;                                  /* optional scratch of mvae_rnn_bwd_workspace(d) bytes: enables the split-K

@@ -924,6 +924,8 @@ def rnn_bwd(cell, dtype, T, B, H, w_hhT, ldw_hhT, w_ihT, ldw_ihT, dy, dy_ld, hs,
             drop_mask=None, drop_p=0.0, drop_seed=0, dy_a=None, dy_w=None, dy_k=0, persist=None, poison=None):
     """dy_a [T*B, ld] / dy_w [H, ld] (dtype, zero-padded to dy_k columns): the output gradient as a product dy = dy_a . dy_w^T, contracted
     by the top layer's cell itself (no [T, B, H] fp32 dy tensor).
+    dGh: reserved and ignored -- it fills mvae_rnn_bwd_desc.dGh, which no kernel reads or writes (the GRU's W_hh-side gradient rows are the
+    slots r, z, n*r of dG); do not pass it.
     persist: True / False / None (= PERSIST_DEFAULT): the weights-resident dataflow backward where the library serves the shape (it wants the
     output gradient as `dy`, see rnn_bwd_persist_served), and the layer-concurrent row-resident form of the narrow f32 stacks.  poison: as in
     rnn_fwd."""
