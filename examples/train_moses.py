@@ -26,6 +26,9 @@ ap.add_argument("--epochs", default=100, type=int)
 ap.add_argument("--n_samples", default=1024, type=int)
 ap.add_argument("--n_synth", default=8192, type=int, help="size of the synthetic corpus when no --smi is given")
 ap.add_argument("--out_dir", default=".")
+ap.add_argument("--word-dropout", default=0.0, type=float, help="probability that a decoder input token becomes <unk> (0 = off)")
+ap.add_argument("--free-bits", default=0.0, type=float, help="nats per latent dimension that cost no KL (0 = off)")
+ap.add_argument("--kl-cycle", default=0, type=int, help="cyclical KL weight with cycles of this many epochs (0: the linear KLAnnealer)")
 ap.add_argument("--report", default=None, help="write a JSON summary (the per-epoch postfix dictionaries + samples) here")
 args = ap.parse_args()
 
@@ -50,7 +53,8 @@ torch.manual_seed(42)
 model = MV.VAE(vocab).to(dev)
 sync = mv.GradSync() if world > 1 else None
 optimizer = mv.FusedAdam(model.parameters(), lr=3e-4, max_grad_norm=50.0, grad_sync=sync)   # :188, :227
-kl_annealer = mv.KLAnnealer(args.epochs)                                                     # :47-58, :185
+model.word_dropout, model.free_bits = args.word_dropout, args.free_bits                       # remedies for posterior collapse
+kl_annealer = mv.CyclicalKLAnnealer(args.kl_cycle) if args.kl_cycle > 0 else mv.KLAnnealer(args.epochs)    # :47-58, :185
 lr_annealer = mv.CosineAnnealingLRWithRestart(optimizer)                                     # :61-89, :195
 
 report = dict(vocab=len(vocab), n=len(smiles), epochs=[], samples=[])

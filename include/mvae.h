@@ -465,6 +465,31 @@ int mvae_moses_latent_fwd(int B, int dz, const float* mu, const float* logvar, c
                           float* z, float* kl_out, void* ws, size_t ws_bytes, void* stream);
 int mvae_moses_latent_bwd(int B, int dz, const float* mu, const float* logvar, const float* eps, const float* dz_in, const float* dkl,
                           const float* dlogvar_ext, float* dmu, float* dlogvar, void* stream);
+/* Free-bits form of the latent pass (an addition: Kingma et al. 2016 in the per-dimension batch-mean form, against posterior collapse).
+ * With k_bj = 0.5 (exp(logvar_bj) + mu_bj^2 - 1 - logvar_bj) and m_j = (1 / B) sum_b k_bj:
+ *   kl_dim[j] = m_j  (fp32 [dz]),  kl2[0] = sum_j max(m_j, free_bits)  (the objective),  kl2[1] = sum_j m_j  (the KL itself, what
+ *   mvae_moses_latent_fwd reports).  z and eps_out are written exactly as mvae_moses_latent_fwd writes them: the same draw for the same
+ *   (seed, offset), z bitwise the same.  free_bits is in nats per latent dimension; a dimension costs nothing until it carries that much.
+ * The column sums over the batch are two-stage and fixed-order (per-block partial sums in ws, one block finishes; no float atomics):
+ * two calls give the same bits.  k_bj is evaluated as 0.5 ((exp(lv) - 1 - lv) + mu^2) with the bracket free of cancellation.
+ * mvae_moses_latent_fb_bwd is mvae_moses_latent_bwd with the KL term of dimension j multiplied by [kl_dim[j] >= free_bits] -- `>=`, as
+ * torch.clamp(min = free_bits) differentiates, so free_bits = 0 switches nothing off; kl_dim is what the forward wrote.
+ * Any B >= 1, dz >= 1.  Refused before anything is enqueued: free_bits < 0 or NaN, a null operand, B < 1, dz < 1 (MVAE_ERR_INVALID);
+ * ws_bytes < mvae_moses_latent_fb_workspace(B, dz) (MVAE_ERR_WORKSPACE). */
+size_t mvae_moses_latent_fb_workspace(int B, int dz);
+int mvae_moses_latent_fb_fwd(int B, int dz, const float* mu, const float* logvar, const float* eps, uint32_t seed, uint64_t offset, float* eps_out,
+                             float free_bits, float* z, float* kl2, float* kl_dim, void* ws, size_t ws_bytes, void* stream);
+int mvae_moses_latent_fb_bwd(int B, int dz, const float* mu, const float* logvar, const float* eps, const float* dz_in, const float* dkl,
+                             const float* dlogvar_ext, const float* kl_dim, float free_bits, float* dmu, float* dlogvar, void* stream);
+/* Word dropout on the decoder's input tokens (an addition: Bowman et al. 2016): x_out[b, t] = unk_id where position (b, t) is eligible and
+ * not kept, x[b, t] otherwise (x, x_out int64 [B, T]; x_out may not alias x).  Eligible: 1 <= t <= lengths[b] - 2, i.e. never <bos>
+ * (t = 0), the last input token (t = lengths[b] - 1: <eos>, which the decoder reads but predicts nothing from) or padding.  Kept:
+ * keep_mask[b * T + t] != 0 when a mask is given (bytes [B, T]; parity tests), else mvae_dropout_keep(seed, b * T + t, p) -- the counter
+ * is the flat position in the PADDED batch, so the draw of a sequence depends on the batch's width T.  No RNG state anywhere: the host
+ * can restate the draw.  n_dropped (optional, device int32): the number of replaced positions, an integer sum (exact, order-free).
+ * Refused before anything is enqueued (MVAE_ERR_INVALID): p outside [0, 1) or NaN, B < 1, T < 1, null x, lengths or x_out. */
+int mvae_token_dropout(const int64_t* x, const int32_t* lengths, int B, int T, int unk_id, float p, uint32_t seed, const uint8_t* keep_mask,
+                       int64_t* x_out, int32_t* n_dropped, void* stream);
 size_t mvae_ce_loss_workspace(int B, int T);
 int mvae_ce_loss_fwd(int B, int T, int V, const float* logits, int64_t ldl, const int64_t* x, int pad, float* loss2, void* ws, size_t ws_bytes,
                      void* stream);

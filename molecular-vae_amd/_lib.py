@@ -146,6 +146,10 @@ SIGNATURES = {
     "mvae_moses_latent_workspace": (_sz, [_i]),
     "mvae_moses_latent_fwd": (_i, [_i, _i, _vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mvae_moses_latent_bwd": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvae_moses_latent_fb_workspace": (_sz, [_i, _i]),
+    "mvae_moses_latent_fb_fwd": (_i, [_i, _i, _vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mvae_moses_latent_fb_bwd": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
+    "mvae_token_dropout": (_i, [_vp, _vp, _i, _i, _i, _f, C.c_uint32, _vp, _vp, _vp, _vp]),
     "mvae_ce_loss_workspace": (_sz, [_i, _i]),
     "mvae_ce_loss_fwd": (_i, [_i, _i, _i, _vp, _i64, _vp, _i, _vp, _vp, _sz, _vp]),
     "mvae_ce_loss_bwd": (_i, [_i, _i, _i, _i, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _i64, _vp]),

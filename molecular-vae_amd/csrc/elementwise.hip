@@ -1448,6 +1448,99 @@ __global__ __launch_bounds__(256) void moses_latent_bwd_kernel(int B, int dz, co
     dlogvar[i] = d * eps[i] * 0.5f * expf(lv * 0.5f) + g * 0.5f * (expf(lv) - 1.f) / (float)B + (dlogvar_ext ? dlogvar_ext[i] : 0.f);
   }
 }
+// ---- free-bits form of the latent pass (Kingma et al. 2016, per-dimension batch mean): the KL is summed per COLUMN j over the batch, so a
+// thread owns a column (lane = j: coalesced rows) and the four waves of a block take every fourth row of the block's row chunk.  Stage 1
+// leaves one partial column sum per (chunk, j) in the workspace, stage 2 (one block) adds the chunks up in a fixed order: no float atomics.
+constexpr int FB_MAX_CHUNKS = 256;
+static inline int fb_chunks(int B) { const int c = (B + 31) / 32; return c < 1 ? 1 : (c > FB_MAX_CHUNKS ? FB_MAX_CHUNKS : c); }
+// exp(lv) - 1 - lv without the cancellation of the literal form (a near-collapsed dimension has |lv| << 1, where exp(lv) + mu^2 - 1 - lv
+// in fp32 keeps three or four digits of a term of size lv^2 / 2): the Taylor series below 1/4, expm1f above.
+__device__ __forceinline__ float exp_m1_mx(float lv) {
+  if (fabsf(lv) < 0.25f) {
+    float s = 1.f / 40320.f;
+    s = s * lv + 1.f / 5040.f; s = s * lv + 1.f / 720.f; s = s * lv + 1.f / 120.f; s = s * lv + 1.f / 24.f; s = s * lv + 1.f / 6.f;
+    s = s * lv + 0.5f;
+    return lv * lv * s;
+  }
+  return expm1f(lv) - lv;
+}
+__global__ __launch_bounds__(256) void moses_latent_fb_fwd_kernel(int B, int dz, int rpc, const float* mu, const float* logvar, const float* eps,
+                                                                  uint32_t seed, uint64_t offset, float* eps_out, float* z, float* part) {
+  __shared__ float red[4][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int j = blockIdx.x * 64 + lane;
+  const int r0 = blockIdx.y * rpc, r1 = min(B, r0 + rpc);
+  float a = 0.f;
+  if (j < dz) {
+    for (int b = r0 + w; b < r1; b += 4) {
+      const long i = (long)b * dz + j;
+      const float m = mu[i], lv = logvar[i];
+      float e;                                                // the draw and z exactly as moses_latent_fwd_kernel
+      if (eps) e = eps[i];
+      else { e = normal_draw(seed, offset + (uint64_t)i); eps_out[i] = e; }
+      z[i] = m + expf(lv * 0.5f) * e;
+      a += exp_m1_mx(lv) + m * m;
+    }
+  }
+  red[w][lane] = a;
+  __syncthreads();
+  if (w == 0 && j < dz) part[(long)blockIdx.y * dz + j] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+}
+// kl_dim[j] = m_j = 0.5 / B * sum_b (...); kl2[0] = sum_j max(m_j, free_bits) (the objective), kl2[1] = sum_j m_j (the KL itself)
+__global__ __launch_bounds__(256) void moses_latent_fb_final_kernel(int B, int dz, int chunks, const float* part, float free_bits, float* kl_dim,
+                                                                    float* kl2) {
+  __shared__ float red[4];
+  float obj = 0.f, tot = 0.f;
+  for (int j = threadIdx.x; j < dz; j += 256) {
+    float s = 0.f;
+    for (int c = 0; c < chunks; ++c) s += part[(long)c * dz + j];
+    const float m = 0.5f * s / (float)B;
+    kl_dim[j] = m;
+    obj += fmaxf(m, free_bits);
+    tot += m;
+  }
+  obj = block_sum_256(obj, red);
+  tot = block_sum_256(tot, red);
+  if (threadIdx.x == 0) { kl2[0] = obj; kl2[1] = tot; }
+}
+// moses_latent_bwd_kernel with the KL term of column j switched by [kl_dim[j] >= free_bits] (d max(m, l) / dm as torch.clamp(min=l) has it)
+__global__ __launch_bounds__(256) void moses_latent_fb_bwd_kernel(int B, int dz, const float* mu, const float* logvar, const float* eps,
+                                                                  const float* dzv, const float* dkl, const float* dlogvar_ext, const float* kl_dim,
+                                                                  float free_bits, float* dmu, float* dlogvar) {
+  const long n = (long)B * dz;
+  const float g0 = dkl ? dkl[0] : 0.f;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const float g = kl_dim[(int)(i % dz)] >= free_bits ? g0 : 0.f;
+    const float m = mu[i], lv = logvar[i], d = dzv ? dzv[i] : 0.f;
+    dmu[i] = d + g * m / (float)B;
+    dlogvar[i] = d * eps[i] * 0.5f * expf(lv * 0.5f) + g * 0.5f * (expf(lv) - 1.f) / (float)B + (dlogvar_ext ? dlogvar_ext[i] : 0.f);
+  }
+}
+// word dropout on the decoder's input tokens (Bowman et al. 2016): position (b, t) with 1 <= t <= lengths[b] - 2 -- never <bos>, the last
+// input token or padding -- becomes unk unless kept; kept = the injected byte mask, or the counter hash of mvae_dropout_keep at b * T + t.
+// The count of replaced positions is an integer sum (per-block count, one integer atomic per block): exact in any order.
+__global__ __launch_bounds__(256) void token_dropout_kernel(int B, int T_, const int64_t* x, const int32_t* lengths, int64_t unk, uint32_t thresh,
+                                                            uint32_t seed, const uint8_t* keep_mask, int64_t* x_out, int32_t* n_dropped) {
+  const long n = (long)B * T_;
+  int cnt = 0;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const int b = (int)(i / T_), t = (int)(i - (long)b * T_);
+    int64_t v = x[i];
+    if (t >= 1 && t <= lengths[b] - 2) {
+      const bool keep = keep_mask ? (keep_mask[i] != 0) : (drop_hash_u32(seed, (uint32_t)i) >= thresh);
+      if (!keep) { v = unk; ++cnt; }
+    }
+    x_out[i] = v;
+  }
+  if (n_dropped) {                                          // (a kernel argument: uniform over the block)
+    __shared__ int red[4];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) { const int s = red[0] + red[1] + red[2] + red[3]; if (s) atomicAdd(n_dropped, s); }
+  }
+}
 // token cross-entropy of mosesvae.py:193-197: logits row (t*B+b) predicts x[b, t+1]; targets == pad are ignored; mean over the rest.
 // A target outside [0, V) (and not pad) makes the loss NaN, is not counted and is never used as an address (as ce_rows_fwd_kernel).
 // a block = 64 consecutive (t, b) rows, 16 per wave; per-BLOCK partial sums (nll, count), added up in a fixed order by the final kernel.
@@ -1709,6 +1802,39 @@ int mvae_moses_latent_bwd(int B, int dz, const float* mu, const float* logvar, c
   if (!mu || !logvar || !eps || !dmu || !dlogvar || B < 1 || dz < 1) return MVAE_ERR_INVALID;
   hipLaunchKernelGGL(moses_latent_bwd_kernel, dim3(grid_for((long)B * dz)), dim3(256), 0, (hipStream_t)stream, B, dz, mu, logvar, eps, dzv, dkl,
                      dlogvar_ext, dmu, dlogvar);
+  MVAE_CHECK_HIP(hipGetLastError());
+  return MVAE_OK;
+}
+size_t mvae_moses_latent_fb_workspace(int B, int dz) { return (B > 0 && dz > 0) ? (size_t)fb_chunks(B) * dz * sizeof(float) : 0; }
+int mvae_moses_latent_fb_fwd(int B, int dz, const float* mu, const float* logvar, const float* eps, uint32_t seed, uint64_t offset, float* eps_out,
+                             float free_bits, float* z, float* kl2, float* kl_dim, void* ws, size_t ws_bytes, void* stream) {
+  if (!mu || !logvar || (!eps && !eps_out) || !z || !kl2 || !kl_dim || B < 1 || dz < 1 || !(free_bits >= 0.f)) return MVAE_ERR_INVALID;
+  if (!ws || ws_bytes < mvae_moses_latent_fb_workspace(B, dz)) return MVAE_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int chunks = fb_chunks(B);
+  const int rpc = (B + chunks - 1) / chunks;                 // chunks * rpc >= B; a chunk past the last row writes zeros
+  hipLaunchKernelGGL(moses_latent_fb_fwd_kernel, dim3((dz + 63) / 64, chunks), dim3(256), 0, st, B, dz, rpc, mu, logvar, eps, seed, offset, eps_out,
+                     z, (float*)ws);
+  hipLaunchKernelGGL(moses_latent_fb_final_kernel, dim3(1), dim3(256), 0, st, B, dz, chunks, (const float*)ws, free_bits, kl_dim, kl2);
+  MVAE_CHECK_HIP(hipGetLastError());
+  return MVAE_OK;
+}
+int mvae_moses_latent_fb_bwd(int B, int dz, const float* mu, const float* logvar, const float* eps, const float* dzv, const float* dkl,
+                             const float* dlogvar_ext, const float* kl_dim, float free_bits, float* dmu, float* dlogvar, void* stream) {
+  if (!mu || !logvar || !eps || !kl_dim || !dmu || !dlogvar || B < 1 || dz < 1 || !(free_bits >= 0.f)) return MVAE_ERR_INVALID;
+  hipLaunchKernelGGL(moses_latent_fb_bwd_kernel, dim3(grid_for((long)B * dz)), dim3(256), 0, (hipStream_t)stream, B, dz, mu, logvar, eps, dzv, dkl,
+                     dlogvar_ext, kl_dim, free_bits, dmu, dlogvar);
+  MVAE_CHECK_HIP(hipGetLastError());
+  return MVAE_OK;
+}
+int mvae_token_dropout(const int64_t* x, const int32_t* lengths, int B, int T, int unk_id, float p, uint32_t seed, const uint8_t* keep_mask,
+                       int64_t* x_out, int32_t* n_dropped, void* stream) {
+  if (!x || !lengths || !x_out || B < 1 || T < 1 || !(p >= 0.f && p < 1.f)) return MVAE_ERR_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  if (n_dropped) MVAE_CHECK_HIP(hipMemsetAsync(n_dropped, 0, sizeof(int32_t), st));
+  const uint32_t thresh = (uint32_t)((double)p * 4294967296.0);          // as mvae_dropout_keep
+  hipLaunchKernelGGL(token_dropout_kernel, dim3(grid_for((long)B * T)), dim3(256), 0, st, B, T, x, lengths, (int64_t)unk_id, thresh, seed, keep_mask,
+                     x_out, n_dropped);
   MVAE_CHECK_HIP(hipGetLastError());
   return MVAE_OK;
 }

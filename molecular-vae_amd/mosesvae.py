@@ -14,6 +14,11 @@ computes the deterministic network.  Under data parallelism (an initialised ``to
 gradients enabled) takes the token mean of the reconstruction loss (mosesvae.py:193-197) over the GLOBAL number of non-pad targets
 (``dp_global_token_mean``, one 4-byte all-reduce on ``dp_group``), so that the all-reduced gradient equals the single-process gradient of
 the global batch; eval / no_grad forwards never communicate.
+
+Against posterior collapse (additions, train mode only, off by default): ``word_dropout`` replaces the decoder's
+input tokens by ``<unk>`` with that probability (never ``<bos>``, the last input token or padding; the encoder and the targets stay clean)
+and ``free_bits`` makes ``kl_loss`` the objective ``sum_j max(m_j, free_bits)`` over the per-dimension batch means m_j of the KL, with
+the KL itself in ``last_kl``.  With both at 0 the step issues exactly the launches it issues without them.
 """
 import math
 import os
@@ -79,6 +84,11 @@ class VAE(_SavedState, nn.Module):
         self.dp_force = False                # GradSync(force=True): make the token-count all-reduce even on a one-rank group (RCCL rehearsal)
         self.dp_group = None                 # process group of that reduction (None: the default group); moses_train_step sets it from the optimiser's GradSync
         self.last_drop_seed = None           # seed of the most recent train-mode forward (None: eval / injected mask)
+        self.word_dropout = 0.0              # train mode: probability that a decoder INPUT token becomes <unk> (Bowman et al. 2016); 0 = off
+        self.free_bits = 0.0                 # train mode: nats per latent dimension that cost nothing (Kingma et al. 2016, batch-mean form); 0 = off
+        self.last_word_seed = None           # seed of the most recent word-dropout draw (None: off / injected mask)
+        self.last_kl = None                  # free bits on: the KL itself of the most recent forward (device scalar; kl_loss is the objective)
+        self.last_kl_per_dim = None          # free bits on: its per-dimension batch means [d_z] (device, detached)
         self.compute_dtype = dtype
         self.prior = "zeros"                 # sample_z_prior: "zeros" = the reference as written (mosesvae.py:211), "normal" = N(0, I) as its docstring says
         self.noise = "device"                # reparameterisation noise: "device" = drawn by the library inside the latent launch; "torch" = torch.randn on the device generator
@@ -141,6 +151,46 @@ class VAE(_SavedState, nn.Module):
         self.last_drop_seed = seed
         return (float(self.d_dropout), seed, None)
 
+    def _collapse_opts(self):
+        """(word_dropout, free_bits) as this forward applies them -- both 0.0 outside train mode --, after validating the attributes
+        (ValueError, before any device work: a CPU model reports it too)."""
+        p, fb = float(self.word_dropout), float(self.free_bits)
+        if not (0.0 <= p < 1.0):                                       # (NaN fails both)
+            raise ValueError(f"mosesvae.VAE.word_dropout must be in [0, 1), got {self.word_dropout}")
+        if not (0.0 <= fb < math.inf):
+            raise ValueError(f"mosesvae.VAE.free_bits must be finite and >= 0 (nats per latent dimension), got {self.free_bits}")
+        return (p, fb) if self.training else (0.0, 0.0)
+
+    def _word_drop(self, p, x_pad, len_t, word_mask, word_seed):
+        """Train mode with word_dropout > 0: the decoder's input tokens, x_pad with the eligible positions (1 <= t <= len - 2: never <bos>,
+        the last input token or padding) replaced by <unk> unless kept -- by word_mask [B, T] (1 = keep) when given, else by the counter
+        hash of (seed, b * T + t) on the device (ops.dropout_keep_mask(seed, (B, T), p) restates it).  None when off: the decoder reads x_pad."""
+        if p <= 0.0:
+            self.last_word_seed = None
+            return None
+        B, T = x_pad.shape
+        _require_cuda(x_pad.device, "mosesvae.VAE")
+        mask, seed = None, 0
+        if word_mask is not None:
+            mask = torch.as_tensor(word_mask).to(torch.uint8)
+            if tuple(mask.shape) != (B, T):
+                raise ValueError(f"word_mask must be [B, T] = {(B, T)}, got {tuple(mask.shape)}")
+            mask = mask.contiguous().to(x_pad.device)
+            self.last_word_seed = None
+        else:
+            seed = int(torch.randint(0, 2 ** 31 - 1, (1,))) if word_seed is None else int(word_seed)
+            self.last_word_seed = seed
+        x_in = torch.empty_like(x_pad)
+        ops.token_dropout(x_pad, len_t, x_in, B, T, self.unk, p, seed=seed, keep_mask=mask)
+        return x_in
+
+    def _note_kl(self, fb):
+        """Free bits on: keep the KL itself and its per-dimension batch means beside the objective the forward returned as kl_loss."""
+        if fb is None:
+            self.last_kl = self.last_kl_per_dim = None
+        else:
+            self.last_kl, self.last_kl_per_dim = fb["kl2"][1].clone(), fb["kl_dim"].clone()
+
     def _dp_token_mean(self, recon, ntok):
         # Data-parallel TRAINING steps only (train mode, gradients enabled): every rank of `dp_group` makes this call once per step.  Evaluation,
         # no_grad encoding and rank-0-only validation stay collective-free (a collective only some ranks reach would deadlock).
@@ -159,37 +209,54 @@ class VAE(_SavedState, nn.Module):
         sel = [(n, p) for n, p in self.named_parameters() if n.startswith(pre)]
         return [n for n, _ in sel], [p for _, p in sel]
 
-    def forward(self, x, eps=None, drop_mask=None, drop_seed=None):
+    def forward(self, x, eps=None, drop_mask=None, drop_seed=None, word_mask=None, word_seed=None):
         """x: list of LongTensors (one per sequence, sorted by length descending, as collate() yields them).
         Returns (kl_loss, recon_loss, z, logvar, x_padded, y) -- mosesvae.py:126-140 -- from ONE fused autograd node (the encoder and decoder
         halves of forward_encoder / forward_decoder, with the decoder's parameter gradients on a side stream beside the encoder's backward).
-        eps / drop_mask / drop_seed inject the reparameterisation noise and the train-mode inter-layer dropout draw (parity tests)."""
+        eps / drop_mask / drop_seed inject the reparameterisation noise and the train-mode inter-layer dropout draw (parity tests).
+        Train mode, additions against posterior collapse (both off by default):
+          word_dropout > 0: the DECODER reads x with tokens replaced by <unk> (word_mask [B, T], 1 = keep, injects the draw; word_seed fixes
+            the device draw; else a seed is drawn as drop_seed is and kept in last_word_seed).  The encoder, the cross-entropy targets and
+            the returned x_padded stay the clean batch.
+          free_bits > 0: kl_loss is the free-bits objective sum_j max(m_j, free_bits) over the per-dimension batch means m_j of this
+            process's batch (under data parallelism: the rank's own; no collective), so `kl_weight * kl_loss + recon_loss` is the trained
+            loss; the KL itself is in last_kl, the m_j in last_kl_per_dim (both None when free bits is off)."""
+        wd, fb = self._collapse_opts()
         x_pad, len_t = self._batch(x)
         B, T = x_pad.shape
         eps = self._eps(B, eps)                                        # None: mosesvae.py:159's randn_like(mu) is drawn inside mvae_moses_latent_fwd
         drop = self._draw_drop(T, B, drop_mask, drop_seed)
+        x_in = self._word_drop(wd, x_pad, len_t, word_mask, word_seed)
         if x_pad.is_cuda and torch.is_grad_enabled():
             self._side_stream(x_pad.device)                            # first use probes for a concurrent stream: here, not inside the backward
-        kl, recon, z, logvar, y, ntok = _MosesFn.apply(self, x_pad, len_t, eps, drop, *self._plist())
+        opt = _opts(x_in, fb)
+        kl, recon, z, logvar, y, ntok = _MosesFn.apply(self, x_pad, len_t, eps, drop, opt, *self._plist())
+        self._note_kl(opt and opt["fb"])
         return kl, self._dp_token_mean(recon, ntok), z, logvar, x_pad, y
 
     def forward_encoder(self, x, eps=None):
         """mosesvae.py:142-164: x -> (z, kl_loss, logvar).  Runs the encoder half only (GRU(256), heads, reparameterisation + KL); differentiable
-        w.r.t. x_emb / encoder_rnn / q_mu / q_logvar."""
+        w.r.t. x_emb / encoder_rnn / q_mu / q_logvar.  Train mode with free_bits > 0: kl_loss is the free-bits objective, as in `forward`."""
+        _, fb = self._collapse_opts()
         x_pad, len_t = self._batch(x)
         _, params = self._half_params("enc")
-        return _MosesEncFn.apply(self, x_pad, len_t, self._eps(x_pad.shape[0], eps), *params)
+        opt = _opts(None, fb)
+        out = _MosesEncFn.apply(self, x_pad, len_t, self._eps(x_pad.shape[0], eps), opt, *params)
+        self._note_kl(opt and opt["fb"])
+        return out
 
-    def forward_decoder(self, x, z, drop_mask=None, drop_seed=None):
+    def forward_decoder(self, x, z, drop_mask=None, drop_seed=None, word_mask=None, word_seed=None):
         """mosesvae.py:166-199: teacher-forced decoder on the caller's latent z [B, d_z] -> (recon_loss, x_padded, y); differentiable w.r.t. z
-        and x_emb / decoder_rnn / decoder_lat / decoder_fc.  Train mode applies the inter-layer dropout as `forward` does."""
+        and x_emb / decoder_rnn / decoder_lat / decoder_fc.  Train mode applies the inter-layer dropout and the word dropout as `forward` does."""
+        wd, _ = self._collapse_opts()
         x_pad, len_t = self._batch(x)
         B, T = x_pad.shape
         if tuple(z.shape) != (B, self.d_z):
             raise ValueError(f"forward_decoder: z must be [{B}, {self.d_z}], got {tuple(z.shape)}")
         drop = self._draw_drop(T, B, drop_mask, drop_seed)
+        x_in = self._word_drop(wd, x_pad, len_t, word_mask, word_seed)
         _, params = self._half_params("dec")
-        recon, y, ntok = _MosesDecFn.apply(self, x_pad, len_t, z.to(self.device), drop, *params)
+        recon, y, ntok = _MosesDecFn.apply(self, x_pad, len_t, z.to(self.device), drop, _opts(x_in, 0.0), *params)
         return self._dp_token_mean(recon, ntok), x_pad, y
 
     def sample_z_prior(self, n_batch, normal=None):
@@ -501,7 +568,17 @@ class VAE(_SavedState, nn.Module):
 # the encoder's backward), _MosesEncFn (`forward_encoder`: the encoder half alone) and _MosesDecFn (`forward_decoder(x, z)`: the decoder half
 # on a latent the caller supplies, with a gradient w.r.t. that latent).  The halves use disjoint buffer names and keep a generation count
 # each (`_SavedState._next_saved_ws(half)`), so `forward_encoder` followed by `forward_decoder` (the reference's composition) overwrites nothing.
-def _enc_forward(mod, ws, P, x_pad, lengths, eps):
+def _opts(x_in, free_bits):
+    """The collapse remedies of one forward as the autograd nodes carry them: None when both are off (the default path), else
+    dict(x_in = the decoder's word-dropped input tokens | None, fb = None | dict(lam = free bits; the encoder half adds kl2, kl_dim))."""
+    if x_in is None and not free_bits > 0.0:
+        return None
+    return dict(x_in=x_in, fb=dict(lam=free_bits) if free_bits > 0.0 else None)
+
+
+def _enc_forward(mod, ws, P, x_pad, lengths, eps, fb=None):
+    """fb (dict(lam), free bits on): the latent launch is mvae_moses_latent_fb_fwd; the returned kl is the objective, fb receives kl2
+    (objective, KL) and kl_dim [d_z] (the workspace's copy: the backward's gate)."""
     dev, dt, f32 = x_pad.device, mod.compute_dtype, torch.float32
     B, T = x_pad.shape
     V, dz = mod.x_emb.num_embeddings, mod.d_z
@@ -524,18 +601,24 @@ def _enc_forward(mod, ws, P, x_pad, lengths, eps):
     ops.gemm_nt(m1, mod.q_mu[2].weight, mu, B, dz, 256, bias=mod.q_mu[2].bias)
     ops.gemm_nt(h_last, mod.q_logvar[0].weight, l1, B, 256, Hq, bias=mod.q_logvar[0].bias, act=L.ACT_RELU)
     ops.gemm_nt(l1, mod.q_logvar[2].weight, lv, B, dz, 256, bias=mod.q_logvar[2].bias)
-    z = torch.empty(B, dz, device=dev); kl = torch.empty(1, device=dev)
+    z = torch.empty(B, dz, device=dev); kl = torch.empty(1 if fb is None else 2, device=dev)
+    if fb is not None:
+        fb["kl2"], fb["kl_dim"] = kl, W("kl_dim", (dz,))
+        latent = lambda e, **k: ops.moses_latent_fb_fwd(mu, lv, e, z, kl, fb["kl_dim"], B, dz, fb["lam"], **k)
+    else:
+        latent = lambda e, **k: ops.moses_latent_fwd(mu, lv, e, z, kl, B, dz, **k)
     if eps is None:
         seed, off = mod.noise_stream.take(B * dz)
         eps = W("eps", (B, dz))
-        ops.moses_latent_fwd(mu, lv, None, z, kl, B, dz, seed=seed, offset=off, eps_out=eps)
+        latent(None, seed=seed, offset=off, eps_out=eps)
     else:
-        ops.moses_latent_fwd(mu, lv, eps, z, kl, B, dz)
+        latent(eps)
     return z, kl, lv, eps
 
 
-def _dec_forward(mod, ws, P, x_pad, lengths, z, drop, heads=True):
-    """heads=False: return the time-major logits y_tb [T*B, V] alone (no `y` permute, no mean cross-entropy; VAE.score)."""
+def _dec_forward(mod, ws, P, x_pad, lengths, z, drop, heads=True, x_in=None):
+    """heads=False: return the time-major logits y_tb [T*B, V] alone (no `y` permute, no mean cross-entropy; VAE.score).
+    x_in (word dropout): the tokens the GRU READS; the cross-entropy targets stay x_pad."""
     dev, dt, f32 = x_pad.device, mod.compute_dtype, torch.float32
     B, T = x_pad.shape
     V, dz = mod.x_emb.num_embeddings, mod.d_z
@@ -559,7 +642,7 @@ def _dec_forward(mod, ws, P, x_pad, lengths, z, drop, heads=True):
     # layer-0 input [emb(x_t), z] (mosesvae.py:176-188): z part = time-invariant addend zp4, token part = table row x[b, t]
     ops.rnn_fwd(L.CELL_GRU, dt, T, B, Hd, zp4, 0, pd["Wih"], [pd["ldw"]] * NL, pd["Whh"], [pd["ldw"]] * NL, pd["bias"],
                 [h[1:] for h in hsx_d], ldh_d, None, gates_d, hstate_d, h0=[h[0] for h in hsx_d], ldh0=ldh_d, lengths=lengths,
-                add_table=tbl4d, add_index=x_pad,
+                add_table=tbl4d, add_index=(x_pad if x_in is None else x_in),
                 hdrop=hd, drop_mask=(None if drop is None or drop[2] is None else [drop[2][l] for l in range(NL - 1)]),
                 drop_p=(drop[0] if drop else 0.0), drop_seed=(drop[1] if drop else 0), tag="moses_dec_fwd")
     TB = T * B
@@ -583,20 +666,23 @@ def _lin_bwd(ws, grads, dev, B, tag, dy, x, WT, wname, bname, M_in, N_out, need_
     return dx
 
 
-def _onehot(mod, ws, x_pad):
-    """bf16: the token scatter as a contraction, dtbl = onehot(x)^T . dG0 over the T*B rows (both halves' table gradients use the matrix)."""
+def _onehot(mod, ws, x_pad, name="onehot_tb"):
+    """bf16: the token scatter as a contraction, dtbl = onehot(x)^T . dG0 over the T*B rows (both halves' table gradients use the matrix;
+    under word dropout the decoder half has a second one, of the tokens it read)."""
     dt = mod.compute_dtype
     if dt != torch.bfloat16:
         return None
     B, T = x_pad.shape
     V = mod.x_emb.num_embeddings
-    oh = ws.get("onehot_tb", (T * B + 8, _pad(V, 8)), dt, x_pad.device)[:T * B]
+    oh = ws.get(name, (T * B + 8, _pad(V, 8)), dt, x_pad.device)[:T * B]
     ops.onehot_tb(x_pad, oh, B, T, V)
     return oh
 
 
-def _dec_backward(mod, ws, P, grads, x_pad, lengths, drop, drecon, dy_ext, dz_ext, fork, onehot):
-    """Gradients of the decoder half: fills grads[decoder_*] and the decoder's share dE of the embedding gradient; returns (dz, finish) --
+def _dec_backward(mod, ws, P, grads, x_pad, lengths, drop, drecon, dy_ext, dz_ext, fork, onehot, x_in=None):
+    """x_in (word dropout): the tokens the GRU read -- the table gradient is scattered by them (`onehot` is then THEIR matrix), the
+    cross-entropy gradient still takes its targets from x_pad.
+    Gradients of the decoder half: fills grads[decoder_*] and the decoder's share dE of the embedding gradient; returns (dz, finish) --
     dz [B, d_z] = gradient w.r.t. the latent (incl. dz_ext), finish() = the bias column sums + the join of the side stream, to be called
     once the caller has enqueued whatever it wants to run beside the side stream's weight-gradient GEMMs."""
     dev, dt, f32 = x_pad.device, mod.compute_dtype, torch.float32
@@ -674,7 +760,7 @@ def _dec_backward(mod, ws, P, grads, x_pad, lengths, drop, drecon, dy_ext, dz_ex
         if onehot is not None:
             ops.gemm_tn(onehot, dG_d[0].view(TB, ldg_d), dtbl3, V, 3 * Hd, TB, lda=Vp8, ldb=ldg_d)
         else:
-            dtbl4 = W("dec_dtbl4", (V, 4 * Hd)); ops.scatter_rows_tb(x_pad, dG_d[0], dtbl4, B, T, V, 4 * Hd, ldd=ldg_d)
+            dtbl4 = W("dec_dtbl4", (V, 4 * Hd)); ops.scatter_rows_tb(x_pad if x_in is None else x_in, dG_d[0], dtbl4, B, T, V, 4 * Hd, ldd=ldg_d)
             dtbl3.copy_(dtbl4[:, :3 * Hd])
         ops.gemm_nt(dtbl3, pd["WxT"], dE, V, V, 3 * Hd)
         dtblT = W("dec_dtblT", (3 * Hd, Vp)); ops.cast_transpose(dtbl3, V, 3 * Hd, dstT=dtblT)
@@ -718,9 +804,9 @@ def _dec_backward(mod, ws, P, grads, x_pad, lengths, drop, drecon, dy_ext, dz_ex
     return dz_tot, finish
 
 
-def _enc_backward(mod, ws, P, grads, x_pad, lengths, eps, dz_tot, dkl, dlv_ext, onehot):
+def _enc_backward(mod, ws, P, grads, x_pad, lengths, eps, dz_tot, dkl, dlv_ext, onehot, fb=None):
     """Gradients of the encoder half from dz_tot [B, d_z] (None: no gradient through z), the KL weight and an external gradient w.r.t. logvar:
-    fills grads[encoder_rnn.*, q_mu.*, q_logvar.*] and the encoder's share dE2 of the embedding gradient."""
+    fills grads[encoder_rnn.*, q_mu.*, q_logvar.*] and the encoder's share dE2 of the embedding gradient.  fb: the forward's free-bits record."""
     dev, dt, f32 = x_pad.device, mod.compute_dtype, torch.float32
     B, T = x_pad.shape
     V, dz = mod.x_emb.num_embeddings, mod.d_z
@@ -737,7 +823,10 @@ def _enc_backward(mod, ws, P, grads, x_pad, lengths, eps, dz_tot, dkl, dlv_ext, 
     dmu, dlv = W("dmu", (B, dz)), W("dlv", (B, dz))
     if dz_tot is None:
         dz_tot = W("dz_zero", (B, dz))                                # allocated zero, never written
-    ops.moses_latent_bwd(mu, lv, eps, dz_tot, g1(dkl), c(dlv_ext), dmu, dlv, B, dz)
+    if fb is not None:
+        ops.moses_latent_fb_bwd(mu, lv, eps, dz_tot, g1(dkl), c(dlv_ext), W("kl_dim", (dz,)), fb["lam"], dmu, dlv, B, dz)
+    else:
+        ops.moses_latent_bwd(mu, lv, eps, dz_tot, g1(dkl), c(dlv_ext), dmu, dlv, B, dz)
     m1, l1 = W("m1", (B, 256)), W("l1", (B, 256))
     h_last = W("enc_hstate0", (2, B, Hq))[(T - 1) & 1]
     dm1 = lin_bwd("mu2", dmu, m1, P["mu_W2T"], "q_mu.2.weight", "q_mu.2.bias", 256, dz); ops.relu_bwd(dm1, m1)
@@ -783,15 +872,16 @@ class _MosesFn(torch.autograd.Function):
 
     @staticmethod
     @ops.traced("moses_step_fwd")
-    def forward(ctx, mod, x_pad, lengths, eps, drop, *params):
+    def forward(ctx, mod, x_pad, lengths, eps, drop, opt, *params):
         dev = x_pad.device
         _require_cuda(dev, "mosesvae.VAE")
         P = mod._pack(dev)
         slot, ws, gen = mod._next_saved_ws("enc")
         dslot, dws, dgen = mod._next_saved_ws("dec")
-        z, kl, lv, eps = _enc_forward(mod, ws, P, x_pad, lengths, eps)
-        recon, y, ntok = _dec_forward(mod, dws, P, x_pad, lengths, z, drop)
-        ctx.mod, ctx.x_pad, ctx.lengths, ctx.eps, ctx.drop = mod, x_pad, lengths, eps, drop
+        x_in, fb = (opt["x_in"], opt["fb"]) if opt else (None, None)
+        z, kl, lv, eps = _enc_forward(mod, ws, P, x_pad, lengths, eps, fb)
+        recon, y, ntok = _dec_forward(mod, dws, P, x_pad, lengths, z, drop, x_in=x_in)
+        ctx.mod, ctx.x_pad, ctx.lengths, ctx.eps, ctx.drop, ctx.x_in, ctx.fb = mod, x_pad, lengths, eps, drop, x_in, fb
         ctx.slot, ctx.gen, ctx.dslot, ctx.dgen = slot, gen, dslot, dgen
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(ntok)
@@ -809,12 +899,14 @@ class _MosesFn(torch.autograd.Function):
         names = [n for n, _ in mod.named_parameters()]
         grads = _moses_grad_views(mod, ws, names, params, dev)
         onehot = _onehot(mod, ws, x_pad)
-        dz_tot, finish = _dec_backward(mod, dws, P, grads, x_pad, lengths, drop, drecon, dy_ext, dz_ext, dy_ext is None, onehot)
-        _enc_backward(mod, ws, P, grads, x_pad, lengths, eps, dz_tot, dkl, dlv_ext, onehot)
+        x_in = ctx.x_in
+        onehot_d = onehot if x_in is None else _onehot(mod, dws, x_in, "onehot_tb_in")     # the decoder scatters by the tokens it read
+        dz_tot, finish = _dec_backward(mod, dws, P, grads, x_pad, lengths, drop, drecon, dy_ext, dz_ext, dy_ext is None, onehot_d, x_in)
+        _enc_backward(mod, ws, P, grads, x_pad, lengths, eps, dz_tot, dkl, dlv_ext, onehot, ctx.fb)
         finish()
         ge = grads["x_emb.weight"]; torch.add(grads["_dE_dec"], grads["_dE_enc"], out=ge)
         ge[mod.pad].zero_()                                           # nn.Embedding(padding_idx=pad): no gradient to the pad row
-        return (None, None, None, None, None) + tuple(grads[n] for n in names)
+        return (None, None, None, None, None, None) + tuple(grads[n] for n in names)
 
 
 class _MosesEncFn(torch.autograd.Function):
@@ -822,13 +914,14 @@ class _MosesEncFn(torch.autograd.Function):
 
     @staticmethod
     @ops.traced("moses_encoder_fwd")
-    def forward(ctx, mod, x_pad, lengths, eps, *params):
+    def forward(ctx, mod, x_pad, lengths, eps, opt, *params):
         dev = x_pad.device
         _require_cuda(dev, "mosesvae.VAE.forward_encoder")
         P = mod._pack(dev)
         slot, ws, gen = mod._next_saved_ws("enc")
-        z, kl, lv, eps = _enc_forward(mod, ws, P, x_pad, lengths, eps)
-        ctx.mod, ctx.slot, ctx.gen, ctx.x_pad, ctx.lengths, ctx.eps = mod, slot, gen, x_pad, lengths, eps
+        fb = opt["fb"] if opt else None
+        z, kl, lv, eps = _enc_forward(mod, ws, P, x_pad, lengths, eps, fb)
+        ctx.mod, ctx.slot, ctx.gen, ctx.x_pad, ctx.lengths, ctx.eps, ctx.fb = mod, slot, gen, x_pad, lengths, eps, fb
         ctx.set_materialize_grads(False)
         return z, kl[0].clone(), lv.clone()
 
@@ -842,10 +935,10 @@ class _MosesEncFn(torch.autograd.Function):
         grads = _moses_grad_views(mod, ws, names, params, dev)
         onehot = _onehot(mod, ws, x_pad)
         dz = dz_ext.contiguous().float() if dz_ext is not None else None
-        _enc_backward(mod, ws, mod._packed, grads, x_pad, lengths, eps, dz, dkl, dlv_ext, onehot)
+        _enc_backward(mod, ws, mod._packed, grads, x_pad, lengths, eps, dz, dkl, dlv_ext, onehot, ctx.fb)
         ge = grads["x_emb.weight"]; ge.copy_(grads["_dE_enc"])
         ge[mod.pad].zero_()
-        return (None, None, None, None) + tuple(grads[n] for n in names)
+        return (None, None, None, None, None) + tuple(grads[n] for n in names)
 
 
 class _MosesDecFn(torch.autograd.Function):
@@ -853,13 +946,14 @@ class _MosesDecFn(torch.autograd.Function):
 
     @staticmethod
     @ops.traced("moses_decoder_fwd")
-    def forward(ctx, mod, x_pad, lengths, z, drop, *params):
+    def forward(ctx, mod, x_pad, lengths, z, drop, opt, *params):
         dev = x_pad.device
         _require_cuda(dev, "mosesvae.VAE.forward_decoder")
         P = mod._pack(dev)
         dslot, dws, dgen = mod._next_saved_ws("dec")
-        recon, y, ntok = _dec_forward(mod, dws, P, x_pad, lengths, z.contiguous().float(), drop)
-        ctx.mod, ctx.x_pad, ctx.lengths, ctx.drop = mod, x_pad, lengths, drop
+        x_in = opt["x_in"] if opt else None
+        recon, y, ntok = _dec_forward(mod, dws, P, x_pad, lengths, z.contiguous().float(), drop, x_in=x_in)
+        ctx.mod, ctx.x_pad, ctx.lengths, ctx.drop, ctx.x_in = mod, x_pad, lengths, drop, x_in
         ctx.dslot, ctx.dgen = dslot, dgen
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(ntok)
@@ -873,10 +967,11 @@ class _MosesDecFn(torch.autograd.Function):
         dev = x_pad.device
         names, params = mod._half_params("dec")
         grads = _moses_grad_views(mod, ws, names, params, dev)
-        onehot = _onehot(mod, ws, x_pad)
-        dz_tot, finish = _dec_backward(mod, ws, mod._packed, grads, x_pad, lengths, drop, drecon, dy_ext, None, dy_ext is None, onehot)
+        x_in = ctx.x_in
+        onehot = _onehot(mod, ws, x_pad if x_in is None else x_in)
+        dz_tot, finish = _dec_backward(mod, ws, mod._packed, grads, x_pad, lengths, drop, drecon, dy_ext, None, dy_ext is None, onehot, x_in)
         finish()
         ge = grads["x_emb.weight"]; ge.copy_(grads["_dE_dec"])
         ge[mod.pad].zero_()
         dz = dz_tot.clone() if ctx.needs_input_grad[3] else None
-        return (None, None, None, dz, None) + tuple(grads[n] for n in names)
+        return (None, None, None, dz, None, None) + tuple(grads[n] for n in names)

@@ -555,6 +555,30 @@ def moses_latent_bwd(mu, logvar, eps, dz_in, dkl, dlogvar_ext, dmu, dlogvar, B, 
                                          stream_ptr()), "mvae_moses_latent_bwd")
 
 
+def moses_latent_fb_fwd(mu, logvar, eps, z, kl2, kl_dim, B, dz, free_bits, seed=0, offset=0, eps_out=None):
+    """moses_latent_fwd with free bits: kl_dim [dz] = the per-dimension batch-mean KL m_j, kl2[0] = sum_j max(m_j, free_bits) (the
+    objective), kl2[1] = sum_j m_j (the KL); z / eps_out bitwise as moses_latent_fwd writes them (mvae_moses_latent_fb_fwd)."""
+    lib = L.load()
+    need = lib.mvae_moses_latent_fb_workspace(B, dz)
+    ws = Scratch.get(need, mu.device)
+    check(lib.mvae_moses_latent_fb_fwd(B, dz, ptr(mu), ptr(logvar), ptr(eps), int(seed) & 0xFFFFFFFF, int(offset), ptr(eps_out), float(free_bits),
+                                       ptr(z), ptr(kl2), ptr(kl_dim), ptr(ws), need, stream_ptr()), "mvae_moses_latent_fb_fwd")
+
+
+def moses_latent_fb_bwd(mu, logvar, eps, dz_in, dkl, dlogvar_ext, kl_dim, free_bits, dmu, dlogvar, B, dz):
+    """moses_latent_bwd with the KL term of dimension j switched by kl_dim[j] >= free_bits (mvae_moses_latent_fb_bwd)."""
+    check(L.load().mvae_moses_latent_fb_bwd(B, dz, ptr(mu), ptr(logvar), ptr(eps), ptr(dz_in), ptr(dkl), ptr(dlogvar_ext), ptr(kl_dim),
+                                            float(free_bits), ptr(dmu), ptr(dlogvar), stream_ptr()), "mvae_moses_latent_fb_bwd")
+
+
+def token_dropout(x, lengths, x_out, B, T, unk_id, p, seed=0, keep_mask=None, n_dropped=None):
+    """Word dropout: x_out[b, t] = unk_id at the eligible positions (1 <= t <= lengths[b] - 2) that are not kept, x[b, t] elsewhere.  Kept =
+    keep_mask [B, T] bytes when given, else the counter hash at b * T + t -- dropout_keep_mask(seed, (B, T), p) restates it on the host.
+    n_dropped (int32 [1], optional) receives the number of replaced positions (mvae_token_dropout)."""
+    check(L.load().mvae_token_dropout(ptr(x), ptr(lengths), B, T, int(unk_id), float(p), int(seed) & 0xFFFFFFFF, ptr(keep_mask), ptr(x_out),
+                                      ptr(n_dropped), stream_ptr()), "mvae_token_dropout")
+
+
 def ce_loss_fwd(logits, ldl, x, pad, loss2, B, T, V):
     lib = L.load()
     need = lib.mvae_ce_loss_workspace(B, T)

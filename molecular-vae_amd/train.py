@@ -600,6 +600,23 @@ class KLAnnealer:
         return self.w_start + k * self.inc
 
 
+class CyclicalKLAnnealer:
+    """Cyclical KL-weight schedule (an addition: Fu et al. 2019, *Cyclical Annealing Schedule: A Simple Approach to Mitigating KL
+    Vanishing*): within every cycle of `n_steps_per_cycle` steps the weight rises linearly from 0 to `w_max` over the first `ratio` of
+    the cycle and then holds at `w_max`; the next cycle starts from 0 again.  Callable with a step index, like KLAnnealer."""
+
+    def __init__(self, n_steps_per_cycle, ratio=0.5, w_max=1.0):
+        if int(n_steps_per_cycle) < 1 or int(n_steps_per_cycle) != n_steps_per_cycle:
+            raise ValueError(f"CyclicalKLAnnealer: n_steps_per_cycle must be an integer >= 1, got {n_steps_per_cycle}")
+        if not (0.0 < ratio <= 1.0):
+            raise ValueError(f"CyclicalKLAnnealer: ratio must be in (0, 1], got {ratio}")
+        self.n_steps_per_cycle, self.ratio, self.w_max = int(n_steps_per_cycle), float(ratio), float(w_max)
+
+    def __call__(self, i):
+        pos = (int(i) % self.n_steps_per_cycle) / self.n_steps_per_cycle          # position inside the cycle, [0, 1)
+        return self.w_max * min(1.0, pos / self.ratio)
+
+
 # ------------------------------------------------------------------------------------------------ evaluation / checkpoints
 @torch.no_grad()
 def evaluate(model, loss_function, batches):
@@ -713,7 +730,9 @@ def moses_train_step(model, optimizer, kl_weight, batch, eps=None):
 
 def moses_train_epoch(model, epoch, batches, kl_weight, optimizer=None, log_every=0, log=print):
     """``_train_epoch`` (moses_train_distrib.py:200-258): train when an optimiser is given, else evaluate; returns the same ``postfix``
-    dictionary (epoch means instead of the reference's 1000-entry circular-buffer means, which average over unwritten zeros)."""
+    dictionary (epoch means instead of the reference's 1000-entry circular-buffer means, which average over unwritten zeros).  While the
+    model trains with free bits (``model.free_bits > 0``: ``kl_loss`` is then the free-bits objective) the KL itself, ``model.last_kl``,
+    is logged beside it and returned as ``kl_true``."""
     model.train(optimizer is not None)
     sums, n = None, 0
     for i, batch in enumerate(batches):
@@ -723,16 +742,22 @@ def moses_train_epoch(model, epoch, batches, kl_weight, optimizer=None, log_ever
             with torch.no_grad():
                 kl, rec, _, _, _, _ = model(batch)
             vals = (kl_weight * kl + rec, kl, rec)
+        if getattr(model, "last_kl", None) is not None:           # free bits on: kl is the objective, last_kl the KL itself
+            vals = tuple(vals) + (model.last_kl,)
         v = torch.stack([x.float() for x in vals])
         sums = v if sums is None else sums + v
         n += 1
         if log_every and i % log_every == 0:
             cur = (sums / n).tolist()
-            log(f"epoch {epoch} it {i}: loss={cur[0]:.5f} (kl={cur[1]:.5f} recon={cur[2]:.5f}) klw={kl_weight:.5f}")
+            true_kl = f" kl_true={cur[3]:.5f}" if len(cur) > 3 else ""
+            log(f"epoch {epoch} it {i}: loss={cur[0]:.5f} (kl={cur[1]:.5f}{true_kl} recon={cur[2]:.5f}) klw={kl_weight:.5f}")
     mean = (sums / max(n, 1)).tolist() if sums is not None else [float("nan")] * 3
     lr = optimizer.param_groups[0]["lr"] if optimizer is not None else None
-    return {"epoch": epoch, "kl_weight": kl_weight, "lr": lr, "kl_loss": mean[1], "recon_loss": mean[2], "loss": mean[0],
+    post = {"epoch": epoch, "kl_weight": kl_weight, "lr": lr, "kl_loss": mean[1], "recon_loss": mean[2], "loss": mean[0],
             "mode": "Eval" if optimizer is None else "Train"}
+    if len(mean) > 3:
+        post["kl_true"] = mean[3]
+    return post
 
 
 @torch.no_grad()
