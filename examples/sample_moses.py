@@ -4,9 +4,11 @@
 here ``mv.moses_generate`` hashes the token rows inside the sampling launches and deduplicates them on the device, so only sequences not
 seen before in their round reach the host; the rounds are merged in a dictionary.  Checkpoint and vocabulary as ``examples/train_moses.py``
 writes them (without them: a seeded random model over a synthetic corpus' vocabulary, which exercises the path but generates noise).
-``valid`` needs rdkit (``Chem.MolFromSmiles``); without it the column is left empty.
+``valid`` needs rdkit (``Chem.MolFromSmiles``); without it the column is left empty.  ``syntax_valid`` needs nothing: it is the number of
+samples (duplicates included) that are well-formed SMILES strings -- balanced branches, closed rings and brackets, no dangling bond;
+syntax, not chemistry -- counted on the device.  ``--syntax`` samples under that grammar, so that every sample is well-formed.
 
-    python examples/sample_moses.py --ckpt trained_save.pt --vocab vocab.pkl --rounds 10 --top_p 0.95
+    python examples/sample_moses.py --ckpt trained_save.pt --vocab vocab.pkl --rounds 10 --top_p 0.95 --syntax
 """
 import argparse
 import os
@@ -30,6 +32,7 @@ ap.add_argument("--max_len", default=100, type=int)
 ap.add_argument("--temp", default=1.0, type=float)
 ap.add_argument("--top_k", default=None, type=int)
 ap.add_argument("--top_p", default=None, type=float)
+ap.add_argument("--syntax", action="store_true", help="constrain every step to the tokens that keep the string well-formed SMILES")
 ap.add_argument("--prior", default="normal", choices=["normal", "zeros"], help="zeros = sample_z_prior as the reference is written")
 ap.add_argument("--seed", default=0, type=int)
 ap.add_argument("--log", default="log_small.csv")
@@ -64,15 +67,16 @@ def is_valid(s):
         return False
 
 
-seen, total, valid = {}, 0, 0
+seen, total, valid, syntax_valid = {}, 0, 0, 0
 per_round = args.batch_size * args.batches_per_round
 start = time.time()
 with open(args.log, "w", buffering=1) as f:
-    f.write("time,unique,valid,total\n")
+    f.write("time,unique,valid,total,syntax_valid\n")
     for r in range(args.rounds):
         res = mv.moses_generate(model, per_round, batch_size=args.batch_size, max_len=args.max_len, temp=args.temp, top_k=args.top_k,
-                                top_p=args.top_p, seed=args.seed + r * args.batches_per_round)
+                                top_p=args.top_p, seed=args.seed + r * args.batches_per_round, syntax=args.syntax, count_valid=True)
         total += res["total"]
+        syntax_valid += res["valid"]
         for s, c in zip(res["strings"], res["counts"]):
             if s not in seen:
                 seen[s] = 0
@@ -80,9 +84,10 @@ with open(args.log, "w", buffering=1) as f:
                     valid += 1
             seen[s] += c
         now = time.time()
-        f.write("{0},{1},{2},{3}\n".format(now, len(seen), valid if Chem is not None else "", total))
+        f.write("{0},{1},{2},{3},{4}\n".format(now, len(seen), valid if Chem is not None else "", total, syntax_valid))
         print(f"round {r}: unique {len(seen)} ({len(seen) / total:.3f}), sampled {total}, samples per second {total / (now - start):.0f}, "
-              f"unique per second {len(seen) / (now - start):.0f}" + (f", valid unique {valid}" if Chem is not None else ""), flush=True)
+              f"unique per second {len(seen) / (now - start):.0f}, well-formed {syntax_valid} ({syntax_valid / total:.3f})"
+              + (f", valid unique {valid}" if Chem is not None else ""), flush=True)
 if args.out:
     with open(args.out, "w") as f:
         for s, c in sorted(seen.items(), key=lambda kv: -kv[1]):

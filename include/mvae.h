@@ -524,6 +524,41 @@ int mvae_moses_sample_filtered_step(int dtype, int B, int V, int H, const void* 
                                     float temp, int top_k, float top_p, uint32_t seed, int step, int eos_id, const float* table, int W,
                                     const float* base, float* add_out, int64_t* x, int64_t x_ld, int64_t* end_pads, uint8_t* eos_mask,
                                     int64_t* w_out, float* logq /* [B] or NULL */, int64_t* hash /* [B] or NULL */, void* stream);
+/* SMILES syntax (an addition): a small automaton over the tokens decides whether a character-level SMILES string is well-formed --
+ * balanced branches, closed rings and brackets, no dangling bond, a bracket-atom grammar.  Syntax only: valence and aromaticity are not
+ * checked.  It accepts a conservative subset of OpenSMILES: no %nn ring numbers, no '.', no isotopes, no "++" / "--", no ring digit
+ * after a bond, at most 15 open branches; a ring may not close on the atom that opened it.  Accepted strings, with a = an organic-subset
+ * atom (B C N O P S F I b c n o p s, Cl, Br), bond = one of = # : / \ -:
+ *   chain   := atom ( ringdigit* ( bond? atom | '(' bond? chain ')' )* )*        every ring digit opened is closed on a later atom
+ *   atom    := a | '[' ( a | 'H' ) '@'{0,2} ( 'H' digit? )? ( ('+'|'-') digit? )? ']'       ("[H" takes no chirality or H count)
+ * Layouts (the tests build states with them):
+ *   tok_info int32 [V], one word per token id: bits 0-7 the class -- 0 OTHER (never allowed: <bos>, <pad>, <unk>, unknown characters),
+ *     1 ATOM, 2 TAIL ('l' / 'r'), 3 H, 4 BOND (= # : / \), 5 MINUS, 6 PLUS, 7 AT, 8 DIGIT, 9 LPAR, 10 RPAR, 11 LBRK, 12 RBRK, 13 EOS --,
+ *     bits 8-15 for a TAIL the id of the token it must follow ('C' / 'B') plus 1, bits 16-19 for a DIGIT its value.
+ *   state int32 [B, 2]: word 0 = mode | depth << 8 | prev_id << 16 (prev_id 0xFF: none), word 1 = open | cur << 16; depth = open
+ *     branches, open = 10-bit mask of open ring digits, cur = mask of the ring digits already used on the current atom.  Modes: 0 START,
+ *     1 ATOM, 2 ATOMX (after Cl / Br / ']'), 3 RING, 4 BOND, 5 OPEN, 6 CLOSE, 7 KOPEN ('['), 8 KSYM, 9 KSYMX, 10 KCHI1, 11 KCHI2, 12 KH,
+ *     13 KHN, 14 KCHG, 15 KCHGN, 16 END, 17 ERROR.  The initial state is {0 | 0xFF << 16, 0}.
+ * mvae_moses_sample_syntax_step: mvae_moses_sample_filtered_step constrained by the automaton.  For a row that had not ended, class v
+ *   is allowed iff the automaton takes it from gstate[b] AND the tokens still needed to finish the string after it (<eos> included) fit
+ *   the max_len - 1 - step that remain.  The stabilising max of the softmax runs over the allowed classes only, the others get
+ *   probability 0; top-k / top-p rank the allowed classes among themselves (top_p of the legal mass); the draw, its "u rounded up"
+ *   fallback (the last class kept AND allowed), logq (of the constrained distribution), hash and the bookkeeping are those of the
+ *   filtered step; gstate[b] advances by the drawn token.  Some allowed token always lowers the need by one, so with max_len >= 3 the
+ *   allowed set is never empty and every row draws <eos> by step max_len - 1; were it empty, the row emits <eos> and its mode becomes
+ *   ERROR.  Rows that had ended are neither masked nor advanced.  Refused (MVAE_ERR_INVALID) before anything is enqueued: what the
+ *   filtered entry refuses, a null tok_info or gstate, max_len < 3, step < 1, step >= max_len, eos_id outside [0, V).
+ * mvae_smiles_syntax_check: one thread per row of x [B, T] int64 (bos first; x_ld >= T) runs the automaton over x[b, 1:] until <eos> is
+ *   taken.  valid[b] = 1 iff it is; bad_pos[b] (optional) = the index of the first refused token (an id outside [0, V) is refused), T when
+ *   the row ran out without <eos>, -1 when the row is valid.  eos_id is the only token that ends a row: it counts as EOS whatever
+ *   tok_info says of it, and another id that tok_info calls EOS is refused.  V <= 64. */
+int mvae_moses_sample_syntax_step(int dtype, int B, int V, int H, const void* h_top, int64_t ldh, const void* w_fc, int64_t ldw, const float* bias,
+                                  float temp, int top_k, float top_p, uint32_t seed, int step, int eos_id, const float* table, int W,
+                                  const float* base, float* add_out, int64_t* x, int64_t x_ld, int64_t* end_pads, uint8_t* eos_mask,
+                                  int64_t* w_out, float* logq /* [B] or NULL */, int64_t* hash /* [B] or NULL */, const int32_t* tok_info /* [V] */,
+                                  int32_t* gstate /* [B, 2] */, int max_len, void* stream);
+int mvae_smiles_syntax_check(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */, int eos_id,
+                             uint8_t* valid /* [B] */, int32_t* bad_pos /* [B] or NULL */, void* stream);
 /* Beam-search decoding (an addition beyond the reference, which only samples): R = B * K rows, molecule m owning rows m*K .. m*K + K-1.
  * mvae_moses_beam_step: one launch per generated token behind the GRU step.  logp = log_softmax(decoder_fc(h_top)) (w_fc [V, ldw] dtype,
  *   V <= 64 else MVAE_ERR_UNSUPPORTED; 1 <= K <= min(16, V) else MVAE_ERR_INVALID).  An active beam proposes its top-K tokens at

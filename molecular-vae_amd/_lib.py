@@ -157,6 +157,9 @@ SIGNATURES = {
     "mvae_moses_sample_step": (_i, [_i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _f, C.c_uint32, _i, _i, _vp, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "mvae_moses_sample_filtered_step": (_i, [_i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _f, _i, _f, C.c_uint32, _i, _i, _vp, _i, _vp, _vp, _vp, _i64,
                                              _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvae_moses_sample_syntax_step": (_i, [_i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _f, _i, _f, C.c_uint32, _i, _i, _vp, _i, _vp, _vp, _vp, _i64,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "mvae_smiles_syntax_check": (_i, [_i, _i, _i, _vp, _i64, _vp, _i, _vp, _vp, _vp]),
     "mvae_moses_beam_step": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                   _vp, _vp]),
     "mvae_moses_beam_finalize": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -5,6 +5,7 @@
 #include <atomic>
 #include "common.hpp"
 #include "kernels.hpp"
+#include "smiles_syntax.hpp"
 #include <stdlib.h>
 
 static inline int grid_for(long n, int per_block = 256, int cap = 2048) {
@@ -1019,20 +1020,29 @@ __global__ __launch_bounds__(256) void moses_sample_step_kernel(int B, int V, in
 // "read lane u (uniform index), compare, add".  keep = (rank < top_k, 0: off) and (before < top_p * sum(p) or rank 0; top_p >= 1: off), both
 // on the unfiltered p;  q = keep ? e : 0;  the draw is the first KEPT class with cumsum(q) > u * sum(q).  With both filters off q == e and
 // the draw is the existing one.  A row that had not ended before this step adds log(q_w / sum q) to logq[b] and folds w into hash[b].
-template <typename T>
+//
+// SYNTAX (mvae_moses_sample_syntax_step; the other instantiation compiles none of it): a row that had not ended carries a SMILES automaton
+// state gstate[b] (smiles_syntax.hpp).  Lane v decides whether class v is allowed -- the automaton takes it AND the string can still be
+// finished in the max_len - 1 - step tokens left after it -- before the softmax: the stabilising max runs over the allowed classes only (a
+// dominant illegal logit would underflow every legal one), e = 0 for the others, and the filters rank the legal classes among
+// themselves.  The drawn token then advances gstate[b].  Ended rows are neither masked nor advanced.
+template <typename T, bool SYNTAX>
 __global__ __launch_bounds__(256) void moses_sample_filtered_step_kernel(int B, int V, int H, const T* __restrict__ h, long ldh, const T* __restrict__ wfc,
                                                                          long ldw, const float* __restrict__ bias, float inv_temp, int top_k, float top_p,
                                                                          uint32_t seed, int step, int eos_id, const float* __restrict__ table, int W,
                                                                          const float* __restrict__ base, float* __restrict__ add_out,
                                                                          int64_t* __restrict__ x, long x_ld, int64_t* __restrict__ end_pads,
                                                                          uint8_t* __restrict__ eos_mask, int64_t* __restrict__ w_out,
-                                                                         float* __restrict__ logq, int64_t* __restrict__ hash) {
+                                                                         float* __restrict__ logq, int64_t* __restrict__ hash,
+                                                                         const int32_t* __restrict__ tok_info, int32_t* __restrict__ gstate, int max_len) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   T* ws = reinterpret_cast<T*>(smem_raw);                    // [V][H]
   for (int i = threadIdx.x; i < V * H; i += 256) ws[i] = wfc[(long)(i / H) * ldw + (i % H)];
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool filtered = top_k > 0 || top_p < 1.f;            // kernel-uniform
+  int32_t my_info = 0;
+  if constexpr (SYNTAX) my_info = lane < V ? tok_info[lane] : 0;
   for (int b = blockIdx.x * 4 + wave; b < B; b += gridDim.x * 4) {
     float mine = -INFINITY;
     for (int v = 0; v < V; ++v) {
@@ -1041,19 +1051,32 @@ __global__ __launch_bounds__(256) void moses_sample_filtered_step_kernel(int B, 
       a = wave_sum(a);
       if (lane == v) mine = (a + (bias ? bias[v] : 0.f)) * inv_temp;
     }
-    const float mx = wave_max(mine);
-    const float e = (lane < V) ? __expf(mine - mx) : 0.f;
+    bool allowed = lane < V;
+    bool live = false;                                       // SYNTAX: the row had not ended before this step (wave-uniform)
+    smi::State gs{};
+    if constexpr (SYNTAX) {
+      live = eos_mask[b] == 0;
+      if (live) {
+        gs = smi::unpack(gstate[2 * (long)b], gstate[2 * (long)b + 1]);
+        smi::State nx;
+        allowed = allowed && smi::step(gs, lane, my_info, &nx) && smi::need(nx) <= max_len - 1 - step;
+      }
+    }
+    const unsigned long long amask = SYNTAX ? __ballot(allowed) : 0ull;
+    const float mx = SYNTAX ? wave_max(allowed ? mine : -INFINITY) : wave_max(mine);
+    const float e = SYNTAX ? (allowed ? __expf(mine - mx) : 0.f) : ((lane < V) ? __expf(mine - mx) : 0.f);
     float c = e;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) { const float up = __shfl_up(c, o, 64); if (lane >= o) c += up; }
     float tot = __shfl(c, 63, 64);
-    bool keep = lane < V;
+    bool keep = allowed;
     float q = e;
     if (filtered) {
       int rank = 0;
       float before = 0.f;
       for (int u = 0; u < V; ++u) {                          // uniform index: a lane read, not a permute
         const float eu = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e), u));
+        if (SYNTAX && !((amask >> u) & 1ull)) continue;      // the legal classes are ranked among themselves
         if (eu > e || (eu == e && u < lane)) { ++rank; before += eu; }
       }
       keep = keep && (top_k == 0 || rank < top_k) && (!(top_p < 1.f) || rank == 0 || before < top_p * tot);
@@ -1067,15 +1090,23 @@ __global__ __launch_bounds__(256) void moses_sample_filtered_step_kernel(int B, 
     const float u = (float)hsh * (1.0f / 4294967296.0f) * tot;
     const unsigned long long kept = __ballot(keep);          // never empty: the rank-0 class is kept
     const unsigned long long above = __ballot(keep && c > u);
-    const int w = above ? (int)__builtin_ctzll(above) : (kept ? 63 - (int)__builtin_clzll(kept) : V - 1);   // (u rounds up to tot: the last kept class)
+    int w = above ? (int)__builtin_ctzll(above) : (kept ? 63 - (int)__builtin_clzll(kept) : V - 1);   // (u rounds up to tot: the last kept class)
+    const bool stuck = SYNTAX && live && amask == 0ull;      // an empty allowed set (the feasibility rule excludes it): <eos>, state ERROR
+    if (stuck) w = eos_id;
     const float qw = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q), w));
     if (lane == 0) {
       const bool done = eos_mask[b] != 0;
       if (!done) {
         x[(long)b * x_ld + step] = w;
         if (w == eos_id) { end_pads[b] = step + 1; eos_mask[b] = 1; }
-        if (logq) logq[b] += logf(qw / tot);
+        if (logq && !stuck) logq[b] += logf(qw / tot);
         if (hash) hash[b] = (int64_t)(((uint64_t)hash[b] ^ (uint64_t)w) * 0x100000001b3ULL);
+        if constexpr (SYNTAX) {
+          smi::State nx;
+          if (stuck || !smi::step(gs, w, tok_info[w], &nx)) { nx = gs; nx.mode = smi::ERROR; }
+          gstate[2 * (long)b] = smi::pack0(nx);
+          gstate[2 * (long)b + 1] = smi::pack1(nx);
+        }
       }
       w_out[b] = w;
     }
@@ -1087,6 +1118,32 @@ __global__ __launch_bounds__(256) void moses_sample_filtered_step_kernel(int B, 
       *reinterpret_cast<float4*>(orow + cidx) = make_float4(tv.x + bv.x, tv.y + bv.y, tv.z + bv.z, tv.w + bv.w);
     }
   }
+}
+
+// The automaton over finished token rows: one thread per row runs smi::step over x[b, 1:] until it reaches END (the <eos> token taken in a
+// state that may end).  valid[b] = 1 iff it does; bad_pos[b] = the index of the first refused token (an id outside [0, V) is one), T when
+// the row ran out without <eos>, -1 when the row is valid.  eos_id is the only token that ends a row: it counts as EOS whatever the
+// table says of it, and another id the table calls EOS is refused.
+__global__ __launch_bounds__(64) void smiles_syntax_check_kernel(int B, int T, int V, const int64_t* __restrict__ x, long x_ld,
+                                                                 const int32_t* __restrict__ tok_info, int eos_id,
+                                                                 uint8_t* __restrict__ valid, int32_t* __restrict__ bad_pos) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  smi::State s{smi::START, 0, smi::NO_PREV, 0, 0};
+  int bad = T;
+  for (int t = 1; t < T; ++t) {
+    const int64_t tok = x[(long)b * x_ld + t];
+    smi::State nx;
+    if (tok < 0 || tok >= V) { bad = t; break; }
+    int32_t info = tok_info[tok];
+    if (tok == eos_id) info = smi::C_EOS;
+    else if ((info & 0xFF) == smi::C_EOS) info = smi::C_OTHER;
+    if (!smi::step(s, (int)tok, info, &nx)) { bad = t; break; }
+    s = nx;
+    if (s.mode == smi::END) { bad = -1; break; }
+  }
+  valid[b] = bad < 0 ? 1 : 0;
+  if (bad_pos) bad_pos[b] = bad;
 }
 
 // ------------------------------------------------------------------------------------------- beam-search decoding step (no reference counterpart)
@@ -1652,6 +1709,50 @@ __global__ __launch_bounds__(256) void onehot_tb_kernel(const int64_t* idx, int 
   }
 }
 
+// the launch behind mvae_moses_sample_filtered_step (SYNTAX = false) and mvae_moses_sample_syntax_step (true); the callers have checked
+template <bool SYNTAX>
+static int sample_filtered_launch(int dtype, int B, int V, int H, const void* h_top, int64_t ldh, const void* w_fc, int64_t ldw, const float* bias,
+                                  float temp, int top_k, float top_p, uint32_t seed, int step, int eos_id, const float* table, int W,
+                                  const float* base, float* add_out, int64_t* x, int64_t x_ld, int64_t* end_pads, uint8_t* eos_mask,
+                                  int64_t* w_out, float* logq, int64_t* hash, const int32_t* tok_info, int32_t* gstate, int max_len, void* stream) {
+  const size_t lds = (size_t)V * H * (dtype == MVAE_BF16 ? 2 : 4);
+  if (lds > 160 * 1024) return MVAE_ERR_UNSUPPORTED;                 // the head must fit the CU's LDS, as in mvae_moses_sample_step
+  if (lds > 64 * 1024) {                                              // above the default dynamic-LDS limit: opt in
+    static std::atomic<bool> attr[64];
+    int dev_id = 0;
+    MVAE_CHECK_HIP(hipGetDevice(&dev_id));
+    if (dev_id < 0 || dev_id >= 64 || !attr[dev_id].load(std::memory_order_acquire)) {
+      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(moses_sample_filtered_step_kernel<float, SYNTAX>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(moses_sample_filtered_step_kernel<bf16_t, SYNTAX>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      if (dev_id >= 0 && dev_id < 64) attr[dev_id].store(true, std::memory_order_release);
+    }
+  }
+  if (top_p > 1.f) top_p = 1.f;                                       // larger values mean off
+  int blocks = (B + 3) / 4; if (blocks > 1024) blocks = 1024;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MVAE_BF16)
+    hipLaunchKernelGGL((moses_sample_filtered_step_kernel<bf16_t, SYNTAX>), dim3(blocks), dim3(256), lds, st, B, V, H, (const bf16_t*)h_top, (long)ldh,
+                       (const bf16_t*)w_fc, (long)ldw, bias, 1.f / temp, top_k, top_p, seed, step, eos_id, table, W, base, add_out, x, (long)x_ld,
+                       end_pads, eos_mask, w_out, logq, hash, tok_info, gstate, max_len);
+  else
+    hipLaunchKernelGGL((moses_sample_filtered_step_kernel<float, SYNTAX>), dim3(blocks), dim3(256), lds, st, B, V, H, (const float*)h_top, (long)ldh,
+                       (const float*)w_fc, (long)ldw, bias, 1.f / temp, top_k, top_p, seed, step, eos_id, table, W, base, add_out, x, (long)x_ld,
+                       end_pads, eos_mask, w_out, logq, hash, tok_info, gstate, max_len);
+  MVAE_CHECK_HIP(hipGetLastError());
+  return MVAE_OK;
+}
+
+// what mvae_moses_sample_filtered_step refuses (MVAE_ERR_INVALID), shared with the syntax entry
+static bool sample_filtered_args_ok(int dtype, int B, int V, int H, const void* h_top, const void* w_fc, float temp, int top_k, float top_p, int step,
+                                    const float* table, int W, const float* base, float* add_out, int64_t* x, int64_t* end_pads, uint8_t* eos_mask,
+                                    int64_t* w_out) {
+  if (!h_top || !w_fc || !table || !base || !add_out || !x || !end_pads || !eos_mask || !w_out) return false;
+  if (dtype != MVAE_F32 && dtype != MVAE_BF16) return false;
+  if (B < 1 || V < 1 || V > 64 || H < 1 || (W & 3) || W < 4 || !(temp > 0.f) || step < 0) return false;
+  if (top_k < 0 || top_k > V || !(top_p > 0.f)) return false;                 // (a NaN top_p fails the comparison)
+  return true;
+}
+
 // ------------------------------------------------------------------------------------------- extern "C" surface
 extern "C" {
 
@@ -2092,33 +2193,28 @@ int mvae_moses_sample_filtered_step(int dtype, int B, int V, int H, const void* 
                                     float temp, int top_k, float top_p, uint32_t seed, int step, int eos_id, const float* table, int W,
                                     const float* base, float* add_out, int64_t* x, int64_t x_ld, int64_t* end_pads, uint8_t* eos_mask,
                                     int64_t* w_out, float* logq, int64_t* hash, void* stream) {
-  if (!h_top || !w_fc || !table || !base || !add_out || !x || !end_pads || !eos_mask || !w_out) return MVAE_ERR_INVALID;
-  if (dtype != MVAE_F32 && dtype != MVAE_BF16) return MVAE_ERR_INVALID;
-  if (B < 1 || V < 1 || V > 64 || H < 1 || (W & 3) || W < 4 || !(temp > 0.f) || step < 0) return MVAE_ERR_INVALID;
-  if (top_k < 0 || top_k > V || !(top_p > 0.f)) return MVAE_ERR_INVALID;     // (a NaN top_p fails the comparison)
-  const size_t lds = (size_t)V * H * (dtype == MVAE_BF16 ? 2 : 4);
-  if (lds > 160 * 1024) return MVAE_ERR_UNSUPPORTED;                 // the head must fit the CU's LDS, as in mvae_moses_sample_step
-  if (lds > 64 * 1024) {                                              // above the default dynamic-LDS limit: opt in
-    static std::atomic<bool> attr[64];
-    int dev_id = 0;
-    MVAE_CHECK_HIP(hipGetDevice(&dev_id));
-    if (dev_id < 0 || dev_id >= 64 || !attr[dev_id].load(std::memory_order_acquire)) {
-      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(moses_sample_filtered_step_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(moses_sample_filtered_step_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      if (dev_id >= 0 && dev_id < 64) attr[dev_id].store(true, std::memory_order_release);
-    }
-  }
-  if (top_p > 1.f) top_p = 1.f;                                       // larger values mean off
-  int blocks = (B + 3) / 4; if (blocks > 1024) blocks = 1024;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == MVAE_BF16)
-    hipLaunchKernelGGL((moses_sample_filtered_step_kernel<bf16_t>), dim3(blocks), dim3(256), lds, st, B, V, H, (const bf16_t*)h_top, (long)ldh,
-                       (const bf16_t*)w_fc, (long)ldw, bias, 1.f / temp, top_k, top_p, seed, step, eos_id, table, W, base, add_out, x, (long)x_ld,
-                       end_pads, eos_mask, w_out, logq, hash);
-  else
-    hipLaunchKernelGGL((moses_sample_filtered_step_kernel<float>), dim3(blocks), dim3(256), lds, st, B, V, H, (const float*)h_top, (long)ldh,
-                       (const float*)w_fc, (long)ldw, bias, 1.f / temp, top_k, top_p, seed, step, eos_id, table, W, base, add_out, x, (long)x_ld,
-                       end_pads, eos_mask, w_out, logq, hash);
+  if (!sample_filtered_args_ok(dtype, B, V, H, h_top, w_fc, temp, top_k, top_p, step, table, W, base, add_out, x, end_pads, eos_mask, w_out))
+    return MVAE_ERR_INVALID;
+  return sample_filtered_launch<false>(dtype, B, V, H, h_top, ldh, w_fc, ldw, bias, temp, top_k, top_p, seed, step, eos_id, table, W, base, add_out,
+                                       x, x_ld, end_pads, eos_mask, w_out, logq, hash, nullptr, nullptr, 0, stream);
+}
+
+int mvae_moses_sample_syntax_step(int dtype, int B, int V, int H, const void* h_top, int64_t ldh, const void* w_fc, int64_t ldw, const float* bias,
+                                  float temp, int top_k, float top_p, uint32_t seed, int step, int eos_id, const float* table, int W,
+                                  const float* base, float* add_out, int64_t* x, int64_t x_ld, int64_t* end_pads, uint8_t* eos_mask,
+                                  int64_t* w_out, float* logq, int64_t* hash, const int32_t* tok_info, int32_t* gstate, int max_len, void* stream) {
+  if (!sample_filtered_args_ok(dtype, B, V, H, h_top, w_fc, temp, top_k, top_p, step, table, W, base, add_out, x, end_pads, eos_mask, w_out))
+    return MVAE_ERR_INVALID;
+  if (!tok_info || !gstate || max_len < 3 || step < 1 || step >= max_len) return MVAE_ERR_INVALID;
+  if (eos_id < 0 || eos_id >= V) return MVAE_ERR_INVALID;            // the empty-set fallback emits it
+  return sample_filtered_launch<true>(dtype, B, V, H, h_top, ldh, w_fc, ldw, bias, temp, top_k, top_p, seed, step, eos_id, table, W, base, add_out,
+                                      x, x_ld, end_pads, eos_mask, w_out, logq, hash, tok_info, gstate, max_len, stream);
+}
+
+int mvae_smiles_syntax_check(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, int eos_id, uint8_t* valid, int32_t* bad_pos,
+                             void* stream) {
+  if (!x || !tok_info || !valid || B < 1 || T < 1 || V < 1 || V > 64 || x_ld < T || eos_id < 0 || eos_id >= V) return MVAE_ERR_INVALID;
+  hipLaunchKernelGGL(smiles_syntax_check_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, T, V, x, (long)x_ld, tok_info, eos_id, valid, bad_pos);
   MVAE_CHECK_HIP(hipGetLastError());
   return MVAE_OK;
 }

@@ -31,7 +31,7 @@ from . import _lib as L
 from . import ops
 from .models import (LinearWeights, EmbeddingWeights, RNNWeights, _Workspace, _SavedState, _pad, _require_cuda, _LDPAD, _dyk, _grad_views, _kmajor_gemm,
                      _pack_rnn_stack, _gru_param_grads)
-from .vocab import PaddedBatch, pad_batch
+from .vocab import PaddedBatch, pad_batch, smiles_token_table
 
 
 class _RowsWorkspace(_Workspace):
@@ -271,7 +271,8 @@ class VAE(_SavedState, nn.Module):
         return torch.randn(n_batch, self.d_z, device=self.device)
 
     @torch.no_grad()
-    def sample(self, n_batch, max_len=100, z=None, temp=1.0, return_tokens=False, seed=None, top_k=None, top_p=None, return_logp=False):
+    def sample(self, n_batch, max_len=100, z=None, temp=1.0, return_tokens=False, seed=None, top_k=None, top_p=None, return_logp=False,
+               syntax=False):
         """mosesvae.py:214-262 (autoregressive decoding, multinomial sampling at temperature `temp`) on the GRU step kernels: per generated token
         one wavefront pass of the 3-layer stack (T = 1) and ONE sampling launch (head GEMV + softmax + multinomial + eos / end-pad bookkeeping +
         the next token's input rows: mvae_moses_sample_step) -- 4 launches per token, no torch arithmetic in the loop.  Randomness is explicit:
@@ -283,8 +284,16 @@ class VAE(_SavedState, nn.Module):
         logq, float32 [B] on the device: the summed log-probability of tokens 1 .. end under the distribution they were drawn from,
         temperature and truncation included (at temp = 1 with the filters off that is log p(x | z) as `decode` reports it: an emitted `pad`
         token counts, unlike in `score`).  With a filter or return_logp the sampling launch is mvae_moses_sample_filtered_step (still 4
-        launches per token); without them the method runs the launches it always ran.  The same seed gives the same tokens either way."""
+        launches per token); without them the method runs the launches it always ran.  The same seed gives the same tokens either way.
+        `syntax=True` (an addition) constrains every step to the tokens that keep the string a well-formed SMILES
+        string that can still be finished within max_len: balanced branches, closed rings and brackets, no dangling bond, a conservative
+        bracket-atom grammar -- syntax only, valence and aromaticity stay unchecked.  The mask sits in front of the softmax inside the
+        sampling launch (mvae_moses_sample_syntax_step, still 4 launches per token); top_k / top_p then act on the legal tokens and logq
+        is that of the constrained distribution.  Every row then ends in <eos>.  Needs max_len >= 3 (ValueError) and a vocabulary with an
+        atom token."""
         top_k, top_p = self._check_filters(top_k, top_p)
+        if syntax:
+            self._check_syntax(max_len)
         dev = self.device
         _require_cuda(dev, "mosesvae.VAE.sample")
         if z is None:
@@ -292,7 +301,7 @@ class VAE(_SavedState, nn.Module):
         if seed is None:
             seed = int(torch.randint(0, 2 ** 31 - 1, (1,)))
         filtered = top_k > 0 or top_p < 1.0 or return_logp
-        x, end_pads, logq, _ = self._sample_tokens(z[:n_batch], max_len, temp, seed, top_k, top_p, filtered=filtered)
+        x, end_pads, logq, _ = self._sample_tokens(z[:n_batch], max_len, temp, seed, top_k, top_p, filtered=filtered, syntax=syntax)
         xs, ends = x.cpu(), end_pads.cpu()
         if return_tokens:                                                # raw id tensors (specials included), for tests / downstream scoring
             out = [xs[b, :ends[b]] for b in range(n_batch)]
@@ -320,12 +329,61 @@ class VAE(_SavedState, nn.Module):
             p = min(p, 1.0)
         return k, p
 
+    def _check_syntax(self, max_len):
+        """syntax=True needs max_len >= 3 (<bos>, one atom, <eos>) and a vocabulary the automaton can write an atom with: ValueError
+        otherwise, before any device work (a CPU model reports it too)."""
+        if int(max_len) < 3:
+            raise ValueError(f"sample: syntax=True needs max_len >= 3 (<bos>, an atom, <eos>), got {max_len}")
+        self._smiles_table(None)
+
+    def _smiles_table(self, dev):
+        """vocab.smiles_token_table: built once per model on the host (dev None), its device copy cached in the pack."""
+        host = self.__dict__.get("_smi_tok")
+        if host is None:
+            host = self.__dict__["_smi_tok"] = smiles_token_table(self.vocabulary)
+        if dev is None:
+            return host
+        P = self._pack(dev)
+        if "smi_tok" not in P:
+            P["smi_tok"] = host.to(dev)
+        return P["smi_tok"]
+
+    _SMI_START = 0xFF << 16                  # the automaton's initial state word 0: mode START, depth 0, no previous token
+
+    @torch.no_grad()
+    def syntax_valid(self, x, bad_pos=False):
+        """Which token rows are well-formed SMILES strings ending in <eos> (the automaton of sample(syntax=True), run over finished rows by
+        mvae_smiles_syntax_check; syntax only, no chemistry).  x: padded ids [B, T] (bos first) on the device, or a list of id tensors
+        (bos first) or strings.  Returns a bool [B] device tensor; bad_pos=True also returns int32 [B]: the index of the first refused
+        token, T for a row without <eos>, -1 for a valid row."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.syntax_valid")
+        if not torch.is_tensor(x):
+            seqs = [self.string2tensor(s, device="cpu") if isinstance(s, str) else torch.as_tensor(s, dtype=torch.long) for s in x]
+            if not seqs:
+                raise ValueError("syntax_valid: needs at least one row")
+            x = torch.nn.utils.rnn.pad_sequence(seqs, batch_first=True, padding_value=self.pad)
+        if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError(f"syntax_valid: x must be [B, T], got {tuple(x.shape)}")
+        x = x.to(dev, torch.long)
+        if x.stride(1) != 1:
+            x = x.contiguous()
+        B = x.shape[0]
+        valid = torch.empty(B, dtype=torch.uint8, device=dev)
+        bad = torch.empty(B, dtype=torch.int32, device=dev) if bad_pos else None
+        ops.smiles_syntax_check(x, self._smiles_table(dev), self.eos, valid, bad)
+        return (valid.bool(), bad) if bad_pos else valid.bool()
+
     _FNV_BASIS = -3750763034362895579       # 0xcbf29ce484222325, the 64-bit FNV-1a offset basis, as an int64
 
-    def _sample_tokens(self, z, max_len, temp, seed, top_k=0, top_p=1.0, filtered=True):
+    def _sample_tokens(self, z, max_len, temp, seed, top_k=0, top_p=1.0, filtered=True, syntax=False):
         """The sampling loop without the host side: (x [B, max_len] int64 -- bos first, pad after each end --, ends [B] int64, logq [B] fp32,
         hash [B] int64: FNV-1a over x[b, 1 : end]) on the device.  top_k (0: off) / top_p (1.0: off) as _check_filters returns them.
-        filtered=False issues mvae_moses_sample_step instead (sample()'s default path) and returns None for logq and hash."""
+        filtered=False issues mvae_moses_sample_step instead (sample()'s default path) and returns None for logq and hash.  syntax=True
+        issues mvae_moses_sample_syntax_step (the filtered launch under the SMILES automaton; filtered is then implied)."""
+        if syntax:
+            self._check_syntax(max_len)
+            filtered = True                                               # logq and hash come with it
         dev = self.device
         _require_cuda(dev, "mosesvae.VAE.sample")
         P = self._pack(dev)
@@ -355,12 +413,19 @@ class VAE(_SavedState, nn.Module):
         if filtered:
             logq = torch.zeros(B, dtype=f32, device=dev)
             hsh = torch.full((B,), self._FNV_BASIS, dtype=torch.long, device=dev)
+        if syntax:
+            tok_info = self._smiles_table(dev)
+            gstate = torch.zeros((B, 2), dtype=torch.int32, device=dev)
+            gstate[:, 0] = self._SMI_START
         ops.gather_rows_tb(w.view(B, 1), tbl4, add, B, 1, V, 4 * Hd, base=zp4)      # the <bos> input rows; later ones come out of the sampling launch
         cur = 0
         for i in range(1, max_len):
             ops.rnn_fwd(L.CELL_GRU, dt, 1, B, Hd, add, 0, pd["Wih"], [pd["ldw"]] * NL, pd["Whh"], [pd["ldw"]] * NL, pd["bias"],
                         [h[1 - cur:2 - cur] for h in hbuf], ldh, None, gates, hstate, h0=[h[cur] for h in hbuf], ldh0=ldh, persist=False)
-            if filtered:
+            if syntax:
+                ops.moses_sample_syntax_step(hbuf[-1][1 - cur], ldh, P["Wfc"], self.decoder_fc.bias, temp, top_k, top_p, seed, i, self.eos, tbl4,
+                                             zp4, add, x, end_pads, eos_mask, w, B, V, Hd, tok_info, gstate, max_len, logq=logq, hash=hsh)
+            elif filtered:
                 ops.moses_sample_filtered_step(hbuf[-1][1 - cur], ldh, P["Wfc"], self.decoder_fc.bias, temp, top_k, top_p, seed, i, self.eos, tbl4,
                                                zp4, add, x, end_pads, eos_mask, w, B, V, Hd, logq=logq, hash=hsh)
             else:

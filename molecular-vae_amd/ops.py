@@ -488,6 +488,25 @@ def moses_sample_filtered_step(h_top, ldh, w_fc, bias, temp, top_k, top_p, seed,
                                                    ptr(w_out), ptr(logq), ptr(hash), stream_ptr()), "mvae_moses_sample_filtered_step")
 
 
+def moses_sample_syntax_step(h_top, ldh, w_fc, bias, temp, top_k, top_p, seed, step, eos_id, table, base, add_out, x, end_pads, eos_mask, w_out,
+                             B, V, H, tok_info, gstate, max_len, logq=None, hash=None):
+    """moses_sample_filtered_step under the SMILES syntax automaton: tok_info int32 [V] (vocab.smiles_token_table), gstate int32 [B, 2] the
+    packed state of every row (advanced by the drawn token for the rows that had not ended).  Tokens the automaton refuses, or after which
+    the string could not be finished by step max_len - 1, are masked before the softmax -- one launch (mvae_moses_sample_syntax_step)."""
+    check(L.load().mvae_moses_sample_syntax_step(dt_code(h_top.dtype), B, V, H, ptr(h_top), ldh, ptr(w_fc), w_fc.stride(0), ptr(bias), float(temp),
+                                                 int(top_k), float(top_p), int(seed) & 0xFFFFFFFF, int(step), int(eos_id), ptr(table),
+                                                 table.shape[1], ptr(base), ptr(add_out), ptr(x), x.stride(0), ptr(end_pads), ptr(eos_mask),
+                                                 ptr(w_out), ptr(logq), ptr(hash), ptr(tok_info), ptr(gstate), int(max_len), stream_ptr()),
+          "mvae_moses_sample_syntax_step")
+
+
+def smiles_syntax_check(x, tok_info, eos_id, valid, bad_pos=None):
+    """valid [B] uint8 = 1 where the token row x[b] (int64 [B, T], bos first) is a well-formed SMILES string ending in <eos>; bad_pos [B]
+    int32: the first refused index, T without <eos>, -1 when valid (mvae_smiles_syntax_check)."""
+    B, T = x.shape
+    check(L.load().mvae_smiles_syntax_check(B, T, tok_info.numel(), ptr(x), x.stride(0), ptr(tok_info), int(eos_id), ptr(valid), ptr(bad_pos),
+                                            stream_ptr()), "mvae_smiles_syntax_check")
+
 
 def moses_beam_step(state, ldh, w_fc, bias, step, eos_id, pad_id, table, base, add_out, score, fin, ends, hist_tok, hist_par, B, K, V, H):
     """One beam-search token behind the GRU step: head GEMV, log-softmax, per-beam top-K, per-molecule merge, backpointers and the next

@@ -790,7 +790,8 @@ def moses_reconstruction(model, batches, beam_width=1, max_len=100):
 
 
 @torch.no_grad()
-def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top_k=None, top_p=None, seed=0, z=None):
+def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top_k=None, top_p=None, seed=0, z=None, syntax=False,
+                   count_valid=False):
     """The reference's generation pipeline (``hugesample.py``: sample in batches, hash the strings, count unique / total) with the hashing
     and the deduplication on the device: ``n_samples`` sequences from a ``mosesvae.VAE`` in batches of ``batch_size`` (the last one shorter),
     batch j with seed ``seed + j`` and ``temp`` / ``top_k`` / ``top_p`` as ``VAE.sample`` takes them.  ``z`` None draws each batch's latents
@@ -803,11 +804,16 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     each was drawn, "logq": the log-probability of each one's first occurrence under the distribution it was drawn from (VAE.sample's
     return_logp)}.  Equality is decided by the hash alone: n distinct sequences collide with probability about n^2 / 2^65 (3e-8 at a
     million), in which case the later sequence is counted as the earlier one.  The hash is over token ids, so two sequences that differ
-    only in how they end (<eos> against the max_len cut) are distinct entries with equal strings."""
+    only in how they end (<eos> against the max_len cut) are distinct entries with equal strings.
+    ``syntax=True`` samples under the SMILES syntax automaton (``VAE.sample(syntax=True)``; needs max_len >= 3).  ``count_valid=True`` runs
+    the syntax check (``VAE.syntax_valid``) on each batch's rows on the device and adds "valid" (the number of well-formed samples,
+    duplicates included) and "valid_unique" (of distinct ones) to the result -- syntax only, no chemistry, no rdkit."""
     n_samples, batch_size, max_len = int(n_samples), int(batch_size), int(max_len)
     if n_samples < 1 or batch_size < 1 or max_len < 1:
         raise ValueError(f"moses_generate: n_samples, batch_size and max_len must be >= 1, got {n_samples}, {batch_size}, {max_len}")
     k, p = model._check_filters(top_k, top_p)
+    if syntax:
+        model._check_syntax(max_len)
     if z is not None and tuple(z.shape) != (n_samples, model.d_z):
         raise ValueError(f"moses_generate: z must be [{n_samples}, {model.d_z}], got {tuple(z.shape)}")
     dev = model.device
@@ -816,6 +822,8 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     seen_g = torch.empty(0, dtype=i64, device=dev)
     counts = torch.empty(0, dtype=i64, device=dev)             # in first-seen order
     logqs, strings = [], []
+    n_valid = torch.zeros((), dtype=i64, device=dev) if count_valid else None
+    n_valid_new = torch.zeros((), dtype=i64, device=dev) if count_valid else None
     stage = [None, None]                                        # pinned staging rows [batch_size, max_len + 1] (ids, end), alternating
     pending = None
 
@@ -828,7 +836,8 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     for j, b0 in enumerate(range(0, n_samples, batch_size)):
         n = min(batch_size, n_samples - b0)
         zb = model.sample_z_prior(n) if z is None else z[b0:b0 + n]
-        x, ends, logq, h = model._sample_tokens(zb, max_len, temp, int(seed) + j, k, p)
+        x, ends, logq, h = model._sample_tokens(zb, max_len, temp, int(seed) + j, k, p, syntax=bool(syntax))
+        ok = model.syntax_valid(x) if count_valid else None
         hs, order = torch.sort(h, stable=True)                  # equal hashes: ascending row, so a run starts at its first occurrence
         first = torch.ones(n, dtype=torch.bool, device=dev)
         first[1:] = hs[1:] != hs[:-1]
@@ -841,6 +850,9 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
             new = first & ~hit
         else:
             new = first
+        if count_valid:
+            n_valid += ok.sum()
+            n_valid_new += (ok[order] & new).sum()
         key, ord2 = torch.sort(torch.where(new, order, torch.full_like(order, n)))     # the new rows first, in first-seen order
         n_new = int(new.sum())                                   # the batch's one host wait (the copy queued last round has landed too)
         if pending is not None:
@@ -861,8 +873,11 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     torch.cuda.current_stream(dev).synchronize()
     if pending is not None:
         convert(pending)
-    return {"total": n_samples, "unique": len(strings), "strings": strings, "counts": counts.tolist(),
-            "logq": torch.cat(logqs).tolist() if logqs else []}
+    res = {"total": n_samples, "unique": len(strings), "strings": strings, "counts": counts.tolist(),
+           "logq": torch.cat(logqs).tolist() if logqs else []}
+    if count_valid:
+        res["valid"], res["valid_unique"] = int(n_valid), int(n_valid_new)
+    return res
 
 
 def active_units(mu, delta=0.01):

@@ -108,3 +108,38 @@ def get_padded_collate_fn(vocab, pin_memory=False):
             b = PaddedBatch(b.x_pad.pin_memory(), b.lengths.pin_memory())
         return b
     return collate
+
+
+# token classes of the SMILES syntax automaton (include/mvae.h, "SMILES syntax"; csrc/smiles_syntax.hpp)
+(SMI_OTHER, SMI_ATOM, SMI_TAIL, SMI_H, SMI_BOND, SMI_MINUS, SMI_PLUS, SMI_AT, SMI_DIGIT, SMI_LPAR, SMI_RPAR, SMI_LBRK, SMI_RBRK,
+ SMI_EOS) = range(14)
+_SMI_TAIL_HEAD = {"l": "C", "r": "B"}
+_SMI_CLASS = {**{ch: SMI_ATOM for ch in "BCNOPSFIbcnops"}, **{ch: SMI_BOND for ch in "=#:/\\"}, **{ch: SMI_DIGIT for ch in "0123456789"},
+              "l": SMI_TAIL, "r": SMI_TAIL, "H": SMI_H, "-": SMI_MINUS, "+": SMI_PLUS, "@": SMI_AT, "(": SMI_LPAR, ")": SMI_RPAR,
+              "[": SMI_LBRK, "]": SMI_RBRK}
+
+
+def smiles_token_table(vocab):
+    """The per-token table of the SMILES syntax automaton for a CharVocab: int32 [V], one word per id -- bits 0-7 the class (SMI_*), bits
+    8-15 for a tail ('l' of Cl, 'r' of Br) the id of its head character plus 1, bits 16-19 for a digit its value.  A tail whose head
+    character the vocabulary lacks is OTHER (never allowed), and so are '(' / ')' and '[' / ']' unless both of the pair exist; <eos> is
+    EOS, every other special and every unknown character OTHER.  ValueError when no atom token exists (nothing could be generated)."""
+    c2i = vocab.c2i
+    table = [SMI_OTHER] * len(vocab)
+    for ch, i in c2i.items():
+        cls = _SMI_CLASS.get(ch, SMI_OTHER)
+        word = cls
+        if cls == SMI_TAIL:
+            head = c2i.get(_SMI_TAIL_HEAD[ch])
+            word = SMI_OTHER if head is None else cls | (head + 1) << 8
+        elif cls == SMI_DIGIT:
+            word = cls | int(ch) << 16
+        elif cls in (SMI_LPAR, SMI_RPAR) and not ("(" in c2i and ")" in c2i):
+            word = SMI_OTHER
+        elif cls in (SMI_LBRK, SMI_RBRK) and not ("[" in c2i and "]" in c2i):
+            word = SMI_OTHER
+        table[i] = word
+    table[vocab.eos] = SMI_EOS
+    if not any(w & 0xFF == SMI_ATOM for w in table):
+        raise ValueError("smiles_token_table: the vocabulary has no atom token (one of B C N O P S F I b c n o p s)")
+    return torch.tensor(table, dtype=torch.int32)
