@@ -5,6 +5,10 @@ process per GPU under torch.distributed.run (the reference's DistributedDataPara
 here the gradient all-reduce is FusedAdam's GradSync and the data shard is ShardedSampler).
 
     python examples/train_moses.py --smi data/moses_train.smi --epochs 2 -b 128
+    python examples/train_moses.py --smi data/moses_train.smi --epochs 2 -b 1024 --device-data --bucket 8
+
+--device-data keeps the tokenised corpus in HBM and collates every batch in one launch (data.MosesDeviceDataset: the same batches, no host
+work in the step); --bucket K additionally groups rows of similar length within windows of K batches, which shortens the batches' T.
 """
 import argparse
 import os
@@ -29,8 +33,12 @@ ap.add_argument("--out_dir", default=".")
 ap.add_argument("--word-dropout", default=0.0, type=float, help="probability that a decoder input token becomes <unk> (0 = off)")
 ap.add_argument("--free-bits", default=0.0, type=float, help="nats per latent dimension that cost no KL (0 = off)")
 ap.add_argument("--kl-cycle", default=0, type=int, help="cyclical KL weight with cycles of this many epochs (0: the linear KLAnnealer)")
+ap.add_argument("--device-data", action="store_true", help="feed from a device-resident corpus (data.MosesDeviceDataset) instead of the DataLoader")
+ap.add_argument("--bucket", default=0, type=int, help="with --device-data: group rows of similar length within windows of this many batches (0 = off)")
 ap.add_argument("--report", default=None, help="write a JSON summary (the per-epoch postfix dictionaries + samples) here")
 args = ap.parse_args()
+if args.bucket and not args.device_data:
+    ap.error("--bucket needs --device-data")
 
 rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
 torch.cuda.set_device(args.local_rank)
@@ -48,6 +56,7 @@ vocab = VC.OneHotVocab.from_data(smiles)                 # moses_train_distrib.p
 collate = VC.get_padded_collate_fn(vocab, pin_memory=True)
 sampler = mv.ShardedSampler(len(smiles), rank=rank, world=world, seed=0)
 loader = torch.utils.data.DataLoader(smiles, batch_size=args.batch_size, sampler=sampler, collate_fn=collate, drop_last=True)
+device_data = D.MosesDeviceDataset(smiles, vocab, device=dev) if args.device_data else None
 
 torch.manual_seed(42)
 model = MV.VAE(vocab).to(dev)
@@ -61,7 +70,11 @@ report = dict(vocab=len(vocab), n=len(smiles), epochs=[], samples=[])
 for epoch in range(args.epochs):
     sampler.set_epoch(epoch)
     kl_weight = kl_annealer(epoch)
-    post = mv.moses_train_epoch(model, epoch, (b.to(dev) for b in loader), kl_weight, optimizer, log_every=100 if rank == 0 else 0)
+    if device_data is not None:                          # the same shard of the same permutation as the sampler's (seed 0 + epoch)
+        batches = device_data.batches(args.batch_size, epoch=epoch, seed=0, rank=rank, world=world, bucket=args.bucket)
+    else:
+        batches = (b.to(dev) for b in loader)
+    post = mv.moses_train_epoch(model, epoch, batches, kl_weight, optimizer, log_every=100 if rank == 0 else 0)
     if rank == 0:                                        # :342-353
         print(post, flush=True)
         report["epochs"].append(post)

@@ -444,6 +444,22 @@ int mvae_bce_kl_logits_bwd(int dtype, int B, int L, int C, const float* logits, 
  */
 int mvae_expand_indices(const uint8_t* store, const int64_t* rows, int B, int L, int C, int64_t* idx, float* ohe, void* stream);
 
+/* The MOSES counterpart: the tokenised corpus lives in HBM in CSR form -- tokens uint8 [total] (ids without specials) and offsets int64
+ * [N + 1] -- and ONE launch is the reference's collate (moses_train_distrib.py:127-135: sorted(data, key=len, reverse=True), which is
+ * stable, then <bos> + ids + <eos>) followed by pad_sequence: batch member i is corpus row rows[i] (int64 [B], any order, repeats allowed),
+ * its output row is rank_i = #{j : len_j > len_i} + #{j < i : len_j == len_i}, and
+ *   x_pad [B, x_ld] int64: row rank_i = bos, the row's tokens, eos, then pad up to column T - 1 (columns T .. x_ld - 1 are not touched);
+ *   lengths [B] int32: lengths[rank_i] = len_i + 2 -- descending, the precondition of every recurrent kernel here (mvae_rnn_*_desc.lengths);
+ *   rows_sorted [B] int64 (optional): rows_sorted[rank_i] = rows[i], the corpus row behind each batch row;
+ *   err [1] int32 (optional, the caller zeroes it): raised with atomicMax to 1 by a row with len + 2 > T -- only its first T columns are
+ *     written and its length is reported as T -- and to 2 by a row id outside [0, N), which is collated as an empty row (bos, eos).
+ * Nothing is ever written outside x_pad[:, :T], lengths[0..B) and rows_sorted[0..B); offsets must be a non-decreasing CSR index into tokens.
+ * Any B >= 1 in one launch with no dependency between blocks.  Refused before anything is enqueued (MVAE_ERR_INVALID): a null tokens /
+ * offsets / rows / x_pad / lengths, B < 1, T < 2, N < 1, x_ld < T, or bos / eos / pad outside [0, 65535].
+ */
+int mvae_moses_collate(const uint8_t* tokens, const int64_t* offsets, const int64_t* rows, int B, int T, int64_t N, int bos, int eos, int pad,
+                       int64_t* x_pad, int64_t x_ld, int32_t* lengths, int64_t* rows_sorted, int32_t* err, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * MOSES GRU path (mosesvae.py:126-199).
  *   mvae_moses_latent_*: z = mu + exp(logvar/2)*eps and kl = 0.5*mean_b sum_j(exp(logvar) + mu^2 - 1 - logvar)  (mosesvae.py:158-162);

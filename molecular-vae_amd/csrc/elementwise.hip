@@ -1456,6 +1456,60 @@ __global__ __launch_bounds__(256) void expand_indices_kernel(const uint8_t* stor
   }
 }
 
+// The MOSES feed: the tokenised corpus lives in HBM in CSR form (uint8 tokens without specials, int64 offsets [N + 1]); rows[i] names the
+// corpus row of batch member i.  One launch does what get_padded_collate_fn does on the host (moses_train_distrib.py:127-135 + pad_sequence):
+// sorted(data, key=len, reverse=True) -- stable -- then <bos> tokens <eos> and pad up to T.  One wave per batch member: it counts its rank
+// rank_i = #{j : len_j > len_i} + #{j < i : len_j == len_i} over all B lengths (staged through LDS 1024 at a time, so a block reads rows /
+// offsets once, coalesced), which is a permutation of [0, B) -- no two waves write the same row, no block waits for another -- and writes
+// the T columns of output row rank_i.  A row id outside [0, N) counts as an empty row (err := 2); a row longer than T - 2 is cut at T
+// columns (err := 1) and reports length T.
+__device__ __forceinline__ long collate_row_len(const int64_t* offsets, const int64_t* rows, int j, long N) {
+  const long r = rows[j];
+  if (r < 0 || r >= N) return 0;
+  const long n = offsets[r + 1] - offsets[r];
+  return n > 0 ? n : 0;
+}
+__global__ __launch_bounds__(256) void moses_collate_kernel(const uint8_t* tokens, const int64_t* offsets, const int64_t* rows, int B, int T, long N,
+                                                            int bos, int eos, int pad, int64_t* x_pad, long x_ld, int32_t* lengths,
+                                                            int64_t* rows_sorted, int32_t* err) {
+  __shared__ long len_s[1024];
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const bool live = i < B;                                      // a dead wave of the last block still helps to stage the lengths
+  const long li = live ? collate_row_len(offsets, rows, i, N) : 0;
+  int rank = 0;
+  for (int j0 = 0; j0 < B; j0 += 1024) {
+    const int n = B - j0 < 1024 ? B - j0 : 1024;
+    __syncthreads();
+    for (int j = threadIdx.x; j < n; j += 256) len_s[j] = collate_row_len(offsets, rows, j0 + j, N);
+    __syncthreads();
+    for (int j = lane; j < n; j += 64) {
+      const long lj = len_s[j];
+      rank += (lj > li || (lj == li && j0 + j < i)) ? 1 : 0;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) rank += __shfl_xor(rank, o, 64);
+  if (!live) return;
+  const long ri = rows[i];
+  const bool bad = ri < 0 || ri >= N;
+  const long base = bad ? 0 : offsets[ri];
+  const bool cut = li + 2 > (long)T;
+  if (lane == 0) {
+    lengths[rank] = cut ? T : (int)(li + 2);
+    if (rows_sorted) rows_sorted[rank] = ri;
+    if (err && (bad || cut)) atomicMax(err, bad ? 2 : 1);
+  }
+  int64_t* out = x_pad + (long)rank * x_ld;
+  for (int t = lane; t < T; t += 64) {
+    const long k = t - 1;                                       // position inside the source row
+    int v = pad;
+    if (t == 0) v = bos;
+    else if (k < li) v = tokens[base + k];
+    else if (k == li) v = eos;
+    out[t] = v;
+  }
+}
+
 // ------------------------------------------------------------------------------------------- MOSES path (mosesvae.py)
 __global__ __launch_bounds__(256) void relu_bwd_kernel(long n, float* dy, const float* y) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) dy[i] = y[i] > 0.f ? dy[i] : 0.f;
@@ -1871,6 +1925,15 @@ int mvae_colsum(int M, int N, const float* X, int64_t ldx, float* out, void* ws,
 int mvae_expand_indices(const uint8_t* store, const int64_t* rows, int B, int L, int C, int64_t* idx, float* ohe, void* stream) {
   if (!store || !rows || !idx || B < 1 || L < 1 || C < 1) return MVAE_ERR_INVALID;
   hipLaunchKernelGGL(expand_indices_kernel, dim3(grid_for((long)B * L)), dim3(256), 0, (hipStream_t)stream, store, rows, B, L, C, idx, ohe);
+  MVAE_CHECK_HIP(hipGetLastError());
+  return MVAE_OK;
+}
+int mvae_moses_collate(const uint8_t* tokens, const int64_t* offsets, const int64_t* rows, int B, int T, int64_t N, int bos, int eos, int pad,
+                       int64_t* x_pad, int64_t x_ld, int32_t* lengths, int64_t* rows_sorted, int32_t* err, void* stream) {
+  if (!tokens || !offsets || !rows || !x_pad || !lengths || B < 1 || T < 2 || N < 1 || x_ld < T) return MVAE_ERR_INVALID;
+  if (bos < 0 || bos > 65535 || eos < 0 || eos > 65535 || pad < 0 || pad > 65535) return MVAE_ERR_INVALID;
+  hipLaunchKernelGGL(moses_collate_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, tokens, offsets, rows, B, T, (long)N, bos, eos, pad,
+                     x_pad, (long)x_ld, lengths, rows_sorted, err);
   MVAE_CHECK_HIP(hipGetLastError());
   return MVAE_OK;
 }

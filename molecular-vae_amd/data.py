@@ -7,6 +7,10 @@
   * ``encode_smiles``   -- whole-corpus vectorised encoding to uint8 ``[N, L]`` (120 B / molecule; 250k ZINC = 30 MB).
   * ``DeviceDataset``   -- the encoded corpus resident in HBM; per-epoch shuffled, rank-sharded batches expanded on device
                            (``mvae_expand_indices``) to the same ``(idx, ohe)`` pair -- no host work in the step.
+  * ``tokenize_corpus`` -- the MOSES corpus as CSR (uint8 tokens without specials + int64 offsets) through a 256-entry byte table.
+  * ``moses_epoch_plan`` / ``MosesDeviceDataset`` -- that corpus resident in HBM; every batch is ONE launch (``mvae_moses_collate``) that
+                           yields the ``PaddedBatch`` ``mosesvae.VAE.forward`` takes: the stable length-descending collate of
+                           ``vocab.get_padded_collate_fn`` without its per-string host work.  Opt-in length bucketing.
   * ``load_smiles`` / ``save_encoded`` / ``load_encoded`` -- ``.smi``/CSV in, ``.npz`` (indices + charset + max_len) out.
 """
 import numpy as np
@@ -90,6 +94,180 @@ class DeviceDataset:
             ohe = torch.empty(B, self.L, self.C, dtype=torch.float32, device=self.device) if want_onehot else None
             ops.expand_indices(self.store, rows, idx, ohe, B, self.L, self.C)
             yield idx, ohe
+
+
+def tokenize_corpus(smiles, vocab):
+    """A list of strings -> (tokens uint8 [total], offsets int64 [N + 1]): ``vocab.string2ids`` of every string, without specials, back to
+    back.  Vectorised: the joined strings go through a 256-entry table built from ``vocab.c2i`` (a character the vocabulary lacks gets what
+    ``CharVocab.char2id`` gives it, <unk>).  Empty strings are legal.  ValueError: more than 256 ids, or a character of the vocabulary or of
+    the corpus that is not one byte in latin-1."""
+    if len(vocab) > 256:
+        raise ValueError(f"tokenize_corpus: {len(vocab)} ids do not fit uint8")
+    table = np.full(256, vocab.unk, dtype=np.uint8)
+    for ch, i in vocab.c2i.items():
+        if len(ch) != 1:
+            continue                                          # the specials: never part of a string
+        if ord(ch) > 255:
+            raise ValueError(f"tokenize_corpus: vocabulary character {ch!r} is not a single latin-1 byte")
+        table[ord(ch)] = i
+    smiles = list(smiles)
+    offsets = np.zeros(len(smiles) + 1, dtype=np.int64)
+    if smiles:
+        np.cumsum(np.fromiter(map(len, smiles), dtype=np.int64, count=len(smiles)), out=offsets[1:])
+    try:
+        raw = "".join(smiles).encode("latin-1")
+    except UnicodeEncodeError as e:
+        raise ValueError(f"tokenize_corpus: corpus character {e.object[e.start]!r} is not a single latin-1 byte") from None
+    return table[np.frombuffer(raw, dtype=np.uint8)], offsets
+
+
+def moses_epoch_plan(lengths, batch_size, epoch=0, seed=0, shuffle=True, rank=0, world=1, drop_last=True, bucket=0):
+    """One epoch of ``MosesDeviceDataset.batches`` for one rank, on the host: (order, cuts) -- ``order`` int64 ndarray, the corpus rows
+    of this rank's batches back to back, and ``cuts`` a list of (lo, hi, T): batch i is ``order[lo:hi]`` and T its longest row + 2.
+    `lengths`: the corpus' row lengths without specials.
+
+    bucket = 0: the batches of ``DataLoader(sampler=ShardedSampler(n, rank, world, seed), batch_size, drop_last)`` at that epoch -- this
+      rank's contiguous shard of ``torch.randperm(n, generator=manual_seed(seed + epoch))`` (``arange`` without shuffle) in chunks.
+    bucket = k > 0: the global order is cut into windows of k * world batches; each window's rows are sorted by length (stable, descending)
+      and cut into batches; the `world` consecutive batches of a window form one step (rank r takes the r-th: neighbouring lengths, so the
+      ranks' T are balanced); the steps are then shuffled with the same generator, so length is not monotone in time.  Every rank has the
+      same number of batches; the rows that do not fill a last global step are dropped (world == 1 and drop_last=False: kept as a short
+      batch)."""
+    lengths = np.asarray(lengths)
+    n = int(lengths.shape[0])
+    for name, v in (("batch_size", batch_size), ("world", world)):
+        if int(v) != v or v < 1:
+            raise ValueError(f"{name} must be a positive integer, got {v!r}")
+    for name, v in (("bucket", bucket), ("epoch", epoch), ("seed", seed)):
+        if int(v) != v or v < 0:
+            raise ValueError(f"{name} must be a non-negative integer, got {v!r}")
+    if int(rank) != rank or not 0 <= rank < world:
+        raise ValueError(f"rank {rank!r} outside [0, {world})")
+    if not drop_last and world != 1:
+        raise ValueError("drop_last=False would give the ranks different batch counts: world == 1 only")
+    B, world, rank, bucket = int(batch_size), int(world), int(rank), int(bucket)
+    g = torch.Generator(); g.manual_seed(int(seed) + int(epoch))
+    perm = (torch.randperm(n, generator=g) if shuffle else torch.arange(n)).numpy()
+    if bucket == 0:
+        per = n // world
+        stop = per - per % B if drop_last else per
+        order = perm[rank * per:rank * per + stop]
+        bounds = [(lo, min(lo + B, stop)) for lo in range(0, stop, B)]
+    else:
+        G = B * world                                         # rows of one global step
+        steps = n // G if drop_last else -(-n // G)
+        perm = perm[:min(n, steps * G)]
+        win = bucket * G
+        mine = []
+        for w0 in range(0, perm.shape[0], win):
+            rows = perm[w0:w0 + win]
+            rows = rows[np.argsort(-lengths[rows].astype(np.int64), kind="stable")]
+            for s0 in range(0, rows.shape[0], G):
+                mine.append(rows[s0 + rank * B:s0 + (rank + 1) * B])
+        if shuffle:
+            mine = [mine[i] for i in torch.randperm(len(mine), generator=g).tolist()]
+        order = np.concatenate(mine) if mine else perm[:0]
+        ends = np.cumsum([m.shape[0] for m in mine]).tolist()
+        bounds = list(zip([0] + ends[:-1], ends))
+    order = np.ascontiguousarray(order, dtype=np.int64)
+    if bounds:
+        starts = np.array([lo for lo, _ in bounds])
+        tmax = np.maximum.reduceat(lengths[order].astype(np.int64), starts)
+    else:
+        tmax = []
+    return order, [(lo, hi, int(t) + 2) for (lo, hi), t in zip(bounds, tmax)]
+
+
+class MosesDeviceDataset:
+    """The tokenised MOSES corpus in HBM (CSR: uint8 tokens, int64 offsets) and its batches as device ``PaddedBatch``es, one
+    ``mvae_moses_collate`` launch each: what ``DataLoader(smiles, sampler=ShardedSampler, collate_fn=get_padded_collate_fn(vocab))``
+    feeds ``mosesvae.VAE``, without host work in the step.  The row lengths stay on the host as well (``lengths``, int32, without
+    specials), so a batch's T is known without asking the device.
+
+    ``gather`` / ``batches`` never wait for the device; ``err`` (int32 [1], device) is raised by a launch whose T was too small (1) or
+    that met a row id outside the corpus (2) -- ``check_errors()`` reads it.  The batches of ``batches()`` cannot raise it."""
+
+    def __init__(self, smiles_or_encoded, vocab, device="cuda"):
+        enc = smiles_or_encoded
+        if isinstance(enc, tuple) and len(enc) == 2 and not isinstance(enc[0], str):
+            tokens, offsets = np.asarray(enc[0]), np.asarray(enc[1])
+            if tokens.dtype != np.uint8 or tokens.ndim != 1 or offsets.ndim != 1 or offsets.shape[0] < 1:
+                raise ValueError("MosesDeviceDataset: (tokens uint8 [total], offsets int64 [N + 1]) expected")
+            offsets = offsets.astype(np.int64)
+            if offsets[0] != 0 or offsets[-1] != tokens.shape[0] or (np.diff(offsets) < 0).any():
+                raise ValueError("MosesDeviceDataset: offsets must rise from 0 to len(tokens)")
+            if tokens.size and int(tokens.max()) >= len(vocab):
+                raise ValueError("MosesDeviceDataset: token id outside the vocabulary")
+        else:
+            tokens, offsets = tokenize_corpus(enc, vocab)
+        if offsets.shape[0] < 2:
+            raise ValueError("MosesDeviceDataset: empty corpus")
+        for name in ("bos", "eos", "pad"):
+            if not 0 <= getattr(vocab, name) <= 65535:
+                raise ValueError(f"MosesDeviceDataset: vocab.{name} outside [0, 65535]")
+        self.vocab, self.n = vocab, int(offsets.shape[0] - 1)
+        self.lengths = np.diff(offsets).astype(np.int32)
+        self.max_len = int(self.lengths.max())
+        self.device = torch.device(device)
+        # one spare byte, so that a corpus of empty strings still has a tokens pointer
+        self.tokens = torch.from_numpy(np.concatenate([tokens, np.zeros(1, np.uint8)])).to(self.device)
+        self.offsets = torch.from_numpy(np.ascontiguousarray(offsets)).to(self.device)
+        self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def __len__(self):
+        return self.n
+
+    def _collate(self, rows, T):
+        from . import ops
+        from .vocab import PaddedBatch
+        B, v = rows.numel(), self.vocab
+        x_pad = torch.empty(B, T, dtype=torch.long, device=self.device)
+        lengths = torch.empty(B, dtype=torch.int32, device=self.device)
+        rows_sorted = torch.empty(B, dtype=torch.long, device=self.device)
+        ops.moses_collate(self.tokens, self.offsets, rows, x_pad, lengths, T, self.n, v.bos, v.eos, v.pad, rows_sorted, self.err)
+        return PaddedBatch(x_pad, lengths, rows=rows_sorted)
+
+    def gather(self, rows, T=None):
+        """Corpus rows (a list, an ndarray or a tensor; any order, repeats allowed) -> PaddedBatch of T columns, its rows in the collate's
+        stable length-descending order and ``.rows`` the corpus row behind each.  T=None: the longest of the rows + 2 when `rows` is on the
+        host, else the corpus' longest + 2 (no device round trip)."""
+        if torch.is_tensor(rows) and rows.is_cuda:
+            rows_d = rows.to(self.device, torch.long).contiguous().view(-1)
+            T = self.max_len + 2 if T is None else T
+        else:
+            host = np.asarray(rows.cpu() if torch.is_tensor(rows) else rows)
+            if host.size and not np.issubdtype(host.dtype, np.integer):
+                raise ValueError("gather: integer row ids expected")
+            host = host.astype(np.int64).reshape(-1)
+            if host.size and (host.min() < 0 or host.max() >= self.n):
+                raise ValueError(f"gather: row id outside [0, {self.n})")
+            if T is None and host.size:
+                T = int(self.lengths[host].max()) + 2
+            rows_d = torch.from_numpy(host).to(self.device)
+        if rows_d.numel() < 1:
+            raise ValueError("gather: no rows")
+        if int(T) != T or T < 2:
+            raise ValueError(f"gather: T must be an integer >= 2, got {T!r}")
+        return self._collate(rows_d, int(T))
+
+    def check_errors(self):
+        """Waits for the device; raises when a launch since the last call cut a row (T too small) or met a row id outside the corpus."""
+        e = int(self.err.item())
+        self.err.zero_()
+        if e:
+            raise RuntimeError("mvae_moses_collate: " + ("a row id outside the corpus" if e == 2 else "a row longer than T - 2 was cut"))
+
+    def batches(self, batch_size, epoch=0, seed=0, shuffle=True, rank=0, world=1, drop_last=True, bucket=0):
+        """Generator of this rank's device PaddedBatches of one epoch (``moses_epoch_plan``): one host plan and one upload of the order per
+        epoch, then a slice and one launch per batch.  bucket=0 gives exactly the batches of the DataLoader + ShardedSampler +
+        get_padded_collate_fn feed; bucket=k groups rows of similar length within windows of k batches per rank (other batches, smaller T)."""
+        order, cuts = moses_epoch_plan(self.lengths, batch_size, epoch, seed, shuffle, rank, world, drop_last, bucket)
+        return self._run_plan(order, cuts)
+
+    def _run_plan(self, order, cuts):
+        order_d = torch.from_numpy(order).to(self.device)
+        for lo, hi, T in cuts:
+            yield self._collate(order_d[lo:hi], T)
 
 
 def synthetic_smiles(n, seed=0, lo=20, hi=60, structured=True):

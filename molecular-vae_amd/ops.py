@@ -456,6 +456,13 @@ def expand_indices(store, rows, idx, ohe, B, Lq, C_):
     check(L.load().mvae_expand_indices(ptr(store), ptr(rows), B, Lq, C_, ptr(idx), ptr(ohe), stream_ptr()), "mvae_expand_indices")
 
 
+def moses_collate(tokens, offsets, rows, x_pad, lengths, T, N, bos, eos, pad, rows_sorted=None, err=None):
+    """The MOSES collate in one launch (include/mvae.h): corpus rows `rows` (int64 [B]) of the CSR corpus (tokens uint8, offsets int64
+    [N + 1]) -> x_pad[:, :T] int64 (stable length-descending order, bos / eos / pad) and lengths int32 [B]; rows_sorted / err optional."""
+    check(L.load().mvae_moses_collate(ptr(tokens), ptr(offsets), ptr(rows), rows.numel(), T, N, bos, eos, pad, ptr(x_pad), x_pad.stride(0),
+                                      ptr(lengths), ptr(rows_sorted), ptr(err), stream_ptr()), "mvae_moses_collate")
+
+
 def relu_bwd(dy, y):
     check(L.load().mvae_relu_bwd(dy.numel(), ptr(dy), ptr(y), stream_ptr()), "mvae_relu_bwd")
 

@@ -73,16 +73,18 @@ def get_collate_fn(vocab):
 class PaddedBatch:
     """A collated batch already in the layout the kernels read: ``x_pad`` int64 [B, T] (pad-filled, rows sorted by length descending)
     and ``lengths`` int32 [B], both on the target device.  ``mosesvae.VAE.forward`` takes it in place of the list of per-sequence
-    tensors: ONE host->device transfer per batch instead of the reference's one ``.cuda()`` per sequence (moses_train_distrib.py:271)."""
+    tensors: ONE host->device transfer per batch instead of the reference's one ``.cuda()`` per sequence (moses_train_distrib.py:271).
+    ``rows`` (optional, int64 [B]): the corpus row behind each batch row, where the batch came from a corpus (data.MosesDeviceDataset)."""
 
-    def __init__(self, x_pad, lengths):
-        self.x_pad, self.lengths = x_pad, lengths
+    def __init__(self, x_pad, lengths, rows=None):
+        self.x_pad, self.lengths, self.rows = x_pad, lengths, rows
 
     def __len__(self):
         return self.x_pad.shape[0]
 
     def to(self, device, non_blocking=True):
-        return PaddedBatch(self.x_pad.to(device, non_blocking=non_blocking), self.lengths.to(device, non_blocking=non_blocking))
+        return PaddedBatch(self.x_pad.to(device, non_blocking=non_blocking), self.lengths.to(device, non_blocking=non_blocking),
+                           rows=None if self.rows is None else self.rows.to(device, non_blocking=non_blocking))
 
     def tensors(self):
         """The reference's representation (list of LongTensors) -- for code that still wants it."""
