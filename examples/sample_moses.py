@@ -7,8 +7,10 @@ writes them (without them: a seeded random model over a synthetic corpus' vocabu
 ``valid`` needs rdkit (``Chem.MolFromSmiles``); without it the column is left empty.  ``syntax_valid`` needs nothing: it is the number of
 samples (duplicates included) that are well-formed SMILES strings -- balanced branches, closed rings and brackets, no dangling bond;
 syntax, not chemistry -- counted on the device.  ``--syntax`` samples under that grammar, so that every sample is well-formed.
+``--novel_against FILE`` loads the training strings (one per line) into a ``data.MosesDeviceDataset`` and counts ``novel``: the distinct
+samples whose token row equals no row of that corpus, looked up on the device in its exact index (no set of strings on the host).
 
-    python examples/sample_moses.py --ckpt trained_save.pt --vocab vocab.pkl --rounds 10 --top_p 0.95 --syntax
+    python examples/sample_moses.py --ckpt trained_save.pt --vocab vocab.pkl --rounds 10 --top_p 0.95 --syntax --novel_against train.smi
 """
 import argparse
 import os
@@ -36,7 +38,9 @@ ap.add_argument("--syntax", action="store_true", help="constrain every step to t
 ap.add_argument("--prior", default="normal", choices=["normal", "zeros"], help="zeros = sample_z_prior as the reference is written")
 ap.add_argument("--seed", default=0, type=int)
 ap.add_argument("--log", default="log_small.csv")
-ap.add_argument("--out", default=None, help="write the unique strings with their counts here (tab separated)")
+ap.add_argument("--novel_against", default=None, metavar="FILE", help="training strings, one per line: count the unique samples not among them")
+ap.add_argument("--out", default=None, help="write the unique strings with their counts (and, with --novel_against, 1 for novel / 0) here, "
+                                            "tab separated")
 args = ap.parse_args()
 
 try:
@@ -58,6 +62,7 @@ if args.ckpt:
 model = model.to(dev).eval()
 model.prior = args.prior
 model.seed_noise(args.seed)
+corpus = mv.MosesDeviceDataset(D.load_smiles(args.novel_against), vocab, device=dev) if args.novel_against else None
 
 
 def is_valid(s):
@@ -68,27 +73,33 @@ def is_valid(s):
 
 
 seen, total, valid, syntax_valid = {}, 0, 0, 0
+novel = set()                                             # the unique strings that are not in the corpus
 per_round = args.batch_size * args.batches_per_round
 start = time.time()
 with open(args.log, "w", buffering=1) as f:
-    f.write("time,unique,valid,total,syntax_valid\n")
+    f.write("time,unique,valid,total,syntax_valid" + (",novel\n" if corpus is not None else "\n"))
     for r in range(args.rounds):
         res = mv.moses_generate(model, per_round, batch_size=args.batch_size, max_len=args.max_len, temp=args.temp, top_k=args.top_k,
-                                top_p=args.top_p, seed=args.seed + r * args.batches_per_round, syntax=args.syntax, count_valid=True)
+                                top_p=args.top_p, seed=args.seed + r * args.batches_per_round, syntax=args.syntax, count_valid=True,
+                                novel_against=corpus)
         total += res["total"]
         syntax_valid += res["valid"]
-        for s, c in zip(res["strings"], res["counts"]):
+        for i, (s, c) in enumerate(zip(res["strings"], res["counts"])):
             if s not in seen:
                 seen[s] = 0
+                if corpus is not None and res["is_novel"][i]:
+                    novel.add(s)
                 if Chem is not None and is_valid(s):
                     valid += 1
             seen[s] += c
         now = time.time()
-        f.write("{0},{1},{2},{3},{4}\n".format(now, len(seen), valid if Chem is not None else "", total, syntax_valid))
+        f.write("{0},{1},{2},{3},{4}".format(now, len(seen), valid if Chem is not None else "", total, syntax_valid)
+                + (f",{len(novel)}\n" if corpus is not None else "\n"))
         print(f"round {r}: unique {len(seen)} ({len(seen) / total:.3f}), sampled {total}, samples per second {total / (now - start):.0f}, "
               f"unique per second {len(seen) / (now - start):.0f}, well-formed {syntax_valid} ({syntax_valid / total:.3f})"
-              + (f", valid unique {valid}" if Chem is not None else ""), flush=True)
+              + (f", valid unique {valid}" if Chem is not None else "")
+              + (f", novel {len(novel)} ({len(novel) / len(seen):.3f} of unique)" if corpus is not None else ""), flush=True)
 if args.out:
     with open(args.out, "w") as f:
         for s, c in sorted(seen.items(), key=lambda kv: -kv[1]):
-            f.write(f"{s}\t{c}\n")
+            f.write(f"{s}\t{c}" + (f"\t{int(s in novel)}\n" if corpus is not None else "\n"))

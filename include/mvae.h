@@ -460,6 +460,34 @@ int mvae_expand_indices(const uint8_t* store, const int64_t* rows, int B, int L,
 int mvae_moses_collate(const uint8_t* tokens, const int64_t* offsets, const int64_t* rows, int B, int T, int64_t N, int bos, int eos, int pad,
                        int64_t* x_pad, int64_t x_ld, int32_t* lengths, int64_t* rows_sorted, int32_t* err, void* stream);
 
+/* An exact index of that corpus: which corpus row, if any, has exactly the tokens of a sampled row (the "novel" of valid / unique / novel).
+ * Corpus row r is the byte string tokens[offsets[r] : offsets[r + 1]] of the CSR above; empty rows are legal.  The index is an
+ * open-addressing hash table with linear probing: slots int64 [n_slots], allocated by the caller, n_slots a power of two greater than N,
+ * so at least one slot is always empty and every probe sequence ends.  What the slots hold is opaque: only these two entries read them.
+ * mvae_corpus_index_build: fills the table in one launch.  It sets every slot to empty itself (the caller need not clear anything) and
+ *   zeroes n_distinct.  Every row is hashed over its token values and walks forward from its home slot: an empty slot is claimed by a
+ *   compare-and-swap; at an occupied one the row is compared, byte for byte, with the occupant's, equal content leaves the lower row id
+ *   in the slot (an atomic min), anything else moves on.  No thread waits for another and a walk takes at most n_slots steps.  Afterwards
+ *   every distinct content owns exactly one slot, which names the LOWEST corpus row with that content, and n_distinct[0] (optional) is the
+ *   number of distinct rows.  Which slot a content owns may depend on the order of execution; what mvae_corpus_index_probe and n_distinct
+ *   return does not.  Building again into the same slots gives an equivalent table.
+ * mvae_corpus_index_probe: one launch for a batch x [B, x_ld] int64 of token rows with <bos> in column 0 (x_ld >= T).  The content of row
+ *   b is x[b, 1:] up to, and not including, the first column that holds `eos`; without one it runs to column T - 1 (a sample cut at
+ *   max_len is compared by the tokens it has).  Nothing at or behind the <eos> takes part: whatever stands there -- ids outside the
+ *   vocabulary, another row's tokens -- the answer is the same, and no column >= T is ever loaded.  match[b] = the lowest corpus row whose
+ *   tokens equal that content, or -1.  A hash decides where to look and a 24-bit tag lets most foreign slots be passed unread, but a hit
+ *   is always confirmed on the bytes: there are no false matches.  An id outside [0, 255] inside the content can equal no corpus token:
+ *   the row gets -1 and the id is never used as an index.  T = 1, or `eos` in column 1, is the empty content and matches the lowest
+ *   empty corpus row if there is one.  The walk is bounded by n_slots steps and checks every row id it finds against N, so a launch on
+ *   slots that no build filled ends too, with meaningless answers.
+ * Both refuse, before anything is enqueued (MVAE_ERR_INVALID): a null tokens / offsets / slots (/ x / match), N < 1 or N >= 2^40, n_slots
+ * not a power of two or not greater than N; the probe also B < 1, T < 1, x_ld < T, eos outside [0, 65535].
+ */
+int mvae_corpus_index_build(const uint8_t* tokens, const int64_t* offsets, int64_t N, int64_t* slots, int64_t n_slots,
+                            int64_t* n_distinct /* [1] or NULL */, void* stream);
+int mvae_corpus_index_probe(const uint8_t* tokens, const int64_t* offsets, int64_t N, const int64_t* slots, int64_t n_slots, int B, int T,
+                            const int64_t* x, int64_t x_ld, int eos, int64_t* match /* [B] */, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * MOSES GRU path (mosesvae.py:126-199).
  *   mvae_moses_latent_*: z = mu + exp(logvar/2)*eps and kl = 0.5*mean_b sum_j(exp(logvar) + mu^2 - 1 - logvar)  (mosesvae.py:158-162);

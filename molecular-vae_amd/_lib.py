@@ -144,6 +144,8 @@ SIGNATURES = {
     "mvae_bce_kl_logits_bwd": (_i, [_i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _vp, _f, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "mvae_expand_indices": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "mvae_moses_collate": (_i, [_vp, _vp, _vp, _i, _i, _i64, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "mvae_corpus_index_build": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "mvae_corpus_index_probe": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _vp, _i64, _i, _vp, _vp]),
     "mvae_moses_latent_workspace": (_sz, [_i]),
     "mvae_moses_latent_fwd": (_i, [_i, _i, _vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mvae_moses_latent_bwd": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -103,4 +103,13 @@ int mvae_rnn_bwd(const mvae_rnn_bwd_desc* d, void* stream, const void** status_o
 size_t mvae_rnn_bwd_persist_workspace(const mvae_rnn_bwd_desc* d) { return (d && rnn_persist_bwd_supported(d)) ? rnn_persist_bwd_workspace_bytes(d->T) : 0; }
 size_t mvae_rnn_bwd_workspace(const mvae_rnn_bwd_desc* d) { return rnn_bwd_workspace_bytes(d); }
 
+int mvae_corpus_index_build(const uint8_t* tokens, const int64_t* offsets, int64_t N, int64_t* slots, int64_t n_slots, int64_t* n_distinct,
+                            void* stream) {
+  return launch_corpus_index_build(tokens, offsets, N, slots, n_slots, n_distinct, (hipStream_t)stream);
+}
+int mvae_corpus_index_probe(const uint8_t* tokens, const int64_t* offsets, int64_t N, const int64_t* slots, int64_t n_slots, int B, int T,
+                            const int64_t* x, int64_t x_ld, int eos, int64_t* match, void* stream) {
+  return launch_corpus_index_probe(tokens, offsets, N, slots, n_slots, B, T, x, x_ld, eos, match, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -28,6 +28,11 @@ int launch_cast_transpose(int dsrc, int ddst, int R, int C, const void* src, lon
 size_t colsum_workspace_bytes(int M, int N);
 int launch_colsum(int M, int N, const float* X, long ldx, float* out, void* ws, size_t ws_bytes, hipStream_t st);
 int launch_selu_bwd(long n, float* dy, const float* y, hipStream_t st);
+// corpus_index.hip: the exact hash index over the CSR corpus (both check their arguments before anything is enqueued)
+int launch_corpus_index_build(const uint8_t* tokens, const int64_t* offsets, int64_t N, int64_t* slots, int64_t n_slots, int64_t* n_distinct,
+                              hipStream_t st);
+int launch_corpus_index_probe(const uint8_t* tokens, const int64_t* offsets, int64_t N, const int64_t* slots, int64_t n_slots, int B, int T,
+                              const int64_t* x, int64_t x_ld, int eos, int64_t* match, hipStream_t st);
 
 // Where the launches of the current mvae_rnn_fwd / mvae_rnn_bwd call report a bounded spin that ran out (capi.hip clears it before dispatching
 // and hands it to the caller as *status_out): set by every launcher that enqueues a kernel with bounded spins, left alone by the others.

@@ -11,6 +11,8 @@
   * ``moses_epoch_plan`` / ``MosesDeviceDataset`` -- that corpus resident in HBM; every batch is ONE launch (``mvae_moses_collate``) that
                            yields the ``PaddedBatch`` ``mosesvae.VAE.forward`` takes: the stable length-descending collate of
                            ``vocab.get_padded_collate_fn`` without its per-string host work.  Opt-in length bucketing.
+                           ``lookup`` / ``contains`` / ``n_distinct``: an exact hash index of the corpus rows on the device
+                           (``mvae_corpus_index_build`` / ``_probe``), which ``train.moses_generate(novel_against=)`` counts novelty with.
   * ``load_smiles`` / ``save_encoded`` / ``load_encoded`` -- ``.smi``/CSV in, ``.npz`` (indices + charset + max_len) out.
 """
 import numpy as np
@@ -213,9 +215,82 @@ class MosesDeviceDataset:
         self.tokens = torch.from_numpy(np.concatenate([tokens, np.zeros(1, np.uint8)])).to(self.device)
         self.offsets = torch.from_numpy(np.ascontiguousarray(offsets)).to(self.device)
         self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._slots = self._n_distinct_d = self._n_distinct = None     # the corpus index: built on first use
 
     def __len__(self):
         return self.n
+
+    def build_index(self):
+        """The exact corpus index behind ``lookup`` / ``contains`` / ``n_distinct``: an open-addressing hash table over the CSR rows (int64
+        slots, the smallest power of two >= 2 N of them, so at most half full), filled by one ``mvae_corpus_index_build`` launch.  Does
+        nothing when the index is there; never waits for the device.  Returns self."""
+        if self._slots is None:
+            from . import ops
+            from .models import _require_cuda
+            _require_cuda(self.device, "MosesDeviceDataset's corpus index")
+            n_slots = 1 << (2 * self.n - 1).bit_length()
+            slots = torch.empty(n_slots, dtype=torch.long, device=self.device)
+            self._n_distinct_d = torch.empty(1, dtype=torch.long, device=self.device)
+            ops.corpus_index_build(self.tokens, self.offsets, self.n, slots, self._n_distinct_d)
+            self._slots = slots
+        return self
+
+    @property
+    def n_distinct(self):
+        """The number of distinct corpus rows, a Python int (waits for the device once, then cached)."""
+        if self._n_distinct is None:
+            self.build_index()
+            self._n_distinct = int(self._n_distinct_d.item())
+        return self._n_distinct
+
+    def _probe(self, x):
+        """lookup() of a device int64 [B, T] with unit column stride: one launch, no wait."""
+        from . import ops
+        self.build_index()
+        match = torch.empty(x.shape[0], dtype=torch.long, device=self.device)
+        ops.corpus_index_probe(self.tokens, self.offsets, self.n, self._slots, x, self.vocab.eos, match)
+        return match
+
+    def lookup(self, x):
+        """Which corpus row each token row equals: int64 [B] on the device, the LOWEST corpus row with exactly those tokens, -1 for none
+        (``mvae_corpus_index_probe``; builds the index on first use).  x: padded ids [B, T] (bos first) on the device, or a list of id
+        tensors (bos first) or strings.  A row's content is what stands between <bos> and its first <eos> (or its last column); a special
+        token inside it matches nothing.  Strings go through ``tokenize_corpus``' byte table, as the corpus did, so an unknown character
+        is <unk> on both sides.  Exact: token rows are compared, not hashes."""
+        v = self.vocab
+        if not torch.is_tensor(x):
+            x = list(x)
+            if not x:
+                raise ValueError("lookup: needs at least one row")
+            csr = None
+            if all(isinstance(s, str) for s in x):
+                try:
+                    csr = tokenize_corpus(x, v)
+                except ValueError:                                # a character beyond latin-1: <unk> by the slow route below
+                    pass
+            if csr is not None:
+                tokens, offsets = csr
+                lens = np.diff(offsets)
+                cols = int(lens.max()) + 2
+                host = np.full((len(x), cols), v.pad, dtype=np.int64)
+                host[:, 0] = v.bos
+                host[:, 1:-1][np.arange(cols - 2)[None, :] < lens[:, None]] = tokens      # the mask's row-major order is the CSR's order
+                host[np.arange(len(x)), lens + 1] = v.eos
+                x = torch.from_numpy(host)
+            else:
+                seqs = [torch.as_tensor(v.string2ids(s, add_bos=True, add_eos=True) if isinstance(s, str) else s, dtype=torch.long).view(-1)
+                        for s in x]
+                x = torch.nn.utils.rnn.pad_sequence(seqs, batch_first=True, padding_value=v.pad)
+        if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError(f"lookup: x must be [B, T], got {tuple(x.shape)}")
+        x = x.to(self.device, torch.long)
+        if x.stride(1) != 1:
+            x = x.contiguous()
+        return self._probe(x)
+
+    def contains(self, x):
+        """``lookup(x) >= 0``: bool [B] on the device."""
+        return self.lookup(x) >= 0
 
     def _collate(self, rows, T):
         from . import ops

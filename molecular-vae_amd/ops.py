@@ -463,6 +463,21 @@ def moses_collate(tokens, offsets, rows, x_pad, lengths, T, N, bos, eos, pad, ro
                                       ptr(lengths), ptr(rows_sorted), ptr(err), stream_ptr()), "mvae_moses_collate")
 
 
+def corpus_index_build(tokens, offsets, N, slots, n_distinct=None):
+    """Fills the exact hash index `slots` (int64 [n_slots], n_slots a power of two > N; cleared by the launch itself) over the CSR corpus
+    (tokens uint8, offsets int64 [N + 1]); n_distinct (int64 [1], optional) := the number of distinct rows (mvae_corpus_index_build)."""
+    check(L.load().mvae_corpus_index_build(ptr(tokens), ptr(offsets), N, ptr(slots), slots.numel(), ptr(n_distinct), stream_ptr()),
+          "mvae_corpus_index_build")
+
+
+def corpus_index_probe(tokens, offsets, N, slots, x, eos, match):
+    """match [B] int64 := the lowest corpus row whose tokens equal x[b, 1:] cut before its first `eos` (x int64 [B, T], bos first), -1 for
+    none -- exact, one launch (mvae_corpus_index_probe)."""
+    B, T = x.shape
+    check(L.load().mvae_corpus_index_probe(ptr(tokens), ptr(offsets), N, ptr(slots), slots.numel(), B, T, ptr(x), x.stride(0), int(eos),
+                                           ptr(match), stream_ptr()), "mvae_corpus_index_probe")
+
+
 def relu_bwd(dy, y):
     check(L.load().mvae_relu_bwd(dy.numel(), ptr(dy), ptr(y), stream_ptr()), "mvae_relu_bwd")
 

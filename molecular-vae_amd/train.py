@@ -791,7 +791,7 @@ def moses_reconstruction(model, batches, beam_width=1, max_len=100):
 
 @torch.no_grad()
 def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top_k=None, top_p=None, seed=0, z=None, syntax=False,
-                   count_valid=False):
+                   count_valid=False, novel_against=None):
     """The reference's generation pipeline (``hugesample.py``: sample in batches, hash the strings, count unique / total) with the hashing
     and the deduplication on the device: ``n_samples`` sequences from a ``mosesvae.VAE`` in batches of ``batch_size`` (the last one shorter),
     batch j with seed ``seed + j`` and ``temp`` / ``top_k`` / ``top_p`` as ``VAE.sample`` takes them.  ``z`` None draws each batch's latents
@@ -807,7 +807,16 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     only in how they end (<eos> against the max_len cut) are distinct entries with equal strings.
     ``syntax=True`` samples under the SMILES syntax automaton (``VAE.sample(syntax=True)``; needs max_len >= 3).  ``count_valid=True`` runs
     the syntax check (``VAE.syntax_valid``) on each batch's rows on the device and adds "valid" (the number of well-formed samples,
-    duplicates included) and "valid_unique" (of distinct ones) to the result -- syntax only, no chemistry, no rdkit."""
+    duplicates included) and "valid_unique" (of distinct ones) to the result -- syntax only, no chemistry, no rdkit.
+    ``novel_against`` takes a ``data.MosesDeviceDataset`` on the model's device whose vocabulary gives every character and special the id
+    ``model.vocabulary`` gives it (ValueError otherwise, before any device work): each batch's rows are looked up in its corpus index on
+    the device (one ``mvae_corpus_index_probe`` launch per batch, no further host wait) and the result gains "novel" (the number of distinct
+    samples that equal no corpus row), "is_novel" and "corpus_row" (lists aligned with "strings": whether the sample is novel, and the
+    lowest corpus row it equals or -1; they travel like "logq", once, at the end) and, with ``count_valid``, "valid_unique_novel" (distinct,
+    well-formed and novel: the numerator of the usual novelty figure).  Equality with a corpus row is of token rows and exact -- no hash
+    decides it; a sample cut at ``max_len`` is compared by the tokens it has; a sample with a special token inside its content (<pad>,
+    <bos>, <unk> before the <eos>) equals nothing, the corpus holding no specials.  Without ``novel_against`` the launches and the keys of
+    the result are what they were."""
     n_samples, batch_size, max_len = int(n_samples), int(batch_size), int(max_len)
     if n_samples < 1 or batch_size < 1 or max_len < 1:
         raise ValueError(f"moses_generate: n_samples, batch_size and max_len must be >= 1, got {n_samples}, {batch_size}, {max_len}")
@@ -817,6 +826,16 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     if z is not None and tuple(z.shape) != (n_samples, model.d_z):
         raise ValueError(f"moses_generate: z must be [{n_samples}, {model.d_z}], got {tuple(z.shape)}")
     dev = model.device
+    if novel_against is not None:
+        from .data import MosesDeviceDataset
+        if not isinstance(novel_against, MosesDeviceDataset):
+            raise ValueError(f"moses_generate: novel_against must be a MosesDeviceDataset, got {type(novel_against).__name__}")
+        if novel_against.vocab.c2i != model.vocabulary.c2i:
+            raise ValueError("moses_generate: novel_against was tokenised with another vocabulary than the model's")
+        d = novel_against.device
+        if d.type != dev.type or (d.type == "cuda" and (torch.cuda.current_device() if d.index is None else d.index)
+                                  != (torch.cuda.current_device() if dev.index is None else dev.index)):
+            raise ValueError(f"moses_generate: novel_against lives on {d}, the model on {dev}")
     i64 = torch.long
     seen_h = torch.empty(0, dtype=i64, device=dev)             # the hashes seen so far, sorted, and the first-seen index of each
     seen_g = torch.empty(0, dtype=i64, device=dev)
@@ -824,6 +843,8 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     logqs, strings = [], []
     n_valid = torch.zeros((), dtype=i64, device=dev) if count_valid else None
     n_valid_new = torch.zeros((), dtype=i64, device=dev) if count_valid else None
+    n_valid_novel = torch.zeros((), dtype=i64, device=dev) if count_valid and novel_against is not None else None
+    matches = []                                                # the corpus row of each new sample, on the device until the end
     stage = [None, None]                                        # pinned staging rows [batch_size, max_len + 1] (ids, end), alternating
     pending = None
 
@@ -838,6 +859,7 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         zb = model.sample_z_prior(n) if z is None else z[b0:b0 + n]
         x, ends, logq, h = model._sample_tokens(zb, max_len, temp, int(seed) + j, k, p, syntax=bool(syntax))
         ok = model.syntax_valid(x) if count_valid else None
+        match = novel_against.lookup(x) if novel_against is not None else None
         hs, order = torch.sort(h, stable=True)                  # equal hashes: ascending row, so a run starts at its first occurrence
         first = torch.ones(n, dtype=torch.bool, device=dev)
         first[1:] = hs[1:] != hs[:-1]
@@ -853,6 +875,8 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         if count_valid:
             n_valid += ok.sum()
             n_valid_new += (ok[order] & new).sum()
+            if match is not None:
+                n_valid_novel += (ok[order] & new & (match[order] < 0)).sum()
         key, ord2 = torch.sort(torch.where(new, order, torch.full_like(order, n)))     # the new rows first, in first-seen order
         n_new = int(new.sum())                                   # the batch's one host wait (the copy queued last round has landed too)
         if pending is not None:
@@ -866,6 +890,8 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
             rows[:n_new].copy_(torch.cat([x[sel], ends[sel, None]], 1), non_blocking=True)
             pending = (rows, n_new)
             logqs.append(logq[sel])
+            if match is not None:
+                matches.append(match[sel])
             g0 = counts.numel()
             counts = torch.cat([counts, cnt[src]])
             seen_h, perm = torch.sort(torch.cat([seen_h, hs[src]]))
@@ -877,6 +903,12 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
            "logq": torch.cat(logqs).tolist() if logqs else []}
     if count_valid:
         res["valid"], res["valid_unique"] = int(n_valid), int(n_valid_new)
+    if novel_against is not None:
+        res["corpus_row"] = torch.cat(matches).tolist() if matches else []
+        res["is_novel"] = [r < 0 for r in res["corpus_row"]]
+        res["novel"] = sum(res["is_novel"])
+        if count_valid:
+            res["valid_unique_novel"] = int(n_valid_novel)
     return res
 
 
