@@ -213,7 +213,8 @@ typedef struct {
   const void* w_ih[MVAE_MAX_LAYERS]; int64_t ldw_ih[MVAE_MAX_LAYERS];   /* [G*H, in] (w_ih[0] unused when x0 == NULL) */
   const void* w_hh[MVAE_MAX_LAYERS]; int64_t ldw_hh[MVAE_MAX_LAYERS];   /* [G*H, H] */
   const float* bias[MVAE_MAX_LAYERS];                                    /* LSTM: b_ih+b_hh [4H]; GRU: [b_ir+b_hr; b_iz+b_hz; b_in; b_hn] [4H] */
-  const void* h0[MVAE_MAX_LAYERS]; int64_t ldh0;                         /* optional initial hidden state [B, ldh0] dtype (NULL = zeros) */
+  const void* h0[MVAE_MAX_LAYERS]; int64_t ldh0;                         /* GRU: optional initial hidden state [B, ldh0] dtype (NULL = zeros).  LSTM: must be NULL
+                                                                            (zero initial state, there is no c0): any h0[l] != NULL -> MVAE_ERR_UNSUPPORTED */
   const int32_t* lengths;
   void* hs[MVAE_MAX_LAYERS]; int64_t ldh;
   void* cs[MVAE_MAX_LAYERS];
@@ -278,15 +279,16 @@ typedef struct {
   const int32_t* lengths;
   const float* dy; int64_t dy_ld;
   const void* dy_a; int64_t dy_a_ld; const void* dy_w; int64_t dy_w_ld; int dy_k;   /* optional (NULL): see above */
-  const float* dh_last[MVAE_MAX_LAYERS];                                  /* optional fp32 [B,H] gradient w.r.t. the final hidden state */
+  const float* dh_last[MVAE_MAX_LAYERS];                                  /* GRU: optional fp32 [B,H] gradient w.r.t. the final hidden state.  LSTM: must be NULL */
   const void* hs[MVAE_MAX_LAYERS]; int64_t ldh;
-  const void* h0[MVAE_MAX_LAYERS]; int64_t ldh0;
+  const void* h0[MVAE_MAX_LAYERS]; int64_t ldh0;                          /* GRU only, as in mvae_rnn_fwd_desc.  LSTM: h0[l], dh_last[l] and dh0[l] must all be
+                                                                             NULL -- a non-NULL one is refused with MVAE_ERR_UNSUPPORTED before anything is enqueued */
   const void* cs[MVAE_MAX_LAYERS];
   const void* gates[MVAE_MAX_LAYERS];
   void* dG[MVAE_MAX_LAYERS]; int64_t ldg;                                  /* row stride of dG (>= G*H; pad it off powers of two) */
   void* dGh[MVAE_MAX_LAYERS];                                              /* RESERVED, ignored: no kernel reads or writes it (the W_hh-side rows are dG's slots r, z, n*r); kept for the struct layout */
   float* dstate[MVAE_MAX_LAYERS];                                         /* fp32 [2][B][H] ping-pong: LSTM dc, GRU dh carry */
-  float* dh0[MVAE_MAX_LAYERS];                                            /* optional out: gradient w.r.t. h0 (GRU decoder_lat path) */
+  float* dh0[MVAE_MAX_LAYERS];                                            /* GRU: optional out: gradient w.r.t. h0 (decoder_lat path).  LSTM: must be NULL */
   void* split_ws; size_t split_ws_bytes;                                  /* optional scratch of mvae_rnn_bwd_workspace(d) bytes: enables the split-K
                                                                              schedules (fp32 partial tiles of dh summed across workgroups) */
   /* inter-layer dropout of the forward pass (same mask / seed / p): the gradient that layer l receives from layer l+1

@@ -1189,6 +1189,9 @@ int rnn_fwd_impl(const mvae_rnn_fwd_desc* d, hipStream_t st) {
   const int epc = (dt == MVAE_BF16) ? 8 : 4;
   const bool gru = d->cell == MVAE_CELL_GRU;
   if (d->lengths && !gru) return MVAE_ERR_UNSUPPORTED;
+  // LSTM: zero initial state only (there is no c0 to go with an h0) -- refused here, before anything is enqueued
+  for (int l = 0; l < NL && !gru; ++l)
+    if (d->h0[l]) return MVAE_ERR_UNSUPPORTED;
   // forward-only (inference) call: no save buffers at all -- gates[l] == cs[l] == NULL for every layer
   const bool infer = !d->gates[0];
   for (int l = 0; l < NL; ++l) {
@@ -1382,6 +1385,10 @@ int rnn_bwd_impl(const mvae_rnn_bwd_desc* d, hipStream_t st) {
                   ((reinterpret_cast<uintptr_t>(d->dy_a) | reinterpret_cast<uintptr_t>(d->dy_w)) & 15)))
     return MVAE_ERR_INVALID;
   if (d->lengths && !gru) return MVAE_ERR_UNSUPPORTED;
+  // LSTM: no gradient enters through the final hidden state and none is returned for an initial one (the cell below carries dc only):
+  // refused here, before anything is enqueued, instead of being ignored
+  for (int l = 0; l < NL && !gru; ++l)
+    if (d->h0[l] || d->dh_last[l] || d->dh0[l]) return MVAE_ERR_UNSUPPORTED;
   for (int l = 0; l < NL; ++l) {
     if (!d->w_hhT[l] || (!gru && !d->cs[l]) || !d->gates[l] || !d->dG[l] || !d->dstate[l]) return MVAE_ERR_INVALID;
     if (gru && !d->hs[l]) return MVAE_ERR_INVALID;
