@@ -9,6 +9,8 @@ samples (duplicates included) that are well-formed SMILES strings -- balanced br
 syntax, not chemistry -- counted on the device.  ``--syntax`` samples under that grammar, so that every sample is well-formed.
 ``--novel_against FILE`` loads the training strings (one per line) into a ``data.MosesDeviceDataset`` and counts ``novel``: the distinct
 samples whose token row equals no row of that corpus, looked up on the device in its exact index (no set of strings on the host).
+``--neighbors K`` (with ``--novel_against``) encodes that corpus once (``MosesDeviceDataset.encode_latents``) and prints, for the first few
+unique samples, their K nearest training molecules in latent space with the squared distances (``MosesLatentIndex.neighbors``).
 
     python examples/sample_moses.py --ckpt trained_save.pt --vocab vocab.pkl --rounds 10 --top_p 0.95 --syntax --novel_against train.smi
 """
@@ -39,6 +41,8 @@ ap.add_argument("--prior", default="normal", choices=["normal", "zeros"], help="
 ap.add_argument("--seed", default=0, type=int)
 ap.add_argument("--log", default="log_small.csv")
 ap.add_argument("--novel_against", default=None, metavar="FILE", help="training strings, one per line: count the unique samples not among them")
+ap.add_argument("--neighbors", default=0, type=int, metavar="K", help="with --novel_against: print the K nearest training molecules (latent "
+                                                                    "space) of the first few unique samples")
 ap.add_argument("--out", default=None, help="write the unique strings with their counts (and, with --novel_against, 1 for novel / 0) here, "
                                             "tab separated")
 args = ap.parse_args()
@@ -99,6 +103,21 @@ with open(args.log, "w", buffering=1) as f:
               f"unique per second {len(seen) / (now - start):.0f}, well-formed {syntax_valid} ({syntax_valid / total:.3f})"
               + (f", valid unique {valid}" if Chem is not None else "")
               + (f", novel {len(novel)} ({len(novel) / len(seen):.3f} of unique)" if corpus is not None else ""), flush=True)
+if args.neighbors > 0 and corpus is None:
+    print("--neighbors needs --novel_against (the training strings to search)", flush=True)
+elif args.neighbors > 0:
+    t0 = time.time()
+    index = corpus.encode_latents(model)
+    shown = [s for s in list(seen)[:8] if s]
+    if shown:
+        dist, rows = index.neighbors(shown, args.neighbors, model)
+        names = corpus.smiles(rows)                                 # waits for the search; one copy
+        print(f"latent table of {len(corpus)} molecules and {len(shown)} searches: {time.time() - t0:.2f} s")
+        for i, (s, d) in enumerate(zip(shown, dist.tolist())):
+            print(f"{s}  ({'novel' if s in novel else 'in the corpus'})")
+            for j in range(args.neighbors):
+                if names[i * args.neighbors + j] is not None:
+                    print(f"    {d[j]:10.4f}  {names[i * args.neighbors + j]}")
 if args.out:
     with open(args.out, "w") as f:
         for s, c in sorted(seen.items(), key=lambda kv: -kv[1]):

@@ -652,6 +652,27 @@ int mvae_gauss_pairwise_lse(int Nz, int Nx, int dz, const float* z, int64_t ldz,
                             void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Exact k nearest neighbours in latent space (an addition: the table is the encoder mean of every corpus row, data.MosesLatentIndex).
+ * mvae_latent_knn: for each of Q queries (q [Q, ldq]) the k rows of table [N, ldt] at the smallest squared Euclidean distance
+ *   d2(i, j) = sum_d (q[i,d] - table[j,d])^2, computed in fp32 as a sum of squares of fp32 differences -- no norm expansion, so a row's
+ *   distance to itself is exactly 0 and close neighbours keep their order.  The order of the sum is fixed (it does not depend on Q, N, k
+ *   or on how the launch is laid out).
+ *   Row i of dist / idx ([Q, k], dense) holds the k eligible rows with the smallest (d2, j), ascending in that pair: equal distances rank
+ *   by the lower row index.  A row is eligible unless it is exclude[i] (exclude [Q] int64 or NULL; -1 = none) or its distance is NaN; a
+ *   distance that overflowed to +inf is eligible.  With fewer than k eligible rows the tail of the output row is (+inf, -1).  Every element
+ *   of dist and idx is written, nothing else is; two runs are bitwise equal.
+ *   Nothing of size Q x N exists: one scan launch keeps a k-entry list per (query, wave) in LDS, and, when the table rows are split over
+ *   `slots` partial lists per query to fill the chip (slots depends on Q and N alone, <= 256), one merge launch combines them by (d2, j).
+ *   Workspace: mvae_latent_knn_workspace(Q, N, dz, k) = slots * Q * k * 12 bytes (8-byte aligned; 0: one slot, none needed).
+ *   Limits: dz <= 192 and k <= 32, else MVAE_ERR_UNSUPPORTED (the workspace function then returns 0).  Q, N, k or dz < 1, a leading
+ *   dimension < dz or a NULL pointer other than exclude give MVAE_ERR_INVALID, a short or missing workspace MVAE_ERR_WORKSPACE; all of
+ *   these before anything is enqueued.
+ */
+size_t mvae_latent_knn_workspace(int Q, int64_t N, int dz, int k);
+int mvae_latent_knn(int Q, int64_t N, int dz, int k, const float* q, int64_t ldq, const float* table, int64_t ldt, const int64_t* exclude,
+                    float* dist, int64_t* idx, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Optimiser surface (K14 + K15): torch.nn.utils.clip_grad_norm_(params, max_norm) (train.py:102) followed by
  * torch.optim.Adam.step() (train.py:81,104) on a FLAT fp32 parameter / gradient / m / v buffer.
  *   mvae_sumsq: partial[i] = sum of squares of chunk i (deterministic); norm_out[0] = sqrt(total) is

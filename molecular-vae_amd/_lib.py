@@ -177,6 +177,8 @@ SIGNATURES = {
     "mvae_group_logmeanexp": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mvae_gauss_pairwise_lse_workspace": (_sz, [_i, _i, _i]),
     "mvae_gauss_pairwise_lse": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "mvae_latent_knn_workspace": (_sz, [_i, _i64, _i, _i]),
+    "mvae_latent_knn": (_i, [_i, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -13,6 +13,8 @@
                            ``vocab.get_padded_collate_fn`` without its per-string host work.  Opt-in length bucketing.
                            ``lookup`` / ``contains`` / ``n_distinct``: an exact hash index of the corpus rows on the device
                            (``mvae_corpus_index_build`` / ``_probe``), which ``train.moses_generate(novel_against=)`` counts novelty with.
+                           ``encode_latents`` -> ``MosesLatentIndex``: the encoder mean of every corpus row in HBM and an exact k-NN
+                           search over it (``mvae_latent_knn``); ``smiles`` reads corpus rows back as strings.
   * ``load_smiles`` / ``save_encoded`` / ``load_encoded`` -- ``.smi``/CSV in, ``.npz`` (indices + charset + max_len) out.
 """
 import numpy as np
@@ -292,6 +294,59 @@ class MosesDeviceDataset:
         """``lookup(x) >= 0``: bool [B] on the device."""
         return self.lookup(x) >= 0
 
+    def _check_model(self, model, who):
+        """The checks ``moses_generate(novel_against=)`` makes, before any device work: the model's vocabulary gives every character and
+        special the id this corpus was tokenised with, and the model lives on this corpus' device."""
+        if self.vocab.c2i != model.vocabulary.c2i:
+            raise ValueError(f"{who}: the corpus was tokenised with another vocabulary than the model's")
+        d, dev = self.device, model.device
+        if d.type != dev.type or (d.type == "cuda" and (torch.cuda.current_device() if d.index is None else d.index)
+                                  != (torch.cuda.current_device() if dev.index is None else dev.index)):
+            raise ValueError(f"{who}: the corpus lives on {d}, the model on {dev}")
+
+    @torch.no_grad()
+    def encode_latents(self, model, batch_size=4096):
+        """The latent table of the corpus: a ``MosesLatentIndex`` whose ``mu`` (float32 [N, d_z], on the device) holds in row r the
+        encoder mean of corpus row r under ``model`` (``VAE.encode``: eps = 0, eval mode, no gradients).  The rows are visited in
+        ascending order in chunks of ``batch_size`` (the last one shorter); each chunk is collated by ``gather`` (T = the chunk's longest
+        row + 2, known on the host), encoded and scattered to ``mu[batch.rows]``.  Never waits for the device.  ValueError, before any
+        device work: another vocabulary than the model's, or a model on another device."""
+        self._check_model(model, "encode_latents")
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError(f"encode_latents: batch_size must be >= 1, got {batch_size}")
+        mu = torch.empty(self.n, model.d_z, dtype=torch.float32, device=self.device)
+        rows = torch.arange(self.n, device=self.device)
+        for lo in range(0, self.n, batch_size):
+            hi = min(lo + batch_size, self.n)
+            batch = self.gather(rows[lo:hi], T=int(self.lengths[lo:hi].max()) + 2)
+            mu[batch.rows] = model.encode(batch)[0]
+        return MosesLatentIndex(mu, self)
+
+    def smiles(self, rows):
+        """The strings of corpus rows (a list, an ndarray or a tensor on either side, any shape; the result is flat): the rows' CSR slices
+        are gathered on the device and come back in ONE device-to-host copy.  A row id of -1 (the tail of a short k-NN answer) gives
+        None; any other id outside the corpus raises ValueError."""
+        r = torch.as_tensor(rows).to(self.device, torch.long).reshape(-1)
+        if r.numel() < 1:
+            return []
+        L = max(self.max_len, 1)
+        safe = r.clamp(0, self.n - 1)
+        start = self.offsets[safe]
+        lens = self.offsets[safe + 1] - start
+        pos = (start[:, None] + torch.arange(L, device=self.device)[None, :]).clamp_(max=self.tokens.numel() - 1)
+        host = torch.cat([r[:, None], lens[:, None], self.tokens[pos].long()], dim=1).cpu().numpy()
+        table = np.array([self.vocab.i2c[i] for i in range(len(self.vocab))], dtype=object)
+        out = []
+        for row in host:
+            if row[0] == -1:
+                out.append(None)
+                continue
+            if not 0 <= row[0] < self.n:
+                raise ValueError(f"smiles: row id {int(row[0])} outside [0, {self.n})")
+            out.append("".join(table[row[2:2 + row[1]]]))
+        return out
+
     def _collate(self, rows, T):
         from . import ops
         from .vocab import PaddedBatch
@@ -343,6 +398,52 @@ class MosesDeviceDataset:
         order_d = torch.from_numpy(order).to(self.device)
         for lo, hi, T in cuts:
             yield self._collate(order_d[lo:hi], T)
+
+
+class MosesLatentIndex:
+    """The latent table of a ``MosesDeviceDataset`` (``encode_latents``): ``mu`` float32 [N, d_z] on the device, row r the encoder mean of
+    corpus row r, and ``dataset``.  ``search`` is the exact k-nearest-neighbour search over it (``mvae_latent_knn``: squared Euclidean
+    distance as a direct f32 difference, ties by the lower row, no Q x N buffer)."""
+
+    def __init__(self, mu, dataset):
+        if mu.dim() != 2 or mu.dtype != torch.float32 or mu.shape[0] != dataset.n:
+            raise ValueError(f"MosesLatentIndex: mu must be float32 [{dataset.n}, d_z], got {mu.dtype} {tuple(mu.shape)}")
+        self.mu, self.dataset = mu, dataset
+
+    def __len__(self):
+        return self.mu.shape[0]
+
+    def search(self, z, k, exclude=None):
+        """(dist2 float32 [Q, k], rows int64 [Q, k]) on the device: the k corpus rows nearest to each latent point of z [Q, d_z], ascending
+        in (distance, row); ``exclude`` (int64 [Q], -1 = none) names a row each query skips; a tail that cannot be filled is (+inf, -1).
+        One launch (two when the table is split over workgroups), no host wait."""
+        from . import ops
+        z = z.to(self.mu.device, torch.float32)
+        if z.dim() != 2 or z.shape[1] != self.mu.shape[1] or z.shape[0] < 1:
+            raise ValueError(f"search: z must be [Q, {self.mu.shape[1]}], got {tuple(z.shape)}")
+        if exclude is not None:
+            exclude = exclude.to(self.mu.device, torch.long)
+        return ops.latent_knn(z, self.mu, k, exclude=exclude)
+
+    def neighbors(self, x, k, model, exclude_self=False):
+        """``search`` around the encoder means of x under ``model``: x is a list of strings or of id tensors (bos first; any order), or a
+        PaddedBatch; the answers are in the order of x.  ``exclude_self``: a query that is itself a corpus row (``dataset.lookup``: its
+        lowest row with those tokens) does not answer with that row."""
+        from .vocab import PaddedBatch
+        self.dataset._check_model(model, "neighbors")
+        if isinstance(x, PaddedBatch):
+            mu, keys = model.encode(x)[0], x.x_pad
+        else:
+            keys = list(x)
+            if not keys:
+                raise ValueError("neighbors: needs at least one query")
+            seqs = [model.string2tensor(s) if isinstance(s, str) else torch.as_tensor(s, dtype=torch.long).view(-1) for s in keys]
+            order = sorted(range(len(seqs)), key=lambda i: -seqs[i].numel())        # stable, length descending: what the encoder takes
+            mu_sorted = model.encode([seqs[i] for i in order])[0]
+            mu = torch.empty_like(mu_sorted)
+            mu[torch.tensor(order, device=mu.device)] = mu_sorted
+        exclude = self.dataset.lookup(keys) if exclude_self else None
+        return self.search(mu, k, exclude=exclude)
 
 
 def synthetic_smiles(n, seed=0, lo=20, hi=60, structured=True):

@@ -245,6 +245,20 @@ class VAE(_SavedState, nn.Module):
         self._note_kl(opt and opt["fb"])
         return out
 
+    @torch.no_grad()
+    def encode(self, x):
+        """The posterior of every sequence of x (what forward_encoder takes: a list of id tensors sorted by length descending, or a
+        PaddedBatch): (mu, logvar), float32 [B, d_z] on the device, in the order of x.  forward_encoder with eps = 0, so that z = mu; runs
+        without gradients and in eval mode for the call (the training flag is restored)."""
+        was_training = self.training
+        self.eval()
+        try:
+            B = len(x)
+            z, _, logvar = self.forward_encoder(x, eps=torch.zeros(B, self.d_z, device=self.device))
+        finally:
+            self.train(was_training)
+        return z.float(), logvar.float()
+
     def forward_decoder(self, x, z, drop_mask=None, drop_seed=None, word_mask=None, word_seed=None):
         """mosesvae.py:166-199: teacher-forced decoder on the caller's latent z [B, d_z] -> (recon_loss, x_padded, y); differentiable w.r.t. z
         and x_emb / decoder_rnn / decoder_lat / decoder_fc.  Train mode applies the inter-layer dropout and the word dropout as `forward` does."""

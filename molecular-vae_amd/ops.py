@@ -571,6 +571,38 @@ def gauss_pairwise_lse(z, mu, logvar, out, Nz, Nx, dz, ldz=None, ldp=None):
           "mvae_gauss_pairwise_lse")
 
 
+def latent_knn(q, table, k, exclude=None, dist=None, idx=None):
+    """The k nearest rows of table [N, dz] for every row of q [Q, dz] (float32, unit stride along d; row strides are passed through) by
+    squared Euclidean distance, summed as direct f32 differences: (dist [Q, k] float32, idx [Q, k] int64), ascending in (distance, row);
+    exclude (int64 [Q], optional) names one table row per query to skip (-1: none); rows at a NaN distance are skipped; a short tail
+    is (+inf, -1) (mvae_latent_knn; its workspace comes from Scratch)."""
+    lib = L.load()
+    assert q.dim() == 2 and table.dim() == 2 and q.shape[1] == table.shape[1], (q.shape, table.shape)
+    assert q.dtype == table.dtype == torch.float32 and q.device == table.device
+    Q, dz = q.shape
+    N, k = table.shape[0], int(k)
+    if dz > 1 and q.stride(1) != 1:
+        q = q.contiguous()
+    if dz > 1 and table.stride(1) != 1:
+        table = table.contiguous()
+    ldq = q.stride(0) if Q > 1 else max(q.stride(0), dz)
+    ldt = table.stride(0) if N > 1 else max(table.stride(0), dz)
+    if exclude is not None:
+        assert exclude.dtype == torch.int64 and exclude.shape == (Q,) and exclude.device == q.device
+        exclude = exclude.contiguous()
+    if dist is None:
+        dist = torch.empty(Q, max(k, 0), dtype=torch.float32, device=q.device)
+    if idx is None:
+        idx = torch.empty(Q, max(k, 0), dtype=torch.int64, device=q.device)
+    assert dist.shape == (Q, k) and idx.shape == (Q, k) and dist.is_contiguous() and idx.is_contiguous()
+    assert dist.dtype == torch.float32 and idx.dtype == torch.int64 and dist.device == q.device == idx.device
+    nb = lib.mvae_latent_knn_workspace(Q, N, dz, k)
+    ws = Scratch.get(nb, q.device, "latent_knn") if nb else None
+    check(lib.mvae_latent_knn(Q, N, dz, k, ptr(q), ldq, ptr(table), ldt, ptr(exclude), ptr(dist), ptr(idx), ptr(ws), nb, stream_ptr()),
+          "mvae_latent_knn")
+    return dist, idx
+
+
 def sample_uniform(seed, step, B):
     """Host restatement of the sampling step's uniforms u(b) = hash(seed, step * B + b) / 2^32 (tests)."""
     import numpy as np
