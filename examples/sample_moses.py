@@ -11,6 +11,9 @@ syntax, not chemistry -- counted on the device.  ``--syntax`` samples under that
 samples whose token row equals no row of that corpus, looked up on the device in its exact index (no set of strings on the host).
 ``--neighbors K`` (with ``--novel_against``) encodes that corpus once (``MosesDeviceDataset.encode_latents``) and prints, for the first few
 unique samples, their K nearest training molecules in latent space with the squared distances (``MosesLatentIndex.neighbors``).
+``--reconstruct FILE`` (strings, one per line) skips the generation: it encodes the strings (z = mu), decodes them deterministically
+(``--beam_width``) without and with the syntax constraint (``mv.moses_reconstruction(..., syntax=)``) and prints the exact-match
+reconstruction fraction of each and the mean log p(x | mu).
 
     python examples/sample_moses.py --ckpt trained_save.pt --vocab vocab.pkl --rounds 10 --top_p 0.95 --syntax --novel_against train.smi
 """
@@ -43,6 +46,9 @@ ap.add_argument("--log", default="log_small.csv")
 ap.add_argument("--novel_against", default=None, metavar="FILE", help="training strings, one per line: count the unique samples not among them")
 ap.add_argument("--neighbors", default=0, type=int, metavar="K", help="with --novel_against: print the K nearest training molecules (latent "
                                                                     "space) of the first few unique samples")
+ap.add_argument("--reconstruct", default=None, metavar="FILE", help="strings, one per line: report exact-match reconstruction at z = mu "
+                                                                  "without and with the syntax constraint, then exit")
+ap.add_argument("--beam_width", default=1, type=int, help="with --reconstruct: the beam width of the deterministic decode")
 ap.add_argument("--out", default=None, help="write the unique strings with their counts (and, with --novel_against, 1 for novel / 0) here, "
                                             "tab separated")
 args = ap.parse_args()
@@ -67,6 +73,17 @@ model = model.to(dev).eval()
 model.prior = args.prior
 model.seed_noise(args.seed)
 corpus = mv.MosesDeviceDataset(D.load_smiles(args.novel_against), vocab, device=dev) if args.novel_against else None
+
+if args.reconstruct:
+    collate = VC.get_collate_fn(vocab)
+    strings = D.load_smiles(args.reconstruct)
+    batches = [collate(strings[i:i + args.batch_size]) for i in range(0, len(strings), args.batch_size)]
+    for syntax in (False, True):
+        t0 = time.time()
+        frac, mean_lp = mv.moses_reconstruction(model, batches, beam_width=args.beam_width, max_len=args.max_len, syntax=syntax)
+        print(f"reconstruction of {len(strings)} strings, beam width {args.beam_width}, syntax={syntax}: exact match {frac:.4f}, "
+              f"mean log p(x | mu) {mean_lp:.3f}, {time.time() - t0:.2f} s", flush=True)
+    sys.exit(0)
 
 
 def is_valid(s):

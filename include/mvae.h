@@ -616,6 +616,21 @@ int mvae_smiles_syntax_check(int B, int T, int V, const int64_t* x, int64_t x_ld
  *   (offset l * layer_stride elements), half 0 = the state the GRU step read as h0 and half 1 (offset half_stride) = the state it wrote,
  *   rows of ldh elements; the parent's half-1 row is copied into row r of half 0 for every layer.  h_top is half 1 of the last layer.
  *   Initial state: score 0 for beam 0 and -inf for beams 1..K-1 of every molecule, fin 0, ends max_len.
+ * mvae_moses_beam_syntax_step: mvae_moses_beam_step over well-formed strings only (the automaton of "SMILES syntax" above).  gstate
+ *   int32 [B*K, 2] holds the packed automaton state of every beam row, initially {0 | 0xFF << 16, 0}.  An active row may propose class v
+ *   iff the automaton takes it from gstate[r] AND the tokens still needed to finish the string after it (<eos> included) fit the
+ *   max_len - 1 - step that remain -- the rule of mvae_moses_sample_syntax_step; it proposes its best min(K, allowed) classes in the order
+ *   (score desc, token asc).  The score is NOT renormalised: logp stays the log-softmax over all V classes and the mask only removes
+ *   candidates, so a hypothesis' score is still log p(tokens | z) and the search returns the most probable well-formed strings the beam
+ *   finds (sampling renormalises because it defines a distribution; decoding does not).  Finished rows (fin != 0) are neither masked
+ *   nor advanced and propose themselves once.  gstate is reordered with the recurrent state: new row r with parent p gets p's old
+ *   state if p was finished, else step(p's old state, token), mode ERROR if the step is refused (in place: a workgroup owns whole
+ *   molecules).  A molecule can have fewer than K candidates (K = 16 at max_len = 3: one per atom token): a slot without one is dead --
+ *   score -inf, parent 0, token pad_id, which puts its automaton in ERROR, so it proposes nothing again, stays at -inf and never
+ *   outranks a finite hypothesis; its ids and ends are unspecified but deterministic.  Some allowed token always lowers the need by one,
+ *   so an active state is never left without an allowed token: beam 0 of every molecule is finite and every finite hypothesis takes
+ *   <eos> by step max_len - 1.  Refused (MVAE_ERR_INVALID) before anything is enqueued: what mvae_moses_beam_step refuses, a null
+ *   tok_info or gstate, max_len < 3, step < 1, step >= max_len, eos_id outside [0, V); V > 64 stays MVAE_ERR_UNSUPPORTED.
  * mvae_moses_beam_finalize: ids [B, K, max_len] int64 from the backpointers (bos_id first, pad after each end), in score order (the beams
  *   are kept sorted by mvae_moses_beam_step); ends_out [B*K] / score_out [B*K] (optional) copy ends / score.
  * mvae_ce_rows_fwd: out[b] = log p(x[b] | z) = sum over t of log_softmax(logits row t*B+b)[x[b, t+1]] for x[b, t+1] != pad -- the targets of
@@ -624,6 +639,10 @@ int mvae_moses_beam_step(int dtype, int B, int K, int V, int H, int layers, void
                          const void* w_fc, int64_t ldw, const float* bias, int step, int eos_id, int pad_id, const float* table, int W,
                          const float* base, float* add_out, float* score, uint8_t* fin, int64_t* ends, int32_t* hist_tok, int32_t* hist_par,
                          void* stream);
+int mvae_moses_beam_syntax_step(int dtype, int B, int K, int V, int H, int layers, void* state, int64_t layer_stride, int64_t half_stride,
+                                int64_t ldh, const void* w_fc, int64_t ldw, const float* bias, int step, int eos_id, int pad_id, const float* table,
+                                int W, const float* base, float* add_out, float* score, uint8_t* fin, int64_t* ends, int32_t* hist_tok,
+                                int32_t* hist_par, const int32_t* tok_info /* [V] */, int32_t* gstate /* [B*K, 2] */, int max_len, void* stream);
 int mvae_moses_beam_finalize(int B, int K, int max_len, int bos_id, const int32_t* hist_tok, const int32_t* hist_par, const int64_t* ends,
                              const float* score, int64_t* ids, int64_t* ends_out, float* score_out, void* stream);
 int mvae_ce_rows_fwd(int B, int T, int V, const float* logits, int64_t ldl, const int64_t* x, int pad, float* out, void* stream);

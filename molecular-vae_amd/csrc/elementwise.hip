@@ -1157,16 +1157,26 @@ __global__ __launch_bounds__(64) void smiles_syntax_check_kernel(int B, int T, i
 // otherwise), the next step's layer-0 addend row table[token] + base[r], and reorders the recurrent state: for every layer, the parent's row
 // of the state the GRU step just wrote (half 1 of `state`) is copied into row r of half 0, which that step has already consumed and which
 // the next step reads as its h0.  Parents are rows of the same molecule, so a workgroup touches only its own rows.
+//
+// SYNTAX (mvae_moses_beam_syntax_step; the other instantiation compiles none of it): every row carries a SMILES automaton state gstate[r]
+// (smiles_syntax.hpp).  Lane v of an active row decides whether class v may be proposed -- the automaton takes it AND the string can still
+// be finished in the max_len - 1 - step tokens left after it, the rule of the sampling launch -- and the row proposes its best
+// min(K, allowed) classes.  logp stays the log-softmax over ALL classes: the mask removes candidates, it does not renormalise, so a score is
+// still log p(tokens | z).  A molecule may be left with fewer than K candidates: a slot without one gets (-inf, parent 0, pad), its pad
+// token puts its automaton in ERROR, which allows nothing, so it stays dead.  Phase 1 reads the pass's old states into LDS, phase 3 writes
+// row r's new one: the parent's old state if the parent was finished, else step(parent's old state, token).
 constexpr int BEAM_KMAX = 16;
-template <typename T>
+template <typename T, bool SYNTAX>
 __global__ __launch_bounds__(256) void moses_beam_step_kernel(int B, int K, int V, int H, int NL, T* __restrict__ state, long layer_stride,
                                                               long half_stride, long ldh, const T* __restrict__ wfc, long ldw,
                                                               const float* __restrict__ bias, int step, int eos_id, int pad_id,
                                                               const float* __restrict__ table, int W, const float* __restrict__ base,
                                                               float* __restrict__ add_out, float* __restrict__ score, uint8_t* __restrict__ fin,
-                                                              int64_t* __restrict__ ends, int32_t* __restrict__ hist_tok, int32_t* __restrict__ hist_par) {
+                                                              int64_t* __restrict__ ends, int32_t* __restrict__ hist_tok, int32_t* __restrict__ hist_par,
+                                                              const int32_t* __restrict__ tok_info, int32_t* __restrict__ gstate, int max_len) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   T* ws = reinterpret_cast<T*>(smem_raw);                    // [V][H]
+  __shared__ int32_t old_g[SYNTAX ? 2 * BEAM_KMAX : 1];      // SYNTAX: the automaton states the pass started from
   __shared__ float cand_s[BEAM_KMAX * BEAM_KMAX];            // [row of the pass][rank within the row]
   __shared__ int cand_t[BEAM_KMAX * BEAM_KMAX];
   __shared__ int cand_n[BEAM_KMAX];
@@ -1181,6 +1191,8 @@ __global__ __launch_bounds__(256) void moses_beam_step_kernel(int B, int K, int 
   const int G = K >= 4 ? 1 : 4 / K;                         // molecules per pass: G * K <= 16 rows
   const long R = (long)B * K;
   const T* htop = state + (long)(NL - 1) * layer_stride + half_stride;
+  int32_t my_info = 0;
+  if constexpr (SYNTAX) my_info = lane < V ? tok_info[lane] : 0;
   for (int m0 = blockIdx.x * G; m0 < B; m0 += gridDim.x * G) {
     const int nm = (B - m0 < G) ? B - m0 : G, nr = nm * K;
     const long r0 = (long)m0 * K;
@@ -1191,6 +1203,12 @@ __global__ __launch_bounds__(256) void moses_beam_step_kernel(int B, int K, int 
       if (s != s) s = -INFINITY;
       const bool done = fin[r] != 0;
       if (lane == 0) { old_s[lr] = s; old_f[lr] = done; old_e[lr] = (long)ends[r]; }
+      smi::State gs{};
+      if constexpr (SYNTAX) {
+        const int32_t g0 = gstate[2 * r], g1 = gstate[2 * r + 1];
+        if (lane == 0) { old_g[2 * lr] = g0; old_g[2 * lr + 1] = g1; }
+        gs = smi::unpack(g0, g1);
+      }
       if (done) {
         if (lane == 0) { cand_s[lr * K] = s; cand_t[lr * K] = pad_id; cand_n[lr] = 1; }
         continue;                                            // wave-uniform
@@ -1207,14 +1225,21 @@ __global__ __launch_bounds__(256) void moses_beam_step_kernel(int B, int K, int 
       float c = s + (mine - (mx + logf(se)));
       if (c != c) c = -INFINITY;
       bool avail = lane < V;
-      for (int j = 0; j < K; ++j) {                          // K <= V: an available class is always left
+      int nc = K;                                            // K <= V: an available class is always left
+      if constexpr (SYNTAX) {
+        smi::State nx;
+        avail = avail && smi::step(gs, lane, my_info, &nx) && smi::need(nx) <= max_len - 1 - step;
+        const int na = (int)__builtin_popcountll(__ballot(avail));
+        nc = na < K ? na : K;                                // wave-uniform; 0 for a row in ERROR (a dead slot)
+      }
+      for (int j = 0; j < nc; ++j) {
         const float best = wave_max(avail ? c : -INFINITY);
         const unsigned long long hit = __ballot(avail && c == best);
         const int v = hit ? (int)__builtin_ctzll(hit) : 0;
         if (lane == v) avail = false;
         if (lane == 0) { cand_s[lr * K + j] = best; cand_t[lr * K + j] = v; }
       }
-      if (lane == 0) cand_n[lr] = K;
+      if (lane == 0) cand_n[lr] = nc;
     }
     __syncthreads();
     // 2. per molecule, a K-way merge of its K sorted candidate lists (lane p = the head of parent p's list): the best K survive
@@ -1227,7 +1252,7 @@ __global__ __launch_bounds__(256) void moses_beam_step_kernel(int B, int K, int 
         const float key = valid ? cand_s[ci] : -INFINITY;
         const int tk = valid ? cand_t[ci] : pad_id;
         const float best = wave_max(key);
-        const unsigned long long hit = __ballot(valid && key == best);   // at least K candidates exist: never empty
+        const unsigned long long hit = __ballot(valid && key == best);   // empty only under SYNTAX: a slot left without a candidate
         const int p = hit ? (int)__builtin_ctzll(hit) : 0;
         const int tok = __shfl(tk, p, 64);
         if (lane == p) ++ptr;
@@ -1247,6 +1272,13 @@ __global__ __launch_bounds__(256) void moses_beam_step_kernel(int B, int K, int 
         ends[r] = (!pdone && tok == eos_id) ? (int64_t)(step + 1) : (int64_t)old_e[lp];
         hist_tok[(long)step * R + r] = tok;
         hist_par[(long)step * R + r] = p;
+        if constexpr (SYNTAX) {
+          const smi::State os = smi::unpack(old_g[2 * lp], old_g[2 * lp + 1]);
+          smi::State nx = os;                                // a finished parent's state is carried unchanged
+          if (!pdone && !smi::step(os, tok, tok_info[tok], &nx)) { nx = os; nx.mode = smi::ERROR; }
+          gstate[2 * r] = smi::pack0(nx);
+          gstate[2 * r + 1] = smi::pack1(nx);
+        }
       }
       const float* trow = table + (long)tok * W;
       const float* brow = base + r * W;
@@ -1807,6 +1839,54 @@ static bool sample_filtered_args_ok(int dtype, int B, int V, int H, const void* 
   return true;
 }
 
+// what mvae_moses_beam_step refuses (MVAE_ERR_INVALID), shared with the syntax entry
+static bool beam_step_args_ok(int dtype, int B, int K, int V, int H, int layers, const void* state, int64_t ldh, const void* w_fc, int64_t ldw, int step,
+                              int eos_id, int pad_id, const float* table, int W, const float* base, const float* add_out, const float* score,
+                              const uint8_t* fin, const int64_t* ends, const int32_t* hist_tok, const int32_t* hist_par) {
+  if (!state || !w_fc || !table || !base || !add_out || !score || !fin || !ends || !hist_tok || !hist_par) return false;
+  if (dtype != MVAE_F32 && dtype != MVAE_BF16) return false;
+  if (B < 1 || V < 1 || H < 1 || layers < 1 || layers > MVAE_MAX_LAYERS || ldh < H || ldw < H || (W & 3) || W < 4 || step < 1) return false;
+  if (K < 1 || K > BEAM_KMAX || K > V) return false;
+  if (eos_id < 0 || eos_id >= V || pad_id < 0 || pad_id >= V) return false;
+  if ((reinterpret_cast<uintptr_t>(table) | reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(add_out)) & 15) return false;
+  return true;
+}
+
+// the launch behind mvae_moses_beam_step (SYNTAX = false) and mvae_moses_beam_syntax_step (true); the callers have checked
+template <bool SYNTAX>
+static int beam_step_launch(int dtype, int B, int K, int V, int H, int layers, void* state, int64_t layer_stride, int64_t half_stride, int64_t ldh,
+                            const void* w_fc, int64_t ldw, const float* bias, int step, int eos_id, int pad_id, const float* table, int W,
+                            const float* base, float* add_out, float* score, uint8_t* fin, int64_t* ends, int32_t* hist_tok, int32_t* hist_par,
+                            const int32_t* tok_info, int32_t* gstate, int max_len, void* stream) {
+  if (V > 64) return MVAE_ERR_UNSUPPORTED;                           // one class per lane
+  const size_t lds = (size_t)V * H * (dtype == MVAE_BF16 ? 2 : 4);
+  constexpr size_t lds_cap = 156 * 1024;                             // the CU's 160 KB less the kernel's static candidate arrays
+  if (lds > lds_cap) return MVAE_ERR_UNSUPPORTED;
+  if (lds > 64 * 1024) {                                              // above the default dynamic-LDS limit: opt in, as the sampler does
+    static std::atomic<bool> attr[64];                               // (per instantiation: the attribute is per kernel function)
+    int dev_id = 0;
+    MVAE_CHECK_HIP(hipGetDevice(&dev_id));
+    if (dev_id < 0 || dev_id >= 64 || !attr[dev_id].load(std::memory_order_acquire)) {
+      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(moses_beam_step_kernel<float, SYNTAX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
+      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(moses_beam_step_kernel<bf16_t, SYNTAX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
+      if (dev_id >= 0 && dev_id < 64) attr[dev_id].store(true, std::memory_order_release);
+    }
+  }
+  const int G = K >= 4 ? 1 : 4 / K;
+  int blocks = (B + G - 1) / G; if (blocks > 1024) blocks = 1024;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MVAE_BF16)
+    hipLaunchKernelGGL((moses_beam_step_kernel<bf16_t, SYNTAX>), dim3(blocks), dim3(256), lds, st, B, K, V, H, layers, (bf16_t*)state, (long)layer_stride,
+                       (long)half_stride, (long)ldh, (const bf16_t*)w_fc, (long)ldw, bias, step, eos_id, pad_id, table, W, base, add_out, score, fin,
+                       ends, hist_tok, hist_par, tok_info, gstate, max_len);
+  else
+    hipLaunchKernelGGL((moses_beam_step_kernel<float, SYNTAX>), dim3(blocks), dim3(256), lds, st, B, K, V, H, layers, (float*)state, (long)layer_stride,
+                       (long)half_stride, (long)ldh, (const float*)w_fc, (long)ldw, bias, step, eos_id, pad_id, table, W, base, add_out, score, fin,
+                       ends, hist_tok, hist_par, tok_info, gstate, max_len);
+  MVAE_CHECK_HIP(hipGetLastError());
+  return MVAE_OK;
+}
+
 // ------------------------------------------------------------------------------------------- extern "C" surface
 extern "C" {
 
@@ -2286,39 +2366,24 @@ int mvae_moses_beam_step(int dtype, int B, int K, int V, int H, int layers, void
                          const void* w_fc, int64_t ldw, const float* bias, int step, int eos_id, int pad_id, const float* table, int W,
                          const float* base, float* add_out, float* score, uint8_t* fin, int64_t* ends, int32_t* hist_tok, int32_t* hist_par,
                          void* stream) {
-  if (!state || !w_fc || !table || !base || !add_out || !score || !fin || !ends || !hist_tok || !hist_par) return MVAE_ERR_INVALID;
-  if (dtype != MVAE_F32 && dtype != MVAE_BF16) return MVAE_ERR_INVALID;
-  if (B < 1 || V < 1 || H < 1 || layers < 1 || layers > MVAE_MAX_LAYERS || ldh < H || ldw < H || (W & 3) || W < 4 || step < 1) return MVAE_ERR_INVALID;
-  if (K < 1 || K > BEAM_KMAX || K > V) return MVAE_ERR_INVALID;
-  if (eos_id < 0 || eos_id >= V || pad_id < 0 || pad_id >= V) return MVAE_ERR_INVALID;
-  if ((reinterpret_cast<uintptr_t>(table) | reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(add_out)) & 15) return MVAE_ERR_INVALID;
-  if (V > 64) return MVAE_ERR_UNSUPPORTED;                           // one class per lane
-  const size_t lds = (size_t)V * H * (dtype == MVAE_BF16 ? 2 : 4);
-  constexpr size_t lds_cap = 156 * 1024;                             // the CU's 160 KB less the kernel's static candidate arrays
-  if (lds > lds_cap) return MVAE_ERR_UNSUPPORTED;
-  if (lds > 64 * 1024) {                                              // above the default dynamic-LDS limit: opt in, as the sampler does
-    static std::atomic<bool> attr[64];
-    int dev_id = 0;
-    MVAE_CHECK_HIP(hipGetDevice(&dev_id));
-    if (dev_id < 0 || dev_id >= 64 || !attr[dev_id].load(std::memory_order_acquire)) {
-      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(moses_beam_step_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
-      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(moses_beam_step_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
-      if (dev_id >= 0 && dev_id < 64) attr[dev_id].store(true, std::memory_order_release);
-    }
-  }
-  const int G = K >= 4 ? 1 : 4 / K;
-  int blocks = (B + G - 1) / G; if (blocks > 1024) blocks = 1024;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == MVAE_BF16)
-    hipLaunchKernelGGL((moses_beam_step_kernel<bf16_t>), dim3(blocks), dim3(256), lds, st, B, K, V, H, layers, (bf16_t*)state, (long)layer_stride,
-                       (long)half_stride, (long)ldh, (const bf16_t*)w_fc, (long)ldw, bias, step, eos_id, pad_id, table, W, base, add_out, score, fin,
-                       ends, hist_tok, hist_par);
-  else
-    hipLaunchKernelGGL((moses_beam_step_kernel<float>), dim3(blocks), dim3(256), lds, st, B, K, V, H, layers, (float*)state, (long)layer_stride,
-                       (long)half_stride, (long)ldh, (const float*)w_fc, (long)ldw, bias, step, eos_id, pad_id, table, W, base, add_out, score, fin,
-                       ends, hist_tok, hist_par);
-  MVAE_CHECK_HIP(hipGetLastError());
-  return MVAE_OK;
+  if (!beam_step_args_ok(dtype, B, K, V, H, layers, state, ldh, w_fc, ldw, step, eos_id, pad_id, table, W, base, add_out, score, fin, ends, hist_tok,
+                         hist_par))
+    return MVAE_ERR_INVALID;
+  return beam_step_launch<false>(dtype, B, K, V, H, layers, state, layer_stride, half_stride, ldh, w_fc, ldw, bias, step, eos_id, pad_id, table, W,
+                                 base, add_out, score, fin, ends, hist_tok, hist_par, nullptr, nullptr, 0, stream);
+}
+
+int mvae_moses_beam_syntax_step(int dtype, int B, int K, int V, int H, int layers, void* state, int64_t layer_stride, int64_t half_stride,
+                                int64_t ldh, const void* w_fc, int64_t ldw, const float* bias, int step, int eos_id, int pad_id, const float* table,
+                                int W, const float* base, float* add_out, float* score, uint8_t* fin, int64_t* ends, int32_t* hist_tok,
+                                int32_t* hist_par, const int32_t* tok_info, int32_t* gstate, int max_len, void* stream) {
+  if (!beam_step_args_ok(dtype, B, K, V, H, layers, state, ldh, w_fc, ldw, step, eos_id, pad_id, table, W, base, add_out, score, fin, ends, hist_tok,
+                         hist_par))
+    return MVAE_ERR_INVALID;
+  if (!tok_info || !gstate || max_len < 3 || step < 1 || step >= max_len) return MVAE_ERR_INVALID;
+  if (eos_id < 0 || eos_id >= V) return MVAE_ERR_INVALID;
+  return beam_step_launch<true>(dtype, B, K, V, H, layers, state, layer_stride, half_stride, ldh, w_fc, ldw, bias, step, eos_id, pad_id, table, W,
+                                base, add_out, score, fin, ends, hist_tok, hist_par, tok_info, gstate, max_len, stream);
 }
 
 int mvae_moses_beam_finalize(int B, int K, int max_len, int bos_id, const int32_t* hist_tok, const int32_t* hist_par, const int64_t* ends,

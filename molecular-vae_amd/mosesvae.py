@@ -347,7 +347,7 @@ class VAE(_SavedState, nn.Module):
         """syntax=True needs max_len >= 3 (<bos>, one atom, <eos>) and a vocabulary the automaton can write an atom with: ValueError
         otherwise, before any device work (a CPU model reports it too)."""
         if int(max_len) < 3:
-            raise ValueError(f"sample: syntax=True needs max_len >= 3 (<bos>, an atom, <eos>), got {max_len}")
+            raise ValueError(f"sample / decode: syntax=True needs max_len >= 3 (<bos>, an atom, <eos>), got {max_len}")
         self._smiles_table(None)
 
     def _smiles_table(self, dev):
@@ -449,7 +449,7 @@ class VAE(_SavedState, nn.Module):
         return x, end_pads, logq, hsh
 
     @torch.no_grad()
-    def decode(self, z, beam_width=1, max_len=100, return_tokens=False):
+    def decode(self, z, beam_width=1, max_len=100, return_tokens=False, syntax=False):
         """Deterministic decoding of the latents z [B, d_z] by beam search (an addition: the reference only samples); beam_width=1 is greedy
         decoding.  The `sample()` loop with the beam launch in place of the sampling launch: per generated token one wavefront pass of the
         3-layer stack (T = 1) and ONE mvae_moses_beam_step launch, which also reorders the recurrent state to the surviving beams -- 4 launches
@@ -457,8 +457,17 @@ class VAE(_SavedState, nn.Module):
         its raw summed log-probability log p(tokens 1..end | z) (no length normalisation; the `pad` steps after <eos> add nothing); ties
         are broken by (parent beam, token id), so a decode is deterministic.  Dropout is never applied.
         Returns (best string per molecule, scores [B]); return_tokens=True: (per molecule, its beam_width id tensors cut at their ends --
-        bos first, <eos> last when it came -- best first, scores [B, beam_width])."""
-        ids, ends, scores = self._beam_search(z, beam_width, max_len)
+        bos first, <eos> last when it came -- best first, scores [B, beam_width]).
+        `syntax=True` (an addition) searches over well-formed SMILES strings only: the automaton of
+        sample(syntax=True) runs inside the beam launch (mvae_moses_beam_syntax_step, still 4 launches per token), and a beam proposes only
+        the tokens that keep its string well-formed and finishable within max_len.  The score is NOT renormalised over the allowed tokens:
+        it stays the model's log p(tokens | z) over all V classes -- the mask only removes candidates --, so `score` agrees with it and the
+        search returns the most probable well-formed strings the beam finds (sampling renormalises because it defines a distribution;
+        decoding does not).  Every returned string is then well-formed and ends in <eos> within max_len.  A molecule can have fewer than
+        beam_width well-formed continuations (beam_width = 16 at max_len = 3): with return_tokens=True a hypothesis whose score is -inf
+        is dead -- its tokens mean nothing -- and should be dropped by the caller; the best hypothesis is always finite.  Needs
+        max_len >= 3 (ValueError) and a vocabulary with an atom token.  syntax=False runs the launches it always ran."""
+        ids, ends, scores = self._beam_search(z, beam_width, max_len, syntax=syntax)
         xs, es = ids.cpu(), ends.cpu()
         B, K = es.shape
         if return_tokens:
@@ -466,8 +475,13 @@ class VAE(_SavedState, nn.Module):
         best, n = xs[:, 0].tolist(), es[:, 0].tolist()        # Python lists: per-row tensor indexing costs ~10 us a molecule
         return [self.vocabulary.ids2string(best[b][:n[b]], rem_bos=True, rem_eos=True) for b in range(B)], scores[:, 0]
 
-    def _beam_search(self, z, beam_width, max_len):
-        """decode() without the host side: (ids [B, K, max_len] int64, ends [B, K] int64, scores [B, K] fp32) on the device, best first."""
+    def _beam_search(self, z, beam_width, max_len, syntax=False):
+        """decode() without the host side: (ids [B, K, max_len] int64, ends [B, K] int64, scores [B, K] fp32) on the device, best first.
+        syntax=True issues mvae_moses_beam_syntax_step instead of mvae_moses_beam_step: every hypothesis with a finite score is a
+        well-formed SMILES string ending in <eos>; the scores stay log p(tokens | z) (no renormalisation); a score of -inf marks a dead
+        slot (fewer than K well-formed candidates), sorted last."""
+        if syntax:
+            self._check_syntax(max_len)
         V, dz = self.x_emb.num_embeddings, self.d_z
         K = int(beam_width)
         if not (1 <= K <= 16) or K > V:
@@ -504,13 +518,21 @@ class VAE(_SavedState, nn.Module):
         hist_tok = torch.empty((max_len, R), dtype=torch.int32, device=dev)          # row 0 (bos) is never read
         hist_par = torch.empty((max_len, R), dtype=torch.int32, device=dev)
         w = torch.full((R, 1), self.bos, dtype=torch.long, device=dev)
+        if syntax:
+            tok_info = self._smiles_table(dev)
+            gstate = torch.zeros((R, 2), dtype=torch.int32, device=dev)
+            gstate[:, 0] = self._SMI_START
         ops.gather_rows_tb(w, tbl4, add, R, 1, V, 4 * Hd, base=zp4)     # the <bos> input rows; later ones come out of the beam launch
         h_out, h_in, ldws = [state[l][1:2] for l in range(NL)], [state[l][0] for l in range(NL)], [pd["ldw"]] * NL    # fixed: no swap
         for i in range(1, max_len):
             ops.rnn_fwd(L.CELL_GRU, dt, 1, R, Hd, add, 0, pd["Wih"], ldws, pd["Whh"], ldws, pd["bias"], h_out, ldh, None, gates, hstate,
                         h0=h_in, ldh0=ldh, persist=False)
-            ops.moses_beam_step(state, ldh, P["Wfc"], self.decoder_fc.bias, i, self.eos, self.pad, tbl4, zp4, add, score, fin, ends,
-                                hist_tok, hist_par, B, K, V, Hd)
+            if syntax:
+                ops.moses_beam_syntax_step(state, ldh, P["Wfc"], self.decoder_fc.bias, i, self.eos, self.pad, tbl4, zp4, add, score, fin, ends,
+                                           hist_tok, hist_par, B, K, V, Hd, tok_info, gstate, max_len)
+            else:
+                ops.moses_beam_step(state, ldh, P["Wfc"], self.decoder_fc.bias, i, self.eos, self.pad, tbl4, zp4, add, score, fin, ends,
+                                    hist_tok, hist_par, B, K, V, Hd)
         ids = torch.empty((B, K, max_len), dtype=torch.long, device=dev)
         ends_out = torch.empty((B, K), dtype=torch.long, device=dev)
         scores = torch.empty((B, K), device=dev)

@@ -540,6 +540,19 @@ def moses_beam_step(state, ldh, w_fc, bias, step, eos_id, pad_id, table, base, a
           "mvae_moses_beam_step")
 
 
+def moses_beam_syntax_step(state, ldh, w_fc, bias, step, eos_id, pad_id, table, base, add_out, score, fin, ends, hist_tok, hist_par, B, K, V, H,
+                           tok_info, gstate, max_len):
+    """moses_beam_step over well-formed SMILES strings only: tok_info int32 [V] (vocab.smiles_token_table), gstate int32 [B*K, 2] the packed
+    automaton state of every beam row (reordered and advanced with the beams).  A row proposes only tokens the automaton takes and after
+    which the string can still be finished by step max_len - 1; the scores stay log-probabilities over all V classes -- one launch
+    (mvae_moses_beam_syntax_step)."""
+    check(L.load().mvae_moses_beam_syntax_step(dt_code(state.dtype), B, K, V, H, state.shape[0], ptr(state), state.stride(0), state.stride(1), ldh,
+                                               ptr(w_fc), w_fc.stride(0), ptr(bias), int(step), int(eos_id), int(pad_id), ptr(table),
+                                               table.shape[1], ptr(base), ptr(add_out), ptr(score), ptr(fin), ptr(ends), ptr(hist_tok),
+                                               ptr(hist_par), ptr(tok_info), ptr(gstate), int(max_len), stream_ptr()),
+          "mvae_moses_beam_syntax_step")
+
+
 def moses_beam_finalize(hist_tok, hist_par, ends, score, ids, ends_out, score_out, bos_id, B, K, max_len):
     """ids [B, K, max_len] int64 from the beam search's backpointers, in score order; ends / scores copied out (mvae_moses_beam_finalize)."""
     check(L.load().mvae_moses_beam_finalize(B, K, max_len, int(bos_id), ptr(hist_tok), ptr(hist_par), ptr(ends), ptr(score), ptr(ids),

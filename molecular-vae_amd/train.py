@@ -761,12 +761,15 @@ def moses_train_epoch(model, epoch, batches, kl_weight, optimizer=None, log_ever
 
 
 @torch.no_grad()
-def moses_reconstruction(model, batches, beam_width=1, max_len=100):
+def moses_reconstruction(model, batches, beam_width=1, max_len=100, syntax=False):
     """Reconstruction of a ``mosesvae.VAE`` (an addition: the reference only reports teacher-forced token accuracy): every batch (a list of
     id tensors, bos first, or a PaddedBatch) is encoded with eps = 0 (z = mu), decoded deterministically (``VAE.decode(z, beam_width,
     max_len)``, best hypothesis) and compared as a string with its input; ``VAE.score(x, mu)`` gives each molecule's log p(x | mu).
-    Returns (exact-match fraction, mean per-molecule log p(x | mu)) as Python floats; the host waits once, at the end."""
+    Returns (exact-match fraction, mean per-molecule log p(x | mu)) as Python floats; the host waits once, at the end.
+    ``syntax=True`` decodes over well-formed SMILES strings only (``VAE.decode(..., syntax=True)``); the log p(x | mu) term does not change."""
     from .vocab import PaddedBatch
+    if syntax:
+        model._check_syntax(max_len)                       # ValueError before any device work
     dev = model.device
     lp_sum, n = torch.zeros((), dtype=torch.float64, device=dev), 0
     kept = []
@@ -777,7 +780,7 @@ def moses_reconstruction(model, batches, beam_width=1, max_len=100):
             seqs = list(batch)
         B = len(seqs)
         mu, _, _ = model.forward_encoder(batch, eps=torch.zeros(B, model.d_z, device=dev))
-        ids, ends, _ = model._beam_search(mu, beam_width, max_len)
+        ids, ends, _ = model._beam_search(mu, beam_width, max_len, syntax=syntax)
         lp_sum += model.score(seqs, mu).double().sum()
         kept.append((seqs, ids[:, 0], ends[:, 0]))
         n += B
