@@ -40,6 +40,7 @@ ap.add_argument("--temp", default=1.0, type=float)
 ap.add_argument("--top_k", default=None, type=int)
 ap.add_argument("--top_p", default=None, type=float)
 ap.add_argument("--syntax", action="store_true", help="constrain every step to the tokens that keep the string well-formed SMILES")
+ap.add_argument("--prefix", default=None, metavar="STRING", help="every sample starts with this fragment; the model finishes the string")
 ap.add_argument("--prior", default="normal", choices=["normal", "zeros"], help="zeros = sample_z_prior as the reference is written")
 ap.add_argument("--seed", default=0, type=int)
 ap.add_argument("--log", default="log_small.csv")
@@ -102,7 +103,7 @@ with open(args.log, "w", buffering=1) as f:
     for r in range(args.rounds):
         res = mv.moses_generate(model, per_round, batch_size=args.batch_size, max_len=args.max_len, temp=args.temp, top_k=args.top_k,
                                 top_p=args.top_p, seed=args.seed + r * args.batches_per_round, syntax=args.syntax, count_valid=True,
-                                novel_against=corpus)
+                                novel_against=corpus, prefix=args.prefix)
         total += res["total"]
         syntax_valid += res["valid"]
         for i, (s, c) in enumerate(zip(res["strings"], res["counts"])):

@@ -603,6 +603,27 @@ int mvae_moses_sample_syntax_step(int dtype, int B, int V, int H, const void* h_
                                   const float* base, float* add_out, int64_t* x, int64_t x_ld, int64_t* end_pads, uint8_t* eos_mask,
                                   int64_t* w_out, float* logq /* [B] or NULL */, int64_t* hash /* [B] or NULL */, const int32_t* tok_info /* [V] */,
                                   int32_t* gstate /* [B, 2] */, int max_len, void* stream);
+/* Forced tokens in the sampling launch (prefix-constrained sampling, an addition): mvae_moses_sample_filtered_step (tok_info and gstate
+ * NULL: the automaton is off) or mvae_moses_sample_syntax_step (both given) with a table forced int32 [B, forced_ld], forced_ld > step.
+ * forced[b, step] in [0, V) is the token row b writes at this step instead of drawing one: no temperature, filter or mask is applied and
+ * no random draw is consumed (the draw of a free step stays u(b) = hash(seed, step * B + b)).  The token goes through the bookkeeping of a
+ * drawn one -- x[b, step] and end_pads / eos_mask unless the row had ended, hash[b] folded, gstate[b] advanced (mode ERROR if the automaton
+ * refuses the token), w_out[b], add_out[b] = table[token] + base[b] -- and adds NOTHING to logq[b].  Any other value (-1 by convention)
+ * leaves the row free: it gets, bit for bit, what the sibling launch writes.  Refused: what the sibling refuses (the syntax conditions only
+ * when tok_info is given), a NULL forced, forced_ld <= step, exactly one of tok_info / gstate NULL (MVAE_ERR_INVALID). */
+int mvae_moses_sample_forced_step(int dtype, int B, int V, int H, const void* h_top, int64_t ldh, const void* w_fc, int64_t ldw, const float* bias,
+                                  float temp, int top_k, float top_p, uint32_t seed, int step, int eos_id, const float* table, int W,
+                                  const float* base, float* add_out, int64_t* x, int64_t x_ld, int64_t* end_pads, uint8_t* eos_mask,
+                                  int64_t* w_out, float* logq /* [B] or NULL */, int64_t* hash /* [B] or NULL */,
+                                  const int32_t* tok_info /* [V] or NULL */, int32_t* gstate /* [B, 2] or NULL */, int max_len,
+                                  const int32_t* forced /* [B, forced_ld], -1 = free */, int64_t forced_ld, void* stream);
+/* mvae_smiles_prefix_state: one thread per row walks the automaton from its initial state over ids[b, 0 : lens[b]] (int32 [B, P], row
+ * stride ids_ld >= P; lens clamped to 0 .. P).  state [B, 2] = the packed state reached, need [B] = the tokens still required to finish
+ * the string from it (<eos> included), bad_pos [B] = the index of the first refused token (an id outside [0, V) is one), -1 if none; after
+ * a refusal the state is the one in front of the refused token with mode ERROR, and need is 0.  V <= 64. */
+int mvae_smiles_prefix_state(int B, int P, int V, const int32_t* ids, int64_t ids_ld, const int32_t* lens /* [B] */,
+                             const int32_t* tok_info /* [V] */, int32_t* state /* [B, 2] */, int32_t* need /* [B] */, int32_t* bad_pos /* [B] */,
+                             void* stream);
 int mvae_smiles_syntax_check(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */, int eos_id,
                              uint8_t* valid /* [B] */, int32_t* bad_pos /* [B] or NULL */, void* stream);
 /* Beam-search decoding (an addition beyond the reference, which only samples): R = B * K rows, molecule m owning rows m*K .. m*K + K-1.
@@ -643,6 +664,18 @@ int mvae_moses_beam_syntax_step(int dtype, int B, int K, int V, int H, int layer
                                 int64_t ldh, const void* w_fc, int64_t ldw, const float* bias, int step, int eos_id, int pad_id, const float* table,
                                 int W, const float* base, float* add_out, float* score, uint8_t* fin, int64_t* ends, int32_t* hist_tok,
                                 int32_t* hist_par, const int32_t* tok_info /* [V] */, int32_t* gstate /* [B*K, 2] */, int max_len, void* stream);
+/* Forced tokens in the beam launch (prefix-constrained decoding): mvae_moses_beam_step (tok_info and gstate NULL) or
+ * mvae_moses_beam_syntax_step (both given) with a table forced int32 [B, forced_ld], one row per MOLECULE, forced_ld > step.  With
+ * forced[m, step] in [0, V) every active beam of molecule m proposes exactly one candidate, that token at score + logp[token] (logp the
+ * log-softmax over all V classes: the score stays log p(tokens | z), prefix included); under the automaton the token is not masked, the
+ * state advances with it and a refused token puts it in ERROR.  The beams that were dead (-inf) stay dead through the forced steps and
+ * come alive at the first free one, as they do at step 1.  Any other value (-1) leaves the molecule free: bit for bit the sibling launch.
+ * Refused: what the sibling refuses, a NULL forced, forced_ld <= step, exactly one of tok_info / gstate NULL (MVAE_ERR_INVALID). */
+int mvae_moses_beam_forced_step(int dtype, int B, int K, int V, int H, int layers, void* state, int64_t layer_stride, int64_t half_stride,
+                                int64_t ldh, const void* w_fc, int64_t ldw, const float* bias, int step, int eos_id, int pad_id, const float* table,
+                                int W, const float* base, float* add_out, float* score, uint8_t* fin, int64_t* ends, int32_t* hist_tok,
+                                int32_t* hist_par, const int32_t* tok_info /* [V] or NULL */, int32_t* gstate /* [B*K, 2] or NULL */, int max_len,
+                                const int32_t* forced /* [B, forced_ld], -1 = free */, int64_t forced_ld, void* stream);
 int mvae_moses_beam_finalize(int B, int K, int max_len, int bos_id, const int32_t* hist_tok, const int32_t* hist_par, const int64_t* ends,
                              const float* score, int64_t* ids, int64_t* ends_out, float* score_out, void* stream);
 int mvae_ce_rows_fwd(int B, int T, int V, const float* logits, int64_t ldl, const int64_t* x, int pad, float* out, void* stream);

@@ -162,11 +162,16 @@ SIGNATURES = {
                                              _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvae_moses_sample_syntax_step": (_i, [_i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _f, _i, _f, C.c_uint32, _i, _i, _vp, _i, _vp, _vp, _vp, _i64,
                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "mvae_moses_sample_forced_step": (_i, [_i, _i, _i, _i, _vp, _i64, _vp, _i64, _vp, _f, _i, _f, C.c_uint32, _i, _i, _vp, _i, _vp, _vp, _vp, _i64,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp]),
+    "mvae_smiles_prefix_state": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvae_smiles_syntax_check": (_i, [_i, _i, _i, _vp, _i64, _vp, _i, _vp, _vp, _vp]),
     "mvae_moses_beam_step": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                   _vp, _vp]),
     "mvae_moses_beam_syntax_step": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp,
                                          _vp, _vp, _vp, _vp, _i, _vp]),
+    "mvae_moses_beam_forced_step": (_i, [_i, _i, _i, _i, _i, _i, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _i, _vp, _i64, _vp]),
     "mvae_moses_beam_finalize": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvae_ce_rows_fwd": (_i, [_i, _i, _i, _vp, _i64, _vp, _i, _vp, _vp]),
     "mvae_relu_bwd": (_i, [_i64, _vp, _vp, _vp]),

@@ -1026,7 +1026,13 @@ __global__ __launch_bounds__(256) void moses_sample_step_kernel(int B, int V, in
 // finished in the max_len - 1 - step tokens left after it -- before the softmax: the stabilising max runs over the allowed classes only (a
 // dominant illegal logit would underflow every legal one), e = 0 for the others, and the filters rank the legal classes among
 // themselves.  The drawn token then advances gstate[b].  Ended rows are neither masked nor advanced.
-template <typename T, bool SYNTAX>
+//
+// FORCED (mvae_moses_sample_forced_step; the other instantiations compile none of it): forced[b, step] >= 0 names the token row b writes at
+// this step instead of drawing one.  The value is read once per row, wave-uniform.  A forced row skips the head, the softmax, the mask and
+// the filter ranking; its token goes through the bookkeeping of a drawn one (x, end_pads / eos_mask, hash, gstate -- ERROR if the
+// automaton refuses it --, w_out, the next input row) and adds nothing to logq.  A free row (-1, or a value outside [0, V)) runs the code
+// of the other instantiations unchanged.
+template <typename T, bool SYNTAX, bool FORCED = false>
 __global__ __launch_bounds__(256) void moses_sample_filtered_step_kernel(int B, int V, int H, const T* __restrict__ h, long ldh, const T* __restrict__ wfc,
                                                                          long ldw, const float* __restrict__ bias, float inv_temp, int top_k, float top_p,
                                                                          uint32_t seed, int step, int eos_id, const float* __restrict__ table, int W,
@@ -1034,7 +1040,8 @@ __global__ __launch_bounds__(256) void moses_sample_filtered_step_kernel(int B, 
                                                                          int64_t* __restrict__ x, long x_ld, int64_t* __restrict__ end_pads,
                                                                          uint8_t* __restrict__ eos_mask, int64_t* __restrict__ w_out,
                                                                          float* __restrict__ logq, int64_t* __restrict__ hash,
-                                                                         const int32_t* __restrict__ tok_info, int32_t* __restrict__ gstate, int max_len) {
+                                                                         const int32_t* __restrict__ tok_info, int32_t* __restrict__ gstate, int max_len,
+                                                                         const int32_t* __restrict__ forced, long forced_ld) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   T* ws = reinterpret_cast<T*>(smem_raw);                    // [V][H]
   for (int i = threadIdx.x; i < V * H; i += 256) ws[i] = wfc[(long)(i / H) * ldw + (i % H)];
@@ -1044,6 +1051,34 @@ __global__ __launch_bounds__(256) void moses_sample_filtered_step_kernel(int B, 
   int32_t my_info = 0;
   if constexpr (SYNTAX) my_info = lane < V ? tok_info[lane] : 0;
   for (int b = blockIdx.x * 4 + wave; b < B; b += gridDim.x * 4) {
+    if constexpr (FORCED) {
+      const int fw = __builtin_amdgcn_readfirstlane(forced[(long)b * forced_ld + step]);
+      if (fw >= 0 && fw < V) {                               // wave-uniform: the whole row is forced
+        if (lane == 0) {
+          if (eos_mask[b] == 0) {
+            x[(long)b * x_ld + step] = fw;
+            if (fw == eos_id) { end_pads[b] = step + 1; eos_mask[b] = 1; }
+            if (hash) hash[b] = (int64_t)(((uint64_t)hash[b] ^ (uint64_t)fw) * 0x100000001b3ULL);
+            if constexpr (SYNTAX) {
+              const smi::State os = smi::unpack(gstate[2 * (long)b], gstate[2 * (long)b + 1]);
+              smi::State nx;
+              if (!smi::step(os, fw, tok_info[fw], &nx)) { nx = os; nx.mode = smi::ERROR; }
+              gstate[2 * (long)b] = smi::pack0(nx);
+              gstate[2 * (long)b + 1] = smi::pack1(nx);
+            }
+          }
+          w_out[b] = fw;
+        }
+        const float* trow = table + (long)fw * W;
+        const float* brow = base + (long)b * W;
+        float* orow = add_out + (long)b * W;
+        for (int cidx = lane * 4; cidx < W; cidx += 256) {
+          const float4 tv = *reinterpret_cast<const float4*>(trow + cidx), bv = *reinterpret_cast<const float4*>(brow + cidx);
+          *reinterpret_cast<float4*>(orow + cidx) = make_float4(tv.x + bv.x, tv.y + bv.y, tv.z + bv.z, tv.w + bv.w);
+        }
+        continue;
+      }
+    }
     float mine = -INFINITY;
     for (int v = 0; v < V; ++v) {
       float a = 0.f;
@@ -1146,6 +1181,23 @@ __global__ __launch_bounds__(64) void smiles_syntax_check_kernel(int B, int T, i
   if (bad_pos) bad_pos[b] = bad;
 }
 
+// The automaton over prefixes (smi::walk): one thread per row walks ids[b, 0 : len_b] from the initial state and writes the packed state it
+// reached, smi::need of it and the index of the first refused token (-1: none; the state is then in ERROR and need 0).
+__global__ __launch_bounds__(64) void smiles_prefix_state_kernel(int B, int P, int V, const int32_t* __restrict__ ids, long ids_ld,
+                                                                 const int32_t* __restrict__ lens, const int32_t* __restrict__ tok_info,
+                                                                 int32_t* __restrict__ state, int32_t* __restrict__ need, int32_t* __restrict__ bad_pos) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  int n = lens[b];
+  n = n < 0 ? 0 : (n > P ? P : n);
+  smi::State s;
+  const int bad = smi::walk(ids + (long)b * ids_ld, n, V, tok_info, &s);
+  state[2 * (long)b] = smi::pack0(s);
+  state[2 * (long)b + 1] = smi::pack1(s);
+  need[b] = smi::need(s);
+  bad_pos[b] = bad;
+}
+
 // ------------------------------------------------------------------------------------------- beam-search decoding step (no reference counterpart)
 // ONE launch per generated token for everything behind the GRU step, for R = B * K rows (molecule m owns rows m*K .. m*K + K-1, beam k of it
 // being row m*K + k):  logp = log_softmax(decoder_fc(h_top));  an active beam r proposes its own top-K tokens at score[r] + logp, a finished
@@ -1165,15 +1217,22 @@ __global__ __launch_bounds__(64) void smiles_syntax_check_kernel(int B, int T, i
 // still log p(tokens | z).  A molecule may be left with fewer than K candidates: a slot without one gets (-inf, parent 0, pad), its pad
 // token puts its automaton in ERROR, which allows nothing, so it stays dead.  Phase 1 reads the pass's old states into LDS, phase 3 writes
 // row r's new one: the parent's old state if the parent was finished, else step(parent's old state, token).
+//
+// FORCED (mvae_moses_beam_forced_step; the other instantiations compile none of it): forced[m, step] >= 0 names the token every hypothesis
+// of molecule m takes at this step.  The value is read once per row, wave-uniform.  An active row of such a molecule proposes exactly one
+// candidate, the forced token at score + logp[forced] -- unmasked under SYNTAX: the state advances with it in phase 3 and a refused token
+// puts it in ERROR --, so the beams that were dead (-inf) stay dead through the forced steps and come alive at the first free one, as they
+// do at step 1.  A molecule with -1 (or a value outside [0, V)) runs the code of the other instantiations unchanged.
 constexpr int BEAM_KMAX = 16;
-template <typename T, bool SYNTAX>
+template <typename T, bool SYNTAX, bool FORCED = false>
 __global__ __launch_bounds__(256) void moses_beam_step_kernel(int B, int K, int V, int H, int NL, T* __restrict__ state, long layer_stride,
                                                               long half_stride, long ldh, const T* __restrict__ wfc, long ldw,
                                                               const float* __restrict__ bias, int step, int eos_id, int pad_id,
                                                               const float* __restrict__ table, int W, const float* __restrict__ base,
                                                               float* __restrict__ add_out, float* __restrict__ score, uint8_t* __restrict__ fin,
                                                               int64_t* __restrict__ ends, int32_t* __restrict__ hist_tok, int32_t* __restrict__ hist_par,
-                                                              const int32_t* __restrict__ tok_info, int32_t* __restrict__ gstate, int max_len) {
+                                                              const int32_t* __restrict__ tok_info, int32_t* __restrict__ gstate, int max_len,
+                                                              const int32_t* __restrict__ forced, long forced_ld) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   T* ws = reinterpret_cast<T*>(smem_raw);                    // [V][H]
   __shared__ int32_t old_g[SYNTAX ? 2 * BEAM_KMAX : 1];      // SYNTAX: the automaton states the pass started from
@@ -1224,6 +1283,14 @@ __global__ __launch_bounds__(256) void moses_beam_step_kernel(int B, int K, int 
       const float se = wave_sum(lane < V ? expf(mine - mx) : 0.f);
       float c = s + (mine - (mx + logf(se)));
       if (c != c) c = -INFINITY;
+      if constexpr (FORCED) {
+        const int fw = __builtin_amdgcn_readfirstlane(forced[(long)(m0 + lr / K) * forced_ld + step]);
+        if (fw >= 0 && fw < V) {                             // wave-uniform: the one candidate of a forced row
+          const float cf = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c), fw));
+          if (lane == 0) { cand_s[lr * K] = cf; cand_t[lr * K] = fw; cand_n[lr] = 1; }
+          continue;
+        }
+      }
       bool avail = lane < V;
       int nc = K;                                            // K <= V: an available class is always left
       if constexpr (SYNTAX) {
@@ -1795,12 +1862,14 @@ __global__ __launch_bounds__(256) void onehot_tb_kernel(const int64_t* idx, int 
   }
 }
 
-// the launch behind mvae_moses_sample_filtered_step (SYNTAX = false) and mvae_moses_sample_syntax_step (true); the callers have checked
-template <bool SYNTAX>
+// the launch behind mvae_moses_sample_filtered_step (SYNTAX = false), mvae_moses_sample_syntax_step (true) and, with FORCED and either
+// SYNTAX, mvae_moses_sample_forced_step; the callers have checked
+template <bool SYNTAX, bool FORCED = false>
 static int sample_filtered_launch(int dtype, int B, int V, int H, const void* h_top, int64_t ldh, const void* w_fc, int64_t ldw, const float* bias,
                                   float temp, int top_k, float top_p, uint32_t seed, int step, int eos_id, const float* table, int W,
                                   const float* base, float* add_out, int64_t* x, int64_t x_ld, int64_t* end_pads, uint8_t* eos_mask,
-                                  int64_t* w_out, float* logq, int64_t* hash, const int32_t* tok_info, int32_t* gstate, int max_len, void* stream) {
+                                  int64_t* w_out, float* logq, int64_t* hash, const int32_t* tok_info, int32_t* gstate, int max_len, void* stream,
+                                  const int32_t* forced = nullptr, int64_t forced_ld = 0) {
   const size_t lds = (size_t)V * H * (dtype == MVAE_BF16 ? 2 : 4);
   if (lds > 160 * 1024) return MVAE_ERR_UNSUPPORTED;                 // the head must fit the CU's LDS, as in mvae_moses_sample_step
   if (lds > 64 * 1024) {                                              // above the default dynamic-LDS limit: opt in
@@ -1808,8 +1877,8 @@ static int sample_filtered_launch(int dtype, int B, int V, int H, const void* h_
     int dev_id = 0;
     MVAE_CHECK_HIP(hipGetDevice(&dev_id));
     if (dev_id < 0 || dev_id >= 64 || !attr[dev_id].load(std::memory_order_acquire)) {
-      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(moses_sample_filtered_step_kernel<float, SYNTAX>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(moses_sample_filtered_step_kernel<bf16_t, SYNTAX>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(moses_sample_filtered_step_kernel<float, SYNTAX, FORCED>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(moses_sample_filtered_step_kernel<bf16_t, SYNTAX, FORCED>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       if (dev_id >= 0 && dev_id < 64) attr[dev_id].store(true, std::memory_order_release);
     }
   }
@@ -1817,13 +1886,13 @@ static int sample_filtered_launch(int dtype, int B, int V, int H, const void* h_
   int blocks = (B + 3) / 4; if (blocks > 1024) blocks = 1024;
   hipStream_t st = (hipStream_t)stream;
   if (dtype == MVAE_BF16)
-    hipLaunchKernelGGL((moses_sample_filtered_step_kernel<bf16_t, SYNTAX>), dim3(blocks), dim3(256), lds, st, B, V, H, (const bf16_t*)h_top, (long)ldh,
+    hipLaunchKernelGGL((moses_sample_filtered_step_kernel<bf16_t, SYNTAX, FORCED>), dim3(blocks), dim3(256), lds, st, B, V, H, (const bf16_t*)h_top, (long)ldh,
                        (const bf16_t*)w_fc, (long)ldw, bias, 1.f / temp, top_k, top_p, seed, step, eos_id, table, W, base, add_out, x, (long)x_ld,
-                       end_pads, eos_mask, w_out, logq, hash, tok_info, gstate, max_len);
+                       end_pads, eos_mask, w_out, logq, hash, tok_info, gstate, max_len, forced, (long)forced_ld);
   else
-    hipLaunchKernelGGL((moses_sample_filtered_step_kernel<float, SYNTAX>), dim3(blocks), dim3(256), lds, st, B, V, H, (const float*)h_top, (long)ldh,
+    hipLaunchKernelGGL((moses_sample_filtered_step_kernel<float, SYNTAX, FORCED>), dim3(blocks), dim3(256), lds, st, B, V, H, (const float*)h_top, (long)ldh,
                        (const float*)w_fc, (long)ldw, bias, 1.f / temp, top_k, top_p, seed, step, eos_id, table, W, base, add_out, x, (long)x_ld,
-                       end_pads, eos_mask, w_out, logq, hash, tok_info, gstate, max_len);
+                       end_pads, eos_mask, w_out, logq, hash, tok_info, gstate, max_len, forced, (long)forced_ld);
   MVAE_CHECK_HIP(hipGetLastError());
   return MVAE_OK;
 }
@@ -1852,12 +1921,14 @@ static bool beam_step_args_ok(int dtype, int B, int K, int V, int H, int layers,
   return true;
 }
 
-// the launch behind mvae_moses_beam_step (SYNTAX = false) and mvae_moses_beam_syntax_step (true); the callers have checked
-template <bool SYNTAX>
+// the launch behind mvae_moses_beam_step (SYNTAX = false), mvae_moses_beam_syntax_step (true) and, with FORCED and either SYNTAX,
+// mvae_moses_beam_forced_step; the callers have checked
+template <bool SYNTAX, bool FORCED = false>
 static int beam_step_launch(int dtype, int B, int K, int V, int H, int layers, void* state, int64_t layer_stride, int64_t half_stride, int64_t ldh,
                             const void* w_fc, int64_t ldw, const float* bias, int step, int eos_id, int pad_id, const float* table, int W,
                             const float* base, float* add_out, float* score, uint8_t* fin, int64_t* ends, int32_t* hist_tok, int32_t* hist_par,
-                            const int32_t* tok_info, int32_t* gstate, int max_len, void* stream) {
+                            const int32_t* tok_info, int32_t* gstate, int max_len, void* stream, const int32_t* forced = nullptr,
+                            int64_t forced_ld = 0) {
   if (V > 64) return MVAE_ERR_UNSUPPORTED;                           // one class per lane
   const size_t lds = (size_t)V * H * (dtype == MVAE_BF16 ? 2 : 4);
   constexpr size_t lds_cap = 156 * 1024;                             // the CU's 160 KB less the kernel's static candidate arrays
@@ -1867,8 +1938,8 @@ static int beam_step_launch(int dtype, int B, int K, int V, int H, int layers, v
     int dev_id = 0;
     MVAE_CHECK_HIP(hipGetDevice(&dev_id));
     if (dev_id < 0 || dev_id >= 64 || !attr[dev_id].load(std::memory_order_acquire)) {
-      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(moses_beam_step_kernel<float, SYNTAX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
-      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(moses_beam_step_kernel<bf16_t, SYNTAX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
+      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(moses_beam_step_kernel<float, SYNTAX, FORCED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
+      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(moses_beam_step_kernel<bf16_t, SYNTAX, FORCED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cap));
       if (dev_id >= 0 && dev_id < 64) attr[dev_id].store(true, std::memory_order_release);
     }
   }
@@ -1876,13 +1947,13 @@ static int beam_step_launch(int dtype, int B, int K, int V, int H, int layers, v
   int blocks = (B + G - 1) / G; if (blocks > 1024) blocks = 1024;
   hipStream_t st = (hipStream_t)stream;
   if (dtype == MVAE_BF16)
-    hipLaunchKernelGGL((moses_beam_step_kernel<bf16_t, SYNTAX>), dim3(blocks), dim3(256), lds, st, B, K, V, H, layers, (bf16_t*)state, (long)layer_stride,
+    hipLaunchKernelGGL((moses_beam_step_kernel<bf16_t, SYNTAX, FORCED>), dim3(blocks), dim3(256), lds, st, B, K, V, H, layers, (bf16_t*)state, (long)layer_stride,
                        (long)half_stride, (long)ldh, (const bf16_t*)w_fc, (long)ldw, bias, step, eos_id, pad_id, table, W, base, add_out, score, fin,
-                       ends, hist_tok, hist_par, tok_info, gstate, max_len);
+                       ends, hist_tok, hist_par, tok_info, gstate, max_len, forced, (long)forced_ld);
   else
-    hipLaunchKernelGGL((moses_beam_step_kernel<float, SYNTAX>), dim3(blocks), dim3(256), lds, st, B, K, V, H, layers, (float*)state, (long)layer_stride,
+    hipLaunchKernelGGL((moses_beam_step_kernel<float, SYNTAX, FORCED>), dim3(blocks), dim3(256), lds, st, B, K, V, H, layers, (float*)state, (long)layer_stride,
                        (long)half_stride, (long)ldh, (const float*)w_fc, (long)ldw, bias, step, eos_id, pad_id, table, W, base, add_out, score, fin,
-                       ends, hist_tok, hist_par, tok_info, gstate, max_len);
+                       ends, hist_tok, hist_par, tok_info, gstate, max_len, forced, (long)forced_ld);
   MVAE_CHECK_HIP(hipGetLastError());
   return MVAE_OK;
 }
@@ -2354,6 +2425,33 @@ int mvae_moses_sample_syntax_step(int dtype, int B, int V, int H, const void* h_
                                       x, x_ld, end_pads, eos_mask, w_out, logq, hash, tok_info, gstate, max_len, stream);
 }
 
+int mvae_moses_sample_forced_step(int dtype, int B, int V, int H, const void* h_top, int64_t ldh, const void* w_fc, int64_t ldw, const float* bias,
+                                  float temp, int top_k, float top_p, uint32_t seed, int step, int eos_id, const float* table, int W,
+                                  const float* base, float* add_out, int64_t* x, int64_t x_ld, int64_t* end_pads, uint8_t* eos_mask,
+                                  int64_t* w_out, float* logq, int64_t* hash, const int32_t* tok_info, int32_t* gstate, int max_len,
+                                  const int32_t* forced, int64_t forced_ld, void* stream) {
+  if (!sample_filtered_args_ok(dtype, B, V, H, h_top, w_fc, temp, top_k, top_p, step, table, W, base, add_out, x, end_pads, eos_mask, w_out))
+    return MVAE_ERR_INVALID;
+  if (!forced || forced_ld <= step) return MVAE_ERR_INVALID;
+  if (!tok_info != !gstate) return MVAE_ERR_INVALID;                 // both or neither: NULL turns the automaton off
+  if (!tok_info)
+    return sample_filtered_launch<false, true>(dtype, B, V, H, h_top, ldh, w_fc, ldw, bias, temp, top_k, top_p, seed, step, eos_id, table, W, base,
+                                               add_out, x, x_ld, end_pads, eos_mask, w_out, logq, hash, nullptr, nullptr, 0, stream, forced, forced_ld);
+  if (max_len < 3 || step < 1 || step >= max_len) return MVAE_ERR_INVALID;
+  if (eos_id < 0 || eos_id >= V) return MVAE_ERR_INVALID;
+  return sample_filtered_launch<true, true>(dtype, B, V, H, h_top, ldh, w_fc, ldw, bias, temp, top_k, top_p, seed, step, eos_id, table, W, base,
+                                            add_out, x, x_ld, end_pads, eos_mask, w_out, logq, hash, tok_info, gstate, max_len, stream, forced, forced_ld);
+}
+
+int mvae_smiles_prefix_state(int B, int P, int V, const int32_t* ids, int64_t ids_ld, const int32_t* lens, const int32_t* tok_info, int32_t* state,
+                             int32_t* need, int32_t* bad_pos, void* stream) {
+  if (!ids || !lens || !tok_info || !state || !need || !bad_pos || B < 1 || P < 0 || V < 1 || V > 64 || ids_ld < P) return MVAE_ERR_INVALID;
+  hipLaunchKernelGGL(smiles_prefix_state_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, P, V, ids, (long)ids_ld, lens, tok_info,
+                     state, need, bad_pos);
+  MVAE_CHECK_HIP(hipGetLastError());
+  return MVAE_OK;
+}
+
 int mvae_smiles_syntax_check(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, int eos_id, uint8_t* valid, int32_t* bad_pos,
                              void* stream) {
   if (!x || !tok_info || !valid || B < 1 || T < 1 || V < 1 || V > 64 || x_ld < T || eos_id < 0 || eos_id >= V) return MVAE_ERR_INVALID;
@@ -2384,6 +2482,24 @@ int mvae_moses_beam_syntax_step(int dtype, int B, int K, int V, int H, int layer
   if (eos_id < 0 || eos_id >= V) return MVAE_ERR_INVALID;
   return beam_step_launch<true>(dtype, B, K, V, H, layers, state, layer_stride, half_stride, ldh, w_fc, ldw, bias, step, eos_id, pad_id, table, W,
                                 base, add_out, score, fin, ends, hist_tok, hist_par, tok_info, gstate, max_len, stream);
+}
+
+int mvae_moses_beam_forced_step(int dtype, int B, int K, int V, int H, int layers, void* state, int64_t layer_stride, int64_t half_stride,
+                                int64_t ldh, const void* w_fc, int64_t ldw, const float* bias, int step, int eos_id, int pad_id, const float* table,
+                                int W, const float* base, float* add_out, float* score, uint8_t* fin, int64_t* ends, int32_t* hist_tok,
+                                int32_t* hist_par, const int32_t* tok_info, int32_t* gstate, int max_len, const int32_t* forced, int64_t forced_ld,
+                                void* stream) {
+  if (!beam_step_args_ok(dtype, B, K, V, H, layers, state, ldh, w_fc, ldw, step, eos_id, pad_id, table, W, base, add_out, score, fin, ends, hist_tok,
+                         hist_par))
+    return MVAE_ERR_INVALID;
+  if (!forced || forced_ld <= step) return MVAE_ERR_INVALID;
+  if (!tok_info != !gstate) return MVAE_ERR_INVALID;                 // both or neither: NULL turns the automaton off
+  if (!tok_info)
+    return beam_step_launch<false, true>(dtype, B, K, V, H, layers, state, layer_stride, half_stride, ldh, w_fc, ldw, bias, step, eos_id, pad_id,
+                                         table, W, base, add_out, score, fin, ends, hist_tok, hist_par, nullptr, nullptr, 0, stream, forced, forced_ld);
+  if (max_len < 3 || step >= max_len) return MVAE_ERR_INVALID;
+  return beam_step_launch<true, true>(dtype, B, K, V, H, layers, state, layer_stride, half_stride, ldh, w_fc, ldw, bias, step, eos_id, pad_id, table,
+                                      W, base, add_out, score, fin, ends, hist_tok, hist_par, tok_info, gstate, max_len, stream, forced, forced_ld);
 }
 
 int mvae_moses_beam_finalize(int B, int K, int max_len, int bos_id, const int32_t* hist_tok, const int32_t* hist_par, const int64_t* ends,

@@ -98,4 +98,19 @@ SMI_HD int need(const State& s) {
   return pre + n + extra + s.depth + 1;
 }
 
+// The automaton over a prefix: toks[0 .. n) from the initial state.  Returns the index of the first refused token (an id outside [0, V) is
+// one), -1 when every token is taken.  *out = the state reached; after a refusal the state in front of the refused token, its mode ERROR.
+SMI_HD int walk(const int32_t* toks, int n, int V, const int32_t* tok_info, State* out) {
+  State s{START, 0, NO_PREV, 0, 0};
+  int bad = -1;
+  for (int t = 0; t < n; ++t) {
+    const int tok = toks[t];
+    State nx;
+    if (tok < 0 || tok >= V || !step(s, tok, tok_info[tok], &nx)) { bad = t; s.mode = ERROR; break; }
+    s = nx;
+  }
+  *out = s;
+  return bad;
+}
+
 }  // namespace smi

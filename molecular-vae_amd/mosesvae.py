@@ -286,7 +286,7 @@ class VAE(_SavedState, nn.Module):
 
     @torch.no_grad()
     def sample(self, n_batch, max_len=100, z=None, temp=1.0, return_tokens=False, seed=None, top_k=None, top_p=None, return_logp=False,
-               syntax=False):
+               syntax=False, prefix=None):
         """mosesvae.py:214-262 (autoregressive decoding, multinomial sampling at temperature `temp`) on the GRU step kernels: per generated token
         one wavefront pass of the 3-layer stack (T = 1) and ONE sampling launch (head GEMV + softmax + multinomial + eos / end-pad bookkeeping +
         the next token's input rows: mvae_moses_sample_step) -- 4 launches per token, no torch arithmetic in the loop.  Randomness is explicit:
@@ -304,10 +304,22 @@ class VAE(_SavedState, nn.Module):
         bracket-atom grammar -- syntax only, valence and aromaticity stay unchecked.  The mask sits in front of the softmax inside the
         sampling launch (mvae_moses_sample_syntax_step, still 4 launches per token); top_k / top_p then act on the legal tokens and logq
         is that of the constrained distribution.  Every row then ends in <eos>.  Needs max_len >= 3 (ValueError) and a vocabulary with an
-        atom token."""
+        atom token.
+        `prefix` (an addition) keeps a fragment and lets the model finish the string: the tokens that follow <bos>,
+        as one string or 1-D id tensor (without <bos> / <eos>) for every row, or a list of n_batch of them (an empty entry leaves its row
+        unconstrained).  Row b writes its P_b prefix tokens at steps 1 .. P_b -- no temperature, filter or mask, no random draw consumed --
+        and steps P_b + 1 .. run as they always do, inside the same launches (mvae_moses_sample_forced_step, still 4 launches per token).
+        logq is then the log-probability of the FREE tokens given the prefix (a forced token adds nothing); `score` gives log p of the
+        whole string.  The draw of a free step depends on (seed, step, row) alone, so a sample replayed with its own leading tokens as the
+        prefix returns the same row, bit for bit.  ValueError, before any device work: a list of another length than n_batch, a character
+        outside the vocabulary, an id outside [0, V) or one of <bos> / <eos> / <pad>, more than max_len - 2 prefix tokens.  With
+        syntax=True the prefixes are walked by the automaton first (mvae_smiles_prefix_state, one host synchronisation before the loop):
+        ValueError names the first row and position whose token it refuses, or whose prefix leaves too little room to finish the string
+        within max_len; every row is then well-formed and ends in <eos>, prefix included.  prefix=None runs the launches it always ran."""
         top_k, top_p = self._check_filters(top_k, top_p)
         if syntax:
             self._check_syntax(max_len)
+        forced = self._prefix_table(prefix, n_batch, max_len, "sample")
         dev = self.device
         _require_cuda(dev, "mosesvae.VAE.sample")
         if z is None:
@@ -315,7 +327,7 @@ class VAE(_SavedState, nn.Module):
         if seed is None:
             seed = int(torch.randint(0, 2 ** 31 - 1, (1,)))
         filtered = top_k > 0 or top_p < 1.0 or return_logp
-        x, end_pads, logq, _ = self._sample_tokens(z[:n_batch], max_len, temp, seed, top_k, top_p, filtered=filtered, syntax=syntax)
+        x, end_pads, logq, _ = self._sample_tokens(z[:n_batch], max_len, temp, seed, top_k, top_p, filtered=filtered, syntax=syntax, forced=forced)
         xs, ends = x.cpu(), end_pads.cpu()
         if return_tokens:                                                # raw id tensors (specials included), for tests / downstream scoring
             out = [xs[b, :ends[b]] for b in range(n_batch)]
@@ -349,6 +361,73 @@ class VAE(_SavedState, nn.Module):
         if int(max_len) < 3:
             raise ValueError(f"sample / decode: syntax=True needs max_len >= 3 (<bos>, an atom, <eos>), got {max_len}")
         self._smiles_table(None)
+
+    def _prefix_table(self, prefix, n, max_len, what):
+        """`prefix` of sample / decode / moses_generate as the forced launches take it: None for None, else (table, lens) on the host --
+        table int32 [n, max_len] ([1, max_len] for one prefix broadcast to all rows), table[b, 1 : 1 + P_b] = the prefix ids and -1 (free)
+        everywhere else, step 0 (<bos>) included; lens int32 [n] or [1] = P_b.  Raises the ValueErrors of the docstrings, before any
+        device work."""
+        if prefix is None:
+            return None
+        V, max_len = self.x_emb.num_embeddings, int(max_len)
+        if isinstance(prefix, str) or torch.is_tensor(prefix):
+            entries = [prefix]
+        else:
+            entries = list(prefix)
+            if len(entries) != n:
+                raise ValueError(f"{what}: prefix must be one string / id tensor or a list of {n} of them, got {len(entries)}")
+        table = torch.full((len(entries), max(max_len, 1)), -1, dtype=torch.int32)
+        lens = torch.zeros(len(entries), dtype=torch.int32)
+        for b, e in enumerate(entries):
+            if isinstance(e, str):
+                bad = [ch for ch in e if ch not in self.vocabulary.c2i]
+                if bad:
+                    raise ValueError(f"{what}: prefix of row {b}: character {bad[0]!r} is not in the vocabulary")
+                ids = self.vocabulary.string2ids(e)
+            else:
+                t = torch.as_tensor(e)
+                if t.dim() != 1 or t.dtype.is_floating_point or t.dtype == torch.bool:
+                    raise ValueError(f"{what}: prefix of row {b} must be a string or a 1-D integer id tensor, got {tuple(t.shape)} {t.dtype}")
+                ids = [int(i) for i in t.tolist()]
+            for pos, i in enumerate(ids):
+                if not 0 <= i < V or i in (self.bos, self.eos, self.pad):
+                    raise ValueError(f"{what}: prefix of row {b}, position {pos}: id {i} is outside [0, {V}) or one of <bos> / <eos> / <pad>")
+            if len(ids) > max(max_len - 2, 0):
+                raise ValueError(f"{what}: prefix of row {b} has {len(ids)} tokens, max_len = {max_len} leaves room for {max(max_len - 2, 0)} "
+                                 f"(<bos> and one more token are needed)")
+            if ids:
+                table[b, 1:1 + len(ids)] = torch.tensor(ids, dtype=torch.int32)
+                lens[b] = len(ids)
+        return table, lens
+
+    def _check_prefix_syntax(self, forced, max_len, what):
+        """The automaton over the prefixes of _prefix_table's (table, lens), all rows at once: one mvae_smiles_prefix_state launch and one
+        host synchronisation.  ValueError naming the first row and position whose token the automaton refuses, or whose prefix leaves too
+        few steps to finish the string within max_len."""
+        table, lens = forced
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE." + what)
+        n, max_len = table.shape[0], int(max_len)
+        state = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        res = torch.empty((2, n), dtype=torch.int32, device=dev)                  # need, bad_pos
+        ops.smiles_prefix_state(table.to(dev)[:, 1:], lens.to(dev), self._smiles_table(dev), state, res[0], res[1])
+        res = res.cpu()
+        wrong = torch.nonzero((res[1] >= 0) | (res[0] > max_len - 1 - lens))
+        if wrong.numel():
+            b = int(wrong[0])
+            need, bad, P = int(res[0, b]), int(res[1, b]), int(lens[b])
+            if bad >= 0:
+                raise ValueError(f"{what}: syntax=True: prefix of row {b}, position {bad}: token "
+                                 f"{self.vocabulary.id2char(int(table[b, 1 + bad]))!r} is refused by the SMILES automaton")
+            raise ValueError(f"{what}: syntax=True: prefix of row {b}, position {P}: the string needs {need} more tokens "
+                             f"(<eos> included), max_len = {max_len} leaves {max_len - 1 - P}")
+
+    def _forced_rows(self, forced, B, max_len, dev, what):
+        """_prefix_table's (table, lens) on the device as int32 [B, max_len] (a broadcast prefix expanded)."""
+        table = forced[0]
+        if table.shape[0] not in (1, B) or table.shape[1] != max_len:
+            raise ValueError(f"{what}: the prefix table is {tuple(table.shape)}, the batch needs [{B}, {max_len}]")
+        return table.to(dev).expand(B, -1).contiguous()
 
     def _smiles_table(self, dev):
         """vocab.smiles_token_table: built once per model on the host (dev None), its device copy cached in the pack."""
@@ -390,11 +469,14 @@ class VAE(_SavedState, nn.Module):
 
     _FNV_BASIS = -3750763034362895579       # 0xcbf29ce484222325, the 64-bit FNV-1a offset basis, as an int64
 
-    def _sample_tokens(self, z, max_len, temp, seed, top_k=0, top_p=1.0, filtered=True, syntax=False):
+    def _sample_tokens(self, z, max_len, temp, seed, top_k=0, top_p=1.0, filtered=True, syntax=False, forced=None, check_prefix=True):
         """The sampling loop without the host side: (x [B, max_len] int64 -- bos first, pad after each end --, ends [B] int64, logq [B] fp32,
         hash [B] int64: FNV-1a over x[b, 1 : end]) on the device.  top_k (0: off) / top_p (1.0: off) as _check_filters returns them.
         filtered=False issues mvae_moses_sample_step instead (sample()'s default path) and returns None for logq and hash.  syntax=True
-        issues mvae_moses_sample_syntax_step (the filtered launch under the SMILES automaton; filtered is then implied)."""
+        issues mvae_moses_sample_syntax_step (the filtered launch under the SMILES automaton; filtered is then implied).  forced
+        (_prefix_table's result, rows for this batch) issues mvae_moses_sample_forced_step in place of any of the three: the rows write
+        their prefix tokens first; logq and hash stay None with filtered=False.  With syntax the prefixes are walked by the automaton
+        first (_check_prefix_syntax) unless the caller has done so for all its batches (check_prefix=False)."""
         if syntax:
             self._check_syntax(max_len)
             filtered = True                                               # logq and hash come with it
@@ -431,12 +513,20 @@ class VAE(_SavedState, nn.Module):
             tok_info = self._smiles_table(dev)
             gstate = torch.zeros((B, 2), dtype=torch.int32, device=dev)
             gstate[:, 0] = self._SMI_START
+        if forced is not None:
+            if syntax and check_prefix:
+                self._check_prefix_syntax(forced, max_len, "sample")
+            ftab = self._forced_rows(forced, B, max_len, dev, "sample")
         ops.gather_rows_tb(w.view(B, 1), tbl4, add, B, 1, V, 4 * Hd, base=zp4)      # the <bos> input rows; later ones come out of the sampling launch
         cur = 0
         for i in range(1, max_len):
             ops.rnn_fwd(L.CELL_GRU, dt, 1, B, Hd, add, 0, pd["Wih"], [pd["ldw"]] * NL, pd["Whh"], [pd["ldw"]] * NL, pd["bias"],
                         [h[1 - cur:2 - cur] for h in hbuf], ldh, None, gates, hstate, h0=[h[cur] for h in hbuf], ldh0=ldh, persist=False)
-            if syntax:
+            if forced is not None:
+                ops.moses_sample_forced_step(hbuf[-1][1 - cur], ldh, P["Wfc"], self.decoder_fc.bias, temp, top_k, top_p, seed, i, self.eos, tbl4,
+                                             zp4, add, x, end_pads, eos_mask, w, B, V, Hd, ftab, tok_info=tok_info if syntax else None,
+                                             gstate=gstate if syntax else None, max_len=max_len, logq=logq, hash=hsh)
+            elif syntax:
                 ops.moses_sample_syntax_step(hbuf[-1][1 - cur], ldh, P["Wfc"], self.decoder_fc.bias, temp, top_k, top_p, seed, i, self.eos, tbl4,
                                              zp4, add, x, end_pads, eos_mask, w, B, V, Hd, tok_info, gstate, max_len, logq=logq, hash=hsh)
             elif filtered:
@@ -449,7 +539,7 @@ class VAE(_SavedState, nn.Module):
         return x, end_pads, logq, hsh
 
     @torch.no_grad()
-    def decode(self, z, beam_width=1, max_len=100, return_tokens=False, syntax=False):
+    def decode(self, z, beam_width=1, max_len=100, return_tokens=False, syntax=False, prefix=None):
         """Deterministic decoding of the latents z [B, d_z] by beam search (an addition: the reference only samples); beam_width=1 is greedy
         decoding.  The `sample()` loop with the beam launch in place of the sampling launch: per generated token one wavefront pass of the
         3-layer stack (T = 1) and ONE mvae_moses_beam_step launch, which also reorders the recurrent state to the surviving beams -- 4 launches
@@ -466,8 +556,14 @@ class VAE(_SavedState, nn.Module):
         decoding does not).  Every returned string is then well-formed and ends in <eos> within max_len.  A molecule can have fewer than
         beam_width well-formed continuations (beam_width = 16 at max_len = 3): with return_tokens=True a hypothesis whose score is -inf
         is dead -- its tokens mean nothing -- and should be dropped by the caller; the best hypothesis is always finite.  Needs
-        max_len >= 3 (ValueError) and a vocabulary with an atom token.  syntax=False runs the launches it always ran."""
-        ids, ends, scores = self._beam_search(z, beam_width, max_len, syntax=syntax)
+        max_len >= 3 (ValueError) and a vocabulary with an atom token.  syntax=False runs the launches it always ran.
+        `prefix` (an addition) searches the completions of a fragment: one prefix for every molecule or a list of
+        B of them, in the forms and with the ValueErrors of `sample(prefix=)`.  At steps 1 .. P_b every live beam of molecule b proposes
+        exactly one candidate, the prefix token, at score + log p(token) (mvae_moses_beam_forced_step, still 4 launches per token): the
+        scores stay log p(tokens | z) of the whole string, prefix included, so `score` keeps agreeing with them; beams 1 .. K-1 stay dead
+        through the prefix and come alive at the first free step.  With syntax=True the prefixes are checked by the automaton before the
+        loop as in `sample`.  prefix=None runs the launches it always ran."""
+        ids, ends, scores = self._beam_search(z, beam_width, max_len, syntax=syntax, prefix=prefix)
         xs, es = ids.cpu(), ends.cpu()
         B, K = es.shape
         if return_tokens:
@@ -475,11 +571,11 @@ class VAE(_SavedState, nn.Module):
         best, n = xs[:, 0].tolist(), es[:, 0].tolist()        # Python lists: per-row tensor indexing costs ~10 us a molecule
         return [self.vocabulary.ids2string(best[b][:n[b]], rem_bos=True, rem_eos=True) for b in range(B)], scores[:, 0]
 
-    def _beam_search(self, z, beam_width, max_len, syntax=False):
+    def _beam_search(self, z, beam_width, max_len, syntax=False, prefix=None):
         """decode() without the host side: (ids [B, K, max_len] int64, ends [B, K] int64, scores [B, K] fp32) on the device, best first.
         syntax=True issues mvae_moses_beam_syntax_step instead of mvae_moses_beam_step: every hypothesis with a finite score is a
         well-formed SMILES string ending in <eos>; the scores stay log p(tokens | z) (no renormalisation); a score of -inf marks a dead
-        slot (fewer than K well-formed candidates), sorted last."""
+        slot (fewer than K well-formed candidates), sorted last.  prefix (decode's) issues mvae_moses_beam_forced_step in place of either."""
         if syntax:
             self._check_syntax(max_len)
         V, dz = self.x_emb.num_embeddings, self.d_z
@@ -490,6 +586,7 @@ class VAE(_SavedState, nn.Module):
             raise ValueError(f"decode: max_len must be >= 1, got {max_len}")
         if z.dim() != 2 or z.shape[1] != dz or z.shape[0] < 1:
             raise ValueError(f"decode: z must be [B, {dz}], got {tuple(z.shape)}")
+        forced = self._prefix_table(prefix, z.shape[0], max_len, "decode")
         dev = self.device
         _require_cuda(dev, "mosesvae.VAE.decode")
         max_len = int(max_len)
@@ -522,12 +619,20 @@ class VAE(_SavedState, nn.Module):
             tok_info = self._smiles_table(dev)
             gstate = torch.zeros((R, 2), dtype=torch.int32, device=dev)
             gstate[:, 0] = self._SMI_START
+        if forced is not None:
+            if syntax:
+                self._check_prefix_syntax(forced, max_len, "decode")
+            ftab = self._forced_rows(forced, B, max_len, dev, "decode")
         ops.gather_rows_tb(w, tbl4, add, R, 1, V, 4 * Hd, base=zp4)     # the <bos> input rows; later ones come out of the beam launch
         h_out, h_in, ldws = [state[l][1:2] for l in range(NL)], [state[l][0] for l in range(NL)], [pd["ldw"]] * NL    # fixed: no swap
         for i in range(1, max_len):
             ops.rnn_fwd(L.CELL_GRU, dt, 1, R, Hd, add, 0, pd["Wih"], ldws, pd["Whh"], ldws, pd["bias"], h_out, ldh, None, gates, hstate,
                         h0=h_in, ldh0=ldh, persist=False)
-            if syntax:
+            if forced is not None:
+                ops.moses_beam_forced_step(state, ldh, P["Wfc"], self.decoder_fc.bias, i, self.eos, self.pad, tbl4, zp4, add, score, fin, ends,
+                                           hist_tok, hist_par, B, K, V, Hd, ftab, tok_info=tok_info if syntax else None,
+                                           gstate=gstate if syntax else None, max_len=max_len)
+            elif syntax:
                 ops.moses_beam_syntax_step(state, ldh, P["Wfc"], self.decoder_fc.bias, i, self.eos, self.pad, tbl4, zp4, add, score, fin, ends,
                                            hist_tok, hist_par, B, K, V, Hd, tok_info, gstate, max_len)
             else:

@@ -522,6 +522,27 @@ def moses_sample_syntax_step(h_top, ldh, w_fc, bias, temp, top_k, top_p, seed, s
           "mvae_moses_sample_syntax_step")
 
 
+def moses_sample_forced_step(h_top, ldh, w_fc, bias, temp, top_k, top_p, seed, step, eos_id, table, base, add_out, x, end_pads, eos_mask, w_out,
+                             B, V, H, forced, tok_info=None, gstate=None, max_len=0, logq=None, hash=None):
+    """moses_sample_filtered_step (tok_info / gstate None) or moses_sample_syntax_step with forced tokens: forced int32 [B, >= step + 1],
+    forced[b, step] >= 0 is written in place of a drawn token -- bookkeeping, hash and automaton state as for a drawn one, nothing added
+    to logq --, -1 leaves the row to the draw of the sibling launch -- one launch (mvae_moses_sample_forced_step)."""
+    check(L.load().mvae_moses_sample_forced_step(dt_code(h_top.dtype), B, V, H, ptr(h_top), ldh, ptr(w_fc), w_fc.stride(0), ptr(bias), float(temp),
+                                                 int(top_k), float(top_p), int(seed) & 0xFFFFFFFF, int(step), int(eos_id), ptr(table),
+                                                 table.shape[1], ptr(base), ptr(add_out), ptr(x), x.stride(0), ptr(end_pads), ptr(eos_mask),
+                                                 ptr(w_out), ptr(logq), ptr(hash), ptr(tok_info), ptr(gstate), int(max_len), ptr(forced),
+                                                 forced.stride(0), stream_ptr()), "mvae_moses_sample_forced_step")
+
+
+def smiles_prefix_state(ids, lens, tok_info, state, need, bad_pos):
+    """The SMILES automaton over prefixes: ids int32 [B, P] (any row stride), lens int32 [B]; per row the packed state int32 [B, 2] reached
+    after ids[b, :lens[b]], need [B] int32 = the tokens still required to finish from it (<eos> included) and bad_pos [B] int32 = the index
+    of the first refused token, -1 if none (mvae_smiles_prefix_state)."""
+    B, P = ids.shape
+    check(L.load().mvae_smiles_prefix_state(B, P, tok_info.numel(), ptr(ids), ids.stride(0), ptr(lens), ptr(tok_info), ptr(state), ptr(need),
+                                            ptr(bad_pos), stream_ptr()), "mvae_smiles_prefix_state")
+
+
 def smiles_syntax_check(x, tok_info, eos_id, valid, bad_pos=None):
     """valid [B] uint8 = 1 where the token row x[b] (int64 [B, T], bos first) is a well-formed SMILES string ending in <eos>; bad_pos [B]
     int32: the first refused index, T without <eos>, -1 when valid (mvae_smiles_syntax_check)."""
@@ -551,6 +572,18 @@ def moses_beam_syntax_step(state, ldh, w_fc, bias, step, eos_id, pad_id, table, 
                                                table.shape[1], ptr(base), ptr(add_out), ptr(score), ptr(fin), ptr(ends), ptr(hist_tok),
                                                ptr(hist_par), ptr(tok_info), ptr(gstate), int(max_len), stream_ptr()),
           "mvae_moses_beam_syntax_step")
+
+
+def moses_beam_forced_step(state, ldh, w_fc, bias, step, eos_id, pad_id, table, base, add_out, score, fin, ends, hist_tok, hist_par, B, K, V, H,
+                           forced, tok_info=None, gstate=None, max_len=0):
+    """moses_beam_step (tok_info / gstate None) or moses_beam_syntax_step with forced tokens: forced int32 [B, >= step + 1], one row per
+    molecule; forced[m, step] >= 0 is the only candidate an active beam of molecule m proposes (at score + logp[forced], unmasked), -1
+    leaves the molecule to the sibling launch's search -- one launch (mvae_moses_beam_forced_step)."""
+    check(L.load().mvae_moses_beam_forced_step(dt_code(state.dtype), B, K, V, H, state.shape[0], ptr(state), state.stride(0), state.stride(1), ldh,
+                                               ptr(w_fc), w_fc.stride(0), ptr(bias), int(step), int(eos_id), int(pad_id), ptr(table),
+                                               table.shape[1], ptr(base), ptr(add_out), ptr(score), ptr(fin), ptr(ends), ptr(hist_tok),
+                                               ptr(hist_par), ptr(tok_info), ptr(gstate), int(max_len), ptr(forced), forced.stride(0),
+                                               stream_ptr()), "mvae_moses_beam_forced_step")
 
 
 def moses_beam_finalize(hist_tok, hist_par, ends, score, ids, ends_out, score_out, bos_id, B, K, max_len):

@@ -794,7 +794,7 @@ def moses_reconstruction(model, batches, beam_width=1, max_len=100, syntax=False
 
 @torch.no_grad()
 def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top_k=None, top_p=None, seed=0, z=None, syntax=False,
-                   count_valid=False, novel_against=None):
+                   count_valid=False, novel_against=None, prefix=None):
     """The reference's generation pipeline (``hugesample.py``: sample in batches, hash the strings, count unique / total) with the hashing
     and the deduplication on the device: ``n_samples`` sequences from a ``mosesvae.VAE`` in batches of ``batch_size`` (the last one shorter),
     batch j with seed ``seed + j`` and ``temp`` / ``top_k`` / ``top_p`` as ``VAE.sample`` takes them.  ``z`` None draws each batch's latents
@@ -819,7 +819,12 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     well-formed and novel: the numerator of the usual novelty figure).  Equality with a corpus row is of token rows and exact -- no hash
     decides it; a sample cut at ``max_len`` is compared by the tokens it has; a sample with a special token inside its content (<pad>,
     <bos>, <unk> before the <eos>) equals nothing, the corpus holding no specials.  Without ``novel_against`` the launches and the keys of
-    the result are what they were."""
+    the result are what they were.
+    ``prefix`` (``VAE.sample(prefix=)``): one prefix -- a string or a 1-D id tensor -- that every sample starts with, or a list of
+    ``n_samples`` of them consumed batch by batch as ``z`` is; its ValueErrors are raised before any device work, and with ``syntax=True``
+    all prefixes are walked by the automaton once, before the first batch (a refusal names the sample index).  The hash covers the whole
+    row, prefix included, so whole strings are deduplicated; "logq" is that of the free tokens.  Everything else about the result is
+    unchanged."""
     n_samples, batch_size, max_len = int(n_samples), int(batch_size), int(max_len)
     if n_samples < 1 or batch_size < 1 or max_len < 1:
         raise ValueError(f"moses_generate: n_samples, batch_size and max_len must be >= 1, got {n_samples}, {batch_size}, {max_len}")
@@ -828,6 +833,7 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         model._check_syntax(max_len)
     if z is not None and tuple(z.shape) != (n_samples, model.d_z):
         raise ValueError(f"moses_generate: z must be [{n_samples}, {model.d_z}], got {tuple(z.shape)}")
+    forced = model._prefix_table(prefix, n_samples, max_len, "moses_generate")
     dev = model.device
     if novel_against is not None:
         from .data import MosesDeviceDataset
@@ -839,6 +845,8 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         if d.type != dev.type or (d.type == "cuda" and (torch.cuda.current_device() if d.index is None else d.index)
                                   != (torch.cuda.current_device() if dev.index is None else dev.index)):
             raise ValueError(f"moses_generate: novel_against lives on {d}, the model on {dev}")
+    if forced is not None and syntax:
+        model._check_prefix_syntax(forced, max_len, "moses_generate")      # every sample's prefix, once, before the first batch: rows are sample indices
     i64 = torch.long
     seen_h = torch.empty(0, dtype=i64, device=dev)             # the hashes seen so far, sorted, and the first-seen index of each
     seen_g = torch.empty(0, dtype=i64, device=dev)
@@ -860,7 +868,8 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     for j, b0 in enumerate(range(0, n_samples, batch_size)):
         n = min(batch_size, n_samples - b0)
         zb = model.sample_z_prior(n) if z is None else z[b0:b0 + n]
-        x, ends, logq, h = model._sample_tokens(zb, max_len, temp, int(seed) + j, k, p, syntax=bool(syntax))
+        fb = None if forced is None else forced if forced[0].shape[0] == 1 else (forced[0][b0:b0 + n], forced[1][b0:b0 + n])
+        x, ends, logq, h = model._sample_tokens(zb, max_len, temp, int(seed) + j, k, p, syntax=bool(syntax), forced=fb, check_prefix=False)
         ok = model.syntax_valid(x) if count_valid else None
         match = novel_against.lookup(x) if novel_against is not None else None
         hs, order = torch.sort(h, stable=True)                  # equal hashes: ascending row, so a run starts at its first occurrence
