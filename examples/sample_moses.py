@@ -11,9 +11,12 @@ syntax, not chemistry -- counted on the device.  ``--syntax`` samples under that
 samples whose token row equals no row of that corpus, looked up on the device in its exact index (no set of strings on the host).
 ``--neighbors K`` (with ``--novel_against``) encodes that corpus once (``MosesDeviceDataset.encode_latents``) and prints, for the first few
 unique samples, their K nearest training molecules in latent space with the squared distances (``MosesLatentIndex.neighbors``).
+``--nearest`` (with ``--novel_against``) also asks for every unique sample's nearest training string by token-level Levenshtein distance
+(``mv.moses_generate(nearest=True)``, ``MosesDeviceDataset.nearest_strings``) and prints the mean and the histogram of that distance and a
+few sample / neighbour pairs.
 ``--reconstruct FILE`` (strings, one per line) skips the generation: it encodes the strings (z = mu), decodes them deterministically
 (``--beam_width``) without and with the syntax constraint (``mv.moses_reconstruction(..., syntax=)``) and prints the exact-match
-reconstruction fraction of each and the mean log p(x | mu).
+reconstruction fraction of each, the mean log p(x | mu) and the mean token edit distance between input and decode.
 
     python examples/sample_moses.py --ckpt trained_save.pt --vocab vocab.pkl --rounds 10 --top_p 0.95 --syntax --novel_against train.smi
 """
@@ -47,6 +50,8 @@ ap.add_argument("--log", default="log_small.csv")
 ap.add_argument("--novel_against", default=None, metavar="FILE", help="training strings, one per line: count the unique samples not among them")
 ap.add_argument("--neighbors", default=0, type=int, metavar="K", help="with --novel_against: print the K nearest training molecules (latent "
                                                                     "space) of the first few unique samples")
+ap.add_argument("--nearest", action="store_true", help="with --novel_against: the nearest training string of every unique sample by "
+                                                       "token-level Levenshtein distance")
 ap.add_argument("--reconstruct", default=None, metavar="FILE", help="strings, one per line: report exact-match reconstruction at z = mu "
                                                                   "without and with the syntax constraint, then exit")
 ap.add_argument("--beam_width", default=1, type=int, help="with --reconstruct: the beam width of the deterministic decode")
@@ -81,9 +86,10 @@ if args.reconstruct:
     batches = [collate(strings[i:i + args.batch_size]) for i in range(0, len(strings), args.batch_size)]
     for syntax in (False, True):
         t0 = time.time()
-        frac, mean_lp = mv.moses_reconstruction(model, batches, beam_width=args.beam_width, max_len=args.max_len, syntax=syntax)
+        frac, mean_lp, mean_ed = mv.moses_reconstruction(model, batches, beam_width=args.beam_width, max_len=args.max_len, syntax=syntax,
+                                                         edit_distance=True)
         print(f"reconstruction of {len(strings)} strings, beam width {args.beam_width}, syntax={syntax}: exact match {frac:.4f}, "
-              f"mean log p(x | mu) {mean_lp:.3f}, {time.time() - t0:.2f} s", flush=True)
+              f"mean log p(x | mu) {mean_lp:.3f}, mean token edit distance {mean_ed:.3f}, {time.time() - t0:.2f} s", flush=True)
     sys.exit(0)
 
 
@@ -94,7 +100,10 @@ def is_valid(s):
         return False
 
 
+if args.nearest and corpus is None:
+    sys.exit("--nearest needs --novel_against (the training strings to search)")
 seen, total, valid, syntax_valid = {}, 0, 0, 0
+near = {}                                                 # unique string -> (distance, corpus row) of its nearest training string
 novel = set()                                             # the unique strings that are not in the corpus
 per_round = args.batch_size * args.batches_per_round
 start = time.time()
@@ -103,7 +112,7 @@ with open(args.log, "w", buffering=1) as f:
     for r in range(args.rounds):
         res = mv.moses_generate(model, per_round, batch_size=args.batch_size, max_len=args.max_len, temp=args.temp, top_k=args.top_k,
                                 top_p=args.top_p, seed=args.seed + r * args.batches_per_round, syntax=args.syntax, count_valid=True,
-                                novel_against=corpus, prefix=args.prefix)
+                                novel_against=corpus, prefix=args.prefix, nearest=args.nearest)
         total += res["total"]
         syntax_valid += res["valid"]
         for i, (s, c) in enumerate(zip(res["strings"], res["counts"])):
@@ -111,6 +120,8 @@ with open(args.log, "w", buffering=1) as f:
                 seen[s] = 0
                 if corpus is not None and res["is_novel"][i]:
                     novel.add(s)
+                if args.nearest:
+                    near[s] = (res["nearest_dist"][i], res["nearest_row"][i])
                 if Chem is not None and is_valid(s):
                     valid += 1
             seen[s] += c
@@ -121,6 +132,16 @@ with open(args.log, "w", buffering=1) as f:
               f"unique per second {len(seen) / (now - start):.0f}, well-formed {syntax_valid} ({syntax_valid / total:.3f})"
               + (f", valid unique {valid}" if Chem is not None else "")
               + (f", novel {len(novel)} ({len(novel) / len(seen):.3f} of unique)" if corpus is not None else ""), flush=True)
+if near:
+    dists = sorted(d for d, _ in near.values())
+    hist = {}
+    for d in dists:
+        hist[min(d, 10)] = hist.get(min(d, 10), 0) + 1
+    print(f"nearest training string of {len(near)} unique samples: mean token edit distance {sum(dists) / len(dists):.2f}, median "
+          f"{dists[len(dists) // 2]}; histogram " + ", ".join(f"{'10+' if d == 10 else d}: {hist[d]}" for d in sorted(hist)), flush=True)
+    shown = [s for s in list(near)[:8]]
+    for s, name in zip(shown, corpus.smiles([near[s][1] for s in shown])):
+        print(f"    {near[s][0]:4d}  {s}  <-  {name}")
 if args.neighbors > 0 and corpus is None:
     print("--neighbors needs --novel_against (the training strings to search)", flush=True)
 elif args.neighbors > 0:

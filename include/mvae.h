@@ -725,6 +725,45 @@ int mvae_latent_knn(int Q, int64_t N, int dz, int k, const float* q, int64_t ldq
                     float* dist, int64_t* idx, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Token-level Levenshtein distance (an addition: how far two strings are apart, where mvae_corpus_index_probe only says equal or not, and
+ * the model-free counterpart of mvae_latent_knn).
+ * Content of a row, the convention of mvae_corpus_index_probe: for a row r of an int64 [*, T] tensor it is r[1:] up to, and not including,
+ *   the first column equal to `eos`; without one it runs to column T - 1.  Column 0 (<bos>) is never part of it and its value does not
+ *   matter; nothing at or behind the <eos> takes part -- whatever stands there, the answer is the same -- and no column >= T is ever
+ *   loaded.  T = 1, or `eos` in column 1, is the empty content.  Corpus row j is the byte string tokens[offsets[j] : offsets[j + 1]] of the
+ *   CSR above; empty rows are legal, and only bytes inside tokens[0 : offsets[N]) are ever loaded.
+ * Distance: plain Levenshtein with unit costs for insert, delete and substitute, no transposition.  Token p of the pattern side and token
+ *   t of the text side are equal iff p == t and 0 <= p < V: an id outside [0, V) on either side -- a corpus byte >= V, a negative id, an
+ *   int64 far out of range -- equals nothing, not even itself, and is never used as an index.  The distance between contents of lengths
+ *   m and n is exact (a bit-parallel dynamic program in 64-bit words, one word for m <= 64, two with a carry for m <= 128), lies between
+ *   |m - n| and max(m, n) and is returned as int32.
+ * mvae_edit_distance_rows: dist[i] = the distance between the content of a[i] ([B, a_ld] int64, Ta columns) and the content of b[i]
+ *   ([B, b_ld], Tb columns), one launch.  a is the pattern side: Ta - 1 <= MVAE_EDIT_PATTERN_MAX, else MVAE_ERR_UNSUPPORTED; Tb is
+ *   unlimited.  Exactly dist[0..B) is written.
+ * mvae_edit_knn: for each of Q queries (x [Q, x_ld] int64, T columns; the pattern side, T - 1 <= MVAE_EDIT_PATTERN_MAX) row i of dist /
+ *   idx ([Q, k], dense) holds the k eligible corpus rows with the smallest (distance, row), ascending in that pair: equal distances rank
+ *   by the lower row, so a query whose content equals a corpus row gets (0, lowest such row) first -- mvae_corpus_index_probe's answer.
+ *   Every corpus row is eligible except exclude[i] (exclude [Q] int64 or NULL; -1 = none).  With fewer than k eligible rows the tail of
+ *   the output row is (MVAE_EDIT_NONE, -1).  Every element of dist and idx is written, nothing else is.  A query's answer does not depend
+ *   on Q, on the other queries or on how the launch is laid out; two runs are equal.
+ *   Nothing of size Q x N exists: one scan launch keeps a k-entry list per (query, wave) in LDS, and, when the corpus rows are split
+ *   over `slots` partial lists per query to fill the chip (slots depends on Q and N alone, <= 256), one merge launch combines them by
+ *   (distance, row).  Workspace: mvae_edit_knn_workspace(Q, N, k) = slots * Q * k * 12 bytes (8-byte aligned; 0: one slot, none needed);
+ *   it depends on (Q, N, k) alone.
+ * Refused before anything is enqueued.  MVAE_ERR_INVALID: a NULL pointer other than exclude; B, Q, N, k, T, Ta or Tb < 1; a leading
+ *   dimension below its T; eos outside [0, 65535]; V outside [1, 64].  MVAE_ERR_UNSUPPORTED: k > 32, or a pattern side wider than 129
+ *   columns (the workspace function then returns 0).  MVAE_ERR_WORKSPACE: a missing or short workspace.
+ */
+#define MVAE_EDIT_NONE 2147483647      /* distance of an empty k-NN entry */
+#define MVAE_EDIT_PATTERN_MAX 128      /* longest content on the pattern side */
+int mvae_edit_distance_rows(int B, int V, int eos, const int64_t* a, int64_t a_ld, int Ta, const int64_t* b, int64_t b_ld, int Tb,
+                            int32_t* dist /* [B] */, void* stream);
+size_t mvae_edit_knn_workspace(int Q, int64_t N, int k);
+int mvae_edit_knn(int Q, int T, int V, int eos, const int64_t* x, int64_t x_ld, const uint8_t* tokens, const int64_t* offsets, int64_t N, int k,
+                  const int64_t* exclude /* [Q] or NULL, -1 = none */, int32_t* dist /* [Q, k] */, int64_t* idx /* [Q, k] */, void* ws,
+                  size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Optimiser surface (K14 + K15): torch.nn.utils.clip_grad_norm_(params, max_norm) (train.py:102) followed by
  * torch.optim.Adam.step() (train.py:81,104) on a FLAT fp32 parameter / gradient / m / v buffer.
  *   mvae_sumsq: partial[i] = sum of squares of chunk i (deterministic); norm_out[0] = sqrt(total) is

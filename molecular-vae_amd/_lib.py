@@ -186,6 +186,9 @@ SIGNATURES = {
     "mvae_gauss_pairwise_lse": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
     "mvae_latent_knn_workspace": (_sz, [_i, _i64, _i, _i]),
     "mvae_latent_knn": (_i, [_i, _i64, _i, _i, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mvae_edit_distance_rows": (_i, [_i, _i, _i, _vp, _i64, _i, _vp, _i64, _i, _vp, _vp]),
+    "mvae_edit_knn_workspace": (_sz, [_i, _i64, _i]),
+    "mvae_edit_knn": (_i, [_i, _i, _i, _i, _vp, _i64, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

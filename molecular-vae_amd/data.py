@@ -14,7 +14,8 @@
                            ``lookup`` / ``contains`` / ``n_distinct``: an exact hash index of the corpus rows on the device
                            (``mvae_corpus_index_build`` / ``_probe``), which ``train.moses_generate(novel_against=)`` counts novelty with.
                            ``encode_latents`` -> ``MosesLatentIndex``: the encoder mean of every corpus row in HBM and an exact k-NN
-                           search over it (``mvae_latent_knn``); ``smiles`` reads corpus rows back as strings.
+                           search over it (``mvae_latent_knn``); ``smiles`` reads corpus rows back as strings; ``nearest_strings``
+                           is the exact k-NN by token-level Levenshtein distance over the same corpus (``mvae_edit_knn``).
   * ``load_smiles`` / ``save_encoded`` / ``load_encoded`` -- ``.smi``/CSV in, ``.npz`` (indices + charset + max_len) out.
 """
 import numpy as np
@@ -253,17 +254,14 @@ class MosesDeviceDataset:
         ops.corpus_index_probe(self.tokens, self.offsets, self.n, self._slots, x, self.vocab.eos, match)
         return match
 
-    def lookup(self, x):
-        """Which corpus row each token row equals: int64 [B] on the device, the LOWEST corpus row with exactly those tokens, -1 for none
-        (``mvae_corpus_index_probe``; builds the index on first use).  x: padded ids [B, T] (bos first) on the device, or a list of id
-        tensors (bos first) or strings.  A row's content is what stands between <bos> and its first <eos> (or its last column); a special
-        token inside it matches nothing.  Strings go through ``tokenize_corpus``' byte table, as the corpus did, so an unknown character
-        is <unk> on both sides.  Exact: token rows are compared, not hashes."""
+    def _token_rows(self, x, who):
+        """What ``lookup`` and ``nearest_strings`` take -- padded ids [B, T] (bos first), or a list of id tensors (bos first) or strings --
+        as a device int64 [B, T] with unit column stride.  Strings go through ``tokenize_corpus``' byte table, as the corpus did."""
         v = self.vocab
         if not torch.is_tensor(x):
             x = list(x)
             if not x:
-                raise ValueError("lookup: needs at least one row")
+                raise ValueError(f"{who}: needs at least one row")
             csr = None
             if all(isinstance(s, str) for s in x):
                 try:
@@ -284,11 +282,45 @@ class MosesDeviceDataset:
                         for s in x]
                 x = torch.nn.utils.rnn.pad_sequence(seqs, batch_first=True, padding_value=v.pad)
         if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-            raise ValueError(f"lookup: x must be [B, T], got {tuple(x.shape)}")
+            raise ValueError(f"{who}: x must be [B, T], got {tuple(x.shape)}")
         x = x.to(self.device, torch.long)
         if x.stride(1) != 1:
             x = x.contiguous()
-        return self._probe(x)
+        return x
+
+    def lookup(self, x):
+        """Which corpus row each token row equals: int64 [B] on the device, the LOWEST corpus row with exactly those tokens, -1 for none
+        (``mvae_corpus_index_probe``; builds the index on first use).  x: padded ids [B, T] (bos first) on the device, or a list of id
+        tensors (bos first) or strings.  A row's content is what stands between <bos> and its first <eos> (or its last column); a special
+        token inside it matches nothing.  Strings go through ``tokenize_corpus``' byte table, as the corpus did, so an unknown character
+        is <unk> on both sides.  Exact: token rows are compared, not hashes."""
+        return self._probe(self._token_rows(x, "lookup"))
+
+    def nearest_strings(self, x, k=1, exclude_self=False):
+        """The k corpus rows at the smallest token-level Levenshtein distance (unit costs, no transposition) from each row of x, which is
+        whatever ``lookup`` takes: (dist int32 [Q, k], rows int64 [Q, k]) on the device, ascending in (distance, row) -- equal distances
+        rank by the lower row, so a query that IS a corpus row gets (0, ``lookup``'s row) first; a tail that cannot be filled is
+        (``ops.EDIT_NONE``, -1).  The model-free counterpart of ``MosesLatentIndex.neighbors``: one ``mvae_edit_knn`` launch (two when the
+        corpus is split over workgroups), no host wait.  A special token inside a query's content equals no corpus token.
+        ``exclude_self``: a query that is itself a corpus row (``lookup``) does not answer with that row.  ValueError, before any device
+        work: a vocabulary of more than 64 ids, k outside [1, 32], a query wider than 129 columns."""
+        from . import ops
+        if len(self.vocab) > ops.EDIT_V_MAX:
+            raise ValueError(f"nearest_strings: the vocabulary has {len(self.vocab)} ids, at most {ops.EDIT_V_MAX} are supported")
+        if int(k) != k or not 1 <= k <= ops.EDIT_K_MAX:
+            raise ValueError(f"nearest_strings: k must be an integer in [1, {ops.EDIT_K_MAX}], got {k!r}")
+        if torch.is_tensor(x):
+            width = x.shape[1] if x.dim() == 2 else 0
+        else:
+            x = list(x)
+            width = max((len(s) + 2 if isinstance(s, str) else int(torch.as_tensor(s).numel()) for s in x), default=0)
+        if width - 1 > ops.EDIT_PATTERN_MAX:
+            raise ValueError(f"nearest_strings: a query has {width} columns, at most {ops.EDIT_PATTERN_MAX + 1} are supported")
+        x = self._token_rows(x, "nearest_strings")
+        from .models import _require_cuda
+        _require_cuda(self.device, "MosesDeviceDataset.nearest_strings")
+        exclude = self._probe(x) if exclude_self else None
+        return ops.edit_knn(x, self.tokens, self.offsets, self.n, int(k), self.vocab.eos, len(self.vocab), exclude=exclude)
 
     def contains(self, x):
         """``lookup(x) >= 0``: bool [B] on the device."""

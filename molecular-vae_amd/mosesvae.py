@@ -467,6 +467,34 @@ class VAE(_SavedState, nn.Module):
         ops.smiles_syntax_check(x, self._smiles_table(dev), self.eos, valid, bad)
         return (valid.bool(), bad) if bad_pos else valid.bool()
 
+    def _edit_rows(self, x, who):
+        if not torch.is_tensor(x):
+            seqs = [self.string2tensor(s, device="cpu") if isinstance(s, str) else torch.as_tensor(s, dtype=torch.long).view(-1) for s in x]
+            if not seqs:
+                raise ValueError(f"{who}: needs at least one row")
+            x = torch.nn.utils.rnn.pad_sequence(seqs, batch_first=True, padding_value=self.pad)
+        if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError(f"{who}: token rows must be [B, T], got {tuple(x.shape)}")
+        return x
+
+    def edit_distance(self, x, y):
+        """The token-level Levenshtein distance (unit costs for insert, delete and substitute, no transposition) between the rows of two
+        batches, pair by pair: int32 [B] on the device, one launch (mvae_edit_distance_rows), no host wait.  x, y: padded ids [B, T] (bos
+        first), or a list of id tensors (bos first) or of strings, under the model's vocabulary.  A row's content is what stands between
+        <bos> and its first <eos> (or its last column); ids outside the vocabulary equal nothing.  ValueError, before any device work:
+        batches of different sizes, a vocabulary of more than 64 ids, both sides wider than 129 columns."""
+        x, y = self._edit_rows(x, "edit_distance"), self._edit_rows(y, "edit_distance")
+        if x.shape[0] != y.shape[0]:
+            raise ValueError(f"edit_distance: {x.shape[0]} rows against {y.shape[0]}")
+        V = len(self.vocabulary)
+        if V > ops.EDIT_V_MAX:
+            raise ValueError(f"edit_distance: the vocabulary has {V} ids, at most {ops.EDIT_V_MAX} are supported")
+        if min(x.shape[1], y.shape[1]) - 1 > ops.EDIT_PATTERN_MAX:
+            raise ValueError(f"edit_distance: one side must have at most {ops.EDIT_PATTERN_MAX + 1} columns, got {x.shape[1]} and {y.shape[1]}")
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.edit_distance")
+        return ops.edit_distance_rows(x.to(dev, torch.long), y.to(dev, torch.long), self.eos, V)
+
     _FNV_BASIS = -3750763034362895579       # 0xcbf29ce484222325, the 64-bit FNV-1a offset basis, as an int64
 
     def _sample_tokens(self, z, max_len, temp, seed, top_k=0, top_p=1.0, filtered=True, syntax=False, forced=None, check_prefix=True):

@@ -649,6 +649,66 @@ def latent_knn(q, table, k, exclude=None, dist=None, idx=None):
     return dist, idx
 
 
+EDIT_PATTERN_MAX = 128                       # include/mvae.h: MVAE_EDIT_PATTERN_MAX, the longest content on the pattern side
+EDIT_K_MAX = 32
+EDIT_V_MAX = 64
+EDIT_NONE = 2147483647                       # MVAE_EDIT_NONE: the distance of an empty k-NN entry
+
+
+def _token_rows(t, name):
+    assert t.dim() == 2 and t.dtype == torch.int64 and t.shape[0] >= 1 and t.shape[1] >= 1, (name, t.dtype, tuple(t.shape))
+    if t.shape[1] > 1 and t.stride(1) != 1:
+        t = t.contiguous()
+    return t, (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
+
+
+def edit_distance_rows(a, b, eos, V, dist=None):
+    """dist [B] int32 := the token-level Levenshtein distance between the content of a[i] and of b[i] (int64 [B, Ta] / [B, Tb], bos first;
+    the content is what stands between column 0 and the first `eos`, or the last column), ids outside [0, V) equal to nothing -- one
+    launch (mvae_edit_distance_rows).  The distance is symmetric, so the narrower tensor goes to the kernel's pattern side (at most 129
+    columns); ValueError when both are wider."""
+    a, lda = _token_rows(a, "a")
+    b, ldb = _token_rows(b, "b")
+    assert a.shape[0] == b.shape[0] and a.device == b.device, (a.shape, b.shape)
+    if min(a.shape[1], b.shape[1]) - 1 > EDIT_PATTERN_MAX:
+        raise ValueError(f"edit_distance_rows: one side must have at most {EDIT_PATTERN_MAX + 1} columns, got {a.shape[1]} and {b.shape[1]}")
+    if a.shape[1] > b.shape[1]:
+        a, lda, b, ldb = b, ldb, a, lda
+    B = a.shape[0]
+    if dist is None:
+        dist = torch.empty(B, dtype=torch.int32, device=a.device)
+    assert dist.shape == (B,) and dist.dtype == torch.int32 and dist.is_contiguous() and dist.device == a.device
+    check(L.load().mvae_edit_distance_rows(B, int(V), int(eos), ptr(a), lda, a.shape[1], ptr(b), ldb, b.shape[1], ptr(dist), stream_ptr()),
+          "mvae_edit_distance_rows")
+    return dist
+
+
+def edit_knn(x, tokens, offsets, N, k, eos, V, exclude=None, dist=None, idx=None):
+    """The k corpus rows of the CSR corpus (tokens uint8, offsets int64 [N + 1]) at the smallest token-level Levenshtein distance from the
+    content of every row of x (int64 [Q, T], bos first, T <= 129): (dist [Q, k] int32, idx [Q, k] int64), ascending in (distance, row);
+    exclude (int64 [Q], optional) names one corpus row per query to skip (-1: none); a short tail is (EDIT_NONE, -1) (mvae_edit_knn; its
+    workspace comes from Scratch)."""
+    lib = L.load()
+    x, ldx = _token_rows(x, "x")
+    Q, T = x.shape
+    N, k = int(N), int(k)
+    assert tokens.dtype == torch.uint8 and offsets.dtype == torch.int64 and offsets.numel() >= N + 1 and tokens.device == x.device == offsets.device
+    if exclude is not None:
+        assert exclude.dtype == torch.int64 and exclude.shape == (Q,) and exclude.device == x.device
+        exclude = exclude.contiguous()
+    if dist is None:
+        dist = torch.empty(Q, max(k, 0), dtype=torch.int32, device=x.device)
+    if idx is None:
+        idx = torch.empty(Q, max(k, 0), dtype=torch.int64, device=x.device)
+    assert dist.shape == (Q, k) and idx.shape == (Q, k) and dist.is_contiguous() and idx.is_contiguous()
+    assert dist.dtype == torch.int32 and idx.dtype == torch.int64 and dist.device == x.device == idx.device
+    nb = lib.mvae_edit_knn_workspace(Q, N, k)
+    ws = Scratch.get(nb, x.device, "edit_knn") if nb else None
+    check(lib.mvae_edit_knn(Q, T, int(V), int(eos), ptr(x), ldx, ptr(tokens), ptr(offsets), N, k, ptr(exclude), ptr(dist), ptr(idx), ptr(ws), nb,
+                            stream_ptr()), "mvae_edit_knn")
+    return dist, idx
+
+
 def sample_uniform(seed, step, B):
     """Host restatement of the sampling step's uniforms u(b) = hash(seed, step * B + b) / 2^32 (tests)."""
     import numpy as np

@@ -761,17 +761,21 @@ def moses_train_epoch(model, epoch, batches, kl_weight, optimizer=None, log_ever
 
 
 @torch.no_grad()
-def moses_reconstruction(model, batches, beam_width=1, max_len=100, syntax=False):
+def moses_reconstruction(model, batches, beam_width=1, max_len=100, syntax=False, edit_distance=False):
     """Reconstruction of a ``mosesvae.VAE`` (an addition: the reference only reports teacher-forced token accuracy): every batch (a list of
     id tensors, bos first, or a PaddedBatch) is encoded with eps = 0 (z = mu), decoded deterministically (``VAE.decode(z, beam_width,
     max_len)``, best hypothesis) and compared as a string with its input; ``VAE.score(x, mu)`` gives each molecule's log p(x | mu).
     Returns (exact-match fraction, mean per-molecule log p(x | mu)) as Python floats; the host waits once, at the end.
-    ``syntax=True`` decodes over well-formed SMILES strings only (``VAE.decode(..., syntax=True)``); the log p(x | mu) term does not change."""
-    from .vocab import PaddedBatch
+    ``syntax=True`` decodes over well-formed SMILES strings only (``VAE.decode(..., syntax=True)``); the log p(x | mu) term does not change.
+    ``edit_distance=True`` returns a third value: the mean token-level Levenshtein distance between each input and its decoded best
+    hypothesis (``VAE.edit_distance``, computed per batch on the device from the decoded rows and the padded input; 0 for an exact match,
+    so a near miss and garbage no longer count alike).  The host still waits once, at the end."""
+    from .vocab import PaddedBatch, pad_batch
     if syntax:
         model._check_syntax(max_len)                       # ValueError before any device work
     dev = model.device
     lp_sum, n = torch.zeros((), dtype=torch.float64, device=dev), 0
+    ed_sum = torch.zeros((), dtype=torch.int64, device=dev)
     kept = []
     for batch in batches:
         if isinstance(batch, PaddedBatch):
@@ -782,6 +786,9 @@ def moses_reconstruction(model, batches, beam_width=1, max_len=100, syntax=False
         mu, _, _ = model.forward_encoder(batch, eps=torch.zeros(B, model.d_z, device=dev))
         ids, ends, _ = model._beam_search(mu, beam_width, max_len, syntax=syntax)
         lp_sum += model.score(seqs, mu).double().sum()
+        if edit_distance:
+            x_pad = batch.x_pad if isinstance(batch, PaddedBatch) else pad_batch(seqs, model.pad).x_pad
+            ed_sum += model.edit_distance(ids[:, 0], x_pad).sum()
         kept.append((seqs, ids[:, 0], ends[:, 0]))
         n += B
     hits = 0
@@ -789,12 +796,14 @@ def moses_reconstruction(model, batches, beam_width=1, max_len=100, syntax=False
         ids, ends = ids.tolist(), ends.tolist()
         hits += sum(model.vocabulary.ids2string(ids[b][:ends[b]], rem_bos=True, rem_eos=True) == model.tensor2string(seqs[b].cpu())
                     for b in range(len(seqs)))
+    if edit_distance:
+        return hits / max(n, 1), float(lp_sum) / max(n, 1), int(ed_sum) / max(n, 1)
     return hits / max(n, 1), float(lp_sum) / max(n, 1)
 
 
 @torch.no_grad()
 def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top_k=None, top_p=None, seed=0, z=None, syntax=False,
-                   count_valid=False, novel_against=None, prefix=None):
+                   count_valid=False, novel_against=None, prefix=None, nearest=False):
     """The reference's generation pipeline (``hugesample.py``: sample in batches, hash the strings, count unique / total) with the hashing
     and the deduplication on the device: ``n_samples`` sequences from a ``mosesvae.VAE`` in batches of ``batch_size`` (the last one shorter),
     batch j with seed ``seed + j`` and ``temp`` / ``top_k`` / ``top_p`` as ``VAE.sample`` takes them.  ``z`` None draws each batch's latents
@@ -824,7 +833,13 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     ``n_samples`` of them consumed batch by batch as ``z`` is; its ValueErrors are raised before any device work, and with ``syntax=True``
     all prefixes are walked by the automaton once, before the first batch (a refusal names the sample index).  The hash covers the whole
     row, prefix included, so whole strings are deduplicated; "logq" is that of the free tokens.  Everything else about the result is
-    unchanged."""
+    unchanged.
+    ``nearest=True`` (needs ``novel_against``; ValueError otherwise, as for a vocabulary of more than 64 ids or max_len > 129, before any
+    device work): each batch's NEW rows also go through one ``MosesDeviceDataset.nearest_strings`` launch (k = 1, no further host wait)
+    and the result gains "nearest_row" and "nearest_dist", aligned with "strings": the corpus row at the smallest token-level Levenshtein
+    distance (the lowest such row) and that distance -- "novel, and 2 edits from training row r" against "novel, and 30 edits from
+    anything".  They travel once, at the end, as "corpus_row" does; nearest_dist == 0 exactly where corpus_row >= 0, and there
+    nearest_row == corpus_row."""
     n_samples, batch_size, max_len = int(n_samples), int(batch_size), int(max_len)
     if n_samples < 1 or batch_size < 1 or max_len < 1:
         raise ValueError(f"moses_generate: n_samples, batch_size and max_len must be >= 1, got {n_samples}, {batch_size}, {max_len}")
@@ -845,6 +860,14 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         if d.type != dev.type or (d.type == "cuda" and (torch.cuda.current_device() if d.index is None else d.index)
                                   != (torch.cuda.current_device() if dev.index is None else dev.index)):
             raise ValueError(f"moses_generate: novel_against lives on {d}, the model on {dev}")
+    if nearest:
+        from . import ops
+        if novel_against is None:
+            raise ValueError("moses_generate: nearest=True needs novel_against, the corpus to search")
+        if len(model.vocabulary) > ops.EDIT_V_MAX:
+            raise ValueError(f"moses_generate: nearest=True supports at most {ops.EDIT_V_MAX} ids, the vocabulary has {len(model.vocabulary)}")
+        if max_len - 1 > ops.EDIT_PATTERN_MAX:
+            raise ValueError(f"moses_generate: nearest=True supports max_len <= {ops.EDIT_PATTERN_MAX + 1}, got {max_len}")
     if forced is not None and syntax:
         model._check_prefix_syntax(forced, max_len, "moses_generate")      # every sample's prefix, once, before the first batch: rows are sample indices
     i64 = torch.long
@@ -856,6 +879,7 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     n_valid_new = torch.zeros((), dtype=i64, device=dev) if count_valid else None
     n_valid_novel = torch.zeros((), dtype=i64, device=dev) if count_valid and novel_against is not None else None
     matches = []                                                # the corpus row of each new sample, on the device until the end
+    near = []                                                   # (distance, row) of each new sample's nearest corpus row, likewise
     stage = [None, None]                                        # pinned staging rows [batch_size, max_len + 1] (ids, end), alternating
     pending = None
 
@@ -904,6 +928,8 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
             logqs.append(logq[sel])
             if match is not None:
                 matches.append(match[sel])
+            if nearest:
+                near.append(novel_against.nearest_strings(x[sel], k=1))
             g0 = counts.numel()
             counts = torch.cat([counts, cnt[src]])
             seen_h, perm = torch.sort(torch.cat([seen_h, hs[src]]))
@@ -921,6 +947,9 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         res["novel"] = sum(res["is_novel"])
         if count_valid:
             res["valid_unique_novel"] = int(n_valid_novel)
+    if nearest:
+        res["nearest_dist"] = torch.cat([d[:, 0] for d, _ in near]).tolist() if near else []
+        res["nearest_row"] = torch.cat([r[:, 0] for _, r in near]).tolist() if near else []
     return res
 
 
