@@ -14,6 +14,10 @@ unique samples, their K nearest training molecules in latent space with the squa
 ``--nearest`` (with ``--novel_against``) also asks for every unique sample's nearest training string by token-level Levenshtein distance
 (``mv.moses_generate(nearest=True)``, ``MosesDeviceDataset.nearest_strings``) and prints the mean and the histogram of that distance and a
 few sample / neighbour pairs.
+``--valence`` runs the SMILES graph walk on every batch (``mv.moses_generate(valence=True)``): it prints how many samples are
+valence-consistent -- well-formed, every atom within its allowed valence, sane ring bonds, aromatic atoms in rings; a necessary condition
+for chemical validity, not rdkit's verdict -- and the others by reason, and the mean and standard deviation of molecular weight and heavy
+atoms over the valence-consistent unique samples and, with ``--novel_against``, over the corpus (``MosesDeviceDataset.descriptors``).
 ``--reconstruct FILE`` (strings, one per line) skips the generation: it encodes the strings (z = mu), decodes them deterministically
 (``--beam_width``) without and with the syntax constraint (``mv.moses_reconstruction(..., syntax=)``) and prints the exact-match
 reconstruction fraction of each, the mean log p(x | mu) and the mean token edit distance between input and decode.
@@ -52,6 +56,8 @@ ap.add_argument("--neighbors", default=0, type=int, metavar="K", help="with --no
                                                                     "space) of the first few unique samples")
 ap.add_argument("--nearest", action="store_true", help="with --novel_against: the nearest training string of every unique sample by "
                                                        "token-level Levenshtein distance")
+ap.add_argument("--valence", action="store_true", help="count the valence-consistent samples and the others by reason; print weight and "
+                                                       "heavy-atom statistics")
 ap.add_argument("--reconstruct", default=None, metavar="FILE", help="strings, one per line: report exact-match reconstruction at z = mu "
                                                                   "without and with the syntax constraint, then exit")
 ap.add_argument("--beam_width", default=1, type=int, help="with --reconstruct: the beam width of the deterministic decode")
@@ -103,6 +109,7 @@ def is_valid(s):
 if args.nearest and corpus is None:
     sys.exit("--nearest needs --novel_against (the training strings to search)")
 seen, total, valid, syntax_valid = {}, 0, 0, 0
+chem_valid, reasons, props = 0, [0] * 7, {}               # unique valence-consistent string -> (weight, heavy atoms)
 near = {}                                                 # unique string -> (distance, corpus row) of its nearest training string
 novel = set()                                             # the unique strings that are not in the corpus
 per_round = args.batch_size * args.batches_per_round
@@ -112,8 +119,12 @@ with open(args.log, "w", buffering=1) as f:
     for r in range(args.rounds):
         res = mv.moses_generate(model, per_round, batch_size=args.batch_size, max_len=args.max_len, temp=args.temp, top_k=args.top_k,
                                 top_p=args.top_p, seed=args.seed + r * args.batches_per_round, syntax=args.syntax, count_valid=True,
-                                novel_against=corpus, prefix=args.prefix, nearest=args.nearest)
+                                novel_against=corpus, prefix=args.prefix, nearest=args.nearest, valence=args.valence)
         total += res["total"]
+        if args.valence:
+            chem_valid += res["chem_valid"]
+            reasons = [a + res["status_counts"][k] for k, a in enumerate(reasons)]
+            props.update((s, (w, h)) for s, st, w, h in zip(res["strings"], res["status"], res["weight"], res["heavy_atoms"]) if st == 0)
         syntax_valid += res["valid"]
         for i, (s, c) in enumerate(zip(res["strings"], res["counts"])):
             if s not in seen:
@@ -130,8 +141,23 @@ with open(args.log, "w", buffering=1) as f:
                 + (f",{len(novel)}\n" if corpus is not None else "\n"))
         print(f"round {r}: unique {len(seen)} ({len(seen) / total:.3f}), sampled {total}, samples per second {total / (now - start):.0f}, "
               f"unique per second {len(seen) / (now - start):.0f}, well-formed {syntax_valid} ({syntax_valid / total:.3f})"
+              + (f", valence-consistent {chem_valid} ({chem_valid / total:.3f})" if args.valence else "")
               + (f", valid unique {valid}" if Chem is not None else "")
               + (f", novel {len(novel)} ({len(novel) / len(seen):.3f} of unique)" if corpus is not None else ""), flush=True)
+if args.valence:
+    from molecular_vae_amd import ops
+
+    def mean_std(t):
+        t = torch.as_tensor(t, dtype=torch.float64)
+        return f"{float(t.mean()):.2f} +- {float(t.std(unbiased=False)):.2f}" if t.numel() else "n/a"
+    print(f"valence check of {total} samples: " + ", ".join(f"{ops.SMILES_STATUS_NAMES[k]} {n}" for k, n in enumerate(reasons)), flush=True)
+    print(f"    {len(props)} valence-consistent unique samples: weight {mean_std([w for w, _ in props.values()])}, heavy atoms "
+          f"{mean_std([h for _, h in props.values()])}", flush=True)
+    if corpus is not None:
+        d = corpus.descriptors()
+        ok = d["status"] == 0
+        print(f"    {int(ok.sum())} of {len(corpus)} corpus rows valence-consistent: weight {mean_std(d['weight'][ok].cpu())}, heavy atoms "
+              f"{mean_std(d['heavy_atoms'][ok].cpu())}", flush=True)
 if near:
     dists = sorted(d for d, _ in near.values())
     hist = {}

@@ -764,6 +764,70 @@ int mvae_edit_knn(int Q, int T, int V, int eos, const int64_t* x, int64_t x_ld, 
                   size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * SMILES graph (an addition: "SMILES syntax" above decides whether a row is well-formed and says that valence is not its business; this is
+ * the second automaton on top of it).  The token row is parsed into its molecular graph, the valence rules and the graph rules that need
+ * no kekulisation are enforced, and per-row integers come out: a status, the heavy-atom / bond / ring / hydrogen counts, the molecular
+ * formula.  Status 0 is a NECESSARY condition for chemical validity, not a sufficient one: it means correct valences, sane ring bonds and
+ * aromatic atoms in rings.  It does not test whether an aromatic system kekulises and it does not reject c1(C)(C)cccc1; a row with
+ * status 0 is "valence-consistent", which is less than what a cheminformatics toolkit calls valid.
+ * Input language: exactly what the syntax automaton accepts.  Under that grammar a ring digit never follows a bond, there is no '.', and
+ *   no isotopes: ring-closure bonds are always implicit and the graph is connected.
+ * Elements, in this order (MVAE_SMILES_ELEMENTS = 11): H B C N O F P S Cl Br I; a lower-case atom is the aromatic form of its element.
+ * Bond contribution: '=' counts 2, '#' counts 3, every other bond counts 1 -- implicit, - : / \ and ring closures.  Aromatic bonds count 1
+ *   on purpose (the hydrogen rule of OpenSMILES); nothing kekulises.  '@' is ignored.
+ * chem_info int32 [V], one word per token id beside tok_info: bits 0-3 the element (ATOM and H tokens: the token's element; a TAIL: the
+ *   element the pair spells, Cl or Br), bit 4 the aromatic flag, bits 8-9 the bond order of a BOND or MINUS token.
+ * The walk: the row goes through smi::step.  A row the automaton refuses, or one without <eos>, gets status SYNTAX and the bad_pos of
+ *   mvae_smiles_syntax_check, whatever else the row holds.  Alongside, the graph:
+ *   - an organic-subset atom comes into being at its ATOM token; a TAIL token (l, r) changes the element of the current atom (C -> Cl,
+ *     B -> Br) and re-checks it; a bracket atom comes into being at its ']', with H count 1 for 'H' and the digit for 'Hn', and charge
+ *     sign * (digit if present, else 1).  [H] is a graph node of element H.
+ *   - a new atom gets a bond of the pending order to the current atom, if there is one; the pending order is set by a bond token and
+ *     defaults to 1.  '(' pushes the current atom, ')' pops it back to current.
+ *   - an opening ring digit records the current atom.  A closing digit on atom j with opener i first checks for a duplicate bond -- i is
+ *     j's tree predecessor, or (i, j) were already joined by another digit: status RING_BOND --, otherwise adds a bond of 1 to both atoms
+ *     and marks as ring members every atom on the tree path i .. j through their lowest common ancestor.
+ *   - after every update of an atom (creation, new bond, tail) its used valence U = sum of bond contributions + bracket H count is
+ *     checked against the largest allowed valence of (element, charge); exceeding it gives status VALENCE.  Unbracketed atoms have
+ *     charge 0.  A bracket atom with |charge| >= 2, or with no table entry, gets status CHARGE at its ']' -- decided before the atom is
+ *     bonded, so CHARGE wins over a VALENCE the same ']' would raise.  Allowed valences (charge -1 / 0 / +1; - = no entry):
+ *       H {0} {1} {0}    B {4} {3} -     C {3} {4} {3}    N {2} {3} {4}        O {1} {2} {3}      F {0} {1} -
+ *       P {2} {3,5} {4}  S {1} {2,4,6} {3,5}              Cl {0} {1} -         Br {0} {1} -       I {0} {1,3,5} -
+ *   - at <eos>: a well-formed row with more than 127 content tokens gets status TOO_LONG (bad_pos the <eos> column) and nothing else is
+ *     reported for it; else the first graph error in token order stands; else an aromatic atom that is no ring member gives status
+ *     AROMATIC with bad_pos the <eos> column.
+ *   bad_pos: for SYNTAX what mvae_smiles_syntax_check gives; for VALENCE / CHARGE / RING_BOND the column of the token being processed
+ *     when the first error was found (both ends of a new bond are checked at that one token); -1 for status 0.
+ *   Implicit hydrogens, unbracketed atoms only: with S the atom's bond sum and v0 the smallest allowed valence (charge 0) >= S, an
+ *     aliphatic atom has v0 - S, an aromatic one max(0, v0 - S - 1).  Bracket atoms have none beyond their H count.
+ * Status: 0 OK, 1 SYNTAX, 2 VALENCE, 3 CHARGE, 4 RING_BOND, 5 AROMATIC, 6 TOO_LONG.
+ * Outputs, per row: status int32 [B]; bad_pos int32 [B] (optional); desc int32 [B, 8] (optional) = heavy atoms (nodes that are not H),
+ *   bonds, rings (= bonds - nodes + 1), ring atoms, aromatic atoms, hydrogens (implicit + bracket counts + [H] nodes), net charge, hetero
+ *   atoms (heavy, not C); formula int32 [B, 11] (optional) = atoms per element in the order above, slot 0 the hydrogens.  A row whose
+ *   status is not 0 gets zeros in desc and formula.  Every element of the given outputs is written, nothing else is.
+ * mvae_smiles_graph_rows: one thread per row of x [B, T] int64 (bos first; x_ld >= T); eos_id and ids outside [0, V) are treated exactly
+ *   as mvae_smiles_syntax_check treats them.
+ * mvae_smiles_graph_corpus: the same over the CSR corpus (uint8 rows without specials, tokens[offsets[j] : offsets[j + 1]]): the end of the
+ *   row acts as <eos>, bad_pos is 0-based in the row (the row's length for the <eos> column), an empty row gets SYNTAX at 0.
+ * mvae_smiles_graph_host: mvae_smiles_graph_rows on HOST pointers, a plain loop over the rows through the same source compiled for the
+ *   CPU (the precedent of mvae_dropout_keep and mvae_normal_words): the parse can be tested and sanitised without a device.
+ * Refused before anything is enqueued: V > 64 (MVAE_ERR_UNSUPPORTED); a NULL x / tokens / offsets / tok_info / chem_info / status, B, N, T
+ *   or V < 1, x_ld < T, eos_id outside [0, V) (MVAE_ERR_INVALID).
+ */
+#define MVAE_SMILES_ELEMENTS 11
+#define MVAE_SMILES_DESC 8
+#define MVAE_SMILES_CONTENT_MAX 127    /* content tokens of a row the graph is kept for */
+int mvae_smiles_graph_rows(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */, const int32_t* chem_info /* [V] */,
+                           int eos_id, int32_t* status /* [B] */, int32_t* bad_pos /* [B] or NULL */, int32_t* desc /* [B, 8] or NULL */,
+                           int32_t* formula /* [B, 11] or NULL */, void* stream);
+int mvae_smiles_graph_corpus(const uint8_t* tokens, const int64_t* offsets /* [N + 1] */, int64_t N, int V, const int32_t* tok_info /* [V] */,
+                             const int32_t* chem_info /* [V] */, int32_t* status /* [N] */, int32_t* bad_pos /* [N] or NULL */,
+                             int32_t* desc /* [N, 8] or NULL */, int32_t* formula /* [N, 11] or NULL */, void* stream);
+int mvae_smiles_graph_host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */, const int32_t* chem_info /* [V] */,
+                           int eos_id, int32_t* status /* [B] */, int32_t* bad_pos /* [B] or NULL */, int32_t* desc /* [B, 8] or NULL */,
+                           int32_t* formula /* [B, 11] or NULL */);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Optimiser surface (K14 + K15): torch.nn.utils.clip_grad_norm_(params, max_norm) (train.py:102) followed by
  * torch.optim.Adam.step() (train.py:81,104) on a FLAT fp32 parameter / gradient / m / v buffer.
  *   mvae_sumsq: partial[i] = sum of squares of chunk i (deterministic); norm_out[0] = sqrt(total) is

@@ -189,6 +189,9 @@ SIGNATURES = {
     "mvae_edit_distance_rows": (_i, [_i, _i, _i, _vp, _i64, _i, _vp, _i64, _i, _vp, _vp]),
     "mvae_edit_knn_workspace": (_sz, [_i, _i64, _i]),
     "mvae_edit_knn": (_i, [_i, _i, _i, _i, _vp, _i64, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mvae_smiles_graph_rows": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mvae_smiles_graph_corpus": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvae_smiles_graph_host": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -219,6 +219,7 @@ class MosesDeviceDataset:
         self.offsets = torch.from_numpy(np.ascontiguousarray(offsets)).to(self.device)
         self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._slots = self._n_distinct_d = self._n_distinct = None     # the corpus index: built on first use
+        self._descriptors = None                                       # descriptors(): computed on first use
 
     def __len__(self):
         return self.n
@@ -321,6 +322,21 @@ class MosesDeviceDataset:
         _require_cuda(self.device, "MosesDeviceDataset.nearest_strings")
         exclude = self._probe(x) if exclude_self else None
         return ops.edit_knn(x, self.tokens, self.offsets, self.n, int(k), self.vocab.eos, len(self.vocab), exclude=exclude)
+
+    def descriptors(self):
+        """``VAE.descriptors`` of every corpus row, in corpus order: the same dict (status, bad_pos, heavy_atoms, ..., formula, weight), from
+        ONE ``mvae_smiles_graph_corpus`` launch over the CSR rows (and the matrix-vector product of the weight).  bad_pos is 0-based in the row's string.  Cached; never waits for the
+        device.  ValueError for a vocabulary of more than 64 ids."""
+        if self._descriptors is None:
+            from . import ops
+            from .models import _require_cuda
+            from .vocab import smiles_token_table, smiles_chem_table
+            if len(self.vocab) > 64:
+                raise ValueError(f"descriptors: the vocabulary has {len(self.vocab)} ids, at most 64 are supported")
+            _require_cuda(self.device, "MosesDeviceDataset.descriptors")
+            tok, chem = smiles_token_table(self.vocab).to(self.device), smiles_chem_table(self.vocab).to(self.device)
+            self._descriptors = ops.graph_descriptors(*ops.smiles_graph_corpus(self.tokens, self.offsets, self.n, tok, chem))
+        return self._descriptors
 
     def contains(self, x):
         """``lookup(x) >= 0``: bool [B] on the device."""
@@ -492,6 +508,30 @@ def synthetic_smiles(n, seed=0, lo=20, hi=60, structured=True):
             out.append("".join(np.resize(m, ln)))
         else:
             out.append("".join(rs.choice(alphabet, size=ln)))
+    return out
+
+
+def formula_strings(formula, charge=None):
+    """Molecular formulas in Hill notation from ``formula`` rows ([B, 11] counts per element of ``vocab.SMI_ELEMENTS``, hydrogens first; a
+    tensor on either side, an ndarray or lists): carbon, hydrogen, then the other elements alphabetically -- all alphabetically when
+    there is no carbon --, a count of 1 left out: ``C9H8O4``.  ``charge`` ([B], optional) appends the net charge: ``C4H12N+``,
+    ``C2H3O2-``, beyond one ``(2+)`` / ``(2-)``.  An all-zero row (a row that is not ok) gives the empty string.  Waits for the device
+    when given device tensors."""
+    from .vocab import SMI_ELEMENTS
+    f = np.asarray(formula.cpu() if torch.is_tensor(formula) else formula).reshape(-1, len(SMI_ELEMENTS))
+    q = np.zeros(f.shape[0], np.int64) if charge is None else np.asarray(charge.cpu() if torch.is_tensor(charge) else charge).reshape(-1)
+    if q.shape[0] != f.shape[0]:
+        raise ValueError(f"formula_strings: {f.shape[0]} formulas, {q.shape[0]} charges")
+    with_c = ["C", "H"] + sorted(e for e in SMI_ELEMENTS if e not in ("C", "H"))
+    without_c = sorted(SMI_ELEMENTS)
+    col = {e: i for i, e in enumerate(SMI_ELEMENTS)}
+    out = []
+    for row, c in zip(f.tolist(), q.tolist()):
+        s = "".join(e + (str(row[col[e]]) if row[col[e]] > 1 else "") for e in (with_c if row[col["C"]] else without_c) if row[col[e]] > 0)
+        if c:
+            sign = "+" if c > 0 else "-"
+            s += sign if abs(c) == 1 else f"({abs(c)}{sign})"
+        out.append(s)
     return out
 
 

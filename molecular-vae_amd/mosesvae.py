@@ -31,7 +31,7 @@ from . import _lib as L
 from . import ops
 from .models import (LinearWeights, EmbeddingWeights, RNNWeights, _Workspace, _SavedState, _pad, _require_cuda, _LDPAD, _dyk, _grad_views, _kmajor_gemm,
                      _pack_rnn_stack, _gru_param_grads)
-from .vocab import PaddedBatch, pad_batch, smiles_token_table
+from .vocab import PaddedBatch, pad_batch, smiles_token_table, smiles_chem_table
 
 
 class _RowsWorkspace(_Workspace):
@@ -466,6 +466,53 @@ class VAE(_SavedState, nn.Module):
         bad = torch.empty(B, dtype=torch.int32, device=dev) if bad_pos else None
         ops.smiles_syntax_check(x, self._smiles_table(dev), self.eos, valid, bad)
         return (valid.bool(), bad) if bad_pos else valid.bool()
+
+    def _smiles_chem_table(self, dev):
+        """vocab.smiles_chem_table: built once per model on the host (dev None), its device copy cached in the pack."""
+        host = self.__dict__.get("_smi_chem")
+        if host is None:
+            host = self.__dict__["_smi_chem"] = smiles_chem_table(self.vocabulary)
+        if dev is None:
+            return host
+        P = self._pack(dev)
+        if "smi_chem" not in P:
+            P["smi_chem"] = host.to(dev)
+        return P["smi_chem"]
+
+    def _graph_rows(self, x, who):
+        """syntax_valid's input handling, then one mvae_smiles_graph_rows launch: (status, bad_pos, desc, formula), int32, on the device."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE." + who)
+        if len(self.vocabulary) > 64:
+            raise ValueError(f"{who}: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
+        if not torch.is_tensor(x):
+            seqs = [self.string2tensor(s, device="cpu") if isinstance(s, str) else torch.as_tensor(s, dtype=torch.long) for s in x]
+            if not seqs:
+                raise ValueError(f"{who}: needs at least one row")
+            x = torch.nn.utils.rnn.pad_sequence(seqs, batch_first=True, padding_value=self.pad)
+        if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+            raise ValueError(f"{who}: x must be [B, T], got {tuple(x.shape)}")
+        x = x.to(dev, torch.long)
+        return ops.smiles_graph_rows(x, self._smiles_table(dev), self._smiles_chem_table(dev), self.eos)
+
+    @torch.no_grad()
+    def chem_valid(self, x, return_status=False):
+        """Which token rows are well-formed AND valence-consistent SMILES strings (the graph walk of include/mvae.h, "SMILES graph", one
+        mvae_smiles_graph_rows launch, no host wait): every atom within the largest valence its element and charge allow, no ring bond
+        doubling an existing bond, every aromatic atom in a ring.  A necessary condition for chemical validity, not a sufficient one:
+        nothing is kekulised.  x: what ``syntax_valid`` takes.  Returns a bool [B] device tensor; return_status=True also returns the
+        int32 [B] status (ops.SMILES_STATUS_NAMES) and the int32 [B] bad_pos (the column of the first error, -1 for a row that is ok)."""
+        status, bad, _, _ = self._graph_rows(x, "chem_valid")
+        return (status == 0, status, bad) if return_status else status == 0
+
+    @torch.no_grad()
+    def descriptors(self, x):
+        """The graph walk's figures for token rows x (what ``syntax_valid`` takes), a dict of device tensors -- one graph-walk launch, one matrix-vector product for the weight, no host wait:
+        "status" and "bad_pos" as ``chem_valid`` returns them; "heavy_atoms", "bonds", "rings", "ring_atoms", "aromatic_atoms",
+        "hydrogens", "charge", "hetero_atoms" (int32 [B]); "formula" (int32 [B, 11]: atoms per element of vocab.SMI_ELEMENTS, hydrogens
+        first; ``data.formula_strings`` spells it); "weight" (float32 [B]: formula . vocab.ATOMIC_WEIGHTS).  Rows whose status is not 0
+        have zeros everywhere."""
+        return ops.graph_descriptors(*self._graph_rows(x, "descriptors"))
 
     def _edit_rows(self, x, who):
         if not torch.is_tensor(x):

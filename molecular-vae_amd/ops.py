@@ -709,6 +709,86 @@ def edit_knn(x, tokens, offsets, N, k, eos, V, exclude=None, dist=None, idx=None
     return dist, idx
 
 
+SMILES_ELEMENTS = 11                          # include/mvae.h: MVAE_SMILES_ELEMENTS, the columns of `formula`
+SMILES_DESC = 8                               # MVAE_SMILES_DESC, the columns of `desc`
+SMILES_CONTENT_MAX = 127                      # MVAE_SMILES_CONTENT_MAX: a well-formed row with more content tokens is TOO_LONG
+SMILES_DESC_NAMES = ("heavy_atoms", "bonds", "rings", "ring_atoms", "aromatic_atoms", "hydrogens", "charge", "hetero_atoms")
+(SMILES_OK, SMILES_SYNTAX, SMILES_VALENCE, SMILES_CHARGE, SMILES_RING_BOND, SMILES_AROMATIC, SMILES_TOO_LONG) = range(7)
+SMILES_STATUS_NAMES = ("ok", "syntax", "valence", "charge", "ring_bond", "aromatic", "too_long")
+
+
+def _graph_outputs(n, dev, status, bad_pos, desc, formula):
+    i32 = torch.int32
+    status = torch.empty(n, dtype=i32, device=dev) if status is None else status
+    bad_pos = torch.empty(n, dtype=i32, device=dev) if bad_pos is None else bad_pos
+    desc = torch.empty(n, SMILES_DESC, dtype=i32, device=dev) if desc is None else desc
+    formula = torch.empty(n, SMILES_ELEMENTS, dtype=i32, device=dev) if formula is None else formula
+    for t, shape in ((status, (n,)), (bad_pos, (n,)), (desc, (n, SMILES_DESC)), (formula, (n, SMILES_ELEMENTS))):
+        assert t.dtype == i32 and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev, (t.dtype, tuple(t.shape), t.device)
+    return status, bad_pos, desc, formula
+
+
+def _graph_tables(tok_info, chem_info, dev):
+    assert tok_info.dtype == chem_info.dtype == torch.int32 and tok_info.dim() == 1 and tok_info.shape == chem_info.shape
+    assert tok_info.is_contiguous() and chem_info.is_contiguous() and tok_info.device == chem_info.device == dev
+
+
+def smiles_graph_rows(x, tok_info, chem_info, eos_id, status=None, bad_pos=None, desc=None, formula=None):
+    """The SMILES graph walk over token rows x (int64 [B, T], bos first) on the device: (status [B], bad_pos [B], desc [B, 8],
+    formula [B, 11]), all int32 -- status 0 where the row is well-formed AND valence-consistent (include/mvae.h, "SMILES graph"), the
+    counts and the molecular formula of those rows, zeros for the others.  tok_info / chem_info: vocab.smiles_token_table /
+    smiles_chem_table on x's device.  One launch (mvae_smiles_graph_rows)."""
+    x, ldx = _token_rows(x, "x")
+    _graph_tables(tok_info, chem_info, x.device)
+    out = _graph_outputs(x.shape[0], x.device, status, bad_pos, desc, formula)
+    check(L.load().mvae_smiles_graph_rows(x.shape[0], x.shape[1], tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), int(eos_id),
+                                          *map(ptr, out), stream_ptr()), "mvae_smiles_graph_rows")
+    return out
+
+
+def smiles_graph_corpus(tokens, offsets, N, tok_info, chem_info, status=None, bad_pos=None, desc=None, formula=None):
+    """smiles_graph_rows over the CSR corpus (tokens uint8, offsets int64 [N + 1]; rows without specials, the end of a row acting as <eos>,
+    bad_pos 0-based in the row): one launch (mvae_smiles_graph_corpus)."""
+    N = int(N)
+    assert tokens.dtype == torch.uint8 and offsets.dtype == torch.int64 and offsets.numel() >= N + 1 and tokens.device == offsets.device
+    assert tokens.is_contiguous() and offsets.is_contiguous()
+    _graph_tables(tok_info, chem_info, tokens.device)
+    out = _graph_outputs(max(N, 0), tokens.device, status, bad_pos, desc, formula)
+    check(L.load().mvae_smiles_graph_corpus(ptr(tokens), ptr(offsets), N, tok_info.numel(), ptr(tok_info), ptr(chem_info), *map(ptr, out),
+                                            stream_ptr()), "mvae_smiles_graph_corpus")
+    return out
+
+
+def smiles_graph_host(x, tok_info, chem_info, eos_id, status=None, bad_pos=None, desc=None, formula=None):
+    """smiles_graph_rows on HOST tensors: the same walk compiled for the CPU, a plain loop over the rows (mvae_smiles_graph_host) -- for
+    tests and for machines without a device; not a fallback of the device entries."""
+    x, ldx = _token_rows(x, "x")
+    assert x.device.type == "cpu", x.device
+    _graph_tables(tok_info, chem_info, x.device)
+    out = _graph_outputs(x.shape[0], x.device, status, bad_pos, desc, formula)
+    check(L.load().mvae_smiles_graph_host(x.shape[0], x.shape[1], tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), int(eos_id),
+                                          *map(ptr, out)), "mvae_smiles_graph_host")
+    return out
+
+
+_ATOMIC_WEIGHTS = {}                          # device -> vocab.ATOMIC_WEIGHTS as float32 [11]
+
+
+def graph_descriptors(status, bad_pos, desc, formula):
+    """The outputs of a smiles_graph_* launch as the dict VAE.descriptors documents: status, bad_pos, the eight desc columns by name,
+    formula and weight = formula . vocab.ATOMIC_WEIGHTS (float32; 0 for rows that are not ok, whose formula is zero)."""
+    from .vocab import ATOMIC_WEIGHTS
+    dev = formula.device
+    w = _ATOMIC_WEIGHTS.get(dev)
+    if w is None:                                # uploaded once per device, so that later calls never wait
+        w = _ATOMIC_WEIGHTS[dev] = torch.tensor(ATOMIC_WEIGHTS, dtype=torch.float32).to(dev)
+    out = {"status": status, "bad_pos": bad_pos}
+    out.update((name, desc[:, i]) for i, name in enumerate(SMILES_DESC_NAMES))
+    out["formula"] = formula
+    out["weight"] = formula.float() @ w
+    return out
+
+
 def sample_uniform(seed, step, B):
     """Host restatement of the sampling step's uniforms u(b) = hash(seed, step * B + b) / 2^32 (tests)."""
     import numpy as np

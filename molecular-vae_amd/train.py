@@ -803,7 +803,7 @@ def moses_reconstruction(model, batches, beam_width=1, max_len=100, syntax=False
 
 @torch.no_grad()
 def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top_k=None, top_p=None, seed=0, z=None, syntax=False,
-                   count_valid=False, novel_against=None, prefix=None, nearest=False):
+                   count_valid=False, novel_against=None, prefix=None, nearest=False, valence=False):
     """The reference's generation pipeline (``hugesample.py``: sample in batches, hash the strings, count unique / total) with the hashing
     and the deduplication on the device: ``n_samples`` sequences from a ``mosesvae.VAE`` in batches of ``batch_size`` (the last one shorter),
     batch j with seed ``seed + j`` and ``temp`` / ``top_k`` / ``top_p`` as ``VAE.sample`` takes them.  ``z`` None draws each batch's latents
@@ -839,7 +839,16 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     and the result gains "nearest_row" and "nearest_dist", aligned with "strings": the corpus row at the smallest token-level Levenshtein
     distance (the lowest such row) and that distance -- "novel, and 2 edits from training row r" against "novel, and 30 edits from
     anything".  They travel once, at the end, as "corpus_row" does; nearest_dist == 0 exactly where corpus_row >= 0, and there
-    nearest_row == corpus_row."""
+    nearest_row == corpus_row.
+    ``valence=True`` (ValueError for a vocabulary of more than 64 ids, before any device work): each batch's rows also go through the
+    SMILES graph walk (``VAE.descriptors``: one ``mvae_smiles_graph_rows`` launch per batch and the matrix-vector product of the weight, no
+    further host wait) and the result gains
+    "chem_valid" (the number of well-formed AND valence-consistent samples, duplicates included -- every atom within its allowed valence,
+    sane ring bonds, aromatic atoms in rings: a necessary condition for chemical validity, nothing is kekulised), "chem_valid_unique" (of
+    distinct ones) and, with ``novel_against``, "chem_valid_unique_novel"; "status_counts" ({status: count} over all samples, the codes
+    of ``ops.SMILES_STATUS_NAMES``); and the lists "status", "weight" (molecular weight, 0.0 for a sample that is not ok), "heavy_atoms"
+    and "rings", aligned with "strings", which travel once, at the end, as "corpus_row" does.  Without ``valence`` the launches and the
+    keys of the result are what they were."""
     n_samples, batch_size, max_len = int(n_samples), int(batch_size), int(max_len)
     if n_samples < 1 or batch_size < 1 or max_len < 1:
         raise ValueError(f"moses_generate: n_samples, batch_size and max_len must be >= 1, got {n_samples}, {batch_size}, {max_len}")
@@ -868,6 +877,8 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
             raise ValueError(f"moses_generate: nearest=True supports at most {ops.EDIT_V_MAX} ids, the vocabulary has {len(model.vocabulary)}")
         if max_len - 1 > ops.EDIT_PATTERN_MAX:
             raise ValueError(f"moses_generate: nearest=True supports max_len <= {ops.EDIT_PATTERN_MAX + 1}, got {max_len}")
+    if valence and len(model.vocabulary) > 64:
+        raise ValueError(f"moses_generate: valence=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
     if forced is not None and syntax:
         model._check_prefix_syntax(forced, max_len, "moses_generate")      # every sample's prefix, once, before the first batch: rows are sample indices
     i64 = torch.long
@@ -880,6 +891,10 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     n_valid_novel = torch.zeros((), dtype=i64, device=dev) if count_valid and novel_against is not None else None
     matches = []                                                # the corpus row of each new sample, on the device until the end
     near = []                                                   # (distance, row) of each new sample's nearest corpus row, likewise
+    chem = []                                                   # (status, weight, heavy atoms, rings) of each new sample, likewise
+    n_chem = torch.zeros(3, dtype=i64, device=dev) if valence else None      # status 0: all samples, distinct ones, distinct and novel
+    status_counts = torch.zeros(7, dtype=i64, device=dev) if valence else None
+    status_codes = torch.arange(7, dtype=torch.int32, device=dev) if valence else None
     stage = [None, None]                                        # pinned staging rows [batch_size, max_len + 1] (ids, end), alternating
     pending = None
 
@@ -896,6 +911,7 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         x, ends, logq, h = model._sample_tokens(zb, max_len, temp, int(seed) + j, k, p, syntax=bool(syntax), forced=fb, check_prefix=False)
         ok = model.syntax_valid(x) if count_valid else None
         match = novel_against.lookup(x) if novel_against is not None else None
+        graph = model.descriptors(x) if valence else None
         hs, order = torch.sort(h, stable=True)                  # equal hashes: ascending row, so a run starts at its first occurrence
         first = torch.ones(n, dtype=torch.bool, device=dev)
         first[1:] = hs[1:] != hs[:-1]
@@ -913,6 +929,13 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
             n_valid_new += (ok[order] & new).sum()
             if match is not None:
                 n_valid_novel += (ok[order] & new & (match[order] < 0)).sum()
+        if valence:
+            good = graph["status"] == 0
+            n_chem[0] += good.sum()
+            n_chem[1] += (good[order] & new).sum()
+            if match is not None:
+                n_chem[2] += (good[order] & new & (match[order] < 0)).sum()
+            status_counts += (graph["status"][:, None] == status_codes).sum(0)      # no bincount: on a device tensor it reads min / max back
         key, ord2 = torch.sort(torch.where(new, order, torch.full_like(order, n)))     # the new rows first, in first-seen order
         n_new = int(new.sum())                                   # the batch's one host wait (the copy queued last round has landed too)
         if pending is not None:
@@ -930,6 +953,8 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
                 matches.append(match[sel])
             if nearest:
                 near.append(novel_against.nearest_strings(x[sel], k=1))
+            if valence:
+                chem.append(tuple(graph[name][sel] for name in ("status", "weight", "heavy_atoms", "rings")))
             g0 = counts.numel()
             counts = torch.cat([counts, cnt[src]])
             seen_h, perm = torch.sort(torch.cat([seen_h, hs[src]]))
@@ -950,6 +975,14 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     if nearest:
         res["nearest_dist"] = torch.cat([d[:, 0] for d, _ in near]).tolist() if near else []
         res["nearest_row"] = torch.cat([r[:, 0] for _, r in near]).tolist() if near else []
+    if valence:
+        n_chem = n_chem.tolist()
+        res["chem_valid"], res["chem_valid_unique"] = n_chem[0], n_chem[1]
+        if novel_against is not None:
+            res["chem_valid_unique_novel"] = n_chem[2]
+        res["status_counts"] = dict(enumerate(status_counts.tolist()))
+        for i, name in enumerate(("status", "weight", "heavy_atoms", "rings")):
+            res[name] = torch.cat([c[i] for c in chem]).tolist() if chem else []
     return res
 
 

@@ -145,3 +145,30 @@ def smiles_token_table(vocab):
     if not any(w & 0xFF == SMI_ATOM for w in table):
         raise ValueError("smiles_token_table: the vocabulary has no atom token (one of B C N O P S F I b c n o p s)")
     return torch.tensor(table, dtype=torch.int32)
+
+
+# the SMILES graph walk (include/mvae.h, "SMILES graph"; csrc/smiles_graph.hpp): the elements in formula order and their standard atomic weights
+SMI_ELEMENTS = ("H", "B", "C", "N", "O", "F", "P", "S", "Cl", "Br", "I")
+ATOMIC_WEIGHTS = (1.008, 10.81, 12.011, 14.007, 15.999, 18.998, 30.974, 32.06, 35.45, 79.904, 126.904)
+SMI_AROMATIC = 1 << 4
+_SMI_BOND_ORDER = {"=": 2, "#": 3, ":": 1, "/": 1, "\\": 1, "-": 1}
+_SMI_TAIL_ELEMENT = {"l": "Cl", "r": "Br"}
+
+
+def smiles_chem_table(vocab):
+    """The per-token chemistry table of the SMILES graph walk for a CharVocab, beside ``smiles_token_table``: int32 [V], one word per id --
+    bits 0-3 the element as an index into SMI_ELEMENTS (an atom token and 'H': the token's element; a tail: the element the pair spells,
+    'l' Cl and 'r' Br), bit 4 set for a lower-case (aromatic) atom, bits 8-9 the bond order of a bond token and of '-' (= 2, # 3, every
+    other 1).  Every other token has 0."""
+    table = [0] * len(vocab)
+    for ch, i in vocab.c2i.items():
+        cls = _SMI_CLASS.get(ch, SMI_OTHER)
+        if cls == SMI_ATOM:
+            table[i] = SMI_ELEMENTS.index(ch.upper()) | (SMI_AROMATIC if ch.islower() else 0)
+        elif cls == SMI_H:
+            table[i] = SMI_ELEMENTS.index("H")
+        elif cls == SMI_TAIL:
+            table[i] = SMI_ELEMENTS.index(_SMI_TAIL_ELEMENT[ch])
+        elif cls in (SMI_BOND, SMI_MINUS):
+            table[i] = _SMI_BOND_ORDER[ch] << 8
+    return torch.tensor(table, dtype=torch.int32)
