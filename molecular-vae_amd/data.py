@@ -258,13 +258,12 @@ class MosesDeviceDataset:
     def _token_rows(self, x, who):
         """What ``lookup`` and ``nearest_strings`` take -- padded ids [B, T] (bos first), or a list of id tensors (bos first) or strings --
         as a device int64 [B, T] with unit column stride.  Strings go through ``tokenize_corpus``' byte table, as the corpus did."""
+        from .vocab import token_rows
         v = self.vocab
         if not torch.is_tensor(x):
             x = list(x)
-            if not x:
-                raise ValueError(f"{who}: needs at least one row")
             csr = None
-            if all(isinstance(s, str) for s in x):
+            if x and all(isinstance(s, str) for s in x):
                 try:
                     csr = tokenize_corpus(x, v)
                 except ValueError:                                # a character beyond latin-1: <unk> by the slow route below
@@ -278,16 +277,7 @@ class MosesDeviceDataset:
                 host[:, 1:-1][np.arange(cols - 2)[None, :] < lens[:, None]] = tokens      # the mask's row-major order is the CSR's order
                 host[np.arange(len(x)), lens + 1] = v.eos
                 x = torch.from_numpy(host)
-            else:
-                seqs = [torch.as_tensor(v.string2ids(s, add_bos=True, add_eos=True) if isinstance(s, str) else s, dtype=torch.long).view(-1)
-                        for s in x]
-                x = torch.nn.utils.rnn.pad_sequence(seqs, batch_first=True, padding_value=v.pad)
-        if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-            raise ValueError(f"{who}: x must be [B, T], got {tuple(x.shape)}")
-        x = x.to(self.device, torch.long)
-        if x.stride(1) != 1:
-            x = x.contiguous()
-        return x
+        return token_rows(x, lambda s: v.string2ids(s, add_bos=True, add_eos=True), v.pad, who, self.device)
 
     def lookup(self, x):
         """Which corpus row each token row equals: int64 [B] on the device, the LOWEST corpus row with exactly those tokens, -1 for none
@@ -477,7 +467,7 @@ class MosesLatentIndex:
         """``search`` around the encoder means of x under ``model``: x is a list of strings or of id tensors (bos first; any order), or a
         PaddedBatch; the answers are in the order of x.  ``exclude_self``: a query that is itself a corpus row (``dataset.lookup``: its
         lowest row with those tokens) does not answer with that row."""
-        from .vocab import PaddedBatch
+        from .vocab import PaddedBatch, length_order
         self.dataset._check_model(model, "neighbors")
         if isinstance(x, PaddedBatch):
             mu, keys = model.encode(x)[0], x.x_pad
@@ -486,10 +476,10 @@ class MosesLatentIndex:
             if not keys:
                 raise ValueError("neighbors: needs at least one query")
             seqs = [model.string2tensor(s) if isinstance(s, str) else torch.as_tensor(s, dtype=torch.long).view(-1) for s in keys]
-            order = sorted(range(len(seqs)), key=lambda i: -seqs[i].numel())        # stable, length descending: what the encoder takes
+            order, perm = length_order(seqs, model.device)
             mu_sorted = model.encode([seqs[i] for i in order])[0]
             mu = torch.empty_like(mu_sorted)
-            mu[torch.tensor(order, device=mu.device)] = mu_sorted
+            mu[perm] = mu_sorted
         exclude = self.dataset.lookup(keys) if exclude_self else None
         return self.search(mu, k, exclude=exclude)
 

@@ -20,8 +20,10 @@ input tokens by ``<unk>`` with that probability (never ``<bos>``, the last input
 and ``free_bits`` makes ``kl_loss`` the objective ``sum_j max(m_j, free_bits)`` over the per-dimension batch means m_j of the KL, with
 the KL itself in ``last_kl``.  With both at 0 the step issues exactly the launches it issues without them.
 """
+import functools
 import math
 import os
+import types
 
 import torch
 import torch.distributed as dist
@@ -31,7 +33,7 @@ from . import _lib as L
 from . import ops
 from .models import (LinearWeights, EmbeddingWeights, RNNWeights, _Workspace, _SavedState, _pad, _require_cuda, _LDPAD, _dyk, _grad_views, _kmajor_gemm,
                      _pack_rnn_stack, _gru_param_grads)
-from .vocab import PaddedBatch, pad_batch, smiles_token_table, smiles_chem_table
+from .vocab import PaddedBatch, pad_batch, token_rows, length_order, smiles_token_table, smiles_chem_table
 
 
 class _RowsWorkspace(_Workspace):
@@ -109,6 +111,14 @@ class VAE(_SavedState, nn.Module):
 
     def tensor2string(self, tensor):
         return self.vocabulary.ids2string(tensor.tolist(), rem_bos=True, rem_eos=True)
+
+    def _seqs(self, x):
+        """A list of strings and id tensors (bos first) as the list of int64 id tensors the reference passes around; strings on the host."""
+        return [self.string2tensor(s, device="cpu") if isinstance(s, str) else torch.as_tensor(s, dtype=torch.long) for s in x]
+
+    def _rows(self, x, who, dev=None):
+        """vocab.token_rows under the model's vocabulary."""
+        return token_rows(x, functools.partial(self.string2tensor, device="cpu"), self.pad, who, dev)
 
     # -- unique parameters in a fixed order (parameters() already de-duplicates the aliases)
     def _plist(self):
@@ -429,17 +439,20 @@ class VAE(_SavedState, nn.Module):
             raise ValueError(f"{what}: the prefix table is {tuple(table.shape)}, the batch needs [{B}, {max_len}]")
         return table.to(dev).expand(B, -1).contiguous()
 
-    def _smiles_table(self, dev):
-        """vocab.smiles_token_table: built once per model on the host (dev None), its device copy cached in the pack."""
-        host = self.__dict__.get("_smi_tok")
+    def _vocab_table(self, key, build, dev):
+        """build(vocabulary): made once per model on the host (dev None), its device copy cached in the pack."""
+        host = self.__dict__.get("_" + key)
         if host is None:
-            host = self.__dict__["_smi_tok"] = smiles_token_table(self.vocabulary)
+            host = self.__dict__["_" + key] = build(self.vocabulary)
         if dev is None:
             return host
         P = self._pack(dev)
-        if "smi_tok" not in P:
-            P["smi_tok"] = host.to(dev)
-        return P["smi_tok"]
+        if key not in P:
+            P[key] = host.to(dev)
+        return P[key]
+
+    def _smiles_table(self, dev):
+        return self._vocab_table("smi_tok", smiles_token_table, dev)
 
     _SMI_START = 0xFF << 16                  # the automaton's initial state word 0: mode START, depth 0, no previous token
 
@@ -451,16 +464,7 @@ class VAE(_SavedState, nn.Module):
         token, T for a row without <eos>, -1 for a valid row."""
         dev = self.device
         _require_cuda(dev, "mosesvae.VAE.syntax_valid")
-        if not torch.is_tensor(x):
-            seqs = [self.string2tensor(s, device="cpu") if isinstance(s, str) else torch.as_tensor(s, dtype=torch.long) for s in x]
-            if not seqs:
-                raise ValueError("syntax_valid: needs at least one row")
-            x = torch.nn.utils.rnn.pad_sequence(seqs, batch_first=True, padding_value=self.pad)
-        if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-            raise ValueError(f"syntax_valid: x must be [B, T], got {tuple(x.shape)}")
-        x = x.to(dev, torch.long)
-        if x.stride(1) != 1:
-            x = x.contiguous()
+        x = self._rows(x, "syntax_valid", dev)
         B = x.shape[0]
         valid = torch.empty(B, dtype=torch.uint8, device=dev)
         bad = torch.empty(B, dtype=torch.int32, device=dev) if bad_pos else None
@@ -468,16 +472,7 @@ class VAE(_SavedState, nn.Module):
         return (valid.bool(), bad) if bad_pos else valid.bool()
 
     def _smiles_chem_table(self, dev):
-        """vocab.smiles_chem_table: built once per model on the host (dev None), its device copy cached in the pack."""
-        host = self.__dict__.get("_smi_chem")
-        if host is None:
-            host = self.__dict__["_smi_chem"] = smiles_chem_table(self.vocabulary)
-        if dev is None:
-            return host
-        P = self._pack(dev)
-        if "smi_chem" not in P:
-            P["smi_chem"] = host.to(dev)
-        return P["smi_chem"]
+        return self._vocab_table("smi_chem", smiles_chem_table, dev)
 
     def _graph_rows(self, x, who):
         """syntax_valid's input handling, then one mvae_smiles_graph_rows launch: (status, bad_pos, desc, formula), int32, on the device."""
@@ -485,15 +480,7 @@ class VAE(_SavedState, nn.Module):
         _require_cuda(dev, "mosesvae.VAE." + who)
         if len(self.vocabulary) > 64:
             raise ValueError(f"{who}: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
-        if not torch.is_tensor(x):
-            seqs = [self.string2tensor(s, device="cpu") if isinstance(s, str) else torch.as_tensor(s, dtype=torch.long) for s in x]
-            if not seqs:
-                raise ValueError(f"{who}: needs at least one row")
-            x = torch.nn.utils.rnn.pad_sequence(seqs, batch_first=True, padding_value=self.pad)
-        if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-            raise ValueError(f"{who}: x must be [B, T], got {tuple(x.shape)}")
-        x = x.to(dev, torch.long)
-        return ops.smiles_graph_rows(x, self._smiles_table(dev), self._smiles_chem_table(dev), self.eos)
+        return ops.smiles_graph_rows(self._rows(x, who, dev), self._smiles_table(dev), self._smiles_chem_table(dev), self.eos)
 
     @torch.no_grad()
     def chem_valid(self, x, return_status=False):
@@ -514,23 +501,13 @@ class VAE(_SavedState, nn.Module):
         have zeros everywhere."""
         return ops.graph_descriptors(*self._graph_rows(x, "descriptors"))
 
-    def _edit_rows(self, x, who):
-        if not torch.is_tensor(x):
-            seqs = [self.string2tensor(s, device="cpu") if isinstance(s, str) else torch.as_tensor(s, dtype=torch.long).view(-1) for s in x]
-            if not seqs:
-                raise ValueError(f"{who}: needs at least one row")
-            x = torch.nn.utils.rnn.pad_sequence(seqs, batch_first=True, padding_value=self.pad)
-        if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-            raise ValueError(f"{who}: token rows must be [B, T], got {tuple(x.shape)}")
-        return x
-
     def edit_distance(self, x, y):
         """The token-level Levenshtein distance (unit costs for insert, delete and substitute, no transposition) between the rows of two
         batches, pair by pair: int32 [B] on the device, one launch (mvae_edit_distance_rows), no host wait.  x, y: padded ids [B, T] (bos
         first), or a list of id tensors (bos first) or of strings, under the model's vocabulary.  A row's content is what stands between
         <bos> and its first <eos> (or its last column); ids outside the vocabulary equal nothing.  ValueError, before any device work:
         batches of different sizes, a vocabulary of more than 64 ids, both sides wider than 129 columns."""
-        x, y = self._edit_rows(x, "edit_distance"), self._edit_rows(y, "edit_distance")
+        x, y = self._rows(x, "edit_distance"), self._rows(y, "edit_distance")          # on the host: the checks come before any device work
         if x.shape[0] != y.shape[0]:
             raise ValueError(f"edit_distance: {x.shape[0]} rows against {y.shape[0]}")
         V = len(self.vocabulary)
@@ -540,7 +517,53 @@ class VAE(_SavedState, nn.Module):
             raise ValueError(f"edit_distance: one side must have at most {ops.EDIT_PATTERN_MAX + 1} columns, got {x.shape[1]} and {y.shape[1]}")
         dev = self.device
         _require_cuda(dev, "mosesvae.VAE.edit_distance")
-        return ops.edit_distance_rows(x.to(dev, torch.long), y.to(dev, torch.long), self.eos, V)
+        return ops.edit_distance_rows(x.to(dev), y.to(dev), self.eos, V)
+
+    def _decode_setup(self, z, n_mol, pre, max_len, syntax, forced, who, check_prefix=True):
+        """What _sample_tokens and _beam_search do in front of their token loops, for the rows of z (fp32 [rows, d_z] on the device: one
+        per sample, or one per beam with each molecule's latent repeated) in workspace buffers named pre + ...: the initial state from
+        decoder_lat, the 4-slot copies tbl4 / zp4 of the layer-0 addends, state [layers, 2, rows, ldh] (half 0 = h0 in every layer) with
+        gates / hstate / add, the automaton's tok_info / gstate (syntax; else None), the device prefix table ftab (forced =
+        _prefix_table's result for n_mol molecules, checked by the automaton first under syntax and check_prefix; else None) and the
+        <bos> input rows gathered into add.  rnn[c] is the bound GRU pass that reads state half c and writes half 1 - c, h_top[c] the top
+        layer's state in half c.  Uploading the prefix table waits for the device, so the callers allocate their own buffers before this
+        call and nothing but the gather follows the upload."""
+        dev = self.device
+        P = self._pack(dev)
+        ws, dt, f32 = self._ws, self.compute_dtype, torch.float32
+        R, V, dz = z.shape[0], self.x_emb.num_embeddings, self.d_z
+        pd = P["dec"]; Hd = pd["H"]; NL = self.decoder_rnn.num_layers
+        Vp, ldh = _pad(V, 4), Hd + _LDPAD
+        W = lambda name, shape, d=f32: ws.get(pre + name, shape, d, dev)
+        h0 = W("h0", (R, Hd)); ops.gemm_nt(z, self.decoder_lat.weight, h0, R, Hd, dz, bias=self.decoder_lat.bias)
+        tbl3 = W("tbl3", (V, 3 * Hd)); ops.gemm_nt(P["E_p"], pd["Wx_p"], tbl3, V, 3 * Hd, Vp)
+        tbl4 = W("tbl4", (V, 4 * Hd)); tbl4[:, :3 * Hd].copy_(tbl3)
+        zp3 = W("zp3", (R, 3 * Hd)); ops.gemm_nt(z, P["Wz"], zp3, R, 3 * Hd, dz)
+        zp4 = W("zp4", (R, 4 * Hd)); zp4[:, :3 * Hd].copy_(zp3)
+        state = W("state", (NL, 2, R, ldh), dt)            # [l][c] = the state a GRU step reads (c = 0 first), [l][1 - c] = the state it writes
+        for l in range(NL):
+            ops.cast_transpose(h0, R, Hd, dst=state[l][0])
+        gates = [W(f"gates{l}", (1, R, 4 * Hd), dt) for l in range(NL)]
+        hstate = [W(f"hstate{l}", (2, R, Hd)) for l in range(NL)]
+        add = W("add", (1, R, 4 * Hd))
+        w = torch.full((R, 1), self.bos, dtype=torch.long, device=dev)
+        halves = [h.unbind(0) for h in state.unbind(1)]                  # [c][l] = layer l's [R, ldh] state in half c (at T = 1 also its output)
+        ldws = [pd["ldw"]] * NL
+        rnn = [functools.partial(ops.rnn_fwd, L.CELL_GRU, dt, 1, R, Hd, add, 0, pd["Wih"], ldws, pd["Whh"], ldws, pd["bias"], halves[1 - c], ldh,
+                                 None, gates, hstate, h0=halves[c], ldh0=ldh, persist=False) for c in (0, 1)]
+        tok_info = gstate = ftab = None
+        if syntax:
+            tok_info = self._smiles_table(dev)
+            gstate = torch.zeros((R, 2), dtype=torch.int32, device=dev)
+            gstate[:, 0] = self._SMI_START
+        if forced is not None:
+            if syntax and check_prefix:
+                self._check_prefix_syntax(forced, max_len, who)
+            ftab = self._forced_rows(forced, n_mol, max_len, dev, who)
+        ops.gather_rows_tb(w, tbl4, add, R, 1, V, 4 * Hd, base=zp4)      # the <bos> input rows; later ones come out of the loop's own launch
+        return types.SimpleNamespace(tbl4=tbl4, zp4=zp4, add=add, state=state, h_top=(halves[0][-1], halves[1][-1]), rnn=rnn, w=w,
+                                     tok_info=tok_info, gstate=gstate, ftab=ftab,
+                                     w_fc=P["Wfc"], b_fc=self.decoder_fc.bias, ldh=ldh, V=V, H=Hd)
 
     _FNV_BASIS = -3750763034362895579       # 0xcbf29ce484222325, the 64-bit FNV-1a offset basis, as an int64
 
@@ -557,59 +580,33 @@ class VAE(_SavedState, nn.Module):
             filtered = True                                               # logq and hash come with it
         dev = self.device
         _require_cuda(dev, "mosesvae.VAE.sample")
-        P = self._pack(dev)
-        ws, dt, f32 = self._ws, self.compute_dtype, torch.float32
         z = z.to(dev).float().contiguous()
-        B, V, dz = z.shape[0], self.x_emb.num_embeddings, self.d_z
-        pd = P["dec"]; Hd = pd["H"]; NL = self.decoder_rnn.num_layers
-        Vp, ldh = _pad(V, 4), Hd + _LDPAD
-        W = lambda name, shape, d=f32: ws.get("smp_" + name, shape, d, dev)
-        h0 = W("h0", (B, Hd)); ops.gemm_nt(z, self.decoder_lat.weight, h0, B, Hd, dz, bias=self.decoder_lat.bias)
-        tbl3 = W("tbl3", (V, 3 * Hd)); ops.gemm_nt(P["E_p"], pd["Wx_p"], tbl3, V, 3 * Hd, Vp)
-        tbl4 = W("tbl4", (V, 4 * Hd)); tbl4[:, :3 * Hd].copy_(tbl3)
-        zp3 = W("zp3", (B, 3 * Hd)); ops.gemm_nt(z, P["Wz"], zp3, B, 3 * Hd, dz)
-        zp4 = W("zp4", (B, 4 * Hd)); zp4[:, :3 * Hd].copy_(zp3)
-        hbuf = [W(f"h{l}", (2, B, ldh), dt) for l in range(NL)]        # [0] = previous state, [1] = new state (swapped every token)
-        for l in range(NL):
-            ops.cast_transpose(h0, B, Hd, dst=hbuf[l][0])
-        gates = [W(f"gates{l}", (1, B, 4 * Hd), dt) for l in range(NL)]
-        hstate = [W(f"hstate{l}", (2, B, Hd)) for l in range(NL)]
-        add = W("add", (1, B, 4 * Hd))
-        w = torch.full((B,), self.bos, dtype=torch.long, device=dev)
+        B = z.shape[0]
         x = torch.full((B, max_len), self.pad, dtype=torch.long, device=dev)
         x[:, 0] = self.bos
         end_pads = torch.full((B,), max_len, dtype=torch.long, device=dev)
         eos_mask = torch.zeros(B, dtype=torch.uint8, device=dev)
         logq = hsh = None
         if filtered:
-            logq = torch.zeros(B, dtype=f32, device=dev)
+            logq = torch.zeros(B, dtype=torch.float32, device=dev)
             hsh = torch.full((B,), self._FNV_BASIS, dtype=torch.long, device=dev)
+        d = self._decode_setup(z, B, "smp_", max_len, syntax, forced, "sample", check_prefix)
+        launch, tail = ops.moses_sample_step, {}
+        if filtered or forced is not None:
+            launch, tail = ops.moses_sample_filtered_step, dict(top_k=top_k, top_p=top_p, logq=logq, hash=hsh)
         if syntax:
-            tok_info = self._smiles_table(dev)
-            gstate = torch.zeros((B, 2), dtype=torch.int32, device=dev)
-            gstate[:, 0] = self._SMI_START
+            launch = ops.moses_sample_syntax_step
+            tail.update(tok_info=d.tok_info, gstate=d.gstate, max_len=max_len)
         if forced is not None:
-            if syntax and check_prefix:
-                self._check_prefix_syntax(forced, max_len, "sample")
-            ftab = self._forced_rows(forced, B, max_len, dev, "sample")
-        ops.gather_rows_tb(w.view(B, 1), tbl4, add, B, 1, V, 4 * Hd, base=zp4)      # the <bos> input rows; later ones come out of the sampling launch
-        cur = 0
+            launch = ops.moses_sample_forced_step
+            tail.update(forced=d.ftab, max_len=max_len)
+        step = functools.partial(launch, ldh=d.ldh, w_fc=d.w_fc, bias=d.b_fc, temp=temp, seed=seed, eos_id=self.eos, table=d.tbl4, base=d.zp4,
+                                 add_out=d.add, x=x, end_pads=end_pads, eos_mask=eos_mask, w_out=d.w, B=B, V=d.V, H=d.H, **tail)
+        rnn, h_top = d.rnn, d.h_top
+        cur = 0                                                           # the half the GRU step reads (swapped every token)
         for i in range(1, max_len):
-            ops.rnn_fwd(L.CELL_GRU, dt, 1, B, Hd, add, 0, pd["Wih"], [pd["ldw"]] * NL, pd["Whh"], [pd["ldw"]] * NL, pd["bias"],
-                        [h[1 - cur:2 - cur] for h in hbuf], ldh, None, gates, hstate, h0=[h[cur] for h in hbuf], ldh0=ldh, persist=False)
-            if forced is not None:
-                ops.moses_sample_forced_step(hbuf[-1][1 - cur], ldh, P["Wfc"], self.decoder_fc.bias, temp, top_k, top_p, seed, i, self.eos, tbl4,
-                                             zp4, add, x, end_pads, eos_mask, w, B, V, Hd, ftab, tok_info=tok_info if syntax else None,
-                                             gstate=gstate if syntax else None, max_len=max_len, logq=logq, hash=hsh)
-            elif syntax:
-                ops.moses_sample_syntax_step(hbuf[-1][1 - cur], ldh, P["Wfc"], self.decoder_fc.bias, temp, top_k, top_p, seed, i, self.eos, tbl4,
-                                             zp4, add, x, end_pads, eos_mask, w, B, V, Hd, tok_info, gstate, max_len, logq=logq, hash=hsh)
-            elif filtered:
-                ops.moses_sample_filtered_step(hbuf[-1][1 - cur], ldh, P["Wfc"], self.decoder_fc.bias, temp, top_k, top_p, seed, i, self.eos, tbl4,
-                                               zp4, add, x, end_pads, eos_mask, w, B, V, Hd, logq=logq, hash=hsh)
-            else:
-                ops.moses_sample_step(hbuf[-1][1 - cur], ldh, P["Wfc"], self.decoder_fc.bias, temp, seed, i, self.eos, tbl4, zp4, add, x, end_pads,
-                                      eos_mask, w, B, V, Hd)
+            rnn[cur]()
+            step(h_top[1 - cur], step=i)
             cur = 1 - cur
         return x, end_pads, logq, hsh
 
@@ -665,54 +662,27 @@ class VAE(_SavedState, nn.Module):
         dev = self.device
         _require_cuda(dev, "mosesvae.VAE.decode")
         max_len = int(max_len)
-        P = self._pack(dev)
-        ws, dt, f32 = self._ws, self.compute_dtype, torch.float32
         B = z.shape[0]; R = B * K
         zr = z.to(dev).float().repeat_interleave(K, 0).contiguous()              # beams of molecule m: rows m*K .. m*K + K-1
-        pd = P["dec"]; Hd = pd["H"]; NL = self.decoder_rnn.num_layers
-        Vp, ldh = _pad(V, 4), Hd + _LDPAD
-        W = lambda name, shape, d=f32: ws.get("bm_" + name, shape, d, dev)
-        h0 = W("h0", (R, Hd)); ops.gemm_nt(zr, self.decoder_lat.weight, h0, R, Hd, dz, bias=self.decoder_lat.bias)
-        tbl3 = W("tbl3", (V, 3 * Hd)); ops.gemm_nt(P["E_p"], pd["Wx_p"], tbl3, V, 3 * Hd, Vp)
-        tbl4 = W("tbl4", (V, 4 * Hd)); tbl4[:, :3 * Hd].copy_(tbl3)
-        zp3 = W("zp3", (R, 3 * Hd)); ops.gemm_nt(zr, P["Wz"], zp3, R, 3 * Hd, dz)
-        zp4 = W("zp4", (R, 4 * Hd)); zp4[:, :3 * Hd].copy_(zp3)
-        state = W("state", (NL, 2, R, ldh), dt)            # [l][0] = the state the next GRU step reads, [l][1] = the state it writes
-        for l in range(NL):
-            ops.cast_transpose(h0, R, Hd, dst=state[l][0])
-        gates = [W(f"gates{l}", (1, R, 4 * Hd), dt) for l in range(NL)]
-        hstate = [W(f"hstate{l}", (2, R, Hd)) for l in range(NL)]
-        add = W("add", (1, R, 4 * Hd))
         score = torch.full((B, K), float("-inf"), device=dev); score[:, 0] = 0.0    # beams 1..K-1 start dead: no duplicates at step 1
         score = score.view(R)
         fin = torch.zeros(R, dtype=torch.uint8, device=dev)
         ends = torch.full((R,), max_len, dtype=torch.long, device=dev)
         hist_tok = torch.empty((max_len, R), dtype=torch.int32, device=dev)          # row 0 (bos) is never read
         hist_par = torch.empty((max_len, R), dtype=torch.int32, device=dev)
-        w = torch.full((R, 1), self.bos, dtype=torch.long, device=dev)
+        d = self._decode_setup(zr, B, "bm_", max_len, syntax, forced, "decode")
+        launch, tail = ops.moses_beam_step, {}
         if syntax:
-            tok_info = self._smiles_table(dev)
-            gstate = torch.zeros((R, 2), dtype=torch.int32, device=dev)
-            gstate[:, 0] = self._SMI_START
+            launch, tail = ops.moses_beam_syntax_step, dict(tok_info=d.tok_info, gstate=d.gstate, max_len=max_len)
         if forced is not None:
-            if syntax:
-                self._check_prefix_syntax(forced, max_len, "decode")
-            ftab = self._forced_rows(forced, B, max_len, dev, "decode")
-        ops.gather_rows_tb(w, tbl4, add, R, 1, V, 4 * Hd, base=zp4)     # the <bos> input rows; later ones come out of the beam launch
-        h_out, h_in, ldws = [state[l][1:2] for l in range(NL)], [state[l][0] for l in range(NL)], [pd["ldw"]] * NL    # fixed: no swap
+            launch = ops.moses_beam_forced_step
+            tail.update(forced=d.ftab, max_len=max_len)
+        step = functools.partial(launch, d.state, d.ldh, d.w_fc, d.b_fc, eos_id=self.eos, pad_id=self.pad, table=d.tbl4, base=d.zp4, add_out=d.add,
+                                 score=score, fin=fin, ends=ends, hist_tok=hist_tok, hist_par=hist_par, B=B, K=K, V=d.V, H=d.H, **tail)
+        rnn = d.rnn[0]                                        # the beam launch reorders the new state into half 0: no swap
         for i in range(1, max_len):
-            ops.rnn_fwd(L.CELL_GRU, dt, 1, R, Hd, add, 0, pd["Wih"], ldws, pd["Whh"], ldws, pd["bias"], h_out, ldh, None, gates, hstate,
-                        h0=h_in, ldh0=ldh, persist=False)
-            if forced is not None:
-                ops.moses_beam_forced_step(state, ldh, P["Wfc"], self.decoder_fc.bias, i, self.eos, self.pad, tbl4, zp4, add, score, fin, ends,
-                                           hist_tok, hist_par, B, K, V, Hd, ftab, tok_info=tok_info if syntax else None,
-                                           gstate=gstate if syntax else None, max_len=max_len)
-            elif syntax:
-                ops.moses_beam_syntax_step(state, ldh, P["Wfc"], self.decoder_fc.bias, i, self.eos, self.pad, tbl4, zp4, add, score, fin, ends,
-                                           hist_tok, hist_par, B, K, V, Hd, tok_info, gstate, max_len)
-            else:
-                ops.moses_beam_step(state, ldh, P["Wfc"], self.decoder_fc.bias, i, self.eos, self.pad, tbl4, zp4, add, score, fin, ends,
-                                    hist_tok, hist_par, B, K, V, Hd)
+            rnn()
+            step(step=i)
         ids = torch.empty((B, K, max_len), dtype=torch.long, device=dev)
         ends_out = torch.empty((B, K), dtype=torch.long, device=dev)
         scores = torch.empty((B, K), device=dev)
@@ -724,14 +694,13 @@ class VAE(_SavedState, nn.Module):
         """log p(x | z) per molecule: the teacher-forced decoder (no dropout) on the latents z [B, d_z], followed by mvae_ce_rows_fwd -- the
         raw summed log-probability of tokens 1 .. end of each sequence (the targets of the mean reconstruction loss).  x: a list of id
         tensors (bos first) or strings, in any order.  Returns a float32 [B] device tensor; no gradients."""
-        seqs = [self.string2tensor(s, device="cpu") if isinstance(s, str) else torch.as_tensor(s, dtype=torch.long) for s in x]
+        seqs = self._seqs(x)
         B = len(seqs)
         if B < 1 or z.dim() != 2 or tuple(z.shape) != (B, self.d_z):
             raise ValueError(f"score: z must be [{B}, {self.d_z}], got {tuple(z.shape)}")
         dev = self.device
         _require_cuda(dev, "mosesvae.VAE.score")
-        order = sorted(range(B), key=lambda b: -int(seqs[b].numel()))          # the decoder's packed layout wants lengths descending
-        perm = torch.tensor(order, dtype=torch.long, device=dev)
+        order, perm = length_order(seqs, dev)
         x_pad, len_t = self._batch([seqs[b].to(dev) for b in order])
         T, V = x_pad.shape[1], self.x_emb.num_embeddings
         # a workspace of its own: a pending forward_decoder's saved state (self._ws) stays intact
@@ -756,7 +725,7 @@ class VAE(_SavedState, nn.Module):
         the length-sorted order the decoder runs (a stable sort: molecules of equal length keep their input order).  So with drawn noise,
         a permutation of x permutes the result only when it keeps the relative order of molecules of equal length; two molecules of the
         same length that swap places also swap their draws.  No gradients, no dropout."""
-        seqs = [self.string2tensor(s, device="cpu") if isinstance(s, str) else torch.as_tensor(s, dtype=torch.long) for s in x]
+        seqs = self._seqs(x)
         stream = ops.NoiseStream(seed) if seed is not None else self.noise_stream
         log_px, elbo, _, _ = self._iw(seqs, n_samples, eps, stream)
         return log_px, elbo
@@ -770,9 +739,8 @@ class VAE(_SavedState, nn.Module):
             raise ValueError(f"iw_log_likelihood: eps must be [{B}, {K}, {dz}], got {tuple(eps.shape)}")
         dev = self.device
         _require_cuda(dev, "mosesvae.VAE.iw_log_likelihood")
-        order = sorted(range(B), key=lambda b: -int(seqs[b].numel()))          # the GRUs' packed layout wants lengths descending
+        order, perm = length_order(seqs, dev)
         lens = [int(seqs[b].numel()) for b in order]
-        perm = torch.tensor(order, dtype=torch.long, device=dev)
         x_pad, len_t = self._batch([seqs[b].to(dev) for b in order])
         V, f32 = self.x_emb.num_embeddings, torch.float32
         P = self._pack(dev)

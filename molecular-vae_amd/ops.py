@@ -491,12 +491,18 @@ def permute102(inp, out, T, B, V):
     check(L.load().mvae_permute102(T, B, V, ptr(inp), ptr(out), stream_ptr()), "mvae_permute102")
 
 
+def _sample_head(h_top, ldh, w_fc, bias, temp, filt, seed, step, eos_id, table, base, add_out, x, end_pads, eos_mask, w_out, B, V, H):
+    """The arguments the four sampling launches share, `dtype, B, V, H, h_top ... w_out`; filt: () or (top_k, top_p), which follow temp."""
+    return (dt_code(h_top.dtype), B, V, H, ptr(h_top), ldh, ptr(w_fc), w_fc.stride(0), ptr(bias), float(temp), *filt, int(seed) & 0xFFFFFFFF,
+            int(step), int(eos_id), ptr(table), table.shape[1], ptr(base), ptr(add_out), ptr(x), x.stride(0), ptr(end_pads), ptr(eos_mask),
+            ptr(w_out))
+
+
 def moses_sample_step(h_top, ldh, w_fc, bias, temp, seed, step, eos_id, table, base, add_out, x, end_pads, eos_mask, w_out, B, V, H):
     """One generated token behind the GRU step: head GEMV, temperature softmax, multinomial draw (counter hash of (seed, step, row)), the
     reference's eos / end-pad bookkeeping and the next step's layer-0 addend rows -- one launch (mvae_moses_sample_step)."""
-    check(L.load().mvae_moses_sample_step(dt_code(h_top.dtype), B, V, H, ptr(h_top), ldh, ptr(w_fc), w_fc.stride(0), ptr(bias), float(temp),
-                                          int(seed) & 0xFFFFFFFF, int(step), int(eos_id), ptr(table), table.shape[1], ptr(base), ptr(add_out),
-                                          ptr(x), x.stride(0), ptr(end_pads), ptr(eos_mask), ptr(w_out), stream_ptr()), "mvae_moses_sample_step")
+    head = _sample_head(h_top, ldh, w_fc, bias, temp, (), seed, step, eos_id, table, base, add_out, x, end_pads, eos_mask, w_out, B, V, H)
+    check(L.load().mvae_moses_sample_step(*head, stream_ptr()), "mvae_moses_sample_step")
 
 
 def moses_sample_filtered_step(h_top, ldh, w_fc, bias, temp, top_k, top_p, seed, step, eos_id, table, base, add_out, x, end_pads, eos_mask, w_out,
@@ -504,10 +510,9 @@ def moses_sample_filtered_step(h_top, ldh, w_fc, bias, temp, top_k, top_p, seed,
     """moses_sample_step with top-k (0: off) / top-p (>= 1: off) truncation; logq [B] fp32 accumulates the drawn token's log-probability
     under the truncated distribution and hash [B] int64 the FNV-1a hash of the row's tokens, for the rows that had not ended -- one launch
     (mvae_moses_sample_filtered_step)."""
-    check(L.load().mvae_moses_sample_filtered_step(dt_code(h_top.dtype), B, V, H, ptr(h_top), ldh, ptr(w_fc), w_fc.stride(0), ptr(bias), float(temp),
-                                                   int(top_k), float(top_p), int(seed) & 0xFFFFFFFF, int(step), int(eos_id), ptr(table),
-                                                   table.shape[1], ptr(base), ptr(add_out), ptr(x), x.stride(0), ptr(end_pads), ptr(eos_mask),
-                                                   ptr(w_out), ptr(logq), ptr(hash), stream_ptr()), "mvae_moses_sample_filtered_step")
+    head = _sample_head(h_top, ldh, w_fc, bias, temp, (int(top_k), float(top_p)), seed, step, eos_id, table, base, add_out, x, end_pads, eos_mask,
+                        w_out, B, V, H)
+    check(L.load().mvae_moses_sample_filtered_step(*head, ptr(logq), ptr(hash), stream_ptr()), "mvae_moses_sample_filtered_step")
 
 
 def moses_sample_syntax_step(h_top, ldh, w_fc, bias, temp, top_k, top_p, seed, step, eos_id, table, base, add_out, x, end_pads, eos_mask, w_out,
@@ -515,10 +520,9 @@ def moses_sample_syntax_step(h_top, ldh, w_fc, bias, temp, top_k, top_p, seed, s
     """moses_sample_filtered_step under the SMILES syntax automaton: tok_info int32 [V] (vocab.smiles_token_table), gstate int32 [B, 2] the
     packed state of every row (advanced by the drawn token for the rows that had not ended).  Tokens the automaton refuses, or after which
     the string could not be finished by step max_len - 1, are masked before the softmax -- one launch (mvae_moses_sample_syntax_step)."""
-    check(L.load().mvae_moses_sample_syntax_step(dt_code(h_top.dtype), B, V, H, ptr(h_top), ldh, ptr(w_fc), w_fc.stride(0), ptr(bias), float(temp),
-                                                 int(top_k), float(top_p), int(seed) & 0xFFFFFFFF, int(step), int(eos_id), ptr(table),
-                                                 table.shape[1], ptr(base), ptr(add_out), ptr(x), x.stride(0), ptr(end_pads), ptr(eos_mask),
-                                                 ptr(w_out), ptr(logq), ptr(hash), ptr(tok_info), ptr(gstate), int(max_len), stream_ptr()),
+    head = _sample_head(h_top, ldh, w_fc, bias, temp, (int(top_k), float(top_p)), seed, step, eos_id, table, base, add_out, x, end_pads, eos_mask,
+                        w_out, B, V, H)
+    check(L.load().mvae_moses_sample_syntax_step(*head, ptr(logq), ptr(hash), ptr(tok_info), ptr(gstate), int(max_len), stream_ptr()),
           "mvae_moses_sample_syntax_step")
 
 
@@ -527,10 +531,9 @@ def moses_sample_forced_step(h_top, ldh, w_fc, bias, temp, top_k, top_p, seed, s
     """moses_sample_filtered_step (tok_info / gstate None) or moses_sample_syntax_step with forced tokens: forced int32 [B, >= step + 1],
     forced[b, step] >= 0 is written in place of a drawn token -- bookkeeping, hash and automaton state as for a drawn one, nothing added
     to logq --, -1 leaves the row to the draw of the sibling launch -- one launch (mvae_moses_sample_forced_step)."""
-    check(L.load().mvae_moses_sample_forced_step(dt_code(h_top.dtype), B, V, H, ptr(h_top), ldh, ptr(w_fc), w_fc.stride(0), ptr(bias), float(temp),
-                                                 int(top_k), float(top_p), int(seed) & 0xFFFFFFFF, int(step), int(eos_id), ptr(table),
-                                                 table.shape[1], ptr(base), ptr(add_out), ptr(x), x.stride(0), ptr(end_pads), ptr(eos_mask),
-                                                 ptr(w_out), ptr(logq), ptr(hash), ptr(tok_info), ptr(gstate), int(max_len), ptr(forced),
+    head = _sample_head(h_top, ldh, w_fc, bias, temp, (int(top_k), float(top_p)), seed, step, eos_id, table, base, add_out, x, end_pads, eos_mask,
+                        w_out, B, V, H)
+    check(L.load().mvae_moses_sample_forced_step(*head, ptr(logq), ptr(hash), ptr(tok_info), ptr(gstate), int(max_len), ptr(forced),
                                                  forced.stride(0), stream_ptr()), "mvae_moses_sample_forced_step")
 
 
@@ -551,14 +554,19 @@ def smiles_syntax_check(x, tok_info, eos_id, valid, bad_pos=None):
                                             stream_ptr()), "mvae_smiles_syntax_check")
 
 
+def _beam_head(state, ldh, w_fc, bias, step, eos_id, pad_id, table, base, add_out, score, fin, ends, hist_tok, hist_par, B, K, V, H):
+    """The arguments the three beam launches share, `dtype, B, K, V, H, layers, state ... hist_par`."""
+    return (dt_code(state.dtype), B, K, V, H, state.shape[0], ptr(state), state.stride(0), state.stride(1), ldh, ptr(w_fc), w_fc.stride(0),
+            ptr(bias), int(step), int(eos_id), int(pad_id), ptr(table), table.shape[1], ptr(base), ptr(add_out), ptr(score), ptr(fin), ptr(ends),
+            ptr(hist_tok), ptr(hist_par))
+
+
 def moses_beam_step(state, ldh, w_fc, bias, step, eos_id, pad_id, table, base, add_out, score, fin, ends, hist_tok, hist_par, B, K, V, H):
     """One beam-search token behind the GRU step: head GEMV, log-softmax, per-beam top-K, per-molecule merge, backpointers and the next
     step's layer-0 addend rows, and the recurrent state reordered from state[:, 1] (just written) into state[:, 0] (the next h0) -- one
     launch (mvae_moses_beam_step).  state: [layers, 2, B*K, ldh] in the compute dtype."""
-    check(L.load().mvae_moses_beam_step(dt_code(state.dtype), B, K, V, H, state.shape[0], ptr(state), state.stride(0), state.stride(1), ldh,
-                                        ptr(w_fc), w_fc.stride(0), ptr(bias), int(step), int(eos_id), int(pad_id), ptr(table), table.shape[1],
-                                        ptr(base), ptr(add_out), ptr(score), ptr(fin), ptr(ends), ptr(hist_tok), ptr(hist_par), stream_ptr()),
-          "mvae_moses_beam_step")
+    head = _beam_head(state, ldh, w_fc, bias, step, eos_id, pad_id, table, base, add_out, score, fin, ends, hist_tok, hist_par, B, K, V, H)
+    check(L.load().mvae_moses_beam_step(*head, stream_ptr()), "mvae_moses_beam_step")
 
 
 def moses_beam_syntax_step(state, ldh, w_fc, bias, step, eos_id, pad_id, table, base, add_out, score, fin, ends, hist_tok, hist_par, B, K, V, H,
@@ -567,11 +575,8 @@ def moses_beam_syntax_step(state, ldh, w_fc, bias, step, eos_id, pad_id, table, 
     automaton state of every beam row (reordered and advanced with the beams).  A row proposes only tokens the automaton takes and after
     which the string can still be finished by step max_len - 1; the scores stay log-probabilities over all V classes -- one launch
     (mvae_moses_beam_syntax_step)."""
-    check(L.load().mvae_moses_beam_syntax_step(dt_code(state.dtype), B, K, V, H, state.shape[0], ptr(state), state.stride(0), state.stride(1), ldh,
-                                               ptr(w_fc), w_fc.stride(0), ptr(bias), int(step), int(eos_id), int(pad_id), ptr(table),
-                                               table.shape[1], ptr(base), ptr(add_out), ptr(score), ptr(fin), ptr(ends), ptr(hist_tok),
-                                               ptr(hist_par), ptr(tok_info), ptr(gstate), int(max_len), stream_ptr()),
-          "mvae_moses_beam_syntax_step")
+    head = _beam_head(state, ldh, w_fc, bias, step, eos_id, pad_id, table, base, add_out, score, fin, ends, hist_tok, hist_par, B, K, V, H)
+    check(L.load().mvae_moses_beam_syntax_step(*head, ptr(tok_info), ptr(gstate), int(max_len), stream_ptr()), "mvae_moses_beam_syntax_step")
 
 
 def moses_beam_forced_step(state, ldh, w_fc, bias, step, eos_id, pad_id, table, base, add_out, score, fin, ends, hist_tok, hist_par, B, K, V, H,
@@ -579,11 +584,9 @@ def moses_beam_forced_step(state, ldh, w_fc, bias, step, eos_id, pad_id, table, 
     """moses_beam_step (tok_info / gstate None) or moses_beam_syntax_step with forced tokens: forced int32 [B, >= step + 1], one row per
     molecule; forced[m, step] >= 0 is the only candidate an active beam of molecule m proposes (at score + logp[forced], unmasked), -1
     leaves the molecule to the sibling launch's search -- one launch (mvae_moses_beam_forced_step)."""
-    check(L.load().mvae_moses_beam_forced_step(dt_code(state.dtype), B, K, V, H, state.shape[0], ptr(state), state.stride(0), state.stride(1), ldh,
-                                               ptr(w_fc), w_fc.stride(0), ptr(bias), int(step), int(eos_id), int(pad_id), ptr(table),
-                                               table.shape[1], ptr(base), ptr(add_out), ptr(score), ptr(fin), ptr(ends), ptr(hist_tok),
-                                               ptr(hist_par), ptr(tok_info), ptr(gstate), int(max_len), ptr(forced), forced.stride(0),
-                                               stream_ptr()), "mvae_moses_beam_forced_step")
+    head = _beam_head(state, ldh, w_fc, bias, step, eos_id, pad_id, table, base, add_out, score, fin, ends, hist_tok, hist_par, B, K, V, H)
+    check(L.load().mvae_moses_beam_forced_step(*head, ptr(tok_info), ptr(gstate), int(max_len), ptr(forced), forced.stride(0), stream_ptr()),
+          "mvae_moses_beam_forced_step")
 
 
 def moses_beam_finalize(hist_tok, hist_par, ends, score, ids, ends_out, score_out, bos_id, B, K, max_len):

@@ -778,10 +778,7 @@ def moses_reconstruction(model, batches, beam_width=1, max_len=100, syntax=False
     ed_sum = torch.zeros((), dtype=torch.int64, device=dev)
     kept = []
     for batch in batches:
-        if isinstance(batch, PaddedBatch):
-            seqs = [batch.x_pad[b, :n] for b, n in enumerate(batch.lengths.tolist())]
-        else:
-            seqs = list(batch)
+        seqs = batch.tensors() if isinstance(batch, PaddedBatch) else list(batch)
         B = len(seqs)
         mu, _, _ = model.forward_encoder(batch, eps=torch.zeros(B, model.d_z, device=dev))
         ids, ends, _ = model._beam_search(mu, beam_width, max_len, syntax=syntax)
@@ -1016,10 +1013,8 @@ def moses_latent_diagnostics(model, batches, n_samples=500, seed=None):
         stream = ops.NoiseStream(seed) if seed is not None else model.noise_stream
         nll, elbo, mus, lvs, n_tok = [], [], [], [], 0
         for batch in batches:
-            if isinstance(batch, PaddedBatch):                  # its lengths in one copy (a wait when they live on the device)
-                seqs = [batch.x_pad[b, :n] for b, n in enumerate(batch.lengths.tolist())]
-            else:
-                seqs = [model.string2tensor(s, device="cpu") if isinstance(s, str) else torch.as_tensor(s, dtype=torch.long) for s in batch]
+            # a PaddedBatch gives its lengths in one copy (a wait when they live on the device)
+            seqs = batch.tensors() if isinstance(batch, PaddedBatch) else model._seqs(batch)
             log_px, el, mu, lv = model._iw(seqs, n_samples, None, stream)
             n_tok += sum(int(s.numel()) - 1 for s in seqs)
             nll.append(-log_px); elbo.append(el); mus.append(mu); lvs.append(lv)

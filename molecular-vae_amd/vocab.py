@@ -100,6 +100,29 @@ def pad_batch(tensors, pad):
     return PaddedBatch(x_pad, torch.tensor(lengths, dtype=torch.int32, device=x_pad.device))
 
 
+def token_rows(x, to_ids, pad, who, device=None):
+    """Token rows in, for every entry point that takes them: padded ids [B, T] (bos first), or a list of strings (to_ids(s): one string's
+    ids, <bos> and <eos> included) and id tensors (bos first; flattened), padded with `pad` -> int64 [B, T] with unit column stride, on
+    `device` (None: where it is).  ValueError with the caller's name `who` in front for an empty list and for anything but two
+    dimensions."""
+    if not torch.is_tensor(x):
+        seqs = [torch.as_tensor(to_ids(s) if isinstance(s, str) else s, dtype=torch.long).view(-1) for s in x]
+        if not seqs:
+            raise ValueError(f"{who}: needs at least one row")
+        x = torch.nn.utils.rnn.pad_sequence(seqs, batch_first=True, padding_value=pad)
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise ValueError(f"{who}: x must be [B, T], got {tuple(x.shape)}")
+    x = x.to(device=device, dtype=torch.long)
+    return x if x.stride(1) == 1 else x.contiguous()
+
+
+def length_order(seqs, device):
+    """The stable length-descending order the GRUs' packed layout wants (sequences of equal length keep their input order):
+    (order as a list of indices into seqs, the same as an int64 tensor on `device`, to scatter the results back with)."""
+    order = sorted(range(len(seqs)), key=lambda b: -int(seqs[b].numel()))
+    return order, torch.tensor(order, dtype=torch.long, device=device)
+
+
 def get_padded_collate_fn(vocab, pin_memory=False):
     """Like ``get_collate_fn`` but returns a PaddedBatch (host tensors, optionally pinned) ready for one asynchronous ``.to(device)``."""
     inner = get_collate_fn(vocab)

@@ -336,3 +336,34 @@ def test_sharded_fused_adam_refuses_a_stale_state_dict():
         mv.save_checkpoint(io.BytesIO(), torch.nn.Linear(2, 2), opt, 0, ["a"], 4)
     opt._moments_stale = False                                      # gather_state() clears it
     opt.state_dict()
+
+
+# ------------------------------------------------------------------------------------------------ vocab.token_rows: the one row intake
+def test_token_rows_takes_strings_id_tensors_and_padded_tensors_alike():
+    v = V.OneHotVocab(list("CNO(=)1#[]+-Hcn"))
+    ids = lambda s: v.string2ids(s, add_bos=True, add_eos=True)
+    strings = ["CC(=O)", "c1cn", "N"]                                             # 8, 6 and 3 ids: [3, 8] padded ...
+    seqs = [torch.tensor(ids(s)) for s in strings]
+    want = torch.nn.utils.rnn.pad_sequence(seqs, batch_first=True, padding_value=v.pad)[:, :7]       # ... cut to the [3, 7] the rows below use
+    seqs = [s[:7] for s in seqs]
+    assert want.shape == (3, 7) and want.dtype == torch.int64
+    got = V.token_rows(strings, lambda s: ids(s)[:7], v.pad, "who")
+    assert got.dtype == torch.int64 and got.stride(1) == 1 and torch.equal(got, want)
+    for x in (seqs, [seqs[0], strings[1], seqs[2].view(1, -1)], [s.to(torch.int32) for s in seqs], want, want.to(torch.int32)):
+        got = V.token_rows(x, lambda s: ids(s)[:7], v.pad, "who")
+        assert got.dtype == torch.int64 and got.shape == (3, 7) and got.stride(1) == 1 and torch.equal(got, want)
+    # a view with column stride 2 comes back as its contiguous copy; device=None stays on the host
+    wide = torch.full((3, 14), -5, dtype=torch.long)
+    wide[:, ::2] = want
+    view = wide[:, ::2]
+    assert view.stride(1) == 2
+    got = V.token_rows(view, ids, v.pad, "who")
+    assert got.stride(1) == 1 and torch.equal(got, want) and got.device.type == "cpu"
+    assert V.token_rows(want, ids, v.pad, "who", device=torch.device("cpu")).data_ptr() == want.data_ptr()      # nothing to do: no copy
+    for bad in (torch.tensor(3), torch.zeros(7, dtype=torch.long), torch.zeros(2, 3, 7, dtype=torch.long), [], torch.zeros(0, 7, dtype=torch.long)):
+        with pytest.raises(ValueError, match="^caller: "):
+            V.token_rows(bad, ids, v.pad, "caller")
+    with pytest.raises(ValueError, match="caller: needs at least one row"):
+        V.token_rows([], ids, v.pad, "caller")
+    with pytest.raises(ValueError, match=r"caller: x must be \[B, T\], got \(2, 3, 7\)"):
+        V.token_rows(torch.zeros(2, 3, 7, dtype=torch.long), ids, v.pad, "caller")
