@@ -18,6 +18,11 @@ few sample / neighbour pairs.
 valence-consistent -- well-formed, every atom within its allowed valence, sane ring bonds, aromatic atoms in rings; a necessary condition
 for chemical validity, not rdkit's verdict -- and the others by reason, and the mean and standard deviation of molecular weight and heavy
 atoms over the valence-consistent unique samples and, with ``--novel_against``, over the corpus (``MosesDeviceDataset.descriptors``).
+``--int_div`` and ``--snn`` (the latter with ``--novel_against``) print the two MOSES figures defined on fingerprints for each round's
+samples (``mv.moses_generate(int_div=True, snn=True)``): IntDiv, 1 - the mean pairwise Tanimoto similarity inside the round's distinct
+valence-consistent samples (each with itself included, the MOSES form), and SNN, the mean over those samples of the largest similarity to
+any training molecule.  The fingerprint is this library's own 1024-bit circular fingerprint (``VAE.fingerprints``), built like ECFP4 but
+not rdkit's Morgan fingerprint: the figures compare runs of this script, not published tables.
 ``--reconstruct FILE`` (strings, one per line) skips the generation: it encodes the strings (z = mu), decodes them deterministically
 (``--beam_width``) without and with the syntax constraint (``mv.moses_reconstruction(..., syntax=)``) and prints the exact-match
 reconstruction fraction of each, the mean log p(x | mu) and the mean token edit distance between input and decode.
@@ -58,6 +63,9 @@ ap.add_argument("--nearest", action="store_true", help="with --novel_against: th
                                                        "token-level Levenshtein distance")
 ap.add_argument("--valence", action="store_true", help="count the valence-consistent samples and the others by reason; print weight and "
                                                        "heavy-atom statistics")
+ap.add_argument("--int_div", action="store_true", help="print each round's internal diversity (1 - mean pairwise Tanimoto similarity of the "
+                                                       "library's circular fingerprints)")
+ap.add_argument("--snn", action="store_true", help="with --novel_against: print each round's mean similarity to the nearest training molecule")
 ap.add_argument("--reconstruct", default=None, metavar="FILE", help="strings, one per line: report exact-match reconstruction at z = mu "
                                                                   "without and with the syntax constraint, then exit")
 ap.add_argument("--beam_width", default=1, type=int, help="with --reconstruct: the beam width of the deterministic decode")
@@ -108,6 +116,8 @@ def is_valid(s):
 
 if args.nearest and corpus is None:
     sys.exit("--nearest needs --novel_against (the training strings to search)")
+if args.snn and corpus is None:
+    sys.exit("--snn needs --novel_against (the training strings to search)")
 seen, total, valid, syntax_valid = {}, 0, 0, 0
 chem_valid, reasons, props = 0, [0] * 7, {}               # unique valence-consistent string -> (weight, heavy atoms)
 near = {}                                                 # unique string -> (distance, corpus row) of its nearest training string
@@ -119,7 +129,8 @@ with open(args.log, "w", buffering=1) as f:
     for r in range(args.rounds):
         res = mv.moses_generate(model, per_round, batch_size=args.batch_size, max_len=args.max_len, temp=args.temp, top_k=args.top_k,
                                 top_p=args.top_p, seed=args.seed + r * args.batches_per_round, syntax=args.syntax, count_valid=True,
-                                novel_against=corpus, prefix=args.prefix, nearest=args.nearest, valence=args.valence)
+                                novel_against=corpus, prefix=args.prefix, nearest=args.nearest, valence=args.valence,
+                                int_div=args.int_div, snn=args.snn)
         total += res["total"]
         if args.valence:
             chem_valid += res["chem_valid"]
@@ -142,6 +153,8 @@ with open(args.log, "w", buffering=1) as f:
         print(f"round {r}: unique {len(seen)} ({len(seen) / total:.3f}), sampled {total}, samples per second {total / (now - start):.0f}, "
               f"unique per second {len(seen) / (now - start):.0f}, well-formed {syntax_valid} ({syntax_valid / total:.3f})"
               + (f", valence-consistent {chem_valid} ({chem_valid / total:.3f})" if args.valence else "")
+              + (f", IntDiv of this round's {res['n_fingerprinted']} valence-consistent unique samples {res['int_div']:.4f}" if args.int_div else "")
+              + (f", SNN {res['snn']:.4f}" if args.snn else "")
               + (f", valid unique {valid}" if Chem is not None else "")
               + (f", novel {len(novel)} ({len(novel) / len(seen):.3f} of unique)" if corpus is not None else ""), flush=True)
 if args.valence:

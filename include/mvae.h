@@ -828,6 +828,76 @@ int mvae_smiles_graph_host(int B, int T, int V, const int64_t* x, int64_t x_ld, 
                            int32_t* formula /* [B, 11] or NULL */);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Circular fingerprint (an addition: a second consumer of the "SMILES graph" walk above).  A 1024-bit circular fingerprint of radius 2,
+ * built like ECFP4 but NOT rdkit's Morgan fingerprint: the bits are this library's own, nothing is kekulised, and two toolkits' bit
+ * vectors are not comparable -- "shares most substructures" within this library, in the same sense in which status 0 is
+ * "valence-consistent" and not what a toolkit calls valid.  Not Morgan, not kekulised.
+ * It is defined on the graph exactly as the walk builds it.  Ring-closure bonds are order 1, as they are there.  All arithmetic is
+ *   mod 2^32.
+ * mix.  mix(h) is: h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16.
+ * Atom invariant.  For atom a, w(a) = elem | arom << 4 | (charge + 1) << 5 | in_ring << 7 | degree << 8 | used << 12.
+ *   - elem is the index into H B C N O F P S Cl Br I.
+ *   - degree is the number of graph neighbours.  Explicit [H] atoms are atoms.
+ *   - used is the final used valence: the sum of bond orders plus bracket hydrogens (what the atom word holds at <eos>).
+ *   - in_ring is the bit of the walk's ring mask.
+ *   - id_0(a) = mix(w(a)).
+ * Bond type.  For a bond between a and b, bt is 4 if its order is 1 and both ends are aromatic atoms.  Otherwise bt is the order.
+ * Rounds r = 1, 2.  id_r(a) = mix(id_{r-1}(a) * 0x9E3779B1 + r + SUM_{b in nbrs(a)} mix(id_{r-1}(b) ^ (bt(a,b) * 0x7FEB352D))).
+ *   - The neighbour sum is commutative.  Nothing is sorted.
+ *   - The result does not depend on how the atoms are numbered.
+ * Bits.  For every atom and every r in {0, 1, 2}, set bit id_r(a) & 1023.
+ *   - Bit b lives in word b >> 6, bit b & 63.
+ *   - A fingerprint is MVAE_FP_WORDS = 16 int64 words, 128 B.
+ *   - ECFP's duplicate-substructure removal is deliberately omitted.
+ * Rows that are not OK.  A row whose status is not OK (syntax, valence, charge, ring bond, aromatic, too long) gets an all-zero
+ *   fingerprint.  Status and fingerprint are written together: status int32 [B] as the graph entries give it, fp int64 [B, 16]; every
+ *   element of both is written, nothing else is.
+ * mvae_smiles_fp_rows / _corpus / _host: the inputs of mvae_smiles_graph_rows / _corpus / _host (padded int64 rows; the CSR corpus in one
+ *   launch; the same source compiled for the CPU, on host pointers).  One thread per row; 112 KiB of LDS per 64-row block.
+ * Refused before anything is enqueued: what the graph entries refuse (V > 64: MVAE_ERR_UNSUPPORTED; the rest MVAE_ERR_INVALID), and a
+ *   NULL fp.
+ */
+#define MVAE_FP_WORDS 16
+int mvae_smiles_fp_rows(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */, const int32_t* chem_info /* [V] */,
+                        int eos_id, int32_t* status /* [B] */, int64_t* fp /* [B, 16] */, void* stream);
+int mvae_smiles_fp_corpus(const uint8_t* tokens, const int64_t* offsets /* [N + 1] */, int64_t N, int V, const int32_t* tok_info /* [V] */,
+                          const int32_t* chem_info /* [V] */, int32_t* status /* [N] */, int64_t* fp /* [N, 16] */, void* stream);
+int mvae_smiles_fp_host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */, const int32_t* chem_info /* [V] */,
+                        int eos_id, int32_t* status /* [B] */, int64_t* fp /* [B, 16] */);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Tanimoto similarity of fingerprints (an addition: the structure-aware counterpart of mvae_latent_knn and mvae_edit_knn).  Fingerprints
+ * are dense rows of MVAE_FP_WORDS int64 words, 16-byte aligned (else MVAE_ERR_INVALID); any 1024-bit rows will do.
+ * Similarity.  T(a, b) = c / (p_a + p_b - c), with p the popcounts and c the popcount of a AND b; T is 0 when the union is empty.  T is
+ *   ONE correctly rounded f32 division of the two integers.  Numerators and denominators are <= 2048, so two different fractions differ
+ *   by at least 2^-22 and equal fractions give equal floats: f32 order is exact rational order.
+ * mvae_tanimoto_knn: for each of Q queries (q [Q, 16]) row i of sim / idx ([Q, k], dense) holds the k eligible rows of table [N, 16] with
+ *   the largest similarity, ordered by (similarity descending, row ascending).  Every row is eligible except exclude[i] (exclude [Q] int64
+ *   or NULL; -1 = none).  With fewer than k eligible rows the tail of the output row is (-1.0f, -1).  Every element of sim and idx is
+ *   written, nothing else is.  A query's answer does not depend on Q, on the other queries or on how the launch is laid out; two runs are
+ *   bitwise equal.  Nothing of size Q x N exists: one scan launch keeps a k-entry list per (query, wave) in LDS (as exact fractions; the
+ *   division happens where a result is written), and, when the table rows are split over `slots` partial lists per query to fill the chip
+ *   (slots depends on Q and N alone, <= 256), one merge launch combines them.  Workspace: mvae_tanimoto_knn_workspace(Q, N, k) = slots *
+ *   Q * k * 12 bytes (8-byte aligned; 0: one slot, none needed); it depends on (Q, N, k) alone.
+ *   Refused before anything is enqueued.  MVAE_ERR_INVALID: a NULL or misaligned pointer other than exclude; Q, N or k < 1.
+ *   MVAE_ERR_UNSUPPORTED: k > 32 (the workspace function then returns 0).  MVAE_ERR_WORKSPACE: a missing or short workspace.
+ * mvae_tanimoto_sum: out[0] (float64, device) = the sum of the f32 similarities over all M x N ordered pairs of a [M, 16] and b [N, 16];
+ *   with skip_diagonal != 0 the pairs with i == j are left out.  Accumulated in float64 in a fixed order (per lane over a's rows, a fixed
+ *   tree per block, then one block over the per-block partials): two runs are bitwise equal, and no floating-point atomic is used.
+ *   Internal diversity: IntDiv = 1 - sum / (M * M) with a == b is the MOSES form, diagonal included; skip_diagonal and M * (M - 1) give
+ *   the other convention.  Workspace: mvae_tanimoto_sum_workspace(M, N) bytes (8-byte aligned, never 0; it depends on (M, N) alone).
+ *   Refused before anything is enqueued.  MVAE_ERR_INVALID: a NULL or misaligned a / b, a NULL out, M or N < 1.  MVAE_ERR_WORKSPACE: a
+ *   missing or short workspace.
+ */
+size_t mvae_tanimoto_knn_workspace(int Q, int64_t N, int k);
+int mvae_tanimoto_knn(int Q, int64_t N, int k, const int64_t* q /* [Q, 16] */, const int64_t* table /* [N, 16] */,
+                      const int64_t* exclude /* [Q] or NULL, -1 = none */, float* sim /* [Q, k] */, int64_t* idx /* [Q, k] */, void* ws,
+                      size_t ws_bytes, void* stream);
+size_t mvae_tanimoto_sum_workspace(int64_t M, int64_t N);
+int mvae_tanimoto_sum(int64_t M, int64_t N, const int64_t* a /* [M, 16] */, const int64_t* b /* [N, 16] */, int skip_diagonal,
+                      double* out /* [1] */, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Optimiser surface (K14 + K15): torch.nn.utils.clip_grad_norm_(params, max_norm) (train.py:102) followed by
  * torch.optim.Adam.step() (train.py:81,104) on a FLAT fp32 parameter / gradient / m / v buffer.
  *   mvae_sumsq: partial[i] = sum of squares of chunk i (deterministic); norm_out[0] = sqrt(total) is

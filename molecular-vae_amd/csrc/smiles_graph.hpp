@@ -30,7 +30,7 @@ SMI_HD int vmax(int elem, int chg) {
 }
 
 // atom word: bits 0-7 the tree predecessor (NONE for the first atom), 8-15 the valence used (bonds + bracket hydrogens), 16-19 the
-// element, 20 aromatic, 21 bracket atom, 22-23 charge + 1
+// element, 20 aromatic, 21 bracket atom, 22-23 charge + 1; bits 24-31 are free for a recorder (below)
 SMI_HD uint32_t a_make(int pred, int used, int elem, int arom, int brk, int chg) {
   return (uint32_t)pred | (uint32_t)used << 8 | (uint32_t)elem << 16 | (uint32_t)arom << 20 | (uint32_t)brk << 21 | (uint32_t)(chg + 1) << 22;
 }
@@ -64,10 +64,22 @@ struct Row {
   u64 cnt_lo, cnt_hi;                 // atoms of element e = 1 .. 10, one byte each: e - 1 = 0 .. 7 in cnt_lo, 8 .. 9 in cnt_hi
 };
 
+// What a second consumer of the walk wants kept beyond the checks and the counts (fingerprint.hip).  The walk calls
+//   atom_bits(order)  at a new atom: bits 24-31 of its atom word (the order of the bond to its tree predecessor is not stored otherwise);
+//   closure(i, j)     at every ring-closure bond it accepts (those exist only as the `partner` mask of the current atom);
+//   done(n, ring)     at <eos> of a row whose status is OK: the number of atoms and the ring members.
+// NoRec keeps nothing: every call is empty and the walk compiles to what it was without a recorder.
+struct NoRec {
+  SMI_HD uint32_t atom_bits(int) const { return 0u; }
+  SMI_HD void closure(int, int) {}
+  SMI_HD void done(int, const Mask&) {}
+};
+
 // The graph under construction.  `at` holds the atom words 0 .. n - 1.
-template <class Atoms>
+template <class Atoms, class Rec = NoRec>
 struct Graph {
   Atoms& at;
+  Rec& rec;
   int status = OK, bad = -1;          // the first graph error and the column of its token
   int n = 0, cur = NONE, order = 1;   // atoms so far, the current atom, the pending bond order
   int nring = 0, hsum = 0, charge = 0;
@@ -76,7 +88,7 @@ struct Graph {
   u64 open_lo = 0, open_hi = 0;       // the atom that opened ring digit d, one byte each: 0 .. 7 in open_lo, 8 .. 9 in open_hi
   int k_elem = 0, k_arom = 0, k_h = 0, k_sign = 0, k_mag = -1;      // the bracket atom being read
 
-  SMI_HD explicit Graph(Atoms& a) : at(a) {}
+  SMI_HD Graph(Atoms& a, Rec& r) : at(a), rec(r) {}
 
   SMI_HD void fail(int st, int col) {
     if (status == OK) { status = st; bad = col; }
@@ -93,7 +105,7 @@ struct Graph {
       used += order;
       if (!a_fits(pw)) fail(VALENCE, col);
     }
-    const uint32_t w = a_make(cur, used, elem, ar, brk, chg);
+    const uint32_t w = a_make(cur, used, elem, ar, brk, chg) | rec.atom_bits(order);
     at.set(k, w);
     if (!a_fits(w)) fail(VALENCE, col);
     if (ar) m_set(arom, k);
@@ -121,6 +133,7 @@ struct Graph {
     if (!a_fits(wi) || !a_fits(wj)) fail(VALENCE, col);
     m_set(partner, i);
     ++nring;
+    rec.closure(i, j);
     // the tree path i .. j through the lowest common ancestor: a predecessor has a lower index than its atom, so the higher of the two
     // ends steps up until they meet
     int a = i, b = j;
@@ -208,12 +221,12 @@ struct Graph {
 
 // One row.  src.tok(t) is the token at column t, first <= t < end.  end_is_eos: the end of the row acts as <eos> at column `end` (the CSR
 // corpus); else only the id eos_id ends the row (pass eos_id = -1 with end_is_eos: no id does).  An id that tok_info calls EOS and that is
-// not eos_id is refused, as mvae_smiles_syntax_check refuses it.
-template <class Atoms, class Src>
+// not eos_id is refused, as mvae_smiles_syntax_check refuses it.  rec: the recorder (NoRec: the overload below).
+template <class Atoms, class Src, class Rec>
 SMI_HD void walk(Atoms& at, const Src& src, int first, int end, bool end_is_eos, int V, const int32_t* tok_info, const int32_t* chem_info,
-                 int eos_id, Row* r) {
+                 int eos_id, Row* r, Rec& rec) {
   smi::State s{smi::START, 0, smi::NO_PREV, 0, 0};
-  Graph<Atoms> g(at);
+  Graph<Atoms, Rec> g(at, rec);
   int syn_bad = end, eos_col = -1;
   const int last = end_is_eos ? end + 1 : end;
   for (int t = first; t < last; ++t) {
@@ -240,6 +253,14 @@ SMI_HD void walk(Atoms& at, const Src& src, int first, int end, bool end_is_eos,
   if (eos_col - first > CONTENT_MAX) { r->status = TOO_LONG; r->bad_pos = eos_col; return; }
   if (g.status == OK) g.finish(eos_col, r);
   if (g.status != OK) { *r = Row{g.status, g.bad, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; }
+  else rec.done(g.n, g.ring);
+}
+
+template <class Atoms, class Src>
+SMI_HD void walk(Atoms& at, const Src& src, int first, int end, bool end_is_eos, int V, const int32_t* tok_info, const int32_t* chem_info,
+                 int eos_id, Row* r) {
+  NoRec rec;
+  walk(at, src, first, end, end_is_eos, V, tok_info, chem_info, eos_id, r, rec);
 }
 
 // Row b of the outputs; a row that is not OK gets zeros in desc and formula.

@@ -220,6 +220,7 @@ class MosesDeviceDataset:
         self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._slots = self._n_distinct_d = self._n_distinct = None     # the corpus index: built on first use
         self._descriptors = None                                       # descriptors(): computed on first use
+        self._fingerprints = None                                      # fingerprints(): computed on first use
 
     def __len__(self):
         return self.n
@@ -327,6 +328,48 @@ class MosesDeviceDataset:
             tok, chem = smiles_token_table(self.vocab).to(self.device), smiles_chem_table(self.vocab).to(self.device)
             self._descriptors = ops.graph_descriptors(*ops.smiles_graph_corpus(self.tokens, self.offsets, self.n, tok, chem))
         return self._descriptors
+
+    def _fp_tables(self, who):
+        from .models import _require_cuda
+        from .vocab import smiles_token_table, smiles_chem_table
+        if len(self.vocab) > 64:
+            raise ValueError(f"{who}: the vocabulary has {len(self.vocab)} ids, at most 64 are supported")
+        _require_cuda(self.device, "MosesDeviceDataset." + who)
+        if self.__dict__.get("_smi_tables") is None:
+            self._smi_tables = (smiles_token_table(self.vocab).to(self.device), smiles_chem_table(self.vocab).to(self.device))
+        return self._smi_tables
+
+    def fingerprints(self):
+        """The circular fingerprint of every corpus row, in corpus order: {"status": int32 [N], "fp": int64 [N, 16]} on the device
+        (``VAE.fingerprints``: 1024 bits, built like ECFP4 but not rdkit's Morgan fingerprint; zeros where status is not 0), from ONE
+        ``mvae_smiles_fp_corpus`` launch over the CSR rows.  Cached; never waits for the device.  ValueError for a vocabulary of more
+        than 64 ids."""
+        if self._fingerprints is None:
+            from . import ops
+            tok, chem = self._fp_tables("fingerprints")
+            status, fp = ops.smiles_fp_corpus(self.tokens, self.offsets, self.n, tok, chem)
+            self._fingerprints = {"status": status, "fp": fp}
+        return self._fingerprints
+
+    def nearest_fingerprints(self, x, k=1, exclude_self=False):
+        """The k corpus rows whose fingerprints are most similar (Tanimoto) to that of each row of x, which is whatever ``lookup``
+        takes: (sim float32 [Q, k], rows int64 [Q, k]) on the device, ordered by (similarity descending, row ascending); a tail that
+        cannot be filled is (-1.0, -1).  The structure-aware counterpart of ``nearest_strings``: one fingerprint launch for x and one
+        ``mvae_tanimoto_knn`` launch (two when the corpus is split over workgroups) against ``fingerprints()``, no host wait.  Every
+        corpus row is eligible, a row that is not ok with its all-zero fingerprint (similarity 0); a query that is not ok is similar
+        to nothing (0 everywhere, so it answers with the lowest rows).  ``exclude_self``: a query that is itself a corpus row
+        (``lookup``) does not answer with that row.  ValueError, before any device work: a vocabulary of more than 64 ids, k outside
+        [1, 32]."""
+        from . import ops
+        if len(self.vocab) > 64:
+            raise ValueError(f"nearest_fingerprints: the vocabulary has {len(self.vocab)} ids, at most 64 are supported")
+        if int(k) != k or not 1 <= k <= ops.TANIMOTO_K_MAX:
+            raise ValueError(f"nearest_fingerprints: k must be an integer in [1, {ops.TANIMOTO_K_MAX}], got {k!r}")
+        x = self._token_rows(x, "nearest_fingerprints")
+        tok, chem = self._fp_tables("nearest_fingerprints")
+        _, fp = ops.smiles_fp_rows(x, tok, chem, self.vocab.eos)
+        exclude = self._probe(x) if exclude_self else None
+        return ops.tanimoto_knn(fp, self.fingerprints()["fp"], int(k), exclude=exclude)
 
     def contains(self, x):
         """``lookup(x) >= 0``: bool [B] on the device."""

@@ -501,6 +501,34 @@ class VAE(_SavedState, nn.Module):
         have zeros everywhere."""
         return ops.graph_descriptors(*self._graph_rows(x, "descriptors"))
 
+    @torch.no_grad()
+    def fingerprints(self, x):
+        """The circular fingerprint of token rows x (what ``syntax_valid`` takes): {"status": int32 [B], "fp": int64 [B, 16]} on the
+        device, one mvae_smiles_fp_rows launch, no host wait.  1024 bits per row, radius 2, built like ECFP4 on the graph of the SMILES
+        graph walk but NOT rdkit's Morgan fingerprint (include/mvae.h, "Circular fingerprint": nothing is kekulised, the bits are
+        comparable within this library only); "status" is ``chem_valid``'s, and a row whose status is not 0 has an all-zero
+        fingerprint.  ValueError for a vocabulary of more than 64 ids."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.fingerprints")
+        if len(self.vocabulary) > 64:
+            raise ValueError(f"fingerprints: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
+        status, fp = ops.smiles_fp_rows(self._rows(x, "fingerprints", dev), self._smiles_table(dev), self._smiles_chem_table(dev), self.eos)
+        return {"status": status, "fp": fp}
+
+    @torch.no_grad()
+    def tanimoto(self, x, y):
+        """The Tanimoto similarity of the fingerprints of two batches, pair by pair: float32 [B] on the device, |a & b| / |a | b| as one
+        f32 division, 0 where the union is empty (so 0 wherever a row is not ok).  x, y: what ``fingerprints`` takes, equally many
+        rows (ValueError otherwise).  Two fingerprint launches and a few torch ops; the search over a corpus is
+        ``MosesDeviceDataset.nearest_fingerprints``."""
+        a, b = self.fingerprints(x)["fp"], self.fingerprints(y)["fp"]
+        if a.shape[0] != b.shape[0]:
+            raise ValueError(f"tanimoto: {a.shape[0]} rows against {b.shape[0]}")
+        count = lambda t: ((t.view(torch.uint8)[:, :, None] >> torch.arange(8, device=t.device, dtype=torch.uint8)) & 1).sum((1, 2))
+        c = count(a & b)
+        u = count(a) + count(b) - c
+        return torch.where(u > 0, c.float() / u.clamp(min=1).float(), torch.zeros((), device=a.device))
+
     def edit_distance(self, x, y):
         """The token-level Levenshtein distance (unit costs for insert, delete and substitute, no transposition) between the rows of two
         batches, pair by pair: int32 [B] on the device, one launch (mvae_edit_distance_rows), no host wait.  x, y: padded ids [B, T] (bos

@@ -792,6 +792,102 @@ def graph_descriptors(status, bad_pos, desc, formula):
     return out
 
 
+FP_WORDS = 16                                 # include/mvae.h: MVAE_FP_WORDS, the int64 words of a fingerprint (1024 bits)
+TANIMOTO_K_MAX = 32
+
+
+def _fp_outputs(n, dev, status, fp):
+    status = torch.empty(n, dtype=torch.int32, device=dev) if status is None else status
+    fp = torch.empty(n, FP_WORDS, dtype=torch.int64, device=dev) if fp is None else fp
+    for t, dt, shape in ((status, torch.int32, (n,)), (fp, torch.int64, (n, FP_WORDS))):
+        assert t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev, (t.dtype, tuple(t.shape), t.device)
+    return status, fp
+
+
+def smiles_fp_rows(x, tok_info, chem_info, eos_id, status=None, fp=None):
+    """The circular fingerprint of token rows x (int64 [B, T], bos first) on the device: (status int32 [B], fp int64 [B, 16]) -- the
+    status of smiles_graph_rows and 1024 bits per row, radius 2, built like ECFP4 but NOT rdkit's Morgan fingerprint (include/mvae.h,
+    "Circular fingerprint"); all zeros for a row whose status is not 0.  One launch (mvae_smiles_fp_rows)."""
+    x, ldx = _token_rows(x, "x")
+    _graph_tables(tok_info, chem_info, x.device)
+    out = _fp_outputs(x.shape[0], x.device, status, fp)
+    check(L.load().mvae_smiles_fp_rows(x.shape[0], x.shape[1], tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), int(eos_id),
+                                       *map(ptr, out), stream_ptr()), "mvae_smiles_fp_rows")
+    return out
+
+
+def smiles_fp_corpus(tokens, offsets, N, tok_info, chem_info, status=None, fp=None):
+    """smiles_fp_rows over the CSR corpus (tokens uint8, offsets int64 [N + 1]; rows without specials, the end of a row acting as
+    <eos>): one launch (mvae_smiles_fp_corpus)."""
+    N = int(N)
+    assert tokens.dtype == torch.uint8 and offsets.dtype == torch.int64 and offsets.numel() >= N + 1 and tokens.device == offsets.device
+    assert tokens.is_contiguous() and offsets.is_contiguous()
+    _graph_tables(tok_info, chem_info, tokens.device)
+    out = _fp_outputs(max(N, 0), tokens.device, status, fp)
+    check(L.load().mvae_smiles_fp_corpus(ptr(tokens), ptr(offsets), N, tok_info.numel(), ptr(tok_info), ptr(chem_info), *map(ptr, out),
+                                         stream_ptr()), "mvae_smiles_fp_corpus")
+    return out
+
+
+def smiles_fp_host(x, tok_info, chem_info, eos_id, status=None, fp=None):
+    """smiles_fp_rows on HOST tensors: the same source compiled for the CPU, a plain loop over the rows (mvae_smiles_fp_host) -- for tests
+    and for machines without a device; not a fallback of the device entries."""
+    x, ldx = _token_rows(x, "x")
+    assert x.device.type == "cpu", x.device
+    _graph_tables(tok_info, chem_info, x.device)
+    out = _fp_outputs(x.shape[0], x.device, status, fp)
+    check(L.load().mvae_smiles_fp_host(x.shape[0], x.shape[1], tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), int(eos_id),
+                                       *map(ptr, out)), "mvae_smiles_fp_host")
+    return out
+
+
+def _fp_table(t, name):
+    assert t.dim() == 2 and t.shape[1] == FP_WORDS and t.dtype == torch.int64 and t.shape[0] >= 1, (name, t.dtype, tuple(t.shape))
+    return t.contiguous()
+
+
+def tanimoto_knn(q, table, k, exclude=None, sim=None, idx=None):
+    """The k rows of table [N, 16] most similar to every row of q [Q, 16] (int64 fingerprints) by Tanimoto similarity |a & b| / |a | b|
+    (0 for an empty union; one correctly rounded f32 division): (sim [Q, k] float32, idx [Q, k] int64), ordered by (similarity
+    descending, row ascending); exclude (int64 [Q], optional) names one table row per query to skip (-1: none); a short tail is
+    (-1.0, -1) (mvae_tanimoto_knn; its workspace comes from Scratch)."""
+    lib = L.load()
+    q, table = _fp_table(q, "q"), _fp_table(table, "table")
+    assert q.device == table.device
+    Q, N, k = q.shape[0], table.shape[0], int(k)
+    if exclude is not None:
+        assert exclude.dtype == torch.int64 and exclude.shape == (Q,) and exclude.device == q.device
+        exclude = exclude.contiguous()
+    if sim is None:
+        sim = torch.empty(Q, max(k, 0), dtype=torch.float32, device=q.device)
+    if idx is None:
+        idx = torch.empty(Q, max(k, 0), dtype=torch.int64, device=q.device)
+    assert sim.shape == (Q, k) and idx.shape == (Q, k) and sim.is_contiguous() and idx.is_contiguous()
+    assert sim.dtype == torch.float32 and idx.dtype == torch.int64 and sim.device == q.device == idx.device
+    nb = lib.mvae_tanimoto_knn_workspace(Q, N, k)
+    ws = Scratch.get(nb, q.device, "tanimoto_knn") if nb else None
+    check(lib.mvae_tanimoto_knn(Q, N, k, ptr(q), ptr(table), ptr(exclude), ptr(sim), ptr(idx), ptr(ws), nb, stream_ptr()), "mvae_tanimoto_knn")
+    return sim, idx
+
+
+def tanimoto_sum(a, b, skip_diagonal=False, out=None):
+    """out (float64 [1], on the device) := the sum of the f32 Tanimoto similarities over all ordered pairs of a [M, 16] and b [N, 16]
+    (int64 fingerprints); skip_diagonal leaves out the pairs with i == j.  Accumulated in float64 in a fixed order, two runs are bitwise
+    equal (mvae_tanimoto_sum; its workspace comes from Scratch).  IntDiv = 1 - tanimoto_sum(a, a) / M^2 is the MOSES form (diagonal
+    included); skip_diagonal and M (M - 1) give the other convention."""
+    lib = L.load()
+    a, b = _fp_table(a, "a"), _fp_table(b, "b")
+    assert a.device == b.device
+    if out is None:
+        out = torch.empty(1, dtype=torch.float64, device=a.device)
+    assert out.dtype == torch.float64 and out.shape == (1,) and out.device == a.device
+    M, N = a.shape[0], b.shape[0]
+    nb = lib.mvae_tanimoto_sum_workspace(M, N)
+    ws = Scratch.get(nb, a.device, "tanimoto_sum")
+    check(lib.mvae_tanimoto_sum(M, N, ptr(a), ptr(b), int(bool(skip_diagonal)), ptr(out), ptr(ws), nb, stream_ptr()), "mvae_tanimoto_sum")
+    return out
+
+
 def sample_uniform(seed, step, B):
     """Host restatement of the sampling step's uniforms u(b) = hash(seed, step * B + b) / 2^32 (tests)."""
     import numpy as np

@@ -800,7 +800,8 @@ def moses_reconstruction(model, batches, beam_width=1, max_len=100, syntax=False
 
 @torch.no_grad()
 def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top_k=None, top_p=None, seed=0, z=None, syntax=False,
-                   count_valid=False, novel_against=None, prefix=None, nearest=False, valence=False):
+                   count_valid=False, novel_against=None, prefix=None, nearest=False, valence=False,
+                   int_div=False, snn=False):
     """The reference's generation pipeline (``hugesample.py``: sample in batches, hash the strings, count unique / total) with the hashing
     and the deduplication on the device: ``n_samples`` sequences from a ``mosesvae.VAE`` in batches of ``batch_size`` (the last one shorter),
     batch j with seed ``seed + j`` and ``temp`` / ``top_k`` / ``top_p`` as ``VAE.sample`` takes them.  ``z`` None draws each batch's latents
@@ -845,7 +846,18 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     distinct ones) and, with ``novel_against``, "chem_valid_unique_novel"; "status_counts" ({status: count} over all samples, the codes
     of ``ops.SMILES_STATUS_NAMES``); and the lists "status", "weight" (molecular weight, 0.0 for a sample that is not ok), "heavy_atoms"
     and "rings", aligned with "strings", which travel once, at the end, as "corpus_row" does.  Without ``valence`` the launches and the
-    keys of the result are what they were."""
+    keys of the result are what they were.
+    ``int_div=True`` / ``snn=True`` (ValueError for a vocabulary of more than 64 ids, and for ``snn`` without ``novel_against``, before
+    any device work): the two MOSES figures defined on fingerprints, on the fingerprint of ``VAE.fingerprints`` -- 1024 bits of radius 2,
+    built like ECFP4 but NOT rdkit's Morgan fingerprint, so the figures compare runs of this library and not with published tables.
+    Each batch's NEW rows are fingerprinted (one ``mvae_smiles_fp_rows`` launch, no further host wait).  With ``int_div`` the
+    fingerprints of the distinct samples whose status is 0 stay on the device and one ``mvae_tanimoto_sum`` at the end gives "int_div"
+    = 1 - (sum of the similarities over all ordered pairs, each sample with itself included) / n^2, the MOSES form (NaN for n = 0);
+    "n_fingerprinted" is that n (it is added by either flag).  With ``snn`` each batch makes one ``mvae_tanimoto_knn`` launch (k = 1)
+    against ``novel_against.fingerprints()`` and the result gains "snn" (the mean, over the distinct samples whose status is 0, of the
+    largest Tanimoto similarity to any corpus row; NaN for none) and "snn_sim" / "snn_row", aligned with "strings": that similarity
+    and the lowest corpus row that has it, -1.0 / -1 for a sample that is not ok.  They travel once, at the end.  Without either flag
+    the launches and the keys of the result are what they were."""
     n_samples, batch_size, max_len = int(n_samples), int(batch_size), int(max_len)
     if n_samples < 1 or batch_size < 1 or max_len < 1:
         raise ValueError(f"moses_generate: n_samples, batch_size and max_len must be >= 1, got {n_samples}, {batch_size}, {max_len}")
@@ -867,7 +879,6 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
                                   != (torch.cuda.current_device() if dev.index is None else dev.index)):
             raise ValueError(f"moses_generate: novel_against lives on {d}, the model on {dev}")
     if nearest:
-        from . import ops
         if novel_against is None:
             raise ValueError("moses_generate: nearest=True needs novel_against, the corpus to search")
         if len(model.vocabulary) > ops.EDIT_V_MAX:
@@ -876,6 +887,10 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
             raise ValueError(f"moses_generate: nearest=True supports max_len <= {ops.EDIT_PATTERN_MAX + 1}, got {max_len}")
     if valence and len(model.vocabulary) > 64:
         raise ValueError(f"moses_generate: valence=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
+    if (int_div or snn) and len(model.vocabulary) > 64:
+        raise ValueError(f"moses_generate: int_div / snn support at most 64 ids, the vocabulary has {len(model.vocabulary)}")
+    if snn and novel_against is None:
+        raise ValueError("moses_generate: snn=True needs novel_against, the corpus to search")
     if forced is not None and syntax:
         model._check_prefix_syntax(forced, max_len, "moses_generate")      # every sample's prefix, once, before the first batch: rows are sample indices
     i64 = torch.long
@@ -892,6 +907,10 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     n_chem = torch.zeros(3, dtype=i64, device=dev) if valence else None      # status 0: all samples, distinct ones, distinct and novel
     status_counts = torch.zeros(7, dtype=i64, device=dev) if valence else None
     status_codes = torch.arange(7, dtype=torch.int32, device=dev) if valence else None
+    fps = []                                                    # the fingerprints of the new samples whose status is 0, likewise
+    snns = []                                                   # (similarity, row) of each new sample's most similar corpus row, likewise
+    n_fp = torch.zeros((), dtype=i64, device=dev) if int_div or snn else None
+    snn_sum = torch.zeros((), dtype=torch.float64, device=dev) if snn else None
     stage = [None, None]                                        # pinned staging rows [batch_size, max_len + 1] (ids, end), alternating
     pending = None
 
@@ -952,6 +971,17 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
                 near.append(novel_against.nearest_strings(x[sel], k=1))
             if valence:
                 chem.append(tuple(graph[name][sel] for name in ("status", "weight", "heavy_atoms", "rings")))
+            if int_div or snn:
+                f = model.fingerprints(x[sel])
+                fine = f["status"] == 0
+                n_fp += fine.sum()
+                if int_div:
+                    fps.append((f["fp"], fine))                  # compacted once, at the end: a boolean index here would wait for its size
+                if snn:
+                    s_sim, s_row = ops.tanimoto_knn(f["fp"], novel_against.fingerprints()["fp"], 1)
+                    s_sim = torch.where(fine, s_sim[:, 0], torch.full_like(s_sim[:, 0], -1.0))
+                    snns.append((s_sim, torch.where(fine, s_row[:, 0], torch.full_like(s_row[:, 0], -1))))
+                    snn_sum += torch.where(fine, s_sim, torch.zeros_like(s_sim)).double().sum()
             g0 = counts.numel()
             counts = torch.cat([counts, cnt[src]])
             seen_h, perm = torch.sort(torch.cat([seen_h, hs[src]]))
@@ -980,6 +1010,16 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         res["status_counts"] = dict(enumerate(status_counts.tolist()))
         for i, name in enumerate(("status", "weight", "heavy_atoms", "rings")):
             res[name] = torch.cat([c[i] for c in chem]).tolist() if chem else []
+    if int_div or snn:
+        res["n_fingerprinted"] = int(n_fp)
+    if int_div:
+        table = torch.cat([a for a, _ in fps])[torch.cat([b for _, b in fps])] if fps else None
+        m = 0 if table is None else table.shape[0]
+        res["int_div"] = 1.0 - float(ops.tanimoto_sum(table, table)) / (m * m) if m else float("nan")
+    if snn:
+        res["snn"] = float(snn_sum) / res["n_fingerprinted"] if res["n_fingerprinted"] else float("nan")
+        res["snn_sim"] = torch.cat([a for a, _ in snns]).tolist() if snns else []
+        res["snn_row"] = torch.cat([b for _, b in snns]).tolist() if snns else []
     return res
 
 
