@@ -23,6 +23,13 @@ samples (``mv.moses_generate(int_div=True, snn=True)``): IntDiv, 1 - the mean pa
 valence-consistent samples (each with itself included, the MOSES form), and SNN, the mean over those samples of the largest similarity to
 any training molecule.  The fingerprint is this library's own 1024-bit circular fingerprint (``VAE.fingerprints``), built like ECFP4 but
 not rdkit's Morgan fingerprint: the figures compare runs of this script, not published tables.
+``--scaffolds`` prints, for each round, the distinct molecular graphs and the distinct Murcko scaffolds among the samples
+(``mv.moses_generate(scaffolds=True)``: 64-bit graph keys that do not depend on how a string spells its molecule, so ``OCC`` and ``C(O)C``
+are one graph) and, with ``--novel_against``, the MOSES Scaf figure -- the cosine similarity of the generated and the training scaffold
+histograms --, the scaffolds and the graphs absent from the corpus; at the end the five most frequent generated scaffolds, each with a
+sample that has it and one training molecule that has it (``MosesDeviceDataset.rows_with_scaffold``).  The scaffold is the rings, the
+linkers between them and the atoms double-bonded to either, on the graph of the SMILES graph walk: not rdkit's MurckoScaffold, and no
+scaffold SMILES is produced.
 ``--reconstruct FILE`` (strings, one per line) skips the generation: it encodes the strings (z = mu), decodes them deterministically
 (``--beam_width``) without and with the syntax constraint (``mv.moses_reconstruction(..., syntax=)``) and prints the exact-match
 reconstruction fraction of each, the mean log p(x | mu) and the mean token edit distance between input and decode.
@@ -66,6 +73,8 @@ ap.add_argument("--valence", action="store_true", help="count the valence-consis
 ap.add_argument("--int_div", action="store_true", help="print each round's internal diversity (1 - mean pairwise Tanimoto similarity of the "
                                                        "library's circular fingerprints)")
 ap.add_argument("--snn", action="store_true", help="with --novel_against: print each round's mean similarity to the nearest training molecule")
+ap.add_argument("--scaffolds", action="store_true", help="print each round's distinct graphs and Murcko scaffolds and, with --novel_against, the "
+                                                         "Scaf figure; at the end the most frequent generated scaffolds")
 ap.add_argument("--reconstruct", default=None, metavar="FILE", help="strings, one per line: report exact-match reconstruction at z = mu "
                                                                   "without and with the syntax constraint, then exit")
 ap.add_argument("--beam_width", default=1, type=int, help="with --reconstruct: the beam width of the deterministic decode")
@@ -122,6 +131,7 @@ seen, total, valid, syntax_valid = {}, 0, 0, 0
 chem_valid, reasons, props = 0, [0] * 7, {}               # unique valence-consistent string -> (weight, heavy atoms)
 near = {}                                                 # unique string -> (distance, corpus row) of its nearest training string
 novel = set()                                             # the unique strings that are not in the corpus
+scaffold_count, scaffold_sample = {}, {}                  # scaffold key -> samples drawn with it (duplicates included), one such string
 per_round = args.batch_size * args.batches_per_round
 start = time.time()
 with open(args.log, "w", buffering=1) as f:
@@ -130,8 +140,13 @@ with open(args.log, "w", buffering=1) as f:
         res = mv.moses_generate(model, per_round, batch_size=args.batch_size, max_len=args.max_len, temp=args.temp, top_k=args.top_k,
                                 top_p=args.top_p, seed=args.seed + r * args.batches_per_round, syntax=args.syntax, count_valid=True,
                                 novel_against=corpus, prefix=args.prefix, nearest=args.nearest, valence=args.valence,
-                                int_div=args.int_div, snn=args.snn)
+                                int_div=args.int_div, snn=args.snn, scaffolds=args.scaffolds)
         total += res["total"]
+        if args.scaffolds:
+            for s, c, key in zip(res["strings"], res["counts"], res["scaffold_key"]):
+                if key:
+                    scaffold_count[key] = scaffold_count.get(key, 0) + c
+                    scaffold_sample.setdefault(key, s)
         if args.valence:
             chem_valid += res["chem_valid"]
             reasons = [a + res["status_counts"][k] for k, a in enumerate(reasons)]
@@ -155,8 +170,25 @@ with open(args.log, "w", buffering=1) as f:
               + (f", valence-consistent {chem_valid} ({chem_valid / total:.3f})" if args.valence else "")
               + (f", IntDiv of this round's {res['n_fingerprinted']} valence-consistent unique samples {res['int_div']:.4f}" if args.int_div else "")
               + (f", SNN {res['snn']:.4f}" if args.snn else "")
+              + (f", this round's distinct graphs {res['unique_graphs']} and scaffolds {res['n_scaffolds']}" if args.scaffolds else "")
+              + (f", Scaf {res['scaf']:.4f}, scaffolds not in the corpus {res['scaffold_novel']}, graphs not in the corpus {res['graph_novel']}"
+                 if args.scaffolds and corpus is not None else "")
               + (f", valid unique {valid}" if Chem is not None else "")
               + (f", novel {len(novel)} ({len(novel) / len(seen):.3f} of unique)" if corpus is not None else ""), flush=True)
+if args.scaffolds and scaffold_count:
+    top = sorted(scaffold_count, key=lambda k: (-scaffold_count[k], k))[:5]
+    shown = [scaffold_sample[k] for k in top]
+    names = [None] * len(top)
+    if corpus is not None:
+        offsets, rows = corpus.rows_with_scaffold(shown)
+        offsets, rows = offsets.tolist(), rows.tolist()
+        first = [rows[offsets[i]] if offsets[i + 1] > offsets[i] else -1 for i in range(len(top))]
+        names = corpus.smiles(first)
+        shared = [offsets[i + 1] - offsets[i] for i in range(len(top))]
+    print(f"{len(scaffold_count)} distinct scaffolds among {total} samples; the most frequent (samples drawn, a sample that has it"
+          + (", training molecules that have it, one of them" if corpus is not None else "") + "):", flush=True)
+    for i, k in enumerate(top):
+        print(f"    {scaffold_count[k]:8d}  {shown[i]}" + (f"  {shared[i]:8d}  {names[i] if names[i] is not None else '-'}" if corpus is not None else ""))
 if args.valence:
     from molecular_vae_amd import ops
 

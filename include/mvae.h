@@ -866,6 +866,63 @@ int mvae_smiles_fp_host(int B, int T, int V, const int64_t* x, int64_t x_ld, con
                         int eos_id, int32_t* status /* [B] */, int64_t* fp /* [B, 16] */);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Murcko scaffold (an addition: a third consumer of the "SMILES graph" walk above).  The Bemis-Murcko framework of a row -- its rings,
+ * the linkers between them, and the atoms double-bonded to either -- as a set of the row's atoms.  It is defined on the graph exactly as
+ * the walk builds it: explicit [H] are atoms, ring-closure bonds are order 1, nothing is kekulised, '@' '/' '\' carry no information.  So
+ * this is NOT rdkit's MurckoScaffold: the atom sets agree where the two graphs agree, but no scaffold SMILES is produced, nothing is
+ * sanitised, and the keys below are this library's own.  Not rdkit, not kekulised.
+ * Atoms are numbered in string order (the order in which the walk creates them), from 0; a row has at most 127.
+ * Core.  The ring atoms (the walk's ring mask: the atoms that lie on a cycle), plus every non-ring atom that lies on a path between two
+ *   ring atoms.  Equivalently: what is left after repeatedly deleting atoms with at most one remaining neighbour.  Equivalently: a non-ring
+ *   atom belongs to Core iff at least two of the components left when it is removed contain a ring atom.
+ * Exo.  The atoms outside Core joined to a Core atom by a bond of order 2: the =O of a ring or linker carbonyl, both =O of a linker
+ *   sulfonyl, an exocyclic =C.  (rdkit keeps these too.)
+ * S = Core u Exo, with the bonds of the row that join two atoms of S.  A row with no ring has the empty scaffold.
+ * Ring bond.  A bond is a ring bond iff it lies on a cycle: every closure bond, and every tree bond k - pred(k) that some closure's
+ *   tree path (the path between its two ends through their lowest common ancestor) steps over.
+ *
+ * Graph key (an addition).  A 64-bit key of an atom subset U of a row with its induced bonds, equal for equal graphs however the string
+ * spells them.  All arithmetic is mod 2^32; mix and the bond type bt are the "Circular fingerprint" section's.
+ *   id_0(a) = mix(w_U(a)).
+ *   For r = 1 .. MVAE_GRAPH_KEY_ROUNDS (= 8):
+ *     id_r(a) = mix(id_{r-1}(a) * 0x9E3779B1 + r + SUM_{b in nbrs_U(a)} mix(id_{r-1}(b) ^ (bt'(a,b) * 0x7FEB352D))),
+ *     bt'(a,b) = bt(a,b) + 8 * ring_bond(a,b).  The ring-bond bit is what tells decalin from bicyclopentyl, which neighbour refinement
+ *     on atom invariants alone cannot separate.  nbrs_U(a): the neighbours of a that are in U.
+ *   lo = mix(|U| * 0x9E3779B1 + SUM_{a in U} mix(id_8(a)));  hi = mix(bonds(U) * 0x85EBCA6B + SUM_{a in U} mix(id_8(a) ^ 0x5BD1E995)).
+ *   key = lo | hi << 32 as int64; a result of 0 becomes 1.  0 means "none": U is empty, or the row is not OK.
+ *   Molecule key: U = all atoms, w_U(a) = the fingerprint's w(a) (element, aromatic flag, charge, ring membership, degree, used valence).
+ *   Scaffold key: U = S, w_S(a) = elem | arom << 4 | (charge + 1) << 5 | in_ring << 7 | deg_S(a) << 8, deg_S the number of neighbours in S.
+ *     The used valence is left out, because removing substituents changes it: benzene, toluene and phenol have one scaffold key.
+ *   Ring membership and ring bonds are those of the whole row in both keys.  Stereochemistry is ignored.
+ *   What the keys promise.  Equal graphs always get equal keys.  Different graphs get different keys except for collisions of the 64-bit
+ *     hash and for graphs that 8 rounds of neighbour refinement with these invariants cannot separate (regular graphs of equal degree
+ *     and ring-bond pattern, for example).  tests/test_scaffold_host.py lists what is known to be separated.  This is not a canonical
+ *     SMILES, and "distinct graphs" counted on these keys is a lower bound in that sense.
+ * Outputs, per row: status int32 [B] as the graph entries give it; mask int64 [B, 2] (optional, may be NULL): bit a of word a >> 6 = atom
+ *   a is in S; desc int32 [B, 4] = |S|, bonds of S, linker atoms (Core minus the ring atoms), |Exo|; key int64 [B, 2] = molecule key,
+ *   scaffold key.  Every element of the given outputs is written, nothing else is.  A row whose status is not 0 gets zeros everywhere; a
+ *   row with status 0 and no ring gets zeros except for its molecule key.
+ * mvae_smiles_scaffold_rows / _corpus / _host: the inputs of mvae_smiles_fp_rows / _corpus / _host.  One thread per row;
+ *   MVAE_SCAFFOLD_LDS_BYTES = 81920 B (80 KiB) of LDS per 64-row block, so that two blocks fit a CU: the atom words, whose storage
+ *   becomes the neighbour sums once they are packed (32 KiB), the ids (32 KiB), and the packed atoms with the closure pairs (16 KiB).
+ *   The two keys of a row run 16 refinement rounds in all.
+ * Refused before anything is enqueued: what the fingerprint entries refuse (V > 64: MVAE_ERR_UNSUPPORTED; the rest MVAE_ERR_INVALID),
+ *   and a NULL desc or key.
+ */
+#define MVAE_GRAPH_KEY_ROUNDS 8
+#define MVAE_SCAFFOLD_DESC 4
+#define MVAE_SCAFFOLD_LDS_BYTES 81920
+int mvae_smiles_scaffold_rows(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */,
+                              const int32_t* chem_info /* [V] */, int eos_id, int32_t* status /* [B] */, int64_t* mask /* [B, 2] or NULL */,
+                              int32_t* desc /* [B, 4] */, int64_t* key /* [B, 2] */, void* stream);
+int mvae_smiles_scaffold_corpus(const uint8_t* tokens, const int64_t* offsets /* [N + 1] */, int64_t N, int V, const int32_t* tok_info /* [V] */,
+                                const int32_t* chem_info /* [V] */, int32_t* status /* [N] */, int64_t* mask /* [N, 2] or NULL */,
+                                int32_t* desc /* [N, 4] */, int64_t* key /* [N, 2] */, void* stream);
+int mvae_smiles_scaffold_host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */,
+                              const int32_t* chem_info /* [V] */, int eos_id, int32_t* status /* [B] */, int64_t* mask /* [B, 2] or NULL */,
+                              int32_t* desc /* [B, 4] */, int64_t* key /* [B, 2] */);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Tanimoto similarity of fingerprints (an addition: the structure-aware counterpart of mvae_latent_knn and mvae_edit_knn).  Fingerprints
  * are dense rows of MVAE_FP_WORDS int64 words, 16-byte aligned (else MVAE_ERR_INVALID); any 1024-bit rows will do.
  * Similarity.  T(a, b) = c / (p_a + p_b - c), with p the popcounts and c the popcount of a AND b; T is 0 when the union is empty.  T is

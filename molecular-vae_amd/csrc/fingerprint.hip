@@ -1,7 +1,8 @@
 // Circular fingerprints of SMILES token rows and Tanimoto similarity over them (gfx950): mvae_smiles_fp_rows / _corpus / _host,
 // mvae_tanimoto_knn, mvae_tanimoto_sum.  include/mvae.h ("Circular fingerprint", "Tanimoto similarity") states the definitions.
 //
-// Fingerprint: a second consumer of the walk of smiles_graph.hpp.  The walk runs with a recorder that keeps what the rounds need and the
+// Fingerprint: a second consumer of the walk of smiles_graph.hpp.  The walk runs with a recorder (smiles_rounds.hpp, shared with
+// scaffold.hip, as are mix, each_bond, the LDS arrays and the token sources) that keeps what the rounds need and the
 // walk itself does not: the order of the bond to the tree predecessor (bits 24-31 of the atom word) and the ring-closure pairs.  One
 // thread per row, 64-thread blocks, as in smiles_graph.hip; everything indexed by a run-time atom number lives in LDS, lane-minor
 // ([slot][lane]: the 64 lanes of a wave touch 64 consecutive words, lanes never share a word), never in a private array:
@@ -29,48 +30,12 @@
 #include <limits.h>
 
 #include "common.hpp"
-#include "smiles_graph.hpp"
+#include "smiles_rounds.hpp"
 
 namespace fpr {
 
 constexpr int WORDS = MVAE_FP_WORDS;   // int64 words of a fingerprint
 constexpr int DWORDS = 2 * WORDS;
-constexpr int CLOSURES = 64;           // slots of the closure list
-
-SMI_HD uint32_t mix(uint32_t h) {
-  h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-  return h;
-}
-
-// the recorder the walk runs with (smg::NoRec states the three calls)
-template <class Clos>
-struct Rec {
-  Clos& cl;
-  int nclos = 0, n = 0;
-  smg::Mask ring{0, 0};
-  SMI_HD explicit Rec(Clos& c) : cl(c) {}
-  SMI_HD uint32_t atom_bits(int order) const { return (uint32_t)order << 24; }
-  SMI_HD void closure(int i, int j) {
-    if (nclos < CLOSURES) cl.set(nclos++, (uint16_t)(i | j << 8));
-  }
-  SMI_HD void done(int atoms, const smg::Mask& members) { n = atoms; ring = members; }
-};
-
-// f(a, b, bt) for every bond: atom k's bond to its tree predecessor, then the closure pairs
-template <class Atoms, class Clos, class F>
-SMI_HD void each_bond(Atoms& at, Clos& cl, int n, int nclos, F f) {
-  for (int k = 1; k < n; ++k) {
-    const uint32_t w = at.get(k);
-    const int p = smg::a_pred(w);
-    if (p == smg::NONE) continue;
-    const uint32_t order = w >> 24;
-    f(k, p, order == 1 && smg::a_arom(w) && smg::a_arom(at.get(p)) ? 4u : order);
-  }
-  for (int c = 0; c < nclos; ++c) {
-    const int v = cl.get(c), i = v & 0xFF, j = v >> 8;
-    f(i, j, smg::a_arom(at.get(i)) && smg::a_arom(at.get(j)) ? 4u : 1u);
-  }
-}
 
 template <class Bits>
 SMI_HD void set_bit(Bits& bits, uint32_t id) {
@@ -132,19 +97,10 @@ SMI_HD void row(Atoms& at, Ids& A, Ids& B, Clos& cl, Bits& bits, const Src& src,
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------------- fingerprint
-template <class T, int SLOTS>
-struct LdsArr {
-  T* base;             // &lds[lane]
-  __device__ __forceinline__ T get(int i) const { return base[(i & (SLOTS - 1)) * 64]; }
-  __device__ __forceinline__ void set(int i, T v) { base[(i & (SLOTS - 1)) * 64] = v; }
-};
-
-template <class T, int SLOTS>
-struct HostArr {
-  T w[SLOTS];
-  T get(int i) const { return w[i & (SLOTS - 1)]; }
-  void set(int i, T v) { w[i & (SLOTS - 1)] = v; }
-};
+using fpr::LdsArr;
+using fpr::HostArr;
+using fpr::PaddedSrc;
+using fpr::CsrSrc;
 
 typedef LdsArr<uint32_t, smg::ATOM_SLOTS> LdsWords;
 typedef LdsArr<uint16_t, fpr::CLOSURES> LdsClos;
@@ -153,16 +109,6 @@ typedef LdsArr<uint32_t, fpr::DWORDS> LdsBits;
 struct FpLds {
   uint32_t atoms[smg::ATOM_SLOTS * 64], a[smg::ATOM_SLOTS * 64], b[smg::ATOM_SLOTS * 64], bits[fpr::DWORDS * 64];
   uint16_t clos[fpr::CLOSURES * 64];
-};
-
-struct PaddedSrc {
-  const int64_t* row;
-  __host__ __device__ __forceinline__ long tok(int t) const { return (long)row[t]; }
-};
-
-struct CsrSrc {
-  const uint8_t* row;
-  __device__ __forceinline__ long tok(int t) const { return (long)row[t]; }
 };
 
 __global__ __launch_bounds__(64) void smiles_fp_rows_kernel(int B, int T, int V, const int64_t* __restrict__ x, long x_ld,

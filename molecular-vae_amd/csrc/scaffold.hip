@@ -1,0 +1,287 @@
+// Murcko scaffolds and graph keys of SMILES token rows (gfx950): mvae_smiles_scaffold_rows / _corpus / _host.  include/mvae.h ("Murcko
+// scaffold", "Graph key") states the definitions.
+//
+// A third consumer of the walk of smiles_graph.hpp, next to smiles_graph.hip and fingerprint.hip, with the fingerprint's recorder
+// (smiles_rounds.hpp): bond orders in bits 24-31 of the atom words, the ring-closure pairs in a list, the ring mask at <eos>.  One thread
+// per row, 64-thread blocks; everything indexed by a run-time atom number lives in LDS, lane-minor, never in a private array:
+//   words                 128 slots x 64 lanes x 4 B = 32 KiB      the walk's atom words; once they are packed, the neighbour sums
+//   ids                   128 x 64 x 4 B             = 32 KiB      id_{r-1}, overwritten by id_r once the sums are complete
+//   packed atoms + pairs  128 x 64 x 2 B             = 16 KiB      closure c in slot 127 - c, packed atom k in slot k
+// 80 KiB per block: two blocks per CU.  The rounds need three things per atom -- predecessor, bond order, aromatic flag -- and the first
+// ids two more -- element, charge --: 16 bits (scf::pack).  So the walk's 32-bit words are read for the ring bonds, the sets and the
+// molecule key's first ids (the only reader of the used valence), packed, and their storage becomes the sums.  An atom costs one of the
+// 127 tokens and a closure two, so n + nclos <= 127 and the closure pairs, which the walk appends from slot 127 down, never meet the
+// packed atoms.  The shared each_bond runs over the packed atoms through an adaptor that hands it atom words again.
+// Every atom SET is an smg::Mask in registers: the ring members (the walk's), the tree bonds that are ring bonds (bit k: the bond
+// k - pred(k)), Core, S.
+//   Ring bonds: every closure walks its tree path again, as the walk did for the ring members, and marks the bonds it steps over.
+//   Core without pruning: a non-ring atom has only bridges, and every bridge is a tree bond, so what is left when it is removed are its
+//   children's subtrees and the rest.  One pass down the atom numbers counts, saturating at two, the children whose subtree holds a ring
+//   atom (two masks); one pass up hands every atom whether the rest outside its subtree holds one.  A non-ring atom is a linker iff two
+//   of those parts hold ring atoms -- the component criterion of the definition, which is what repeated leaf deletion leaves.
+//   Keys: the rounds are edge-centric as the fingerprint's, restricted to the bonds inside the subset; the molecule key and the scaffold
+//   key run one after the other through the same two arrays.
+#include <limits.h>
+
+#include "common.hpp"
+#include "smiles_rounds.hpp"
+
+namespace scf {
+
+constexpr int ROUNDS = MVAE_GRAPH_KEY_ROUNDS;
+
+SMI_HD smg::Mask m_or(const smg::Mask& a, const smg::Mask& b) { return smg::Mask{a.lo | b.lo, a.hi | b.hi}; }
+SMI_HD smg::Mask m_first(int n) {      // atoms 0 .. n - 1, n <= 127
+  return smg::Mask{n >= 64 ? ~0ull : (1ull << n) - 1ull, n > 64 ? (1ull << (n - 64)) - 1ull : 0ull};
+}
+
+// bit k: the tree bond k - pred(k) lies on a cycle, that is, some closure's tree path steps over it
+template <class Atoms, class Clos>
+SMI_HD smg::Mask ring_bonds(Atoms& at, Clos& cl, int nclos) {
+  smg::Mask rb{0, 0};
+  for (int c = 0; c < nclos; ++c) {
+    const int v = cl.get(c);
+    int a = v & 0xFF, b = v >> 8;
+    for (int g = 0; g < 2 * smg::ATOM_SLOTS && a != b; ++g) {
+      if (a > b) { smg::m_set(rb, a); a = smg::a_pred(at.get(a)); }
+      else { smg::m_set(rb, b); b = smg::a_pred(at.get(b)); }
+    }
+  }
+  return rb;
+}
+
+struct Sets {
+  smg::Mask core, s;
+  int exo;
+};
+
+template <class Atoms>
+SMI_HD Sets scaffold_sets(Atoms& at, int n, const smg::Mask& ring) {
+  smg::Mask one{0, 0}, two{0, 0};      // at least one / two children whose subtree holds a ring atom
+  for (int k = n - 1; k >= 1; --k) {
+    if (!smg::m_get(ring, k) && !smg::m_get(one, k)) continue;
+    const int p = smg::a_pred(at.get(k));
+    if (p == smg::NONE) continue;
+    if (smg::m_get(one, p)) smg::m_set(two, p);
+    else smg::m_set(one, p);
+  }
+  Sets r{ring, {0, 0}, 0};
+  smg::Mask up{0, 0}, exo{0, 0};       // up: the part outside the atom's subtree holds a ring atom
+  for (int k = 0; k < n; ++k) {
+    const uint32_t w = at.get(k);
+    const int p = k ? smg::a_pred(w) : smg::NONE;
+    const bool sub = smg::m_get(ring, k) || smg::m_get(one, k);
+    bool u = false;
+    if (p != smg::NONE) u = smg::m_get(up, p) || smg::m_get(ring, p) || smg::m_get(two, p) || (smg::m_get(one, p) && !sub);
+    if (u) smg::m_set(up, k);
+    if (!smg::m_get(ring, k) && (smg::m_get(two, k) || (smg::m_get(one, k) && u))) smg::m_set(r.core, k);
+    // a predecessor has a lower number: its Core bit is final
+    if (p != smg::NONE && (w >> 24) == 2u) {
+      const bool ck = smg::m_get(r.core, k), cp = smg::m_get(r.core, p);
+      if (cp && !ck) smg::m_set(exo, k);
+      if (ck && !cp) smg::m_set(exo, p);
+    }
+  }
+  r.s = m_or(r.core, exo);
+  r.exo = smg::m_count(exo);
+  return r;
+}
+
+// The 16 bits of an atom word the rounds and the scaffold key's first ids read: predecessor (7 bits; atom 0 has none and is never asked),
+// bond order to it (2), aromatic flag, element (4), charge + 1 (2)
+SMI_HD uint16_t pack(uint32_t w) {
+  return (uint16_t)((w & 0x7Fu) | ((w >> 24) & 3u) << 7 | (uint32_t)smg::a_arom(w) << 9 | (uint32_t)smg::a_elem(w) << 10 | ((w >> 22) & 3u) << 14);
+}
+SMI_HD uint32_t unpack(uint32_t e) {     // an atom word again, with used valence 0
+  return (e & 0x7Fu) | ((e >> 10) & 0xFu) << 16 | ((e >> 9) & 1u) << 20 | ((e >> 14) & 3u) << 22 | ((e >> 7) & 3u) << 24;
+}
+
+// the 16-bit array as the walk's closure list (from the top down) and as atom words for each_bond (from the bottom up)
+template <class Half>
+struct TopClos {
+  Half& h;
+  SMI_HD int get(int c) const { return h.get(smg::ATOM_SLOTS - 1 - c); }
+  SMI_HD void set(int c, uint16_t v) { h.set(smg::ATOM_SLOTS - 1 - c, v); }
+};
+template <class Half>
+struct PackedAtoms {
+  Half& h;
+  SMI_HD uint32_t get(int k) const { return unpack(h.get(k)); }
+};
+
+// w_U(a) without the used valence
+SMI_HD uint32_t invariant(uint32_t w, bool in_ring, uint32_t degree) {
+  return (uint32_t)smg::a_elem(w) | (uint32_t)smg::a_arom(w) << 4 | (uint32_t)(smg::a_chg(w) + 1) << 5 | (uint32_t)in_ring << 7 | degree << 8;
+}
+
+// D[k] := the number of bonds of atom k inside U; returns the number of bonds inside U
+template <class Atoms, class Ids, class Clos>
+SMI_HD int degrees(Atoms& at, Ids& D, Clos& cl, int n, int nclos, const smg::Mask& U) {
+  for (int k = 0; k < n; ++k) D.set(k, 0u);
+  int nb = 0;
+  fpr::each_bond(at, cl, n, nclos, [&](int a, int b, uint32_t) {
+    if (!smg::m_get(U, a) || !smg::m_get(U, b)) return;
+    D.set(a, D.get(a) + 1u);
+    D.set(b, D.get(b) + 1u);
+    ++nb;
+  });
+  return nb;
+}
+
+// The key of the atom subset U with its nb induced bonds, from the first ids in I.  D: the neighbour sums.
+template <class Atoms, class Ids, class Clos>
+SMI_HD uint64_t graph_key(Atoms& at, Ids& I, Ids& D, Clos& cl, int n, int nclos, const smg::Mask& U, const smg::Mask& rb, int nb) {
+  for (uint32_t r = 1; r <= (uint32_t)ROUNDS; ++r) {
+    for (int k = 0; k < n; ++k) D.set(k, 0u);
+    // each_bond hands a tree bond as (k, pred(k)), k > pred(k), and a closure as (opener, closer), opener < closer
+    fpr::each_bond(at, cl, n, nclos, [&](int a, int b, uint32_t bt) {
+      if (!smg::m_get(U, a) || !smg::m_get(U, b)) return;
+      const uint32_t in_ring = a > b ? (uint32_t)smg::m_get(rb, a) : 1u;
+      const uint32_t key = (bt + 8u * in_ring) * 0x7FEB352Du, ia = I.get(a), ib = I.get(b);
+      D.set(a, D.get(a) + fpr::mix(ib ^ key));
+      D.set(b, D.get(b) + fpr::mix(ia ^ key));
+    });
+    for (int k = 0; k < n; ++k)
+      if (smg::m_get(U, k)) I.set(k, fpr::mix(I.get(k) * 0x9E3779B1u + r + D.get(k)));
+  }
+  uint32_t lo = 0u, hi = 0u;
+  for (int k = 0; k < n; ++k) {
+    if (!smg::m_get(U, k)) continue;
+    const uint32_t id = I.get(k);
+    lo += fpr::mix(id);
+    hi += fpr::mix(id ^ 0x5BD1E995u);
+  }
+  lo = fpr::mix((uint32_t)smg::m_count(U) * 0x9E3779B1u + lo);
+  hi = fpr::mix((uint32_t)nb * 0x85EBCA6Bu + hi);
+  const uint64_t key = (uint64_t)lo | (uint64_t)hi << 32;
+  return key ? key : 1ull;
+}
+
+// One row: the walk, the sets, the two keys; all outputs are written together (zeros for a row that is not OK).  W: the walk's atom
+// words and then the sums; I: the ids; H: the 16-bit array.
+template <class Words, class Half, class Src>
+SMI_HD void row(Words& W, Words& I, Half& H, const Src& src, int first, int end, bool end_is_eos, int V, const int32_t* tok_info,
+                const int32_t* chem_info, int eos_id, long b, int32_t* status, int64_t* mask, int32_t* desc, int64_t* key) {
+  TopClos<Half> cl{H};
+  fpr::Rec<TopClos<Half>> rec(cl);
+  smg::Row r;
+  smg::walk(W, src, first, end, end_is_eos, V, tok_info, chem_info, eos_id, &r, rec);
+  smg::Mask s{0, 0};
+  int d0 = 0, d1 = 0, d2 = 0, d3 = 0;
+  uint64_t kmol = 0, kscaf = 0;
+  if (r.status == smg::OK) {
+    const int n = rec.n, nclos = rec.nclos;
+    const smg::Mask ring = rec.ring, all = m_first(n);
+    const bool has_ring = (ring.lo | ring.hi) != 0;
+    const smg::Mask rb = ring_bonds(W, cl, nclos);
+    Sets st{{0, 0}, {0, 0}, 0};
+    if (has_ring) st = scaffold_sets(W, n, ring);
+    // the molecule key's first ids, the only reader of the used valence; then the words give way to the sums
+    const int nb = degrees(W, I, cl, n, nclos, all);
+    for (int k = 0; k < n; ++k) {
+      const uint32_t w = W.get(k);
+      I.set(k, fpr::mix(invariant(w, smg::m_get(ring, k), I.get(k)) | (uint32_t)smg::a_used(w) << 12));
+      H.set(k, pack(w));
+    }
+    PackedAtoms<Half> at{H};
+    kmol = graph_key(at, I, W, cl, n, nclos, all, rb, nb);
+    if (has_ring) {
+      s = st.s;
+      d1 = degrees(at, W, cl, n, nclos, s);
+      for (int k = 0; k < n; ++k)
+        if (smg::m_get(s, k)) I.set(k, fpr::mix(invariant(at.get(k), smg::m_get(ring, k), W.get(k))));
+      kscaf = graph_key(at, I, W, cl, n, nclos, s, rb, d1);
+      d0 = smg::m_count(s);
+      d2 = smg::m_count(st.core) - smg::m_count(ring);
+      d3 = st.exo;
+    }
+  }
+  status[b] = r.status;
+  if (mask) { mask[2 * b] = (int64_t)s.lo; mask[2 * b + 1] = (int64_t)s.hi; }
+  desc[4 * b] = d0; desc[4 * b + 1] = d1; desc[4 * b + 2] = d2; desc[4 * b + 3] = d3;
+  key[2 * b] = (int64_t)kmol; key[2 * b + 1] = (int64_t)kscaf;
+}
+
+}  // namespace scf
+
+namespace {
+
+typedef fpr::LdsArr<uint32_t, smg::ATOM_SLOTS> LdsWords;
+typedef fpr::LdsArr<uint16_t, smg::ATOM_SLOTS> LdsHalf;
+
+struct ScfLds {
+  uint32_t words[smg::ATOM_SLOTS * 64], ids[smg::ATOM_SLOTS * 64];
+  uint16_t half[smg::ATOM_SLOTS * 64];
+};
+static_assert(sizeof(ScfLds) == MVAE_SCAFFOLD_LDS_BYTES, "include/mvae.h states the LDS per block");
+
+__global__ __launch_bounds__(64) void smiles_scaffold_rows_kernel(int B, int T, int V, const int64_t* __restrict__ x, long x_ld,
+                                                                  const int32_t* __restrict__ tok_info, const int32_t* __restrict__ chem_info,
+                                                                  int eos_id, int32_t* __restrict__ status, int64_t* __restrict__ mask,
+                                                                  int32_t* __restrict__ desc, int64_t* __restrict__ key) {
+  __shared__ ScfLds lds;
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  LdsWords W{lds.words + threadIdx.x}, I{lds.ids + threadIdx.x};
+  LdsHalf H{lds.half + threadIdx.x};
+  scf::row(W, I, H, fpr::PaddedSrc{x + (long)b * x_ld}, 1, T, false, V, tok_info, chem_info, eos_id, (long)b, status, mask, desc, key);
+}
+
+__global__ __launch_bounds__(64) void smiles_scaffold_corpus_kernel(const uint8_t* __restrict__ tokens, const int64_t* __restrict__ offsets, long N,
+                                                                    int V, const int32_t* __restrict__ tok_info,
+                                                                    const int32_t* __restrict__ chem_info, int32_t* __restrict__ status,
+                                                                    int64_t* __restrict__ mask, int32_t* __restrict__ desc,
+                                                                    int64_t* __restrict__ key) {
+  __shared__ ScfLds lds;
+  const long b = (long)blockIdx.x * 64 + threadIdx.x;
+  if (b >= N) return;
+  const long lo = offsets[b], hi = offsets[b + 1];
+  const long len = hi > lo ? hi - lo : 0;
+  LdsWords W{lds.words + threadIdx.x}, I{lds.ids + threadIdx.x};
+  LdsHalf H{lds.half + threadIdx.x};
+  scf::row(W, I, H, fpr::CsrSrc{tokens + lo}, 0, (int)(len < INT_MAX - 1 ? len : INT_MAX - 1), true, V, tok_info, chem_info, -1, b, status,
+           mask, desc, key);
+}
+
+bool scaffold_rows_args_ok(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info, int eos_id,
+                           const int32_t* status, const int32_t* desc, const int64_t* key) {
+  return x && tok_info && chem_info && status && desc && key && B >= 1 && T >= 1 && V >= 1 && x_ld >= T && eos_id >= 0 && eos_id < V;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvae_smiles_scaffold_rows(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info, int eos_id,
+                              int32_t* status, int64_t* mask, int32_t* desc, int64_t* key, void* stream) {
+  if (V > 64) return MVAE_ERR_UNSUPPORTED;
+  if (!scaffold_rows_args_ok(B, T, V, x, x_ld, tok_info, chem_info, eos_id, status, desc, key)) return MVAE_ERR_INVALID;
+  hipLaunchKernelGGL(smiles_scaffold_rows_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, T, V, x, (long)x_ld, tok_info,
+                     chem_info, eos_id, status, mask, desc, key);
+  MVAE_CHECK_HIP(hipGetLastError());
+  return MVAE_OK;
+}
+
+int mvae_smiles_scaffold_corpus(const uint8_t* tokens, const int64_t* offsets, int64_t N, int V, const int32_t* tok_info,
+                                const int32_t* chem_info, int32_t* status, int64_t* mask, int32_t* desc, int64_t* key, void* stream) {
+  if (V > 64) return MVAE_ERR_UNSUPPORTED;
+  if (!tokens || !offsets || !tok_info || !chem_info || !status || !desc || !key || N < 1 || V < 1) return MVAE_ERR_INVALID;
+  if ((N + 63) / 64 > (int64_t)INT_MAX) return MVAE_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(smiles_scaffold_corpus_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, tokens, offsets, (long)N,
+                     V, tok_info, chem_info, status, mask, desc, key);
+  MVAE_CHECK_HIP(hipGetLastError());
+  return MVAE_OK;
+}
+
+int mvae_smiles_scaffold_host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info, int eos_id,
+                              int32_t* status, int64_t* mask, int32_t* desc, int64_t* key) {
+  if (V > 64) return MVAE_ERR_UNSUPPORTED;
+  if (!scaffold_rows_args_ok(B, T, V, x, x_ld, tok_info, chem_info, eos_id, status, desc, key)) return MVAE_ERR_INVALID;
+  fpr::HostArr<uint32_t, smg::ATOM_SLOTS> W, I;
+  fpr::HostArr<uint16_t, smg::ATOM_SLOTS> H;
+  for (long b = 0; b < B; ++b)
+    scf::row(W, I, H, fpr::PaddedSrc{x + b * x_ld}, 1, T, false, V, tok_info, chem_info, eos_id, b, status, mask, desc, key);
+  return MVAE_OK;
+}
+
+}  // extern "C"

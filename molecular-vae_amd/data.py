@@ -221,6 +221,7 @@ class MosesDeviceDataset:
         self._slots = self._n_distinct_d = self._n_distinct = None     # the corpus index: built on first use
         self._descriptors = None                                       # descriptors(): computed on first use
         self._fingerprints = None                                      # fingerprints(): computed on first use
+        self._scaffolds = self._scaffold_hist = self._scaffold_order = self._mol_keys = None     # scaffolds() and what is derived from it
 
     def __len__(self):
         return self.n
@@ -370,6 +371,64 @@ class MosesDeviceDataset:
         _, fp = ops.smiles_fp_rows(x, tok, chem, self.vocab.eos)
         exclude = self._probe(x) if exclude_self else None
         return ops.tanimoto_knn(fp, self.fingerprints()["fp"], int(k), exclude=exclude)
+
+    def scaffolds(self):
+        """The Murcko scaffold and the graph keys of every corpus row, in corpus order: ``VAE.scaffolds``' dict (status, mask, atoms,
+        bonds, linker_atoms, exo_atoms, mol_key, scaffold_key) on the device, from ONE ``mvae_smiles_scaffold_corpus`` launch over the
+        CSR rows.  Not rdkit's MurckoScaffold, and the keys ignore stereochemistry (include/mvae.h, "Murcko scaffold", "Graph key").
+        Cached; never waits for the device.  ValueError for a vocabulary of more than 64 ids."""
+        if self._scaffolds is None:
+            from . import ops
+            tok, chem = self._fp_tables("scaffolds")
+            self._scaffolds = ops.scaffold_dict(*ops.smiles_scaffold_corpus(self.tokens, self.offsets, self.n, tok, chem))
+        return self._scaffolds
+
+    def scaffold_histogram(self):
+        """(keys int64 [n], counts int64 [n]) on the device: the distinct scaffold keys of the corpus rows whose status is 0, ascending,
+        and how many rows have each (``ops.key_histogram``; rows without a ring have no scaffold and are not counted).  Cached."""
+        if self._scaffold_hist is None:
+            from . import ops
+            self._scaffold_hist = ops.key_histogram(self.scaffolds()["scaffold_key"])       # a row that is not ok has key 0
+        return self._scaffold_hist
+
+    def mol_keys_sorted(self):
+        """The molecule keys of the corpus rows, ascending (zeros, the rows that are not ok, included): what ``ops.keys_in`` searches to
+        tell whether a generated graph is in the corpus.  Cached; never waits."""
+        if self._mol_keys is None:
+            self._mol_keys = torch.sort(self.scaffolds()["mol_key"])[0]
+        return self._mol_keys
+
+    def rows_with_scaffold(self, x):
+        """For each row of x (whatever ``lookup`` takes), the corpus rows that have its scaffold key: CSR ``(offsets int64 [Q + 1], rows
+        int64 [offsets[-1]])`` on the device, the rows of query i at ``rows[offsets[i] : offsets[i + 1]]``, ascending.  A query without a
+        scaffold (no ring, or not ok) gets none.  One scaffold launch for x against the cached, sorted corpus keys; the one host wait is
+        the size of the answer."""
+        from . import ops
+        if len(self.vocab) > 64:
+            raise ValueError(f"rows_with_scaffold: the vocabulary has {len(self.vocab)} ids, at most 64 are supported")
+        x = self._token_rows(x, "rows_with_scaffold")
+        tok, chem = self._fp_tables("rows_with_scaffold")
+        if self._scaffold_order is None:
+            self._scaffold_order = torch.sort(self.scaffolds()["scaffold_key"], stable=True)       # equal keys: ascending rows
+        keys, order = self._scaffold_order
+        q = ops.smiles_scaffold_rows(x, tok, chem, self.vocab.eos, mask=False)[3][:, 1].contiguous()
+        lo = torch.searchsorted(keys, q)
+        n = torch.where(q != 0, torch.searchsorted(keys, q, right=True) - lo, torch.zeros_like(lo))
+        offsets = torch.zeros(q.shape[0] + 1, dtype=torch.long, device=self.device)
+        offsets[1:] = torch.cumsum(n, 0)
+        owner = torch.repeat_interleave(torch.arange(q.shape[0], device=self.device), n)
+        rows = order[lo[owner] + torch.arange(owner.shape[0], device=self.device) - offsets[owner]]
+        return offsets, rows
+
+    def scaffold_split(self, test_fraction, seed=0):
+        """A scaffold-held-out split: ``(train_rows, test_rows)``, int64 on the device, ascending, disjoint, covering every row.  Whole
+        scaffolds go to the test side, in an order drawn from ``seed``, until at least ``test_fraction`` of the ring-bearing rows are
+        there, so no non-zero scaffold key occurs on both sides; acyclic rows and rows that are not ok stay in train.  Deterministic
+        (``ops.scaffold_split_rows``).  ValueError for a fraction outside [0, 1]."""
+        from . import ops
+        if not 0.0 <= float(test_fraction) <= 1.0:
+            raise ValueError(f"scaffold_split: test_fraction must be in [0, 1], got {test_fraction!r}")
+        return ops.scaffold_split_rows(self.scaffolds()["scaffold_key"].contiguous(), test_fraction, seed)
 
     def contains(self, x):
         """``lookup(x) >= 0``: bool [B] on the device."""

@@ -529,6 +529,22 @@ class VAE(_SavedState, nn.Module):
         u = count(a) + count(b) - c
         return torch.where(u > 0, c.float() / u.clamp(min=1).float(), torch.zeros((), device=a.device))
 
+    @torch.no_grad()
+    def scaffolds(self, x):
+        """The Murcko scaffold and the graph keys of token rows x (what ``fingerprints`` takes), on the device, one
+        mvae_smiles_scaffold_rows launch, no host wait: {"status": int32 [B], "mask": int64 [B, 2] (bit a of word a >> 6: atom a, in
+        string order, is in the scaffold), "atoms", "bonds", "linker_atoms", "exo_atoms": int32 [B] (of the scaffold), "mol_key",
+        "scaffold_key": int64 [B]}.  The scaffold is the ring atoms, the linkers between rings and the atoms double-bonded to either, on
+        the graph of the SMILES graph walk -- NOT rdkit's MurckoScaffold; the keys are equal for equal graphs however the string spells
+        them, ignore stereochemistry, and are no canonical SMILES (include/mvae.h, "Murcko scaffold", "Graph key").  A key of 0 means
+        none: the row's status is not 0, or (scaffold key) it has no ring.  ValueError for a vocabulary of more than 64 ids."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.scaffolds")
+        if len(self.vocabulary) > 64:
+            raise ValueError(f"scaffolds: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
+        return ops.scaffold_dict(*ops.smiles_scaffold_rows(self._rows(x, "scaffolds", dev), self._smiles_table(dev),
+                                                           self._smiles_chem_table(dev), self.eos))
+
     def edit_distance(self, x, y):
         """The token-level Levenshtein distance (unit costs for insert, delete and substitute, no transposition) between the rows of two
         batches, pair by pair: int32 [B] on the device, one launch (mvae_edit_distance_rows), no host wait.  x, y: padded ids [B, T] (bos

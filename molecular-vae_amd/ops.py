@@ -888,6 +888,135 @@ def tanimoto_sum(a, b, skip_diagonal=False, out=None):
     return out
 
 
+GRAPH_KEY_ROUNDS = 8                          # include/mvae.h: MVAE_GRAPH_KEY_ROUNDS
+SCAFFOLD_DESC = ("atoms", "bonds", "linker_atoms", "exo_atoms")      # the columns of desc [*, 4]
+
+
+def _scaffold_outputs(n, dev, status, mask, desc, key):
+    status = torch.empty(n, dtype=torch.int32, device=dev) if status is None else status
+    mask = None if mask is False else torch.empty(n, 2, dtype=torch.int64, device=dev) if mask is None else mask
+    desc = torch.empty(n, 4, dtype=torch.int32, device=dev) if desc is None else desc
+    key = torch.empty(n, 2, dtype=torch.int64, device=dev) if key is None else key
+    for t, dt, shape in ((status, torch.int32, (n,)), (mask, torch.int64, (n, 2)), (desc, torch.int32, (n, 4)), (key, torch.int64, (n, 2))):
+        assert t is None or (t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev), (dt, shape)
+    return status, mask, desc, key
+
+
+def smiles_scaffold_rows(x, tok_info, chem_info, eos_id, status=None, mask=None, desc=None, key=None):
+    """The Murcko scaffold and the graph keys of token rows x (int64 [B, T], bos first) on the device: (status int32 [B], mask int64
+    [B, 2], desc int32 [B, 4], key int64 [B, 2]) -- the status of smiles_graph_rows; bit a of mask word a >> 6 = atom a (string order) is in
+    the scaffold; desc = scaffold atoms, scaffold bonds, linker atoms, exo atoms; key = (molecule key, scaffold key), 0 = none.  Defined
+    on the walk's graph, NOT rdkit's MurckoScaffold, and the keys ignore stereochemistry (include/mvae.h, "Murcko scaffold", "Graph
+    key").  Zeros for a row whose status is not 0.  ``mask=False``: no mask is computed (None is returned in its place).  One launch
+    (mvae_smiles_scaffold_rows)."""
+    x, ldx = _token_rows(x, "x")
+    _graph_tables(tok_info, chem_info, x.device)
+    out = _scaffold_outputs(x.shape[0], x.device, status, mask, desc, key)
+    check(L.load().mvae_smiles_scaffold_rows(x.shape[0], x.shape[1], tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), int(eos_id),
+                                             *map(ptr, out), stream_ptr()), "mvae_smiles_scaffold_rows")
+    return out
+
+
+def smiles_scaffold_corpus(tokens, offsets, N, tok_info, chem_info, status=None, mask=None, desc=None, key=None):
+    """smiles_scaffold_rows over the CSR corpus (tokens uint8, offsets int64 [N + 1]; rows without specials, the end of a row acting as
+    <eos>): one launch (mvae_smiles_scaffold_corpus)."""
+    N = int(N)
+    assert tokens.dtype == torch.uint8 and offsets.dtype == torch.int64 and offsets.numel() >= N + 1 and tokens.device == offsets.device
+    assert tokens.is_contiguous() and offsets.is_contiguous()
+    _graph_tables(tok_info, chem_info, tokens.device)
+    out = _scaffold_outputs(max(N, 0), tokens.device, status, mask, desc, key)
+    check(L.load().mvae_smiles_scaffold_corpus(ptr(tokens), ptr(offsets), N, tok_info.numel(), ptr(tok_info), ptr(chem_info), *map(ptr, out),
+                                               stream_ptr()), "mvae_smiles_scaffold_corpus")
+    return out
+
+
+def smiles_scaffold_host(x, tok_info, chem_info, eos_id, status=None, mask=None, desc=None, key=None):
+    """smiles_scaffold_rows on HOST tensors: the same source compiled for the CPU, a plain loop over the rows
+    (mvae_smiles_scaffold_host) -- for tests and for machines without a device; not a fallback of the device entries."""
+    x, ldx = _token_rows(x, "x")
+    assert x.device.type == "cpu", x.device
+    _graph_tables(tok_info, chem_info, x.device)
+    out = _scaffold_outputs(x.shape[0], x.device, status, mask, desc, key)
+    check(L.load().mvae_smiles_scaffold_host(x.shape[0], x.shape[1], tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), int(eos_id),
+                                             *map(ptr, out)), "mvae_smiles_scaffold_host")
+    return out
+
+
+def scaffold_dict(status, mask, desc, key):
+    """The outputs of the scaffold entries under their names: status, mask, atoms, bonds, linker_atoms, exo_atoms, mol_key, scaffold_key."""
+    out = {"status": status, "mask": mask}
+    out.update((name, desc[:, i]) for i, name in enumerate(SCAFFOLD_DESC))
+    out["mol_key"], out["scaffold_key"] = key[:, 0], key[:, 1]
+    return out
+
+
+def key_histogram(keys, weights=None):
+    """The distinct non-zero keys of an int64 tensor, ascending (as signed integers), and how often each occurs -- or, with ``weights``
+    (an integer tensor of the same shape), the sum of its weights: (keys int64 [n], counts int64 [n]) on the keys' device.  One
+    torch.sort and a segment sum, all integer; the one read-back is the size n of the result."""
+    keys = keys.reshape(-1)
+    assert keys.dtype == torch.int64, keys.dtype
+    w = torch.ones_like(keys) if weights is None else weights.reshape(-1).to(torch.int64)
+    assert w.shape == keys.shape and w.device == keys.device
+    if keys.numel() == 0:
+        return keys.clone(), w.clone()
+    ks, order = torch.sort(keys)
+    first = torch.ones_like(ks, dtype=torch.bool)
+    first[1:] = ks[1:] != ks[:-1]
+    run = torch.cumsum(first, 0) - 1
+    sums = torch.zeros_like(ks).index_add_(0, run, w[order])[run]
+    keep = first & (ks != 0)
+    return ks[keep], sums[keep]
+
+
+def keys_in(sorted_keys, q):
+    """bool, q's shape: which elements of q (int64) occur in the ascending int64 tensor sorted_keys.  No host wait."""
+    if sorted_keys.numel() == 0:
+        return torch.zeros_like(q, dtype=torch.bool)
+    pos = torch.searchsorted(sorted_keys, q).clamp_(max=sorted_keys.numel() - 1)
+    return sorted_keys[pos] == q
+
+
+def histogram_cosine(ka, ca, kb, cb):
+    """The cosine similarity of two key histograms (what key_histogram returns: distinct ascending keys and int64 counts), as a float64
+    0-d tensor on their device: dot / sqrt(|a|^2 |b|^2) with the dot product and the two squared norms exact in int64, one sqrt and one
+    division.  NaN if either side is empty.  This is the MOSES Scaf figure when the keys are scaffold keys.  No host wait."""
+    for k, c in ((ka, ca), (kb, cb)):
+        assert k.dtype == c.dtype == torch.int64 and k.dim() == 1 and k.shape == c.shape and k.device == ka.device
+    if ka.numel() == 0 or kb.numel() == 0:
+        return torch.full((), float("nan"), dtype=torch.float64, device=ka.device)
+    pos = torch.searchsorted(kb, ka).clamp_(max=kb.numel() - 1)
+    dot = (ca * torch.where(kb[pos] == ka, cb[pos], torch.zeros_like(ca))).sum()
+    na, nb = (ca * ca).sum(), (cb * cb).sum()
+    return dot.double() / torch.sqrt(na.double() * nb.double())
+
+
+def scaffold_split_rows(scaffold_key, test_fraction, seed=0):
+    """(train_rows, test_rows), int64 ascending on the keys' device, of rows with the given scaffold keys (int64 [N], 0 = no scaffold):
+    whole scaffolds go to the test side, in an order drawn from ``seed`` (a CPU generator: the same split on every device), until at
+    least ``test_fraction`` of the rows with a non-zero key are there; rows with key 0 stay in train.  No non-zero key occurs on both
+    sides.  Deterministic."""
+    if not 0.0 <= float(test_fraction) <= 1.0:
+        raise ValueError(f"scaffold_split: test_fraction must be in [0, 1], got {test_fraction!r}")
+    assert scaffold_key.dtype == torch.int64 and scaffold_key.dim() == 1
+    dev = scaffold_key.device
+    ks, cs = key_histogram(scaffold_key)
+    in_test = torch.zeros(scaffold_key.shape[0], dtype=torch.bool, device=dev)
+    if ks.numel():
+        order = torch.randperm(ks.numel(), generator=torch.Generator().manual_seed(int(seed))).to(dev)
+        c = cs[order]
+        before = torch.cumsum(c, 0) - c                            # rows already on the test side when this scaffold's turn comes
+        total = cs.sum()
+        # a scaffold is taken while fewer than test_fraction * total rows are there (float64: the counts are far below 2^53)
+        taken = before.double() < float(test_fraction) * total.double()
+        key_in_test = torch.zeros(ks.numel(), dtype=torch.bool, device=dev)
+        key_in_test[order] = taken
+        pos = torch.searchsorted(ks, scaffold_key).clamp_(max=ks.numel() - 1)
+        in_test = (ks[pos] == scaffold_key) & key_in_test[pos]
+    rows = torch.arange(scaffold_key.shape[0], dtype=torch.int64, device=dev)
+    return rows[~in_test], rows[in_test]
+
+
 def sample_uniform(seed, step, B):
     """Host restatement of the sampling step's uniforms u(b) = hash(seed, step * B + b) / 2^32 (tests)."""
     import numpy as np

@@ -801,7 +801,7 @@ def moses_reconstruction(model, batches, beam_width=1, max_len=100, syntax=False
 @torch.no_grad()
 def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top_k=None, top_p=None, seed=0, z=None, syntax=False,
                    count_valid=False, novel_against=None, prefix=None, nearest=False, valence=False,
-                   int_div=False, snn=False):
+                   int_div=False, snn=False, scaffolds=False):
     """The reference's generation pipeline (``hugesample.py``: sample in batches, hash the strings, count unique / total) with the hashing
     and the deduplication on the device: ``n_samples`` sequences from a ``mosesvae.VAE`` in batches of ``batch_size`` (the last one shorter),
     batch j with seed ``seed + j`` and ``temp`` / ``top_k`` / ``top_p`` as ``VAE.sample`` takes them.  ``z`` None draws each batch's latents
@@ -857,7 +857,18 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     against ``novel_against.fingerprints()`` and the result gains "snn" (the mean, over the distinct samples whose status is 0, of the
     largest Tanimoto similarity to any corpus row; NaN for none) and "snn_sim" / "snn_row", aligned with "strings": that similarity
     and the lowest corpus row that has it, -1.0 / -1 for a sample that is not ok.  They travel once, at the end.  Without either flag
-    the launches and the keys of the result are what they were."""
+    the launches and the keys of the result are what they were.
+    ``scaffolds=True`` (ValueError for a vocabulary of more than 64 ids, before any device work): Murcko scaffolds and identity modulo
+    spelling, on ``VAE.scaffolds`` -- the scaffold of the graph walk's graph, NOT rdkit's MurckoScaffold, and 64-bit graph keys that are
+    equal for equal graphs however the string spells them, ignore stereochemistry and are no canonical SMILES.  Each batch's NEW rows go
+    through one ``mvae_smiles_scaffold_rows`` launch, no further host wait.  The result gains the lists "mol_key", "scaffold_key" (0:
+    none -- the sample is not ok or, for the scaffold, has no ring) and "scaffold_atoms", aligned with "strings", which travel once, at
+    the end; "unique_graphs", the distinct non-zero molecule keys (``OCC`` and ``C(O)C`` are two of "unique" and one of these), and
+    "n_scaffolds", the distinct non-zero scaffold keys.  With ``novel_against`` it further gains "scaf", the MOSES Scaf figure: the
+    cosine similarity (``ops.histogram_cosine``) of the generated scaffold histogram, every drawn sample counting (each distinct sample
+    weighted by its "counts"), and ``novel_against.scaffold_histogram()`` (NaN when either has no scaffold); "scaffold_novel", the
+    generated scaffolds absent from the corpus; and "graph_novel", the distinct generated graphs whose molecule key equals no corpus
+    row's.  Without the flag the launches and the keys of the result are what they were."""
     n_samples, batch_size, max_len = int(n_samples), int(batch_size), int(max_len)
     if n_samples < 1 or batch_size < 1 or max_len < 1:
         raise ValueError(f"moses_generate: n_samples, batch_size and max_len must be >= 1, got {n_samples}, {batch_size}, {max_len}")
@@ -891,6 +902,8 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         raise ValueError(f"moses_generate: int_div / snn support at most 64 ids, the vocabulary has {len(model.vocabulary)}")
     if snn and novel_against is None:
         raise ValueError("moses_generate: snn=True needs novel_against, the corpus to search")
+    if scaffolds and len(model.vocabulary) > 64:
+        raise ValueError(f"moses_generate: scaffolds=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
     if forced is not None and syntax:
         model._check_prefix_syntax(forced, max_len, "moses_generate")      # every sample's prefix, once, before the first batch: rows are sample indices
     i64 = torch.long
@@ -911,6 +924,7 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     snns = []                                                   # (similarity, row) of each new sample's most similar corpus row, likewise
     n_fp = torch.zeros((), dtype=i64, device=dev) if int_div or snn else None
     snn_sum = torch.zeros((), dtype=torch.float64, device=dev) if snn else None
+    scafs = []                                                  # (molecule key, scaffold key, scaffold atoms) of each new sample, likewise
     stage = [None, None]                                        # pinned staging rows [batch_size, max_len + 1] (ids, end), alternating
     pending = None
 
@@ -982,6 +996,9 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
                     s_sim = torch.where(fine, s_sim[:, 0], torch.full_like(s_sim[:, 0], -1.0))
                     snns.append((s_sim, torch.where(fine, s_row[:, 0], torch.full_like(s_row[:, 0], -1))))
                     snn_sum += torch.where(fine, s_sim, torch.zeros_like(s_sim)).double().sum()
+            if scaffolds:
+                sc = model.scaffolds(x[sel])
+                scafs.append((sc["mol_key"], sc["scaffold_key"], sc["atoms"]))
             g0 = counts.numel()
             counts = torch.cat([counts, cnt[src]])
             seen_h, perm = torch.sort(torch.cat([seen_h, hs[src]]))
@@ -1020,6 +1037,18 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         res["snn"] = float(snn_sum) / res["n_fingerprinted"] if res["n_fingerprinted"] else float("nan")
         res["snn_sim"] = torch.cat([a for a, _ in snns]).tolist() if snns else []
         res["snn_row"] = torch.cat([b for _, b in snns]).tolist() if snns else []
+    if scaffolds:
+        mol, scaf, atoms = (torch.cat([c[i] for c in scafs]) if scafs else torch.empty(0, dtype=t, device=dev)
+                            for i, t in enumerate((i64, i64, torch.int32)))
+        res["mol_key"], res["scaffold_key"], res["scaffold_atoms"] = mol.tolist(), scaf.tolist(), atoms.tolist()
+        graphs = ops.key_histogram(mol)[0]
+        sk, sc_counts = ops.key_histogram(scaf, counts)          # every drawn sample counts: a distinct sample weighs its multiplicity
+        res["unique_graphs"], res["n_scaffolds"] = graphs.numel(), sk.numel()
+        if novel_against is not None:
+            ck, cc = novel_against.scaffold_histogram()
+            res["scaf"] = float(ops.histogram_cosine(sk, sc_counts, ck, cc))
+            res["scaffold_novel"] = int((~ops.keys_in(ck, sk)).sum())
+            res["graph_novel"] = int((~ops.keys_in(novel_against.mol_keys_sorted(), graphs)).sum())
     return res
 
 
