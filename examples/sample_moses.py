@@ -30,6 +30,10 @@ histograms --, the scaffolds and the graphs absent from the corpus; at the end t
 sample that has it and one training molecule that has it (``MosesDeviceDataset.rows_with_scaffold``).  The scaffold is the rings, the
 linkers between them and the atoms double-bonded to either, on the graph of the SMILES graph walk: not rdkit's MurckoScaffold, and no
 scaffold SMILES is produced.
+``--kekule`` prints, for each round, how many samples are kekulisable (``mv.moses_generate(kekule=True)``: valence-consistent, and every
+aromatic atom that needs a ring double bond gets one -- an exact matching on the graph of the SMILES graph walk) and how many fail on
+that alone, and with ``--novel_against`` audits the corpus once (``MosesDeviceDataset.kekule``).  A tighter necessary condition than
+``--valence`` counts, still not rdkit's verdict: no aromaticity perception, not rdkit's Kekulize.
 ``--reconstruct FILE`` (strings, one per line) skips the generation: it encodes the strings (z = mu), decodes them deterministically
 (``--beam_width``) without and with the syntax constraint (``mv.moses_reconstruction(..., syntax=)``) and prints the exact-match
 reconstruction fraction of each, the mean log p(x | mu) and the mean token edit distance between input and decode.
@@ -75,6 +79,8 @@ ap.add_argument("--int_div", action="store_true", help="print each round's inter
 ap.add_argument("--snn", action="store_true", help="with --novel_against: print each round's mean similarity to the nearest training molecule")
 ap.add_argument("--scaffolds", action="store_true", help="print each round's distinct graphs and Murcko scaffolds and, with --novel_against, the "
                                                          "Scaf figure; at the end the most frequent generated scaffolds")
+ap.add_argument("--kekule", action="store_true", help="count the kekulisable samples (valence-consistent, and the aromatic atoms can all take "
+                                                      "their ring double bond)")
 ap.add_argument("--reconstruct", default=None, metavar="FILE", help="strings, one per line: report exact-match reconstruction at z = mu "
                                                                   "without and with the syntax constraint, then exit")
 ap.add_argument("--beam_width", default=1, type=int, help="with --reconstruct: the beam width of the deterministic decode")
@@ -131,6 +137,7 @@ seen, total, valid, syntax_valid = {}, 0, 0, 0
 chem_valid, reasons, props = 0, [0] * 7, {}               # unique valence-consistent string -> (weight, heavy atoms)
 near = {}                                                 # unique string -> (distance, corpus row) of its nearest training string
 novel = set()                                             # the unique strings that are not in the corpus
+kekule_valid, kekule_failed = 0, 0                        # samples with status 0 / 7 under the kekule entry, duplicates included
 scaffold_count, scaffold_sample = {}, {}                  # scaffold key -> samples drawn with it (duplicates included), one such string
 per_round = args.batch_size * args.batches_per_round
 start = time.time()
@@ -140,8 +147,11 @@ with open(args.log, "w", buffering=1) as f:
         res = mv.moses_generate(model, per_round, batch_size=args.batch_size, max_len=args.max_len, temp=args.temp, top_k=args.top_k,
                                 top_p=args.top_p, seed=args.seed + r * args.batches_per_round, syntax=args.syntax, count_valid=True,
                                 novel_against=corpus, prefix=args.prefix, nearest=args.nearest, valence=args.valence,
-                                int_div=args.int_div, snn=args.snn, scaffolds=args.scaffolds)
+                                int_div=args.int_div, snn=args.snn, scaffolds=args.scaffolds, kekule=args.kekule)
         total += res["total"]
+        if args.kekule:
+            kekule_valid += res["kekule_valid"]
+            kekule_failed += res["kekule_status_counts"][7]
         if args.scaffolds:
             for s, c, key in zip(res["strings"], res["counts"], res["scaffold_key"]):
                 if key:
@@ -168,6 +178,8 @@ with open(args.log, "w", buffering=1) as f:
         print(f"round {r}: unique {len(seen)} ({len(seen) / total:.3f}), sampled {total}, samples per second {total / (now - start):.0f}, "
               f"unique per second {len(seen) / (now - start):.0f}, well-formed {syntax_valid} ({syntax_valid / total:.3f})"
               + (f", valence-consistent {chem_valid} ({chem_valid / total:.3f})" if args.valence else "")
+              + (f", kekulisable {kekule_valid} ({kekule_valid / total:.3f}), valence-consistent but not kekulisable {kekule_failed}"
+                 if args.kekule else "")
               + (f", IntDiv of this round's {res['n_fingerprinted']} valence-consistent unique samples {res['int_div']:.4f}" if args.int_div else "")
               + (f", SNN {res['snn']:.4f}" if args.snn else "")
               + (f", this round's distinct graphs {res['unique_graphs']} and scaffolds {res['n_scaffolds']}" if args.scaffolds else "")
@@ -175,6 +187,10 @@ with open(args.log, "w", buffering=1) as f:
                  if args.scaffolds and corpus is not None else "")
               + (f", valid unique {valid}" if Chem is not None else "")
               + (f", novel {len(novel)} ({len(novel) / len(seen):.3f} of unique)" if corpus is not None else ""), flush=True)
+if args.kekule and corpus is not None:
+    st = corpus.kekule()["status"]
+    print(f"corpus: {int((st == 0).sum())} of {corpus.n} rows kekulisable, {int((st == 7).sum())} valence-consistent but not kekulisable",
+          flush=True)
 if args.scaffolds and scaffold_count:
     top = sorted(scaffold_count, key=lambda k: (-scaffold_count[k], k))[:5]
     shown = [scaffold_sample[k] for k in top]

@@ -923,6 +923,54 @@ int mvae_smiles_scaffold_host(int B, int T, int V, const int64_t* x, int64_t x_l
                               int32_t* desc /* [B, 4] */, int64_t* key /* [B, 2] */);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Kekulisation (an addition: a fourth consumer of the "SMILES graph" walk above).  The graph, fingerprint and scaffold entries give status
+ * 0 to a row whose aromatic system cannot be written with alternating single and double bonds -- c1cccn1 (pyrrole without its H),
+ * c1cccc1, c1(C)(C)cccc1 --, and they keep doing so.  The entries below add that test: a row they give status 0 is "kekulisable", a
+ * tighter necessary condition for chemical validity than "valence-consistent", and still no sufficient one.
+ * What this is NOT: it is not rdkit's Kekulize or SanitizeMol, and agreement with either is neither tested nor claimed.  No aromaticity
+ *   perception is done (no Hueckel count: c1ccc1 and c1ccccccc1 pass); radicals are not diagnosed (a bracket [c] with two ring bonds
+ *   passes); no Kekule form is written and no other entry sees the bond orders found.
+ * It is defined on the graph exactly as the walk builds it, with the walk's own valence table ("SMILES graph").
+ *   U(a): the atom's final used valence, as the atom word holds it at <eos>: the sum of bond contributions (aromatic bonds count 1) plus
+ *     bracket hydrogens.
+ *   v0(a): the smallest allowed valence of (element, charge) that is >= U(a).  Unbracketed atoms have charge 0.
+ *   N: the aromatic atoms with v0(a) - U(a) >= 1 -- the atoms that take exactly one ring double bond.  This is the condition under which
+ *     the implicit-hydrogen rule max(0, v0 - S - 1) already reserves one valence unit, so the double bond never exceeds v0 and the
+ *     hydrogen counts of the graph entries stay right.  In N: c with two or three sigma bonds, pyridine n, [n+] with three neighbours,
+ *     [nH+], [cH].  Not in N: [nH], n(C), o, s, c(=O), [n-], [cH-], c with four sigma bonds.
+ *   E: the bonds of bond type 4 ("Circular fingerprint": order 1, both ends aromatic) that are ring bonds ("Murcko scaffold") and have
+ *     both ends in N.  The bond between the rings of c1ccccc1c1ccccc1 is not in E.  A bond between two aromatic atoms that closes a
+ *     NON-aromatic ring (the five-ring of fluorene written with lower-case atoms on both sides) IS in E, because the walk does not know
+ *     which ring is aromatic; an extra edge can only help a matching, so this errs towards passing.
+ *   A row whose walk status is 0 kekulises iff the graph (N, E) has a perfect matching; else it gets status MVAE_SMILES_KEKULE = 7.  A row
+ *     whose walk status is not 0 keeps that status.  A row without aromatic atoms kekulises trivially.  (N, E) is a general graph --
+ *     aromatic systems contain odd rings -- and the matching is a maximum matching, exact (Edmonds' blossom algorithm).
+ * Outputs, per row: status int32 [B] (0 - 6 as the graph entries give it, or 7); desc int32 [B, 4] = |N|, |E|, pairs (the size of a
+ *   maximum matching of (N, E)), deficiency (|N| - 2 * pairs), for status 0 AND status 7, zeros for any other status -- all four are
+ *   determined by the row alone; mate uint8 [B, 128] (optional, may be NULL): mate[a] is the partner of atom a (string order) in the
+ *   maximum matching found, 255 for an atom that is not matched or not in N or does not exist, and 255 everywhere for a row whose status
+ *   is neither 0 nor 7.  A maximum matching is not unique: what is promised is that mate is a valid maximum matching of (N, E) and that
+ *   the three entries give the same one (they are one source).  Every element of the given outputs is written, nothing else is.
+ * mvae_smiles_kekule_rows / _corpus / _host: the inputs of mvae_smiles_scaffold_rows / _corpus / _host.  One thread per row;
+ *   MVAE_KEKULE_LDS_BYTES = 73728 B (72 KiB) of LDS per 64-row block, so that two blocks fit a CU: the atom words (32 KiB), the closure
+ *   pairs (8 KiB) and four byte arrays -- mate, parent, base, queue (8 KiB each).  Every loop is bounded by the 127 atoms a row can have.
+ * Refused before anything is enqueued: what the scaffold entries refuse of these arguments (V > 64: MVAE_ERR_UNSUPPORTED; the rest
+ *   MVAE_ERR_INVALID), and a NULL desc.
+ */
+#define MVAE_SMILES_KEKULE 7
+#define MVAE_KEKULE_DESC 4
+#define MVAE_KEKULE_LDS_BYTES 73728
+int mvae_smiles_kekule_rows(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */,
+                            const int32_t* chem_info /* [V] */, int eos_id, int32_t* status /* [B] */, int32_t* desc /* [B, 4] */,
+                            uint8_t* mate /* [B, 128] or NULL */, void* stream);
+int mvae_smiles_kekule_corpus(const uint8_t* tokens, const int64_t* offsets /* [N + 1] */, int64_t N, int V, const int32_t* tok_info /* [V] */,
+                              const int32_t* chem_info /* [V] */, int32_t* status /* [N] */, int32_t* desc /* [N, 4] */,
+                              uint8_t* mate /* [N, 128] or NULL */, void* stream);
+int mvae_smiles_kekule_host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */,
+                            const int32_t* chem_info /* [V] */, int eos_id, int32_t* status /* [B] */, int32_t* desc /* [B, 4] */,
+                            uint8_t* mate /* [B, 128] or NULL */);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Tanimoto similarity of fingerprints (an addition: the structure-aware counterpart of mvae_latent_knn and mvae_edit_knn).  Fingerprints
  * are dense rows of MVAE_FP_WORDS int64 words, 16-byte aligned (else MVAE_ERR_INVALID); any 1024-bit rows will do.
  * Similarity.  T(a, b) = c / (p_a + p_b - c), with p the popcounts and c the popcount of a AND b; T is 0 when the union is empty.  T is

@@ -30,25 +30,9 @@ namespace scf {
 
 constexpr int ROUNDS = MVAE_GRAPH_KEY_ROUNDS;
 
-SMI_HD smg::Mask m_or(const smg::Mask& a, const smg::Mask& b) { return smg::Mask{a.lo | b.lo, a.hi | b.hi}; }
-SMI_HD smg::Mask m_first(int n) {      // atoms 0 .. n - 1, n <= 127
-  return smg::Mask{n >= 64 ? ~0ull : (1ull << n) - 1ull, n > 64 ? (1ull << (n - 64)) - 1ull : 0ull};
-}
-
-// bit k: the tree bond k - pred(k) lies on a cycle, that is, some closure's tree path steps over it
-template <class Atoms, class Clos>
-SMI_HD smg::Mask ring_bonds(Atoms& at, Clos& cl, int nclos) {
-  smg::Mask rb{0, 0};
-  for (int c = 0; c < nclos; ++c) {
-    const int v = cl.get(c);
-    int a = v & 0xFF, b = v >> 8;
-    for (int g = 0; g < 2 * smg::ATOM_SLOTS && a != b; ++g) {
-      if (a > b) { smg::m_set(rb, a); a = smg::a_pred(at.get(a)); }
-      else { smg::m_set(rb, b); b = smg::a_pred(at.get(b)); }
-    }
-  }
-  return rb;
-}
+using fpr::m_or;
+using fpr::m_first;
+using fpr::ring_bonds;
 
 struct Sets {
   smg::Mask core, s;

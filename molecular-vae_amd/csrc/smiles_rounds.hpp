@@ -1,5 +1,5 @@
-// What the consumers of the SMILES graph walk that run hash rounds over the finished graph share (fingerprint.hip, scaffold.hip): the mix
-// function, the recorder that keeps bond orders and ring-closure pairs, the loop over all bonds, lane-minor LDS storage for everything
+// What the consumers of the SMILES graph walk that work on the finished graph share (fingerprint.hip, scaffold.hip, kekule.hip): the mix
+// function, the recorder that keeps bond orders and ring-closure pairs, the loop over all bonds, the ring bonds, lane-minor LDS storage for everything
 // indexed by a run-time atom number (and its host twin), and the two token sources.  Definitions: include/mvae.h, "Circular fingerprint".
 #pragma once
 #include "smiles_graph.hpp"
@@ -41,6 +41,26 @@ SMI_HD void each_bond(Atoms& at, Clos& cl, int n, int nclos, F f) {
     const int v = cl.get(c), i = v & 0xFF, j = v >> 8;
     f(i, j, smg::a_arom(at.get(i)) && smg::a_arom(at.get(j)) ? 4u : 1u);
   }
+}
+
+SMI_HD smg::Mask m_or(const smg::Mask& a, const smg::Mask& b) { return smg::Mask{a.lo | b.lo, a.hi | b.hi}; }
+SMI_HD smg::Mask m_first(int n) {      // atoms 0 .. n - 1, n <= 127
+  return smg::Mask{n >= 64 ? ~0ull : (1ull << n) - 1ull, n > 64 ? (1ull << (n - 64)) - 1ull : 0ull};
+}
+
+// bit k: the tree bond k - pred(k) lies on a cycle, that is, some closure's tree path steps over it
+template <class Atoms, class Clos>
+SMI_HD smg::Mask ring_bonds(Atoms& at, Clos& cl, int nclos) {
+  smg::Mask rb{0, 0};
+  for (int c = 0; c < nclos; ++c) {
+    const int v = cl.get(c);
+    int a = v & 0xFF, b = v >> 8;
+    for (int g = 0; g < 2 * smg::ATOM_SLOTS && a != b; ++g) {
+      if (a > b) { smg::m_set(rb, a); a = smg::a_pred(at.get(a)); }
+      else { smg::m_set(rb, b); b = smg::a_pred(at.get(b)); }
+    }
+  }
+  return rb;
 }
 
 // [slot][lane]: the 64 lanes of a wave touch 64 consecutive elements, lanes never share one

@@ -222,6 +222,7 @@ class MosesDeviceDataset:
         self._descriptors = None                                       # descriptors(): computed on first use
         self._fingerprints = None                                      # fingerprints(): computed on first use
         self._scaffolds = self._scaffold_hist = self._scaffold_order = self._mol_keys = None     # scaffolds() and what is derived from it
+        self._kekule = None
 
     def __len__(self):
         return self.n
@@ -382,6 +383,20 @@ class MosesDeviceDataset:
             tok, chem = self._fp_tables("scaffolds")
             self._scaffolds = ops.scaffold_dict(*ops.smiles_scaffold_corpus(self.tokens, self.offsets, self.n, tok, chem))
         return self._scaffolds
+
+    def kekule(self):
+        """The kekulisation test of every corpus row, in corpus order: {"status", "n_atoms", "n_bonds", "pairs", "deficiency": int32
+        [N]} on the device (``VAE.kekule`` without the mates), from ONE ``mvae_smiles_kekule_corpus`` launch over the CSR rows.  Status
+        0 means "kekulisable", 7 that the aromatic atoms cannot all take their ring double bond; not rdkit's Kekulize (include/mvae.h,
+        "Kekulisation").  The tool to audit a training file: every row of a sanitised corpus should pass.  Cached; never waits for
+        the device.  ValueError for a vocabulary of more than 64 ids."""
+        if self._kekule is None:
+            from . import ops
+            tok, chem = self._fp_tables("kekule")
+            out = ops.kekule_dict(*ops.smiles_kekule_corpus(self.tokens, self.offsets, self.n, tok, chem, mate=False))
+            del out["mate"]
+            self._kekule = out
+        return self._kekule
 
     def scaffold_histogram(self):
         """(keys int64 [n], counts int64 [n]) on the device: the distinct scaffold keys of the corpus rows whose status is 0, ascending,

@@ -483,14 +483,37 @@ class VAE(_SavedState, nn.Module):
         return ops.smiles_graph_rows(self._rows(x, who, dev), self._smiles_table(dev), self._smiles_chem_table(dev), self.eos)
 
     @torch.no_grad()
-    def chem_valid(self, x, return_status=False):
+    def chem_valid(self, x, return_status=False, kekule=False):
         """Which token rows are well-formed AND valence-consistent SMILES strings (the graph walk of include/mvae.h, "SMILES graph", one
         mvae_smiles_graph_rows launch, no host wait): every atom within the largest valence its element and charge allow, no ring bond
         doubling an existing bond, every aromatic atom in a ring.  A necessary condition for chemical validity, not a sufficient one:
         nothing is kekulised.  x: what ``syntax_valid`` takes.  Returns a bool [B] device tensor; return_status=True also returns the
-        int32 [B] status (ops.SMILES_STATUS_NAMES) and the int32 [B] bad_pos (the column of the first error, -1 for a row that is ok)."""
+        int32 [B] status (ops.SMILES_STATUS_NAMES) and the int32 [B] bad_pos (the column of the first error, -1 for a row that is ok).
+        ``kekule=True``: the answer is "status 0 under ``kekule``" instead -- valence-consistent and kekulisable, one
+        mvae_smiles_kekule_rows launch; return_status=True then returns the status of ops.KEKULE_STATUS_NAMES alone, the kekule entry
+        having no bad_pos.  Still a necessary condition only, and not rdkit's verdict."""
+        if kekule:
+            status = self.kekule(x, mate=False)["status"]
+            return (status == 0, status) if return_status else status == 0
         status, bad, _, _ = self._graph_rows(x, "chem_valid")
         return (status == 0, status, bad) if return_status else status == 0
+
+    @torch.no_grad()
+    def kekule(self, x, mate=True):
+        """The kekulisation test of token rows x (what ``syntax_valid`` takes), on the device, one mvae_smiles_kekule_rows launch, no
+        host wait: {"status": int32 [B] (ops.KEKULE_STATUS_NAMES: ``chem_valid``'s status, or 7 where a valence-consistent row's aromatic
+        atoms cannot all take their one ring double bond), "n_atoms", "n_bonds", "pairs", "deficiency": int32 [B] (the aromatic atoms
+        that need a double bond, the aromatic ring bonds among them, the size of a maximum matching, the atoms it leaves over; zeros
+        unless the status is 0 or 7), "mate": uint8 [B, 128] (the partner of atom a, in string order, in the matching found; 255: none),
+        None with ``mate=False``}.  Status 0 is "kekulisable": tighter than valence-consistent, still necessary and not sufficient, with
+        no aromaticity perception -- NOT rdkit's Kekulize or SanitizeMol (include/mvae.h, "Kekulisation").  ValueError for a vocabulary
+        of more than 64 ids."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.kekule")
+        if len(self.vocabulary) > 64:
+            raise ValueError(f"kekule: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
+        return ops.kekule_dict(*ops.smiles_kekule_rows(self._rows(x, "kekule", dev), self._smiles_table(dev), self._smiles_chem_table(dev),
+                                                       self.eos, mate=None if mate else False))
 
     @torch.no_grad()
     def descriptors(self, x):

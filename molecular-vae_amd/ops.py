@@ -950,6 +950,68 @@ def scaffold_dict(status, mask, desc, key):
     return out
 
 
+SMILES_STATUS_KEKULE = 7                      # include/mvae.h: MVAE_SMILES_KEKULE, given by the kekule entries only
+KEKULE_STATUS_NAMES = SMILES_STATUS_NAMES + ("kekule",)
+KEKULE_DESC = ("n_atoms", "n_bonds", "pairs", "deficiency")          # the columns of desc [*, 4]: |N|, |E|, maximum matching, |N| - 2 pairs
+
+
+def _kekule_outputs(n, dev, status, desc, mate):
+    status = torch.empty(n, dtype=torch.int32, device=dev) if status is None else status
+    desc = torch.empty(n, 4, dtype=torch.int32, device=dev) if desc is None else desc
+    mate = None if mate is False else torch.empty(n, 128, dtype=torch.uint8, device=dev) if mate is None else mate
+    for t, dt, shape in ((status, torch.int32, (n,)), (desc, torch.int32, (n, 4)), (mate, torch.uint8, (n, 128))):
+        assert t is None or (t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev), (dt, shape)
+    return status, desc, mate
+
+
+def smiles_kekule_rows(x, tok_info, chem_info, eos_id, status=None, desc=None, mate=None):
+    """The kekulisation test of token rows x (int64 [B, T], bos first) on the device: (status int32 [B], desc int32 [B, 4], mate uint8
+    [B, 128]) -- the status of smiles_graph_rows, except that a row it calls 0 whose aromatic atoms cannot all take their one ring double
+    bond gets SMILES_STATUS_KEKULE (7); desc = |N|, |E|, the size of a maximum matching, the deficiency, for status 0 and 7 (zeros
+    otherwise); mate[a] = the partner of atom a in the matching found, 255 = none.  Status 0 here means "kekulisable": a tighter
+    necessary condition than valence-consistent, NOT rdkit's Kekulize or SanitizeMol, no aromaticity perception (include/mvae.h,
+    "Kekulisation").  ``mate=False``: no mate is written (None is returned in its place).  One launch (mvae_smiles_kekule_rows)."""
+    x, ldx = _token_rows(x, "x")
+    _graph_tables(tok_info, chem_info, x.device)
+    out = _kekule_outputs(x.shape[0], x.device, status, desc, mate)
+    check(L.load().mvae_smiles_kekule_rows(x.shape[0], x.shape[1], tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), int(eos_id),
+                                           *map(ptr, out), stream_ptr()), "mvae_smiles_kekule_rows")
+    return out
+
+
+def smiles_kekule_corpus(tokens, offsets, N, tok_info, chem_info, status=None, desc=None, mate=None):
+    """smiles_kekule_rows over the CSR corpus (tokens uint8, offsets int64 [N + 1]; rows without specials, the end of a row acting as
+    <eos>): one launch (mvae_smiles_kekule_corpus)."""
+    N = int(N)
+    assert tokens.dtype == torch.uint8 and offsets.dtype == torch.int64 and offsets.numel() >= N + 1 and tokens.device == offsets.device
+    assert tokens.is_contiguous() and offsets.is_contiguous()
+    _graph_tables(tok_info, chem_info, tokens.device)
+    out = _kekule_outputs(max(N, 0), tokens.device, status, desc, mate)
+    check(L.load().mvae_smiles_kekule_corpus(ptr(tokens), ptr(offsets), N, tok_info.numel(), ptr(tok_info), ptr(chem_info), *map(ptr, out),
+                                             stream_ptr()), "mvae_smiles_kekule_corpus")
+    return out
+
+
+def smiles_kekule_host(x, tok_info, chem_info, eos_id, status=None, desc=None, mate=None):
+    """smiles_kekule_rows on HOST tensors: the same source compiled for the CPU, a plain loop over the rows (mvae_smiles_kekule_host) --
+    for tests and for machines without a device; not a fallback of the device entries."""
+    x, ldx = _token_rows(x, "x")
+    assert x.device.type == "cpu", x.device
+    _graph_tables(tok_info, chem_info, x.device)
+    out = _kekule_outputs(x.shape[0], x.device, status, desc, mate)
+    check(L.load().mvae_smiles_kekule_host(x.shape[0], x.shape[1], tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), int(eos_id),
+                                           *map(ptr, out)), "mvae_smiles_kekule_host")
+    return out
+
+
+def kekule_dict(status, desc, mate):
+    """The outputs of the kekule entries under their names: status, n_atoms, n_bonds, pairs, deficiency, mate."""
+    out = {"status": status}
+    out.update((name, desc[:, i]) for i, name in enumerate(KEKULE_DESC))
+    out["mate"] = mate
+    return out
+
+
 def key_histogram(keys, weights=None):
     """The distinct non-zero keys of an int64 tensor, ascending (as signed integers), and how often each occurs -- or, with ``weights``
     (an integer tensor of the same shape), the sum of its weights: (keys int64 [n], counts int64 [n]) on the keys' device.  One

@@ -801,7 +801,7 @@ def moses_reconstruction(model, batches, beam_width=1, max_len=100, syntax=False
 @torch.no_grad()
 def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top_k=None, top_p=None, seed=0, z=None, syntax=False,
                    count_valid=False, novel_against=None, prefix=None, nearest=False, valence=False,
-                   int_div=False, snn=False, scaffolds=False):
+                   int_div=False, snn=False, scaffolds=False, kekule=False):
     """The reference's generation pipeline (``hugesample.py``: sample in batches, hash the strings, count unique / total) with the hashing
     and the deduplication on the device: ``n_samples`` sequences from a ``mosesvae.VAE`` in batches of ``batch_size`` (the last one shorter),
     batch j with seed ``seed + j`` and ``temp`` / ``top_k`` / ``top_p`` as ``VAE.sample`` takes them.  ``z`` None draws each batch's latents
@@ -868,7 +868,15 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     cosine similarity (``ops.histogram_cosine``) of the generated scaffold histogram, every drawn sample counting (each distinct sample
     weighted by its "counts"), and ``novel_against.scaffold_histogram()`` (NaN when either has no scaffold); "scaffold_novel", the
     generated scaffolds absent from the corpus; and "graph_novel", the distinct generated graphs whose molecule key equals no corpus
-    row's.  Without the flag the launches and the keys of the result are what they were."""
+    row's.  Without the flag the launches and the keys of the result are what they were.
+    ``kekule=True`` (ValueError for a vocabulary of more than 64 ids, before any device work; independent of ``valence``): each batch's
+    rows also go through the kekulisation test (``VAE.kekule``: one ``mvae_smiles_kekule_rows`` launch per batch, no further host
+    wait) and the result gains "kekule_valid" (the number of samples that are well-formed, valence-consistent AND kekulisable,
+    duplicates included -- a tighter necessary condition than "chem_valid", not rdkit's verdict and not a sufficient one),
+    "kekule_valid_unique" (of distinct ones) and, with ``novel_against``, "kekule_valid_unique_novel"; "kekule_status_counts" ({status:
+    count} over all samples, the codes of ``ops.KEKULE_STATUS_NAMES``); and the lists "kekule_status" and "kekule_deficiency" (the
+    aromatic atoms a maximum matching leaves without their double bond; 0 unless the status is 7), aligned with "strings", which travel
+    once, at the end.  Without the flag the launches and the keys of the result are what they were."""
     n_samples, batch_size, max_len = int(n_samples), int(batch_size), int(max_len)
     if n_samples < 1 or batch_size < 1 or max_len < 1:
         raise ValueError(f"moses_generate: n_samples, batch_size and max_len must be >= 1, got {n_samples}, {batch_size}, {max_len}")
@@ -904,6 +912,8 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         raise ValueError("moses_generate: snn=True needs novel_against, the corpus to search")
     if scaffolds and len(model.vocabulary) > 64:
         raise ValueError(f"moses_generate: scaffolds=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
+    if kekule and len(model.vocabulary) > 64:
+        raise ValueError(f"moses_generate: kekule=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
     if forced is not None and syntax:
         model._check_prefix_syntax(forced, max_len, "moses_generate")      # every sample's prefix, once, before the first batch: rows are sample indices
     i64 = torch.long
@@ -925,6 +935,10 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     n_fp = torch.zeros((), dtype=i64, device=dev) if int_div or snn else None
     snn_sum = torch.zeros((), dtype=torch.float64, device=dev) if snn else None
     scafs = []                                                  # (molecule key, scaffold key, scaffold atoms) of each new sample, likewise
+    keks = []                                                   # (status, deficiency) of each new sample under the kekule entry, likewise
+    n_kek = torch.zeros(3, dtype=i64, device=dev) if kekule else None        # status 0: all samples, distinct ones, distinct and novel
+    kek_counts = torch.zeros(8, dtype=i64, device=dev) if kekule else None
+    kek_codes = torch.arange(8, dtype=torch.int32, device=dev) if kekule else None
     stage = [None, None]                                        # pinned staging rows [batch_size, max_len + 1] (ids, end), alternating
     pending = None
 
@@ -942,6 +956,7 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         ok = model.syntax_valid(x) if count_valid else None
         match = novel_against.lookup(x) if novel_against is not None else None
         graph = model.descriptors(x) if valence else None
+        kek = model.kekule(x, mate=False) if kekule else None
         hs, order = torch.sort(h, stable=True)                  # equal hashes: ascending row, so a run starts at its first occurrence
         first = torch.ones(n, dtype=torch.bool, device=dev)
         first[1:] = hs[1:] != hs[:-1]
@@ -966,6 +981,13 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
             if match is not None:
                 n_chem[2] += (good[order] & new & (match[order] < 0)).sum()
             status_counts += (graph["status"][:, None] == status_codes).sum(0)      # no bincount: on a device tensor it reads min / max back
+        if kekule:
+            good = kek["status"] == 0
+            n_kek[0] += good.sum()
+            n_kek[1] += (good[order] & new).sum()
+            if match is not None:
+                n_kek[2] += (good[order] & new & (match[order] < 0)).sum()
+            kek_counts += (kek["status"][:, None] == kek_codes).sum(0)
         key, ord2 = torch.sort(torch.where(new, order, torch.full_like(order, n)))     # the new rows first, in first-seen order
         n_new = int(new.sum())                                   # the batch's one host wait (the copy queued last round has landed too)
         if pending is not None:
@@ -999,6 +1021,8 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
             if scaffolds:
                 sc = model.scaffolds(x[sel])
                 scafs.append((sc["mol_key"], sc["scaffold_key"], sc["atoms"]))
+            if kekule:
+                keks.append((kek["status"][sel], kek["deficiency"][sel]))
             g0 = counts.numel()
             counts = torch.cat([counts, cnt[src]])
             seen_h, perm = torch.sort(torch.cat([seen_h, hs[src]]))
@@ -1049,6 +1073,14 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
             res["scaf"] = float(ops.histogram_cosine(sk, sc_counts, ck, cc))
             res["scaffold_novel"] = int((~ops.keys_in(ck, sk)).sum())
             res["graph_novel"] = int((~ops.keys_in(novel_against.mol_keys_sorted(), graphs)).sum())
+    if kekule:
+        n_kek = n_kek.tolist()
+        res["kekule_valid"], res["kekule_valid_unique"] = n_kek[0], n_kek[1]
+        if novel_against is not None:
+            res["kekule_valid_unique_novel"] = n_kek[2]
+        res["kekule_status_counts"] = dict(enumerate(kek_counts.tolist()))
+        for i, name in enumerate(("kekule_status", "kekule_deficiency")):
+            res[name] = torch.cat([c[i] for c in keks]).tolist() if keks else []
     return res
 
 
