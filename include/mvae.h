@@ -64,8 +64,15 @@ int mvae_knob_int(const char* name, int dflt);
  * Dense contraction  C[M,N] = act( A[M,K] . B[N,K]^T + bias[N] )          (MFMA, fp32 accumulate)
  * Replaces nn.Linear at models.py:122,87-88,153,157 and mosesvae.py:66-67,81-82, and is the GEMM under the
  * conv / weight-gradient ops below.  dtype_ab: storage of A and B; dtype_c: storage of C.
- * accumulate != 0: C += result (fp32 C only).  ws: scratch for split-K partials (may be NULL when
- * mvae_gemm_nt_workspace() returns 0).
+ * accumulate != 0: C += result (fp32 C only; with a bf16 C the call is refused, MVAE_ERR_INVALID, nothing written).  ws: scratch for
+ * split-K partials (may be NULL when mvae_gemm_nt_workspace() returns 0).
+ * Operand rows are read in whole 16-byte chunks (4 f32 / 8 bf16 elements): the elements K .. roundup(K, chunk) - 1 of every row of A and
+ * of B are read and must hold ZERO (so lda, ldb >= roundup(K, chunk)); nothing beyond them is read.  lda / ldb need not be multiples of
+ * 16 bytes (such operands take the register-staged main loop instead of the LDS-direct one).  K == 0 reads nothing of A and B: C = act(bias),
+ * zeros without a bias; under accumulate C += bias or stays as it was.  Columns N .. ldc - 1 of C are never written.
+ * MVAE_F32X3 is honoured only where the LDS-direct loop runs (K a multiple of 32 and >= 128, 16-byte aligned rows) on the 64 x 64 or
+ * 128 x 128 tile; elsewhere -- the other main loop, and the 128 x 32 tile that N <= 32 with M >= 128 takes -- the result is the
+ * exact-fp32 one.
  */
 size_t mvae_gemm_nt_workspace(int M, int N, int K, int dtype_ab);
 int mvae_gemm_nt(int dtype_ab, int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb,
@@ -75,7 +82,11 @@ int mvae_gemm_nt(int dtype_ab, int M, int N, int K, const void* A, int64_t lda, 
 /* C[M,N] = act( A^T . B + bias[N] ) with A [K, lda] and B [K, ldb] both K-major (row = k): the weight-gradient contraction
  * dW = dG^T . X reading dG [T*B, 4H] and X [T*B, H] as the recurrent kernels wrote them (hardware-transposed LDS reads, no
  * transposed copies).  bf16 operands: lda, ldb multiples of 8.  f32 operands (exact v_mfma_f32_16x16x4_f32 kernel): lda, ldb
- * multiples of 4, 16-byte aligned bases, fp32 C, no bias / activation.  Rows k >= K are never read.  Replaces autograd's weight-gradient GEMMs of models.py:128,164,157. */
+ * multiples of 4, 16-byte aligned bases, fp32 C, no bias / activation.  Rows k >= K are never read.  Replaces autograd's weight-gradient GEMMs of models.py:128,164,157.
+ * bf16: the pad columns M .. lda - 1 / N .. ldb - 1 ARE read, but reach only accumulators outside the matrix, which are not stored: they may
+ * hold anything, NaN included.  K == 0: C = act(bias) (zeros without one), or C unchanged under accumulate.  bf16 operands of 2 GiB and more
+ * (K * ld * 2 bytes) are contracted in equal K-chunks, one launch each, accumulating onto C: fp32 C, no bias / activation there
+ * (MVAE_ERR_UNSUPPORTED otherwise). */
 size_t mvae_gemm_tn_workspace(int M, int N, int K, int dtype_ab);
 int mvae_gemm_tn(int dtype_ab, int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb,
                  void* C, int64_t ldc, int dtype_c, const float* bias, int act, int accumulate,
@@ -117,7 +128,9 @@ int mvae_gemm_tn_grouped_capped(int n, const mvae_gemm_tn_problem* problems, int
  * each leaves most of the chip idle.  Problem i: C[M,N] (+)= A^T . B over K rows, A / B row-major fp32 with optional row groups (row r starts
  * at (r / group) * gstride + (r % group) * ld when group > 0: the overlapping windows of a channels-last Conv1d), colsum_out (optional):
  * column sums of A through a virtual ones column (as mvae_gemm_tn_f32_colsum), x3 != 0: products as 3 x bf16 (MVAE_F32X3).  lda, ldb and the
- * group strides multiples of 4, bases 16-byte aligned.  At most MVAE_TN_F32_MULTI_MAX problems; outputs must not overlap. */
+ * group strides multiples of 4, bases 16-byte aligned.  At most MVAE_TN_F32_MULTI_MAX problems; outputs must not overlap.  Every problem needs
+ * M >= 1 and N >= 1 (K == 0 is served: C = 0 or unchanged): n outside 1 .. MVAE_TN_F32_MULTI_MAX or an empty problem is MVAE_ERR_INVALID for
+ * the whole call, with nothing launched. */
 #define MVAE_TN_F32_MULTI_MAX 16
 typedef struct {
   int M, N; int64_t K;
