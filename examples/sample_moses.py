@@ -34,6 +34,8 @@ scaffold SMILES is produced.
 aromatic atom that needs a ring double bond gets one -- an exact matching on the graph of the SMILES graph walk) and how many fail on
 that alone, and with ``--novel_against`` audits the corpus once (``MosesDeviceDataset.kekule``).  A tighter necessary condition than
 ``--valence`` counts, still not rdkit's verdict: no aromaticity perception, not rdkit's Kekulize.
+``--respell N`` prints, at the end, N randomised spellings of each of the first five unique samples (``VAE.respell``: the same graph
+under the SMILES graph walk, written from a random root in a random neighbour order -- not canonical, not rdkit's doRandom).
 ``--reconstruct FILE`` (strings, one per line) skips the generation: it encodes the strings (z = mu), decodes them deterministically
 (``--beam_width``) without and with the syntax constraint (``mv.moses_reconstruction(..., syntax=)``) and prints the exact-match
 reconstruction fraction of each, the mean log p(x | mu) and the mean token edit distance between input and decode.
@@ -81,6 +83,8 @@ ap.add_argument("--scaffolds", action="store_true", help="print each round's dis
                                                          "Scaf figure; at the end the most frequent generated scaffolds")
 ap.add_argument("--kekule", action="store_true", help="count the kekulisable samples (valence-consistent, and the aromatic atoms can all take "
                                                       "their ring double bond)")
+ap.add_argument("--respell", default=0, type=int, metavar="N", help="at the end print N randomised spellings (VAE.respell) of each of the first "
+                                                                   "five unique samples the walk accepts")
 ap.add_argument("--reconstruct", default=None, metavar="FILE", help="strings, one per line: report exact-match reconstruction at z = mu "
                                                                   "without and with the syntax constraint, then exit")
 ap.add_argument("--beam_width", default=1, type=int, help="with --reconstruct: the beam width of the deterministic decode")
@@ -187,6 +191,16 @@ with open(args.log, "w", buffering=1) as f:
                  if args.scaffolds and corpus is not None else "")
               + (f", valid unique {valid}" if Chem is not None else "")
               + (f", novel {len(novel)} ({len(novel) / len(seen):.3f} of unique)" if corpus is not None else ""), flush=True)
+if args.respell > 0 and seen:
+    picked = [s for s in list(seen)[:256] if s][:64]
+    ok = model.chem_valid(picked).tolist() if picked else []
+    for s in [s for s, good in zip(picked, ok) if good][:5]:
+        rows, status = model.respell([s] * args.respell, seed=args.seed, draw=torch.arange(args.respell))
+        texts = set()
+        for ids, st in zip(rows.tolist(), status.tolist()):
+            if st == 0:
+                texts.add("".join(vocab.i2c[i] for i in ids[1:ids.index(vocab.eos)]))
+        print(f"respell {s}: " + " ".join(sorted(texts)), flush=True)
 if args.kekule and corpus is not None:
     st = corpus.kekule()["status"]
     print(f"corpus: {int((st == 0).sum())} of {corpus.n} rows kekulisable, {int((st == 7).sum())} valence-consistent but not kekulisable",

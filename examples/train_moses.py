@@ -9,6 +9,9 @@ here the gradient all-reduce is FusedAdam's GradSync and the data shard is Shard
 
 --device-data keeps the tokenised corpus in HBM and collates every batch in one launch (data.MosesDeviceDataset: the same batches, no host
 work in the step); --bucket K additionally groups rows of similar length within windows of K batches, which shortens the batches' T.
+--augment (with --device-data) is SMILES enumeration: every molecule goes in under another randomised spelling of the same graph each
+epoch (MosesDeviceDataset.batches(augment=True): one mvae_smiles_rewrite_corpus launch in front of the collate); rows that cannot be
+respelled, or whose spelling does not fit the batch's width plus --augment-slack, go in unchanged and are counted.
 """
 import argparse
 import os
@@ -20,7 +23,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import molecular_vae_amd as mv                          # noqa: E402
-from molecular_vae_amd import data as D, mosesvae as MV, vocab as VC   # noqa: E402
+from molecular_vae_amd import data as D, mosesvae as MV, vocab as VC, ops   # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--local_rank", default=int(os.environ.get("LOCAL_RANK", 0)), type=int)     # moses_train_distrib.py:27
@@ -35,10 +38,15 @@ ap.add_argument("--free-bits", default=0.0, type=float, help="nats per latent di
 ap.add_argument("--kl-cycle", default=0, type=int, help="cyclical KL weight with cycles of this many epochs (0: the linear KLAnnealer)")
 ap.add_argument("--device-data", action="store_true", help="feed from a device-resident corpus (data.MosesDeviceDataset) instead of the DataLoader")
 ap.add_argument("--bucket", default=0, type=int, help="with --device-data: group rows of similar length within windows of this many batches (0 = off)")
+ap.add_argument("--augment", action="store_true", help="with --device-data: SMILES enumeration -- every molecule goes in under another randomised "
+                                                       "spelling each epoch (one more launch per batch, no host work)")
+ap.add_argument("--augment-slack", default=0, type=int, help="with --augment: extra columns per batch for spellings longer than the original")
 ap.add_argument("--report", default=None, help="write a JSON summary (the per-epoch postfix dictionaries + samples) here")
 args = ap.parse_args()
 if args.bucket and not args.device_data:
     ap.error("--bucket needs --device-data")
+if args.augment and not args.device_data:
+    ap.error("--augment needs --device-data")
 
 rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
 torch.cuda.set_device(args.local_rank)
@@ -71,12 +79,17 @@ for epoch in range(args.epochs):
     sampler.set_epoch(epoch)
     kl_weight = kl_annealer(epoch)
     if device_data is not None:                          # the same shard of the same permutation as the sampler's (seed 0 + epoch)
-        batches = device_data.batches(args.batch_size, epoch=epoch, seed=0, rank=rank, world=world, bucket=args.bucket)
+        batches = device_data.batches(args.batch_size, epoch=epoch, seed=0, rank=rank, world=world, bucket=args.bucket, augment=args.augment,
+                                      augment_seed=0, augment_slack=args.augment_slack)
     else:
         batches = (b.to(dev) for b in loader)
     post = mv.moses_train_epoch(model, epoch, batches, kl_weight, optimizer, log_every=100 if rank == 0 else 0)
     if rank == 0:                                        # :342-353
         print(post, flush=True)
+        if args.augment:
+            counts = device_data.augment_counts.tolist()
+            print("augment: respelled", counts[0], "of", sum(counts), "rows so far; unchanged by reason:",
+                  {ops.REWRITE_STATUS_NAMES[i]: c for i, c in enumerate(counts[:14]) if i and c}, flush=True)
         report["epochs"].append(post)
         torch.save(model.state_dict(), os.path.join(args.out_dir, "trained_save.pt"))
         with open(os.path.join(args.out_dir, "vocab.pkl"), "wb") as f:

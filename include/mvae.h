@@ -984,6 +984,93 @@ int mvae_smiles_kekule_host(int B, int T, int V, const int64_t* x, int64_t x_ld,
                             uint8_t* mate /* [B, 128] or NULL */);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * SMILES rewrite (an addition: a fifth consumer of the "SMILES graph" walk above, and the first that writes a string).  A token row is
+ * read into its graph and written back as another well-formed row that spells the same graph -- a randomised SMILES, the usual
+ * augmentation for string models of molecules.  The spelling is a pure function of (row, seed, draw): there is no RNG state anywhere.
+ * What this is NOT: no canonical SMILES (the priorities are a hash, not a refinement), no stereochemistry, not rdkit's
+ *   MolToSmiles(doRandom=True): the set of spellings reached is this section's, and only "same graph under this library's walk" is claimed.
+ * Graph.  The walk's graph with the fingerprint's recorder: atoms in string order, the order of the bond of every atom to its tree
+ *   predecessor, the closure pairs (order 1), the ring mask.  h(a), the hydrogens of a bracket atom = its used valence minus the sum of
+ *   its bond contributions (the orders of its tree bonds, 1 per closure).
+ * Refusals.  A refused row is copied through unchanged (below) and its status says why:
+ *   1 - 6  the walk's status, for a row the walk does not give 0;
+ *   8  MVAE_SMILES_STEREO       the row has a token of class AT, or a bond token '/' or '\' (the ids of emit's stereo mask).  The walk
+ *        ignores stereo: keeping the tokens would be wrong, dropping them would change the molecule silently;
+ *   9  MVAE_SMILES_RING_MULTI   the traversal made a ring closure of a bond of order 2 or 3 (the grammar has no bond token before a digit);
+ *   10 MVAE_SMILES_RING_DIGITS  no ring digit was free;
+ *   11 MVAE_SMILES_DEPTH        more than 15 open branches;
+ *   12 MVAE_SMILES_LONG         more than max_content content tokens;
+ *   13 MVAE_SMILES_NO_TOKEN     the emit table has -1 for a token the output needs.
+ *   (7 stays the kekule entries'.)  Precedence: the walk's status; then STEREO; then RING_MULTI (the whole traversal runs before anything
+ *   is written); then whichever of 10 - 13 comes first as the tokens are written in order -- a "(" tests DEPTH before it is written,
+ *   a token tests NO_TOKEN before LONG.
+ * Priorities.  All arithmetic mod 2^32, mix the "Circular fingerprint" section's.  prio(a) = mix(mix(seed * 0x9E3779B1 + draw_b) ^
+ *   (a * 0x85EBCA6B)) for atom a (string order) of row b; draw_b = draw[b] (uint32 [B]), or b when draw is NULL.  Atoms compare by
+ *   (prio, atom number).
+ * Traversal.  A depth-first search from the least atom.  At an atom its bonds other than the one to its search parent are taken in this
+ *   order: the bonds of order 2 or 3 first, then by the other end's (prio, number) ascending.  An unvisited other end becomes a child (and is searched at
+ *   once); a visited one with a smaller search index is an ancestor and the bond becomes a ring closure -- RING_MULTI if its order is not
+ *   1; a visited one with a larger index is a descendant that has closed that bond already.  Multiple bonds first keeps them on the tree:
+ *   RING_MULTI then needs one atom with two multiple bonds on a common cycle (C1=C=CCCC1 on some draws; never O=S1(=O)CCCC1 or C1=CC=CC=C1).
+ * Emission, in pre-order of the search tree.  For each atom, in this order:
+ *   the bond to its parent: '=' / '#' for a tree bond of order 2 / 3, nothing for order 1 (between aromatic atoms too: the walk reads
+ *     "cc", "c-c" and "c:c" alike);
+ *   the atom: unbracketed, its element token (lower case if aromatic; Cl, Br as head plus tail); a bracket atom as '[', the symbol, 'H' if
+ *     h >= 1, the digit h if h >= 2, '+' / '-' for charge +1 / -1, ']'.  [N+1] becomes [N+]; [C] and [CH4] stay bracketed;
+ *   the ring digits it closes (it is the descendant), by digit value 0 .. 9 ascending; they become free;
+ *   the ring digits it opens (it is the ancestor), one per closure in ascending search index of the descendant: each the first of
+ *     1 2 .. 9 0 that is neither open nor written at this atom already (the automaton refuses a digit twice on one atom); none: RING_DIGITS;
+ *   its children in visiting order, every one but the last as '(' subtree ')', the last bare.  A '(' with 15 branches open: DEPTH.
+ *   A token beyond max_content: LONG.
+ * emit int32 [MVAE_REWRITE_EMIT = 48] (vocab.smiles_emit_table): one id per role, -1 where the vocabulary has no usable token --
+ *   [0 .. 10] the first character of element e written upper case (H B C N O F P S C(l) B(r) I), [11 .. 21] lower case (b c n o p s only),
+ *   22 'l', 23 'r', 24 '[', 25 ']', 26 'H', 27 '+', 28 '-', 29 '=', 30 '#', 31 '(', 32 ')', [33 .. 42] the digits 0 .. 9, 43 / 44 the low /
+ *   high 32 bits of the stereo mask (bit i: id i is '@', '/' or '\'), the rest 0.
+ * mvae_smiles_rewrite_rows (padded rows, <bos> in column 0, the inputs of mvae_smiles_kekule_rows):
+ *   out int64 [B, T_out]: bos_id, the new tokens, eos_id, then pad_id.  A refused row: columns 0 .. k - 1 of x, k = the column of its first
+ *     eos_id plus one (T without one), then pad_id.  A row longer than T_out is cut at T_out.
+ *   out_len int32 [B]: tokens + 2, or k: the uncut length, so out_len[b] > T_out tells a cut row.  status int32 [B].
+ * mvae_smiles_rewrite_corpus (rows int64 [B] of the CSR corpus, the end of a row acting as <eos>), one launch:
+ *   tokens_out uint8 [B, stride]: batch member b's new tokens (a refused row: its own) from byte b * stride, zeros up to the next;
+ *   offsets_out int64 [2 B + 1] = 0, len_0, stride, stride + len_1, 2 stride, ..., B stride: tokens_out as a CSR of 2 B rows whose even
+ *     rows are the batch members and whose odd rows are the gaps, so mvae_moses_collate with rows = 0, 2, 4, .. collates it as it stands;
+ *   err int32 [1] (optional, the caller zeroes it): raised with atomicMax to 1 by a refused row longer than stride, which is cut at
+ *     stride, and to 2 by a row id outside [0, N), which gives an empty row with status 1.
+ * Both take counts int32 [16] (optional, the caller zeroes it): counts[s] += the rows of status s, by integer atomic adds -- exact.
+ * mvae_smiles_rewrite_host: _rows on host memory, the same source compiled for the CPU (no counts).
+ * Every element of the given outputs is written, nothing else is; two runs are bit-identical.
+ * One thread per row; MVAE_REWRITE_LDS_BYTES = 81920 B (80 KiB) of LDS per 64-row block, so that two blocks fit a CU: the atom words
+ *   (32 KiB), the closure pairs, whose storage becomes the staged output row (8 KiB), the adjacency as <= 252 half-edge bytes (16 KiB)
+ *   and three byte arrays -- CSR start, search index, search parent (8 KiB each).  No recursion and no stack: the search returns through
+ *   the parent array.  Every loop is bounded by the 127 atoms and 252 half-edges a row can have.  The staged rows are stored by the
+ *   whole wave over consecutive columns.
+ * Refused before anything is enqueued: what the scaffold entries refuse of these arguments (V > 64: MVAE_ERR_UNSUPPORTED; the rest
+ *   MVAE_ERR_INVALID), a NULL emit or output (counts, err and draw may be NULL), max_content outside [1, 127], T_out < 2, bos_id / pad_id
+ *   outside [0, 65535], a NULL rows, B < 1, stride < max_content.
+ */
+#define MVAE_SMILES_STEREO 8
+#define MVAE_SMILES_RING_MULTI 9
+#define MVAE_SMILES_RING_DIGITS 10
+#define MVAE_SMILES_DEPTH 11
+#define MVAE_SMILES_LONG 12
+#define MVAE_SMILES_NO_TOKEN 13
+#define MVAE_REWRITE_EMIT 48
+#define MVAE_REWRITE_LDS_BYTES 81920
+int mvae_smiles_rewrite_rows(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */,
+                             const int32_t* chem_info /* [V] */, const int32_t* emit /* [48] */, int bos_id, int eos_id, int pad_id,
+                             uint32_t seed, const uint32_t* draw /* [B] or NULL */, int max_content, int T_out, int64_t* out /* [B, T_out] */,
+                             int32_t* out_len /* [B] */, int32_t* status /* [B] */, int32_t* counts /* [16] or NULL */, void* stream);
+int mvae_smiles_rewrite_corpus(const uint8_t* tokens, const int64_t* offsets /* [N + 1] */, int64_t N, const int64_t* rows /* [B] */, int B,
+                               int V, const int32_t* tok_info /* [V] */, const int32_t* chem_info /* [V] */, const int32_t* emit /* [48] */,
+                               uint32_t seed, const uint32_t* draw /* [B] or NULL */, int max_content, int stride,
+                               uint8_t* tokens_out /* [B, stride] */, int64_t* offsets_out /* [2 B + 1] */, int32_t* status /* [B] */,
+                               int32_t* counts /* [16] or NULL */, int32_t* err /* [1] or NULL */, void* stream);
+int mvae_smiles_rewrite_host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */,
+                             const int32_t* chem_info /* [V] */, const int32_t* emit /* [48] */, int bos_id, int eos_id, int pad_id,
+                             uint32_t seed, const uint32_t* draw /* [B] or NULL */, int max_content, int T_out, int64_t* out /* [B, T_out] */,
+                             int32_t* out_len /* [B] */, int32_t* status /* [B] */);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Tanimoto similarity of fingerprints (an addition: the structure-aware counterpart of mvae_latent_knn and mvae_edit_knn).  Fingerprints
  * are dense rows of MVAE_FP_WORDS int64 words, 16-byte aligned (else MVAE_ERR_INVALID); any 1024-bit rows will do.
  * Similarity.  T(a, b) = c / (p_a + p_b - c), with p the popcounts and c the popcount of a AND b; T is 0 when the union is empty.  T is

@@ -21,7 +21,7 @@ ACT_NONE, ACT_SELU, ACT_RELU = 0, 1, 2
 CELL_LSTM, CELL_GRU = 0, 1
 MAX_LAYERS = 8
 
-_vp, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
+_vp, _i, _i64, _f, _sz, _u32 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_uint32
 
 
 class RnnFwdDesc(C.Structure):
@@ -201,6 +201,9 @@ SIGNATURES = {
     "mvae_smiles_kekule_rows": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "mvae_smiles_kekule_corpus": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvae_smiles_kekule_host": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp]),
+    "mvae_smiles_rewrite_rows": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _u32, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mvae_smiles_rewrite_corpus": (_i, [_vp, _vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _u32, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvae_smiles_rewrite_host": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _u32, _vp, _i, _i, _vp, _vp, _vp]),
     "mvae_tanimoto_knn_workspace": (_sz, [_i, _i64, _i]),
     "mvae_tanimoto_knn": (_i, [_i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mvae_tanimoto_sum_workspace": (_sz, [_i64, _i64]),

@@ -16,6 +16,8 @@
                            ``encode_latents`` -> ``MosesLatentIndex``: the encoder mean of every corpus row in HBM and an exact k-NN
                            search over it (``mvae_latent_knn``); ``smiles`` reads corpus rows back as strings; ``nearest_strings``
                            is the exact k-NN by token-level Levenshtein distance over the same corpus (``mvae_edit_knn``).
+                           ``batches(augment=True)`` respells every row on the device first (SMILES enumeration:
+                           ``mvae_smiles_rewrite_corpus`` in front of the unchanged collate); ``randomized_smiles`` does it for strings.
   * ``load_smiles`` / ``save_encoded`` / ``load_encoded`` -- ``.smi``/CSV in, ``.npz`` (indices + charset + max_len) out.
 """
 import numpy as np
@@ -512,10 +514,44 @@ class MosesDeviceDataset:
         ops.moses_collate(self.tokens, self.offsets, rows, x_pad, lengths, T, self.n, v.bos, v.eos, v.pad, rows_sorted, self.err)
         return PaddedBatch(x_pad, lengths, rows=rows_sorted)
 
-    def gather(self, rows, T=None):
+    def _collate_augmented(self, rows, T, seed, epoch, slack):
+        """_collate with every row respelled first: one mvae_smiles_rewrite_corpus launch into a gapped CSR (batch member b at byte
+        b * stride), which the unchanged collate reads with rows = 0, 2, 4, ...; T + slack columns."""
+        from . import ops
+        from .vocab import PaddedBatch, smiles_emit_table
+        tok, chem = self._fp_tables("augment")
+        if self.__dict__.get("_emit") is None:
+            self._emit = smiles_emit_table(self.vocab).to(self.device)
+            self._augment_counts = torch.zeros(ops.REWRITE_COUNTS, dtype=torch.int32, device=self.device)
+            self._even = {}
+        slack = int(slack)
+        if slack < 0:
+            raise ValueError(f"augment_slack must be >= 0, got {slack}")
+        B, v, T = rows.numel(), self.vocab, T + slack
+        stride = max(T - 2, 1)                                   # a row that is copied through fits: the plan's T covers the longest
+        draw = ops.draw_words(rows + ((int(epoch) * 0x9E3779B1) & 0xFFFFFFFF))
+        tokens_out, offsets_out, _ = ops.smiles_rewrite_corpus(self.tokens, self.offsets, self.n, rows, tok, chem, self._emit, seed, draw,
+                                                               min(stride, 127), stride, counts=self._augment_counts, err=self.err)
+        if B not in self._even:
+            self._even[B] = torch.arange(0, 2 * B, 2, dtype=torch.long, device=self.device)
+        x_pad = torch.empty(B, T, dtype=torch.long, device=self.device)
+        lengths = torch.empty(B, dtype=torch.int32, device=self.device)
+        member = torch.empty(B, dtype=torch.long, device=self.device)
+        ops.moses_collate(tokens_out.view(-1), offsets_out, self._even[B], x_pad, lengths, T, 2 * B, v.bos, v.eos, v.pad, member, self.err)
+        return PaddedBatch(x_pad, lengths, rows=rows[member // 2])
+
+    @property
+    def augment_counts(self):
+        """The per-status histogram of every row respelled so far by ``batches(augment=True)`` / ``gather(augment=True)``: int32 [16] on the
+        device, indexed by the codes of ``ops.REWRITE_STATUS_NAMES`` (0: respelled; anything else: that row went in unchanged); kept by the
+        kernel's integer atomic adds.  None before the first augmented batch."""
+        return self.__dict__.get("_augment_counts")
+
+    def gather(self, rows, T=None, augment=False, augment_seed=0, augment_epoch=0, augment_slack=0):
         """Corpus rows (a list, an ndarray or a tensor; any order, repeats allowed) -> PaddedBatch of T columns, its rows in the collate's
         stable length-descending order and ``.rows`` the corpus row behind each.  T=None: the longest of the rows + 2 when `rows` is on the
-        host, else the corpus' longest + 2 (no device round trip)."""
+        host, else the corpus' longest + 2 (no device round trip).  ``augment=True``: every row is respelled first (``batches``), the
+        batch has T + augment_slack columns and its order follows the new lengths."""
         if torch.is_tensor(rows) and rows.is_cuda:
             rows_d = rows.to(self.device, torch.long).contiguous().view(-1)
             T = self.max_len + 2 if T is None else T
@@ -533,6 +569,8 @@ class MosesDeviceDataset:
             raise ValueError("gather: no rows")
         if int(T) != T or T < 2:
             raise ValueError(f"gather: T must be an integer >= 2, got {T!r}")
+        if augment:
+            return self._collate_augmented(rows_d, int(T), augment_seed, augment_epoch, augment_slack)
         return self._collate(rows_d, int(T))
 
     def check_errors(self):
@@ -542,17 +580,29 @@ class MosesDeviceDataset:
         if e:
             raise RuntimeError("mvae_moses_collate: " + ("a row id outside the corpus" if e == 2 else "a row longer than T - 2 was cut"))
 
-    def batches(self, batch_size, epoch=0, seed=0, shuffle=True, rank=0, world=1, drop_last=True, bucket=0):
+    def batches(self, batch_size, epoch=0, seed=0, shuffle=True, rank=0, world=1, drop_last=True, bucket=0, augment=False, augment_seed=0,
+                augment_slack=0):
         """Generator of this rank's device PaddedBatches of one epoch (``moses_epoch_plan``): one host plan and one upload of the order per
         epoch, then a slice and one launch per batch.  bucket=0 gives exactly the batches of the DataLoader + ShardedSampler +
-        get_padded_collate_fn feed; bucket=k groups rows of similar length within windows of k batches per rank (other batches, smaller T)."""
+        get_padded_collate_fn feed; bucket=k groups rows of similar length within windows of k batches per rank (other batches, smaller T).
+        ``augment=True`` (SMILES enumeration; ValueError for a vocabulary of more than 64 ids): every row goes in under a randomised
+        spelling of the same graph (include/mvae.h, "SMILES rewrite"), one ``mvae_smiles_rewrite_corpus`` launch in front of the
+        collate and a few elementwise ones for the draws, no host wait.  The spelling of corpus row r is a pure function of (augment_seed,
+        epoch, r) -- draw = epoch * 0x9E3779B1 + r -- whatever the batch size, the rank count or its place in the batch.  A batch keeps
+        its planned width plus ``augment_slack`` columns: a spelling that does not fit (about half are two or more tokens longer than the
+        original, but only one longer than the batch's longest row does not fit) and a row that cannot be respelled go in unchanged, and ``augment_counts`` says how many of each.  The batch order
+        within a batch follows the new lengths.  ``augment=False`` launches exactly what it always did."""
         order, cuts = moses_epoch_plan(self.lengths, batch_size, epoch, seed, shuffle, rank, world, drop_last, bucket)
-        return self._run_plan(order, cuts)
+        if augment:
+            self._fp_tables("augment")                           # raises before the generator is handed out
+            if int(augment_slack) < 0:
+                raise ValueError(f"augment_slack must be >= 0, got {augment_slack}")
+        return self._run_plan(order, cuts, (augment_seed, epoch, augment_slack) if augment else None)
 
-    def _run_plan(self, order, cuts):
+    def _run_plan(self, order, cuts, augment=None):
         order_d = torch.from_numpy(order).to(self.device)
         for lo, hi, T in cuts:
-            yield self._collate(order_d[lo:hi], T)
+            yield self._collate(order_d[lo:hi], T) if augment is None else self._collate_augmented(order_d[lo:hi], T, *augment)
 
 
 class MosesLatentIndex:
@@ -640,6 +690,38 @@ def formula_strings(formula, charge=None):
             s += sign if abs(c) == 1 else f"({abs(c)}{sign})"
         out.append(s)
     return out
+
+
+def randomized_smiles(strings, vocab, n, seed=0, device="cuda", return_status=False):
+    """n randomised spellings of every string (SMILES enumeration): a list of n-lists, spelling j of string i drawn with draw = i * n + j
+    (include/mvae.h, "SMILES rewrite"): the same graph under this library's walk, NOT canonical and not rdkit's doRandom.  A string that
+    cannot be respelled comes back as it is, n times; ``return_status=True`` also returns the int32 [len(strings), n] statuses
+    (ops.REWRITE_STATUS_NAMES).  One mvae_smiles_rewrite_rows launch on ``device``; ``device="cpu"`` asks for the host entry instead
+    (the same source compiled for the CPU).  ValueError for a vocabulary of more than 64 ids, n < 1 or no strings."""
+    from . import ops
+    from .vocab import smiles_token_table, smiles_chem_table, smiles_emit_table
+    strings, n = list(strings), int(n)
+    if n < 1 or not strings:
+        raise ValueError("randomized_smiles: needs at least one string and n >= 1")
+    if len(vocab) > 64:
+        raise ValueError(f"randomized_smiles: the vocabulary has {len(vocab)} ids, at most 64 are supported")
+    dev = torch.device(device)
+    ids = [vocab.string2ids(s, add_bos=True, add_eos=True) for s in strings for _ in range(n)]
+    x = torch.full((len(ids), max(map(len, ids))), vocab.pad, dtype=torch.long)
+    for b, row in enumerate(ids):
+        x[b, :len(row)] = torch.as_tensor(row)
+    tables = (smiles_token_table(vocab), smiles_chem_table(vocab), smiles_emit_table(vocab))
+    if dev.type == "cpu":
+        out, out_len, status = ops.smiles_rewrite_host(x, *tables, vocab.bos, vocab.eos, vocab.pad, seed)
+    else:
+        from .models import _require_cuda
+        _require_cuda(dev, "data.randomized_smiles")
+        out, out_len, status = ops.smiles_rewrite_rows(x.to(dev), *(t.to(dev) for t in tables), vocab.bos, vocab.eos, vocab.pad, seed)
+    out, out_len, status = out.cpu().numpy(), out_len.cpu().numpy(), status.cpu().numpy()
+    table = np.array([vocab.i2c[i] for i in range(len(vocab))], dtype=object)
+    flat = [s if st else "".join(table[row[1:k - 1]]) for s, row, k, st in zip((s for s in strings for _ in range(n)), out, out_len, status)]
+    res = [flat[i * n:(i + 1) * n] for i in range(len(strings))]
+    return (res, status.reshape(len(strings), n)) if return_status else res
 
 
 def indices_to_smiles(idx, charset):

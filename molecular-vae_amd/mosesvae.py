@@ -33,7 +33,7 @@ from . import _lib as L
 from . import ops
 from .models import (LinearWeights, EmbeddingWeights, RNNWeights, _Workspace, _SavedState, _pad, _require_cuda, _LDPAD, _dyk, _grad_views, _kmajor_gemm,
                      _pack_rnn_stack, _gru_param_grads)
-from .vocab import PaddedBatch, pad_batch, token_rows, length_order, smiles_token_table, smiles_chem_table
+from .vocab import PaddedBatch, pad_batch, token_rows, length_order, smiles_token_table, smiles_chem_table, smiles_emit_table
 
 
 class _RowsWorkspace(_Workspace):
@@ -514,6 +514,32 @@ class VAE(_SavedState, nn.Module):
             raise ValueError(f"kekule: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
         return ops.kekule_dict(*ops.smiles_kekule_rows(self._rows(x, "kekule", dev), self._smiles_table(dev), self._smiles_chem_table(dev),
                                                        self.eos, mate=None if mate else False))
+
+    def _smiles_emit_table(self, dev):
+        return self._vocab_table("smi_emit", smiles_emit_table, dev)
+
+    @torch.no_grad()
+    def respell(self, x, seed=0, draw=None, max_content=127):
+        """A randomised respelling of token rows x (what ``syntax_valid`` takes) on the device, one mvae_smiles_rewrite_rows launch, no
+        host wait: (rows int64 [B, max(T, max_content + 2)] -- <bos>, the new tokens, <eos>, <pad> --, status int32 [B],
+        ops.REWRITE_STATUS_NAMES).  Row b is read into the walk's graph and written back from a random root in a random neighbour order,
+        a pure function of (the row, seed, draw[b]); draw: integers [B] taken mod 2^32, None for the row numbers.  A row that cannot be
+        respelled (status != 0: not well-formed or not valence-consistent, stereo tokens, a multiple bond that would close a ring, no
+        free ring digit, more than 15 open branches, more than max_content tokens, a token the vocabulary lacks) comes back unchanged.
+        The same graph under this library's walk; NOT a canonical SMILES and not rdkit's doRandom (include/mvae.h, "SMILES rewrite").
+        ValueError for a vocabulary of more than 64 ids."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.respell")
+        if len(self.vocabulary) > 64:
+            raise ValueError(f"respell: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
+        x = self._rows(x, "respell", dev)
+        if draw is not None:
+            draw = ops.draw_words(torch.as_tensor(draw).to(dev).reshape(-1))
+            if draw.numel() != x.shape[0]:
+                raise ValueError(f"respell: draw has {draw.numel()} entries, x has {x.shape[0]} rows")
+        rows, _, status = ops.smiles_rewrite_rows(x, self._smiles_table(dev), self._smiles_chem_table(dev), self._smiles_emit_table(dev),
+                                                  self.bos, self.eos, self.pad, seed, draw, max_content)
+        return rows, status
 
     @torch.no_grad()
     def descriptors(self, x):

@@ -1012,6 +1012,102 @@ def kekule_dict(status, desc, mate):
     return out
 
 
+# include/mvae.h, "SMILES rewrite": MVAE_SMILES_STEREO .. MVAE_SMILES_NO_TOKEN, given by the rewrite entries only
+(SMILES_STATUS_STEREO, SMILES_STATUS_RING_MULTI, SMILES_STATUS_RING_DIGITS, SMILES_STATUS_DEPTH, SMILES_STATUS_LONG,
+ SMILES_STATUS_NO_TOKEN) = range(8, 14)
+REWRITE_STATUS_NAMES = KEKULE_STATUS_NAMES + ("stereo", "ring_multi", "ring_digits", "depth", "long", "no_token")
+REWRITE_COUNTS = 16                           # the length of the per-status histogram
+REWRITE_EMIT = 48                             # include/mvae.h: MVAE_REWRITE_EMIT
+
+
+def _rewrite_tables(tok_info, chem_info, emit, draw, counts, n, dev, max_content):
+    _graph_tables(tok_info, chem_info, dev)
+    assert emit.dtype == torch.int32 and emit.shape == (REWRITE_EMIT,) and emit.is_contiguous() and emit.device == dev, (emit.dtype, emit.shape)
+    if not 1 <= int(max_content) <= 127:
+        raise ValueError(f"smiles_rewrite: max_content must be in [1, 127], got {max_content}")
+    if draw is not None:                         # uint32 [n], carried as int32 bits
+        assert draw.dtype == torch.int32 and draw.shape == (n,) and draw.is_contiguous() and draw.device == dev, (draw.dtype, tuple(draw.shape))
+    if counts is not None:
+        assert counts.dtype == torch.int32 and counts.shape == (REWRITE_COUNTS,) and counts.is_contiguous() and counts.device == dev
+
+
+def draw_words(values):
+    """An integer tensor (any values; taken mod 2^32) as the int32 tensor whose bits are the uint32 `draw` argument of the rewrite entries."""
+    v = values.to(torch.int64) & 0xFFFFFFFF
+    return torch.where(v >= 1 << 31, v - (1 << 32), v).to(torch.int32)
+
+
+def _rewrite_row_outputs(B, T_out, dev, out, out_len, status):
+    out = torch.empty(B, T_out, dtype=torch.int64, device=dev) if out is None else out
+    out_len = torch.empty(B, dtype=torch.int32, device=dev) if out_len is None else out_len
+    status = torch.empty(B, dtype=torch.int32, device=dev) if status is None else status
+    for t, dt, shape in ((out, torch.int64, (B, T_out)), (out_len, torch.int32, (B,)), (status, torch.int32, (B,))):
+        assert t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev, (dt, shape)
+    return out, out_len, status
+
+
+def smiles_rewrite_rows(x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, seed=0, draw=None, max_content=127, T_out=None, out=None,
+                        out_len=None, status=None, counts=None):
+    """A randomised respelling of token rows x (int64 [B, T], bos first) on the device: (out int64 [B, T_out], out_len int32 [B], status
+    int32 [B]) -- every row read into the walk's graph and written back from a random root in a random neighbour order, a pure function
+    of (row, seed, draw[b]) (include/mvae.h, "SMILES rewrite"); a row that cannot be respelled (status != 0: the walk's 1 - 6, or
+    SMILES_STATUS_STEREO .. SMILES_STATUS_NO_TOKEN) is copied through unchanged.  draw: int32 [B] holding uint32 bits (``draw_words``),
+    None for the row number; T_out defaults to max(T, max_content + 2), so that nothing is cut; counts (int32 [16], optional, zeroed by
+    the caller) += the per-status histogram.  NOT a canonical SMILES, no stereo, not rdkit's doRandom.  One launch
+    (mvae_smiles_rewrite_rows)."""
+    x, ldx = _token_rows(x, "x")
+    B, T = x.shape
+    _rewrite_tables(tok_info, chem_info, emit, draw, counts, B, x.device, max_content)
+    T_out = max(T, int(max_content) + 2) if T_out is None else int(T_out)
+    res = _rewrite_row_outputs(B, T_out, x.device, out, out_len, status)
+    check(L.load().mvae_smiles_rewrite_rows(B, T, tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), ptr(emit), int(bos_id), int(eos_id),
+                                            int(pad_id), int(seed) & 0xFFFFFFFF, ptr(draw), int(max_content), T_out, *map(ptr, res), ptr(counts),
+                                            stream_ptr()), "mvae_smiles_rewrite_rows")
+    return res
+
+
+def smiles_rewrite_host(x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, seed=0, draw=None, max_content=127, T_out=None, out=None,
+                        out_len=None, status=None):
+    """smiles_rewrite_rows on HOST tensors: the same source compiled for the CPU, a plain loop over the rows (mvae_smiles_rewrite_host) --
+    for tests and for machines without a device; not a fallback of the device entries."""
+    x, ldx = _token_rows(x, "x")
+    assert x.device.type == "cpu", x.device
+    B, T = x.shape
+    _rewrite_tables(tok_info, chem_info, emit, draw, None, B, x.device, max_content)
+    T_out = max(T, int(max_content) + 2) if T_out is None else int(T_out)
+    res = _rewrite_row_outputs(B, T_out, x.device, out, out_len, status)
+    check(L.load().mvae_smiles_rewrite_host(B, T, tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), ptr(emit), int(bos_id), int(eos_id),
+                                            int(pad_id), int(seed) & 0xFFFFFFFF, ptr(draw), int(max_content), T_out, *map(ptr, res)),
+          "mvae_smiles_rewrite_host")
+    return res
+
+
+def smiles_rewrite_corpus(tokens, offsets, N, rows, tok_info, chem_info, emit, seed=0, draw=None, max_content=127, stride=None, tokens_out=None,
+                          offsets_out=None, status=None, counts=None, err=None):
+    """smiles_rewrite_rows over the rows `rows` (int64 [B]) of the CSR corpus (tokens uint8, offsets int64 [N + 1]), one launch
+    (mvae_smiles_rewrite_corpus): (tokens_out uint8 [B, stride], offsets_out int64 [2 B + 1], status int32 [B]).  offsets_out = 0, len_0,
+    stride, stride + len_1, ...: tokens_out is a CSR of 2 B rows whose even rows are the batch members, so ``moses_collate`` with rows =
+    0, 2, 4, ... collates it unchanged.  stride defaults to max_content; err (int32 [1], optional, zeroed by the caller) is raised to 1
+    by a copied-through row longer than stride and to 2 by a row id outside [0, N)."""
+    N, B = int(N), rows.numel()
+    dev = tokens.device
+    assert tokens.dtype == torch.uint8 and offsets.dtype == torch.int64 and offsets.numel() >= N + 1 and offsets.device == dev
+    assert tokens.is_contiguous() and offsets.is_contiguous()
+    assert rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_contiguous() and rows.device == dev and B >= 1
+    _rewrite_tables(tok_info, chem_info, emit, draw, counts, B, dev, max_content)
+    stride = int(max_content) if stride is None else int(stride)
+    tokens_out = torch.empty(B, stride, dtype=torch.uint8, device=dev) if tokens_out is None else tokens_out
+    offsets_out = torch.empty(2 * B + 1, dtype=torch.int64, device=dev) if offsets_out is None else offsets_out
+    status = torch.empty(B, dtype=torch.int32, device=dev) if status is None else status
+    for t, dt, shape in ((tokens_out, torch.uint8, (B, stride)), (offsets_out, torch.int64, (2 * B + 1,)), (status, torch.int32, (B,))):
+        assert t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev, (dt, shape)
+    assert err is None or (err.dtype == torch.int32 and err.numel() == 1 and err.device == dev)
+    check(L.load().mvae_smiles_rewrite_corpus(ptr(tokens), ptr(offsets), N, ptr(rows), B, tok_info.numel(), ptr(tok_info), ptr(chem_info), ptr(emit),
+                                              int(seed) & 0xFFFFFFFF, ptr(draw), int(max_content), stride, ptr(tokens_out), ptr(offsets_out),
+                                              ptr(status), ptr(counts), ptr(err), stream_ptr()), "mvae_smiles_rewrite_corpus")
+    return tokens_out, offsets_out, status
+
+
 def key_histogram(keys, weights=None):
     """The distinct non-zero keys of an int64 tensor, ascending (as signed integers), and how often each occurs -- or, with ``weights``
     (an integer tensor of the same shape), the sum of its weights: (keys int64 [n], counts int64 [n]) on the keys' device.  One

@@ -195,3 +195,38 @@ def smiles_chem_table(vocab):
         elif cls in (SMI_BOND, SMI_MINUS):
             table[i] = _SMI_BOND_ORDER[ch] << 8
     return torch.tensor(table, dtype=torch.int32)
+
+
+# the SMILES rewrite (include/mvae.h, "SMILES rewrite"; csrc/smiles_rewrite.hip): the roles of the emit table
+SMI_EMIT_WORDS = 48
+SMI_EMIT_ALIPHATIC, SMI_EMIT_AROMATIC = 0, 11                      # + the element's index into SMI_ELEMENTS
+_SMI_EMIT_ROLES = {22: "l", 23: "r", 24: "[", 25: "]", 26: "H", 27: "+", 28: "-", 29: "=", 30: "#", 31: "(", 32: ")",
+                   **{33 + d: str(d) for d in range(10)}}
+SMI_EMIT_STEREO = 43                                               # words 43 / 44: the low / high half of the stereo mask
+_SMI_STEREO_CHARS = "@/\\"
+
+
+def smiles_emit_table(vocab):
+    """The table the SMILES rewrite writes its output from, beside ``smiles_token_table`` / ``smiles_chem_table``: int32 [48], one id per
+    role -- [0 .. 10] the first character of element e in upper case (H B C N O F P S C B I: Cl and Br are written head plus tail),
+    [11 .. 21] in lower case (b c n o p s; -1 for the rest), then 'l' 'r' '[' ']' 'H' '+' '-' '=' '#' '(' ')' and the digits 0 .. 9;
+    -1 where the vocabulary lacks the character or ``smiles_token_table`` calls it OTHER (a lone parenthesis, a tail without its head).
+    Words 43 / 44: the low / high 32 bits of the mask of the stereo tokens '@' '/' '\\' (bit i: id i).  ValueError for more than 64 ids."""
+    if len(vocab) > 64:
+        raise ValueError(f"smiles_emit_table: the vocabulary has {len(vocab)} ids, at most 64 are supported")
+    usable = smiles_token_table(vocab)
+
+    def role(ch):
+        i = vocab.c2i.get(ch)
+        return -1 if i is None or (int(usable[i]) & 0xFF) == SMI_OTHER else i
+    table = [0] * SMI_EMIT_WORDS
+    for e, sym in enumerate(SMI_ELEMENTS):
+        table[SMI_EMIT_ALIPHATIC + e] = role(sym[0])
+        table[SMI_EMIT_AROMATIC + e] = role(sym.lower()) if sym in ("B", "C", "N", "O", "P", "S") else -1
+    for k, ch in _SMI_EMIT_ROLES.items():
+        table[k] = role(ch)
+    mask = sum(1 << vocab.c2i[ch] for ch in _SMI_STEREO_CHARS if ch in vocab.c2i)
+    for k in range(2):
+        half = (mask >> (32 * k)) & 0xFFFFFFFF
+        table[SMI_EMIT_STEREO + k] = half - (1 << 32) if half >= 1 << 31 else half
+    return torch.tensor(table, dtype=torch.int32)
