@@ -79,69 +79,41 @@ SMI_HD void rounds(Atoms& at, Ids& A, Ids& B, Clos& cl, Bits& bits, int n, int n
   hash_round(2u, at, B, A, cl, bits, n, nclos);
 }
 
-// One row: the walk, then the rounds; status and the 16 words are written together (zeros for a row that is not OK).
-template <class Atoms, class Ids, class Clos, class Bits, class Src>
-SMI_HD void row(Atoms& at, Ids& A, Ids& B, Clos& cl, Bits& bits, const Src& src, int first, int end, bool end_is_eos, int V,
-                const int32_t* tok_info, const int32_t* chem_info, int eos_id, long b, int32_t* status, int64_t* fp) {
-  Rec<Clos> rec(cl);
-  smg::Row r;
-  smg::walk(at, src, first, end, end_is_eos, V, tok_info, chem_info, eos_id, &r, rec);
-  for (int w = 0; w < DWORDS; ++w) bits.set(w, 0u);
-  if (r.status == smg::OK) rounds(at, A, B, cl, bits, rec.n, rec.nclos, rec.ring);
-  status[b] = r.status;
-  for (int w = 0; w < WORDS; ++w) fp[b * WORDS + w] = (int64_t)((uint64_t)bits.get(2 * w) | (uint64_t)bits.get(2 * w + 1) << 32);
-}
+// The consumer the row driver (smiles_rounds.hpp) runs.  at: the atom words; A, B: the two id arrays; bits: the 1024 bits; cl: the closures.
+struct Fp {
+  template <template <class, int> class Arr>
+  struct Store {
+    Arr<uint32_t, smg::ATOM_SLOTS> at, A, B;
+    Arr<uint32_t, DWORDS> bits;
+    Arr<uint16_t, CLOSURES> cl;
+  };
+  typedef Store<LdsMem> Lds;
+  static __device__ Store<LdsArr> lane(Lds& l) { return {l.at.lane(), l.A.lane(), l.B.lane(), l.bits.lane(), l.cl.lane()}; }
+  typedef Store<HostArr> Host;
+
+  struct Out {
+    int32_t* status;
+    int64_t* fp;
+    bool ok() const { return status && fp; }
+  };
+
+  // One row: the walk, then the rounds; status and the 16 words are written together (zeros for a row that is not OK).
+  template <class S, class Src>
+  static SMI_HD void row(S& s, const Src& src, int first, int end, bool end_is_eos, int V, const int32_t* tok_info, const int32_t* chem_info,
+                         int eos_id, long b, const Out& o) {
+    Rec<decltype(s.cl)> rec(s.cl);
+    smg::Row r;
+    smg::walk(s.at, src, first, end, end_is_eos, V, tok_info, chem_info, eos_id, &r, rec);
+    for (int w = 0; w < DWORDS; ++w) s.bits.set(w, 0u);
+    if (r.status == smg::OK) rounds(s.at, s.A, s.B, s.cl, s.bits, rec.n, rec.nclos, rec.ring);
+    o.status[b] = r.status;
+    for (int w = 0; w < WORDS; ++w) o.fp[b * WORDS + w] = (int64_t)((uint64_t)s.bits.get(2 * w) | (uint64_t)s.bits.get(2 * w + 1) << 32);
+  }
+};
 
 }  // namespace fpr
 
 namespace {
-
-// ---------------------------------------------------------------------------------------------------------------- fingerprint
-using fpr::LdsArr;
-using fpr::HostArr;
-using fpr::PaddedSrc;
-using fpr::CsrSrc;
-
-typedef LdsArr<uint32_t, smg::ATOM_SLOTS> LdsWords;
-typedef LdsArr<uint16_t, fpr::CLOSURES> LdsClos;
-typedef LdsArr<uint32_t, fpr::DWORDS> LdsBits;
-
-struct FpLds {
-  uint32_t atoms[smg::ATOM_SLOTS * 64], a[smg::ATOM_SLOTS * 64], b[smg::ATOM_SLOTS * 64], bits[fpr::DWORDS * 64];
-  uint16_t clos[fpr::CLOSURES * 64];
-};
-
-__global__ __launch_bounds__(64) void smiles_fp_rows_kernel(int B, int T, int V, const int64_t* __restrict__ x, long x_ld,
-                                                            const int32_t* __restrict__ tok_info, const int32_t* __restrict__ chem_info, int eos_id,
-                                                            int32_t* __restrict__ status, int64_t* __restrict__ fp) {
-  __shared__ FpLds lds;
-  const int b = blockIdx.x * 64 + threadIdx.x;
-  if (b >= B) return;
-  LdsWords at{lds.atoms + threadIdx.x}, A{lds.a + threadIdx.x}, Bi{lds.b + threadIdx.x};
-  LdsClos cl{lds.clos + threadIdx.x};
-  LdsBits bits{lds.bits + threadIdx.x};
-  fpr::row(at, A, Bi, cl, bits, PaddedSrc{x + (long)b * x_ld}, 1, T, false, V, tok_info, chem_info, eos_id, (long)b, status, fp);
-}
-
-__global__ __launch_bounds__(64) void smiles_fp_corpus_kernel(const uint8_t* __restrict__ tokens, const int64_t* __restrict__ offsets, long N, int V,
-                                                              const int32_t* __restrict__ tok_info, const int32_t* __restrict__ chem_info,
-                                                              int32_t* __restrict__ status, int64_t* __restrict__ fp) {
-  __shared__ FpLds lds;
-  const long b = (long)blockIdx.x * 64 + threadIdx.x;
-  if (b >= N) return;
-  const long lo = offsets[b], hi = offsets[b + 1];
-  const long len = hi > lo ? hi - lo : 0;
-  LdsWords at{lds.atoms + threadIdx.x}, A{lds.a + threadIdx.x}, Bi{lds.b + threadIdx.x};
-  LdsClos cl{lds.clos + threadIdx.x};
-  LdsBits bits{lds.bits + threadIdx.x};
-  fpr::row(at, A, Bi, cl, bits, CsrSrc{tokens + lo}, 0, (int)(len < INT_MAX - 1 ? len : INT_MAX - 1), true, V, tok_info, chem_info, -1, b, status,
-           fp);
-}
-
-bool fp_rows_args_ok(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info, int eos_id,
-                     const int32_t* status, const int64_t* fp) {
-  return x && tok_info && chem_info && status && fp && B >= 1 && T >= 1 && V >= 1 && x_ld >= T && eos_id >= 0 && eos_id < V;
-}
 
 // ---------------------------------------------------------------------------------------------------------------- Tanimoto
 constexpr int TN_QT = 64;           // queries per block tile
@@ -432,35 +404,17 @@ extern "C" {
 
 int mvae_smiles_fp_rows(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info, int eos_id,
                         int32_t* status, int64_t* fp, void* stream) {
-  if (V > 64) return MVAE_ERR_UNSUPPORTED;
-  if (!fp_rows_args_ok(B, T, V, x, x_ld, tok_info, chem_info, eos_id, status, fp)) return MVAE_ERR_INVALID;
-  hipLaunchKernelGGL(smiles_fp_rows_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, T, V, x, (long)x_ld, tok_info, chem_info,
-                     eos_id, status, fp);
-  MVAE_CHECK_HIP(hipGetLastError());
-  return MVAE_OK;
+  return fpr::rows<fpr::Fp>(B, T, V, x, x_ld, tok_info, chem_info, eos_id, stream, status, fp);
 }
 
 int mvae_smiles_fp_corpus(const uint8_t* tokens, const int64_t* offsets, int64_t N, int V, const int32_t* tok_info, const int32_t* chem_info,
                           int32_t* status, int64_t* fp, void* stream) {
-  if (V > 64) return MVAE_ERR_UNSUPPORTED;
-  if (!tokens || !offsets || !tok_info || !chem_info || !status || !fp || N < 1 || V < 1) return MVAE_ERR_INVALID;
-  if ((N + 63) / 64 > (int64_t)INT_MAX) return MVAE_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(smiles_fp_corpus_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, tokens, offsets, (long)N, V,
-                     tok_info, chem_info, status, fp);
-  MVAE_CHECK_HIP(hipGetLastError());
-  return MVAE_OK;
+  return fpr::corpus<fpr::Fp>(tokens, offsets, N, V, tok_info, chem_info, stream, status, fp);
 }
 
 int mvae_smiles_fp_host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info, int eos_id,
                         int32_t* status, int64_t* fp) {
-  if (V > 64) return MVAE_ERR_UNSUPPORTED;
-  if (!fp_rows_args_ok(B, T, V, x, x_ld, tok_info, chem_info, eos_id, status, fp)) return MVAE_ERR_INVALID;
-  HostArr<uint32_t, smg::ATOM_SLOTS> at, A, Bi;
-  HostArr<uint16_t, fpr::CLOSURES> cl;
-  HostArr<uint32_t, fpr::DWORDS> bits;
-  for (long b = 0; b < B; ++b)
-    fpr::row(at, A, Bi, cl, bits, PaddedSrc{x + b * x_ld}, 1, T, false, V, tok_info, chem_info, eos_id, b, status, fp);
-  return MVAE_OK;
+  return fpr::host<fpr::Fp>(B, T, V, x, x_ld, tok_info, chem_info, eos_id, status, fp);
 }
 
 size_t mvae_tanimoto_knn_workspace(int Q, int64_t N, int k) {

@@ -19,8 +19,6 @@
 //   A search that finds no augmenting path leaves its root free for good (no later augmentation can help it), so there are at most
 //   |N| - 2 * greedy searches, and most rows need none; with one free atom at most no path can exist and none is looked for.
 //   Every loop carries a bound that follows from n <= 127 whatever the arrays hold, and every LDS index goes through the slot mask.
-#include <limits.h>
-
 #include "common.hpp"
 #include "smiles_rounds.hpp"
 
@@ -160,143 +158,101 @@ struct Forest {
   }
 };
 
-// One row: the walk, N and E, the matching; all outputs are written together.  W: the atom words; C: the closure list; M, P, Bs, Q: the
-// byte arrays.
-template <class Words, class Clos, class Bytes, class Src>
-SMI_HD void row(Words& W, Clos& C, Bytes& M, Bytes& P, Bytes& Bs, Bytes& Q, const Src& src, int first, int end, bool end_is_eos, int V,
-                const int32_t* tok_info, const int32_t* chem_info, int eos_id, long b, int32_t* status, int32_t* desc, uint8_t* mate) {
-  fpr::Rec<Clos> rec(C);
-  smg::Row r;
-  smg::walk(W, src, first, end, end_is_eos, V, tok_info, chem_info, eos_id, &r, rec);
-  int st = r.status, nN = 0, nE = 0, pairs = 0, n = 0;
-  if (r.status == smg::OK) {
-    n = rec.n;
-    const int nclos = rec.nclos;
-    const smg::Mask rb = fpr::ring_bonds(W, C, nclos);
-    smg::Mask N{0, 0};
-    for (int k = 0; k < n; ++k) {
-      const uint32_t w = W.get(k);
-      if (smg::a_arom(w) && smallest_valence(smg::a_elem(w), smg::a_chg(w), smg::a_used(w)) - smg::a_used(w) >= 1) smg::m_set(N, k);
-      M.set(k, (uint8_t)FREE);
-    }
-    nN = smg::m_count(N);
-    // E, and the greedy matching along it.  An atom of N is aromatic, so "both ends aromatic" is part of "both ends in N".
-    for (int k = 1; k < n; ++k) {
-      const uint32_t w = W.get(k);
-      const int p = smg::a_pred(w);
-      const bool in_e = p != smg::NONE && (w >> 24) == 1u && smg::m_get(rb, k) && smg::m_get(N, k) && smg::m_get(N, p);
-      if (!in_e) { W.set(k, w | 0xFFu); continue; }
-      ++nE;
-      if (M.get(k) == FREE && M.get(p) == FREE) { M.set(k, (uint8_t)p); M.set(p, (uint8_t)k); ++pairs; }
-    }
-    for (int c = 0; c < nclos; ++c) {
-      const int pr = C.get(c), i = pr & 0xFF, j = pr >> 8;
-      if (!smg::m_get(N, i) || !smg::m_get(N, j)) { C.set(c, (uint16_t)0xFFFFu); continue; }
-      ++nE;
-      if (M.get(i) == FREE && M.get(j) == FREE) { M.set(i, (uint8_t)j); M.set(j, (uint8_t)i); ++pairs; }
-    }
-    if (2 * pairs < nN) {
-      Forest<Bytes> f{M, P, Bs, Q, N, n};
-      for (int v = 0; v < n && 2 * pairs + 1 < nN; ++v) {
-        if (!smg::m_get(N, v) || M.get(v) != FREE) continue;
-        const int t = f.search(W, C, nclos, v);
-        if (t != FREE) { f.augment(t); ++pairs; }
+// The consumer the row driver (smiles_rounds.hpp) runs.  W: the atom words; C: the closure list; M, P, Bs, Q: the byte arrays mate, parent,
+// base, queue.
+struct Kekule {
+  template <template <class, int> class Arr>
+  struct Store {
+    Arr<uint32_t, SLOTS> W;
+    Arr<uint16_t, fpr::CLOSURES> C;
+    Arr<uint8_t, SLOTS> M, P, Bs, Q;
+  };
+  typedef Store<fpr::LdsMem> Lds;
+  static __device__ Store<fpr::LdsArr> lane(Lds& l) { return {l.W.lane(), l.C.lane(), l.M.lane(), l.P.lane(), l.Bs.lane(), l.Q.lane()}; }
+  typedef Store<fpr::HostArr> Host;
+  static_assert(sizeof(Lds) == MVAE_KEKULE_LDS_BYTES, "include/mvae.h states the LDS per block");
+
+  struct Out {
+    int32_t* status;
+    int32_t* desc;
+    uint8_t* mate;       // optional
+    bool ok() const { return status && desc; }
+  };
+
+  // One row: the walk, N and E, the matching; all outputs are written together.
+  template <class S, class Src>
+  static SMI_HD void row(S& s, const Src& src, int first, int end, bool end_is_eos, int V, const int32_t* tok_info, const int32_t* chem_info,
+                         int eos_id, long b, const Out& o) {
+    auto& W = s.W;
+    auto& C = s.C;
+    auto &M = s.M, &P = s.P, &Bs = s.Bs, &Q = s.Q;
+    fpr::Rec<decltype(s.C)> rec(C);
+    smg::Row r;
+    smg::walk(W, src, first, end, end_is_eos, V, tok_info, chem_info, eos_id, &r, rec);
+    int st = r.status, nN = 0, nE = 0, pairs = 0, n = 0;
+    if (r.status == smg::OK) {
+      n = rec.n;
+      const int nclos = rec.nclos;
+      const smg::Mask rb = fpr::ring_bonds(W, C, nclos);
+      smg::Mask N{0, 0};
+      for (int k = 0; k < n; ++k) {
+        const uint32_t w = W.get(k);
+        if (smg::a_arom(w) && smallest_valence(smg::a_elem(w), smg::a_chg(w), smg::a_used(w)) - smg::a_used(w) >= 1) smg::m_set(N, k);
+        M.set(k, (uint8_t)FREE);
       }
+      nN = smg::m_count(N);
+      // E, and the greedy matching along it.  An atom of N is aromatic, so "both ends aromatic" is part of "both ends in N".
+      for (int k = 1; k < n; ++k) {
+        const uint32_t w = W.get(k);
+        const int p = smg::a_pred(w);
+        const bool in_e = p != smg::NONE && (w >> 24) == 1u && smg::m_get(rb, k) && smg::m_get(N, k) && smg::m_get(N, p);
+        if (!in_e) { W.set(k, w | 0xFFu); continue; }
+        ++nE;
+        if (M.get(k) == FREE && M.get(p) == FREE) { M.set(k, (uint8_t)p); M.set(p, (uint8_t)k); ++pairs; }
+      }
+      for (int c = 0; c < nclos; ++c) {
+        const int pr = C.get(c), i = pr & 0xFF, j = pr >> 8;
+        if (!smg::m_get(N, i) || !smg::m_get(N, j)) { C.set(c, (uint16_t)0xFFFFu); continue; }
+        ++nE;
+        if (M.get(i) == FREE && M.get(j) == FREE) { M.set(i, (uint8_t)j); M.set(j, (uint8_t)i); ++pairs; }
+      }
+      if (2 * pairs < nN) {
+        Forest<decltype(s.M)> f{M, P, Bs, Q, N, n};
+        for (int v = 0; v < n && 2 * pairs + 1 < nN; ++v) {
+          if (!smg::m_get(N, v) || M.get(v) != FREE) continue;
+          const int t = f.search(W, C, nclos, v);
+          if (t != FREE) { f.augment(t); ++pairs; }
+        }
+      }
+      if (2 * pairs != nN) st = KEKULE;
     }
-    if (2 * pairs != nN) st = KEKULE;
+    o.status[b] = st;
+    int32_t* d = o.desc + 4 * b;
+    d[0] = nN; d[1] = nE; d[2] = pairs; d[3] = nN - 2 * pairs;
+    if (o.mate) {
+      uint8_t* m = o.mate + b * SLOTS;
+      for (int k = 0; k < SLOTS; ++k) m[k] = k < n ? M.get(k) : (uint8_t)FREE;
+    }
   }
-  status[b] = st;
-  desc[4 * b] = nN; desc[4 * b + 1] = nE; desc[4 * b + 2] = pairs; desc[4 * b + 3] = nN - 2 * pairs;
-  if (mate) {
-    uint8_t* m = mate + b * SLOTS;
-    for (int k = 0; k < SLOTS; ++k) m[k] = k < n ? M.get(k) : (uint8_t)FREE;
-  }
-}
+};
 
 }  // namespace kek
-
-namespace {
-
-typedef fpr::LdsArr<uint32_t, smg::ATOM_SLOTS> LdsWords;
-typedef fpr::LdsArr<uint16_t, fpr::CLOSURES> LdsClos;
-typedef fpr::LdsArr<uint8_t, smg::ATOM_SLOTS> LdsBytes;
-
-struct KekLds {
-  uint32_t words[smg::ATOM_SLOTS * 64];
-  uint16_t clos[fpr::CLOSURES * 64];
-  uint8_t mate[smg::ATOM_SLOTS * 64], parent[smg::ATOM_SLOTS * 64], base[smg::ATOM_SLOTS * 64], queue[smg::ATOM_SLOTS * 64];
-};
-static_assert(sizeof(KekLds) == MVAE_KEKULE_LDS_BYTES, "include/mvae.h states the LDS per block");
-
-__global__ __launch_bounds__(64) void smiles_kekule_rows_kernel(int B, int T, int V, const int64_t* __restrict__ x, long x_ld,
-                                                                const int32_t* __restrict__ tok_info, const int32_t* __restrict__ chem_info,
-                                                                int eos_id, int32_t* __restrict__ status, int32_t* __restrict__ desc,
-                                                                uint8_t* __restrict__ mate) {
-  __shared__ KekLds lds;
-  const int b = blockIdx.x * 64 + threadIdx.x;
-  if (b >= B) return;
-  LdsWords W{lds.words + threadIdx.x};
-  LdsClos C{lds.clos + threadIdx.x};
-  LdsBytes M{lds.mate + threadIdx.x}, P{lds.parent + threadIdx.x}, Bs{lds.base + threadIdx.x}, Q{lds.queue + threadIdx.x};
-  kek::row(W, C, M, P, Bs, Q, fpr::PaddedSrc{x + (long)b * x_ld}, 1, T, false, V, tok_info, chem_info, eos_id, (long)b, status, desc, mate);
-}
-
-__global__ __launch_bounds__(64) void smiles_kekule_corpus_kernel(const uint8_t* __restrict__ tokens, const int64_t* __restrict__ offsets, long N,
-                                                                  int V, const int32_t* __restrict__ tok_info,
-                                                                  const int32_t* __restrict__ chem_info, int32_t* __restrict__ status,
-                                                                  int32_t* __restrict__ desc, uint8_t* __restrict__ mate) {
-  __shared__ KekLds lds;
-  const long b = (long)blockIdx.x * 64 + threadIdx.x;
-  if (b >= N) return;
-  const long lo = offsets[b], hi = offsets[b + 1];
-  const long len = hi > lo ? hi - lo : 0;
-  LdsWords W{lds.words + threadIdx.x};
-  LdsClos C{lds.clos + threadIdx.x};
-  LdsBytes M{lds.mate + threadIdx.x}, P{lds.parent + threadIdx.x}, Bs{lds.base + threadIdx.x}, Q{lds.queue + threadIdx.x};
-  kek::row(W, C, M, P, Bs, Q, fpr::CsrSrc{tokens + lo}, 0, (int)(len < INT_MAX - 1 ? len : INT_MAX - 1), true, V, tok_info, chem_info, -1, b,
-           status, desc, mate);
-}
-
-bool kekule_rows_args_ok(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info, int eos_id,
-                         const int32_t* status, const int32_t* desc) {
-  return x && tok_info && chem_info && status && desc && B >= 1 && T >= 1 && V >= 1 && x_ld >= T && eos_id >= 0 && eos_id < V;
-}
-
-}  // namespace
 
 extern "C" {
 
 int mvae_smiles_kekule_rows(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info, int eos_id,
                             int32_t* status, int32_t* desc, uint8_t* mate, void* stream) {
-  if (V > 64) return MVAE_ERR_UNSUPPORTED;
-  if (!kekule_rows_args_ok(B, T, V, x, x_ld, tok_info, chem_info, eos_id, status, desc)) return MVAE_ERR_INVALID;
-  hipLaunchKernelGGL(smiles_kekule_rows_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, T, V, x, (long)x_ld, tok_info,
-                     chem_info, eos_id, status, desc, mate);
-  MVAE_CHECK_HIP(hipGetLastError());
-  return MVAE_OK;
+  return fpr::rows<kek::Kekule>(B, T, V, x, x_ld, tok_info, chem_info, eos_id, stream, status, desc, mate);
 }
 
 int mvae_smiles_kekule_corpus(const uint8_t* tokens, const int64_t* offsets, int64_t N, int V, const int32_t* tok_info,
                               const int32_t* chem_info, int32_t* status, int32_t* desc, uint8_t* mate, void* stream) {
-  if (V > 64) return MVAE_ERR_UNSUPPORTED;
-  if (!tokens || !offsets || !tok_info || !chem_info || !status || !desc || N < 1 || V < 1) return MVAE_ERR_INVALID;
-  if ((N + 63) / 64 > (int64_t)INT_MAX) return MVAE_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(smiles_kekule_corpus_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, tokens, offsets, (long)N, V,
-                     tok_info, chem_info, status, desc, mate);
-  MVAE_CHECK_HIP(hipGetLastError());
-  return MVAE_OK;
+  return fpr::corpus<kek::Kekule>(tokens, offsets, N, V, tok_info, chem_info, stream, status, desc, mate);
 }
 
 int mvae_smiles_kekule_host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info, int eos_id,
                             int32_t* status, int32_t* desc, uint8_t* mate) {
-  if (V > 64) return MVAE_ERR_UNSUPPORTED;
-  if (!kekule_rows_args_ok(B, T, V, x, x_ld, tok_info, chem_info, eos_id, status, desc)) return MVAE_ERR_INVALID;
-  fpr::HostArr<uint32_t, smg::ATOM_SLOTS> W;
-  fpr::HostArr<uint16_t, fpr::CLOSURES> C;
-  fpr::HostArr<uint8_t, smg::ATOM_SLOTS> M, P, Bs, Q;
-  for (long b = 0; b < B; ++b)
-    kek::row(W, C, M, P, Bs, Q, fpr::PaddedSrc{x + b * x_ld}, 1, T, false, V, tok_info, chem_info, eos_id, b, status, desc, mate);
-  return MVAE_OK;
+  return fpr::host<kek::Kekule>(B, T, V, x, x_ld, tok_info, chem_info, eos_id, status, desc, mate);
 }
 
 }  // extern "C"

@@ -21,8 +21,6 @@
 //   of those parts hold ring atoms -- the component criterion of the definition, which is what repeated leaf deletion leaves.
 //   Keys: the rounds are edge-centric as the fingerprint's, restricted to the bonds inside the subset; the molecule key and the scaffold
 //   key run one after the other through the same two arrays.
-#include <limits.h>
-
 #include "common.hpp"
 #include "smiles_rounds.hpp"
 
@@ -141,131 +139,92 @@ SMI_HD uint64_t graph_key(Atoms& at, Ids& I, Ids& D, Clos& cl, int n, int nclos,
   return key ? key : 1ull;
 }
 
-// One row: the walk, the sets, the two keys; all outputs are written together (zeros for a row that is not OK).  W: the walk's atom
-// words and then the sums; I: the ids; H: the 16-bit array.
-template <class Words, class Half, class Src>
-SMI_HD void row(Words& W, Words& I, Half& H, const Src& src, int first, int end, bool end_is_eos, int V, const int32_t* tok_info,
-                const int32_t* chem_info, int eos_id, long b, int32_t* status, int64_t* mask, int32_t* desc, int64_t* key) {
-  TopClos<Half> cl{H};
-  fpr::Rec<TopClos<Half>> rec(cl);
-  smg::Row r;
-  smg::walk(W, src, first, end, end_is_eos, V, tok_info, chem_info, eos_id, &r, rec);
-  smg::Mask s{0, 0};
-  int d0 = 0, d1 = 0, d2 = 0, d3 = 0;
-  uint64_t kmol = 0, kscaf = 0;
-  if (r.status == smg::OK) {
-    const int n = rec.n, nclos = rec.nclos;
-    const smg::Mask ring = rec.ring, all = m_first(n);
-    const bool has_ring = (ring.lo | ring.hi) != 0;
-    const smg::Mask rb = ring_bonds(W, cl, nclos);
-    Sets st{{0, 0}, {0, 0}, 0};
-    if (has_ring) st = scaffold_sets(W, n, ring);
-    // the molecule key's first ids, the only reader of the used valence; then the words give way to the sums
-    const int nb = degrees(W, I, cl, n, nclos, all);
-    for (int k = 0; k < n; ++k) {
-      const uint32_t w = W.get(k);
-      I.set(k, fpr::mix(invariant(w, smg::m_get(ring, k), I.get(k)) | (uint32_t)smg::a_used(w) << 12));
-      H.set(k, pack(w));
+// The consumer the row driver (smiles_rounds.hpp) runs.  W: the walk's atom words and then the sums; I: the ids; H: the 16-bit array.
+struct Scaffold {
+  template <template <class, int> class Arr>
+  struct Store {
+    Arr<uint32_t, smg::ATOM_SLOTS> W, I;
+    Arr<uint16_t, smg::ATOM_SLOTS> H;
+  };
+  typedef Store<fpr::LdsMem> Lds;
+  static __device__ Store<fpr::LdsArr> lane(Lds& l) { return {l.W.lane(), l.I.lane(), l.H.lane()}; }
+  typedef Store<fpr::HostArr> Host;
+  static_assert(sizeof(Lds) == MVAE_SCAFFOLD_LDS_BYTES, "include/mvae.h states the LDS per block");
+
+  struct Out {
+    int32_t* status;
+    int64_t* mask;       // optional
+    int32_t* desc;
+    int64_t* key;
+    bool ok() const { return status && desc && key; }
+  };
+
+  // One row: the walk, the sets, the two keys; all outputs are written together (zeros for a row that is not OK).
+  template <class S, class Src>
+  static SMI_HD void row(S& mem, const Src& src, int first, int end, bool end_is_eos, int V, const int32_t* tok_info, const int32_t* chem_info,
+                         int eos_id, long b, const Out& o) {
+    typedef decltype(mem.H) Half;
+    auto &W = mem.W, &I = mem.I;
+    auto& H = mem.H;
+    TopClos<Half> cl{H};
+    fpr::Rec<TopClos<Half>> rec(cl);
+    smg::Row r;
+    smg::walk(W, src, first, end, end_is_eos, V, tok_info, chem_info, eos_id, &r, rec);
+    smg::Mask s{0, 0};
+    int d0 = 0, d1 = 0, d2 = 0, d3 = 0;
+    uint64_t kmol = 0, kscaf = 0;
+    if (r.status == smg::OK) {
+      const int n = rec.n, nclos = rec.nclos;
+      const smg::Mask ring = rec.ring, all = m_first(n);
+      const bool has_ring = (ring.lo | ring.hi) != 0;
+      const smg::Mask rb = ring_bonds(W, cl, nclos);
+      Sets st{{0, 0}, {0, 0}, 0};
+      if (has_ring) st = scaffold_sets(W, n, ring);
+      // the molecule key's first ids, the only reader of the used valence; then the words give way to the sums
+      const int nb = degrees(W, I, cl, n, nclos, all);
+      for (int k = 0; k < n; ++k) {
+        const uint32_t w = W.get(k);
+        I.set(k, fpr::mix(invariant(w, smg::m_get(ring, k), I.get(k)) | (uint32_t)smg::a_used(w) << 12));
+        H.set(k, pack(w));
+      }
+      PackedAtoms<Half> at{H};
+      kmol = graph_key(at, I, W, cl, n, nclos, all, rb, nb);
+      if (has_ring) {
+        s = st.s;
+        d1 = degrees(at, W, cl, n, nclos, s);
+        for (int k = 0; k < n; ++k)
+          if (smg::m_get(s, k)) I.set(k, fpr::mix(invariant(at.get(k), smg::m_get(ring, k), W.get(k))));
+        kscaf = graph_key(at, I, W, cl, n, nclos, s, rb, d1);
+        d0 = smg::m_count(s);
+        d2 = smg::m_count(st.core) - smg::m_count(ring);
+        d3 = st.exo;
+      }
     }
-    PackedAtoms<Half> at{H};
-    kmol = graph_key(at, I, W, cl, n, nclos, all, rb, nb);
-    if (has_ring) {
-      s = st.s;
-      d1 = degrees(at, W, cl, n, nclos, s);
-      for (int k = 0; k < n; ++k)
-        if (smg::m_get(s, k)) I.set(k, fpr::mix(invariant(at.get(k), smg::m_get(ring, k), W.get(k))));
-      kscaf = graph_key(at, I, W, cl, n, nclos, s, rb, d1);
-      d0 = smg::m_count(s);
-      d2 = smg::m_count(st.core) - smg::m_count(ring);
-      d3 = st.exo;
-    }
+    o.status[b] = r.status;
+    if (o.mask) { o.mask[2 * b] = (int64_t)s.lo; o.mask[2 * b + 1] = (int64_t)s.hi; }
+    int32_t* d = o.desc + 4 * b;
+    d[0] = d0; d[1] = d1; d[2] = d2; d[3] = d3;
+    o.key[2 * b] = (int64_t)kmol; o.key[2 * b + 1] = (int64_t)kscaf;
   }
-  status[b] = r.status;
-  if (mask) { mask[2 * b] = (int64_t)s.lo; mask[2 * b + 1] = (int64_t)s.hi; }
-  desc[4 * b] = d0; desc[4 * b + 1] = d1; desc[4 * b + 2] = d2; desc[4 * b + 3] = d3;
-  key[2 * b] = (int64_t)kmol; key[2 * b + 1] = (int64_t)kscaf;
-}
+};
 
 }  // namespace scf
-
-namespace {
-
-typedef fpr::LdsArr<uint32_t, smg::ATOM_SLOTS> LdsWords;
-typedef fpr::LdsArr<uint16_t, smg::ATOM_SLOTS> LdsHalf;
-
-struct ScfLds {
-  uint32_t words[smg::ATOM_SLOTS * 64], ids[smg::ATOM_SLOTS * 64];
-  uint16_t half[smg::ATOM_SLOTS * 64];
-};
-static_assert(sizeof(ScfLds) == MVAE_SCAFFOLD_LDS_BYTES, "include/mvae.h states the LDS per block");
-
-__global__ __launch_bounds__(64) void smiles_scaffold_rows_kernel(int B, int T, int V, const int64_t* __restrict__ x, long x_ld,
-                                                                  const int32_t* __restrict__ tok_info, const int32_t* __restrict__ chem_info,
-                                                                  int eos_id, int32_t* __restrict__ status, int64_t* __restrict__ mask,
-                                                                  int32_t* __restrict__ desc, int64_t* __restrict__ key) {
-  __shared__ ScfLds lds;
-  const int b = blockIdx.x * 64 + threadIdx.x;
-  if (b >= B) return;
-  LdsWords W{lds.words + threadIdx.x}, I{lds.ids + threadIdx.x};
-  LdsHalf H{lds.half + threadIdx.x};
-  scf::row(W, I, H, fpr::PaddedSrc{x + (long)b * x_ld}, 1, T, false, V, tok_info, chem_info, eos_id, (long)b, status, mask, desc, key);
-}
-
-__global__ __launch_bounds__(64) void smiles_scaffold_corpus_kernel(const uint8_t* __restrict__ tokens, const int64_t* __restrict__ offsets, long N,
-                                                                    int V, const int32_t* __restrict__ tok_info,
-                                                                    const int32_t* __restrict__ chem_info, int32_t* __restrict__ status,
-                                                                    int64_t* __restrict__ mask, int32_t* __restrict__ desc,
-                                                                    int64_t* __restrict__ key) {
-  __shared__ ScfLds lds;
-  const long b = (long)blockIdx.x * 64 + threadIdx.x;
-  if (b >= N) return;
-  const long lo = offsets[b], hi = offsets[b + 1];
-  const long len = hi > lo ? hi - lo : 0;
-  LdsWords W{lds.words + threadIdx.x}, I{lds.ids + threadIdx.x};
-  LdsHalf H{lds.half + threadIdx.x};
-  scf::row(W, I, H, fpr::CsrSrc{tokens + lo}, 0, (int)(len < INT_MAX - 1 ? len : INT_MAX - 1), true, V, tok_info, chem_info, -1, b, status,
-           mask, desc, key);
-}
-
-bool scaffold_rows_args_ok(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info, int eos_id,
-                           const int32_t* status, const int32_t* desc, const int64_t* key) {
-  return x && tok_info && chem_info && status && desc && key && B >= 1 && T >= 1 && V >= 1 && x_ld >= T && eos_id >= 0 && eos_id < V;
-}
-
-}  // namespace
 
 extern "C" {
 
 int mvae_smiles_scaffold_rows(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info, int eos_id,
                               int32_t* status, int64_t* mask, int32_t* desc, int64_t* key, void* stream) {
-  if (V > 64) return MVAE_ERR_UNSUPPORTED;
-  if (!scaffold_rows_args_ok(B, T, V, x, x_ld, tok_info, chem_info, eos_id, status, desc, key)) return MVAE_ERR_INVALID;
-  hipLaunchKernelGGL(smiles_scaffold_rows_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, T, V, x, (long)x_ld, tok_info,
-                     chem_info, eos_id, status, mask, desc, key);
-  MVAE_CHECK_HIP(hipGetLastError());
-  return MVAE_OK;
+  return fpr::rows<scf::Scaffold>(B, T, V, x, x_ld, tok_info, chem_info, eos_id, stream, status, mask, desc, key);
 }
 
 int mvae_smiles_scaffold_corpus(const uint8_t* tokens, const int64_t* offsets, int64_t N, int V, const int32_t* tok_info,
                                 const int32_t* chem_info, int32_t* status, int64_t* mask, int32_t* desc, int64_t* key, void* stream) {
-  if (V > 64) return MVAE_ERR_UNSUPPORTED;
-  if (!tokens || !offsets || !tok_info || !chem_info || !status || !desc || !key || N < 1 || V < 1) return MVAE_ERR_INVALID;
-  if ((N + 63) / 64 > (int64_t)INT_MAX) return MVAE_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(smiles_scaffold_corpus_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, tokens, offsets, (long)N,
-                     V, tok_info, chem_info, status, mask, desc, key);
-  MVAE_CHECK_HIP(hipGetLastError());
-  return MVAE_OK;
+  return fpr::corpus<scf::Scaffold>(tokens, offsets, N, V, tok_info, chem_info, stream, status, mask, desc, key);
 }
 
 int mvae_smiles_scaffold_host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info, int eos_id,
                               int32_t* status, int64_t* mask, int32_t* desc, int64_t* key) {
-  if (V > 64) return MVAE_ERR_UNSUPPORTED;
-  if (!scaffold_rows_args_ok(B, T, V, x, x_ld, tok_info, chem_info, eos_id, status, desc, key)) return MVAE_ERR_INVALID;
-  fpr::HostArr<uint32_t, smg::ATOM_SLOTS> W, I;
-  fpr::HostArr<uint16_t, smg::ATOM_SLOTS> H;
-  for (long b = 0; b < B; ++b)
-    scf::row(W, I, H, fpr::PaddedSrc{x + b * x_ld}, 1, T, false, V, tok_info, chem_info, eos_id, b, status, mask, desc, key);
-  return MVAE_OK;
+  return fpr::host<scf::Scaffold>(B, T, V, x, x_ld, tok_info, chem_info, eos_id, status, mask, desc, key);
 }
 
 }  // extern "C"

@@ -16,8 +16,6 @@
 //   The output row is staged in LDS so that the global stores are done by the whole wave: row r of the block is written by all 64 lanes
 //   over consecutive columns.  That read of the staging area has lanes 64 bytes apart (a 16-way bank conflict); it is two or three
 //   instructions per row against the several thousand of the search.
-#include <limits.h>
-
 #include "common.hpp"
 #include "smiles_rounds.hpp"
 
@@ -354,14 +352,13 @@ __global__ __launch_bounds__(64) void smiles_rewrite_corpus_kernel(const uint8_t
     const long id = rows[b];
     int st = smg::SYNTAX;
     if (id >= 0 && id < N) {
-      lo = offsets[id];
-      const long hi = offsets[id + 1], have = hi > lo ? hi - lo : 0;
+      const long have = fpr::csr_len(offsets, id, &lo);
       LdsWords W{lds.words + lane};
       LdsClos C{lds.clos + lane};
       LdsBytes O{lds.out + lane}, S{lds.start + lane}, D{lds.dfs + lane}, P{lds.parent + lane};
       LdsHalf A{lds.half + lane};
-      st = rew::row(W, C, O, A, S, D, P, fpr::CsrSrc{tokens + lo}, 0, (int)(have < INT_MAX - 1 ? have : INT_MAX - 1), true, V, tok_info,
-                    chem_info, emit, -1, rew::draw_base(seed, draw, b), max_content, &len);
+      st = rew::row(W, C, O, A, S, D, P, fpr::CsrSrc{tokens + lo}, 0, fpr::csr_end(have), true, V, tok_info, chem_info, emit, -1,
+                    rew::draw_base(seed, draw, b), max_content, &len);
       if (len == rew::COPY) {
         keep = (int)(have < stride ? have : stride);
         if (have > stride && err) atomicMax(err, 1);
@@ -392,7 +389,7 @@ __global__ __launch_bounds__(64) void smiles_rewrite_corpus_kernel(const uint8_t
 }
 
 bool rewrite_common_ok(int V, const int32_t* tok_info, const int32_t* chem_info, const int32_t* emit, int max_content, const int32_t* status) {
-  return tok_info && chem_info && emit && status && V >= 1 && max_content >= 1 && max_content <= smg::CONTENT_MAX;
+  return fpr::tables_ok(V, tok_info, chem_info) && emit && status && max_content >= 1 && max_content <= smg::CONTENT_MAX;
 }
 
 bool rewrite_rows_args_ok(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info,

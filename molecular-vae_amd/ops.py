@@ -620,6 +620,21 @@ def gauss_pairwise_lse(z, mu, logvar, out, Nz, Nx, dz, ldz=None, ldp=None):
           "mvae_gauss_pairwise_lse")
 
 
+def _knn_outputs(Q, k, dev, value_dtype, exclude, values, idx):
+    """What the three k-NN wrappers share: exclude (int64 [Q] or None) checked and made contiguous, values [Q, k] of value_dtype and idx
+    [Q, k] int64 allocated where not given, and checked."""
+    if exclude is not None:
+        assert exclude.dtype == torch.int64 and exclude.shape == (Q,) and exclude.device == dev
+        exclude = exclude.contiguous()
+    if values is None:
+        values = torch.empty(Q, max(k, 0), dtype=value_dtype, device=dev)
+    if idx is None:
+        idx = torch.empty(Q, max(k, 0), dtype=torch.int64, device=dev)
+    assert values.shape == (Q, k) and idx.shape == (Q, k) and values.is_contiguous() and idx.is_contiguous()
+    assert values.dtype == value_dtype and idx.dtype == torch.int64 and values.device == dev == idx.device
+    return exclude, values, idx
+
+
 def latent_knn(q, table, k, exclude=None, dist=None, idx=None):
     """The k nearest rows of table [N, dz] for every row of q [Q, dz] (float32, unit stride along d; row strides are passed through) by
     squared Euclidean distance, summed as direct f32 differences: (dist [Q, k] float32, idx [Q, k] int64), ascending in (distance, row);
@@ -636,15 +651,7 @@ def latent_knn(q, table, k, exclude=None, dist=None, idx=None):
         table = table.contiguous()
     ldq = q.stride(0) if Q > 1 else max(q.stride(0), dz)
     ldt = table.stride(0) if N > 1 else max(table.stride(0), dz)
-    if exclude is not None:
-        assert exclude.dtype == torch.int64 and exclude.shape == (Q,) and exclude.device == q.device
-        exclude = exclude.contiguous()
-    if dist is None:
-        dist = torch.empty(Q, max(k, 0), dtype=torch.float32, device=q.device)
-    if idx is None:
-        idx = torch.empty(Q, max(k, 0), dtype=torch.int64, device=q.device)
-    assert dist.shape == (Q, k) and idx.shape == (Q, k) and dist.is_contiguous() and idx.is_contiguous()
-    assert dist.dtype == torch.float32 and idx.dtype == torch.int64 and dist.device == q.device == idx.device
+    exclude, dist, idx = _knn_outputs(Q, k, q.device, torch.float32, exclude, dist, idx)
     nb = lib.mvae_latent_knn_workspace(Q, N, dz, k)
     ws = Scratch.get(nb, q.device, "latent_knn") if nb else None
     check(lib.mvae_latent_knn(Q, N, dz, k, ptr(q), ldq, ptr(table), ldt, ptr(exclude), ptr(dist), ptr(idx), ptr(ws), nb, stream_ptr()),
@@ -656,6 +663,11 @@ EDIT_PATTERN_MAX = 128                       # include/mvae.h: MVAE_EDIT_PATTERN
 EDIT_K_MAX = 32
 EDIT_V_MAX = 64
 EDIT_NONE = 2147483647                       # MVAE_EDIT_NONE: the distance of an empty k-NN entry
+
+
+def _csr(tokens, offsets, N):
+    assert tokens.dtype == torch.uint8 and offsets.dtype == torch.int64 and offsets.numel() >= N + 1 and tokens.device == offsets.device
+    assert tokens.is_contiguous() and offsets.is_contiguous()
 
 
 def _token_rows(t, name):
@@ -695,16 +707,9 @@ def edit_knn(x, tokens, offsets, N, k, eos, V, exclude=None, dist=None, idx=None
     x, ldx = _token_rows(x, "x")
     Q, T = x.shape
     N, k = int(N), int(k)
-    assert tokens.dtype == torch.uint8 and offsets.dtype == torch.int64 and offsets.numel() >= N + 1 and tokens.device == x.device == offsets.device
-    if exclude is not None:
-        assert exclude.dtype == torch.int64 and exclude.shape == (Q,) and exclude.device == x.device
-        exclude = exclude.contiguous()
-    if dist is None:
-        dist = torch.empty(Q, max(k, 0), dtype=torch.int32, device=x.device)
-    if idx is None:
-        idx = torch.empty(Q, max(k, 0), dtype=torch.int64, device=x.device)
-    assert dist.shape == (Q, k) and idx.shape == (Q, k) and dist.is_contiguous() and idx.is_contiguous()
-    assert dist.dtype == torch.int32 and idx.dtype == torch.int64 and dist.device == x.device == idx.device
+    _csr(tokens, offsets, N)
+    assert tokens.device == x.device
+    exclude, dist, idx = _knn_outputs(Q, k, x.device, torch.int32, exclude, dist, idx)
     nb = lib.mvae_edit_knn_workspace(Q, N, k)
     ws = Scratch.get(nb, x.device, "edit_knn") if nb else None
     check(lib.mvae_edit_knn(Q, T, int(V), int(eos), ptr(x), ldx, ptr(tokens), ptr(offsets), N, k, ptr(exclude), ptr(dist), ptr(idx), ptr(ws), nb,
@@ -720,15 +725,22 @@ SMILES_DESC_NAMES = ("heavy_atoms", "bonds", "rings", "ring_atoms", "aromatic_at
 SMILES_STATUS_NAMES = ("ok", "syntax", "valence", "charge", "ring_bond", "aromatic", "too_long")
 
 
-def _graph_outputs(n, dev, status, bad_pos, desc, formula):
-    i32 = torch.int32
-    status = torch.empty(n, dtype=i32, device=dev) if status is None else status
-    bad_pos = torch.empty(n, dtype=i32, device=dev) if bad_pos is None else bad_pos
-    desc = torch.empty(n, SMILES_DESC, dtype=i32, device=dev) if desc is None else desc
-    formula = torch.empty(n, SMILES_ELEMENTS, dtype=i32, device=dev) if formula is None else formula
-    for t, shape in ((status, (n,)), (bad_pos, (n,)), (desc, (n, SMILES_DESC)), (formula, (n, SMILES_ELEMENTS))):
-        assert t.dtype == i32 and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev, (t.dtype, tuple(t.shape), t.device)
-    return status, bad_pos, desc, formula
+def _outputs(n, dev, spec, given):
+    """The output tensors of an entry over n rows.  spec: per output (dtype, trailing shape, may be False); given: the caller's tensors in
+    the same order -- None: allocated here; False where the spec allows it: not computed, None in its place."""
+    out = []
+    for (dt, tail, optional), t in zip(spec, given):
+        if t is None:
+            t = torch.empty(n, *tail, dtype=dt, device=dev)
+        elif t is False and optional:
+            t = None
+        assert t is None or (t.dtype == dt and tuple(t.shape) == (n,) + tail and t.is_contiguous() and t.device == dev), (dt, (n,) + tail)
+        out.append(t)
+    return tuple(out)
+
+
+# status, bad_pos, desc, formula: the outputs of a family as _outputs reads them, in the order of the C entries' arguments
+_GRAPH_OUT = ((torch.int32, (), False), (torch.int32, (), False), (torch.int32, (SMILES_DESC,), False), (torch.int32, (SMILES_ELEMENTS,), False))
 
 
 def _graph_tables(tok_info, chem_info, dev):
@@ -736,42 +748,45 @@ def _graph_tables(tok_info, chem_info, dev):
     assert tok_info.is_contiguous() and chem_info.is_contiguous() and tok_info.device == chem_info.device == dev
 
 
+def _smiles_rows(fn, spec, x, tok_info, chem_info, eos_id, given, host=False):
+    """What the mvae_smiles_<family>_rows and _host entries share: the tensor checks, the outputs of `spec`, the call.  fn: the C entry."""
+    x, ldx = _token_rows(x, "x")
+    assert not host or x.device.type == "cpu", x.device
+    _graph_tables(tok_info, chem_info, x.device)
+    out = _outputs(x.shape[0], x.device, spec, given)
+    check(fn(x.shape[0], x.shape[1], tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), int(eos_id), *map(ptr, out),
+             *(() if host else (stream_ptr(),))), fn.__name__)
+    return out
+
+
+def _smiles_corpus(fn, spec, tokens, offsets, N, tok_info, chem_info, given):
+    """The same for the mvae_smiles_<family>_corpus entries."""
+    N = int(N)
+    _csr(tokens, offsets, N)
+    _graph_tables(tok_info, chem_info, tokens.device)
+    out = _outputs(max(N, 0), tokens.device, spec, given)
+    check(fn(ptr(tokens), ptr(offsets), N, tok_info.numel(), ptr(tok_info), ptr(chem_info), *map(ptr, out), stream_ptr()), fn.__name__)
+    return out
+
+
 def smiles_graph_rows(x, tok_info, chem_info, eos_id, status=None, bad_pos=None, desc=None, formula=None):
     """The SMILES graph walk over token rows x (int64 [B, T], bos first) on the device: (status [B], bad_pos [B], desc [B, 8],
     formula [B, 11]), all int32 -- status 0 where the row is well-formed AND valence-consistent (include/mvae.h, "SMILES graph"), the
     counts and the molecular formula of those rows, zeros for the others.  tok_info / chem_info: vocab.smiles_token_table /
     smiles_chem_table on x's device.  One launch (mvae_smiles_graph_rows)."""
-    x, ldx = _token_rows(x, "x")
-    _graph_tables(tok_info, chem_info, x.device)
-    out = _graph_outputs(x.shape[0], x.device, status, bad_pos, desc, formula)
-    check(L.load().mvae_smiles_graph_rows(x.shape[0], x.shape[1], tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), int(eos_id),
-                                          *map(ptr, out), stream_ptr()), "mvae_smiles_graph_rows")
-    return out
+    return _smiles_rows(L.load().mvae_smiles_graph_rows, _GRAPH_OUT, x, tok_info, chem_info, eos_id, (status, bad_pos, desc, formula))
 
 
 def smiles_graph_corpus(tokens, offsets, N, tok_info, chem_info, status=None, bad_pos=None, desc=None, formula=None):
     """smiles_graph_rows over the CSR corpus (tokens uint8, offsets int64 [N + 1]; rows without specials, the end of a row acting as <eos>,
     bad_pos 0-based in the row): one launch (mvae_smiles_graph_corpus)."""
-    N = int(N)
-    assert tokens.dtype == torch.uint8 and offsets.dtype == torch.int64 and offsets.numel() >= N + 1 and tokens.device == offsets.device
-    assert tokens.is_contiguous() and offsets.is_contiguous()
-    _graph_tables(tok_info, chem_info, tokens.device)
-    out = _graph_outputs(max(N, 0), tokens.device, status, bad_pos, desc, formula)
-    check(L.load().mvae_smiles_graph_corpus(ptr(tokens), ptr(offsets), N, tok_info.numel(), ptr(tok_info), ptr(chem_info), *map(ptr, out),
-                                            stream_ptr()), "mvae_smiles_graph_corpus")
-    return out
+    return _smiles_corpus(L.load().mvae_smiles_graph_corpus, _GRAPH_OUT, tokens, offsets, N, tok_info, chem_info, (status, bad_pos, desc, formula))
 
 
 def smiles_graph_host(x, tok_info, chem_info, eos_id, status=None, bad_pos=None, desc=None, formula=None):
     """smiles_graph_rows on HOST tensors: the same walk compiled for the CPU, a plain loop over the rows (mvae_smiles_graph_host) -- for
     tests and for machines without a device; not a fallback of the device entries."""
-    x, ldx = _token_rows(x, "x")
-    assert x.device.type == "cpu", x.device
-    _graph_tables(tok_info, chem_info, x.device)
-    out = _graph_outputs(x.shape[0], x.device, status, bad_pos, desc, formula)
-    check(L.load().mvae_smiles_graph_host(x.shape[0], x.shape[1], tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), int(eos_id),
-                                          *map(ptr, out)), "mvae_smiles_graph_host")
-    return out
+    return _smiles_rows(L.load().mvae_smiles_graph_host, _GRAPH_OUT, x, tok_info, chem_info, eos_id, (status, bad_pos, desc, formula), host=True)
 
 
 _ATOMIC_WEIGHTS = {}                          # device -> vocab.ATOMIC_WEIGHTS as float32 [11]
@@ -794,51 +809,26 @@ def graph_descriptors(status, bad_pos, desc, formula):
 
 FP_WORDS = 16                                 # include/mvae.h: MVAE_FP_WORDS, the int64 words of a fingerprint (1024 bits)
 TANIMOTO_K_MAX = 32
-
-
-def _fp_outputs(n, dev, status, fp):
-    status = torch.empty(n, dtype=torch.int32, device=dev) if status is None else status
-    fp = torch.empty(n, FP_WORDS, dtype=torch.int64, device=dev) if fp is None else fp
-    for t, dt, shape in ((status, torch.int32, (n,)), (fp, torch.int64, (n, FP_WORDS))):
-        assert t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev, (t.dtype, tuple(t.shape), t.device)
-    return status, fp
+_FP_OUT = ((torch.int32, (), False), (torch.int64, (FP_WORDS,), False))                                  # status, fp
 
 
 def smiles_fp_rows(x, tok_info, chem_info, eos_id, status=None, fp=None):
     """The circular fingerprint of token rows x (int64 [B, T], bos first) on the device: (status int32 [B], fp int64 [B, 16]) -- the
     status of smiles_graph_rows and 1024 bits per row, radius 2, built like ECFP4 but NOT rdkit's Morgan fingerprint (include/mvae.h,
     "Circular fingerprint"); all zeros for a row whose status is not 0.  One launch (mvae_smiles_fp_rows)."""
-    x, ldx = _token_rows(x, "x")
-    _graph_tables(tok_info, chem_info, x.device)
-    out = _fp_outputs(x.shape[0], x.device, status, fp)
-    check(L.load().mvae_smiles_fp_rows(x.shape[0], x.shape[1], tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), int(eos_id),
-                                       *map(ptr, out), stream_ptr()), "mvae_smiles_fp_rows")
-    return out
+    return _smiles_rows(L.load().mvae_smiles_fp_rows, _FP_OUT, x, tok_info, chem_info, eos_id, (status, fp))
 
 
 def smiles_fp_corpus(tokens, offsets, N, tok_info, chem_info, status=None, fp=None):
     """smiles_fp_rows over the CSR corpus (tokens uint8, offsets int64 [N + 1]; rows without specials, the end of a row acting as
     <eos>): one launch (mvae_smiles_fp_corpus)."""
-    N = int(N)
-    assert tokens.dtype == torch.uint8 and offsets.dtype == torch.int64 and offsets.numel() >= N + 1 and tokens.device == offsets.device
-    assert tokens.is_contiguous() and offsets.is_contiguous()
-    _graph_tables(tok_info, chem_info, tokens.device)
-    out = _fp_outputs(max(N, 0), tokens.device, status, fp)
-    check(L.load().mvae_smiles_fp_corpus(ptr(tokens), ptr(offsets), N, tok_info.numel(), ptr(tok_info), ptr(chem_info), *map(ptr, out),
-                                         stream_ptr()), "mvae_smiles_fp_corpus")
-    return out
+    return _smiles_corpus(L.load().mvae_smiles_fp_corpus, _FP_OUT, tokens, offsets, N, tok_info, chem_info, (status, fp))
 
 
 def smiles_fp_host(x, tok_info, chem_info, eos_id, status=None, fp=None):
     """smiles_fp_rows on HOST tensors: the same source compiled for the CPU, a plain loop over the rows (mvae_smiles_fp_host) -- for tests
     and for machines without a device; not a fallback of the device entries."""
-    x, ldx = _token_rows(x, "x")
-    assert x.device.type == "cpu", x.device
-    _graph_tables(tok_info, chem_info, x.device)
-    out = _fp_outputs(x.shape[0], x.device, status, fp)
-    check(L.load().mvae_smiles_fp_host(x.shape[0], x.shape[1], tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), int(eos_id),
-                                       *map(ptr, out)), "mvae_smiles_fp_host")
-    return out
+    return _smiles_rows(L.load().mvae_smiles_fp_host, _FP_OUT, x, tok_info, chem_info, eos_id, (status, fp), host=True)
 
 
 def _fp_table(t, name):
@@ -855,15 +845,7 @@ def tanimoto_knn(q, table, k, exclude=None, sim=None, idx=None):
     q, table = _fp_table(q, "q"), _fp_table(table, "table")
     assert q.device == table.device
     Q, N, k = q.shape[0], table.shape[0], int(k)
-    if exclude is not None:
-        assert exclude.dtype == torch.int64 and exclude.shape == (Q,) and exclude.device == q.device
-        exclude = exclude.contiguous()
-    if sim is None:
-        sim = torch.empty(Q, max(k, 0), dtype=torch.float32, device=q.device)
-    if idx is None:
-        idx = torch.empty(Q, max(k, 0), dtype=torch.int64, device=q.device)
-    assert sim.shape == (Q, k) and idx.shape == (Q, k) and sim.is_contiguous() and idx.is_contiguous()
-    assert sim.dtype == torch.float32 and idx.dtype == torch.int64 and sim.device == q.device == idx.device
+    exclude, sim, idx = _knn_outputs(Q, k, q.device, torch.float32, exclude, sim, idx)
     nb = lib.mvae_tanimoto_knn_workspace(Q, N, k)
     ws = Scratch.get(nb, q.device, "tanimoto_knn") if nb else None
     check(lib.mvae_tanimoto_knn(Q, N, k, ptr(q), ptr(table), ptr(exclude), ptr(sim), ptr(idx), ptr(ws), nb, stream_ptr()), "mvae_tanimoto_knn")
@@ -890,16 +872,8 @@ def tanimoto_sum(a, b, skip_diagonal=False, out=None):
 
 GRAPH_KEY_ROUNDS = 8                          # include/mvae.h: MVAE_GRAPH_KEY_ROUNDS
 SCAFFOLD_DESC = ("atoms", "bonds", "linker_atoms", "exo_atoms")      # the columns of desc [*, 4]
-
-
-def _scaffold_outputs(n, dev, status, mask, desc, key):
-    status = torch.empty(n, dtype=torch.int32, device=dev) if status is None else status
-    mask = None if mask is False else torch.empty(n, 2, dtype=torch.int64, device=dev) if mask is None else mask
-    desc = torch.empty(n, 4, dtype=torch.int32, device=dev) if desc is None else desc
-    key = torch.empty(n, 2, dtype=torch.int64, device=dev) if key is None else key
-    for t, dt, shape in ((status, torch.int32, (n,)), (mask, torch.int64, (n, 2)), (desc, torch.int32, (n, 4)), (key, torch.int64, (n, 2))):
-        assert t is None or (t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev), (dt, shape)
-    return status, mask, desc, key
+# status, mask, desc, key
+_SCAFFOLD_OUT = ((torch.int32, (), False), (torch.int64, (2,), True), (torch.int32, (4,), False), (torch.int64, (2,), False))
 
 
 def smiles_scaffold_rows(x, tok_info, chem_info, eos_id, status=None, mask=None, desc=None, key=None):
@@ -909,37 +883,19 @@ def smiles_scaffold_rows(x, tok_info, chem_info, eos_id, status=None, mask=None,
     on the walk's graph, NOT rdkit's MurckoScaffold, and the keys ignore stereochemistry (include/mvae.h, "Murcko scaffold", "Graph
     key").  Zeros for a row whose status is not 0.  ``mask=False``: no mask is computed (None is returned in its place).  One launch
     (mvae_smiles_scaffold_rows)."""
-    x, ldx = _token_rows(x, "x")
-    _graph_tables(tok_info, chem_info, x.device)
-    out = _scaffold_outputs(x.shape[0], x.device, status, mask, desc, key)
-    check(L.load().mvae_smiles_scaffold_rows(x.shape[0], x.shape[1], tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), int(eos_id),
-                                             *map(ptr, out), stream_ptr()), "mvae_smiles_scaffold_rows")
-    return out
+    return _smiles_rows(L.load().mvae_smiles_scaffold_rows, _SCAFFOLD_OUT, x, tok_info, chem_info, eos_id, (status, mask, desc, key))
 
 
 def smiles_scaffold_corpus(tokens, offsets, N, tok_info, chem_info, status=None, mask=None, desc=None, key=None):
     """smiles_scaffold_rows over the CSR corpus (tokens uint8, offsets int64 [N + 1]; rows without specials, the end of a row acting as
     <eos>): one launch (mvae_smiles_scaffold_corpus)."""
-    N = int(N)
-    assert tokens.dtype == torch.uint8 and offsets.dtype == torch.int64 and offsets.numel() >= N + 1 and tokens.device == offsets.device
-    assert tokens.is_contiguous() and offsets.is_contiguous()
-    _graph_tables(tok_info, chem_info, tokens.device)
-    out = _scaffold_outputs(max(N, 0), tokens.device, status, mask, desc, key)
-    check(L.load().mvae_smiles_scaffold_corpus(ptr(tokens), ptr(offsets), N, tok_info.numel(), ptr(tok_info), ptr(chem_info), *map(ptr, out),
-                                               stream_ptr()), "mvae_smiles_scaffold_corpus")
-    return out
+    return _smiles_corpus(L.load().mvae_smiles_scaffold_corpus, _SCAFFOLD_OUT, tokens, offsets, N, tok_info, chem_info, (status, mask, desc, key))
 
 
 def smiles_scaffold_host(x, tok_info, chem_info, eos_id, status=None, mask=None, desc=None, key=None):
     """smiles_scaffold_rows on HOST tensors: the same source compiled for the CPU, a plain loop over the rows
     (mvae_smiles_scaffold_host) -- for tests and for machines without a device; not a fallback of the device entries."""
-    x, ldx = _token_rows(x, "x")
-    assert x.device.type == "cpu", x.device
-    _graph_tables(tok_info, chem_info, x.device)
-    out = _scaffold_outputs(x.shape[0], x.device, status, mask, desc, key)
-    check(L.load().mvae_smiles_scaffold_host(x.shape[0], x.shape[1], tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), int(eos_id),
-                                             *map(ptr, out)), "mvae_smiles_scaffold_host")
-    return out
+    return _smiles_rows(L.load().mvae_smiles_scaffold_host, _SCAFFOLD_OUT, x, tok_info, chem_info, eos_id, (status, mask, desc, key), host=True)
 
 
 def scaffold_dict(status, mask, desc, key):
@@ -953,15 +909,7 @@ def scaffold_dict(status, mask, desc, key):
 SMILES_STATUS_KEKULE = 7                      # include/mvae.h: MVAE_SMILES_KEKULE, given by the kekule entries only
 KEKULE_STATUS_NAMES = SMILES_STATUS_NAMES + ("kekule",)
 KEKULE_DESC = ("n_atoms", "n_bonds", "pairs", "deficiency")          # the columns of desc [*, 4]: |N|, |E|, maximum matching, |N| - 2 pairs
-
-
-def _kekule_outputs(n, dev, status, desc, mate):
-    status = torch.empty(n, dtype=torch.int32, device=dev) if status is None else status
-    desc = torch.empty(n, 4, dtype=torch.int32, device=dev) if desc is None else desc
-    mate = None if mate is False else torch.empty(n, 128, dtype=torch.uint8, device=dev) if mate is None else mate
-    for t, dt, shape in ((status, torch.int32, (n,)), (desc, torch.int32, (n, 4)), (mate, torch.uint8, (n, 128))):
-        assert t is None or (t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev), (dt, shape)
-    return status, desc, mate
+_KEKULE_OUT = ((torch.int32, (), False), (torch.int32, (4,), False), (torch.uint8, (128,), True))        # status, desc, mate
 
 
 def smiles_kekule_rows(x, tok_info, chem_info, eos_id, status=None, desc=None, mate=None):
@@ -971,37 +919,19 @@ def smiles_kekule_rows(x, tok_info, chem_info, eos_id, status=None, desc=None, m
     otherwise); mate[a] = the partner of atom a in the matching found, 255 = none.  Status 0 here means "kekulisable": a tighter
     necessary condition than valence-consistent, NOT rdkit's Kekulize or SanitizeMol, no aromaticity perception (include/mvae.h,
     "Kekulisation").  ``mate=False``: no mate is written (None is returned in its place).  One launch (mvae_smiles_kekule_rows)."""
-    x, ldx = _token_rows(x, "x")
-    _graph_tables(tok_info, chem_info, x.device)
-    out = _kekule_outputs(x.shape[0], x.device, status, desc, mate)
-    check(L.load().mvae_smiles_kekule_rows(x.shape[0], x.shape[1], tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), int(eos_id),
-                                           *map(ptr, out), stream_ptr()), "mvae_smiles_kekule_rows")
-    return out
+    return _smiles_rows(L.load().mvae_smiles_kekule_rows, _KEKULE_OUT, x, tok_info, chem_info, eos_id, (status, desc, mate))
 
 
 def smiles_kekule_corpus(tokens, offsets, N, tok_info, chem_info, status=None, desc=None, mate=None):
     """smiles_kekule_rows over the CSR corpus (tokens uint8, offsets int64 [N + 1]; rows without specials, the end of a row acting as
     <eos>): one launch (mvae_smiles_kekule_corpus)."""
-    N = int(N)
-    assert tokens.dtype == torch.uint8 and offsets.dtype == torch.int64 and offsets.numel() >= N + 1 and tokens.device == offsets.device
-    assert tokens.is_contiguous() and offsets.is_contiguous()
-    _graph_tables(tok_info, chem_info, tokens.device)
-    out = _kekule_outputs(max(N, 0), tokens.device, status, desc, mate)
-    check(L.load().mvae_smiles_kekule_corpus(ptr(tokens), ptr(offsets), N, tok_info.numel(), ptr(tok_info), ptr(chem_info), *map(ptr, out),
-                                             stream_ptr()), "mvae_smiles_kekule_corpus")
-    return out
+    return _smiles_corpus(L.load().mvae_smiles_kekule_corpus, _KEKULE_OUT, tokens, offsets, N, tok_info, chem_info, (status, desc, mate))
 
 
 def smiles_kekule_host(x, tok_info, chem_info, eos_id, status=None, desc=None, mate=None):
     """smiles_kekule_rows on HOST tensors: the same source compiled for the CPU, a plain loop over the rows (mvae_smiles_kekule_host) --
     for tests and for machines without a device; not a fallback of the device entries."""
-    x, ldx = _token_rows(x, "x")
-    assert x.device.type == "cpu", x.device
-    _graph_tables(tok_info, chem_info, x.device)
-    out = _kekule_outputs(x.shape[0], x.device, status, desc, mate)
-    check(L.load().mvae_smiles_kekule_host(x.shape[0], x.shape[1], tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), int(eos_id),
-                                           *map(ptr, out)), "mvae_smiles_kekule_host")
-    return out
+    return _smiles_rows(L.load().mvae_smiles_kekule_host, _KEKULE_OUT, x, tok_info, chem_info, eos_id, (status, desc, mate), host=True)
 
 
 def kekule_dict(status, desc, mate):
@@ -1037,13 +967,8 @@ def draw_words(values):
     return torch.where(v >= 1 << 31, v - (1 << 32), v).to(torch.int32)
 
 
-def _rewrite_row_outputs(B, T_out, dev, out, out_len, status):
-    out = torch.empty(B, T_out, dtype=torch.int64, device=dev) if out is None else out
-    out_len = torch.empty(B, dtype=torch.int32, device=dev) if out_len is None else out_len
-    status = torch.empty(B, dtype=torch.int32, device=dev) if status is None else status
-    for t, dt, shape in ((out, torch.int64, (B, T_out)), (out_len, torch.int32, (B,)), (status, torch.int32, (B,))):
-        assert t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev, (dt, shape)
-    return out, out_len, status
+def _rewrite_out(T_out):
+    return ((torch.int64, (T_out,), False), (torch.int32, (), False), (torch.int32, (), False))
 
 
 def smiles_rewrite_rows(x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, seed=0, draw=None, max_content=127, T_out=None, out=None,
@@ -1059,7 +984,7 @@ def smiles_rewrite_rows(x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, se
     B, T = x.shape
     _rewrite_tables(tok_info, chem_info, emit, draw, counts, B, x.device, max_content)
     T_out = max(T, int(max_content) + 2) if T_out is None else int(T_out)
-    res = _rewrite_row_outputs(B, T_out, x.device, out, out_len, status)
+    res = _outputs(B, x.device, _rewrite_out(T_out), (out, out_len, status))
     check(L.load().mvae_smiles_rewrite_rows(B, T, tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), ptr(emit), int(bos_id), int(eos_id),
                                             int(pad_id), int(seed) & 0xFFFFFFFF, ptr(draw), int(max_content), T_out, *map(ptr, res), ptr(counts),
                                             stream_ptr()), "mvae_smiles_rewrite_rows")
@@ -1075,7 +1000,7 @@ def smiles_rewrite_host(x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, se
     B, T = x.shape
     _rewrite_tables(tok_info, chem_info, emit, draw, None, B, x.device, max_content)
     T_out = max(T, int(max_content) + 2) if T_out is None else int(T_out)
-    res = _rewrite_row_outputs(B, T_out, x.device, out, out_len, status)
+    res = _outputs(B, x.device, _rewrite_out(T_out), (out, out_len, status))
     check(L.load().mvae_smiles_rewrite_host(B, T, tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), ptr(emit), int(bos_id), int(eos_id),
                                             int(pad_id), int(seed) & 0xFFFFFFFF, ptr(draw), int(max_content), T_out, *map(ptr, res)),
           "mvae_smiles_rewrite_host")
@@ -1091,8 +1016,7 @@ def smiles_rewrite_corpus(tokens, offsets, N, rows, tok_info, chem_info, emit, s
     by a copied-through row longer than stride and to 2 by a row id outside [0, N)."""
     N, B = int(N), rows.numel()
     dev = tokens.device
-    assert tokens.dtype == torch.uint8 and offsets.dtype == torch.int64 and offsets.numel() >= N + 1 and offsets.device == dev
-    assert tokens.is_contiguous() and offsets.is_contiguous()
+    _csr(tokens, offsets, N)
     assert rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_contiguous() and rows.device == dev and B >= 1
     _rewrite_tables(tok_info, chem_info, emit, draw, counts, B, dev, max_content)
     stride = int(max_content) if stride is None else int(stride)

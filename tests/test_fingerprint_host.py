@@ -70,13 +70,13 @@ def test_new_kernels_use_no_scratch(tmp_path):
         assert run.returncode == 0, run.stderr[-2000:]
         text = run.stderr
     names = re.findall(r"Function Name: (\S+)", text)
-    kernels = ("smiles_fp_rows_kernel", "smiles_fp_corpus_kernel", "tanimoto_knn_scan_kernel", "tanimoto_knn_merge_kernel", "tanimoto_sum_kernel",
+    kernels = ("rows_kernelINS_2FpE", "corpus_kernelINS_2FpE", "tanimoto_knn_scan_kernel", "tanimoto_knn_merge_kernel", "tanimoto_sum_kernel",
                "tanimoto_sum_final_kernel")
     assert len(names) == 6 and all(any(k in n for n in names) for k in kernels), names
     assert re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", text) == ["0"] * 6
     assert re.findall(r"VGPRs Spill: (\d+)", text) == ["0"] * 6 and re.findall(r"SGPRs Spill: (\d+)", text) == ["0"] * 6
     lds = dict(zip(names, map(int, re.findall(r"LDS Size \[bytes/block\]: (\d+)", text))))
-    assert [v for n, v in lds.items() if "smiles_fp_" in n] == [112 * 1024] * 2
+    assert [v for n, v in lds.items() if "_kernelINS_2FpE" in n] == [112 * 1024] * 2
     assert all(int(v) <= 128 for v in re.findall(r" VGPRs: (\d+)", text))
 
 

@@ -116,7 +116,7 @@ def test_new_kernels_use_no_scratch(tmp_path):
         assert run.returncode == 0, run.stderr[-2000:]
         text = run.stderr
     names = re.findall(r"Function Name: (\S+)", text)
-    assert len(names) == 2 and all(any(k in n for n in names) for k in ("smiles_kekule_rows_kernel", "smiles_kekule_corpus_kernel")), names
+    assert len(names) == 2 and all(any(k in n for n in names) for k in ("rows_kernelIN3kek6KekuleE", "corpus_kernelIN3kek6KekuleE")), names
     assert re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", text) == ["0"] * 2
     assert re.findall(r"VGPRs Spill: (\d+)", text) == ["0"] * 2 and re.findall(r"SGPRs Spill: (\d+)", text) == ["0"] * 2
     header = open(os.path.join(ROOT, "include", "mvae.h")).read()
