@@ -36,6 +36,9 @@ that alone, and with ``--novel_against`` audits the corpus once (``MosesDeviceDa
 ``--valence`` counts, still not rdkit's verdict: no aromaticity perception, not rdkit's Kekulize.
 ``--respell N`` prints, at the end, N randomised spellings of each of the first five unique samples (``VAE.respell``: the same graph
 under the SMILES graph walk, written from a random root in a random neighbour order -- not canonical, not rdkit's doRandom).
+``--canonical`` prints, for each round, the distinct canonical spellings among its samples (``mv.moses_generate(canonical=True)``:
+this library's canonical SMILES -- two spellings of one graph count once, compared on tokens; no aromaticity perception, no stereo, not
+rdkit's) and, with ``--novel_against``, how many of them are in no row of the canonicalised corpus (``MosesDeviceDataset.canonical``).
 ``--reconstruct FILE`` (strings, one per line) skips the generation: it encodes the strings (z = mu), decodes them deterministically
 (``--beam_width``) without and with the syntax constraint (``mv.moses_reconstruction(..., syntax=)``) and prints the exact-match
 reconstruction fraction of each, the mean log p(x | mu) and the mean token edit distance between input and decode.
@@ -85,6 +88,8 @@ ap.add_argument("--kekule", action="store_true", help="count the kekulisable sam
                                                       "their ring double bond)")
 ap.add_argument("--respell", default=0, type=int, metavar="N", help="at the end print N randomised spellings (VAE.respell) of each of the first "
                                                                    "five unique samples the walk accepts")
+ap.add_argument("--canonical", action="store_true", help="print each round's distinct canonical spellings (unique@k on graphs) and, with "
+                                                         "--novel_against, those absent from the canonicalised corpus")
 ap.add_argument("--reconstruct", default=None, metavar="FILE", help="strings, one per line: report exact-match reconstruction at z = mu "
                                                                   "without and with the syntax constraint, then exit")
 ap.add_argument("--beam_width", default=1, type=int, help="with --reconstruct: the beam width of the deterministic decode")
@@ -151,7 +156,7 @@ with open(args.log, "w", buffering=1) as f:
         res = mv.moses_generate(model, per_round, batch_size=args.batch_size, max_len=args.max_len, temp=args.temp, top_k=args.top_k,
                                 top_p=args.top_p, seed=args.seed + r * args.batches_per_round, syntax=args.syntax, count_valid=True,
                                 novel_against=corpus, prefix=args.prefix, nearest=args.nearest, valence=args.valence,
-                                int_div=args.int_div, snn=args.snn, scaffolds=args.scaffolds, kekule=args.kekule)
+                                int_div=args.int_div, snn=args.snn, scaffolds=args.scaffolds, kekule=args.kekule, canonical=args.canonical)
         total += res["total"]
         if args.kekule:
             kekule_valid += res["kekule_valid"]
@@ -189,6 +194,9 @@ with open(args.log, "w", buffering=1) as f:
               + (f", this round's distinct graphs {res['unique_graphs']} and scaffolds {res['n_scaffolds']}" if args.scaffolds else "")
               + (f", Scaf {res['scaf']:.4f}, scaffolds not in the corpus {res['scaffold_novel']}, graphs not in the corpus {res['graph_novel']}"
                  if args.scaffolds and corpus is not None else "")
+              + (f", this round's distinct canonical spellings {res['unique_canonical']} of {res['canonical_status_counts'][0]} written"
+                 if args.canonical else "")
+              + (f", of which in no corpus row {res['novel_canonical']}" if args.canonical and corpus is not None else "")
               + (f", valid unique {valid}" if Chem is not None else "")
               + (f", novel {len(novel)} ({len(novel) / len(seen):.3f} of unique)" if corpus is not None else ""), flush=True)
 if args.respell > 0 and seen:

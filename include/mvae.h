@@ -1071,6 +1071,60 @@ int mvae_smiles_rewrite_host(int B, int T, int V, const int64_t* x, int64_t x_ld
                              int32_t* out_len /* [B] */, int32_t* status /* [B] */);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * SMILES canon (an addition: a sixth consumer of the "SMILES graph" walk above).  A token row is read into its graph and written back
+ * as ONE spelling that is meant not to depend on how the row was spelled, so that rows can be compared as molecules by comparing tokens.
+ * Graph, refusals, traversal, emission, the emit table and the output layouts are exactly the "SMILES rewrite" section's; only the
+ * order of the atoms changes: atoms compare by canonical rank where that section says (prio, atom number).  There is no seed and no
+ * draw, and no new status code; a refused row is copied through unchanged, as there.
+ * First invariant.  Every atom gets the tuple (element -- its number in H B C N O F P S Cl Br I --, aromatic, charge, bracket flag,
+ *   bracket hydrogens h(a) (0 for an unbracketed atom), degree, sum of its bond orders), compared left to right; rank(a) = the position
+ *   of a's tuple among the distinct tuples.  The bracket flag is part of it: [CH4] and C stay different strings, as the rewrite keeps them.
+ * Refinement.  key(a) = (rank(a), the multiset of (bond order, rank(b)) over the neighbours b of a, compared as an ascending sorted
+ *   tuple); the new rank(a) = the position of key(a) among the distinct keys.  Rounds are repeated until one does not raise the number of
+ *   classes (distinct ranks).  The comparison is exact: nothing is hashed.  Bond orders are the graph's: 1, 2, 3, a closure 1, a bond
+ *   between aromatic atoms 1.
+ * Ties.  While there are fewer classes than atoms: in the class of lowest rank that has more than one member, the member of lowest atom
+ *   number (string order) keeps the rank and the others come just above it (every higher rank moves up by one); then refine again.
+ * Bounds.  Every round of a refinement but its last adds a class, and so does every tie; n atoms have at most n classes, so there are at
+ *   most n - 1 ties and class-adding rounds together, at most n refinements, and at most 2 n rounds in all.  The loops are bounded by that.
+ * Search.  The root is the atom of rank 0; at an atom, bonds of order 2 or 3 first, then by the other end's rank; RING_MULTI and the
+ *   other refusals keep the rewrite's precedence.
+ * What is claimed.  Equal output rows (status 0) => equal graphs, always: the output spells the input's graph.  Equal graphs => equal
+ *   output rows whenever, at every tie, the members of the chosen class are equivalent under a symmetry of the graph; that holds on the
+ *   whole test corpus, cage and spiro rows included, where every choice at every tie is followed, and is NOT proved in general.
+ * What this is NOT: not rdkit's canonical SMILES.  No aromaticity perception (C1=CC=CC=C1 and c1ccccc1 stay two strings), no stereo
+ *   (STEREO refuses such rows), [CH4] is not unbracketed.
+ * mvae_smiles_canon_rows / _corpus / _host take the arguments of mvae_smiles_rewrite_rows / _corpus / _host without seed and draw, and
+ *   two more outputs, both optional (may be NULL):
+ *   info int32 [B, 4] = atoms, classes after the first refinement, refinement rounds in all, ties broken -- for every row whose ranks
+ *     were computed (the walk gave 0 and no stereo token: status 0 and 9 - 13), zeros otherwise;
+ *   rank uint8 [B, 128]: rank[k] = the canonical rank of atom k (string order), a permutation of 0 .. atoms - 1; 0xFF beyond the atoms,
+ *     and everywhere for a row whose ranks were not computed.
+ *   Every element of the given outputs is written, nothing else is; two runs are bit-identical; the three entries are one source.
+ * One thread per row; MVAE_CANON_LDS_BYTES = 81920 B (80 KiB) of LDS per 64-row block, the rewrite's block with nothing added, so that
+ *   two blocks fit a CU: between the adjacency and the search the output row, the search index and the search parent are idle, and the
+ *   ranks, the atoms sorted by rank and the new ranks live there.  Keys are recomputed from the ranks and the half-edges, never stored;
+ *   only atoms of one class are compared.  The worst row is 127 atoms in a chain (126 rounds).
+ * Refused before anything is enqueued: what the rewrite entries refuse of these arguments.
+ */
+#define MVAE_CANON_INFO 4
+#define MVAE_CANON_LDS_BYTES 81920
+int mvae_smiles_canon_rows(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */,
+                           const int32_t* chem_info /* [V] */, const int32_t* emit /* [48] */, int bos_id, int eos_id, int pad_id,
+                           int max_content, int T_out, int64_t* out /* [B, T_out] */, int32_t* out_len /* [B] */, int32_t* status /* [B] */,
+                           int32_t* counts /* [16] or NULL */, int32_t* info /* [B, 4] or NULL */, uint8_t* rank /* [B, 128] or NULL */,
+                           void* stream);
+int mvae_smiles_canon_corpus(const uint8_t* tokens, const int64_t* offsets /* [N + 1] */, int64_t N, const int64_t* rows /* [B] */, int B,
+                             int V, const int32_t* tok_info /* [V] */, const int32_t* chem_info /* [V] */, const int32_t* emit /* [48] */,
+                             int max_content, int stride, uint8_t* tokens_out /* [B, stride] */, int64_t* offsets_out /* [2 B + 1] */,
+                             int32_t* status /* [B] */, int32_t* counts /* [16] or NULL */, int32_t* err /* [1] or NULL */,
+                             int32_t* info /* [B, 4] or NULL */, uint8_t* rank /* [B, 128] or NULL */, void* stream);
+int mvae_smiles_canon_host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */,
+                           const int32_t* chem_info /* [V] */, const int32_t* emit /* [48] */, int bos_id, int eos_id, int pad_id,
+                           int max_content, int T_out, int64_t* out /* [B, T_out] */, int32_t* out_len /* [B] */, int32_t* status /* [B] */,
+                           int32_t* info /* [B, 4] or NULL */, uint8_t* rank /* [B, 128] or NULL */);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Tanimoto similarity of fingerprints (an addition: the structure-aware counterpart of mvae_latent_knn and mvae_edit_knn).  Fingerprints
  * are dense rows of MVAE_FP_WORDS int64 words, 16-byte aligned (else MVAE_ERR_INVALID); any 1024-bit rows will do.
  * Similarity.  T(a, b) = c / (p_a + p_b - c), with p the popcounts and c the popcount of a AND b; T is 0 when the union is empty.  T is

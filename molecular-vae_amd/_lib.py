@@ -204,6 +204,9 @@ SIGNATURES = {
     "mvae_smiles_rewrite_rows": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _u32, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mvae_smiles_rewrite_corpus": (_i, [_vp, _vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _u32, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvae_smiles_rewrite_host": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _u32, _vp, _i, _i, _vp, _vp, _vp]),
+    "mvae_smiles_canon_rows": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvae_smiles_canon_corpus": (_i, [_vp, _vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvae_smiles_canon_host": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "mvae_tanimoto_knn_workspace": (_sz, [_i, _i64, _i]),
     "mvae_tanimoto_knn": (_i, [_i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mvae_tanimoto_sum_workspace": (_sz, [_i64, _i64]),

@@ -1,9 +1,10 @@
 // What the consumers of the SMILES graph walk share.  For those that work on the finished graph (fingerprint.hip, scaffold.hip, kekule.hip,
-// smiles_rewrite.hip): the mix function, the recorder that keeps bond orders and ring-closure pairs, the loop over all bonds, the ring bonds.
+// smiles_rewrite.hip, smiles_canon.hip): the mix function, the recorder that keeps bond orders and ring-closure pairs, the loop over all bonds, the ring bonds.
 // For all of them: lane-minor LDS storage for everything indexed by a run-time atom number (and its host twin), the two token sources, how
 // a CSR row is read, and the row driver -- rows_kernel<C> / corpus_kernel<C> and the host side rows<C> / corpus<C> / host<C> -- which is
 // the one place that maps a row to a thread and refuses arguments before a launch (smiles_graph.hip, fingerprint.hip, scaffold.hip,
-// kekule.hip; smiles_rewrite.hip copies out block-wide after its rows and keeps its own kernels).  Definitions: include/mvae.h,
+// kekule.hip; smiles_rewrite.hip and smiles_canon.hip copy out block-wide after their rows and keep their own kernels, on the shared
+// writer of smiles_writer.hpp).  Definitions: include/mvae.h,
 // "Circular fingerprint".
 #pragma once
 #include <limits.h>

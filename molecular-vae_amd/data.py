@@ -18,6 +18,8 @@
                            is the exact k-NN by token-level Levenshtein distance over the same corpus (``mvae_edit_knn``).
                            ``batches(augment=True)`` respells every row on the device first (SMILES enumeration:
                            ``mvae_smiles_rewrite_corpus`` in front of the unchanged collate); ``randomized_smiles`` does it for strings.
+                           ``canonical()`` is the corpus in canonical spelling (one ``mvae_smiles_canon_corpus`` launch), whose
+                           ``lookup`` / ``n_distinct`` answer per graph; ``canonical_smiles`` does it for strings.
   * ``load_smiles`` / ``save_encoded`` / ``load_encoded`` -- ``.smi``/CSV in, ``.npz`` (indices + charset + max_len) out.
 """
 import numpy as np
@@ -220,11 +222,15 @@ class MosesDeviceDataset:
         self.tokens = torch.from_numpy(np.concatenate([tokens, np.zeros(1, np.uint8)])).to(self.device)
         self.offsets = torch.from_numpy(np.ascontiguousarray(offsets)).to(self.device)
         self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._no_caches()
+
+    def _no_caches(self):
         self._slots = self._n_distinct_d = self._n_distinct = None     # the corpus index: built on first use
         self._descriptors = None                                       # descriptors(): computed on first use
         self._fingerprints = None                                      # fingerprints(): computed on first use
         self._scaffolds = self._scaffold_hist = self._scaffold_order = self._mol_keys = None     # scaffolds() and what is derived from it
         self._kekule = None
+        self._canonical = None                                         # canonical(): (dataset, status, counts), computed on first use
 
     def __len__(self):
         return self.n
@@ -399,6 +405,51 @@ class MosesDeviceDataset:
             del out["mate"]
             self._kekule = out
         return self._kekule
+
+    def canonical(self):
+        """The corpus in canonical spelling: a ``MosesDeviceDataset`` on the same device whose row r is the canonical spelling of this
+        one's row r (include/mvae.h, "SMILES canon"; a row that cannot be written -- ``canonical_status`` != 0 -- keeps its own
+        spelling), from ONE ``mvae_smiles_canon_corpus`` launch over all rows, its gapped CSR compacted on the device.  Its ``lookup`` /
+        ``contains`` / ``n_distinct`` answer at the level of graphs when they are asked with canonical rows (``VAE.canonical``): two
+        spellings of one graph are one row there, exactly -- token rows are compared, no hash decides.  Not rdkit's canonical SMILES: no
+        aromaticity perception, no stereo.  Cached; the host waits once, for the row lengths.  ValueError for a vocabulary of more than
+        64 ids."""
+        if self._canonical is None:
+            from . import ops
+            from .vocab import smiles_emit_table
+            tok, chem = self._fp_tables("canonical")
+            dev, n, stride = self.device, self.n, max(127, self.max_len)          # a row that is copied through fits
+            counts = torch.zeros(ops.REWRITE_COUNTS, dtype=torch.int32, device=dev)
+            tokens_out, offsets_out, status, _, _ = ops.smiles_canon_corpus(
+                self.tokens, self.offsets, n, torch.arange(n, dtype=torch.long, device=dev), tok, chem, smiles_emit_table(self.vocab).to(dev),
+                127, stride, info=False, rank=False, counts=counts)
+            lens = offsets_out[1::2] - offsets_out[0:-1:2]
+            offsets = torch.zeros(n + 1, dtype=torch.long, device=dev)
+            offsets[1:] = torch.cumsum(lens, 0)
+            keep = torch.arange(stride, device=dev)[None, :] < lens[:, None]
+            ds = object.__new__(MosesDeviceDataset)
+            ds.vocab, ds.n, ds.device = self.vocab, n, dev
+            ds.lengths = lens.to(torch.int32).cpu().numpy()
+            ds.max_len = int(ds.lengths.max())
+            ds.tokens = torch.cat([tokens_out[keep], torch.zeros(1, dtype=torch.uint8, device=dev)])      # the spare byte of __init__
+            ds.offsets = offsets
+            ds.err = torch.zeros(1, dtype=torch.int32, device=dev)
+            ds._no_caches()
+            self._canonical = (ds, status, counts)
+        return self._canonical[0]
+
+    @property
+    def canonical_status(self):
+        """The status of every corpus row under ``canonical()``: int32 [N] on the device, the codes of ``ops.REWRITE_STATUS_NAMES`` (0: row
+        r of ``canonical()`` is the canonical spelling; anything else: it is this corpus' own row r)."""
+        self.canonical()
+        return self._canonical[1]
+
+    @property
+    def canonical_counts(self):
+        """How many corpus rows have each ``canonical_status``: int32 [16] on the device, kept by the kernel's integer atomic adds."""
+        self.canonical()
+        return self._canonical[2]
 
     def scaffold_histogram(self):
         """(keys int64 [n], counts int64 [n]) on the device: the distinct scaffold keys of the corpus rows whose status is 0, ascending,
@@ -722,6 +773,38 @@ def randomized_smiles(strings, vocab, n, seed=0, device="cuda", return_status=Fa
     flat = [s if st else "".join(table[row[1:k - 1]]) for s, row, k, st in zip((s for s in strings for _ in range(n)), out, out_len, status)]
     res = [flat[i * n:(i + 1) * n] for i in range(len(strings))]
     return (res, status.reshape(len(strings), n)) if return_status else res
+
+
+def canonical_smiles(strings, vocab, device="cuda", return_status=False):
+    """The canonical spelling of every string (include/mvae.h, "SMILES canon"): a list of strings, equal for two spellings of one graph
+    under this library's walk -- NOT rdkit's canonical SMILES: no aromaticity perception, no stereo.  A string that cannot be written
+    comes back as it is; ``return_status=True`` also returns the int32 [len(strings)] statuses (ops.REWRITE_STATUS_NAMES).  One
+    mvae_smiles_canon_rows launch on ``device``; ``device="cpu"`` asks for the host entry instead (the same source compiled for the
+    CPU).  ValueError for a vocabulary of more than 64 ids or no strings."""
+    from . import ops
+    from .vocab import smiles_token_table, smiles_chem_table, smiles_emit_table
+    strings = list(strings)
+    if not strings:
+        raise ValueError("canonical_smiles: needs at least one string")
+    if len(vocab) > 64:
+        raise ValueError(f"canonical_smiles: the vocabulary has {len(vocab)} ids, at most 64 are supported")
+    dev = torch.device(device)
+    ids = [vocab.string2ids(s, add_bos=True, add_eos=True) for s in strings]
+    x = torch.full((len(ids), max(map(len, ids))), vocab.pad, dtype=torch.long)
+    for b, row in enumerate(ids):
+        x[b, :len(row)] = torch.as_tensor(row)
+    tables = (smiles_token_table(vocab), smiles_chem_table(vocab), smiles_emit_table(vocab))
+    if dev.type == "cpu":
+        out, out_len, status, _, _ = ops.smiles_canon_host(x, *tables, vocab.bos, vocab.eos, vocab.pad, info=False, rank=False)
+    else:
+        from .models import _require_cuda
+        _require_cuda(dev, "data.canonical_smiles")
+        out, out_len, status, _, _ = ops.smiles_canon_rows(x.to(dev), *(t.to(dev) for t in tables), vocab.bos, vocab.eos, vocab.pad, info=False,
+                                                           rank=False)
+    out, out_len, status = out.cpu().numpy(), out_len.cpu().numpy(), status.cpu().numpy()
+    table = np.array([vocab.i2c[i] for i in range(len(vocab))], dtype=object)
+    res = [s if st else "".join(table[row[1:k - 1]]) for s, row, k, st in zip(strings, out, out_len, status)]
+    return (res, status) if return_status else res
 
 
 def indices_to_smiles(idx, charset):

@@ -542,6 +542,30 @@ class VAE(_SavedState, nn.Module):
         return rows, status
 
     @torch.no_grad()
+    def canonical(self, x, max_content=127, info=False):
+        """The canonical spelling of token rows x (what ``syntax_valid`` takes) on the device, one mvae_smiles_canon_rows launch, no host
+        wait: (rows int64 [B, max(T, max_content + 2)] -- <bos>, the new tokens, <eos>, <pad> --, status int32 [B],
+        ops.REWRITE_STATUS_NAMES).  ``respell`` with the atoms ordered by a canonical rank instead of a hash: two spellings of one graph
+        give one row, so rows can be compared as molecules by comparing tokens (include/mvae.h, "SMILES canon": equal rows always mean
+        equal graphs; the converse is tested on every tie of the test corpus, not proved).  No aromaticity perception, no stereo, NOT
+        rdkit's canonical SMILES.  A row that cannot be written (status != 0, ``respell``'s reasons) comes back unchanged.
+        ``info=True`` also returns {"atoms", "first_classes", "rounds", "ties": int32 [B], "rank": uint8 [B, 128]}.  ValueError for a
+        vocabulary of more than 64 ids."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.canonical")
+        if len(self.vocabulary) > 64:
+            raise ValueError(f"canonical: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
+        x = self._rows(x, "canonical", dev)
+        want = None if info else False
+        rows, _, status, inf, rank = ops.smiles_canon_rows(x, self._smiles_table(dev), self._smiles_chem_table(dev), self._smiles_emit_table(dev),
+                                                           self.bos, self.eos, self.pad, max_content, info=want, rank=want)
+        if not info:
+            return rows, status
+        extra = {name: inf[:, i] for i, name in enumerate(ops.CANON_INFO)}
+        extra["rank"] = rank
+        return rows, status, extra
+
+    @torch.no_grad()
     def descriptors(self, x):
         """The graph walk's figures for token rows x (what ``syntax_valid`` takes), a dict of device tensors -- one graph-walk launch, one matrix-vector product for the weight, no host wait:
         "status" and "bad_pos" as ``chem_valid`` returns them; "heavy_atoms", "bonds", "rings", "ring_atoms", "aromatic_atoms",

@@ -1032,6 +1032,69 @@ def smiles_rewrite_corpus(tokens, offsets, N, rows, tok_info, chem_info, emit, s
     return tokens_out, offsets_out, status
 
 
+CANON_INFO = ("atoms", "first_classes", "rounds", "ties")          # the columns of info [*, 4] (include/mvae.h: MVAE_CANON_INFO)
+
+
+def _canon_out(T_out):
+    return _rewrite_out(T_out) + ((torch.int32, (len(CANON_INFO),), True), (torch.uint8, (128,), True))
+
+
+def smiles_canon_rows(x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content=127, T_out=None, out=None, out_len=None, status=None,
+                      info=None, rank=None, counts=None):
+    """The canonical spelling of token rows x (int64 [B, T], bos first) on the device: (out int64 [B, T_out], out_len int32 [B], status
+    int32 [B], info int32 [B, 4], rank uint8 [B, 128]) -- ``smiles_rewrite_rows`` with the atoms ordered by a canonical rank instead of a
+    hash (include/mvae.h, "SMILES canon"), so no seed and no draw: two spellings of one graph give one row (tested, not proved; no
+    aromaticity perception, no stereo, NOT rdkit's canonical SMILES).  The statuses and the copy-through of a refused row are the
+    rewrite's.  info = atoms, classes after the first refinement, rounds, ties (``CANON_INFO``); rank[k] = the canonical rank of atom k,
+    0xFF beyond the atoms; ``info=False`` / ``rank=False``: not written (None in its place).  One launch (mvae_smiles_canon_rows)."""
+    x, ldx = _token_rows(x, "x")
+    B, T = x.shape
+    _rewrite_tables(tok_info, chem_info, emit, None, counts, B, x.device, max_content)
+    T_out = max(T, int(max_content) + 2) if T_out is None else int(T_out)
+    res = _outputs(B, x.device, _canon_out(T_out), (out, out_len, status, info, rank))
+    check(L.load().mvae_smiles_canon_rows(B, T, tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), ptr(emit), int(bos_id), int(eos_id),
+                                          int(pad_id), int(max_content), T_out, *map(ptr, res[:3]), ptr(counts), ptr(res[3]), ptr(res[4]),
+                                          stream_ptr()), "mvae_smiles_canon_rows")
+    return res
+
+
+def smiles_canon_host(x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content=127, T_out=None, out=None, out_len=None, status=None,
+                      info=None, rank=None):
+    """smiles_canon_rows on HOST tensors: the same source compiled for the CPU, a plain loop over the rows (mvae_smiles_canon_host) -- for
+    tests and for machines without a device; not a fallback of the device entries."""
+    x, ldx = _token_rows(x, "x")
+    assert x.device.type == "cpu", x.device
+    B, T = x.shape
+    _rewrite_tables(tok_info, chem_info, emit, None, None, B, x.device, max_content)
+    T_out = max(T, int(max_content) + 2) if T_out is None else int(T_out)
+    res = _outputs(B, x.device, _canon_out(T_out), (out, out_len, status, info, rank))
+    check(L.load().mvae_smiles_canon_host(B, T, tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), ptr(emit), int(bos_id), int(eos_id),
+                                          int(pad_id), int(max_content), T_out, *map(ptr, res)), "mvae_smiles_canon_host")
+    return res
+
+
+def smiles_canon_corpus(tokens, offsets, N, rows, tok_info, chem_info, emit, max_content=127, stride=None, tokens_out=None, offsets_out=None,
+                        status=None, info=None, rank=None, counts=None, err=None):
+    """smiles_canon_rows over the rows `rows` (int64 [B]) of the CSR corpus, one launch (mvae_smiles_canon_corpus): (tokens_out uint8
+    [B, stride], offsets_out int64 [2 B + 1], status int32 [B], info int32 [B, 4], rank uint8 [B, 128]) in the gapped CSR layout of
+    ``smiles_rewrite_corpus``, with its counts and err; ``info=False`` / ``rank=False``: not written (None in its place)."""
+    N, B = int(N), rows.numel()
+    dev = tokens.device
+    _csr(tokens, offsets, N)
+    assert rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_contiguous() and rows.device == dev and B >= 1
+    _rewrite_tables(tok_info, chem_info, emit, None, counts, B, dev, max_content)
+    stride = int(max_content) if stride is None else int(stride)
+    offsets_out = torch.empty(2 * B + 1, dtype=torch.int64, device=dev) if offsets_out is None else offsets_out
+    assert offsets_out.dtype == torch.int64 and offsets_out.shape == (2 * B + 1,) and offsets_out.is_contiguous() and offsets_out.device == dev
+    spec = ((torch.uint8, (stride,), False), (torch.int32, (), False)) + _canon_out(0)[3:]
+    tokens_out, status, info, rank = _outputs(B, dev, spec, (tokens_out, status, info, rank))
+    assert err is None or (err.dtype == torch.int32 and err.numel() == 1 and err.device == dev)
+    check(L.load().mvae_smiles_canon_corpus(ptr(tokens), ptr(offsets), N, ptr(rows), B, tok_info.numel(), ptr(tok_info), ptr(chem_info), ptr(emit),
+                                            int(max_content), stride, ptr(tokens_out), ptr(offsets_out), ptr(status), ptr(counts), ptr(err),
+                                            ptr(info), ptr(rank), stream_ptr()), "mvae_smiles_canon_corpus")
+    return tokens_out, offsets_out, status, info, rank
+
+
 def key_histogram(keys, weights=None):
     """The distinct non-zero keys of an int64 tensor, ascending (as signed integers), and how often each occurs -- or, with ``weights``
     (an integer tensor of the same shape), the sum of its weights: (keys int64 [n], counts int64 [n]) on the keys' device.  One

@@ -801,7 +801,7 @@ def moses_reconstruction(model, batches, beam_width=1, max_len=100, syntax=False
 @torch.no_grad()
 def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top_k=None, top_p=None, seed=0, z=None, syntax=False,
                    count_valid=False, novel_against=None, prefix=None, nearest=False, valence=False,
-                   int_div=False, snn=False, scaffolds=False, kekule=False):
+                   int_div=False, snn=False, scaffolds=False, kekule=False, canonical=False):
     """The reference's generation pipeline (``hugesample.py``: sample in batches, hash the strings, count unique / total) with the hashing
     and the deduplication on the device: ``n_samples`` sequences from a ``mosesvae.VAE`` in batches of ``batch_size`` (the last one shorter),
     batch j with seed ``seed + j`` and ``temp`` / ``top_k`` / ``top_p`` as ``VAE.sample`` takes them.  ``z`` None draws each batch's latents
@@ -876,7 +876,18 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     "kekule_valid_unique" (of distinct ones) and, with ``novel_against``, "kekule_valid_unique_novel"; "kekule_status_counts" ({status:
     count} over all samples, the codes of ``ops.KEKULE_STATUS_NAMES``); and the lists "kekule_status" and "kekule_deficiency" (the
     aromatic atoms a maximum matching leaves without their double bond; 0 unless the status is 7), aligned with "strings", which travel
-    once, at the end.  Without the flag the launches and the keys of the result are what they were."""
+    once, at the end.  Without the flag the launches and the keys of the result are what they were.
+    ``canonical=True`` (ValueError for a vocabulary of more than 64 ids or max_len > 129, before any device work): unique@k and novelty
+    as MOSES defines them, on canonical strings -- ``VAE.canonical``, this library's canonical spelling (include/mvae.h, "SMILES
+    canon"), NOT rdkit's: no aromaticity perception, no stereo.  Each batch's NEW rows go through one ``mvae_smiles_canon_rows`` launch,
+    no further host wait.  The result gains the lists "canonical_status" (the codes of ``ops.REWRITE_STATUS_NAMES``) and
+    "canonical_strings" (the canonical spelling; the sample's own string where the status is not 0), aligned with "strings";
+    "canonical_status_counts" ({status: count} over the distinct samples); and "unique_canonical", the distinct canonical token rows
+    among the samples of status 0, compared on tokens -- ``OCC`` and ``C(O)C`` are two of "unique" and one of these, with no hash and no
+    collision.  With ``novel_against`` it further gains "canonical_corpus_row", aligned with "strings": the lowest row of
+    ``novel_against.canonical()`` that equals the sample's canonical row, -1 for none (one exact ``lookup`` per batch; the corpus is
+    canonicalised once, by one launch, and cached), and "novel_canonical", the distinct canonical rows of status 0 that equal no
+    corpus row's.  Without the flag the launches and the keys of the result are what they were."""
     n_samples, batch_size, max_len = int(n_samples), int(batch_size), int(max_len)
     if n_samples < 1 or batch_size < 1 or max_len < 1:
         raise ValueError(f"moses_generate: n_samples, batch_size and max_len must be >= 1, got {n_samples}, {batch_size}, {max_len}")
@@ -914,6 +925,11 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         raise ValueError(f"moses_generate: scaffolds=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
     if kekule and len(model.vocabulary) > 64:
         raise ValueError(f"moses_generate: kekule=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
+    if canonical:
+        if len(model.vocabulary) > 64:
+            raise ValueError(f"moses_generate: canonical=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
+        if max_len > 129:
+            raise ValueError(f"moses_generate: canonical=True supports max_len <= 129, got {max_len}")
     if forced is not None and syntax:
         model._check_prefix_syntax(forced, max_len, "moses_generate")      # every sample's prefix, once, before the first batch: rows are sample indices
     i64 = torch.long
@@ -939,7 +955,9 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     n_kek = torch.zeros(3, dtype=i64, device=dev) if kekule else None        # status 0: all samples, distinct ones, distinct and novel
     kek_counts = torch.zeros(8, dtype=i64, device=dev) if kekule else None
     kek_codes = torch.arange(8, dtype=torch.int32, device=dev) if kekule else None
-    stage = [None, None]                                        # pinned staging rows [batch_size, max_len + 1] (ids, end), alternating
+    canons = []                                                 # (canonical row [*, 129], status, corpus row or None) of each new sample, likewise
+    canon_corpus = novel_against.canonical() if canonical and novel_against is not None else None       # one launch, cached by the dataset
+    stage = [None, None]                                       # pinned staging rows [batch_size, max_len + 1] (ids, end), alternating
     pending = None
 
     def convert(job):
@@ -1023,6 +1041,9 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
                 scafs.append((sc["mol_key"], sc["scaffold_key"], sc["atoms"]))
             if kekule:
                 keks.append((kek["status"][sel], kek["deficiency"][sel]))
+            if canonical:
+                c_rows, c_status = model.canonical(x[sel])          # 129 columns: 127 content tokens at the most, and max_len <= 129
+                canons.append((c_rows, c_status, canon_corpus.lookup(c_rows) if canon_corpus is not None else None))
             g0 = counts.numel()
             counts = torch.cat([counts, cnt[src]])
             seen_h, perm = torch.sort(torch.cat([seen_h, hs[src]]))
@@ -1081,6 +1102,20 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         res["kekule_status_counts"] = dict(enumerate(kek_counts.tolist()))
         for i, name in enumerate(("kekule_status", "kekule_deficiency")):
             res[name] = torch.cat([c[i] for c in keks]).tolist() if keks else []
+    if canonical:
+        c_rows = torch.cat([c[0] for c in canons]) if canons else torch.empty((0, 129), dtype=i64, device=dev)
+        c_status = torch.cat([c[1] for c in canons]) if canons else torch.empty(0, dtype=torch.int32, device=dev)
+        res["canonical_status"] = c_status.tolist()
+        res["canonical_status_counts"] = dict(enumerate(torch.bincount(c_status.cpu(), minlength=len(ops.REWRITE_STATUS_NAMES)).tolist()))
+        v = model.vocabulary
+        res["canonical_strings"] = [s if st else v.ids2string(r[:r.index(v.eos) + 1], rem_bos=True, rem_eos=True)
+                                    for s, st, r in zip(strings, res["canonical_status"], c_rows.tolist())]
+        fine = c_status == 0
+        distinct = torch.unique(c_rows[fine], dim=0)
+        res["unique_canonical"] = distinct.shape[0]
+        if novel_against is not None:
+            res["canonical_corpus_row"] = torch.cat([c[2] for c in canons]).tolist() if canons else []
+            res["novel_canonical"] = int((canon_corpus.lookup(distinct) < 0).sum()) if distinct.shape[0] else 0
     return res
 
 
