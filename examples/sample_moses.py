@@ -39,6 +39,10 @@ under the SMILES graph walk, written from a random root in a random neighbour or
 ``--canonical`` prints, for each round, the distinct canonical spellings among its samples (``mv.moses_generate(canonical=True)``:
 this library's canonical SMILES -- two spellings of one graph count once, compared on tokens; no aromaticity perception, no stereo, not
 rdkit's) and, with ``--novel_against``, how many of them are in no row of the canonicalised corpus (``MosesDeviceDataset.canonical``).
+``--filters FILE`` (one SMILES fragment per line, at most 64, each of at most 32 atoms) prints, for each round, the MOSES "Filters"
+figure on them (``mv.moses_generate(filters=)``): the share of the valence-consistent samples that contain none of the fragments, and
+the hits per fragment.  Fragments are matched as graphs (element, aromatic flag, charge, bond class) -- not SMARTS, so MOSES' own MCF
+and PAINS lists cannot be given here, and not rdkit's HasSubstructMatch.
 ``--reconstruct FILE`` (strings, one per line) skips the generation: it encodes the strings (z = mu), decodes them deterministically
 (``--beam_width``) without and with the syntax constraint (``mv.moses_reconstruction(..., syntax=)``) and prints the exact-match
 reconstruction fraction of each, the mean log p(x | mu) and the mean token edit distance between input and decode.
@@ -90,6 +94,8 @@ ap.add_argument("--respell", default=0, type=int, metavar="N", help="at the end 
                                                                    "five unique samples the walk accepts")
 ap.add_argument("--canonical", action="store_true", help="print each round's distinct canonical spellings (unique@k on graphs) and, with "
                                                          "--novel_against, those absent from the canonicalised corpus")
+ap.add_argument("--filters", default=None, metavar="FILE", help="SMILES fragments, one per line: print each round's share of valence-consistent "
+                                                                   "samples that contain none of them, and the hits per fragment")
 ap.add_argument("--reconstruct", default=None, metavar="FILE", help="strings, one per line: report exact-match reconstruction at z = mu "
                                                                   "without and with the syntax constraint, then exit")
 ap.add_argument("--beam_width", default=1, type=int, help="with --reconstruct: the beam width of the deterministic decode")
@@ -142,6 +148,10 @@ if args.nearest and corpus is None:
     sys.exit("--nearest needs --novel_against (the training strings to search)")
 if args.snn and corpus is None:
     sys.exit("--snn needs --novel_against (the training strings to search)")
+filters = None
+if args.filters:
+    with open(args.filters) as ff:
+        filters = mv.compile_substructures([line.strip() for line in ff if line.strip()], model.vocabulary)
 seen, total, valid, syntax_valid = {}, 0, 0, 0
 chem_valid, reasons, props = 0, [0] * 7, {}               # unique valence-consistent string -> (weight, heavy atoms)
 near = {}                                                 # unique string -> (distance, corpus row) of its nearest training string
@@ -156,7 +166,8 @@ with open(args.log, "w", buffering=1) as f:
         res = mv.moses_generate(model, per_round, batch_size=args.batch_size, max_len=args.max_len, temp=args.temp, top_k=args.top_k,
                                 top_p=args.top_p, seed=args.seed + r * args.batches_per_round, syntax=args.syntax, count_valid=True,
                                 novel_against=corpus, prefix=args.prefix, nearest=args.nearest, valence=args.valence,
-                                int_div=args.int_div, snn=args.snn, scaffolds=args.scaffolds, kekule=args.kekule, canonical=args.canonical)
+                                int_div=args.int_div, snn=args.snn, scaffolds=args.scaffolds, kekule=args.kekule, canonical=args.canonical,
+                                filters=filters)
         total += res["total"]
         if args.kekule:
             kekule_valid += res["kekule_valid"]
@@ -197,6 +208,8 @@ with open(args.log, "w", buffering=1) as f:
               + (f", this round's distinct canonical spellings {res['unique_canonical']} of {res['canonical_status_counts'][0]} written"
                  if args.canonical else "")
               + (f", of which in no corpus row {res['novel_canonical']}" if args.canonical and corpus is not None else "")
+              + (f", Filters {res['filters']:.4f} (hits " + ", ".join(f"{p} {h}" for p, h in zip(filters.patterns, res["filter_hits"]))
+                 + f"; undecided {sum(res['filter_undecided'])})" if filters is not None else "")
               + (f", valid unique {valid}" if Chem is not None else "")
               + (f", novel {len(novel)} ({len(novel) / len(seen):.3f} of unique)" if corpus is not None else ""), flush=True)
 if args.respell > 0 and seen:

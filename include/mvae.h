@@ -1125,6 +1125,85 @@ int mvae_smiles_canon_host(int B, int T, int V, const int64_t* x, int64_t x_ld, 
                            int32_t* info /* [B, 4] or NULL */, uint8_t* rank /* [B, 128] or NULL */);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * SMILES substructure (an addition: a seventh consumer of the "SMILES graph" walk above).  Does the molecule a token row spells contain
+ * a given fragment?  The graph is the walk's, with the bond classes of "Circular fingerprint"; nothing is perceived and no toolkit is
+ * matched: this is NOT SMARTS and NOT rdkit's HasSubstructMatch.
+ * Query.  A SMILES fragment in the same vocabulary, a padded row like x (bos first), compiled once on the host into a table of
+ *   MVAE_SUBSTRUCT_WORDS int32 words.  It has at most MVAE_SUBSTRUCT_QATOMS = 32 atoms; a launch takes at most MVAE_SUBSTRUCT_QUERIES =
+ *   64 queries.  It must be a row the walk gives status 0 or 5 (AROMATIC: "an aromatic atom outside a ring" is the one rule that speaks
+ *   about the whole molecule, not the fragment, so cC(=O)O and c[N+](=O)[O-] are queries).  Refused, with qstatus[q] = the reason and a
+ *   table of zeros (a query without atoms, which no row contains): any other walk status (1 - 4, 6); else a stereo token '@' '/' '\'
+ *   (MVAE_SMILES_STEREO); else more than 32 atoms (MVAE_SMILES_QUERY_ATOMS = 14, given by the compile entry alone).
+ * Match.  Row t contains query q iff there is an injective map m from the query's atoms to the row's atoms with
+ *   1. atoms: for every query atom i, element, aromatic flag and charge of i and m(i) are equal.  The bracket flag and hydrogen counts
+ *      are not compared: [nH] matches any aromatic n.  [H] is an atom of element H and matches only an explicit [H];
+ *   2. bonds: for every query bond (i, j), m(i) and m(j) are bonded with the same class -- 1, 2, 3, or 4 for a single bond between two
+ *      aromatic atoms; ring-closure bonds count like any others.
+ *   A monomorphism: the row may have more bonds among the matched atoms.
+ * Search.  Fixed, so that the first match and the number of steps are defined.
+ *   Prefilter: for each of the ten heavy elements B .. I, if the query has more atoms of it than the row, the result is a miss, 0 steps.
+ *   Order: query atoms are placed in string order 0 .. nq - 1.  The candidates for atom 0 are the row's atoms in ascending order.  For
+ *     atom i > 0 the anchor is its lowest-numbered query neighbour below i (the tree predecessor is one), and its candidates are the
+ *     neighbours of m(anchor) in ascending atom number.
+ *   Steps: one step is one candidate examined, whatever rejects it -- already used, atom mismatch, fewer neighbours than the query
+ *     atom, or a missing or wrong-class bond to an earlier-placed query neighbour.  The first complete assignment ends the search; it is
+ *     the lexicographically smallest embedding (m(0), m(1), ...).
+ *   Budget: max_steps per (row, query), 1 .. MVAE_SUBSTRUCT_MAX_STEPS = 2^20.  A search that would examine step max_steps + 1 stops
+ *     UNDECIDED, which is neither hit nor miss.  A search that ends within max_steps steps is decided.
+ * Table of one query (int32 [MVAE_SUBSTRUCT_WORDS = 100]):
+ *   word 0        nq, the atoms
+ *   words 1 - 3   the atoms of element e = 1 .. 10, one byte each: e = 1 .. 4 in word 1, 5 .. 8 in word 2, 9 .. 10 in word 3
+ *   words 4 + 3 i .. 6 + 3 i, for atom i:
+ *     first word   bits 0-3 element, 4 aromatic, 5-6 charge + 1 (the key), 8-10 degree, 12-16 anchor, 20-22 the class of the bond to the
+ *                  anchor, 24-26 the number of other neighbours below i (<= 5)
+ *     second, third  those other neighbours in ascending order, one byte each from bit 0 of the second word: bits 0-4 the neighbour,
+ *                  5-7 the class of the bond to it
+ *   The search entries read a table as it is, with every index masked: a table that the compile entry did not write gives results
+ *   without meaning and nothing worse.
+ * mvae_smiles_substruct_compile_host: Q query rows xq [Q, Tq] into table [Q, 100] and qstatus [Q].  stereo_lo / stereo_hi: the mask of
+ *   the stereo tokens' ids (words 43 / 44 of the rewrite's emit table).  Host only.
+ * mvae_smiles_substruct_rows (padded rows) / _corpus (the CSR corpus, one launch, row b = corpus row b; an empty row is what the graph
+ *   entry makes of it) / _host (the rows entry compiled for the CPU from the same source; counts is accumulated there too):
+ *   status    int32 [B]              the walk's status, as the graph entries give it
+ *   hit       int64 [B]              bit q set: the row contains query q (bit 63 is the sign bit)
+ *   undecided int64 [B]              bit q set: the budget ran out on query q
+ *   map       uint8 [B, 32] or NULL  the first embedding for the one query map_query; 0xFF beyond nq and where there is no hit
+ *   steps     int32 [B, Q] or NULL   the steps examined per (row, query)
+ *   counts    int32 [Q, 2] or NULL   += the rows that hit and the rows undecided, per query (integer atomics: one ballot and one add
+ *                                    per wave and figure)
+ *   A row of status != 0 gets zeros in hit, undecided and steps and 0xFF in map.  Every element of every given output is written
+ *   (counts is added to), nothing else is; two runs are bit-identical.
+ * One thread per row; MVAE_SUBSTRUCT_LDS_BYTES = 81920 B (80 KiB) of LDS per 64-row block, the rewrite's block with nothing added: the
+ *   map and the cursors (32 bytes per lane each) and the current query's table (400 B per block) live where the adjacency's scratch
+ *   arrays were.  A row's graph is built once and all Q queries run against it.
+ * Refused before anything is enqueued.  MVAE_ERR_UNSUPPORTED: V > 64.  MVAE_ERR_INVALID: everything the graph entries refuse; Q outside
+ *   1 .. 64; a NULL table, status, hit or undecided; map given with map_query outside [0, Q); max_steps outside 1 .. 2^20.
+ */
+#define MVAE_SUBSTRUCT_QATOMS 32
+#define MVAE_SUBSTRUCT_QUERIES 64
+#define MVAE_SUBSTRUCT_WORDS 100
+#define MVAE_SUBSTRUCT_MAX_STEPS 1048576
+#define MVAE_SUBSTRUCT_LDS_BYTES 81920
+#define MVAE_SMILES_QUERY_ATOMS 14
+int mvae_smiles_substruct_compile_host(int Q, int Tq, int V, const int64_t* xq, int64_t xq_ld, const int32_t* tok_info /* [V] */,
+                                       const int32_t* chem_info /* [V] */, uint32_t stereo_lo, uint32_t stereo_hi, int eos_id,
+                                       int32_t* table /* [Q, MVAE_SUBSTRUCT_WORDS] */, int32_t* qstatus /* [Q] */);
+int mvae_smiles_substruct_rows(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */,
+                               const int32_t* chem_info /* [V] */, int eos_id, int Q, const int32_t* table /* [Q, 100] */, int max_steps,
+                               int map_query, int32_t* status /* [B] */, int64_t* hit /* [B] */, int64_t* undecided /* [B] */,
+                               uint8_t* map /* [B, 32] or NULL */, int32_t* steps /* [B, Q] or NULL */, int32_t* counts /* [Q, 2] or NULL */,
+                               void* stream);
+int mvae_smiles_substruct_corpus(const uint8_t* tokens, const int64_t* offsets /* [N + 1] */, int64_t N, int V,
+                                 const int32_t* tok_info /* [V] */, const int32_t* chem_info /* [V] */, int Q,
+                                 const int32_t* table /* [Q, 100] */, int max_steps, int map_query, int32_t* status /* [N] */,
+                                 int64_t* hit /* [N] */, int64_t* undecided /* [N] */, uint8_t* map /* [N, 32] or NULL */,
+                                 int32_t* steps /* [N, Q] or NULL */, int32_t* counts /* [Q, 2] or NULL */, void* stream);
+int mvae_smiles_substruct_host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */,
+                               const int32_t* chem_info /* [V] */, int eos_id, int Q, const int32_t* table /* [Q, 100] */, int max_steps,
+                               int map_query, int32_t* status /* [B] */, int64_t* hit /* [B] */, int64_t* undecided /* [B] */,
+                               uint8_t* map /* [B, 32] or NULL */, int32_t* steps /* [B, Q] or NULL */, int32_t* counts /* [Q, 2] or NULL */);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Tanimoto similarity of fingerprints (an addition: the structure-aware counterpart of mvae_latent_knn and mvae_edit_knn).  Fingerprints
  * are dense rows of MVAE_FP_WORDS int64 words, 16-byte aligned (else MVAE_ERR_INVALID); any 1024-bit rows will do.
  * Similarity.  T(a, b) = c / (p_a + p_b - c), with p the popcounts and c the popcount of a AND b; T is 0 when the union is empty.  T is

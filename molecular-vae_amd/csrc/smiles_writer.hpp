@@ -1,7 +1,8 @@
 // The writer of SMILES token rows that smiles_rewrite.hip and smiles_canon.hip share: the walk's graph as an adjacency in CSR form
 // (rew::graph), and from it the depth-first search and the emission of the search tree in the language the syntax automaton accepts
 // (rew::write), templated on the one thing the two consumers differ in -- the order of the atoms.  include/mvae.h ("SMILES rewrite")
-// states the definition; "SMILES canon" replaces its (prio, atom number) by a canonical rank and nothing else.
+// states the definition; "SMILES canon" replaces its (prio, atom number) by a canonical rank and nothing else.  smiles_substruct.hip
+// takes the adjacency alone (rew::adjacency, he_order) and searches it instead of writing it.
 //
 // An order policy `Ord` has one member, bool before(int a, int b): atom a comes before atom b (a strict total order on 0 .. n - 1).
 // write() calls it while it picks the root and sorts the half-edges, and never once the emission has begun: a policy may therefore keep
@@ -67,24 +68,10 @@ struct Writer {
   }
 };
 
-// The walk, the stereo test and the adjacency, half-edges in string order.  Returns the status; *n_out = the atoms (>= 1 with status 0).
-template <class Words, class Clos, class Half, class Bytes, class Src>
-SMI_HD int graph(Words& W, Clos& C, Half& A, Bytes& S, Bytes& D, Bytes& P, const Src& src, int first, int end, bool end_is_eos, int V,
-                 const int32_t* tok_info, const int32_t* chem_info, const int32_t* emit, int eos_id, int* n_out) {
-  *n_out = 0;
-  fpr::Rec<Clos> rec(C);
-  smg::Row r;
-  smg::walk(W, src, first, end, end_is_eos, V, tok_info, chem_info, eos_id, &r, rec);
-  if (r.status != smg::OK) return r.status;
-  const smg::u64 stereo = (smg::u64)(uint32_t)emit[EM_STEREO] | (smg::u64)(uint32_t)emit[EM_STEREO + 1] << 32;
-  for (int t = first; t < end && t - first <= smg::CONTENT_MAX; ++t) {
-    const long tok = src.tok(t);
-    if (tok == eos_id) break;
-    if ((stereo >> (tok & 63)) & 1ull) return STEREO;
-  }
-  const int n = rec.n, nclos = rec.nclos < fpr::CLOSURES ? rec.nclos : fpr::CLOSURES;
-  if (n < 1) return smg::SYNTAX;       // cannot happen: the automaton takes no row without an atom
-
+// The adjacency of the n atoms the walk left in W and the nclos closures in C, half-edges in string order (smiles_substruct.hip calls
+// it behind a walk of its own: a row with a stereo token still has a graph to search).
+template <class Words, class Clos, class Half, class Bytes>
+SMI_HD void adjacency(Words& W, Clos& C, Half& A, Bytes& S, Bytes& D, Bytes& P, int n, int nclos) {
   // degrees into S, bond sums into P, then the exclusive prefix sum, then the half-edges with D as the fill cursor
   for (int k = 0; k <= n; ++k) { S.set(k, 0); P.set(k, 0); }
   for (int k = 1; k < n; ++k) {
@@ -123,6 +110,26 @@ SMI_HD int graph(Words& W, Clos& C, Half& A, Bytes& S, Bytes& D, Bytes& P, const
     A.set(ii, (uint8_t)j); D.set(i, (uint8_t)(ii + 1));
     A.set(ij, (uint8_t)i); D.set(j, (uint8_t)(ij + 1));
   }
+}
+
+// The walk, the stereo test and the adjacency.  Returns the status; *n_out = the atoms (>= 1 with status 0).
+template <class Words, class Clos, class Half, class Bytes, class Src>
+SMI_HD int graph(Words& W, Clos& C, Half& A, Bytes& S, Bytes& D, Bytes& P, const Src& src, int first, int end, bool end_is_eos, int V,
+                 const int32_t* tok_info, const int32_t* chem_info, const int32_t* emit, int eos_id, int* n_out) {
+  *n_out = 0;
+  fpr::Rec<Clos> rec(C);
+  smg::Row r;
+  smg::walk(W, src, first, end, end_is_eos, V, tok_info, chem_info, eos_id, &r, rec);
+  if (r.status != smg::OK) return r.status;
+  const smg::u64 stereo = (smg::u64)(uint32_t)emit[EM_STEREO] | (smg::u64)(uint32_t)emit[EM_STEREO + 1] << 32;
+  for (int t = first; t < end && t - first <= smg::CONTENT_MAX; ++t) {
+    const long tok = src.tok(t);
+    if (tok == eos_id) break;
+    if ((stereo >> (tok & 63)) & 1ull) return STEREO;
+  }
+  const int n = rec.n, nclos = rec.nclos < fpr::CLOSURES ? rec.nclos : fpr::CLOSURES;
+  if (n < 1) return smg::SYNTAX;       // cannot happen: the automaton takes no row without an atom
+  adjacency(W, C, A, S, D, P, n, nclos);
   *n_out = n;
   return smg::OK;
 }

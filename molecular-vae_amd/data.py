@@ -451,6 +451,39 @@ class MosesDeviceDataset:
         self.canonical()
         return self._canonical[2]
 
+    def _substructures(self, who, patterns, max_steps, counts=None):
+        from . import ops
+        tok, chem = self._fp_tables(who)
+        table = compile_substructures(patterns, self.vocab)
+        out = ops.smiles_substruct_corpus(self.tokens, self.offsets, self.n, tok, chem, table.on(self.device), max_steps, steps=False, counts=counts)
+        return table, out
+
+    def substructure_counts(self, patterns, max_steps=65536):
+        """How many corpus rows contain each pattern (``compile_substructures``: SMILES fragments or a ``SubstructureTable``), and on how
+        many the search ran out of its ``max_steps`` candidates and says neither: int32 [Q, 2] on the device, columns (hits,
+        undecided), from ONE ``mvae_smiles_substruct_corpus`` launch over the CSR rows -- each row's graph built once for all patterns,
+        the counts kept by the kernel's integer atomic adds; never waits for the device.  Rows the walk refuses contain nothing.  Graph
+        containment on (element, aromatic, charge) and bond classes (include/mvae.h, "SMILES substructure"): not SMARTS, not rdkit's
+        HasSubstructMatch.  ValueError for a refused pattern or a vocabulary of more than 64 ids."""
+        from .models import _require_cuda
+        _require_cuda(self.device, "MosesDeviceDataset.substructure_counts")
+        table = compile_substructures(patterns, self.vocab)
+        counts = torch.zeros(len(table), 2, dtype=torch.int32, device=self.device)
+        self._substructures("substructure_counts", table, max_steps, counts)
+        return counts
+
+    def rows_with_substructure(self, pattern, max_steps=65536, return_undecided=False):
+        """The corpus rows that contain one pattern: int64 row ids on the device, ascending (one ``mvae_smiles_substruct_corpus`` launch;
+        the host waits once, for their number).  ``return_undecided=True`` also returns the rows on which the search ran out of
+        ``max_steps``."""
+        from .models import _require_cuda
+        _require_cuda(self.device, "MosesDeviceDataset.rows_with_substructure")
+        if not isinstance(pattern, str):
+            raise ValueError("rows_with_substructure: one pattern, a string")
+        _, (_, hit, undecided, _, _) = self._substructures("rows_with_substructure", [pattern], max_steps)
+        rows = torch.nonzero(hit & 1).flatten()
+        return (rows, torch.nonzero(undecided & 1).flatten()) if return_undecided else rows
+
     def scaffold_histogram(self):
         """(keys int64 [n], counts int64 [n]) on the device: the distinct scaffold keys of the corpus rows whose status is 0, ascending,
         and how many rows have each (``ops.key_histogram``; rows without a ring have no scaffold and are not counted).  Cached."""
@@ -805,6 +838,60 @@ def canonical_smiles(strings, vocab, device="cuda", return_status=False):
     table = np.array([vocab.i2c[i] for i in range(len(vocab))], dtype=object)
     res = [s if st else "".join(table[row[1:k - 1]]) for s, row, k, st in zip(strings, out, out_len, status)]
     return (res, status) if return_status else res
+
+
+class SubstructureTable:
+    """Compiled substructure queries (``compile_substructures``): ``patterns`` (a tuple of strings), ``table`` (int32 [Q, 100], what the
+    mvae_smiles_substruct entries take) and ``qstatus`` (int32 [Q], all 0), both on the host; ``on(device)`` is the table there,
+    uploaded once per device."""
+
+    def __init__(self, patterns, table, qstatus):
+        self.patterns, self.table, self.qstatus = tuple(patterns), table, qstatus
+        self._on = {}
+
+    def __len__(self):
+        return len(self.patterns)
+
+    def on(self, device):
+        device = torch.device(device)
+        if device.type == "cpu":
+            return self.table
+        if device not in self._on:
+            self._on[device] = self.table.to(device)
+        return self._on[device]
+
+
+def compile_substructures(patterns, vocab):
+    """SMILES fragments compiled into a ``SubstructureTable`` for ``VAE.has_substructure``, ``MosesDeviceDataset.substructure_counts`` /
+    ``rows_with_substructure`` and ``moses_generate(filters=)`` (include/mvae.h, "SMILES substructure"): 1 to 64 patterns in the model's
+    vocabulary, each of at most 32 atoms, each a string the SMILES walk accepts -- or refuses only because an aromatic atom stands
+    outside a ring, so that ``cC(=O)O`` is a pattern.  They are matched as graphs on (element, aromatic, charge) and bond classes: NOT
+    SMARTS -- no wildcards, no recursive queries, no hydrogen counts -- and not rdkit's HasSubstructMatch.  Host only (one
+    mvae_smiles_substruct_compile_host call).  ValueError naming the pattern and the reason for one that is refused (a character outside
+    the vocabulary, ``ops.SUBSTRUCT_QSTATUS_NAMES``: syntax, valence, charge, ring_bond, too_long, stereo, query_atoms), for no patterns
+    or more than 64, and for a vocabulary of more than 64 ids.  A ``SubstructureTable`` is returned as it is."""
+    from . import ops
+    from .vocab import smiles_token_table, smiles_chem_table, smiles_emit_table
+    if isinstance(patterns, SubstructureTable):
+        return patterns
+    patterns = [patterns] if isinstance(patterns, str) else list(patterns)
+    if not 1 <= len(patterns) <= ops.SUBSTRUCT_QUERIES:
+        raise ValueError(f"compile_substructures: 1 to {ops.SUBSTRUCT_QUERIES} patterns, got {len(patterns)}")
+    if len(vocab) > 64:
+        raise ValueError(f"compile_substructures: the vocabulary has {len(vocab)} ids, at most 64 are supported")
+    for p in patterns:
+        missing = sorted({ch for ch in p if ch not in vocab.c2i})
+        if missing:
+            raise ValueError(f"compile_substructures: pattern {p!r}: {''.join(missing)!r} is not in the vocabulary")
+    ids = [vocab.string2ids(p, add_bos=True, add_eos=True) for p in patterns]
+    x = torch.full((len(ids), max(map(len, ids))), vocab.pad, dtype=torch.long)
+    for b, row in enumerate(ids):
+        x[b, :len(row)] = torch.as_tensor(row)
+    table, qstatus = ops.smiles_substruct_compile(x, smiles_token_table(vocab), smiles_chem_table(vocab), smiles_emit_table(vocab), vocab.eos)
+    for p, st in zip(patterns, qstatus.tolist()):
+        if st:
+            raise ValueError(f"compile_substructures: pattern {p!r} is refused: {ops.SUBSTRUCT_QSTATUS_NAMES[st]}")
+    return SubstructureTable(patterns, table, qstatus)
 
 
 def indices_to_smiles(idx, charset):

@@ -565,6 +565,34 @@ class VAE(_SavedState, nn.Module):
         extra["rank"] = rank
         return rows, status, extra
 
+    def _substructure_words(self, x, table, max_steps=65536, map_query=None):
+        """(status, hit, undecided[, map]) of one mvae_smiles_substruct_rows launch over token rows x on the device; table: a
+        ``data.SubstructureTable``."""
+        dev = self.device
+        status, hit, undecided, emb, _ = ops.smiles_substruct_rows(x, self._smiles_table(dev), self._smiles_chem_table(dev), self.eos, table.on(dev),
+                                                                   max_steps, map_query, steps=False)
+        return (status, hit, undecided) if map_query is None else (status, hit, undecided, emb)
+
+    @torch.no_grad()
+    def has_substructure(self, x, patterns, max_steps=65536, return_map=None):
+        """Which of the patterns (``data.compile_substructures``: 1 to 64 SMILES fragments, or a ``SubstructureTable`` to compile them
+        once) the token rows x (what ``syntax_valid`` takes) contain, on the device, one mvae_smiles_substruct_rows launch, no host
+        wait: (hit bool [B, Q], undecided bool [B, Q]).  hit[b, q]: the graph of row b contains pattern q -- an injective map of the
+        pattern's atoms that keeps element, aromatic flag and charge of every atom and the class of every bond (include/mvae.h, "SMILES
+        substructure"): graph containment, NOT SMARTS and not rdkit's HasSubstructMatch.  undecided[b, q]: the backtracking search
+        examined ``max_steps`` candidates (1 to 2^20) without an answer; such a pair is neither hit nor miss.  A row the SMILES walk
+        refuses contains nothing.  ``return_map=q`` also returns uint8 [B, 32]: the first (lexicographically smallest) embedding of
+        pattern q, atom numbers of the row in the pattern's atom order, 0xFF beyond its atoms and where there is no hit.  ValueError
+        for a refused pattern, a vocabulary of more than 64 ids, max_steps or return_map out of range."""
+        from .data import compile_substructures
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.has_substructure")
+        table = compile_substructures(patterns, self.vocabulary)
+        x = self._rows(x, "has_substructure", dev)
+        out = self._substructure_words(x, table, max_steps, return_map)
+        hit, undecided = ops.substruct_bits(out[1], len(table)), ops.substruct_bits(out[2], len(table))
+        return (hit, undecided) if return_map is None else (hit, undecided, out[3])
+
     @torch.no_grad()
     def descriptors(self, x):
         """The graph walk's figures for token rows x (what ``syntax_valid`` takes), a dict of device tensors -- one graph-walk launch, one matrix-vector product for the weight, no host wait:

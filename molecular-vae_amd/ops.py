@@ -1095,6 +1095,103 @@ def smiles_canon_corpus(tokens, offsets, N, rows, tok_info, chem_info, emit, max
     return tokens_out, offsets_out, status, info, rank
 
 
+SUBSTRUCT_QATOMS = 32                         # include/mvae.h: MVAE_SUBSTRUCT_QATOMS, the atoms of a query and the columns of `map`
+SUBSTRUCT_QUERIES = 64                        # MVAE_SUBSTRUCT_QUERIES, the queries of one launch: one bit of an int64 each
+SUBSTRUCT_WORDS = 100                         # MVAE_SUBSTRUCT_WORDS, the int32 words of one compiled query
+SUBSTRUCT_MAX_STEPS = 1 << 20                 # MVAE_SUBSTRUCT_MAX_STEPS, the largest step budget
+SUBSTRUCT_STEPS = 1 << 16                     # the budget the Python surface defaults to
+SMILES_STATUS_QUERY_ATOMS = 14                # MVAE_SMILES_QUERY_ATOMS: a query of more than 32 atoms (the compile entry alone)
+SUBSTRUCT_QSTATUS_NAMES = REWRITE_STATUS_NAMES + ("query_atoms",)
+
+
+def smiles_substruct_compile(xq, tok_info, chem_info, emit, eos_id, table=None, qstatus=None):
+    """Query rows xq (int64 [Q, Tq] on the HOST, bos first, Q <= 64) compiled into the table the substructure entries take: (table int32
+    [Q, 100], qstatus int32 [Q]) on the host (mvae_smiles_substruct_compile_host; include/mvae.h, "SMILES substructure").  qstatus 0: a
+    query; anything else (``SUBSTRUCT_QSTATUS_NAMES``): refused -- a walk status other than ok / aromatic, a stereo token, more than 32
+    atoms -- and its table is a query without atoms, which no row contains.  emit: vocab.smiles_emit_table, for its stereo mask."""
+    xq, ldx = _token_rows(xq, "xq")
+    assert xq.device.type == "cpu", xq.device
+    _graph_tables(tok_info, chem_info, xq.device)
+    assert emit.dtype == torch.int32 and emit.shape == (REWRITE_EMIT,) and emit.device == xq.device, (emit.dtype, emit.shape)
+    Q = xq.shape[0]
+    if Q > SUBSTRUCT_QUERIES:
+        raise ValueError(f"smiles_substruct_compile: at most {SUBSTRUCT_QUERIES} queries, got {Q}")
+    table, qstatus = _outputs(Q, xq.device, ((torch.int32, (SUBSTRUCT_WORDS,), False), (torch.int32, (), False)), (table, qstatus))
+    lo, hi = (int(emit[43 + k]) & 0xFFFFFFFF for k in range(2))
+    check(L.load().mvae_smiles_substruct_compile_host(Q, xq.shape[1], tok_info.numel(), ptr(xq), ldx, ptr(tok_info), ptr(chem_info), lo, hi,
+                                                      int(eos_id), ptr(table), ptr(qstatus)), "mvae_smiles_substruct_compile_host")
+    return table, qstatus
+
+
+def _substruct_out(Q):
+    return ((torch.int32, (), False), (torch.int64, (), False), (torch.int64, (), False), (torch.uint8, (SUBSTRUCT_QATOMS,), True),
+            (torch.int32, (Q,), True))
+
+
+def _substruct_entry(name, front, table, max_steps, map_query, counts, dev):
+    """The C entry `name` as _smiles_rows / _smiles_corpus call it: the query arguments go in behind its first `front` arguments and
+    counts behind its five per-row outputs."""
+    assert table.dtype == torch.int32 and table.dim() == 2 and table.shape[1] == SUBSTRUCT_WORDS and table.is_contiguous() and table.device == dev
+    Q = table.shape[0]
+    if not 1 <= Q <= SUBSTRUCT_QUERIES:
+        raise ValueError(f"smiles_substruct: 1 to {SUBSTRUCT_QUERIES} queries a launch, got {Q}")
+    if not 1 <= int(max_steps) <= SUBSTRUCT_MAX_STEPS:
+        raise ValueError(f"smiles_substruct: max_steps must be in [1, {SUBSTRUCT_MAX_STEPS}], got {max_steps}")
+    if map_query is not None and not 0 <= int(map_query) < Q:
+        raise ValueError(f"smiles_substruct: map_query must be in [0, {Q}), got {map_query}")
+    assert counts is None or (counts.dtype == torch.int32 and counts.shape == (Q, 2) and counts.is_contiguous() and counts.device == dev)
+    fn = getattr(L.load(), name)
+    query = (Q, ptr(table), int(max_steps), -1 if map_query is None else int(map_query))
+
+    # front: the arguments of the C entry before Q -- 8 for _rows / _host (B, T, V, x, x_ld, tok_info, chem_info, eos_id), 6 for _corpus
+    # (tokens, offsets, N, V, tok_info, chem_info); then come the five outputs of _substruct_out and, on the device, the stream
+    n_args = len(L.SIGNATURES[name][1])
+
+    def entry(*a):
+        assert len(a) + len(query) + 1 == n_args and len(a) - front in (5, 6), (name, len(a), n_args)
+        return fn(*a[:front], *query, *a[front:front + 5], ptr(counts), *a[front + 5:])
+    entry.__name__ = name
+    return entry, Q
+
+
+def smiles_substruct_rows(x, tok_info, chem_info, eos_id, table, max_steps=SUBSTRUCT_STEPS, map_query=None, status=None, hit=None,
+                          undecided=None, map=None, steps=None, counts=None):
+    """Which of the Q compiled queries `table` (int32 [Q, 100], ``smiles_substruct_compile``, on x's device) the token rows x (int64
+    [B, T], bos first) contain: (status int32 [B], hit int64 [B], undecided int64 [B], map uint8 [B, 32], steps int32 [B, Q]) -- bit q
+    of hit: the row's graph contains query q as a monomorphism on (element, aromatic, charge) and the bond classes (include/mvae.h,
+    "SMILES substructure"; NOT SMARTS, not rdkit's HasSubstructMatch); bit q of undecided: the backtracking search used up its
+    ``max_steps`` candidates on that (row, query) and says neither.  map: the first (lexicographically smallest) embedding for the one
+    query ``map_query``, 0xFF beyond its atoms and where there is no hit; None without a map_query.  ``steps=False``: not written.
+    counts (int32 [Q, 2], optional, zeroed by the caller) += the rows that hit / are undecided per query.  Rows of status != 0 hit
+    nothing.  One launch (mvae_smiles_substruct_rows), the row's graph built once for all queries."""
+    fn, Q = _substruct_entry("mvae_smiles_substruct_rows", 8, table, max_steps, map_query, counts, x.device)
+    given = (status, hit, undecided, False if map_query is None else map, steps)
+    return _smiles_rows(fn, _substruct_out(Q), x, tok_info, chem_info, eos_id, given)
+
+
+def smiles_substruct_host(x, tok_info, chem_info, eos_id, table, max_steps=SUBSTRUCT_STEPS, map_query=None, status=None, hit=None,
+                          undecided=None, map=None, steps=None, counts=None):
+    """smiles_substruct_rows on HOST tensors: the same source compiled for the CPU, a plain loop over the rows
+    (mvae_smiles_substruct_host) -- for tests and for machines without a device; not a fallback of the device entries."""
+    fn, Q = _substruct_entry("mvae_smiles_substruct_host", 8, table, max_steps, map_query, counts, x.device)
+    given = (status, hit, undecided, False if map_query is None else map, steps)
+    return _smiles_rows(fn, _substruct_out(Q), x, tok_info, chem_info, eos_id, given, host=True)
+
+
+def smiles_substruct_corpus(tokens, offsets, N, tok_info, chem_info, table, max_steps=SUBSTRUCT_STEPS, map_query=None, status=None, hit=None,
+                            undecided=None, map=None, steps=None, counts=None):
+    """smiles_substruct_rows over all N rows of the CSR corpus (tokens uint8, offsets int64 [N + 1]; rows without specials, the end of a
+    row acting as <eos>), one launch (mvae_smiles_substruct_corpus)."""
+    fn, Q = _substruct_entry("mvae_smiles_substruct_corpus", 6, table, max_steps, map_query, counts, tokens.device)
+    given = (status, hit, undecided, False if map_query is None else map, steps)
+    return _smiles_corpus(fn, _substruct_out(Q), tokens, offsets, N, tok_info, chem_info, given)
+
+
+def substruct_bits(words, Q):
+    """hit or undecided (int64 [B]) as bool [B, Q]: column q is bit q."""
+    return ((words.reshape(-1, 1) >> torch.arange(Q, dtype=torch.int64, device=words.device)) & 1).bool()
+
+
 def key_histogram(keys, weights=None):
     """The distinct non-zero keys of an int64 tensor, ascending (as signed integers), and how often each occurs -- or, with ``weights``
     (an integer tensor of the same shape), the sum of its weights: (keys int64 [n], counts int64 [n]) on the keys' device.  One

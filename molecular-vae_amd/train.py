@@ -801,7 +801,7 @@ def moses_reconstruction(model, batches, beam_width=1, max_len=100, syntax=False
 @torch.no_grad()
 def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top_k=None, top_p=None, seed=0, z=None, syntax=False,
                    count_valid=False, novel_against=None, prefix=None, nearest=False, valence=False,
-                   int_div=False, snn=False, scaffolds=False, kekule=False, canonical=False):
+                   int_div=False, snn=False, scaffolds=False, kekule=False, canonical=False, filters=None, filter_steps=65536):
     """The reference's generation pipeline (``hugesample.py``: sample in batches, hash the strings, count unique / total) with the hashing
     and the deduplication on the device: ``n_samples`` sequences from a ``mosesvae.VAE`` in batches of ``batch_size`` (the last one shorter),
     batch j with seed ``seed + j`` and ``temp`` / ``top_k`` / ``top_p`` as ``VAE.sample`` takes them.  ``z`` None draws each batch's latents
@@ -887,7 +887,17 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     collision.  With ``novel_against`` it further gains "canonical_corpus_row", aligned with "strings": the lowest row of
     ``novel_against.canonical()`` that equals the sample's canonical row, -1 for none (one exact ``lookup`` per batch; the corpus is
     canonicalised once, by one launch, and cached), and "novel_canonical", the distinct canonical rows of status 0 that equal no
-    corpus row's.  Without the flag the launches and the keys of the result are what they were."""
+    corpus row's.  Without the flag the launches and the keys of the result are what they were.
+    ``filters`` (SMILES fragments or a ``data.SubstructureTable``; ``data.compile_substructures``' ValueErrors, and one for ``filter_steps``
+    outside 1 .. 2^20, before any device work):
+    the MOSES "Filters" figure on this library's substructure search -- graph containment on (element, aromatic, charge) and bond
+    classes (include/mvae.h, "SMILES substructure").  NO list is shipped: MOSES' own filters (MCF, PAINS) are SMARTS, which this does
+    not read; the caller names the unwanted groups as plain fragments.  Each batch's rows go through one ``mvae_smiles_substruct_rows``
+    launch (every row's graph built once for all patterns, ``filter_steps`` candidates per (row, pattern)), no further host wait, and
+    the result gains ``filter_statistics``' three values over the valence-consistent samples, duplicates included (those "chem_valid"
+    counts): "filters", the share of them with no hit and no undecided bit (NaN for none); "filter_hits" and "filter_undecided", per
+    pattern, how many contain it and on how many the search ran out of steps.  Without ``filters`` the launches and the keys of the
+    result are what they were."""
     n_samples, batch_size, max_len = int(n_samples), int(batch_size), int(max_len)
     if n_samples < 1 or batch_size < 1 or max_len < 1:
         raise ValueError(f"moses_generate: n_samples, batch_size and max_len must be >= 1, got {n_samples}, {batch_size}, {max_len}")
@@ -930,6 +940,11 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
             raise ValueError(f"moses_generate: canonical=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
         if max_len > 129:
             raise ValueError(f"moses_generate: canonical=True supports max_len <= 129, got {max_len}")
+    if filters is not None:
+        from .data import compile_substructures
+        filters = compile_substructures(filters, model.vocabulary)
+        if int(filter_steps) != filter_steps or not 1 <= filter_steps <= ops.SUBSTRUCT_MAX_STEPS:
+            raise ValueError(f"moses_generate: filter_steps must be an integer in [1, {ops.SUBSTRUCT_MAX_STEPS}], got {filter_steps!r}")
     if forced is not None and syntax:
         model._check_prefix_syntax(forced, max_len, "moses_generate")      # every sample's prefix, once, before the first batch: rows are sample indices
     i64 = torch.long
@@ -957,6 +972,7 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     kek_codes = torch.arange(8, dtype=torch.int32, device=dev) if kekule else None
     canons = []                                                 # (canonical row [*, 129], status, corpus row or None) of each new sample, likewise
     canon_corpus = novel_against.canonical() if canonical and novel_against is not None else None       # one launch, cached by the dataset
+    filt = torch.zeros(2 + 2 * len(filters), dtype=i64, device=dev) if filters is not None else None      # _filter_counts, summed over the batches
     stage = [None, None]                                       # pinned staging rows [batch_size, max_len + 1] (ids, end), alternating
     pending = None
 
@@ -975,6 +991,8 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         match = novel_against.lookup(x) if novel_against is not None else None
         graph = model.descriptors(x) if valence else None
         kek = model.kekule(x, mate=False) if kekule else None
+        if filters is not None:
+            filt += _filter_counts(*model._substructure_words(x, filters, filter_steps), len(filters))
         hs, order = torch.sort(h, stable=True)                  # equal hashes: ascending row, so a run starts at its first occurrence
         first = torch.ones(n, dtype=torch.bool, device=dev)
         first[1:] = hs[1:] != hs[:-1]
@@ -1116,7 +1134,28 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         if novel_against is not None:
             res["canonical_corpus_row"] = torch.cat([c[2] for c in canons]).tolist() if canons else []
             res["novel_canonical"] = int((canon_corpus.lookup(distinct) < 0).sum()) if distinct.shape[0] else 0
+    if filters is not None:
+        res.update(_filter_result(filt.tolist(), len(filters)))
     return res
+
+
+def _filter_counts(status, hit, undecided, Q):
+    """int64 [2 + 2 Q] on the rows' device: the rows of status 0, those of them with no hit and no undecided bit, then per query the rows
+    that hit and the rows undecided (rows of another status have no bit set)."""
+    fine = status == 0
+    return torch.cat([fine.sum()[None], (fine & (hit == 0) & (undecided == 0)).sum()[None], ops.substruct_bits(hit, Q).sum(0),
+                      ops.substruct_bits(undecided, Q).sum(0)])
+
+
+def _filter_result(c, Q):
+    return {"filters": c[1] / c[0] if c[0] else float("nan"), "filter_hits": c[2:2 + Q], "filter_undecided": c[2 + Q:2 + 2 * Q]}
+
+
+def filter_statistics(status, hit, undecided, Q):
+    """What ``moses_generate(filters=)`` reports, from the outputs of a substructure launch over Q patterns (``ops.smiles_substruct_rows``):
+    {"filters": the share of the rows of status 0 that contain no pattern and are undecided on none (NaN without such rows),
+    "filter_hits": [Q] rows containing each pattern, "filter_undecided": [Q] rows on which its search ran out of steps}."""
+    return _filter_result(_filter_counts(status, hit, undecided, int(Q)).tolist(), int(Q))
 
 
 def active_units(mu, delta=0.01):
