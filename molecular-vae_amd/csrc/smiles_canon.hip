@@ -3,7 +3,9 @@
 // by a canonical rank -- a first invariant per atom, refined by the sorted (bond order, rank) of the neighbours until the number of
 // classes stops growing, ties broken one at a time by string order with a refinement after each.
 //
-// A sixth consumer of the walk of smiles_graph.hpp.  One thread per row, 64-thread blocks, and the rewrite's 80 KiB of LDS per block
+// A sixth consumer of the walk of smiles_graph.hpp, and the second family of the writer driver (smiles_writer.hpp), which owns the
+// kernels' bodies, the launches and the host loop: this file states the ranks as the family can::Canon and names its two kernels and
+// three entries.  One thread per row, 64-thread blocks, and the rewrite's 80 KiB of LDS per block
 // (rew::Lds) with nothing added: between the adjacency and the search three of its byte arrays are idle, and the ranks live there --
 //   R  rank of atom a            the output row's storage (the closure list's before it; both are dead in between)
 //   Q  atom at position p        the search index's storage: the atoms sorted by rank, so that a class is a run of Q
@@ -161,30 +163,43 @@ SMI_HD void ranks(Words& W, Half& A, Bytes& S, Ranks& R, Bytes& Q, Bytes& N, int
   info[0] = n; info[1] = after_first; info[2] = rounds; info[3] = ties;
 }
 
-// One row: the graph, the ranks, the search, the emission.  Returns the status; *len as rew::write gives it.  info (4 ints) and rank (128
-// bytes) may be NULL; each is written in full: zeros / 0xFF for a row that is refused before its ranks are computed.
-template <class Words, class Clos, class Out, class Half, class Bytes, class Src>
-SMI_HD int row(Words& W, Clos& C, Out& O, Half& A, Bytes& S, Bytes& D, Bytes& P, const Src& src, int first, int end, bool end_is_eos, int V,
-               const int32_t* tok_info, const int32_t* chem_info, const int32_t* emit, int eos_id, int max_content, int* len, int32_t* info,
-               uint8_t* rank) {
-  *len = rew::COPY;
-  int n, got[4] = {0, 0, 0, 0};
-  const int st = rew::graph(W, C, A, S, D, P, src, first, end, end_is_eos, V, tok_info, chem_info, emit, eos_id, &n);
-  if (st == smg::OK) ranks(W, A, S, O, D, P, n, got);
-  else n = 0;
-  if (info) { info[0] = got[0]; info[1] = got[1]; info[2] = got[2]; info[3] = got[3]; }
-  if (rank)
-    for (int k = 0; k < rew::SLOTS; ++k) rank[k] = k < n ? O.get(k) : (uint8_t)0xFF;
-  if (st != smg::OK) return st;
-  return rew::write(RankOrder<Out>{O}, W, O, A, S, D, P, n, emit, max_content, len);
-}
+// The family the writer driver (smiles_writer.hpp) runs.  info [B, 4] and rank [B, 128] may be NULL; each is written in full.
+struct Canon {
+  struct Args {
+    int32_t* info;
+    uint8_t* rank;
+    SMI_HD int32_t* info_of(long b) const { return info ? info + 4 * b : nullptr; }
+    SMI_HD uint8_t* rank_of(long b) const { return rank ? rank + rew::SLOTS * b : nullptr; }
+  };
 
-// info and rank of a row that is not read at all
-SMI_HD void blank(int32_t* info, uint8_t* rank) {
-  if (info) { info[0] = 0; info[1] = 0; info[2] = 0; info[3] = 0; }
-  if (rank)
-    for (int k = 0; k < rew::SLOTS; ++k) rank[k] = (uint8_t)0xFF;
-}
+  // One row: the graph, the ranks, the search, the emission.  Returns the status; *len as rew::write gives it.  info and rank of a row
+  // that is refused before its ranks are computed are zeros / 0xFF.
+  template <class S, class Src>
+  static SMI_HD int row(S& s, const Src& src, int first, int end, bool end_is_eos, int V, const int32_t* tok_info, const int32_t* chem_info,
+                        const int32_t* emit, int eos_id, int max_content, long b, const Args& a, int* len) {
+    *len = rew::COPY;
+    int32_t* info = a.info_of(b);
+    uint8_t* rank = a.rank_of(b);
+    int n, got[4] = {0, 0, 0, 0};
+    const int st = rew::graph(s.W, s.C, s.A, s.S, s.D, s.P, src, first, end, end_is_eos, V, tok_info, chem_info, emit, eos_id, &n);
+    if (st == smg::OK) ranks(s.W, s.A, s.S, s.O, s.D, s.P, n, got);
+    else n = 0;
+    if (info) { info[0] = got[0]; info[1] = got[1]; info[2] = got[2]; info[3] = got[3]; }
+    if (rank)
+      for (int k = 0; k < rew::SLOTS; ++k) rank[k] = k < n ? s.O.get(k) : (uint8_t)0xFF;
+    if (st != smg::OK) return st;
+    return rew::write(RankOrder<decltype(s.O)>{s.O}, s.W, s.O, s.A, s.S, s.D, s.P, n, emit, max_content, len);
+  }
+
+  // info and rank of a row that is not read at all
+  static SMI_HD void skipped(long b, const Args& a) {
+    int32_t* info = a.info_of(b);
+    uint8_t* rank = a.rank_of(b);
+    if (info) { info[0] = 0; info[1] = 0; info[2] = 0; info[3] = 0; }
+    if (rank)
+      for (int k = 0; k < rew::SLOTS; ++k) rank[k] = (uint8_t)0xFF;
+  }
+};
 
 }  // namespace can
 
@@ -201,23 +216,8 @@ __global__ __launch_bounds__(64) void smiles_canon_rows_kernel(int B, int T, int
                                                                int32_t* __restrict__ counts, int32_t* __restrict__ info,
                                                                uint8_t* __restrict__ rank) {
   __shared__ rew::Lds lds;
-  const int lane = threadIdx.x, b0 = blockIdx.x * 64, b = b0 + lane;
-  int len = rew::COPY, keep = 0;
-  if (b < B) {
-    rew::LdsWords W{lds.words + lane};
-    rew::LdsClos C{lds.clos + lane};
-    rew::LdsBytes O{lds.out + lane}, S{lds.start + lane}, D{lds.dfs + lane}, P{lds.parent + lane};
-    rew::LdsHalf A{lds.half + lane};
-    const fpr::PaddedSrc src{x + (long)b * x_ld};
-    const int st = can::row(W, C, O, A, S, D, P, src, 1, T, false, V, tok_info, chem_info, emit, eos_id, max_content, &len,
-                            info ? info + 4 * (long)b : nullptr, rank ? rank + rew::SLOTS * (long)b : nullptr);
-    if (len == rew::COPY) keep = rew::copy_len(src, T, eos_id);
-    status[b] = st;
-    out_len[b] = len == rew::COPY ? keep : len + 2;
-    if (counts) atomicAdd(counts + (st & 15), 1);
-  }
-  __syncthreads();
-  rew::store_rows(lds, B, b0, lane, len, keep, x, x_ld, bos_id, eos_id, pad_id, T_out, out);
+  rew::block_rows<can::Canon>(lds, B, T, V, x, x_ld, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content, T_out, out, out_len, status,
+                              counts, info, rank);
 }
 
 __global__ __launch_bounds__(64) void smiles_canon_corpus_kernel(const uint8_t* __restrict__ tokens, const int64_t* __restrict__ offsets, long N,
@@ -229,34 +229,8 @@ __global__ __launch_bounds__(64) void smiles_canon_corpus_kernel(const uint8_t* 
                                                                  int32_t* __restrict__ err, int32_t* __restrict__ info,
                                                                  uint8_t* __restrict__ rank) {
   __shared__ rew::Lds lds;
-  const int lane = threadIdx.x, b0 = blockIdx.x * 64, b = b0 + lane;
-  int len = rew::COPY, keep = 0;
-  long lo = 0;
-  if (b < B) {
-    const long id = rows[b];
-    int32_t* info_b = info ? info + 4 * (long)b : nullptr;
-    uint8_t* rank_b = rank ? rank + rew::SLOTS * (long)b : nullptr;
-    int st = smg::SYNTAX;
-    if (id >= 0 && id < N) {
-      const long have = fpr::csr_len(offsets, id, &lo);
-      rew::LdsWords W{lds.words + lane};
-      rew::LdsClos C{lds.clos + lane};
-      rew::LdsBytes O{lds.out + lane}, S{lds.start + lane}, D{lds.dfs + lane}, P{lds.parent + lane};
-      rew::LdsHalf A{lds.half + lane};
-      st = can::row(W, C, O, A, S, D, P, fpr::CsrSrc{tokens + lo}, 0, fpr::csr_end(have), true, V, tok_info, chem_info, emit, -1, max_content,
-                    &len, info_b, rank_b);
-      if (len == rew::COPY) {
-        keep = (int)(have < stride ? have : stride);
-        if (have > stride && err) atomicMax(err, 1);
-      }
-    } else {
-      can::blank(info_b, rank_b);
-      if (err) atomicMax(err, 2);
-    }
-    rew::store_corpus_row(b, B, stride, len, keep, st, offsets_out, status, counts);
-  }
-  __syncthreads();
-  rew::store_corpus(lds, B, b0, lane, len, keep, lo, tokens, stride, tokens_out);
+  rew::block_corpus<can::Canon>(lds, tokens, offsets, N, rows, B, V, tok_info, chem_info, emit, max_content, stride, tokens_out, offsets_out,
+                                status, counts, err, info, rank);
 }
 
 }  // namespace
@@ -266,46 +240,23 @@ extern "C" {
 int mvae_smiles_canon_rows(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info,
                            const int32_t* emit, int bos_id, int eos_id, int pad_id, int max_content, int T_out, int64_t* out, int32_t* out_len,
                            int32_t* status, int32_t* counts, int32_t* info, uint8_t* rank, void* stream) {
-  if (V > 64) return MVAE_ERR_UNSUPPORTED;
-  if (!rew::rows_args_ok(B, T, V, x, x_ld, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content, T_out, out, out_len, status))
-    return MVAE_ERR_INVALID;
-  hipLaunchKernelGGL(smiles_canon_rows_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, T, V, x, (long)x_ld, tok_info,
-                     chem_info, emit, bos_id, eos_id, pad_id, max_content, T_out, out, out_len, status, counts, info, rank);
-  MVAE_CHECK_HIP(hipGetLastError());
-  return MVAE_OK;
+  return rew::rows(smiles_canon_rows_kernel, B, T, V, x, x_ld, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content, T_out, out, out_len,
+                   status, counts, stream, info, rank);
 }
 
 int mvae_smiles_canon_corpus(const uint8_t* tokens, const int64_t* offsets, int64_t N, const int64_t* rows, int B, int V,
                              const int32_t* tok_info, const int32_t* chem_info, const int32_t* emit, int max_content, int stride,
                              uint8_t* tokens_out, int64_t* offsets_out, int32_t* status, int32_t* counts, int32_t* err, int32_t* info,
                              uint8_t* rank, void* stream) {
-  if (V > 64) return MVAE_ERR_UNSUPPORTED;
-  if (!rew::corpus_args_ok(tokens, offsets, N, rows, B, V, tok_info, chem_info, emit, max_content, stride, tokens_out, offsets_out, status))
-    return MVAE_ERR_INVALID;
-  hipLaunchKernelGGL(smiles_canon_corpus_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, tokens, offsets, (long)N, rows, B, V,
-                     tok_info, chem_info, emit, max_content, stride, tokens_out, offsets_out, status, counts, err, info, rank);
-  MVAE_CHECK_HIP(hipGetLastError());
-  return MVAE_OK;
+  return rew::corpus(smiles_canon_corpus_kernel, tokens, offsets, N, rows, B, V, tok_info, chem_info, emit, max_content, stride, tokens_out,
+                     offsets_out, status, counts, err, stream, info, rank);
 }
 
 int mvae_smiles_canon_host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info,
                            const int32_t* emit, int bos_id, int eos_id, int pad_id, int max_content, int T_out, int64_t* out, int32_t* out_len,
                            int32_t* status, int32_t* info, uint8_t* rank) {
-  if (V > 64) return MVAE_ERR_UNSUPPORTED;
-  if (!rew::rows_args_ok(B, T, V, x, x_ld, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content, T_out, out, out_len, status))
-    return MVAE_ERR_INVALID;
-  fpr::HostArr<uint32_t, smg::ATOM_SLOTS> W;
-  fpr::HostArr<uint16_t, fpr::CLOSURES> C;
-  fpr::HostArr<uint8_t, smg::ATOM_SLOTS> O, S, D, P;
-  fpr::HostArr<uint8_t, rew::HALF> A;
-  for (long b = 0; b < B; ++b) {
-    const fpr::PaddedSrc src{x + b * x_ld};
-    int len = rew::COPY;
-    status[b] = can::row(W, C, O, A, S, D, P, src, 1, T, false, V, tok_info, chem_info, emit, eos_id, max_content, &len,
-                         info ? info + 4 * b : nullptr, rank ? rank + rew::SLOTS * b : nullptr);
-    rew::host_store_row(O, src, T, len, bos_id, eos_id, pad_id, T_out, out + b * T_out, out_len + b);
-  }
-  return MVAE_OK;
+  return rew::host<can::Canon>(B, T, V, x, x_ld, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content, T_out, out, out_len, status, info,
+                               rank);
 }
 
 }  // extern "C"

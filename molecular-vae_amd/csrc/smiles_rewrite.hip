@@ -3,9 +3,10 @@
 // with multiple bonds first, and the emission of the search tree in pre-order in the language the syntax automaton accepts.
 //
 // A fifth consumer of the walk of smiles_graph.hpp, with the fingerprint's recorder (smiles_rounds.hpp), and the first that writes a
-// string.  The graph, the search and the emission are smiles_writer.hpp's, shared with smiles_canon.hip; this file states the order of
-// the atoms -- (prio, atom number) -- and the kernels.  One thread per row, 64-thread blocks; everything indexed by a run-time atom
-// number lives in LDS, lane-minor, never in a private array:
+// string.  The graph, the search, the emission, the arrays (rew::Store) and the writer driver -- the kernels' bodies, the launches and
+// the host loop -- are smiles_writer.hpp's, shared with smiles_canon.hip; this file states the order of the atoms, (prio, atom number),
+// as the family rew::Respell, and names its two kernels and three entries.  One thread per row, 64-thread blocks; everything indexed by
+// a run-time atom number lives in LDS, lane-minor, never in a private array:
 //   words                128 slots x 64 lanes x 4 B = 32 KiB   the walk's atom words; bits 8-15 and 26-31 are rewritten once the graph is read
 //   closure pairs         64 x 64 x 2 B             =  8 KiB   the walk's list; once the adjacency is built, the SAME storage holds the
 //                                                              output row (128 bytes per lane)
@@ -29,94 +30,60 @@ struct HashOrder {
   }
 };
 
-// One row: the walk, the adjacency, the search, the emission.  Returns the status; *len = the content tokens staged in O, COPY for a
-// row that is to be copied through.  O may share C's storage: C is not read once the adjacency is built.
-template <class Words, class Clos, class Out, class Half, class Bytes, class Src>
-SMI_HD int row(Words& W, Clos& C, Out& O, Half& A, Bytes& S, Bytes& D, Bytes& P, const Src& src, int first, int end, bool end_is_eos, int V,
-               const int32_t* tok_info, const int32_t* chem_info, const int32_t* emit, int eos_id, uint32_t base, int max_content, int* len) {
-  *len = COPY;
-  int n;
-  const int st = graph(W, C, A, S, D, P, src, first, end, end_is_eos, V, tok_info, chem_info, emit, eos_id, &n);
-  if (st != smg::OK) return st;
-  return write(HashOrder{base}, W, O, A, S, D, P, n, emit, max_content, len);
-}
-
 // mix(seed * 0x9E3779B1 + draw_b): what prio() of row b starts from
 SMI_HD uint32_t draw_base(uint32_t seed, const uint32_t* draw, long b) {
   return fpr::mix(seed * 0x9E3779B1u + (draw ? draw[b] : (uint32_t)b));
 }
 
+// The family the writer driver (smiles_writer.hpp) runs
+struct Respell {
+  struct Args {
+    uint32_t seed;
+    const uint32_t* draw;  // optional
+  };
+
+  // One row: the walk, the adjacency, the search, the emission.  Returns the status; *len = the content tokens staged in s.O, COPY for a
+  // row that is to be copied through.
+  template <class S, class Src>
+  static SMI_HD int row(S& s, const Src& src, int first, int end, bool end_is_eos, int V, const int32_t* tok_info, const int32_t* chem_info,
+                        const int32_t* emit, int eos_id, int max_content, long b, const Args& a, int* len) {
+    *len = COPY;
+    const uint32_t base = draw_base(a.seed, a.draw, b);
+    int n;
+    const int st = graph(s.W, s.C, s.A, s.S, s.D, s.P, src, first, end, end_is_eos, V, tok_info, chem_info, emit, eos_id, &n);
+    if (st != smg::OK) return st;
+    return write(HashOrder{base}, s.W, s.O, s.A, s.S, s.D, s.P, n, emit, max_content, len);
+  }
+  static SMI_HD void skipped(long, const Args&) {}
+};
+
 }  // namespace rew
 
 namespace {
 
-using rew::LdsBytes;
-using rew::LdsClos;
-using rew::LdsHalf;
-using rew::LdsWords;
-typedef rew::Lds RewLds;
-static_assert(sizeof(RewLds) == MVAE_REWRITE_LDS_BYTES, "include/mvae.h states the LDS per block");
+static_assert(sizeof(rew::Lds) == MVAE_REWRITE_LDS_BYTES, "include/mvae.h states the LDS per block");
 
 __global__ __launch_bounds__(64) void smiles_rewrite_rows_kernel(int B, int T, int V, const int64_t* __restrict__ x, long x_ld,
                                                                  const int32_t* __restrict__ tok_info, const int32_t* __restrict__ chem_info,
                                                                  const int32_t* __restrict__ emit, int bos_id, int eos_id, int pad_id,
-                                                                 uint32_t seed, const uint32_t* __restrict__ draw, int max_content, int T_out,
-                                                                 int64_t* __restrict__ out, int32_t* __restrict__ out_len,
-                                                                 int32_t* __restrict__ status, int32_t* __restrict__ counts) {
-  __shared__ RewLds lds;
-  const int lane = threadIdx.x, b0 = blockIdx.x * 64, b = b0 + lane;
-  int len = rew::COPY, keep = 0;
-  if (b < B) {
-    LdsWords W{lds.words + lane};
-    LdsClos C{lds.clos + lane};
-    LdsBytes O{lds.out + lane}, S{lds.start + lane}, D{lds.dfs + lane}, P{lds.parent + lane};
-    LdsHalf A{lds.half + lane};
-    const fpr::PaddedSrc src{x + (long)b * x_ld};
-    const int st = rew::row(W, C, O, A, S, D, P, src, 1, T, false, V, tok_info, chem_info, emit, eos_id, rew::draw_base(seed, draw, b),
-                            max_content, &len);
-    if (len == rew::COPY) keep = rew::copy_len(src, T, eos_id);
-    status[b] = st;
-    out_len[b] = len == rew::COPY ? keep : len + 2;
-    if (counts) atomicAdd(counts + (st & 15), 1);
-  }
-  __syncthreads();
-  rew::store_rows(lds, B, b0, lane, len, keep, x, x_ld, bos_id, eos_id, pad_id, T_out, out);
+                                                                 int max_content, int T_out, int64_t* __restrict__ out,
+                                                                 int32_t* __restrict__ out_len, int32_t* __restrict__ status,
+                                                                 int32_t* __restrict__ counts, uint32_t seed, const uint32_t* __restrict__ draw) {
+  __shared__ rew::Lds lds;
+  rew::block_rows<rew::Respell>(lds, B, T, V, x, x_ld, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content, T_out, out, out_len, status,
+                                counts, seed, draw);
 }
 
 __global__ __launch_bounds__(64) void smiles_rewrite_corpus_kernel(const uint8_t* __restrict__ tokens, const int64_t* __restrict__ offsets, long N,
                                                                    const int64_t* __restrict__ rows, int B, int V,
                                                                    const int32_t* __restrict__ tok_info, const int32_t* __restrict__ chem_info,
-                                                                   const int32_t* __restrict__ emit, uint32_t seed,
-                                                                   const uint32_t* __restrict__ draw, int max_content, int stride,
+                                                                   const int32_t* __restrict__ emit, int max_content, int stride,
                                                                    uint8_t* __restrict__ tokens_out, int64_t* __restrict__ offsets_out,
                                                                    int32_t* __restrict__ status, int32_t* __restrict__ counts,
-                                                                   int32_t* __restrict__ err) {
-  __shared__ RewLds lds;
-  const int lane = threadIdx.x, b0 = blockIdx.x * 64, b = b0 + lane;
-  int len = rew::COPY, keep = 0;
-  long lo = 0;
-  if (b < B) {
-    const long id = rows[b];
-    int st = smg::SYNTAX;
-    if (id >= 0 && id < N) {
-      const long have = fpr::csr_len(offsets, id, &lo);
-      LdsWords W{lds.words + lane};
-      LdsClos C{lds.clos + lane};
-      LdsBytes O{lds.out + lane}, S{lds.start + lane}, D{lds.dfs + lane}, P{lds.parent + lane};
-      LdsHalf A{lds.half + lane};
-      st = rew::row(W, C, O, A, S, D, P, fpr::CsrSrc{tokens + lo}, 0, fpr::csr_end(have), true, V, tok_info, chem_info, emit, -1,
-                    rew::draw_base(seed, draw, b), max_content, &len);
-      if (len == rew::COPY) {
-        keep = (int)(have < stride ? have : stride);
-        if (have > stride && err) atomicMax(err, 1);
-      }
-    } else if (err) {
-      atomicMax(err, 2);
-    }
-    rew::store_corpus_row(b, B, stride, len, keep, st, offsets_out, status, counts);
-  }
-  __syncthreads();
-  rew::store_corpus(lds, B, b0, lane, len, keep, lo, tokens, stride, tokens_out);
+                                                                   int32_t* __restrict__ err, uint32_t seed, const uint32_t* __restrict__ draw) {
+  __shared__ rew::Lds lds;
+  rew::block_corpus<rew::Respell>(lds, tokens, offsets, N, rows, B, V, tok_info, chem_info, emit, max_content, stride, tokens_out, offsets_out,
+                                  status, counts, err, seed, draw);
 }
 
 }  // namespace
@@ -126,46 +93,23 @@ extern "C" {
 int mvae_smiles_rewrite_rows(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info,
                              const int32_t* emit, int bos_id, int eos_id, int pad_id, uint32_t seed, const uint32_t* draw, int max_content,
                              int T_out, int64_t* out, int32_t* out_len, int32_t* status, int32_t* counts, void* stream) {
-  if (V > 64) return MVAE_ERR_UNSUPPORTED;
-  if (!rew::rows_args_ok(B, T, V, x, x_ld, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content, T_out, out, out_len, status))
-    return MVAE_ERR_INVALID;
-  hipLaunchKernelGGL(smiles_rewrite_rows_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, T, V, x, (long)x_ld, tok_info,
-                     chem_info, emit, bos_id, eos_id, pad_id, seed, draw, max_content, T_out, out, out_len, status, counts);
-  MVAE_CHECK_HIP(hipGetLastError());
-  return MVAE_OK;
+  return rew::rows(smiles_rewrite_rows_kernel, B, T, V, x, x_ld, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content, T_out, out,
+                   out_len, status, counts, stream, seed, draw);
 }
 
 int mvae_smiles_rewrite_corpus(const uint8_t* tokens, const int64_t* offsets, int64_t N, const int64_t* rows, int B, int V,
                                const int32_t* tok_info, const int32_t* chem_info, const int32_t* emit, uint32_t seed, const uint32_t* draw,
                                int max_content, int stride, uint8_t* tokens_out, int64_t* offsets_out, int32_t* status, int32_t* counts,
                                int32_t* err, void* stream) {
-  if (V > 64) return MVAE_ERR_UNSUPPORTED;
-  if (!rew::corpus_args_ok(tokens, offsets, N, rows, B, V, tok_info, chem_info, emit, max_content, stride, tokens_out, offsets_out, status))
-    return MVAE_ERR_INVALID;
-  hipLaunchKernelGGL(smiles_rewrite_corpus_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, tokens, offsets, (long)N, rows, B, V,
-                     tok_info, chem_info, emit, seed, draw, max_content, stride, tokens_out, offsets_out, status, counts, err);
-  MVAE_CHECK_HIP(hipGetLastError());
-  return MVAE_OK;
+  return rew::corpus(smiles_rewrite_corpus_kernel, tokens, offsets, N, rows, B, V, tok_info, chem_info, emit, max_content, stride, tokens_out,
+                     offsets_out, status, counts, err, stream, seed, draw);
 }
 
 int mvae_smiles_rewrite_host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info,
                              const int32_t* emit, int bos_id, int eos_id, int pad_id, uint32_t seed, const uint32_t* draw, int max_content,
                              int T_out, int64_t* out, int32_t* out_len, int32_t* status) {
-  if (V > 64) return MVAE_ERR_UNSUPPORTED;
-  if (!rew::rows_args_ok(B, T, V, x, x_ld, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content, T_out, out, out_len, status))
-    return MVAE_ERR_INVALID;
-  fpr::HostArr<uint32_t, smg::ATOM_SLOTS> W;
-  fpr::HostArr<uint16_t, fpr::CLOSURES> C;
-  fpr::HostArr<uint8_t, smg::ATOM_SLOTS> O, S, D, P;
-  fpr::HostArr<uint8_t, rew::HALF> A;
-  for (long b = 0; b < B; ++b) {
-    const fpr::PaddedSrc src{x + b * x_ld};
-    int len = rew::COPY;
-    status[b] = rew::row(W, C, O, A, S, D, P, src, 1, T, false, V, tok_info, chem_info, emit, eos_id, rew::draw_base(seed, draw, b), max_content,
-                         &len);
-    rew::host_store_row(O, src, T, len, bos_id, eos_id, pad_id, T_out, out + b * T_out, out_len + b);
-  }
-  return MVAE_OK;
+  return rew::host<rew::Respell>(B, T, V, x, x_ld, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content, T_out, out, out_len, status,
+                                 seed, draw);
 }
 
 }  // extern "C"

@@ -191,11 +191,11 @@ template <class Src>
 inline int compile(const Src& src, int first, int end, int V, const int32_t* tok_info, const int32_t* chem_info, u64 stereo, int eos_id,
                    int32_t* t) {
   for (int i = 0; i < WORDS; ++i) t[i] = 0;
-  fpr::HostArr<uint32_t, smg::ATOM_SLOTS> W;
-  fpr::HostArr<uint16_t, fpr::CLOSURES> C;
-  fpr::HostArr<uint8_t, smg::ATOM_SLOTS> S, D, P;
-  fpr::HostArr<uint8_t, rew::HALF> A;
-  CountRec<decltype(C)> rec(C);
+  rew::Host g;                         // the output row is not used
+  auto& W = g.W;
+  auto& A = g.A;
+  auto& S = g.S;
+  CountRec<decltype(g.C)> rec(g.C);
   smg::Row r;
   smg::walk(W, src, first, end, false, V, tok_info, chem_info, eos_id, &r, rec);
   if (r.status != smg::OK && r.status != smg::AROMATIC) return r.status;
@@ -207,7 +207,7 @@ inline int compile(const Src& src, int first, int end, int V, const int32_t* tok
   const int n = rec.n;
   if (n < 1) return smg::SYNTAX;       // cannot happen: the automaton takes no row without an atom
   if (n > QATOMS) return Q_ATOMS;
-  rew::adjacency(W, C, A, S, D, P, n, rec.nclos < fpr::CLOSURES ? rec.nclos : fpr::CLOSURES);
+  rew::adjacency(W, g.C, A, S, g.D, g.P, n, rec.nclos < fpr::CLOSURES ? rec.nclos : fpr::CLOSURES);
   sort_half_edges(A, S, n);
   u64 lo = 0, hi = 0;
   for (int i = 0; i < n; ++i) {
@@ -244,25 +244,24 @@ inline int compile(const Src& src, int first, int end, int V, const int32_t* tok
 namespace {
 
 // the storage of one 64-row block: rew::Lds with the closure list kept apart (no output row), the map and the cursors in the search
-// index's place and the staged table in the search parent's, both of which the adjacency is done with when the first query starts
+// index's place and the staged table in the search parent's, both of which the adjacency is done with when the first query starts.
+// The writer's arrays are rew::Store's own members.
 struct Lds {
-  uint32_t words[smg::ATOM_SLOTS * 64];
-  uint16_t clos[fpr::CLOSURES * 64];
-  uint8_t half[rew::HALF * 64];
-  uint8_t start[smg::ATOM_SLOTS * 64];
+  decltype(rew::Lds::W) W;
+  decltype(rew::Lds::C) C;
+  decltype(rew::Lds::A) A;
+  decltype(rew::Lds::S) S;
   union {
-    uint8_t dfs[smg::ATOM_SLOTS * 64];
-    uint8_t small[2][sub::QATOMS * 64];            // [0] the map, [1] the cursors
+    decltype(rew::Lds::D) D;
+    fpr::LdsMem<uint8_t, sub::QATOMS> small[2];    // [0] the map, [1] the cursors
   };
   union {
-    uint8_t parent[smg::ATOM_SLOTS * 64];
+    decltype(rew::Lds::P) P;
     int32_t table[sub::WORDS];
   };
 };
 static_assert(sizeof(Lds) == MVAE_SUBSTRUCT_LDS_BYTES, "include/mvae.h states the LDS per block");
 static_assert(MVAE_SUBSTRUCT_LDS_BYTES <= 80 * 1024, "two blocks per CU");
-
-typedef fpr::LdsArr<uint8_t, sub::QATOMS> LdsSmall;
 
 struct LdsTab {
   const int32_t* w;
@@ -279,11 +278,11 @@ __device__ __forceinline__ void block_rows(Lds& lds, bool have, long b, const Sr
                                            int64_t* __restrict__ hit, int64_t* __restrict__ undecided, uint8_t* __restrict__ map,
                                            int32_t* __restrict__ steps, int32_t* __restrict__ counts) {
   const int lane = threadIdx.x;
-  rew::LdsWords W{lds.words + lane};
-  rew::LdsClos C{lds.clos + lane};
-  rew::LdsBytes S{lds.start + lane}, D{lds.dfs + lane}, P{lds.parent + lane};
-  rew::LdsHalf A{lds.half + lane};
-  LdsSmall M{lds.small[0] + lane}, Cu{lds.small[1] + lane};
+  auto W = lds.W.lane();
+  auto C = lds.C.lane();
+  auto A = lds.A.lane();
+  auto S = lds.S.lane(), D = lds.D.lane(), P = lds.P.lane();
+  auto M = lds.small[0].lane(), Cu = lds.small[1].lane();
   int st = smg::SYNTAX, n = 0;
   sub::u64 lo = 0, hi = 0;
   if (have) st = sub::build(W, C, A, S, D, P, src, first, end, end_is_eos, V, tok_info, chem_info, eos_id, &n, &lo, &hi);
@@ -390,15 +389,15 @@ int mvae_smiles_substruct_host(int B, int T, int V, const int64_t* x, int64_t x_
   if (!fpr::padded_rows_ok(B, T, V, x, x_ld, tok_info, chem_info, eos_id) ||
       !sub::args_ok(V, tok_info, chem_info, Q, table, max_steps, map_query, status, hit, undecided, map))
     return MVAE_ERR_INVALID;
-  fpr::HostArr<uint32_t, smg::ATOM_SLOTS> W;
-  fpr::HostArr<uint16_t, fpr::CLOSURES> C;
-  fpr::HostArr<uint8_t, smg::ATOM_SLOTS> S, D, P;
-  fpr::HostArr<uint8_t, rew::HALF> A;
+  rew::Host g;                         // the output row is not used
+  auto& W = g.W;
+  auto& A = g.A;
+  auto& S = g.S;
   fpr::HostArr<uint8_t, sub::QATOMS> M, Cu;
   for (long b = 0; b < B; ++b) {
     int n;
     sub::u64 lo, hi, hits = 0, open = 0;
-    const int st = sub::build(W, C, A, S, D, P, fpr::PaddedSrc{x + b * x_ld}, 1, T, false, V, tok_info, chem_info, eos_id, &n, &lo, &hi);
+    const int st = sub::build(W, g.C, A, S, g.D, g.P, fpr::PaddedSrc{x + b * x_ld}, 1, T, false, V, tok_info, chem_info, eos_id, &n, &lo, &hi);
     for (int q = 0; q < Q; ++q) {
       const sub::HostTab tab{table + (long)q * sub::WORDS};
       int res = sub::MISS, taken = 0;

@@ -2,7 +2,8 @@
 // (rew::graph), and from it the depth-first search and the emission of the search tree in the language the syntax automaton accepts
 // (rew::write), templated on the one thing the two consumers differ in -- the order of the atoms.  include/mvae.h ("SMILES rewrite")
 // states the definition; "SMILES canon" replaces its (prio, atom number) by a canonical rank and nothing else.  smiles_substruct.hip
-// takes the adjacency alone (rew::adjacency, he_order) and searches it instead of writing it.
+// takes the adjacency alone (rew::adjacency, he_order) and searches it instead of writing it.  Below them the writer driver: the arrays
+// stated once (rew::Store), and everything around a row that the two families' kernels, launches and host loops have in common.
 //
 // An order policy `Ord` has one member, bool before(int a, int b): atom a comes before atom b (a strict total order on 0 .. n - 1).
 // write() calls it while it picks the root and sorts the half-edges, and never once the emission has begun: a policy may therefore keep
@@ -293,87 +294,33 @@ SMI_HD int copy_len(const Src& src, int T, int eos_id) {
   return T;
 }
 
-// the storage of one 64-row block and the calling lane's view of it
-typedef fpr::LdsArr<uint32_t, smg::ATOM_SLOTS> LdsWords;
-typedef fpr::LdsArr<uint16_t, fpr::CLOSURES> LdsClos;
-typedef fpr::LdsArr<uint8_t, smg::ATOM_SLOTS> LdsBytes;
-typedef fpr::LdsArr<uint8_t, HALF> LdsHalf;
-
-struct Lds {
-  uint32_t words[smg::ATOM_SLOTS * 64];
-  union {
-    uint16_t clos[fpr::CLOSURES * 64];
-    uint8_t out[smg::ATOM_SLOTS * 64];
-  };
-  uint8_t half[HALF * 64];
-  uint8_t start[smg::ATOM_SLOTS * 64], dfs[smg::ATOM_SLOTS * 64], parent[smg::ATOM_SLOTS * 64];
+// The writer's arrays, stated once as the consumers of the row driver state theirs: Lds the storage of one 64-row block, Host the host
+// entries' arrays, lane(lds) the calling lane's accessors.  C is dead once graph() returns and nothing writes O before, so in LDS the two
+// are one 8 KiB (Front<LdsMem>); as accessors and on the host they stay two things.  W stands in Front with them so that the words keep
+// the front of the block: there the compiler reads and writes them in pairs (ds_read2st64_b32), behind the 8 KiB it does not.
+template <template <class, int> class Arr>
+struct Front {
+  Arr<uint32_t, SLOTS> W;
+  Arr<uint16_t, fpr::CLOSURES> C;
+  Arr<uint8_t, SLOTS> O;
 };
-
-// The staged rows of a block into out [B, T_out], row r by all 64 lanes over consecutive columns; called by the whole block behind a
-// __syncthreads().  len, keep: the calling lane's row (len == COPY: the first keep columns of x).  That read of the staging area has lanes
-// 64 bytes apart (a 16-way bank conflict); it is two or three instructions per row against the several thousand of the search.
-__device__ __forceinline__ void store_rows(const Lds& lds, int B, int b0, int lane, int len, int keep, const int64_t* __restrict__ x, long x_ld,
-                                           int bos_id, int eos_id, int pad_id, int T_out, int64_t* __restrict__ out) {
-  const int rows = B - b0 < 64 ? B - b0 : 64;
-  for (int r = 0; r < rows; ++r) {
-    const int lr = __shfl(len, r), kr = __shfl(keep, r);
-    const int64_t* xr = x + (long)(b0 + r) * x_ld;
-    int64_t* dst = out + (long)(b0 + r) * T_out;
-    for (int t = lane; t < T_out; t += 64) {
-      int64_t v = pad_id;
-      if (lr == COPY) {
-        if (t < kr) v = xr[t];
-      } else if (t == 0) v = bos_id;
-      else if (t <= lr) v = lds.out[((t - 1) & (smg::ATOM_SLOTS - 1)) * 64 + r];
-      else if (t == lr + 1) v = eos_id;
-      dst[t] = v;
-    }
-  }
-}
-
-// the same into tokens_out [B, stride]; lo: where the calling lane's corpus row starts in tokens
-__device__ __forceinline__ void store_corpus(const Lds& lds, int B, int b0, int lane, int len, int keep, long lo, const uint8_t* __restrict__ tokens,
-                                             int stride, uint8_t* __restrict__ tokens_out) {
-  const int nrows = B - b0 < 64 ? B - b0 : 64;
-  for (int r = 0; r < nrows; ++r) {
-    const int lr = __shfl(len, r), kr = __shfl(keep, r);
-    const long lor = __shfl(lo, r);
-    uint8_t* dst = tokens_out + (long)(b0 + r) * stride;
-    for (int t = lane; t < stride; t += 64) {
-      uint8_t v = 0;
-      if (lr == COPY) {
-        if (t < kr) v = tokens[lor + t];
-      } else if (t < lr) v = lds.out[(t & (smg::ATOM_SLOTS - 1)) * 64 + r];
-      dst[t] = v;
-    }
-  }
-}
-
-// what the corpus kernels do for batch member b once its row is written: its slice of the gapped CSR, its status, the histogram
-__device__ __forceinline__ void store_corpus_row(int b, int B, int stride, int len, int keep, int st, int64_t* __restrict__ offsets_out,
-                                                 int32_t* __restrict__ status, int32_t* __restrict__ counts) {
-  status[b] = st;
-  offsets_out[2 * (long)b] = (long)b * stride;
-  offsets_out[2 * (long)b + 1] = (long)b * stride + (len == COPY ? keep : len);
-  if (b == B - 1) offsets_out[2 * (long)B] = (long)B * stride;
-  if (counts) atomicAdd(counts + (st & 15), 1);
-}
-
-// the host entries' copy of row b into out [B, T_out]
-template <class Out>
-inline void host_store_row(const Out& O, const fpr::PaddedSrc& src, int T, int len, int bos_id, int eos_id, int pad_id, int T_out, int64_t* dst,
-                           int32_t* out_len) {
-  const int keep = len == COPY ? copy_len(src, T, eos_id) : 0;
-  *out_len = len == COPY ? keep : len + 2;
-  for (int t = 0; t < T_out; ++t) {
-    int64_t v = pad_id;
-    if (len == COPY) {
-      if (t < keep) v = src.row[t];
-    } else if (t == 0) v = bos_id;
-    else if (t <= len) v = O.get(t - 1);
-    else if (t == len + 1) v = eos_id;
-    dst[t] = v;
-  }
+template <>
+struct Front<fpr::LdsMem> {
+  fpr::LdsMem<uint32_t, SLOTS> W;
+  union {
+    fpr::LdsMem<uint16_t, fpr::CLOSURES> C;
+    fpr::LdsMem<uint8_t, SLOTS> O;
+  };
+};
+template <template <class, int> class Arr>
+struct Store : Front<Arr> {
+  Arr<uint8_t, HALF> A;
+  Arr<uint8_t, SLOTS> S, D, P;
+};
+typedef Store<fpr::LdsMem> Lds;
+typedef Store<fpr::HostArr> Host;
+__device__ __forceinline__ Store<fpr::LdsArr> lane(Lds& l) {
+  return {{l.W.lane(), l.C.lane(), l.O.lane()}, l.A.lane(), l.S.lane(), l.D.lane(), l.P.lane()};
 }
 
 inline bool common_ok(int V, const int32_t* tok_info, const int32_t* chem_info, const int32_t* emit, int max_content, const int32_t* status) {
@@ -387,11 +334,158 @@ inline bool rows_args_ok(int B, int T, int V, const int64_t* x, int64_t x_ld, co
          eos_id < V && bos_id >= 0 && bos_id <= 65535 && pad_id >= 0 && pad_id <= 65535 && T_out >= 2;
 }
 
-inline bool corpus_args_ok(const uint8_t* tokens, const int64_t* offsets, int64_t N, const int64_t* rows, int B, int V, const int32_t* tok_info,
-                           const int32_t* chem_info, const int32_t* emit, int max_content, int stride, const uint8_t* tokens_out,
-                           const int64_t* offsets_out, const int32_t* status) {
-  return common_ok(V, tok_info, chem_info, emit, max_content, status) && tokens && offsets && rows && tokens_out && offsets_out && N >= 1 &&
-         B >= 1 && stride >= max_content;
+// ---------------------------------------------------------------------------------------------------------------- the writer driver
+// The row driver of smiles_rounds.hpp for the families that write a string: one thread per row, 64-thread blocks, and behind the rows a
+// barrier and the block-wide copy-out.  A family R states what differs:
+//   R::Args           its own arguments behind the common ones (seed, draw / info, rank).  Kernels and entries pass them one by one
+//                     (F...), each pointer __restrict__ in the kernel's own list, and the driver makes the Args: as members of a
+//                     by-value kernel argument they would lose the qualifier
+//   R::row(store, src, first, end, end_is_eos, V, tok_info, chem_info, emit, eos_id, max_content, b, args, &len)
+//                     row b into store.O; returns the status, *len as write() gives it
+//   R::skipped(b, args)   what a corpus row whose id is outside [0, N) leaves in the family's own outputs
+// Each family keeps two __global__ kernels of its own name whose bodies are one call of block_rows<R> / block_corpus<R>, and three
+// entries that are one call of rows / corpus / host<R>.
+// The rows are staged in LDS and copied out by the whole block behind a barrier, row r by all 64 lanes over consecutive columns (a row
+// with len == COPY: the first keep columns of its source).  That read of the staging area has lanes 64 bytes apart (a 16-way bank
+// conflict); it is two or three instructions per row against the several thousand of the search.
+template <class R, class... F>
+__device__ __forceinline__ void block_rows(Lds& lds, int B, int T, int V, const int64_t* __restrict__ x, long x_ld,
+                                           const int32_t* __restrict__ tok_info, const int32_t* __restrict__ chem_info,
+                                           const int32_t* __restrict__ emit, int bos_id, int eos_id, int pad_id, int max_content, int T_out,
+                                           int64_t* __restrict__ out, int32_t* __restrict__ out_len, int32_t* __restrict__ status,
+                                           int32_t* __restrict__ counts, F... family) {
+  const int lane = threadIdx.x, b0 = blockIdx.x * 64, b = b0 + lane;
+  int len = COPY, keep = 0;
+  if (b < B) {
+    auto store = rew::lane(lds);
+    const fpr::PaddedSrc src{x + (long)b * x_ld};
+    const int st = R::row(store, src, 1, T, false, V, tok_info, chem_info, emit, eos_id, max_content, (long)b, typename R::Args{family...}, &len);
+    if (len == COPY) keep = copy_len(src, T, eos_id);
+    status[b] = st;
+    out_len[b] = len == COPY ? keep : len + 2;
+    if (counts) atomicAdd(counts + (st & 15), 1);
+  }
+  __syncthreads();
+  const int nrows = B - b0 < 64 ? B - b0 : 64;
+  for (int r = 0; r < nrows; ++r) {
+    const int lr = __shfl(len, r), kr = __shfl(keep, r);
+    const int64_t* xr = x + (long)(b0 + r) * x_ld;
+    int64_t* dst = out + (long)(b0 + r) * T_out;
+    for (int t = lane; t < T_out; t += 64) {
+      int64_t v = pad_id;
+      if (lr == COPY) {
+        if (t < kr) v = xr[t];
+      } else if (t == 0) v = bos_id;
+      else if (t <= lr) v = lds.O.v[((t - 1) & (SLOTS - 1)) * 64 + r];
+      else if (t == lr + 1) v = eos_id;
+      dst[t] = v;
+    }
+  }
+}
+
+// Batch member b is corpus row rows[b]; its slice of the gapped CSR, its status and the histogram are written with the row, and the
+// rows go into tokens_out [B, stride] as above.
+template <class R, class... F>
+__device__ __forceinline__ void block_corpus(Lds& lds, const uint8_t* __restrict__ tokens, const int64_t* __restrict__ offsets, long N,
+                                             const int64_t* __restrict__ rows, int B, int V, const int32_t* __restrict__ tok_info,
+                                             const int32_t* __restrict__ chem_info, const int32_t* __restrict__ emit, int max_content, int stride,
+                                             uint8_t* __restrict__ tokens_out, int64_t* __restrict__ offsets_out, int32_t* __restrict__ status,
+                                             int32_t* __restrict__ counts, int32_t* __restrict__ err, F... family) {
+  const int lane = threadIdx.x, b0 = blockIdx.x * 64, b = b0 + lane;
+  int len = COPY, keep = 0;
+  long lo = 0;                         // where the lane's corpus row starts in tokens
+  if (b < B) {
+    const long id = rows[b];
+    const typename R::Args args{family...};
+    int st = smg::SYNTAX;
+    if (id >= 0 && id < N) {
+      const long have = fpr::csr_len(offsets, id, &lo);
+      auto store = rew::lane(lds);
+      st = R::row(store, fpr::CsrSrc{tokens + lo}, 0, fpr::csr_end(have), true, V, tok_info, chem_info, emit, -1, max_content, (long)b, args, &len);
+      if (len == COPY) {
+        keep = (int)(have < stride ? have : stride);
+        if (have > stride && err) atomicMax(err, 1);
+      }
+    } else {
+      R::skipped((long)b, args);
+      if (err) atomicMax(err, 2);
+    }
+    status[b] = st;
+    offsets_out[2 * (long)b] = (long)b * stride;
+    offsets_out[2 * (long)b + 1] = (long)b * stride + (len == COPY ? keep : len);
+    if (b == B - 1) offsets_out[2 * (long)B] = (long)B * stride;
+    if (counts) atomicAdd(counts + (st & 15), 1);
+  }
+  __syncthreads();
+  const int nrows = B - b0 < 64 ? B - b0 : 64;
+  for (int r = 0; r < nrows; ++r) {
+    const int lr = __shfl(len, r), kr = __shfl(keep, r);
+    const long lor = __shfl(lo, r);
+    uint8_t* dst = tokens_out + (long)(b0 + r) * stride;
+    for (int t = lane; t < stride; t += 64) {
+      uint8_t v = 0;
+      if (lr == COPY) {
+        if (t < kr) v = tokens[lor + t];
+      } else if (t < lr) v = lds.O.v[(t & (SLOTS - 1)) * 64 + r];
+      dst[t] = v;
+    }
+  }
+}
+
+// The entries.  kernel: the family's __global__ function, whose parameters are those of block_rows / block_corpus behind the Lds.
+// V > 64 is refused as unsupported before anything is called invalid.
+template <class K, class... F>
+int rows(K kernel, int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info, const int32_t* emit,
+         int bos_id, int eos_id, int pad_id, int max_content, int T_out, int64_t* out, int32_t* out_len, int32_t* status, int32_t* counts,
+         void* stream, F... family) {
+  if (V > 64) return MVAE_ERR_UNSUPPORTED;
+  if (!rows_args_ok(B, T, V, x, x_ld, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content, T_out, out, out_len, status))
+    return MVAE_ERR_INVALID;
+  hipLaunchKernelGGL(kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, T, V, x, (long)x_ld, tok_info, chem_info, emit, bos_id,
+                     eos_id, pad_id, max_content, T_out, out, out_len, status, counts, family...);
+  MVAE_CHECK_HIP(hipGetLastError());
+  return MVAE_OK;
+}
+
+template <class K, class... F>
+int corpus(K kernel, const uint8_t* tokens, const int64_t* offsets, int64_t N, const int64_t* rows, int B, int V, const int32_t* tok_info,
+           const int32_t* chem_info, const int32_t* emit, int max_content, int stride, uint8_t* tokens_out, int64_t* offsets_out, int32_t* status,
+           int32_t* counts, int32_t* err, void* stream, F... family) {
+  if (V > 64) return MVAE_ERR_UNSUPPORTED;
+  if (!common_ok(V, tok_info, chem_info, emit, max_content, status) || !tokens || !offsets || !rows || !tokens_out || !offsets_out || N < 1 ||
+      B < 1 || stride < max_content)
+    return MVAE_ERR_INVALID;
+  hipLaunchKernelGGL(kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, tokens, offsets, (long)N, rows, B, V, tok_info, chem_info,
+                     emit, max_content, stride, tokens_out, offsets_out, status, counts, err, family...);
+  MVAE_CHECK_HIP(hipGetLastError());
+  return MVAE_OK;
+}
+
+template <class R, class... F>
+int host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info, const int32_t* emit, int bos_id,
+         int eos_id, int pad_id, int max_content, int T_out, int64_t* out, int32_t* out_len, int32_t* status, F... family) {
+  if (V > 64) return MVAE_ERR_UNSUPPORTED;
+  if (!rows_args_ok(B, T, V, x, x_ld, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content, T_out, out, out_len, status))
+    return MVAE_ERR_INVALID;
+  const typename R::Args args{family...};
+  Host store;
+  for (long b = 0; b < B; ++b) {
+    const fpr::PaddedSrc src{x + b * x_ld};
+    int len = COPY;
+    status[b] = R::row(store, src, 1, T, false, V, tok_info, chem_info, emit, eos_id, max_content, b, args, &len);
+    const int keep = len == COPY ? copy_len(src, T, eos_id) : 0;
+    out_len[b] = len == COPY ? keep : len + 2;
+    for (int t = 0; t < T_out; ++t) {
+      int64_t v = pad_id;
+      if (len == COPY) {
+        if (t < keep) v = src.row[t];
+      } else if (t == 0) v = bos_id;
+      else if (t <= len) v = store.O.get(t - 1);
+      else if (t == len + 1) v = eos_id;
+      out[b * T_out + t] = v;
+    }
+  }
+  return MVAE_OK;
 }
 
 }  // namespace rew

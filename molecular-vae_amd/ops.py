@@ -967,8 +967,44 @@ def draw_words(values):
     return torch.where(v >= 1 << 31, v - (1 << 32), v).to(torch.int32)
 
 
-def _rewrite_out(T_out):
-    return ((torch.int64, (T_out,), False), (torch.int32, (), False), (torch.int32, (), False))
+CANON_INFO = ("atoms", "first_classes", "rounds", "ties")          # the columns of info [*, 4] (include/mvae.h: MVAE_CANON_INFO)
+_CANON_OUT = ((torch.int32, (len(CANON_INFO),), True), (torch.uint8, (128,), True))      # info, rank: what canon writes beside the row
+
+
+def _writer_rows(name, host, x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, family_in, max_content, T_out, extra, given, counts):
+    """What the mvae_smiles_rewrite / _canon _rows and _host entries share: the tensor checks, the outputs, the call of the C entry
+    `name`.  family_in: (seed, draw) where the entry takes them (behind pad_id), () where not; extra: the spec of the outputs behind
+    (out, out_len, status), which the C entries take behind counts; given: the caller's outputs, all of them, as ``_outputs`` reads them."""
+    x, ldx = _token_rows(x, "x")
+    assert not host or x.device.type == "cpu", x.device
+    B, T = x.shape
+    seed, draw = family_in or (0, None)
+    _rewrite_tables(tok_info, chem_info, emit, draw, counts, B, x.device, max_content)
+    T_out = max(T, int(max_content) + 2) if T_out is None else int(T_out)
+    res = _outputs(B, x.device, ((torch.int64, (T_out,), False), (torch.int32, (), False), (torch.int32, (), False)) + extra, given)
+    check(getattr(L.load(), name)(B, T, tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), ptr(emit), int(bos_id), int(eos_id),
+                                  int(pad_id), *((int(seed) & 0xFFFFFFFF, ptr(draw)) if family_in else ()), int(max_content), T_out,
+                                  *map(ptr, res[:3]), *(() if host else (ptr(counts),)), *map(ptr, res[3:]),
+                                  *(() if host else (stream_ptr(),))), name)
+    return res
+
+
+def _writer_corpus(name, tokens, offsets, N, rows, tok_info, chem_info, emit, family_in, max_content, stride, extra, given, counts, err):
+    """The same for the _corpus entries; given = (tokens_out, offsets_out, status) and the outputs of `extra`."""
+    N, B = int(N), rows.numel()
+    dev = tokens.device
+    _csr(tokens, offsets, N)
+    assert rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_contiguous() and rows.device == dev and B >= 1
+    seed, draw = family_in or (0, None)
+    _rewrite_tables(tok_info, chem_info, emit, draw, counts, B, dev, max_content)
+    stride = int(max_content) if stride is None else int(stride)
+    offsets_out, = _outputs(2 * B + 1, dev, ((torch.int64, (), False),), given[1:2])
+    tokens_out, status, *more = _outputs(B, dev, ((torch.uint8, (stride,), False), (torch.int32, (), False)) + extra, given[:1] + given[2:])
+    assert err is None or (err.dtype == torch.int32 and err.numel() == 1 and err.device == dev)
+    check(getattr(L.load(), name)(ptr(tokens), ptr(offsets), N, ptr(rows), B, tok_info.numel(), ptr(tok_info), ptr(chem_info), ptr(emit),
+                                  *((int(seed) & 0xFFFFFFFF, ptr(draw)) if family_in else ()), int(max_content), stride, ptr(tokens_out),
+                                  ptr(offsets_out), ptr(status), ptr(counts), ptr(err), *map(ptr, more), stream_ptr()), name)
+    return (tokens_out, offsets_out, status, *more)
 
 
 def smiles_rewrite_rows(x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, seed=0, draw=None, max_content=127, T_out=None, out=None,
@@ -980,31 +1016,16 @@ def smiles_rewrite_rows(x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, se
     None for the row number; T_out defaults to max(T, max_content + 2), so that nothing is cut; counts (int32 [16], optional, zeroed by
     the caller) += the per-status histogram.  NOT a canonical SMILES, no stereo, not rdkit's doRandom.  One launch
     (mvae_smiles_rewrite_rows)."""
-    x, ldx = _token_rows(x, "x")
-    B, T = x.shape
-    _rewrite_tables(tok_info, chem_info, emit, draw, counts, B, x.device, max_content)
-    T_out = max(T, int(max_content) + 2) if T_out is None else int(T_out)
-    res = _outputs(B, x.device, _rewrite_out(T_out), (out, out_len, status))
-    check(L.load().mvae_smiles_rewrite_rows(B, T, tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), ptr(emit), int(bos_id), int(eos_id),
-                                            int(pad_id), int(seed) & 0xFFFFFFFF, ptr(draw), int(max_content), T_out, *map(ptr, res), ptr(counts),
-                                            stream_ptr()), "mvae_smiles_rewrite_rows")
-    return res
+    return _writer_rows("mvae_smiles_rewrite_rows", False, x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, (seed, draw), max_content, T_out,
+                        (), (out, out_len, status), counts)
 
 
 def smiles_rewrite_host(x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, seed=0, draw=None, max_content=127, T_out=None, out=None,
                         out_len=None, status=None):
     """smiles_rewrite_rows on HOST tensors: the same source compiled for the CPU, a plain loop over the rows (mvae_smiles_rewrite_host) --
     for tests and for machines without a device; not a fallback of the device entries."""
-    x, ldx = _token_rows(x, "x")
-    assert x.device.type == "cpu", x.device
-    B, T = x.shape
-    _rewrite_tables(tok_info, chem_info, emit, draw, None, B, x.device, max_content)
-    T_out = max(T, int(max_content) + 2) if T_out is None else int(T_out)
-    res = _outputs(B, x.device, _rewrite_out(T_out), (out, out_len, status))
-    check(L.load().mvae_smiles_rewrite_host(B, T, tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), ptr(emit), int(bos_id), int(eos_id),
-                                            int(pad_id), int(seed) & 0xFFFFFFFF, ptr(draw), int(max_content), T_out, *map(ptr, res)),
-          "mvae_smiles_rewrite_host")
-    return res
+    return _writer_rows("mvae_smiles_rewrite_host", True, x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, (seed, draw), max_content, T_out,
+                        (), (out, out_len, status), None)
 
 
 def smiles_rewrite_corpus(tokens, offsets, N, rows, tok_info, chem_info, emit, seed=0, draw=None, max_content=127, stride=None, tokens_out=None,
@@ -1014,29 +1035,8 @@ def smiles_rewrite_corpus(tokens, offsets, N, rows, tok_info, chem_info, emit, s
     stride, stride + len_1, ...: tokens_out is a CSR of 2 B rows whose even rows are the batch members, so ``moses_collate`` with rows =
     0, 2, 4, ... collates it unchanged.  stride defaults to max_content; err (int32 [1], optional, zeroed by the caller) is raised to 1
     by a copied-through row longer than stride and to 2 by a row id outside [0, N)."""
-    N, B = int(N), rows.numel()
-    dev = tokens.device
-    _csr(tokens, offsets, N)
-    assert rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_contiguous() and rows.device == dev and B >= 1
-    _rewrite_tables(tok_info, chem_info, emit, draw, counts, B, dev, max_content)
-    stride = int(max_content) if stride is None else int(stride)
-    tokens_out = torch.empty(B, stride, dtype=torch.uint8, device=dev) if tokens_out is None else tokens_out
-    offsets_out = torch.empty(2 * B + 1, dtype=torch.int64, device=dev) if offsets_out is None else offsets_out
-    status = torch.empty(B, dtype=torch.int32, device=dev) if status is None else status
-    for t, dt, shape in ((tokens_out, torch.uint8, (B, stride)), (offsets_out, torch.int64, (2 * B + 1,)), (status, torch.int32, (B,))):
-        assert t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev, (dt, shape)
-    assert err is None or (err.dtype == torch.int32 and err.numel() == 1 and err.device == dev)
-    check(L.load().mvae_smiles_rewrite_corpus(ptr(tokens), ptr(offsets), N, ptr(rows), B, tok_info.numel(), ptr(tok_info), ptr(chem_info), ptr(emit),
-                                              int(seed) & 0xFFFFFFFF, ptr(draw), int(max_content), stride, ptr(tokens_out), ptr(offsets_out),
-                                              ptr(status), ptr(counts), ptr(err), stream_ptr()), "mvae_smiles_rewrite_corpus")
-    return tokens_out, offsets_out, status
-
-
-CANON_INFO = ("atoms", "first_classes", "rounds", "ties")          # the columns of info [*, 4] (include/mvae.h: MVAE_CANON_INFO)
-
-
-def _canon_out(T_out):
-    return _rewrite_out(T_out) + ((torch.int32, (len(CANON_INFO),), True), (torch.uint8, (128,), True))
+    return _writer_corpus("mvae_smiles_rewrite_corpus", tokens, offsets, N, rows, tok_info, chem_info, emit, (seed, draw), max_content, stride, (),
+                          (tokens_out, offsets_out, status), counts, err)
 
 
 def smiles_canon_rows(x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content=127, T_out=None, out=None, out_len=None, status=None,
@@ -1047,30 +1047,16 @@ def smiles_canon_rows(x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_
     aromaticity perception, no stereo, NOT rdkit's canonical SMILES).  The statuses and the copy-through of a refused row are the
     rewrite's.  info = atoms, classes after the first refinement, rounds, ties (``CANON_INFO``); rank[k] = the canonical rank of atom k,
     0xFF beyond the atoms; ``info=False`` / ``rank=False``: not written (None in its place).  One launch (mvae_smiles_canon_rows)."""
-    x, ldx = _token_rows(x, "x")
-    B, T = x.shape
-    _rewrite_tables(tok_info, chem_info, emit, None, counts, B, x.device, max_content)
-    T_out = max(T, int(max_content) + 2) if T_out is None else int(T_out)
-    res = _outputs(B, x.device, _canon_out(T_out), (out, out_len, status, info, rank))
-    check(L.load().mvae_smiles_canon_rows(B, T, tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), ptr(emit), int(bos_id), int(eos_id),
-                                          int(pad_id), int(max_content), T_out, *map(ptr, res[:3]), ptr(counts), ptr(res[3]), ptr(res[4]),
-                                          stream_ptr()), "mvae_smiles_canon_rows")
-    return res
+    return _writer_rows("mvae_smiles_canon_rows", False, x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, (), max_content, T_out, _CANON_OUT,
+                        (out, out_len, status, info, rank), counts)
 
 
 def smiles_canon_host(x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content=127, T_out=None, out=None, out_len=None, status=None,
                       info=None, rank=None):
     """smiles_canon_rows on HOST tensors: the same source compiled for the CPU, a plain loop over the rows (mvae_smiles_canon_host) -- for
     tests and for machines without a device; not a fallback of the device entries."""
-    x, ldx = _token_rows(x, "x")
-    assert x.device.type == "cpu", x.device
-    B, T = x.shape
-    _rewrite_tables(tok_info, chem_info, emit, None, None, B, x.device, max_content)
-    T_out = max(T, int(max_content) + 2) if T_out is None else int(T_out)
-    res = _outputs(B, x.device, _canon_out(T_out), (out, out_len, status, info, rank))
-    check(L.load().mvae_smiles_canon_host(B, T, tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), ptr(emit), int(bos_id), int(eos_id),
-                                          int(pad_id), int(max_content), T_out, *map(ptr, res)), "mvae_smiles_canon_host")
-    return res
+    return _writer_rows("mvae_smiles_canon_host", True, x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, (), max_content, T_out, _CANON_OUT,
+                        (out, out_len, status, info, rank), None)
 
 
 def smiles_canon_corpus(tokens, offsets, N, rows, tok_info, chem_info, emit, max_content=127, stride=None, tokens_out=None, offsets_out=None,
@@ -1078,21 +1064,8 @@ def smiles_canon_corpus(tokens, offsets, N, rows, tok_info, chem_info, emit, max
     """smiles_canon_rows over the rows `rows` (int64 [B]) of the CSR corpus, one launch (mvae_smiles_canon_corpus): (tokens_out uint8
     [B, stride], offsets_out int64 [2 B + 1], status int32 [B], info int32 [B, 4], rank uint8 [B, 128]) in the gapped CSR layout of
     ``smiles_rewrite_corpus``, with its counts and err; ``info=False`` / ``rank=False``: not written (None in its place)."""
-    N, B = int(N), rows.numel()
-    dev = tokens.device
-    _csr(tokens, offsets, N)
-    assert rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_contiguous() and rows.device == dev and B >= 1
-    _rewrite_tables(tok_info, chem_info, emit, None, counts, B, dev, max_content)
-    stride = int(max_content) if stride is None else int(stride)
-    offsets_out = torch.empty(2 * B + 1, dtype=torch.int64, device=dev) if offsets_out is None else offsets_out
-    assert offsets_out.dtype == torch.int64 and offsets_out.shape == (2 * B + 1,) and offsets_out.is_contiguous() and offsets_out.device == dev
-    spec = ((torch.uint8, (stride,), False), (torch.int32, (), False)) + _canon_out(0)[3:]
-    tokens_out, status, info, rank = _outputs(B, dev, spec, (tokens_out, status, info, rank))
-    assert err is None or (err.dtype == torch.int32 and err.numel() == 1 and err.device == dev)
-    check(L.load().mvae_smiles_canon_corpus(ptr(tokens), ptr(offsets), N, ptr(rows), B, tok_info.numel(), ptr(tok_info), ptr(chem_info), ptr(emit),
-                                            int(max_content), stride, ptr(tokens_out), ptr(offsets_out), ptr(status), ptr(counts), ptr(err),
-                                            ptr(info), ptr(rank), stream_ptr()), "mvae_smiles_canon_corpus")
-    return tokens_out, offsets_out, status, info, rank
+    return _writer_corpus("mvae_smiles_canon_corpus", tokens, offsets, N, rows, tok_info, chem_info, emit, (), max_content, stride, _CANON_OUT,
+                          (tokens_out, offsets_out, status, info, rank), counts, err)
 
 
 SUBSTRUCT_QATOMS = 32                         # include/mvae.h: MVAE_SUBSTRUCT_QATOMS, the atoms of a query and the columns of `map`
