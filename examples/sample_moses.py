@@ -28,8 +28,10 @@ not rdkit's Morgan fingerprint: the figures compare runs of this script, not pub
 are one graph) and, with ``--novel_against``, the MOSES Scaf figure -- the cosine similarity of the generated and the training scaffold
 histograms --, the scaffolds and the graphs absent from the corpus; at the end the five most frequent generated scaffolds, each with a
 sample that has it and one training molecule that has it (``MosesDeviceDataset.rows_with_scaffold``).  The scaffold is the rings, the
-linkers between them and the atoms double-bonded to either, on the graph of the SMILES graph walk: not rdkit's MurckoScaffold, and no
-scaffold SMILES is produced.
+linkers between them and the atoms double-bonded to either, on the graph of the SMILES graph walk: not rdkit's MurckoScaffold.
+``--top_scaffolds K`` (with ``--scaffolds``) also prints each round's K most frequent scaffolds as SMILES, with the samples drawn
+(``mv.moses_generate(top_scaffolds=K)``: ``VAE.scaffold_smiles``, lost substituents turned into hydrogens, this library's canonical
+spelling -- not rdkit's MurckoScaffoldSmiles: nothing is sanitised, no aromaticity perception, no stereo).
 ``--kekule`` prints, for each round, how many samples are kekulisable (``mv.moses_generate(kekule=True)``: valence-consistent, and every
 aromatic atom that needs a ring double bond gets one -- an exact matching on the graph of the SMILES graph walk) and how many fail on
 that alone, and with ``--novel_against`` audits the corpus once (``MosesDeviceDataset.kekule``).  A tighter necessary condition than
@@ -92,6 +94,8 @@ ap.add_argument("--kekule", action="store_true", help="count the kekulisable sam
                                                       "their ring double bond)")
 ap.add_argument("--respell", default=0, type=int, metavar="N", help="at the end print N randomised spellings (VAE.respell) of each of the first "
                                                                    "five unique samples the walk accepts")
+ap.add_argument("--top_scaffolds", type=int, default=0, help="with --scaffolds: print each round's K most frequent scaffolds as SMILES "
+                                                             "(this library's scaffold SMILES, not rdkit's MurckoScaffoldSmiles)")
 ap.add_argument("--canonical", action="store_true", help="print each round's distinct canonical spellings (unique@k on graphs) and, with "
                                                          "--novel_against, those absent from the canonicalised corpus")
 ap.add_argument("--filters", default=None, metavar="FILE", help="SMILES fragments, one per line: print each round's share of valence-consistent "
@@ -167,7 +171,7 @@ with open(args.log, "w", buffering=1) as f:
                                 top_p=args.top_p, seed=args.seed + r * args.batches_per_round, syntax=args.syntax, count_valid=True,
                                 novel_against=corpus, prefix=args.prefix, nearest=args.nearest, valence=args.valence,
                                 int_div=args.int_div, snn=args.snn, scaffolds=args.scaffolds, kekule=args.kekule, canonical=args.canonical,
-                                filters=filters)
+                                filters=filters, top_scaffolds=args.top_scaffolds if args.scaffolds else 0)
         total += res["total"]
         if args.kekule:
             kekule_valid += res["kekule_valid"]
@@ -212,6 +216,8 @@ with open(args.log, "w", buffering=1) as f:
                  + f"; undecided {sum(res['filter_undecided'])})" if filters is not None else "")
               + (f", valid unique {valid}" if Chem is not None else "")
               + (f", novel {len(novel)} ({len(novel) / len(seen):.3f} of unique)" if corpus is not None else ""), flush=True)
+        if args.scaffolds and args.top_scaffolds > 0:
+            print(f"round {r}: the most frequent scaffolds (samples drawn): " + ", ".join(f"{s} {c}" for s, c in res["top_scaffolds"]), flush=True)
 if args.respell > 0 and seen:
     picked = [s for s in list(seen)[:256] if s][:64]
     ok = model.chem_valid(picked).tolist() if picked else []

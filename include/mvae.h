@@ -882,8 +882,8 @@ int mvae_smiles_fp_host(int B, int T, int V, const int64_t* x, int64_t x_ld, con
  * Murcko scaffold (an addition: a third consumer of the "SMILES graph" walk above).  The Bemis-Murcko framework of a row -- its rings,
  * the linkers between them, and the atoms double-bonded to either -- as a set of the row's atoms.  It is defined on the graph exactly as
  * the walk builds it: explicit [H] are atoms, ring-closure bonds are order 1, nothing is kekulised, '@' '/' '\' carry no information.  So
- * this is NOT rdkit's MurckoScaffold: the atom sets agree where the two graphs agree, but no scaffold SMILES is produced, nothing is
- * sanitised, and the keys below are this library's own.  Not rdkit, not kekulised.
+ * this is NOT rdkit's MurckoScaffold: the atom sets agree where the two graphs agree, but no scaffold SMILES is produced here
+ * ("Scaffold SMILES" below writes one), nothing is sanitised, and the keys below are this library's own.  Not rdkit, not kekulised.
  * Atoms are numbered in string order (the order in which the walk creates them), from 0; a row has at most 127.
  * Core.  The ring atoms (the walk's ring mask: the atoms that lie on a cycle), plus every non-ring atom that lies on a path between two
  *   ring atoms.  Equivalently: what is left after repeatedly deleting atoms with at most one remaining neighbour.  Equivalently: a non-ring
@@ -1092,6 +1092,8 @@ int mvae_smiles_rewrite_host(int B, int T, int V, const int64_t* x, int64_t x_ld
  * What is claimed.  Equal output rows (status 0) => equal graphs, always: the output spells the input's graph.  Equal graphs => equal
  *   output rows whenever, at every tie, the members of the chosen class are equivalent under a symmetry of the graph; that holds on the
  *   whole test corpus, cage and spiro rows included, where every choice at every tie is followed, and is NOT proved in general.
+ *   A known instance where it fails: C1CCC(CC1)CCCCCC1CCCCC1 (1,5-dicyclohexylpentane).  The equitable partition ties ring atoms with
+ *   chain atoms, following every choice at every tie reaches two strings, and the spelling depends on the order of the input.
  * What this is NOT: not rdkit's canonical SMILES.  No aromaticity perception (C1=CC=CC=C1 and c1ccccc1 stay two strings), no stereo
  *   (STEREO refuses such rows), [CH4] is not unbracketed.
  * mvae_smiles_canon_rows / _corpus / _host take the arguments of mvae_smiles_rewrite_rows / _corpus / _host without seed and draw, and
@@ -1202,6 +1204,66 @@ int mvae_smiles_substruct_host(int B, int T, int V, const int64_t* x, int64_t x_
                                const int32_t* chem_info /* [V] */, int eos_id, int Q, const int32_t* table /* [Q, 100] */, int max_steps,
                                int map_query, int32_t* status /* [B] */, int64_t* hit /* [B] */, int64_t* undecided /* [B] */,
                                uint8_t* map /* [B, 32] or NULL */, int32_t* steps /* [B, Q] or NULL */, int32_t* counts /* [Q, 2] or NULL */);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Scaffold SMILES (an addition: an eighth consumer of the "SMILES graph" walk above, and the third that writes a string).  The Murcko
+ * scaffold of a token row as a token row: the scaffold graph G_S of the row, in the spelling of "SMILES canon", so that scaffolds can be
+ * read, written to a file, passed on as substructure queries, and compared exactly by comparing tokens.
+ * What this is NOT: not rdkit's MurckoScaffoldSmiles.  Nothing is sanitised, no aromaticity is perceived (C1=CC=CC=C1 and c1ccccc1 have
+ *   two scaffolds), and there is no stereo: a row with a stereo token gets status STEREO and no scaffold.  There is no generic
+ *   (all-carbon) framework mode.
+ * The scaffold graph G_S.  S = Core u Exo, exactly as "Murcko scaffold" defines them.  The atoms of G_S are the atoms of S, numbered in
+ *   string order among themselves; its bonds are the row's bonds between two atoms of S, with their orders.
+ * Hydrogens.  Every kept atom keeps its total valence, and the bonds it loses become hydrogens.
+ *   h_row(a): the bracket H count of a bracket atom; for an unbracketed atom its implicit hydrogens by the rule of "SMILES graph".
+ *   lost(a): the sum of the orders of a's bonds to atoms outside S (explicit [H] neighbours included).
+ *   h_S(a) = h_row(a) + lost(a).
+ *   A bracket atom stays a bracket atom, with H count h_S; element, aromatic flag and charge are kept.
+ *   An unbracketed atom stays unbracketed iff the implicit-hydrogen rule, applied to its bond sum in G_S, gives exactly h_S; otherwise it
+ *     becomes a bracket atom with H count h_S and charge 0.
+ *   Cn1cccc1 -> c1cc[nH]c1; C[n+]1ccccc1 -> c1cc[nH+]cc1; C[N+]1(C)CCCC1 -> C1CC[NH2+]C1; O=C1CCCCC1C -> C1CCC(=O)CC1;
+ *   N#Cc1ccc(Br)=c1 -> c1cc=[cH]c1; Clc1ccccc1 -> c1ccccc1; CP1(=O)CCCC1 -> C1CCP(=O)C1.
+ *   Because valences are kept, the set N of "Kekulisation" and its matching are the same for the row and for its scaffold.
+ * Spelling.  "SMILES canon" applied to G_S: its first invariant (with the bracket flag and the bracket hydrogens of G_S), its refinement,
+ *   ties, search and emission, with nothing changed.
+ * Canonicity is that section's claim, and carries its limit ("NOT proved in general").  One instance of the limit is known:
+ *   C1CCC(CC1)CCCCCC1CCCCC1 (1,5-dicyclohexylpentane), where the equitable partition ties ring atoms with chain atoms, so that the
+ *   members of the class chosen at a tie are not all equivalent under a symmetry: following every choice at every tie reaches two
+ *   strings, and such a graph can be spelled two ways depending on the order of the input.  The test corpus has no such row.
+ * Status.  0: the scaffold was written.  1 - 6: the walk's refusals.  8 - 13: the rewrite's refusals, with the rewrite's precedence, where
+ *   STEREO is decided before S and 9 - 13 speak of the scaffold's spelling (LONG: the scaffold has more than max_content tokens).
+ *   14 MVAE_SMILES_NO_RING: a row the walk gives 0, without a stereo token, that has no ring (S is empty); decided after STEREO and
+ *   before the search.  (As a number, 14 is also the compile entry's MVAE_SMILES_QUERY_ATOMS; no entry gives both.)
+ * mvae_smiles_scaffold_smiles_rows / _corpus / _host take the arguments of mvae_smiles_canon_rows / _corpus / _host without rank, and
+ *   write their outputs in the same layouts, with one difference: a row whose status is not 0 gets the EMPTY row, never a copy of the
+ *   input -- a molecule is not its own scaffold.  _rows / _host: bos_id, eos_id, then pad_id, and out_len = 2; _corpus: a slice of length
+ *   0, and err is raised only by a row id outside [0, N) (to 2).  counts int32 [16] has room for status 14.
+ *   info int32 [B, MVAE_SCAFFOLD_SMILES_INFO = 4] (optional, may be NULL) = |S|, the bonds of G_S, the atoms that became bracket atoms,
+ *     the sum of lost(a) over S -- for status 0 and 9 - 13, zeros otherwise.
+ *   Every element of every given output is written, nothing else is; two runs are bit-identical; the three entries are one source.
+ * One thread per row; MVAE_SCAFFOLD_SMILES_LDS_BYTES = 81920 B (80 KiB) of LDS per 64-row block, the rewrite's block with nothing
+ *   added: S is two 64-bit masks in registers, the atom words and the closure pairs are cut down to S in place (the new number of an
+ *   atom is the count of the members of S below it), and the adjacency, the ranks and the search run on the cut arrays as they do in
+ *   the canon entries.  No recursion; every loop is bounded by the 127 atoms a row can have.
+ * Refused before anything is enqueued: exactly what the canon entries refuse of these arguments.
+ */
+#define MVAE_SMILES_NO_RING 14
+#define MVAE_SCAFFOLD_SMILES_INFO 4
+#define MVAE_SCAFFOLD_SMILES_LDS_BYTES 81920
+int mvae_smiles_scaffold_smiles_rows(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */,
+                                     const int32_t* chem_info /* [V] */, const int32_t* emit /* [48] */, int bos_id, int eos_id, int pad_id,
+                                     int max_content, int T_out, int64_t* out /* [B, T_out] */, int32_t* out_len /* [B] */,
+                                     int32_t* status /* [B] */, int32_t* counts /* [16] or NULL */, int32_t* info /* [B, 4] or NULL */,
+                                     void* stream);
+int mvae_smiles_scaffold_smiles_corpus(const uint8_t* tokens, const int64_t* offsets /* [N + 1] */, int64_t N, const int64_t* rows /* [B] */,
+                                       int B, int V, const int32_t* tok_info /* [V] */, const int32_t* chem_info /* [V] */,
+                                       const int32_t* emit /* [48] */, int max_content, int stride, uint8_t* tokens_out /* [B, stride] */,
+                                       int64_t* offsets_out /* [2 B + 1] */, int32_t* status /* [B] */, int32_t* counts /* [16] or NULL */,
+                                       int32_t* err /* [1] or NULL */, int32_t* info /* [B, 4] or NULL */, void* stream);
+int mvae_smiles_scaffold_smiles_host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */,
+                                     const int32_t* chem_info /* [V] */, const int32_t* emit /* [48] */, int bos_id, int eos_id, int pad_id,
+                                     int max_content, int T_out, int64_t* out /* [B, T_out] */, int32_t* out_len /* [B] */,
+                                     int32_t* status /* [B] */, int32_t* info /* [B, 4] or NULL */);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Tanimoto similarity of fingerprints (an addition: the structure-aware counterpart of mvae_latent_knn and mvae_edit_knn).  Fingerprints

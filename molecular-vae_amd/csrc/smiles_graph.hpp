@@ -42,6 +42,14 @@ SMI_HD int a_brk(uint32_t w) { return (int)(w >> 21) & 1; }
 SMI_HD int a_chg(uint32_t w) { return ((int)(w >> 22) & 3) - 1; }
 SMI_HD bool a_fits(uint32_t w) { return a_used(w) <= vmax(a_elem(w), a_chg(w)); }
 
+// the implicit hydrogens of an unbracketed atom of element e whose bonds sum to `sum`
+SMI_HD int implicit_h(int e, int arom, int sum) {
+  int v0 = (int)(VMIN_0 >> (4 * e)) & 0xF;
+  while (v0 < sum) v0 += 2;           // {3,5}, {2,4,6}, {1,3,5}: the next allowed valence is two up
+  const int h = v0 - sum;
+  return arom ? (h > 0 ? h - 1 : 0) : h;
+}
+
 struct Mask { u64 lo, hi; };          // one bit per atom
 SMI_HD void m_set(Mask& m, int i) {
   if (i < 64) m.lo |= 1ull << (i & 63);
@@ -205,14 +213,7 @@ struct Graph {
         if (e <= 8) lo += 1ull << (8 * (e - 1));
         else hi += 1ull << (8 * (e - 9));
       }
-      if (!a_brk(w)) {
-        const int used = a_used(w);
-        int v0 = (int)(VMIN_0 >> (4 * e)) & 0xF;
-        while (v0 < used) v0 += 2;                               // {3,5}, {2,4,6}, {1,3,5}: the next allowed valence is two up
-        int h = v0 - used;
-        if (a_arom(w)) h = h > 0 ? h - 1 : 0;
-        hyd += h;
-      }
+      if (!a_brk(w)) hyd += implicit_h(e, a_arom(w), a_used(w));
     }
     r->heavy = heavy; r->bonds = n - 1 + nring; r->rings = nring; r->ring_atoms = m_count(ring); r->arom = m_count(arom);
     r->hyd = hyd; r->charge = charge; r->hetero = hetero; r->cnt_lo = lo; r->cnt_hi = hi;

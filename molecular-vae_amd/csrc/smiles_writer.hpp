@@ -113,12 +113,11 @@ SMI_HD void adjacency(Words& W, Clos& C, Half& A, Bytes& S, Bytes& D, Bytes& P, 
   }
 }
 
-// The walk, the stereo test and the adjacency.  Returns the status; *n_out = the atoms (>= 1 with status 0).
-template <class Words, class Clos, class Half, class Bytes, class Src>
-SMI_HD int graph(Words& W, Clos& C, Half& A, Bytes& S, Bytes& D, Bytes& P, const Src& src, int first, int end, bool end_is_eos, int V,
-                 const int32_t* tok_info, const int32_t* chem_info, const int32_t* emit, int eos_id, int* n_out) {
-  *n_out = 0;
-  fpr::Rec<Clos> rec(C);
+// The walk and the stereo test.  Returns the status; with status 0, rec holds the atoms (>= 1), the closures and the ring members
+// (scaffold_smiles.hip cuts the graph down between this and the adjacency).
+template <class Words, class Clos, class Src>
+SMI_HD int read(Words& W, fpr::Rec<Clos>& rec, const Src& src, int first, int end, bool end_is_eos, int V, const int32_t* tok_info,
+                const int32_t* chem_info, const int32_t* emit, int eos_id) {
   smg::Row r;
   smg::walk(W, src, first, end, end_is_eos, V, tok_info, chem_info, eos_id, &r, rec);
   if (r.status != smg::OK) return r.status;
@@ -128,10 +127,20 @@ SMI_HD int graph(Words& W, Clos& C, Half& A, Bytes& S, Bytes& D, Bytes& P, const
     if (tok == eos_id) break;
     if ((stereo >> (tok & 63)) & 1ull) return STEREO;
   }
-  const int n = rec.n, nclos = rec.nclos < fpr::CLOSURES ? rec.nclos : fpr::CLOSURES;
-  if (n < 1) return smg::SYNTAX;       // cannot happen: the automaton takes no row without an atom
-  adjacency(W, C, A, S, D, P, n, nclos);
-  *n_out = n;
+  if (rec.n < 1) return smg::SYNTAX;   // cannot happen: the automaton takes no row without an atom
+  return smg::OK;
+}
+
+// The walk, the stereo test and the adjacency.  Returns the status; *n_out = the atoms (>= 1 with status 0).
+template <class Words, class Clos, class Half, class Bytes, class Src>
+SMI_HD int graph(Words& W, Clos& C, Half& A, Bytes& S, Bytes& D, Bytes& P, const Src& src, int first, int end, bool end_is_eos, int V,
+                 const int32_t* tok_info, const int32_t* chem_info, const int32_t* emit, int eos_id, int* n_out) {
+  *n_out = 0;
+  fpr::Rec<Clos> rec(C);
+  const int st = read(W, rec, src, first, end, end_is_eos, V, tok_info, chem_info, emit, eos_id);
+  if (st != smg::OK) return st;
+  adjacency(W, C, A, S, D, P, rec.n, rec.nclos < fpr::CLOSURES ? rec.nclos : fpr::CLOSURES);
+  *n_out = rec.n;
   return smg::OK;
 }
 

@@ -231,6 +231,7 @@ class MosesDeviceDataset:
         self._scaffolds = self._scaffold_hist = self._scaffold_order = self._mol_keys = None     # scaffolds() and what is derived from it
         self._kekule = None
         self._canonical = None                                         # canonical(): (dataset, status, counts), computed on first use
+        self._scaffold_smiles = None                                   # scaffold_smiles(): (dataset, rows, status, counts), likewise
 
     def __len__(self):
         return self.n
@@ -406,6 +407,27 @@ class MosesDeviceDataset:
             self._kekule = out
         return self._kekule
 
+    def _compacted(self, tokens_out, offsets_out, rows):
+        """The gapped CSR of a writer _corpus launch (ops.smiles_rewrite_corpus) as a ``MosesDeviceDataset`` on the same device, compacted
+        there: batch members `rows` (int64, ascending), all of them for None.  The host waits once, for the row lengths."""
+        dev, stride = self.device, tokens_out.shape[1]
+        lens = offsets_out[1::2] - offsets_out[0:-1:2]
+        if rows is not None:
+            lens, tokens_out = lens[rows], tokens_out[rows]
+        n = lens.numel()
+        offsets = torch.zeros(n + 1, dtype=torch.long, device=dev)
+        offsets[1:] = torch.cumsum(lens, 0)
+        keep = torch.arange(stride, device=dev)[None, :] < lens[:, None]
+        ds = object.__new__(MosesDeviceDataset)
+        ds.vocab, ds.n, ds.device = self.vocab, n, dev
+        ds.lengths = lens.to(torch.int32).cpu().numpy()
+        ds.max_len = int(ds.lengths.max()) if n else 0
+        ds.tokens = torch.cat([tokens_out[keep], torch.zeros(1, dtype=torch.uint8, device=dev)])      # the spare byte of __init__
+        ds.offsets = offsets
+        ds.err = torch.zeros(1, dtype=torch.int32, device=dev)
+        ds._no_caches()
+        return ds
+
     def canonical(self):
         """The corpus in canonical spelling: a ``MosesDeviceDataset`` on the same device whose row r is the canonical spelling of this
         one's row r (include/mvae.h, "SMILES canon"; a row that cannot be written -- ``canonical_status`` != 0 -- keeps its own
@@ -423,18 +445,7 @@ class MosesDeviceDataset:
             tokens_out, offsets_out, status, _, _ = ops.smiles_canon_corpus(
                 self.tokens, self.offsets, n, torch.arange(n, dtype=torch.long, device=dev), tok, chem, smiles_emit_table(self.vocab).to(dev),
                 127, stride, info=False, rank=False, counts=counts)
-            lens = offsets_out[1::2] - offsets_out[0:-1:2]
-            offsets = torch.zeros(n + 1, dtype=torch.long, device=dev)
-            offsets[1:] = torch.cumsum(lens, 0)
-            keep = torch.arange(stride, device=dev)[None, :] < lens[:, None]
-            ds = object.__new__(MosesDeviceDataset)
-            ds.vocab, ds.n, ds.device = self.vocab, n, dev
-            ds.lengths = lens.to(torch.int32).cpu().numpy()
-            ds.max_len = int(ds.lengths.max())
-            ds.tokens = torch.cat([tokens_out[keep], torch.zeros(1, dtype=torch.uint8, device=dev)])      # the spare byte of __init__
-            ds.offsets = offsets
-            ds.err = torch.zeros(1, dtype=torch.int32, device=dev)
-            ds._no_caches()
+            ds = self._compacted(tokens_out, offsets_out, None)
             self._canonical = (ds, status, counts)
         return self._canonical[0]
 
@@ -450,6 +461,41 @@ class MosesDeviceDataset:
         """How many corpus rows have each ``canonical_status``: int32 [16] on the device, kept by the kernel's integer atomic adds."""
         self.canonical()
         return self._canonical[2]
+
+    def scaffold_smiles(self):
+        """The Murcko scaffolds of the corpus as token rows (include/mvae.h, "Scaffold SMILES"): (ds_scaf, rows) -- a
+        ``MosesDeviceDataset`` on the same device holding the scaffold, in canonical spelling, of every corpus row that has one
+        (``scaffold_smiles_status`` 0), in corpus order and without empty rows, and rows int64 [M], the corpus row of each.  From ONE
+        ``mvae_smiles_scaffold_smiles_corpus`` launch over all rows, its gapped CSR compacted on the device.  ``ds_scaf.n_distinct`` is
+        the exact number of distinct scaffold structures -- token rows are compared, no hash decides -- where ``scaffold_histogram()``
+        counts keys; ``ds_scaf.smiles(i)`` shows one, ``ds_scaf.lookup`` finds one (ask with ``VAE.scaffold_smiles`` rows).  NOT rdkit's
+        MurckoScaffoldSmiles: nothing is sanitised, no aromaticity perception, and a row with a stereo token has no scaffold.  Cached;
+        the host waits for M and for the row lengths.  ValueError for a vocabulary of more than 64 ids."""
+        if self._scaffold_smiles is None:
+            from . import ops
+            from .vocab import smiles_emit_table
+            tok, chem = self._fp_tables("scaffold_smiles")
+            dev, n = self.device, self.n
+            counts = torch.zeros(ops.REWRITE_COUNTS, dtype=torch.int32, device=dev)
+            tokens_out, offsets_out, status, _ = ops.smiles_scaffold_smiles_corpus(
+                self.tokens, self.offsets, n, torch.arange(n, dtype=torch.long, device=dev), tok, chem, smiles_emit_table(self.vocab).to(dev),
+                127, 127, info=False, counts=counts)
+            rows = torch.nonzero(status == 0).flatten()
+            self._scaffold_smiles = (self._compacted(tokens_out, offsets_out, rows), rows, status, counts)
+        return self._scaffold_smiles[:2]
+
+    @property
+    def scaffold_smiles_status(self):
+        """The status of every corpus row under ``scaffold_smiles()``: int32 [N] on the device, the codes of
+        ``ops.SCAFFOLD_SMILES_STATUS_NAMES`` (0: the row has a scaffold there; 14: it has no ring)."""
+        self.scaffold_smiles()
+        return self._scaffold_smiles[2]
+
+    @property
+    def scaffold_smiles_counts(self):
+        """How many corpus rows have each ``scaffold_smiles_status``: int32 [16] on the device, kept by the kernel's integer atomic adds."""
+        self.scaffold_smiles()
+        return self._scaffold_smiles[3]
 
     def _substructures(self, who, patterns, max_steps, counts=None):
         from . import ops
@@ -837,6 +883,39 @@ def canonical_smiles(strings, vocab, device="cuda", return_status=False):
     out, out_len, status = out.cpu().numpy(), out_len.cpu().numpy(), status.cpu().numpy()
     table = np.array([vocab.i2c[i] for i in range(len(vocab))], dtype=object)
     res = [s if st else "".join(table[row[1:k - 1]]) for s, row, k, st in zip(strings, out, out_len, status)]
+    return (res, status) if return_status else res
+
+
+def scaffold_smiles(strings, vocab, device="cuda", return_status=False):
+    """The Murcko scaffold of every string as a string (include/mvae.h, "Scaffold SMILES"): the scaffold atoms of ``scaffolds``, every
+    lost bond turned into hydrogens, in the spelling of ``canonical_smiles`` -- "" where there is no scaffold (no ring, a stereo token,
+    a string the walk refuses).  NOT rdkit's MurckoScaffoldSmiles: nothing is sanitised, no aromaticity perception, no stereo.
+    ``return_status=True`` also returns the int32 [len(strings)] statuses (ops.SCAFFOLD_SMILES_STATUS_NAMES).  One
+    mvae_smiles_scaffold_smiles_rows launch on ``device``; ``device="cpu"`` asks for the host entry instead (the same source compiled
+    for the CPU).  ValueError for a vocabulary of more than 64 ids or no strings."""
+    from . import ops
+    from .vocab import smiles_token_table, smiles_chem_table, smiles_emit_table
+    strings = list(strings)
+    if not strings:
+        raise ValueError("scaffold_smiles: needs at least one string")
+    if len(vocab) > 64:
+        raise ValueError(f"scaffold_smiles: the vocabulary has {len(vocab)} ids, at most 64 are supported")
+    dev = torch.device(device)
+    ids = [vocab.string2ids(s, add_bos=True, add_eos=True) for s in strings]
+    x = torch.full((len(ids), max(map(len, ids))), vocab.pad, dtype=torch.long)
+    for b, row in enumerate(ids):
+        x[b, :len(row)] = torch.as_tensor(row)
+    tables = (smiles_token_table(vocab), smiles_chem_table(vocab), smiles_emit_table(vocab))
+    if dev.type == "cpu":
+        out, out_len, status, _ = ops.smiles_scaffold_smiles_host(x, *tables, vocab.bos, vocab.eos, vocab.pad, info=False)
+    else:
+        from .models import _require_cuda
+        _require_cuda(dev, "data.scaffold_smiles")
+        out, out_len, status, _ = ops.smiles_scaffold_smiles_rows(x.to(dev), *(t.to(dev) for t in tables), vocab.bos, vocab.eos, vocab.pad,
+                                                                  info=False)
+    out, out_len, status = out.cpu().numpy(), out_len.cpu().numpy(), status.cpu().numpy()
+    table = np.array([vocab.i2c[i] for i in range(len(vocab))], dtype=object)
+    res = ["".join(table[row[1:k - 1]]) for row, k in zip(out, out_len)]
     return (res, status) if return_status else res
 
 

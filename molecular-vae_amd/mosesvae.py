@@ -565,6 +565,25 @@ class VAE(_SavedState, nn.Module):
         extra["rank"] = rank
         return rows, status, extra
 
+    @torch.no_grad()
+    def scaffold_smiles(self, x, max_content=127):
+        """The Murcko scaffold of token rows x (what ``syntax_valid`` takes) as token rows on the device, one
+        mvae_smiles_scaffold_smiles_rows launch, no host wait: (out int64 [B, max(T, max_content + 2)] -- <bos>, the scaffold's tokens,
+        <eos>, <pad> --, out_len int32 [B], status int32 [B], ops.SCAFFOLD_SMILES_STATUS_NAMES).  The scaffold atoms of ``scaffolds``
+        with every lost bond turned into hydrogens, in the spelling of ``canonical`` (include/mvae.h, "Scaffold SMILES"): rows that can
+        be shown, handed to ``data.compile_substructures`` once decoded, and compared exactly.  A row without a scaffold (status != 0:
+        ``canonical``'s reasons, or 14: no ring) is the EMPTY row <bos> <eos> with out_len 2, never a copy.  NOT rdkit's
+        MurckoScaffoldSmiles: nothing is sanitised, no aromaticity perception, no stereo.  ValueError for a vocabulary of more than 64 ids."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.scaffold_smiles")
+        if len(self.vocabulary) > 64:
+            raise ValueError(f"scaffold_smiles: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
+        x = self._rows(x, "scaffold_smiles", dev)
+        out, out_len, status, _ = ops.smiles_scaffold_smiles_rows(x, self._smiles_table(dev), self._smiles_chem_table(dev),
+                                                                  self._smiles_emit_table(dev), self.bos, self.eos, self.pad, max_content,
+                                                                  info=False)
+        return out, out_len, status
+
     def _substructure_words(self, x, table, max_steps=65536, map_query=None):
         """(status, hit, undecided[, map]) of one mvae_smiles_substruct_rows launch over token rows x on the device; table: a
         ``data.SubstructureTable``."""

@@ -1068,6 +1068,42 @@ def smiles_canon_corpus(tokens, offsets, N, rows, tok_info, chem_info, emit, max
                           (tokens_out, offsets_out, status, info, rank), counts, err)
 
 
+SMILES_STATUS_NO_RING = 14                    # include/mvae.h: MVAE_SMILES_NO_RING, given by the scaffold SMILES entries only
+SCAFFOLD_SMILES_STATUS_NAMES = REWRITE_STATUS_NAMES + ("no_ring",)
+SCAFFOLD_SMILES_INFO = ("atoms", "bonds", "new_brackets", "lost")      # the columns of info [*, 4] (MVAE_SCAFFOLD_SMILES_INFO)
+_SCAFFOLD_SMILES_OUT = ((torch.int32, (len(SCAFFOLD_SMILES_INFO),), True),)
+
+
+def smiles_scaffold_smiles_rows(x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content=127, T_out=None, out=None, out_len=None,
+                                status=None, info=None, counts=None):
+    """The Murcko scaffold of token rows x (int64 [B, T], bos first) as token rows, on the device: (out int64 [B, T_out], out_len int32
+    [B], status int32 [B], info int32 [B, 4]) -- the scaffold atom set of ``smiles_scaffold_rows`` cut out of the row's graph, every lost
+    bond turned into hydrogens, in the spelling of ``smiles_canon_rows`` (include/mvae.h, "Scaffold SMILES").  A row without a scaffold
+    (status != 0, ``SCAFFOLD_SMILES_STATUS_NAMES``: the canon entries' reasons, or 14 "no_ring") gets the EMPTY row bos, eos, pad..., and
+    out_len 2 -- never a copy.  info = atoms and bonds of the scaffold, atoms that became bracket atoms, bond orders lost
+    (``SCAFFOLD_SMILES_INFO``); ``info=False``: not written (None in its place).  NOT rdkit's MurckoScaffoldSmiles: nothing is sanitised,
+    no aromaticity perception, no stereo.  One launch (mvae_smiles_scaffold_smiles_rows)."""
+    return _writer_rows("mvae_smiles_scaffold_smiles_rows", False, x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, (), max_content, T_out,
+                        _SCAFFOLD_SMILES_OUT, (out, out_len, status, info), counts)
+
+
+def smiles_scaffold_smiles_host(x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content=127, T_out=None, out=None, out_len=None,
+                                status=None, info=None):
+    """smiles_scaffold_smiles_rows on HOST tensors: the same source compiled for the CPU, a plain loop over the rows
+    (mvae_smiles_scaffold_smiles_host) -- for tests and for machines without a device; not a fallback of the device entries."""
+    return _writer_rows("mvae_smiles_scaffold_smiles_host", True, x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, (), max_content, T_out,
+                        _SCAFFOLD_SMILES_OUT, (out, out_len, status, info), None)
+
+
+def smiles_scaffold_smiles_corpus(tokens, offsets, N, rows, tok_info, chem_info, emit, max_content=127, stride=None, tokens_out=None,
+                                  offsets_out=None, status=None, info=None, counts=None, err=None):
+    """smiles_scaffold_smiles_rows over the rows `rows` (int64 [B]) of the CSR corpus, one launch (mvae_smiles_scaffold_smiles_corpus):
+    (tokens_out uint8 [B, stride], offsets_out int64 [2 B + 1], status int32 [B], info int32 [B, 4]) in the gapped CSR layout of
+    ``smiles_rewrite_corpus``, with its counts and err; a row without a scaffold is a slice of length 0."""
+    return _writer_corpus("mvae_smiles_scaffold_smiles_corpus", tokens, offsets, N, rows, tok_info, chem_info, emit, (), max_content, stride,
+                          _SCAFFOLD_SMILES_OUT, (tokens_out, offsets_out, status, info), counts, err)
+
+
 SUBSTRUCT_QATOMS = 32                         # include/mvae.h: MVAE_SUBSTRUCT_QATOMS, the atoms of a query and the columns of `map`
 SUBSTRUCT_QUERIES = 64                        # MVAE_SUBSTRUCT_QUERIES, the queries of one launch: one bit of an int64 each
 SUBSTRUCT_WORDS = 100                         # MVAE_SUBSTRUCT_WORDS, the int32 words of one compiled query

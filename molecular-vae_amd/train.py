@@ -801,7 +801,8 @@ def moses_reconstruction(model, batches, beam_width=1, max_len=100, syntax=False
 @torch.no_grad()
 def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top_k=None, top_p=None, seed=0, z=None, syntax=False,
                    count_valid=False, novel_against=None, prefix=None, nearest=False, valence=False,
-                   int_div=False, snn=False, scaffolds=False, kekule=False, canonical=False, filters=None, filter_steps=65536):
+                   int_div=False, snn=False, scaffolds=False, kekule=False, canonical=False, filters=None, filter_steps=65536,
+                   top_scaffolds=0):
     """The reference's generation pipeline (``hugesample.py``: sample in batches, hash the strings, count unique / total) with the hashing
     and the deduplication on the device: ``n_samples`` sequences from a ``mosesvae.VAE`` in batches of ``batch_size`` (the last one shorter),
     batch j with seed ``seed + j`` and ``temp`` / ``top_k`` / ``top_p`` as ``VAE.sample`` takes them.  ``z`` None draws each batch's latents
@@ -897,7 +898,15 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     the result gains ``filter_statistics``' three values over the valence-consistent samples, duplicates included (those "chem_valid"
     counts): "filters", the share of them with no hit and no undecided bit (NaN for none); "filter_hits" and "filter_undecided", per
     pattern, how many contain it and on how many the search ran out of steps.  Without ``filters`` the launches and the keys of the
-    result are what they were."""
+    result are what they were.
+    ``top_scaffolds=k`` (k >= 1 needs ``scaffolds=True``; ValueError otherwise, and for max_len > 129, before any device work): the
+    scaffolds the model produces most, as strings -- ``VAE.scaffold_smiles`` (include/mvae.h, "Scaffold SMILES"; NOT rdkit's
+    MurckoScaffoldSmiles).  Each batch's NEW rows go through one ``mvae_smiles_scaffold_smiles_rows`` launch, no further host wait, and
+    the result gains "top_scaffolds": a list of at most k (string, count), the most frequent scaffold token rows among the samples that
+    have one, every drawn sample counting (each distinct sample weighted by its "counts"), by descending count; equal counts by the
+    smaller token row (<bos>, the ids, <eos>, <pad>, compared left to right).  Scaffolds are compared on tokens, exactly: two keys of
+    "n_scaffolds" are never merged here and one key may be several strings.  The default 0 leaves the launches and the keys of the
+    result what they were."""
     n_samples, batch_size, max_len = int(n_samples), int(batch_size), int(max_len)
     if n_samples < 1 or batch_size < 1 or max_len < 1:
         raise ValueError(f"moses_generate: n_samples, batch_size and max_len must be >= 1, got {n_samples}, {batch_size}, {max_len}")
@@ -935,6 +944,14 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         raise ValueError(f"moses_generate: scaffolds=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
     if kekule and len(model.vocabulary) > 64:
         raise ValueError(f"moses_generate: kekule=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
+    top_scaffolds = int(top_scaffolds)
+    if top_scaffolds < 0:
+        raise ValueError(f"moses_generate: top_scaffolds must be >= 0, got {top_scaffolds}")
+    if top_scaffolds:
+        if not scaffolds:
+            raise ValueError("moses_generate: top_scaffolds needs scaffolds=True")
+        if max_len > 129:
+            raise ValueError(f"moses_generate: top_scaffolds supports max_len <= 129, got {max_len}")
     if canonical:
         if len(model.vocabulary) > 64:
             raise ValueError(f"moses_generate: canonical=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
@@ -966,6 +983,7 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     n_fp = torch.zeros((), dtype=i64, device=dev) if int_div or snn else None
     snn_sum = torch.zeros((), dtype=torch.float64, device=dev) if snn else None
     scafs = []                                                  # (molecule key, scaffold key, scaffold atoms) of each new sample, likewise
+    scaf_rows = []                                              # (scaffold row [*, 129], status) of each new sample, likewise
     keks = []                                                   # (status, deficiency) of each new sample under the kekule entry, likewise
     n_kek = torch.zeros(3, dtype=i64, device=dev) if kekule else None        # status 0: all samples, distinct ones, distinct and novel
     kek_counts = torch.zeros(8, dtype=i64, device=dev) if kekule else None
@@ -1057,6 +1075,9 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
             if scaffolds:
                 sc = model.scaffolds(x[sel])
                 scafs.append((sc["mol_key"], sc["scaffold_key"], sc["atoms"]))
+                if top_scaffolds:
+                    s_rows, _, s_status = model.scaffold_smiles(x[sel])      # 129 columns, as the canonical rows below
+                    scaf_rows.append((s_rows, s_status))
             if kekule:
                 keks.append((kek["status"][sel], kek["deficiency"][sel]))
             if canonical:
@@ -1112,6 +1133,16 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
             res["scaf"] = float(ops.histogram_cosine(sk, sc_counts, ck, cc))
             res["scaffold_novel"] = int((~ops.keys_in(ck, sk)).sum())
             res["graph_novel"] = int((~ops.keys_in(novel_against.mol_keys_sorted(), graphs)).sum())
+        if top_scaffolds:
+            s_rows = torch.cat([c[0] for c in scaf_rows]) if scaf_rows else torch.empty((0, 129), dtype=i64, device=dev)
+            fine = torch.cat([c[1] for c in scaf_rows]) == 0 if scaf_rows else torch.empty(0, dtype=torch.bool, device=dev)
+            # unique sorts the rows ascending and the sort below is stable: equal counts stay in the order of the token rows
+            distinct, inverse = torch.unique(s_rows[fine], dim=0, return_inverse=True)
+            drawn = torch.zeros(distinct.shape[0], dtype=i64, device=dev).index_add_(0, inverse, counts[fine])
+            best = torch.sort(drawn, descending=True, stable=True)[1][:top_scaffolds]
+            v = model.vocabulary
+            res["top_scaffolds"] = [(v.ids2string(r[:r.index(v.eos) + 1], rem_bos=True, rem_eos=True), c)
+                                    for r, c in zip(distinct[best].tolist(), drawn[best].tolist())]
     if kekule:
         n_kek = n_kek.tolist()
         res["kekule_valid"], res["kekule_valid_unique"] = n_kek[0], n_kek[1]
