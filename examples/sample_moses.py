@@ -29,6 +29,9 @@ are one graph) and, with ``--novel_against``, the MOSES Scaf figure -- the cosin
 histograms --, the scaffolds and the graphs absent from the corpus; at the end the five most frequent generated scaffolds, each with a
 sample that has it and one training molecule that has it (``MosesDeviceDataset.rows_with_scaffold``).  The scaffold is the rings, the
 linkers between them and the atoms double-bonded to either, on the graph of the SMILES graph walk: not rdkit's MurckoScaffold.
+``--fragments`` prints, for each round, the distinct fragments among the samples (``mv.moses_generate(fragments=True)``: every molecule
+cut at its ring substituent bonds and its acyl-heteroatom bonds -- this library's own rule, not BRICS and not RECAP) and, with
+``--novel_against``, the MOSES Frag figure: the cosine similarity of the generated and the training fragment histograms.
 ``--top_scaffolds K`` (with ``--scaffolds``) also prints each round's K most frequent scaffolds as SMILES, with the samples drawn
 (``mv.moses_generate(top_scaffolds=K)``: ``VAE.scaffold_smiles``, lost substituents turned into hydrogens, this library's canonical
 spelling -- not rdkit's MurckoScaffoldSmiles: nothing is sanitised, no aromaticity perception, no stereo).
@@ -94,6 +97,8 @@ ap.add_argument("--kekule", action="store_true", help="count the kekulisable sam
                                                       "their ring double bond)")
 ap.add_argument("--respell", default=0, type=int, metavar="N", help="at the end print N randomised spellings (VAE.respell) of each of the first "
                                                                    "five unique samples the walk accepts")
+ap.add_argument("--fragments", action="store_true", help="print each round's distinct fragments (this library's own cut rule, not BRICS) and, "
+                                                         "with --novel_against, the Frag figure")
 ap.add_argument("--top_scaffolds", type=int, default=0, help="with --scaffolds: print each round's K most frequent scaffolds as SMILES "
                                                              "(this library's scaffold SMILES, not rdkit's MurckoScaffoldSmiles)")
 ap.add_argument("--canonical", action="store_true", help="print each round's distinct canonical spellings (unique@k on graphs) and, with "
@@ -171,7 +176,7 @@ with open(args.log, "w", buffering=1) as f:
                                 top_p=args.top_p, seed=args.seed + r * args.batches_per_round, syntax=args.syntax, count_valid=True,
                                 novel_against=corpus, prefix=args.prefix, nearest=args.nearest, valence=args.valence,
                                 int_div=args.int_div, snn=args.snn, scaffolds=args.scaffolds, kekule=args.kekule, canonical=args.canonical,
-                                filters=filters, top_scaffolds=args.top_scaffolds if args.scaffolds else 0)
+                                filters=filters, top_scaffolds=args.top_scaffolds if args.scaffolds else 0, fragments=args.fragments)
         total += res["total"]
         if args.kekule:
             kekule_valid += res["kekule_valid"]
@@ -207,6 +212,9 @@ with open(args.log, "w", buffering=1) as f:
               + (f", IntDiv of this round's {res['n_fingerprinted']} valence-consistent unique samples {res['int_div']:.4f}" if args.int_div else "")
               + (f", SNN {res['snn']:.4f}" if args.snn else "")
               + (f", this round's distinct graphs {res['unique_graphs']} and scaffolds {res['n_scaffolds']}" if args.scaffolds else "")
+              + (f", this round's distinct fragments {res['n_fragments']} (samples of more than 16 fragments: {res['fragment_many']})"
+                 if args.fragments else "")
+              + (f", Frag {res['frag']:.4f}" if args.fragments and corpus is not None else "")
               + (f", Scaf {res['scaf']:.4f}, scaffolds not in the corpus {res['scaffold_novel']}, graphs not in the corpus {res['graph_novel']}"
                  if args.scaffolds and corpus is not None else "")
               + (f", this round's distinct canonical spellings {res['unique_canonical']} of {res['canonical_status_counts'][0]} written"

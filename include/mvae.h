@@ -1266,6 +1266,85 @@ int mvae_smiles_scaffold_smiles_host(int B, int T, int V, const int64_t* x, int6
                                      int32_t* status /* [B] */, int32_t* info /* [B, 4] or NULL */);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Fragments (an addition: a ninth consumer of the "SMILES graph" walk above, and the fourth family that writes a string).  A row cut
+ * into pieces at its ring substituent bonds and its acyl-heteroatom bonds; every piece gets the graph key of "Graph key" and can be
+ * written as a token row.  The fragment histogram of a set of rows is what the MOSES Frag figure compares.
+ * What this is NOT: it is this library's own rule -- not BRICS, not RECAP, not rdkit's fragmenters --, and agreement with any toolkit is
+ *   neither tested nor claimed.  No dummy atoms mark the cut ends.  It is defined on the graph exactly as the walk builds it: explicit [H]
+ *   are atoms, ring-closure bonds are order 1, nothing is kekulised or sanitised, no aromaticity is perceived, stereo carries nothing.
+ * Where a row is cut.  G is the walk's graph of a valence-consistent row, deg(a) the number of bonds of atom a in G.  A bond a - b is
+ *   cut iff all of these hold:
+ *   1. its recorded order is 1 (a closure is a ring bond and is never cut);
+ *   2. it is not a ring bond ("Murcko scaffold"): it is a bridge, and every bridge is a tree bond;
+ *   3. deg(a) >= 2 and deg(b) >= 2: a terminal atom -- a methyl, a halogen, a hydroxyl -- is never cut off;
+ *   4. at least one of
+ *      R (ring rule): a or b is a ring atom;
+ *      A (acyl rule): one end is a non-ring atom with a double bond to an O or S atom of degree 1, and the other end is an N, O or S
+ *        atom (amide, ester, carbamate, urea, sulfonamide, phosphate ester).
+ * What comes out.  The fragments are the connected components of G without the cut bonds, numbered by their lowest atom in string order;
+ *   a row with c cut bonds has c + 1 of them.
+ *   Fragment key: the "Graph key" of the fragment's atom set U with its induced bonds, exactly as the scaffold key is made:
+ *     w_U(a) = elem | arom << 4 | (charge + 1) << 5 | in_ring << 7 | deg_U(a) << 8, no used valence; ring membership and ring bonds are
+ *     those of the whole row.  No new hash.  A benzene ring cut out of any row has the scaffold key of benzene.
+ *   Fragment SMILES: the row's graph cut down to U, every lost bond turned into a hydrogen of the atom that lost it as "Scaffold SMILES"
+ *     defines (h_U = h_row + lost), in the spelling of "SMILES canon", with that section's claim and limit.
+ *   CC(=O)Oc1ccccc1C(=O)O: 3 cuts (C-O of the ester by rule A alone), 4 fragments CC=O, O, c1ccccc1, O=CO.  Cc1ccccc1, CCOCC: no cut.
+ *   c1ccccc1c1ccccc1: 1 cut, c1ccccc1 twice.  CC(=O)NC: 1 cut by rule A alone, CC=O and CN.  CCn1cccc1: 1 cut, CC and c1cc[nH]c1.
+ * mvae_smiles_fragment_rows / _corpus / _host: the inputs of mvae_smiles_scaffold_rows / _corpus / _host.  Outputs, per row, with
+ *   F = MVAE_FRAGMENT_MAX = 16: status int32 [B]; mask int64 [B, F, 2] (optional, may be NULL): bit a of word a >> 6 of slot f = atom a is
+ *   in fragment f; desc int32 [B, MVAE_FRAGMENT_DESC = 4] = fragments, cut bonds, cut bonds that rule A alone cuts, atoms of the largest
+ *   fragment; key int64 [B, F] = the fragment keys, 0 in the unused slots.  Every element of the given outputs is written, nothing else is.
+ *   Status: 0 - 6 as the graph entries give it, and a row with status other than 0 gets zeros everywhere -- except
+ *   15 MVAE_SMILES_FRAG_MANY: a row the walk gives 0 that has more than F fragments.  Its mask and key are all zeros and its desc holds
+ *   the true four counts: nothing is silently truncated.
+ *   One thread per row; MVAE_FRAGMENT_LDS_BYTES = 81920 B (80 KiB) of LDS per 64-row block, the scaffold entry's arrays with nothing
+ *   added.  The refinement rounds run once per row over all atoms with the cut bonds left out -- no bond joins two fragments, so every
+ *   atom ends with the id a run over its fragment alone would give it -- and one walk along each fragment's atoms sums them into its key.
+ *   Refused before anything is enqueued: what the scaffold entries refuse.
+ * mvae_smiles_fragment_smiles_rows / _corpus / _host take the arguments of mvae_smiles_scaffold_smiles_rows / _corpus / _host with
+ *   `int frag` in front of info, and write fragment number frag of every row in the same layouts.  A row whose status is not 0 gets the
+ *   EMPTY row, never a copy.  Status: 0: written.  1 - 6: the walk's refusals.  8 - 13: the rewrite's, with STEREO decided before the
+ *   cuts and 9 - 13 speaking of the fragment's spelling.  16 MVAE_SMILES_NO_FRAGMENT: a row the walk gives 0, without a stereo token, with
+ *   frag or fewer fragments.  There is no upper limit on frag here: a FRAG_MANY row has its 17th fragment written.  counts, where given,
+ *   is int32 [MVAE_FRAGMENT_SMILES_COUNTS = 32]: slot 16 counts NO_FRAGMENT (the writer families count status & 31; the others never
+ *   give a status above 14, so their int32 [16] stands).  info int32 [B, MVAE_FRAGMENT_SMILES_INFO = 4] (optional) = atoms and bonds of
+ *   the fragment, atoms that became bracket atoms, the sum of lost(a) -- for status 0 and 9 - 13, zeros otherwise.
+ *   MVAE_FRAGMENT_SMILES_LDS_BYTES = 81920 B per 64-row block, the rewrite's block with nothing added; the cut set and the labels are
+ *   the code of the keys entry.  Refused before anything is enqueued: what the scaffold SMILES entries refuse, and frag < 0.
+ */
+#define MVAE_FRAGMENT_MAX 16
+#define MVAE_FRAGMENT_DESC 4
+#define MVAE_FRAGMENT_LDS_BYTES 81920
+#define MVAE_SMILES_FRAG_MANY 15
+#define MVAE_SMILES_NO_FRAGMENT 16
+#define MVAE_FRAGMENT_SMILES_INFO 4
+#define MVAE_FRAGMENT_SMILES_COUNTS 32
+#define MVAE_FRAGMENT_SMILES_LDS_BYTES 81920
+int mvae_smiles_fragment_rows(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */,
+                              const int32_t* chem_info /* [V] */, int eos_id, int32_t* status /* [B] */, int64_t* mask /* [B, 16, 2] or NULL */,
+                              int32_t* desc /* [B, 4] */, int64_t* key /* [B, 16] */, void* stream);
+int mvae_smiles_fragment_corpus(const uint8_t* tokens, const int64_t* offsets /* [N + 1] */, int64_t N, int V, const int32_t* tok_info /* [V] */,
+                                const int32_t* chem_info /* [V] */, int32_t* status /* [N] */, int64_t* mask /* [N, 16, 2] or NULL */,
+                                int32_t* desc /* [N, 4] */, int64_t* key /* [N, 16] */, void* stream);
+int mvae_smiles_fragment_host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */,
+                              const int32_t* chem_info /* [V] */, int eos_id, int32_t* status /* [B] */, int64_t* mask /* [B, 16, 2] or NULL */,
+                              int32_t* desc /* [B, 4] */, int64_t* key /* [B, 16] */);
+int mvae_smiles_fragment_smiles_rows(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */,
+                                     const int32_t* chem_info /* [V] */, const int32_t* emit /* [48] */, int bos_id, int eos_id, int pad_id,
+                                     int max_content, int T_out, int64_t* out /* [B, T_out] */, int32_t* out_len /* [B] */,
+                                     int32_t* status /* [B] */, int32_t* counts /* [32] or NULL */, int frag, int32_t* info /* [B, 4] or NULL */,
+                                     void* stream);
+int mvae_smiles_fragment_smiles_corpus(const uint8_t* tokens, const int64_t* offsets /* [N + 1] */, int64_t N, const int64_t* rows /* [B] */,
+                                       int B, int V, const int32_t* tok_info /* [V] */, const int32_t* chem_info /* [V] */,
+                                       const int32_t* emit /* [48] */, int max_content, int stride, uint8_t* tokens_out /* [B, stride] */,
+                                       int64_t* offsets_out /* [2 B + 1] */, int32_t* status /* [B] */, int32_t* counts /* [32] or NULL */,
+                                       int32_t* err /* [1] or NULL */, int frag, int32_t* info /* [B, 4] or NULL */, void* stream);
+int mvae_smiles_fragment_smiles_host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */,
+                                     const int32_t* chem_info /* [V] */, const int32_t* emit /* [48] */, int bos_id, int eos_id, int pad_id,
+                                     int max_content, int T_out, int64_t* out /* [B, T_out] */, int32_t* out_len /* [B] */,
+                                     int32_t* status /* [B] */, int frag, int32_t* info /* [B, 4] or NULL */);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Tanimoto similarity of fingerprints (an addition: the structure-aware counterpart of mvae_latent_knn and mvae_edit_knn).  Fingerprints
  * are dense rows of MVAE_FP_WORDS int64 words, 16-byte aligned (else MVAE_ERR_INVALID); any 1024-bit rows will do.
  * Similarity.  T(a, b) = c / (p_a + p_b - c), with p the popcounts and c the popcount of a AND b; T is 0 when the union is empty.  T is

@@ -6,64 +6,24 @@
 // kernels' bodies, the launches and the host loop.  This file is the graph producer between the walk and the writer, and nothing else:
 //   rew::read            the walk and the stereo test (smiles_writer.hpp)
 //   scf::scaffold_sets   S as a mask in registers, from the atom words and the ring mask (scaffold_sets.hpp, shared with scaffold.hip)
-//   cut                  the atom words and the closure pairs of S moved down to 0 .. |S| - 1 in increasing atom order, in place: the
-//                        new number of atom k is the members of S below k (a popcount), never more than k
+//   ssm::cut             the atom words and the closure pairs of S moved down to 0 .. |S| - 1 in increasing atom order, in place: the
+//                        new number of atom k is the members of S below k (a popcount), never more than k (smiles_cut.hpp, shared
+//                        with fragment_smiles.hip)
 //   rew::adjacency       on the cut arrays: it leaves used valence - bond sum in the hydrogen field, which for a bracket atom is h_S
 //                        already and for an unbracketed one is lost(a)
-//   hydrogens            an unbracketed atom stays one iff the implicit rule on its bond sum in G_S (the adjacency's P) gives h_S
+//   ssm::hydrogens       an unbracketed atom stays one iff the implicit rule on its bond sum in G_S (the adjacency's P) gives h_S
 //   can::ranks, rew::write   unchanged (smiles_canon.hpp)
 // One thread per row, 64-thread blocks, the rewrite's 80 KiB of LDS per block (rew::Lds) with nothing added.  No runtime-indexed private
 // array, no recursion; every loop is bounded by n <= 127 and every index goes through a slot mask.
 #include "common.hpp"
 #include "scaffold_sets.hpp"
 #include "smiles_canon.hpp"
+#include "smiles_cut.hpp"
 #include "smiles_writer.hpp"
 
 namespace ssm {
 
 enum : int { NO_RING = MVAE_SMILES_NO_RING };
-
-// the members of m below atom k
-SMI_HD int below(const smg::Mask& m, int k) {
-  return k < 64 ? smg::popcount64(m.lo & ((1ull << (k & 63)) - 1ull)) : smg::popcount64(m.lo) + smg::popcount64(m.hi & ((1ull << (k & 63)) - 1ull));
-}
-
-// W and C cut down to the atoms of s.  A kept atom whose predecessor is dropped gets NONE, which the adjacency skips; a closure joins
-// two ring atoms, and those are in s.  Returns |s|; *lost = the sum of the orders of the bonds with one end in s.
-template <class Words, class Clos>
-SMI_HD int cut(Words& W, Clos& C, int n, int nclos, const smg::Mask& s, int* lost) {
-  int m = 0, gone = 0;
-  for (int k = 0; k < n; ++k) {
-    const uint32_t w = W.get(k);
-    const int p = k ? smg::a_pred(w) : rew::NONE;
-    const bool in = smg::m_get(s, k), p_in = p != rew::NONE && smg::m_get(s, p);
-    if (p != rew::NONE && in != p_in) gone += (int)(w >> 24) & 3;
-    if (in) W.set(m++, (w & ~0xFFu) | (uint32_t)(p_in ? below(s, p) : rew::NONE));
-  }
-  for (int c = 0; c < nclos; ++c) {
-    const int pr = C.get(c);
-    C.set(c, (uint16_t)(below(s, pr & 0xFF) | below(s, pr >> 8) << 8));
-  }
-  *lost = gone;
-  return m;
-}
-
-// The hydrogens of the unbracketed atoms behind the adjacency, which left lost(a) in the hydrogen field and the bond sums of G_S in P.
-// Returns the atoms that became bracket atoms.
-template <class Words, class Bytes>
-SMI_HD int hydrogens(Words& W, Bytes& P, int m) {
-  int made = 0;
-  for (int k = 0; k < m; ++k) {
-    const uint32_t w = W.get(k);
-    if (smg::a_brk(w)) continue;
-    const int gone = rew::w_hyd(w), sum = P.get(k), e = smg::a_elem(w), ar = smg::a_arom(w);
-    const int h = smg::implicit_h(e, ar, sum + gone) + gone;
-    const uint32_t bare = w & ~(0xFu << 8);
-    if (smg::implicit_h(e, ar, sum) == h) W.set(k, bare);
-    else { W.set(k, bare | (uint32_t)(h & 0xF) << 8 | 1u << 21); ++made; }
-  }
-  return made;
-}
 
 // The family the writer driver runs.  info [B, 4] may be NULL; it is written in full.
 struct ScaffoldSmiles {
@@ -84,9 +44,9 @@ struct ScaffoldSmiles {
     if (st == smg::OK && !(rec.ring.lo | rec.ring.hi)) st = NO_RING;
     int m = 0, bonds = 0, made = 0, lost = 0;
     if (st == smg::OK) {
-      const int nclos = rec.nclos < fpr::CLOSURES ? rec.nclos : fpr::CLOSURES;
+      int nclos = rec.nclos < fpr::CLOSURES ? rec.nclos : fpr::CLOSURES;
       const scf::Sets sets = scf::scaffold_sets(s.W, rec.n, rec.ring);
-      m = cut(s.W, s.C, rec.n, nclos, sets.s, &lost);
+      m = cut<false>(s.W, s.C, rec.n, &nclos, sets.s, &lost);
       rew::adjacency(s.W, s.C, s.A, s.S, s.D, s.P, m, nclos);
       bonds = s.S.get(m) >> 1;
       made = hydrogens(s.W, s.P, m);

@@ -3,7 +3,7 @@
 // For all of them: lane-minor LDS storage for everything indexed by a run-time atom number (and its host twin), the two token sources, how
 // a CSR row is read, and the row driver -- rows_kernel<C> / corpus_kernel<C> and the host side rows<C> / corpus<C> / host<C> -- which is
 // the one place that maps a row to a thread and refuses arguments before a launch (smiles_graph.hip, fingerprint.hip, scaffold.hip,
-// kekule.hip).  smiles_rewrite.hip and smiles_canon.hip copy out block-wide after their rows: theirs is the writer driver of
+// kekule.hip, fragment.hip).  smiles_rewrite.hip and smiles_canon.hip copy out block-wide after their rows: theirs is the writer driver of
 // smiles_writer.hpp, built the same way on the same storage types.  Definitions: include/mvae.h, "Circular fingerprint".
 #pragma once
 #include <limits.h>

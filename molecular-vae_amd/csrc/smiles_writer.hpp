@@ -354,6 +354,8 @@ inline bool rows_args_ok(int B, int T, int V, const int64_t* x, int64_t x_ld, co
 //   R::skipped(b, args)   what a corpus row whose id is outside [0, N) leaves in the family's own outputs
 // Each family keeps two __global__ kernels of its own name whose bodies are one call of block_rows<R> / block_corpus<R>, and three
 // entries that are one call of rows / corpus / host<R>.
+// counts, where given, is the histogram of status & 31: int32 [16] serves the families whose statuses end at 14, the fragment family
+// (fragment_smiles.hip), whose NO_FRAGMENT is 16, takes int32 [32].
 // The rows are staged in LDS and copied out by the whole block behind a barrier, row r by all 64 lanes over consecutive columns (a row
 // with len == COPY: the first keep columns of its source).  That read of the staging area has lanes 64 bytes apart (a 16-way bank
 // conflict); it is two or three instructions per row against the several thousand of the search.
@@ -372,7 +374,7 @@ __device__ __forceinline__ void block_rows(Lds& lds, int B, int T, int V, const 
     if (len == COPY) keep = copy_len(src, T, eos_id);
     status[b] = st;
     out_len[b] = len == COPY ? keep : len + 2;
-    if (counts) atomicAdd(counts + (st & 15), 1);
+    if (counts) atomicAdd(counts + (st & 31), 1);
   }
   __syncthreads();
   const int nrows = B - b0 < 64 ? B - b0 : 64;
@@ -423,7 +425,7 @@ __device__ __forceinline__ void block_corpus(Lds& lds, const uint8_t* __restrict
     offsets_out[2 * (long)b] = (long)b * stride;
     offsets_out[2 * (long)b + 1] = (long)b * stride + (len == COPY ? keep : len);
     if (b == B - 1) offsets_out[2 * (long)B] = (long)B * stride;
-    if (counts) atomicAdd(counts + (st & 15), 1);
+    if (counts) atomicAdd(counts + (st & 31), 1);
   }
   __syncthreads();
   const int nrows = B - b0 < 64 ? B - b0 : 64;

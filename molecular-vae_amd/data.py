@@ -231,6 +231,7 @@ class MosesDeviceDataset:
         self._scaffolds = self._scaffold_hist = self._scaffold_order = self._mol_keys = None     # scaffolds() and what is derived from it
         self._kekule = None
         self._canonical = None                                         # canonical(): (dataset, status, counts), computed on first use
+        self._fragments = self._fragment_hist = self._fragment_order = None      # fragments() and what is derived from it
         self._scaffold_smiles = None                                   # scaffold_smiles(): (dataset, rows, status, counts), likewise
 
     def __len__(self):
@@ -392,6 +393,56 @@ class MosesDeviceDataset:
             tok, chem = self._fp_tables("scaffolds")
             self._scaffolds = ops.scaffold_dict(*ops.smiles_scaffold_corpus(self.tokens, self.offsets, self.n, tok, chem))
         return self._scaffolds
+
+    def fragments(self):
+        """The fragments of every corpus row and their graph keys, in corpus order: ``VAE.fragments``' dict (status, mask, fragments,
+        cuts, acyl_cuts, largest, keys) on the device, from ONE ``mvae_smiles_fragment_corpus`` launch over the CSR rows.  This
+        library's own rule, not BRICS and not RECAP (include/mvae.h, "Fragments").  Cached; never waits for the device.  ValueError for
+        a vocabulary of more than 64 ids."""
+        if self._fragments is None:
+            from . import ops
+            tok, chem = self._fp_tables("fragments")
+            self._fragments = ops.fragment_dict(*ops.smiles_fragment_corpus(self.tokens, self.offsets, self.n, tok, chem))
+        return self._fragments
+
+    def fragment_histogram(self):
+        """(keys int64 [n], counts int64 [n]) on the device: the distinct fragment keys of the corpus, ascending, and how many fragments
+        have each, a fragment that occurs twice in a row counting twice (``ops.key_histogram`` over all 16 slots; the unused slots, the
+        rows that are not ok and the rows of more than 16 fragments hold 0 and are not counted).  Cached."""
+        if self._fragment_hist is None:
+            from . import ops
+            self._fragment_hist = ops.key_histogram(self.fragments()["keys"])
+        return self._fragment_hist
+
+    def rows_with_fragment(self, x):
+        """For each row of x (whatever ``lookup`` takes; ask with a fragment, such as a decoded ``VAE.fragment_smiles`` row), the corpus
+        rows that have a fragment with the key of its FIRST fragment: CSR ``(offsets int64 [Q + 1], rows int64 [offsets[-1]])`` on the
+        device, the rows of query i at ``rows[offsets[i] : offsets[i + 1]]``, ascending, a row that has the fragment twice listed once.
+        A query that is not ok gets none.  One fragment launch for x against the cached, sorted corpus keys; the one host wait is the
+        size of the answer."""
+        from . import ops
+        if len(self.vocab) > 64:
+            raise ValueError(f"rows_with_fragment: the vocabulary has {len(self.vocab)} ids, at most 64 are supported")
+        x = self._token_rows(x, "rows_with_fragment")
+        tok, chem = self._fp_tables("rows_with_fragment")
+        if self._fragment_order is None:
+            # (key, row) pairs of all slots, sorted by key then row, the repeats of a pair within a row dropped
+            keys = self.fragments()["keys"]
+            row = torch.arange(self.n, device=self.device).repeat_interleave(keys.shape[1])
+            ks, order = torch.sort(keys.reshape(-1), stable=True)
+            rs = row[order]
+            first = torch.ones_like(ks, dtype=torch.bool)
+            first[1:] = (ks[1:] != ks[:-1]) | (rs[1:] != rs[:-1])
+            self._fragment_order = (ks[first].contiguous(), rs[first].contiguous())
+        keys, order = self._fragment_order
+        q = ops.smiles_fragment_rows(x, tok, chem, self.vocab.eos, mask=False)[3][:, 0].contiguous()
+        lo = torch.searchsorted(keys, q)
+        n = torch.where(q != 0, torch.searchsorted(keys, q, right=True) - lo, torch.zeros_like(lo))
+        offsets = torch.zeros(q.shape[0] + 1, dtype=torch.long, device=self.device)
+        offsets[1:] = torch.cumsum(n, 0)
+        owner = torch.repeat_interleave(torch.arange(q.shape[0], device=self.device), n)
+        rows = order[lo[owner] + torch.arange(owner.shape[0], device=self.device) - offsets[owner]]
+        return offsets, rows
 
     def kekule(self):
         """The kekulisation test of every corpus row, in corpus order: {"status", "n_atoms", "n_bonds", "pairs", "deficiency": int32
@@ -917,6 +968,46 @@ def scaffold_smiles(strings, vocab, device="cuda", return_status=False):
     table = np.array([vocab.i2c[i] for i in range(len(vocab))], dtype=object)
     res = ["".join(table[row[1:k - 1]]) for row, k in zip(out, out_len)]
     return (res, status) if return_status else res
+
+
+def fragment_smiles(strings, vocab, device="cuda", return_status=False):
+    """The fragments of every string as strings (include/mvae.h, "Fragments"): a list, per string, of its fragments in the order of their
+    lowest atom, every lost bond turned into hydrogens, in the spelling of ``canonical_smiles`` -- [] for a string the walk refuses or
+    one with a stereo token.  This library's own rule: NOT BRICS, not RECAP.  ``return_status=True`` also returns the int32
+    [len(strings)] statuses of fragment 0 (ops.FRAGMENT_SMILES_STATUS_NAMES).  One mvae_smiles_fragment_rows launch for the counts and
+    one mvae_smiles_fragment_smiles_rows launch per fragment number up to the largest count among the strings, on ``device``;
+    ``device="cpu"`` asks for the host entries instead (the same source compiled for the CPU).  ValueError for a vocabulary of more
+    than 64 ids or no strings."""
+    from . import ops
+    from .vocab import smiles_token_table, smiles_chem_table, smiles_emit_table
+    strings = list(strings)
+    if not strings:
+        raise ValueError("fragment_smiles: needs at least one string")
+    if len(vocab) > 64:
+        raise ValueError(f"fragment_smiles: the vocabulary has {len(vocab)} ids, at most 64 are supported")
+    dev = torch.device(device)
+    ids = [vocab.string2ids(s, add_bos=True, add_eos=True) for s in strings]
+    x = torch.full((len(ids), max(map(len, ids))), vocab.pad, dtype=torch.long)
+    for b, row in enumerate(ids):
+        x[b, :len(row)] = torch.as_tensor(row)
+    tables = [smiles_token_table(vocab), smiles_chem_table(vocab), smiles_emit_table(vocab)]
+    if dev.type == "cpu":
+        count, write = ops.smiles_fragment_host, ops.smiles_fragment_smiles_host
+    else:
+        from .models import _require_cuda
+        _require_cuda(dev, "data.fragment_smiles")
+        count, write = ops.smiles_fragment_rows, ops.smiles_fragment_smiles_rows
+        x, tables = x.to(dev), [t.to(dev) for t in tables]
+    most = int(count(x, tables[0], tables[1], vocab.eos, mask=False)[2][:, 0].max())
+    table = np.array([vocab.i2c[i] for i in range(len(vocab))], dtype=object)
+    res, first = [[] for _ in strings], None
+    for f in range(max(most, 1)):
+        out, out_len, status, _ = write(x, *tables, vocab.bos, vocab.eos, vocab.pad, f, info=False)
+        out, out_len, status = out.cpu().numpy(), out_len.cpu().numpy(), status.cpu().numpy()
+        first = status if first is None else first
+        for b in np.nonzero(status == 0)[0]:
+            res[b].append("".join(table[out[b, 1:out_len[b] - 1]]))
+    return (res, first) if return_status else res
 
 
 class SubstructureTable:

@@ -665,6 +665,42 @@ class VAE(_SavedState, nn.Module):
         return ops.scaffold_dict(*ops.smiles_scaffold_rows(self._rows(x, "scaffolds", dev), self._smiles_table(dev),
                                                            self._smiles_chem_table(dev), self.eos))
 
+    @torch.no_grad()
+    def fragments(self, x):
+        """The fragments of token rows x (what ``fingerprints`` takes) and their graph keys, on the device, one
+        mvae_smiles_fragment_rows launch, no host wait: {"status": int32 [B], "mask": int64 [B, 16, 2] (bit a of word a >> 6 of slot f:
+        atom a, in string order, is in fragment f), "fragments", "cuts", "acyl_cuts", "largest": int32 [B], "keys": int64 [B, 16] (0 in
+        unused slots)}.  A row is cut at the bonds between a ring and its substituents and at acyl-heteroatom bonds (amide, ester, ...),
+        never at a terminal atom; the fragments are numbered by their lowest atom and keyed as ``scaffolds`` keys a scaffold
+        (include/mvae.h, "Fragments").  This library's own rule: NOT BRICS, not RECAP, no agreement with a toolkit is claimed.  A row
+        whose status is not 0 has zeros; one with more than 16 fragments has status ops.SMILES_STATUS_FRAG_MANY (15), zero mask and
+        keys, and its true counts.  ValueError for a vocabulary of more than 64 ids."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.fragments")
+        if len(self.vocabulary) > 64:
+            raise ValueError(f"fragments: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
+        return ops.fragment_dict(*ops.smiles_fragment_rows(self._rows(x, "fragments", dev), self._smiles_table(dev),
+                                                           self._smiles_chem_table(dev), self.eos))
+
+    @torch.no_grad()
+    def fragment_smiles(self, x, frag=0, max_content=127):
+        """Fragment number ``frag`` of token rows x (what ``syntax_valid`` takes) as token rows on the device, one
+        mvae_smiles_fragment_smiles_rows launch, no host wait: (out int64 [B, max(T, max_content + 2)], out_len int32 [B], status int32
+        [B], ops.FRAGMENT_SMILES_STATUS_NAMES).  The atoms of fragment ``frag`` of ``fragments`` with every lost bond turned into
+        hydrogens, in the spelling of ``canonical`` (include/mvae.h, "Fragments"): rows that can be shown and handed to
+        ``data.compile_substructures`` once decoded.  A row without that fragment (status != 0: ``canonical``'s reasons, or 16: fewer
+        fragments) is the EMPTY row <bos> <eos> with out_len 2, never a copy.  NOT BRICS, not RECAP.  ValueError for a vocabulary of
+        more than 64 ids or frag < 0."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.fragment_smiles")
+        if len(self.vocabulary) > 64:
+            raise ValueError(f"fragment_smiles: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
+        x = self._rows(x, "fragment_smiles", dev)
+        out, out_len, status, _ = ops.smiles_fragment_smiles_rows(x, self._smiles_table(dev), self._smiles_chem_table(dev),
+                                                                  self._smiles_emit_table(dev), self.bos, self.eos, self.pad, frag, max_content,
+                                                                  info=False)
+        return out, out_len, status
+
     def edit_distance(self, x, y):
         """The token-level Levenshtein distance (unit costs for insert, delete and substitute, no transposition) between the rows of two
         batches, pair by pair: int32 [B] on the device, one launch (mvae_edit_distance_rows), no host wait.  x, y: padded ids [B, T] (bos

@@ -950,7 +950,7 @@ REWRITE_COUNTS = 16                           # the length of the per-status his
 REWRITE_EMIT = 48                             # include/mvae.h: MVAE_REWRITE_EMIT
 
 
-def _rewrite_tables(tok_info, chem_info, emit, draw, counts, n, dev, max_content):
+def _rewrite_tables(tok_info, chem_info, emit, draw, counts, n, dev, max_content, n_counts=16):
     _graph_tables(tok_info, chem_info, dev)
     assert emit.dtype == torch.int32 and emit.shape == (REWRITE_EMIT,) and emit.is_contiguous() and emit.device == dev, (emit.dtype, emit.shape)
     if not 1 <= int(max_content) <= 127:
@@ -958,7 +958,7 @@ def _rewrite_tables(tok_info, chem_info, emit, draw, counts, n, dev, max_content
     if draw is not None:                         # uint32 [n], carried as int32 bits
         assert draw.dtype == torch.int32 and draw.shape == (n,) and draw.is_contiguous() and draw.device == dev, (draw.dtype, tuple(draw.shape))
     if counts is not None:
-        assert counts.dtype == torch.int32 and counts.shape == (REWRITE_COUNTS,) and counts.is_contiguous() and counts.device == dev
+        assert counts.dtype == torch.int32 and counts.shape == (n_counts,) and counts.is_contiguous() and counts.device == dev
 
 
 def draw_words(values):
@@ -971,39 +971,42 @@ CANON_INFO = ("atoms", "first_classes", "rounds", "ties")          # the columns
 _CANON_OUT = ((torch.int32, (len(CANON_INFO),), True), (torch.uint8, (128,), True))      # info, rank: what canon writes beside the row
 
 
-def _writer_rows(name, host, x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, family_in, max_content, T_out, extra, given, counts):
+def _writer_rows(name, host, x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, family_in, max_content, T_out, extra, given, counts,
+                 family_ints=(), n_counts=None):
     """What the mvae_smiles_rewrite / _canon _rows and _host entries share: the tensor checks, the outputs, the call of the C entry
     `name`.  family_in: (seed, draw) where the entry takes them (behind pad_id), () where not; extra: the spec of the outputs behind
-    (out, out_len, status), which the C entries take behind counts; given: the caller's outputs, all of them, as ``_outputs`` reads them."""
+    (out, out_len, status), which the C entries take behind counts; given: the caller's outputs, all of them, as ``_outputs`` reads them;
+    family_ints: the integers an entry takes in front of those outputs (frag); n_counts: the length of its counts where not 16."""
     x, ldx = _token_rows(x, "x")
     assert not host or x.device.type == "cpu", x.device
     B, T = x.shape
     seed, draw = family_in or (0, None)
-    _rewrite_tables(tok_info, chem_info, emit, draw, counts, B, x.device, max_content)
+    _rewrite_tables(tok_info, chem_info, emit, draw, counts, B, x.device, max_content, n_counts or REWRITE_COUNTS)
     T_out = max(T, int(max_content) + 2) if T_out is None else int(T_out)
     res = _outputs(B, x.device, ((torch.int64, (T_out,), False), (torch.int32, (), False), (torch.int32, (), False)) + extra, given)
     check(getattr(L.load(), name)(B, T, tok_info.numel(), ptr(x), ldx, ptr(tok_info), ptr(chem_info), ptr(emit), int(bos_id), int(eos_id),
                                   int(pad_id), *((int(seed) & 0xFFFFFFFF, ptr(draw)) if family_in else ()), int(max_content), T_out,
-                                  *map(ptr, res[:3]), *(() if host else (ptr(counts),)), *map(ptr, res[3:]),
+                                  *map(ptr, res[:3]), *(() if host else (ptr(counts),)), *map(int, family_ints), *map(ptr, res[3:]),
                                   *(() if host else (stream_ptr(),))), name)
     return res
 
 
-def _writer_corpus(name, tokens, offsets, N, rows, tok_info, chem_info, emit, family_in, max_content, stride, extra, given, counts, err):
+def _writer_corpus(name, tokens, offsets, N, rows, tok_info, chem_info, emit, family_in, max_content, stride, extra, given, counts, err,
+                   family_ints=(), n_counts=None):
     """The same for the _corpus entries; given = (tokens_out, offsets_out, status) and the outputs of `extra`."""
     N, B = int(N), rows.numel()
     dev = tokens.device
     _csr(tokens, offsets, N)
     assert rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_contiguous() and rows.device == dev and B >= 1
     seed, draw = family_in or (0, None)
-    _rewrite_tables(tok_info, chem_info, emit, draw, counts, B, dev, max_content)
+    _rewrite_tables(tok_info, chem_info, emit, draw, counts, B, dev, max_content, n_counts or REWRITE_COUNTS)
     stride = int(max_content) if stride is None else int(stride)
     offsets_out, = _outputs(2 * B + 1, dev, ((torch.int64, (), False),), given[1:2])
     tokens_out, status, *more = _outputs(B, dev, ((torch.uint8, (stride,), False), (torch.int32, (), False)) + extra, given[:1] + given[2:])
     assert err is None or (err.dtype == torch.int32 and err.numel() == 1 and err.device == dev)
     check(getattr(L.load(), name)(ptr(tokens), ptr(offsets), N, ptr(rows), B, tok_info.numel(), ptr(tok_info), ptr(chem_info), ptr(emit),
                                   *((int(seed) & 0xFFFFFFFF, ptr(draw)) if family_in else ()), int(max_content), stride, ptr(tokens_out),
-                                  ptr(offsets_out), ptr(status), ptr(counts), ptr(err), *map(ptr, more), stream_ptr()), name)
+                                  ptr(offsets_out), ptr(status), ptr(counts), ptr(err), *map(int, family_ints), *map(ptr, more), stream_ptr()), name)
     return (tokens_out, offsets_out, status, *more)
 
 
@@ -1102,6 +1105,86 @@ def smiles_scaffold_smiles_corpus(tokens, offsets, N, rows, tok_info, chem_info,
     ``smiles_rewrite_corpus``, with its counts and err; a row without a scaffold is a slice of length 0."""
     return _writer_corpus("mvae_smiles_scaffold_smiles_corpus", tokens, offsets, N, rows, tok_info, chem_info, emit, (), max_content, stride,
                           _SCAFFOLD_SMILES_OUT, (tokens_out, offsets_out, status, info), counts, err)
+
+
+FRAGMENT_MAX = 16                             # include/mvae.h: MVAE_FRAGMENT_MAX, the fragment slots of a row
+SMILES_STATUS_FRAG_MANY = 15                  # MVAE_SMILES_FRAG_MANY, given by the fragment entries only: more than 16 fragments
+SMILES_STATUS_NO_FRAGMENT = 16                # MVAE_SMILES_NO_FRAGMENT, given by the fragment SMILES entries only
+FRAGMENT_STATUS_NAMES = SCAFFOLD_SMILES_STATUS_NAMES + ("frag_many",)                   # index = status; 7 - 14 are never given here
+FRAGMENT_SMILES_STATUS_NAMES = FRAGMENT_STATUS_NAMES + ("no_fragment",)                 # 14 and 15 are never given here
+FRAGMENT_DESC = ("fragments", "cuts", "acyl_cuts", "largest")       # the columns of desc [*, 4]
+FRAGMENT_SMILES_INFO = SCAFFOLD_SMILES_INFO                         # the columns of info [*, 4] (MVAE_FRAGMENT_SMILES_INFO)
+FRAGMENT_SMILES_COUNTS = 32                                         # MVAE_FRAGMENT_SMILES_COUNTS: the per-status histogram has a slot 16
+# status, mask, desc, key
+_FRAGMENT_OUT = ((torch.int32, (), False), (torch.int64, (FRAGMENT_MAX, 2), True), (torch.int32, (4,), False), (torch.int64, (FRAGMENT_MAX,), False))
+_FRAGMENT_SMILES_OUT = ((torch.int32, (len(FRAGMENT_SMILES_INFO),), True),)
+
+
+def smiles_fragment_rows(x, tok_info, chem_info, eos_id, status=None, mask=None, desc=None, key=None):
+    """The fragments of token rows x (int64 [B, T], bos first) on the device: (status int32 [B], mask int64 [B, 16, 2], desc int32 [B, 4],
+    key int64 [B, 16]) -- every row cut at its ring substituent bonds and its acyl-heteroatom bonds (include/mvae.h, "Fragments": this
+    library's own rule, NOT BRICS, not RECAP, no agreement with a toolkit claimed); the fragments are numbered by their lowest atom; bit
+    a of mask[b, f] word a >> 6 = atom a (string order) is in fragment f; desc = fragments, cuts, cuts by the acyl rule alone, atoms of
+    the largest fragment; key[b, f] = the graph key of fragment f made as the scaffold key is, 0 in unused slots.  Zeros for a row whose
+    status is not 0; a row with more than 16 fragments gets SMILES_STATUS_FRAG_MANY (15), zero mask and keys and its true desc.
+    ``mask=False``: no mask is computed (None is returned in its place).  One launch (mvae_smiles_fragment_rows)."""
+    return _smiles_rows(L.load().mvae_smiles_fragment_rows, _FRAGMENT_OUT, x, tok_info, chem_info, eos_id, (status, mask, desc, key))
+
+
+def smiles_fragment_corpus(tokens, offsets, N, tok_info, chem_info, status=None, mask=None, desc=None, key=None):
+    """smiles_fragment_rows over the CSR corpus (tokens uint8, offsets int64 [N + 1]; rows without specials, the end of a row acting as
+    <eos>): one launch (mvae_smiles_fragment_corpus)."""
+    return _smiles_corpus(L.load().mvae_smiles_fragment_corpus, _FRAGMENT_OUT, tokens, offsets, N, tok_info, chem_info, (status, mask, desc, key))
+
+
+def smiles_fragment_host(x, tok_info, chem_info, eos_id, status=None, mask=None, desc=None, key=None):
+    """smiles_fragment_rows on HOST tensors: the same source compiled for the CPU, a plain loop over the rows
+    (mvae_smiles_fragment_host) -- for tests and for machines without a device; not a fallback of the device entries."""
+    return _smiles_rows(L.load().mvae_smiles_fragment_host, _FRAGMENT_OUT, x, tok_info, chem_info, eos_id, (status, mask, desc, key), host=True)
+
+
+def fragment_dict(status, mask, desc, key):
+    """The outputs of the fragment entries under their names: status, mask, fragments, cuts, acyl_cuts, largest, keys."""
+    out = {"status": status, "mask": mask}
+    out.update((name, desc[:, i]) for i, name in enumerate(FRAGMENT_DESC))
+    out["keys"] = key
+    return out
+
+
+def _frag(frag):
+    if int(frag) < 0:
+        raise ValueError(f"smiles_fragment_smiles: frag must be >= 0, got {frag}")
+    return (int(frag),)
+
+
+def smiles_fragment_smiles_rows(x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, frag=0, max_content=127, T_out=None, out=None,
+                                out_len=None, status=None, info=None, counts=None):
+    """Fragment number ``frag`` (by lowest atom, from 0) of token rows x (int64 [B, T], bos first) as token rows, on the device: (out
+    int64 [B, T_out], out_len int32 [B], status int32 [B], info int32 [B, 4]) -- the fragment of ``smiles_fragment_rows`` cut out of the
+    row's graph, every lost bond turned into hydrogens, in the spelling of ``smiles_canon_rows`` (include/mvae.h, "Fragments").  A row
+    without that fragment (status != 0, ``FRAGMENT_SMILES_STATUS_NAMES``: the canon entries' reasons, or 16 "no_fragment") gets the EMPTY
+    row bos, eos, pad..., and out_len 2 -- never a copy.  info = atoms and bonds of the fragment, atoms that became bracket atoms, bond
+    orders lost; ``info=False``: not written.  counts: int32 [32].  NOT BRICS, not RECAP: this library's own rule.  One launch
+    (mvae_smiles_fragment_smiles_rows)."""
+    return _writer_rows("mvae_smiles_fragment_smiles_rows", False, x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, (), max_content, T_out,
+                        _FRAGMENT_SMILES_OUT, (out, out_len, status, info), counts, _frag(frag), FRAGMENT_SMILES_COUNTS)
+
+
+def smiles_fragment_smiles_host(x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, frag=0, max_content=127, T_out=None, out=None,
+                                out_len=None, status=None, info=None):
+    """smiles_fragment_smiles_rows on HOST tensors: the same source compiled for the CPU, a plain loop over the rows
+    (mvae_smiles_fragment_smiles_host) -- for tests and for machines without a device; not a fallback of the device entries."""
+    return _writer_rows("mvae_smiles_fragment_smiles_host", True, x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, (), max_content, T_out,
+                        _FRAGMENT_SMILES_OUT, (out, out_len, status, info), None, _frag(frag), FRAGMENT_SMILES_COUNTS)
+
+
+def smiles_fragment_smiles_corpus(tokens, offsets, N, rows, tok_info, chem_info, emit, frag=0, max_content=127, stride=None, tokens_out=None,
+                                  offsets_out=None, status=None, info=None, counts=None, err=None):
+    """smiles_fragment_smiles_rows over the rows `rows` (int64 [B]) of the CSR corpus, one launch (mvae_smiles_fragment_smiles_corpus):
+    (tokens_out uint8 [B, stride], offsets_out int64 [2 B + 1], status int32 [B], info int32 [B, 4]) in the gapped CSR layout of
+    ``smiles_rewrite_corpus``, with its err and counts (int32 [32]); a row without that fragment is a slice of length 0."""
+    return _writer_corpus("mvae_smiles_fragment_smiles_corpus", tokens, offsets, N, rows, tok_info, chem_info, emit, (), max_content, stride,
+                          _FRAGMENT_SMILES_OUT, (tokens_out, offsets_out, status, info), counts, err, _frag(frag), FRAGMENT_SMILES_COUNTS)
 
 
 SUBSTRUCT_QATOMS = 32                         # include/mvae.h: MVAE_SUBSTRUCT_QATOMS, the atoms of a query and the columns of `map`

@@ -802,7 +802,7 @@ def moses_reconstruction(model, batches, beam_width=1, max_len=100, syntax=False
 def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top_k=None, top_p=None, seed=0, z=None, syntax=False,
                    count_valid=False, novel_against=None, prefix=None, nearest=False, valence=False,
                    int_div=False, snn=False, scaffolds=False, kekule=False, canonical=False, filters=None, filter_steps=65536,
-                   top_scaffolds=0):
+                   top_scaffolds=0, fragments=False):
     """The reference's generation pipeline (``hugesample.py``: sample in batches, hash the strings, count unique / total) with the hashing
     and the deduplication on the device: ``n_samples`` sequences from a ``mosesvae.VAE`` in batches of ``batch_size`` (the last one shorter),
     batch j with seed ``seed + j`` and ``temp`` / ``top_k`` / ``top_p`` as ``VAE.sample`` takes them.  ``z`` None draws each batch's latents
@@ -899,6 +899,14 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     counts): "filters", the share of them with no hit and no undecided bit (NaN for none); "filter_hits" and "filter_undecided", per
     pattern, how many contain it and on how many the search ran out of steps.  Without ``filters`` the launches and the keys of the
     result are what they were.
+    ``fragments=True`` (ValueError for a vocabulary of more than 64 ids, before any device work): the fragments of the samples, on
+    ``VAE.fragments`` -- every molecule cut at its ring substituent bonds and its acyl-heteroatom bonds, each piece keyed like a scaffold
+    (include/mvae.h, "Fragments"; this library's own rule, NOT BRICS and not RECAP, no agreement with a toolkit claimed).  Each batch's
+    NEW rows go through one ``mvae_smiles_fragment_rows`` launch, no further host wait.  The result gains "n_fragments", the distinct
+    fragment keys among the samples, and "fragment_many", the samples of more than 16 fragments (status 15: they add no key).  With
+    ``novel_against`` it further gains "frag", the MOSES Frag figure: the cosine similarity (``ops.histogram_cosine``) of the generated
+    fragment histogram -- every fragment of every drawn sample counting, so a fragment that occurs twice in a molecule counts twice and
+    each distinct sample weighs its "counts" -- and ``novel_against.fragment_histogram()`` (NaN when either is empty).
     ``top_scaffolds=k`` (k >= 1 needs ``scaffolds=True``; ValueError otherwise, and for max_len > 129, before any device work): the
     scaffolds the model produces most, as strings -- ``VAE.scaffold_smiles`` (include/mvae.h, "Scaffold SMILES"; NOT rdkit's
     MurckoScaffoldSmiles).  Each batch's NEW rows go through one ``mvae_smiles_scaffold_smiles_rows`` launch, no further host wait, and
@@ -942,6 +950,8 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         raise ValueError("moses_generate: snn=True needs novel_against, the corpus to search")
     if scaffolds and len(model.vocabulary) > 64:
         raise ValueError(f"moses_generate: scaffolds=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
+    if fragments and len(model.vocabulary) > 64:
+        raise ValueError(f"moses_generate: fragments=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
     if kekule and len(model.vocabulary) > 64:
         raise ValueError(f"moses_generate: kekule=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
     top_scaffolds = int(top_scaffolds)
@@ -983,6 +993,7 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     n_fp = torch.zeros((), dtype=i64, device=dev) if int_div or snn else None
     snn_sum = torch.zeros((), dtype=torch.float64, device=dev) if snn else None
     scafs = []                                                  # (molecule key, scaffold key, scaffold atoms) of each new sample, likewise
+    frags = []                                                  # (fragment keys [*, 16], status) of each new sample, likewise
     scaf_rows = []                                              # (scaffold row [*, 129], status) of each new sample, likewise
     keks = []                                                   # (status, deficiency) of each new sample under the kekule entry, likewise
     n_kek = torch.zeros(3, dtype=i64, device=dev) if kekule else None        # status 0: all samples, distinct ones, distinct and novel
@@ -1078,6 +1089,9 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
                 if top_scaffolds:
                     s_rows, _, s_status = model.scaffold_smiles(x[sel])      # 129 columns, as the canonical rows below
                     scaf_rows.append((s_rows, s_status))
+            if fragments:
+                fr = model.fragments(x[sel])
+                frags.append((fr["keys"], fr["status"]))
             if kekule:
                 keks.append((kek["status"][sel], kek["deficiency"][sel]))
             if canonical:
@@ -1143,6 +1157,13 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
             v = model.vocabulary
             res["top_scaffolds"] = [(v.ids2string(r[:r.index(v.eos) + 1], rem_bos=True, rem_eos=True), c)
                                     for r, c in zip(distinct[best].tolist(), drawn[best].tolist())]
+    if fragments:
+        fkeys = torch.cat([c[0] for c in frags]) if frags else torch.empty((0, ops.FRAGMENT_MAX), dtype=i64, device=dev)
+        fstatus = torch.cat([c[1] for c in frags]) if frags else torch.empty(0, dtype=torch.int32, device=dev)
+        fk, fc = ops.key_histogram(fkeys, counts[:, None].expand_as(fkeys))      # every fragment of every drawn sample counts
+        res["n_fragments"], res["fragment_many"] = fk.numel(), int((fstatus == ops.SMILES_STATUS_FRAG_MANY).sum())
+        if novel_against is not None:
+            res["frag"] = float(ops.histogram_cosine(fk, fc, *novel_against.fragment_histogram()))
     if kekule:
         n_kek = n_kek.tolist()
         res["kekule_valid"], res["kekule_valid_unique"] = n_kek[0], n_kek[1]
