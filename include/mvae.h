@@ -70,9 +70,9 @@ int mvae_knob_int(const char* name, int dflt);
  * of B are read and must hold ZERO (so lda, ldb >= roundup(K, chunk)); nothing beyond them is read.  lda / ldb need not be multiples of
  * 16 bytes (such operands take the register-staged main loop instead of the LDS-direct one).  K == 0 reads nothing of A and B: C = act(bias),
  * zeros without a bias; under accumulate C += bias or stays as it was.  Columns N .. ldc - 1 of C are never written.
- * MVAE_F32X3 is honoured only where the LDS-direct loop runs (K a multiple of 32 and >= 128, 16-byte aligned rows) on the 64 x 64 or
- * 128 x 128 tile; elsewhere -- the other main loop, and the 128 x 32 tile that N <= 32 with M >= 128 takes -- the result is the
- * exact-fp32 one.
+ * MVAE_F32X3 is honoured only where its own kernel runs (K a multiple of 4 and >= 128, 16-byte aligned rows, operands below 2 GiB; 128 x 128,
+ * 128 x 64 or 64 x 128 tile, the operands split into bf16 hi / lo once per workgroup, K split as for MVAE_F32); elsewhere -- and on the 128 x 32 tile that N <= 32 with
+ * M >= 128 takes -- the result is the exact-fp32 one.
  */
 size_t mvae_gemm_nt_workspace(int M, int N, int K, int dtype_ab);
 int mvae_gemm_nt(int dtype_ab, int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb,

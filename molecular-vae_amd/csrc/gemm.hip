@@ -43,8 +43,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int n) {
   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
 }
 
-// X3 (fp32 operands, LDS-direct loop only): products on the bf16 MFMA as hi.hi + hi.lo + lo.hi, see tile_pipe.hpp split_x3
-template <typename T, int BM, int BN, bool PIPE, bool X3 = false>
+template <typename T, int BM, int BN, bool PIPE>
 __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int WM = BM / 2, WN = BN / 2, MI = WM / 16, NI = WN / 16;
@@ -80,7 +79,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs p) {
     const uint32_t bytesA = (uint32_t)(p.a_total * sz - kbeg * sz), bytesB = (uint32_t)((long)p.N * p.ldb * sz - kbeg * sz);
     pipe_seg_init<T, BM, BN>(s0, A + kbeg, bytesA, B + kbeg, bytesB, offA, offB, (int)(kend - kbeg), tid);
     s1 = s0; s1.nk = 0;
-    tile_gemm_pipe<T, BM, BN, MI, NI, NBUF, NI, 0, X3>(smem, s0, s1, wm * WM, wn * WN, acc, tid);
+    tile_gemm_pipe<T, BM, BN, MI, NI, NBUF, NI, 0>(smem, s0, s1, wm * WM, wn * WN, acc, tid);
   } else {
     tile_gemm_segment<T, BM, BN, MI, NI>(smem, rowA, rowB, kbeg, kend, wm * WM, brow, acc, tid);
   }
@@ -97,6 +96,127 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmArgs p) {
         const int row = m0 + wm * WM + i * 16 + lq * 4 + r;
         if (row >= p.M) continue;
         float v = acc[i][j][r];
+        if (p.splits > 1) {
+          p.partial[((long)split * p.M + row) * p.N + col] = v;
+        } else {
+          if (p.bias) v += p.bias[col];
+          if (p.act == MVAE_ACT_SELU) v = selu_f(v); else if (p.act == MVAE_ACT_RELU) v = fmaxf(v, 0.f);
+          store_out(p.C, (long)row * p.ldc + col, p.c_dtype, v, p.accumulate);
+        }
+      }
+    }
+}
+
+// ---- NT, 3 x bf16 products (MVAE_F32X3), operands split ONCE per workgroup: the fp32 rows come in through registers (float4 along K, the
+// next stage's in flight under this stage's MFMAs), are split (split_x3_4) and written as bf16 hi and lo planes in the bf16 tile image
+// (128-byte rows = 64 k, swz()); the loop is the bf16 loop -- plain ds_read_b128 fragments, three MFMAs per pair.  BM x BN tile, waves 2 x 2,
+// 64 k per stage, one LDS buffer of (BM + BN) * 256 bytes, two barriers per stage, two workgroups per CU (three of the 64-row tile): one
+// stages while the other multiplies.  Host: the conditions of the LDS-direct loop (whole 32-element K-steps, 16-byte aligned rows, operands < 2 GiB).
+template <int BM, int BN>
+__global__ __launch_bounds__(256, BM == 64 ? 3 : 2) void gemm_nt_x3_kernel(GemmArgs p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int WM = BM / 2, WN = BN / 2, MI = WM / 16, NI = WN / 16, NA = BM / 16, NB = BN / 16;
+  constexpr int A_HI = 0, A_LO = BM * KB, B_HI = 2 * BM * KB, B_LO = 2 * BM * KB + BN * KB;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+  const int tile = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
+  const int tm = tile / p.tiles_n, tn = tile - tm * p.tiles_n;
+  const int m0 = tm * BM, n0 = tn * BN;
+  const int split = blockIdx.y;
+  const long kbeg = (long)split * p.kper;
+  const long kend = (kbeg + p.kper < (long)p.K) ? (kbeg + p.kper) : (long)p.K;
+  const float* A = reinterpret_cast<const float*>(p.A);
+  const float* B = reinterpret_cast<const float*>(p.B);
+  // thread -> 16-byte chunk j of the stage's 64 k (4 fp32 -> 8 bytes of each plane), rows r16, r16 + 16, ...
+  const int j = tid & 15, r16 = tid >> 4;
+  // Where the chunk goes inside its 32-k step: the MFMA's k-slot 8 * q + e of lane quarter q holds k = 4 * q + e (e < 4) or 16 + 4 * q + e - 4,
+  // the two 16-byte fp32 chunks q and 4 + q that the LDS-direct fp32 loop hands a lane.  With the K-split of the fp32 plan this makes every
+  // accumulator see the same products in the same slots and order as the fp32-image form did: the results are bit for bit the same.
+  const int jc = (j >> 3) * 4 + (j & 3), jh = ((j >> 2) & 1) * 8;        // 16-byte bf16 chunk of the plane row, byte offset inside it
+  // Element offset of the row start (operands < 2 GiB).  Rows outside the matrix read row 0 instead: they only reach accumulators that are
+  // never stored, and the loads stay free of branches (a load under a branch of its own costs the stage a drained memory queue).
+  uint32_t offa[NA], offb[NB];
+#pragma unroll
+  for (int i = 0; i < NA; ++i) { const int gm = m0 + r16 + 16 * i; offa[i] = gm < p.M ? (uint32_t)grow(gm, p.a_group, p.a_gstride, p.lda) : 0u; }
+#pragma unroll
+  for (int i = 0; i < NB; ++i) { const int gn = n0 + r16 + 16 * i; offb[i] = gn < p.N ? (uint32_t)((long)gn * p.ldb) : 0u; }
+  float4 va[NA], vb[NB];
+  bool kin = true;                                            // the loaded chunk lies inside [kbeg, kend) (K a multiple of 4: inside or outside)
+  auto load_stage = [&](long k0) {
+    kin = k0 + 4 * j < kend;
+    const long k = kin ? k0 + 4 * j : kbeg;                   // outside (the last stage's tail): any readable address, zeroed below
+#pragma unroll
+    for (int i = 0; i < NA; ++i) va[i] = *reinterpret_cast<const float4*>(A + offa[i] + k);
+#pragma unroll
+    for (int i = 0; i < NB; ++i) vb[i] = *reinterpret_cast<const float4*>(B + offb[i] + k);
+  };
+  auto store_stage = [&]() {
+    if (!kin) {
+#pragma unroll
+      for (int i = 0; i < NA; ++i) va[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int i = 0; i < NB; ++i) vb[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      uint2 hi, lo;
+      split_x3_4(va[i], hi, lo);
+      char* d = smem + swz(r16 + 16 * i, jc) + jh;
+      *reinterpret_cast<uint2*>(d + A_HI) = hi;
+      *reinterpret_cast<uint2*>(d + A_LO) = lo;
+    }
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      uint2 hi, lo;
+      split_x3_4(vb[i], hi, lo);
+      char* d = smem + swz(r16 + 16 * i, jc) + jh;
+      *reinterpret_cast<uint2*>(d + B_HI) = hi;
+      *reinterpret_cast<uint2*>(d + B_LO) = lo;
+    }
+  };
+  f32x4 acc[MI][NI];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int jj = 0; jj < NI; ++jj) acc[i][jj] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int lr = lane & 15, lq = lane >> 4;
+  const int nst = (int)((kend - kbeg + 63) / 64);
+  if (nst > 0) {
+    load_stage(kbeg);
+    store_stage();
+    for (int s = 0; s < nst; ++s) {
+      __syncthreads();                                        // the stage is in LDS
+      if (s + 1 < nst) load_stage(kbeg + (long)(s + 1) * 64);
+      u32x4 ah[MI], al[MI], bh[NI], bl[NI];
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const int chunk = kk * 4 + lq;
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi) {
+          const char* s_ = smem + swz(wm * WM + mi * 16 + lr, chunk);
+          ah[mi] = *reinterpret_cast<const u32x4*>(s_ + A_HI); al[mi] = *reinterpret_cast<const u32x4*>(s_ + A_LO);
+        }
+#pragma unroll
+        for (int ni = 0; ni < NI; ++ni) {
+          const char* s_ = smem + swz(wn * WN + ni * 16 + lr, chunk);
+          bh[ni] = *reinterpret_cast<const u32x4*>(s_ + B_HI); bl[ni] = *reinterpret_cast<const u32x4*>(s_ + B_LO);
+        }
+        if (kk == 1) __syncthreads();                         // every wave holds the stage's last fragments: the buffer is free
+        mma_x3_block<MI, NI>(ah, al, bh, bl, acc);
+      }
+      if (s + 1 < nst) store_stage();
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int jj = 0; jj < NI; ++jj) {
+      const int col = n0 + wn * WN + jj * 16 + lr;
+      if (col >= p.N) continue;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = m0 + wm * WM + i * 16 + lq * 4 + r;
+        if (row >= p.M) continue;
+        float v = acc[i][jj][r];
         if (p.splits > 1) {
           p.partial[((long)split * p.M + row) * p.N + col] = v;
         } else {
@@ -314,6 +434,22 @@ Plan make_plan(int M, int N, int K, int dtype) {
   // narrow outputs in f32 (the conv stack: 9 / 10 output channels padded to 32): a 128 x 32 tile, so that the slow f32 MFMAs are not
   // spent on the 75 % (128-wide tile) or 50 % (64-wide) of columns that lie outside the matrix
   if (dtype == MVAE_F32 && N <= 32 && M >= 128) { pl.bm = 128; pl.bn = 32; }
+  // 3 x bf16 form (gemm_nt_x3_kernel, two workgroups per CU): 128 rows, and 64 columns where that covers N (the conv stack's 64 channels)
+  if (dtype == MVAE_F32X3) {
+    pl.bm = 128; pl.bn = N <= 64 ? 64 : 128;
+    // More 128 x 128 tiles than the chip holds at once (two per CU): a second round runs for a handful of them (576 tiles: 2 rounds for 1.125
+    // of work).  64 x 128 tiles sit three to a CU and cut the rounds finer; they stage B half again as often per FLOP (the 1.15).
+    const long tiles128 = (long)((M + 127) / 128) * ((N + pl.bn - 1) / pl.bn), tiles64 = (long)((M + 63) / 64) * ((N + pl.bn - 1) / pl.bn);
+    const double cost128 = (double)((tiles128 + 511) / 512) * 2 * 128, cost64 = (double)((tiles64 + 767) / 768) * 3 * 64 * 1.15;
+    if (pl.bn == 128 && tiles128 > 512 && cost64 < cost128) pl.bm = 64;
+    // the K-split is the exact-f32 plan's, whatever the tile: the split-K sums then run over the same slabs in the same order as in the
+    // fp32-image form this kernel replaced, and the results stay bit for bit what they were
+    const Plan pf = make_plan(M, N, K, MVAE_F32);
+    pl.tiles_m = (M + pl.bm - 1) / pl.bm;
+    pl.tiles_n = (N + pl.bn - 1) / pl.bn;
+    pl.splits = pf.splits; pl.kper = pf.kper;
+    return pl;
+  }
   pl.tiles_m = (M + pl.bm - 1) / pl.bm;
   pl.tiles_n = (N + pl.bn - 1) / pl.bn;
   const long tiles = (long)pl.tiles_m * pl.tiles_n;
@@ -336,7 +472,7 @@ Plan make_plan(int M, int N, int K, int dtype) {
 }  // namespace
 
 size_t gemm_nt_workspace_bytes(int M, int N, int K, int dtype) {
-  if (dtype == MVAE_F32X3) dtype = MVAE_F32;
+  if (dtype == MVAE_F32X3) dtype = MVAE_F32;     // the 3 x bf16 kernel splits K as the exact-f32 plan does
   Plan pl = make_plan(M, N, K, dtype);
   return pl.splits > 1 ? (size_t)pl.splits * M * N * sizeof(float) : 0;
 }
@@ -351,12 +487,23 @@ int launch_gemm_nt_grouped(int dtype, int M, int N, int K, const void* A, long l
                            void* ws, size_t ws_bytes, hipStream_t st) {
   if (M <= 0 || N <= 0) return MVAE_OK;
   if (K < 0 || !A || !B || !C) return MVAE_ERR_INVALID;
-  const bool x3 = dtype == MVAE_F32X3;           // fp32 operands, 3 x bf16 products (only the LDS-direct loop has the form; otherwise exact fp32)
+  const bool x3 = dtype == MVAE_F32X3;           // fp32 operands, 3 x bf16 products (gemm_nt_x3_kernel where it can run; otherwise exact fp32)
   if (x3) dtype = MVAE_F32;
   if (dtype != MVAE_F32 && dtype != MVAE_BF16) return MVAE_ERR_INVALID;
   if (c_dtype != MVAE_F32 && c_dtype != MVAE_BF16) return MVAE_ERR_INVALID;
   if (accumulate && c_dtype != MVAE_F32) return MVAE_ERR_INVALID;
-  Plan pl = make_plan(M, N, K, dtype);
+  const int sz = (dtype == MVAE_BF16) ? 2 : 4, ke = KB / sz;
+  // deep-pipelined LDS-direct path: whole K-steps only (a plan's kper is a multiple of ke by construction), 16-byte aligned rows, operands < 2 GiB
+  const bool pipe = (K % ke == 0) && (lda % (16 / sz) == 0) && (ldb % (16 / sz) == 0) &&
+                    ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) % 16 == 0) &&
+                    (a_total * sz < (1L << 31)) && ((long)N * ldb * sz < (1L << 31)) && K >= 4 * ke &&
+                    (a_group == 0 || a_gstride % (16 / sz) == 0);
+  // the split-once 3 x bf16 kernel (register-staged): the same conditions except that K need only be whole float4 chunks; its own tile plan
+  // (narrow outputs stay on the exact 128 x 32 tile, as before)
+  const bool x3k = x3 && (K % 4 == 0) && (lda % 4 == 0) && (ldb % 4 == 0) && ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) % 16 == 0) &&
+                   (a_total * 4 < (1L << 31)) && ((long)N * ldb * 4 < (1L << 31)) && K >= 4 * ke && (a_group == 0 || a_gstride % 4 == 0) &&
+                   !(N <= 32 && M >= 128);
+  Plan pl = make_plan(M, N, K, x3k ? MVAE_F32X3 : dtype);
   GemmArgs p;
   p.A = A; p.B = B; p.C = C; p.bias = bias; p.partial = nullptr;
   p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
@@ -370,13 +517,7 @@ int launch_gemm_nt_grouped(int dtype, int M, int N, int K, const void* A, long l
     p.partial = reinterpret_cast<float*>(ws);
   }
   dim3 grid(pl.tiles_m * pl.tiles_n, pl.splits), block(256);
-  const int sz = (dtype == MVAE_BF16) ? 2 : 4, ke = KB / sz;
-  // deep-pipelined LDS-direct path: whole K-steps only, 16-byte aligned rows, operands < 2 GiB
-  const bool pipe = (K % ke == 0) && (pl.kper % ke == 0) && (lda % (16 / sz) == 0) && (ldb % (16 / sz) == 0) &&
-                    ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) % 16 == 0) &&
-                    (a_total * sz < (1L << 31)) && ((long)N * ldb * sz < (1L << 31)) && K >= 4 * ke &&
-                    (a_group == 0 || a_gstride % (16 / sz) == 0);
-  const size_t lds = (size_t)(pipe ? 4 : 2) * (pl.bm + pl.bn) * KB;
+  const size_t lds = (size_t)(x3k ? 2 : pipe ? 4 : 2) * (pl.bm + pl.bn) * KB;     // x3k: one stage, hi and lo planes
 #define MVAE_GEMM_LAUNCH2(TT_, BM_, BN_, PIPE_)                                                       \
   do {                                                                                                \
     auto kern = gemm_nt_kernel<TT_, BM_, BN_, PIPE_>;                                                 \
@@ -385,9 +526,9 @@ int launch_gemm_nt_grouped(int dtype, int M, int N, int K, const void* A, long l
     hipLaunchKernelGGL(kern, grid, block, lds, st, p);                                                \
   } while (0)
 #define MVAE_GEMM_LAUNCH(TT_, BM_, PIPE_) MVAE_GEMM_LAUNCH2(TT_, BM_, BM_, PIPE_)
-#define MVAE_GEMM_LAUNCH3(BM_)                                                                        \
+#define MVAE_GEMM_LAUNCH3(BM_, BN_)                                                                   \
   do {                                                                                                \
-    auto kern = gemm_nt_kernel<float, BM_, BM_, true, true>;                                          \
+    auto kern = gemm_nt_x3_kernel<BM_, BN_>;                                                          \
     static bool attr_set = false;                                                                     \
     if (!attr_set) { MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr_set = true; } \
     hipLaunchKernelGGL(kern, grid, block, lds, st, p);                                                \
@@ -397,8 +538,8 @@ int launch_gemm_nt_grouped(int dtype, int M, int N, int K, const void* A, long l
   } else if (dtype == MVAE_BF16) {
     if (pl.bm == 128) { if (pipe) MVAE_GEMM_LAUNCH(bf16_t, 128, true); else MVAE_GEMM_LAUNCH(bf16_t, 128, false); }
     else { if (pipe) MVAE_GEMM_LAUNCH(bf16_t, 64, true); else MVAE_GEMM_LAUNCH(bf16_t, 64, false); }
-  } else if (x3 && pipe) {
-    if (pl.bm == 128) MVAE_GEMM_LAUNCH3(128); else MVAE_GEMM_LAUNCH3(64);
+  } else if (x3k) {
+    if (pl.bn == 64) MVAE_GEMM_LAUNCH3(128, 64); else if (pl.bm == 64) MVAE_GEMM_LAUNCH3(64, 128); else MVAE_GEMM_LAUNCH3(128, 128);
   } else {
     if (pl.bm == 128) { if (pipe) MVAE_GEMM_LAUNCH(float, 128, true); else MVAE_GEMM_LAUNCH(float, 128, false); }
     else { if (pipe) MVAE_GEMM_LAUNCH(float, 64, true); else MVAE_GEMM_LAUNCH(float, 64, false); }
@@ -702,6 +843,166 @@ __global__ __launch_bounds__(256) void gemm_tn_f32_kernel(GemmArgs p) {
   gemm_tn_f32_body<X3, CS>(p, xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n), blockIdx.y, As, Bs);
 }
 
+// ---- TN, 3 x bf16 products, operands split ONCE per workgroup (tile_pipe.hpp split_x3_4).  Same GemmArgs contract as gemm_tn_f32_body (row
+// groups, virtual ones column, split-K slabs), M and N multiples of 4.  Tile 64 x 128 (WGM = 1, NI = 2: waves 1 x 4, wave tile 64 x 32; the
+// launcher's choice) or 128 x 128 (WGM = 2, NI = 4: waves 2 x 2, wave tile 64 x 64), 64 reduction rows per stage.  A stage is staged through
+// registers: every thread loads its float4s (the next stage's are in
+// flight under this stage's MFMAs), splits them and writes the bf16 hi and lo planes [64][BM] / [64][BN] (K-major, tnx_f swizzle) with
+// ds_write_b64; the fragments come back through ds_read_b64_tr_b16 (FragReadTN), 8 / 16 fragments and 24 / 48 MFMAs per wave and K-half.  One LDS
+// buffer of 48 / 64 KiB, two barriers per stage, TWO workgroups per CU: one's staging (VALU, LDS stores) runs under the other's MFMAs.  The
+// barrier that frees the buffer sits in front of the stage's last MFMA block, so the next stage's split and stores overlap it in-wave too.
+// Bit for bit the results of gemm_tn_f32_body<true, *>: the same 32-row steps from the split's first row, the same K-split (launcher), and
+// inside a step the same row in every MFMA k-slot -- that loop gives lane quarter q the rows q, q + 4, ..., q + 28 as its eight k, so row r
+// of a step is written to plane row tnx_slot(r) = 8 * (r & 3) + (r >> 2), which the transposed read hands to quarter r & 3 as element r >> 2.
+constexpr int TNX_KS = 64;
+__device__ __forceinline__ int tnx_slot(int r) { return (r & 32) | ((r & 3) << 3) | ((r >> 2) & 7); }
+template <int WGM, int NI, bool CS>
+__global__ __launch_bounds__(256, 2) void gemm_tn_x3_kernel(GemmArgs p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  constexpr int BM = 64 * WGM, WN = 16 * NI, BN = (4 / WGM) * WN;
+  constexpr int RA = BM * 2, RB = BN * 2;                     // bytes per k-row of a plane
+  constexpr int PA = TNX_KS * RA, PB = TNX_KS * RB;           // bytes per plane; LDS = A hi | A lo | B hi | B lo
+  constexpr int CPA = BM / 4, RPA = 256 / CPA, NA = TNX_KS / RPA;      // float4 chunks per row, rows per pass of the 256 threads, passes
+  constexpr int CPB = BN / 4, RPB = 256 / CPB, NB = TNX_KS / RPB;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = WGM == 2 ? (wave >> 1) : 0, wn = WGM == 2 ? (wave & 1) : wave;
+  const int tile = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
+  const int tm = tile / p.tiles_n, tn = tile - tm * p.tiles_n;
+  const int m0 = tm * BM, n0 = tn * BN;
+  const int split = blockIdx.y;
+  const long rbeg = (long)split * p.kper;
+  const long rend = (rbeg + p.kper < (long)p.K) ? (rbeg + p.kper) : (long)p.K;
+  const float* A = reinterpret_cast<const float*>(p.A);
+  const float* B = reinterpret_cast<const float*>(p.B);
+  const int ca = (tid % CPA) * 4, ka = tid / CPA, cb = (tid % CPB) * 4, kb = tid / CPB;
+  const bool a_in = m0 + ca < p.M, b_in = n0 + cb < p.N;      // M, N multiples of 4: a chunk is inside the matrix or outside, never across
+  const bool b_one = CS && n0 + cb == p.ones_col;             // the chunk that starts with the virtual ones column (ones_col = N)
+  // row state of the thread's next row per operand, advanced by RPA / RPB rows after every load (no division inside the loop)
+  long oa, ob; int ia, ib;
+  auto row_init = [&](long r, int group, long gstride, long ld, long& off, int& in_g) {
+    if (group > 0) { const long qg = r / group; in_g = (int)(r - qg * group); off = qg * gstride + (long)in_g * ld; }
+    else { in_g = 0; off = r * ld; }
+  };
+  auto row_step = [&](int rows, int group, long gstride, long ld, long& off, int& in_g) {
+    off += (long)rows * ld;
+    if (group > 0) { in_g += rows; while (in_g >= group) { in_g -= group; off += gstride - (long)group * ld; } }
+  };
+  row_init(rbeg + ka, p.a_group, p.a_gstride, p.lda, oa, ia);
+  row_init(rbeg + kb, p.b_group, p.b_gstride, p.ldb, ob, ib);
+  float4 va[NA], vb[NB];
+  // Loads without branches (a load under a branch of its own costs the stage a drained memory queue): chunks outside the matrix read the row's
+  // first chunk instead -- they only reach accumulators that are never stored -- and rows beyond rend (the split's last stage) read the
+  // operand's first chunk and are zeroed before the split.
+  const int cola = a_in ? m0 + ca : 0, colb = b_in ? n0 + cb : 0;
+  const int nrow = (int)(rend - rbeg);                        // rows of this split; stage rows are counted from rbeg
+  int rpend = 0;                                              // first row of the stage held in va / vb
+  auto load_stage = [&](int r0) {                             // stages in order: the row state advances by one stage per call
+    rpend = r0;
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      va[i] = *reinterpret_cast<const float4*>(r0 + ka + i * RPA < nrow ? A + oa + cola : A);
+      row_step(RPA, p.a_group, p.a_gstride, p.lda, oa, ia);
+    }
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      vb[i] = *reinterpret_cast<const float4*>(r0 + kb + i * RPB < nrow ? B + ob + colb : B);
+      row_step(RPB, p.b_group, p.b_gstride, p.ldb, ob, ib);
+    }
+  };
+  auto store_stage = [&]() {
+    if constexpr (CS) {
+      if (b_one) {                                            // the virtual ones column (the chunk's other three columns are never stored)
+#pragma unroll
+        for (int i = 0; i < NB; ++i) vb[i].x = 1.f;
+      }
+    }
+    if (rpend + TNX_KS > nrow) {                              // workgroup-uniform: only a split's last stage has rows to zero
+#pragma unroll
+      for (int i = 0; i < NA; ++i) if (rpend + ka + i * RPA >= nrow) va[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int i = 0; i < NB; ++i) if (rpend + kb + i * RPB >= nrow) vb[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const int kr = tnx_slot(ka + i * RPA);
+      uint2 hi, lo;
+      split_x3_4(va[i], hi, lo);
+      char* d = smem + kr * RA + ((((uint32_t)(ca >> 4)) ^ tnx_f<RA>(kr)) << 5) + (ca & 15) * 2;
+      *reinterpret_cast<uint2*>(d) = hi;
+      *reinterpret_cast<uint2*>(d + PA) = lo;
+    }
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      const int kr = tnx_slot(kb + i * RPB);
+      uint2 hi, lo;
+      split_x3_4(vb[i], hi, lo);
+      char* d = smem + 2 * PA + kr * RB + ((((uint32_t)(cb >> 4)) ^ tnx_f<RB>(kr)) << 5) + (cb & 15) * 2;
+      *reinterpret_cast<uint2*>(d) = hi;
+      *reinterpret_cast<uint2*>(d + PB) = lo;
+    }
+  };
+  f32x4 acc[4][NI];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < NI; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int nst = (int)((rend - rbeg + TNX_KS - 1) / TNX_KS);
+  if (nst > 0) {
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_void_t*)smem;
+    const int g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
+    uint32_t addrA[4], addrB[NI];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      addrA[i] = (uint32_t)(8 * g + q) * (uint32_t)RA + ((((uint32_t)(wm * 4 + i)) ^ tnx_f<RA>(8 * g + q)) << 5) + (uint32_t)pp * 8u;
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+      addrB[i] = (uint32_t)(8 * g + q) * (uint32_t)RB + ((((uint32_t)(wn * NI + i)) ^ tnx_f<RB>(8 * g + q)) << 5) + (uint32_t)pp * 8u + 2u * PA;
+    u32x4 ah[4], al[4], bh[NI], bl[NI];
+    load_stage(0);
+    store_stage();
+    for (int s = 0; s < nst; ++s) {
+      __syncthreads();                                        // the stage is in LDS
+      asm volatile("" ::: "memory");
+      if (s + 1 < nst) load_stage((s + 1) * TNX_KS);
+      FragReadTN<0, 4, RA>::template run<0>(ah, addrA, lds0);
+      FragReadTN<0, NI, RB>::template run<0>(bh, addrB, lds0);
+      FragReadTN<0, 4, RA>::template run<0>(al, addrA, lds0 + PA);
+      FragReadTN<0, NI, RB>::template run<0>(bl, addrB, lds0 + PB);
+      wait_lgkmcnt<0>();
+      mma_x3_block<4, NI>(ah, al, bh, bl, acc);
+      __builtin_amdgcn_sched_barrier(0);
+      FragReadTN<0, 4, RA>::template run<32 * RA>(ah, addrA, lds0);
+      FragReadTN<0, NI, RB>::template run<32 * RB>(bh, addrB, lds0);
+      FragReadTN<0, 4, RA>::template run<32 * RA>(al, addrA, lds0 + PA);
+      FragReadTN<0, NI, RB>::template run<32 * RB>(bl, addrB, lds0 + PB);
+      wait_lgkmcnt<0>();                                      // every read of the stage is done
+      __syncthreads();                                        // ... by every wave: the buffer is free
+      asm volatile("" ::: "memory");
+      mma_x3_block<4, NI>(ah, al, bh, bl, acc);
+      if (s + 1 < nst) store_stage();
+    }
+  }
+  const int lr = lane & 15, lq = lane >> 4;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+      const int col = n0 + wn * WN + j * 16 + lr;
+      if (col >= p.N && !(CS && col == p.ones_col)) continue;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = m0 + wm * 64 + i * 16 + lq * 4 + r;
+        if (row >= p.M) continue;
+        const float v = acc[i][j][r];
+        if (CS && col == p.ones_col) {                        // column sums of A
+          if (p.splits > 1) p.colsum_partial[(long)split * p.M + row] = v;
+          else p.colsum_out[row] = p.colsum_acc ? p.colsum_out[row] + v : v;
+        } else if (p.splits > 1) p.partial[((long)split * p.M + row) * p.N + col] = v;
+        else store_out(p.C, (long)row * p.ldc + col, p.c_dtype, v, p.accumulate);
+      }
+    }
+}
+
 // ---- several problems of different shapes in ONE launch (mvae_gemm_tn_f32_multi): the argument block carries every problem's GemmArgs (kernel
 // arguments: no device-side table to build or copy); block b serves problem g with first[g] <= b < first[g + 1], tile = local % tiles,
 // split = local / tiles.  flags[g]: bit 0 = x3, bit 1 = column sums.  One second launch sums every problem's split-K slabs (grid.y = problem).
@@ -769,6 +1070,16 @@ Plan make_plan_tn_f32(int M, int N, int R, int target = 768) {
   pl.kper = per * TNF_KS;
   return pl;
 }
+// gemm_tn_x3_kernel: 64 x 128 tiles; the split over r is make_plan_tn_f32's (whole 32-row steps), so that the slabs and the order of their sum
+// are those of gemm_tn_f32_body<true, *> and the results stay bit for bit what they were.  That plan offers ~768 workgroups of 64 x 64, which
+// are ~400 of these: up to two per CU, one round of the chip.
+Plan make_plan_tn_x3(int M, int N, int R) {
+  Plan pl = make_plan_tn_f32(M, N, R);
+  pl.bm = 64; pl.bn = 128;
+  pl.tiles_m = (M + pl.bm - 1) / pl.bm; pl.tiles_n = (N + pl.bn - 1) / pl.bn;
+  return pl;
+}
+bool tn_x3_takes(int M, int N) { return M % 4 == 0 && N % 4 == 0; }      // whole float4 chunks (leading dimensions and bases: every TN f32 launch)
 }  // namespace
 
 size_t gemm_tn_f32_workspace_bytes(int M, int N, int R) {     // sized for the column-sum form too (one more B column, one partial per split)
@@ -787,7 +1098,9 @@ int launch_gemm_tn_f32(int M, int N, int R, const float* A, long lda, int a_grou
   if (R < 0 || !A || !B || !C) return MVAE_ERR_INVALID;
   if ((lda | ldb | a_gstride | b_gstride) & 3) return MVAE_ERR_INVALID;
   if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) return MVAE_ERR_INVALID;
-  Plan pl = make_plan_tn_f32(M, colsum_out ? N + 1 : N, R);
+  // 3 x bf16 form: the split-once kernel; shapes it cannot take (M or N not a multiple of 4) stay on gemm_tn_f32_body<true, *>
+  const bool x3k = x3 && tn_x3_takes(M, N);
+  Plan pl = x3k ? make_plan_tn_x3(M, colsum_out ? N + 1 : N, R) : make_plan_tn_f32(M, colsum_out ? N + 1 : N, R);
   GemmArgs p;
   p.A = A; p.B = B; p.C = C; p.bias = nullptr; p.partial = nullptr;
   p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.M = M; p.N = N; p.K = R;
@@ -802,7 +1115,17 @@ int launch_gemm_tn_f32(int M, int N, int R, const float* A, long lda, int a_grou
     if (colsum_out) p.colsum_partial = p.partial + (size_t)pl.splits * M * N;
   }
   const dim3 tgrid(pl.tiles_m * pl.tiles_n, pl.splits);
-  if (colsum_out) {
+  if (x3k) {
+    static bool attr_set = false;
+    if (!attr_set) {
+      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_x3_kernel<1, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_x3_kernel<1, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      attr_set = true;
+    }
+    const size_t lds = (size_t)2 * TNX_KS * 2 * (pl.bm + pl.bn);        // hi and lo planes of one 64-row stage of both operands
+    if (colsum_out) hipLaunchKernelGGL((gemm_tn_x3_kernel<1, 2, true>), tgrid, dim3(256), lds, st, p);
+    else hipLaunchKernelGGL((gemm_tn_x3_kernel<1, 2, false>), tgrid, dim3(256), lds, st, p);
+  } else if (colsum_out) {
     if (x3) hipLaunchKernelGGL((gemm_tn_f32_kernel<true, true>), tgrid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((gemm_tn_f32_kernel<false, true>), tgrid, dim3(256), 0, st, p);
   } else {
@@ -828,6 +1151,10 @@ Plan tnf_multi_plan(const mvae_gemm_tn_f32_problem& q, int n) { return make_plan
 size_t tnf_multi_need(const mvae_gemm_tn_f32_problem& q, const Plan& pl) {
   return pl.splits > 1 ? (((size_t)pl.splits * q.M * (q.N + (q.colsum_out ? 1 : 0)) * sizeof(float) + 255) & ~(size_t)255) : 0;
 }
+// a launch of ONE 3 x bf16 problem is the single launcher's (the split-once kernel, the same split over r as here); mixed launches keep gemm_tn_f32_body<true, *>
+bool tnf_multi_single_x3(int n, const mvae_gemm_tn_f32_problem* pr) {
+  return n == 1 && pr[0].x3 && pr[0].M > 0 && pr[0].N > 0 && pr[0].K >= 0 && pr[0].K < (1L << 31) && tn_x3_takes(pr[0].M, pr[0].N);
+}
 }  // namespace
 extern "C" size_t mvae_gemm_tn_f32_multi_workspace(int n, const mvae_gemm_tn_f32_problem* pr) {
   if (n < 1 || n > MVAE_TN_F32_MULTI_MAX || !pr) return 0;
@@ -838,6 +1165,12 @@ extern "C" size_t mvae_gemm_tn_f32_multi_workspace(int n, const mvae_gemm_tn_f32
 extern "C" int mvae_gemm_tn_f32_multi(int n, const mvae_gemm_tn_f32_problem* pr, void* ws, size_t ws_bytes, void* stream) {
   if (n < 1 || n > MVAE_TN_F32_MULTI_MAX || !pr) return MVAE_ERR_INVALID;
   if (mvae_gemm_tn_f32_multi_workspace(n, pr) > ws_bytes || (mvae_gemm_tn_f32_multi_workspace(n, pr) && !ws)) return MVAE_ERR_WORKSPACE;
+  if (tnf_multi_single_x3(n, pr)) {
+    const mvae_gemm_tn_f32_problem& q = pr[0];
+    if (!q.A || !q.B || !q.C) return MVAE_ERR_INVALID;
+    return launch_gemm_tn_f32(q.M, q.N, (int)q.K, q.A, q.lda, q.a_group, q.a_gstride, q.B, q.ldb, q.b_group, q.b_gstride, q.C, q.ldc, q.accumulate,
+                              ws, ws_bytes, (hipStream_t)stream, true, q.colsum_out, q.colsum_accumulate);
+  }
   TnF32Multi m;
   m.n = n;
   char* wsp = reinterpret_cast<char*>(ws);

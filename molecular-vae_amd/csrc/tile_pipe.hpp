@@ -107,30 +107,6 @@ __device__ __forceinline__ void split_x3(const u32x4& c0, const u32x4& c1, uint4
   }
   hi = make_uint4(h[0], h[1], h[2], h[3]); lo = make_uint4(l[0], l[1], l[2], l[3]);
 }
-template <int MI, int NI, int JS, int BOUT>
-__device__ __forceinline__ void tile_mma_asm_x3(uint32_t a_base, uint32_t b_base, const uint32_t (&a_lane)[2], const uint32_t (&b_lane)[2],
-                                                f32x4 (&acc)[MI][NI]) {
-  u32x4 a0[MI], b0[NI], a1[MI], b1[NI];
-  FragRead<0, MI, 16 * KB>::run(a0, a_base + a_lane[0]);
-  FragReadB<0, NI, JS, BOUT>::run(b0, b_base + b_lane[0]);
-  FragRead<0, MI, 16 * KB>::run(a1, a_base + a_lane[1]);
-  FragReadB<0, NI, JS, BOUT>::run(b1, b_base + b_lane[1]);
-  wait_lgkmcnt<0>();
-  uint4 ah[MI], al[MI], bh[NI], bl[NI];
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi) split_x3(a0[mi], a1[mi], ah[mi], al[mi]);
-#pragma unroll
-  for (int ni = 0; ni < NI; ++ni) split_x3(b0[ni], b1[ni], bh[ni], bl[ni]);
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni) {
-      mma16<bf16_t>(al[mi], bh[ni], acc[mi][ni]);       // small terms first
-      mma16<bf16_t>(ah[mi], bl[ni], acc[mi][ni]);
-      mma16<bf16_t>(ah[mi], bh[ni], acc[mi][ni]);
-    }
-}
-
 // MFMAs of one K-step from LDS byte addresses (stage base already added).  JS / BOUT: layout of the wave's n-sub-tiles
 // (FragReadB).  a_lane / b_lane: per-lane byte offsets of (row l&15, chunk kk*4 + l>>4)
 // for kk = 0,1 relative to the wave's first A / B row.
@@ -186,10 +162,9 @@ __device__ __forceinline__ void pipe_issue_stage(char* smem, const PipeSeg<BM, B
 }
 
 // acc += sum over segment 0 then segment 1 of A_tile . B_tile^T.   smem: NBUF * (BM + BN) * 128 bytes.
-template <typename T, int BM, int BN, int MI, int NI, int NBUF, int JS, int BOUT, bool X3 = false>
+template <typename T, int BM, int BN, int MI, int NI, int NBUF, int JS, int BOUT>
 __device__ __forceinline__ void tile_gemm_pipe(char* smem, const PipeSeg<BM, BN>& s0, const PipeSeg<BM, BN>& s1, int arow0,
                                                int brow0, f32x4 (&acc)[MI][NI], int tid) {
-  static_assert(!X3 || std::is_same<T, float>::value, "the 3 x bf16 product form takes fp32 operands");
   constexpr int STAGE = (BM + BN) * KB;
   constexpr int LPS = (BM + BN) * 8 / 256;          // buffer loads per thread per stage
   static_assert((NBUF - 2) * LPS < 64, "vmcnt range");
@@ -216,8 +191,7 @@ __device__ __forceinline__ void tile_gemm_pipe(char* smem, const PipeSeg<BM, BN>
     asm volatile("" ::: "memory");                            // keep the fragment reads below the barrier
     if (kt + NBUF - 1 < nk) pipe_issue_stage<BM, BN, NBUF>(smem, s0, s1, kt + NBUF - 1, wave);   // refill the buffer stage kt-1 used
     const uint32_t st = lds0 + (uint32_t)((kt % NBUF) * STAGE);
-    if constexpr (X3) tile_mma_asm_x3<MI, NI, JS, BOUT>(st, st, a_lane, b_lane, acc);
-    else tile_mma_asm<T, MI, NI, JS, BOUT>(st, st, a_lane, b_lane, acc);
+    tile_mma_asm<T, MI, NI, JS, BOUT>(st, st, a_lane, b_lane, acc);
   }
   __builtin_amdgcn_s_barrier();                               // LDS free for the caller (epilogue scratch / next use)
 }
@@ -797,4 +771,44 @@ __device__ __forceinline__ void tile_gemm_tn_256(char* smem, const PipeSegTN2& s
         mma16<bf16_t>(__builtin_bit_cast(uint4, a1[mi]), __builtin_bit_cast(uint4, b1[ni]), acc[mi][ni]);
   }
   ws_barrier();
+}
+
+// =====================================================================================================================
+// 3 x bf16 product form on SPLIT-ONCE LDS images (gemm.hip gemm_tn_x3_kernel / gemm_nt_x3_kernel): the fp32 operands are split into their
+// bf16 hi and lo parts at the LDS fill, once per workgroup, and kept as two bf16 planes; the main loop then is the bf16 loop with three
+// MFMAs per fragment pair.  split_x3_4 is split_x3's arithmetic on one float4: hi and lo are bit for bit the values that form multiplies.
+// =====================================================================================================================
+__device__ __forceinline__ void split_x3_4(const float4& v, uint2& hi, uint2& lo) {
+  const uint32_t h0 = __builtin_bit_cast(uint32_t, v.x) & 0xffff0000u, h1 = __builtin_bit_cast(uint32_t, v.y) & 0xffff0000u;
+  const uint32_t h2 = __builtin_bit_cast(uint32_t, v.z) & 0xffff0000u, h3 = __builtin_bit_cast(uint32_t, v.w) & 0xffff0000u;
+  const float l0 = v.x - __builtin_bit_cast(float, h0), l1 = v.y - __builtin_bit_cast(float, h1);
+  const float l2 = v.z - __builtin_bit_cast(float, h2), l3 = v.w - __builtin_bit_cast(float, h3);
+  hi = make_uint2((h0 >> 16) | h1, (h2 >> 16) | h3);
+  // f2bf's rounding, two at a time (one v_cvt_pk_bf16_f32 per pair)
+  typedef float f32x2_t __attribute__((ext_vector_type(2)));
+  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+  lo = make_uint2(__builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){l0, l1}, bf16x2_t)),
+                  __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){l2, l3}, bf16x2_t)));
+}
+// the three products of every fragment pair, small terms first (the order of gemm_tn_f32_body<true, *>)
+template <int MI, int NI>
+__device__ __forceinline__ void mma_x3_block(const u32x4 (&ah)[MI], const u32x4 (&al)[MI], const u32x4 (&bh)[NI], const u32x4 (&bl)[NI],
+                                             f32x4 (&acc)[MI][NI]) {
+#pragma unroll
+  for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni) {
+      mma16<bf16_t>(__builtin_bit_cast(uint4, al[mi]), __builtin_bit_cast(uint4, bh[ni]), acc[mi][ni]);
+      mma16<bf16_t>(__builtin_bit_cast(uint4, ah[mi]), __builtin_bit_cast(uint4, bl[ni]), acc[mi][ni]);
+      mma16<bf16_t>(__builtin_bit_cast(uint4, ah[mi]), __builtin_bit_cast(uint4, bh[ni]), acc[mi][ni]);
+    }
+}
+// Bank swizzle of a K-major bf16 plane with ROWB-byte rows, XOR-ed into the index of a row's 32-byte column block (TN form above).  The eight
+// k-rows 8g + q (g = 0, 1; q = 0..3) that one 32-lane half of a transposed read touches must land on eight different 32-byte bank groups of
+// the 256-byte bank line: 256-byte (and longer) rows all start on bank 0, so the block index takes all three bits (tn_f); 128-byte rows
+// alternate between the two halves of the bank line by themselves (k & 1), and the block index takes the other two bits.
+template <int ROWB> __device__ __forceinline__ uint32_t tnx_f(int krow) {
+  static_assert(ROWB == 128 || ROWB % 256 == 0, "row length");
+  if constexpr (ROWB == 128) return (uint32_t)(((krow >> 1) & 1) | (((krow >> 3) & 1) << 1));
+  else return tn_f(krow);
 }
