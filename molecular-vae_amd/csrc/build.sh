@@ -24,7 +24,8 @@ if [ "${1:-}" = "tune" ]; then
 fi
 pids=()
 for f in gemm rnn rnn_rowres rnn_persist rnn_persist_bwd fragment_smiles fragment scaffold_smiles smiles_substruct smiles_canon smiles_rewrite kekule moses_decode scaffold fingerprint smiles_graph elementwise edit_distance latent_knn corpus_index conv latent capi; do
-  if [ ! -f build/$f.o ] || [ $f.hip -nt build/$f.o ] || [ common.hpp -nt build/$f.o ] || [ tile.hpp -nt build/$f.o ] || [ tile_pipe.hpp -nt build/$f.o ] || [ kernels.hpp -nt build/$f.o ] || [ persist_common.hpp -nt build/$f.o ] || [ smiles_syntax.hpp -nt build/$f.o ] || [ smiles_graph.hpp -nt build/$f.o ] || [ smiles_rounds.hpp -nt build/$f.o ] || [ smiles_writer.hpp -nt build/$f.o ] || [ smiles_canon.hpp -nt build/$f.o ] || [ scaffold_sets.hpp -nt build/$f.o ] || [ graph_key.hpp -nt build/$f.o ] || [ fragment_sets.hpp -nt build/$f.o ] || [ smiles_cut.hpp -nt build/$f.o ] || [ ../../include/mvae.h -nt build/$f.o ]; then
+  if [ ! -f build/$f.o ] || [ $f.hip -nt build/$f.o ] || [ common.hpp -nt build/$f.o ] || [ tile.hpp -nt build/$f.o ] || [ tile_pipe.hpp -nt build/$f.o ] || [ kernels.hpp -nt build/$f.o ] || [ persist_common.hpp -nt build/$f.o ] || [ smiles_syntax.hpp -nt build/$f.o ] || [ smiles_graph.hpp -nt build/$f.o ] || [ smiles_rounds.hpp -nt build/$f.o ] || [ smiles_writer.hpp -nt build/$f.o ] || [ smiles_canon.hpp -nt build/$f.o ] || [ scaffold_sets.hpp -nt build/$f.o ] || [ graph_key.hpp -nt build/$f.o ] || [ fragment_sets.hpp -nt build/$f.o ] || [ smiles_cut.hpp -nt build/$f.o ] || [ ../../include/mvae.h -nt build/$f.o ] || [ -n "$(find . -maxdepth 1 -name '*.hpp' -newer build/$f.o)" ]; then
+    # (the last test covers every header of this directory, the named ones and any added later)
     # -Rpass-analysis: per-kernel VGPR / scratch / spill figures go to build/$f.usage.txt (tests assert that no kernel uses scratch)
     $HIPCC $FLAGS $(xflags $f) -Rpass-analysis=kernel-resource-usage -c $f.hip -o build/$f.o 2> build/$f.usage.txt &
     pids+=($!)

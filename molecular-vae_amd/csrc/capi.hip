@@ -2,10 +2,6 @@
 #include "common.hpp"
 #include "kernels.hpp"
 
-int rnn_fwd_impl(const mvae_rnn_fwd_desc* d, hipStream_t st);
-int rnn_bwd_impl(const mvae_rnn_bwd_desc* d, hipStream_t st);
-size_t rnn_bwd_workspace_bytes(const mvae_rnn_bwd_desc* d);
-
 thread_local const void* mvae_tls_status = nullptr;
 
 extern "C" {
@@ -22,10 +18,7 @@ size_t mvae_struct_size(int which) {
   }
 }
 
-int mvae_knob_int(const char* name, int dflt) {
-  const char* v = name ? mvae_knob(name) : nullptr;
-  return v ? atoi(v) : dflt;
-}
+int mvae_knob_int(const char* name, int dflt) { return name ? knob_int(name, dflt) : dflt; }
 
 const char* mvae_status_string(int status) {
   switch (status) {
@@ -81,9 +74,10 @@ int mvae_dropout_keep(uint32_t seed, uint32_t idx, float p) {
 
 int mvae_rnn_fwd(const mvae_rnn_fwd_desc* d, void* stream, const void** status_out) {
   mvae_tls_status = nullptr;
-  const int rc = (d && d->persist_ws && !d->no_spin && rnn_persist_fwd_supported(d))
-                     ? rnn_persist_fwd(d, d->persist_ws, d->persist_ws_bytes, (hipStream_t)stream)
-                     : rnn_fwd_impl(d, (hipStream_t)stream);      // (the row-resident f32 stacks use persist_ws for their layer-concurrent form)
+  // the weights-resident dataflow pass where it serves the shape (it says so itself; too little workspace for a served shape is an error),
+  // else every other schedule (the row-resident f32 stacks use persist_ws for their layer-concurrent form)
+  int rc = (d && d->persist_ws && !d->no_spin) ? rnn_persist_fwd(d, d->persist_ws, d->persist_ws_bytes, (hipStream_t)stream) : MVAE_ERR_UNSUPPORTED;
+  if (rc == MVAE_ERR_UNSUPPORTED) rc = rnn_fwd_impl(d, (hipStream_t)stream);
   if (status_out) *status_out = rc == MVAE_OK ? mvae_tls_status : nullptr;
   return rc;
 }
@@ -94,9 +88,8 @@ size_t mvae_rnn_fwd_persist_workspace(const mvae_rnn_fwd_desc* d) {
 }
 int mvae_rnn_bwd(const mvae_rnn_bwd_desc* d, void* stream, const void** status_out) {
   mvae_tls_status = nullptr;
-  const int rc = (d && d->persist_ws && !d->no_spin && rnn_persist_bwd_supported(d))
-                     ? rnn_persist_bwd(d, d->persist_ws, d->persist_ws_bytes, (hipStream_t)stream)
-                     : rnn_bwd_impl(d, (hipStream_t)stream);
+  int rc = (d && d->persist_ws && !d->no_spin) ? rnn_persist_bwd(d, d->persist_ws, d->persist_ws_bytes, (hipStream_t)stream) : MVAE_ERR_UNSUPPORTED;
+  if (rc == MVAE_ERR_UNSUPPORTED) rc = rnn_bwd_impl(d, (hipStream_t)stream);
   if (status_out) *status_out = rc == MVAE_OK ? mvae_tls_status : nullptr;
   return rc;
 }

@@ -24,6 +24,7 @@
 #include <limits.h>
 
 #include "common.hpp"
+#include "launch.hpp"
 
 namespace {
 
@@ -415,12 +416,7 @@ int mvae_edit_knn(int Q, int T, int V, int eos, const int64_t* x, int64_t x_ld, 
     part_d = (int*)(part_j + (size_t)p.slots * (size_t)Q * (size_t)k);
   }
   const size_t smem = ed_smem_bytes(V, k);
-  static bool attr_set = false;                                         // V = 64 with k = 32 needs a little over the default 64 KB
-  if (!attr_set) {
-    MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(edit_knn_scan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)ed_smem_bytes(ED_V_MAX, ED_K_MAX)));
-    attr_set = true;
-  }
+  MVAE_CHECK_HIP(lds_opt_in<edit_knn_scan_kernel>((int)ed_smem_bytes(ED_V_MAX, ED_K_MAX)));      // V = 64 with k = 32 needs a little over the default 64 KB
   const hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(edit_knn_scan_kernel, dim3(p.qtiles, (unsigned)p.slots), dim3(256), smem, st, Q, (long)N, T, V, eos, k, x, (long)x_ld, tokens,
                      offsets, exclude, p.slot_rows, dist, (long*)idx, part_d, part_j);

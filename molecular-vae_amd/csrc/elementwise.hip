@@ -1687,7 +1687,7 @@ int mvae_lambda_bwd(int B, int o, const float* mulv, const float* eps, const flo
   return MVAE_OK;
 }
 
-static bool softmax_tiled_ok() { const char* e = mvae_knob("MVAE_SOFTMAX_TILED"); return !e || atoi(e) != 0; }
+static bool softmax_tiled_ok() { return knob_on("MVAE_SOFTMAX_TILED", true); }
 int mvae_softmax_tb_fwd(int B, int L, int C, const float* logits, int64_t ldl, float* recon, void* stream) {
   if (!logits || !recon || B < 1 || L < 1 || C < 1) return MVAE_ERR_INVALID;
   const long rows = (long)B * L;
@@ -1705,13 +1705,7 @@ int mvae_softmax_tb_fwd(int B, int L, int C, const float* logits, int64_t ldl, f
   }
   if (ldl == C && softmax_tiled_ok() && ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(recon)) & 15) == 0) {
     // tiled form: densely packed logits (what MolDecoder produces); 16 x 16 tiles (256 threads) up to 40 classes, 8 x 16 beyond (LDS)
-    static bool attr_set = false;
-    if (!attr_set) {
-      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(softmax_tile_fwd_kernel<16, 16, 40>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(softmax_tile_fwd_kernel<8, 16, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(softmax_tile_fwd_kernel<8, 16, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr_set = true;
-    }
+    MVAE_CHECK_HIP((lds_opt_in<softmax_tile_fwd_kernel<16, 16, 40>, softmax_tile_fwd_kernel<8, 16, 64>, softmax_tile_fwd_kernel<8, 16, 128>>(160 * 1024)));
     const int CP = C | 1;
     if (C <= 40) {
       const unsigned grid = (unsigned)(((B + 15) / 16) * ((L + 15) / 16));
@@ -1746,13 +1740,7 @@ int mvae_softmax_tb_bwd(int dtype, int B, int L, int C, const float* recon, cons
   }
   if (dtype == MVAE_BF16 && !dlT && softmax_tiled_ok() && (ldd % 8) == 0 && ldd >= ((C + 7) & ~7) &&
       ((reinterpret_cast<uintptr_t>(recon) | reinterpret_cast<uintptr_t>(drecon) | reinterpret_cast<uintptr_t>(dl)) & 15) == 0) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(softmax_tile_bwd_kernel<16, 16, 40>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(softmax_tile_bwd_kernel<8, 16, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(softmax_tile_bwd_kernel<8, 16, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr_set = true;
-    }
+    MVAE_CHECK_HIP((lds_opt_in<softmax_tile_bwd_kernel<16, 16, 40>, softmax_tile_bwd_kernel<8, 16, 64>, softmax_tile_bwd_kernel<8, 16, 128>>(160 * 1024)));
     const int CP = C | 1;
     if (C <= 40) {
       const unsigned grid = (unsigned)(((B + 15) / 16) * ((L + 15) / 16));

@@ -518,21 +518,14 @@ int launch_gemm_nt_grouped(int dtype, int M, int N, int K, const void* A, long l
   }
   dim3 grid(pl.tiles_m * pl.tiles_n, pl.splits), block(256);
   const size_t lds = (size_t)(x3k ? 2 : pipe ? 4 : 2) * (pl.bm + pl.bn) * KB;     // x3k: one stage, hi and lo planes
-#define MVAE_GEMM_LAUNCH2(TT_, BM_, BN_, PIPE_)                                                       \
-  do {                                                                                                \
-    auto kern = gemm_nt_kernel<TT_, BM_, BN_, PIPE_>;                                                 \
-    static bool attr_set = false;                                                                     \
-    if (!attr_set) { MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr_set = true; } \
-    hipLaunchKernelGGL(kern, grid, block, lds, st, p);                                                \
+#define MVAE_GEMM_LAUNCH_KERN(KERN)                     \
+  do {                                                    \
+    MVAE_CHECK_HIP(lds_opt_in<KERN>(160 * 1024));         \
+    hipLaunchKernelGGL(KERN, grid, block, lds, st, p);    \
   } while (0)
+#define MVAE_GEMM_LAUNCH2(TT_, BM_, BN_, PIPE_) MVAE_GEMM_LAUNCH_KERN((gemm_nt_kernel<TT_, BM_, BN_, PIPE_>))
 #define MVAE_GEMM_LAUNCH(TT_, BM_, PIPE_) MVAE_GEMM_LAUNCH2(TT_, BM_, BM_, PIPE_)
-#define MVAE_GEMM_LAUNCH3(BM_, BN_)                                                                   \
-  do {                                                                                                \
-    auto kern = gemm_nt_x3_kernel<BM_, BN_>;                                                          \
-    static bool attr_set = false;                                                                     \
-    if (!attr_set) { MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr_set = true; } \
-    hipLaunchKernelGGL(kern, grid, block, lds, st, p);                                                \
-  } while (0)
+#define MVAE_GEMM_LAUNCH3(BM_, BN_) MVAE_GEMM_LAUNCH_KERN((gemm_nt_x3_kernel<BM_, BN_>))
   if (pl.bn == 32) {
     if (pipe) MVAE_GEMM_LAUNCH2(float, 128, 32, true); else MVAE_GEMM_LAUNCH2(float, 128, 32, false);
   } else if (dtype == MVAE_BF16) {
@@ -547,6 +540,7 @@ int launch_gemm_nt_grouped(int dtype, int M, int N, int K, const void* A, long l
 #undef MVAE_GEMM_LAUNCH
 #undef MVAE_GEMM_LAUNCH2
 #undef MVAE_GEMM_LAUNCH3
+#undef MVAE_GEMM_LAUNCH_KERN
   MVAE_CHECK_HIP(hipGetLastError());
   if (pl.splits > 1) {
     long n = (long)M * N;
@@ -563,8 +557,7 @@ namespace {
 Plan make_plan_tn(int M, int N, int K) {
   Plan pl;
   // 256 x 128 tiles (half the operand bytes per output of 128 x 128) whenever they still give >= 128 tiles: split-K then fills the chip
-  const char* fe = mvae_knob("MVAE_TN_BM");
-  const int force_bm = fe ? atoi(fe) : 0;
+  const int force_bm = knob_int("MVAE_TN_BM", 0);
   pl.bm = ((long)((M + 255) / 256) * ((N + 127) / 128) >= 128) ? 256 : 128;
   // 256 x 256 (pl.bm = 512 as its tag): another third less operand traffic per FLOP; needs whole tiles' worth of work and enough K to split
   if ((long)((M + 255) / 256) * ((N + 255) / 256) >= 32 && N % 256 == 0 && K >= 64 * 64) pl.bm = 512;
@@ -651,14 +644,7 @@ int launch_gemm_tn_bf16_colsum(int M, int N, int K, const void* A, long lda, con
   }
   p.colsum_out = colsum_out;
   dim3 grid(pl.tiles_m * pl.tiles_n, pl.splits);
-  static bool attr_set = false;
-  if (!attr_set) {
-    MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_bf16_kernel<4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_bf16_kernel<3, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_bf16_256_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_bf16_256_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
+  MVAE_CHECK_HIP((lds_opt_in<gemm_tn_bf16_kernel<4, 4>, gemm_tn_bf16_kernel<3, 8>, gemm_tn_bf16_256_kernel<false>, gemm_tn_bf16_256_kernel<true>>(160 * 1024)));
   if (pl.bm == 512) {
     if (colsum_out) hipLaunchKernelGGL(gemm_tn_bf16_256_kernel<true>, grid, dim3(512), 2 * 65536, st, p);
     else hipLaunchKernelGGL(gemm_tn_bf16_256_kernel<false>, grid, dim3(512), 2 * 65536, st, p);
@@ -1116,12 +1102,7 @@ int launch_gemm_tn_f32(int M, int N, int R, const float* A, long lda, int a_grou
   }
   const dim3 tgrid(pl.tiles_m * pl.tiles_n, pl.splits);
   if (x3k) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_x3_kernel<1, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_x3_kernel<1, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr_set = true;
-    }
+    MVAE_CHECK_HIP((lds_opt_in<gemm_tn_x3_kernel<1, 2, false>, gemm_tn_x3_kernel<1, 2, true>>(160 * 1024)));
     const size_t lds = (size_t)2 * TNX_KS * 2 * (pl.bm + pl.bn);        // hi and lo planes of one 64-row stage of both operands
     if (colsum_out) hipLaunchKernelGGL((gemm_tn_x3_kernel<1, 2, true>), tgrid, dim3(256), lds, st, p);
     else hipLaunchKernelGGL((gemm_tn_x3_kernel<1, 2, false>), tgrid, dim3(256), lds, st, p);
@@ -1254,12 +1235,7 @@ extern "C" int mvae_gemm_tn_grouped_capped(int n, const mvae_gemm_tn_problem* pr
     tiles += g.tiles_m * g.tiles_n;
   }
   a.ngroups = n; a.ntiles = tiles;
-  static bool attr_set = false;
-  if (!attr_set) {
-    MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_bf16_256_grouped_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_bf16_256_grouped_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
+  MVAE_CHECK_HIP((lds_opt_in<gemm_tn_bf16_256_grouped_kernel<false>, gemm_tn_bf16_256_grouped_kernel<true>>(160 * 1024)));
   int grid = tiles;
   if (max_workgroups > 0 && max_workgroups < grid) grid = max_workgroups;
   if (any_cs) hipLaunchKernelGGL(gemm_tn_bf16_256_grouped_kernel<true>, dim3(grid), dim3(512), 2 * 65536, st, a);

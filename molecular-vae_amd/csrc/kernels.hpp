@@ -1,9 +1,9 @@
 // Internal launcher declarations (host side).  The extern "C" surface is include/mvae.h.
 #pragma once
-#include <atomic>
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include "../../include/mvae.h"
+#include "launch.hpp"
 
 size_t gemm_nt_workspace_bytes(int M, int N, int K, int dtype);
 int launch_gemm_nt(int dtype, int M, int N, int K, const void* A, long lda, const void* B, long ldb, void* C, long ldc,
@@ -37,7 +37,6 @@ int launch_corpus_index_probe(const uint8_t* tokens, const int64_t* offsets, int
 // Where the launches of the current mvae_rnn_fwd / mvae_rnn_bwd call report a bounded spin that ran out (capi.hip clears it before dispatching
 // and hands it to the caller as *status_out): set by every launcher that enqueues a kernel with bounded spins, left alone by the others.
 extern thread_local const void* mvae_tls_status;
-constexpr int MVAE_MAX_DEVICES = 64;
 
 // rnn_persist.hip: weights-resident dataflow LSTM forward (b = 128, 4 x 1024, bf16)
 bool rnn_persist_fwd_supported(const mvae_rnn_fwd_desc* d);
@@ -47,4 +46,14 @@ int rnn_persist_fwd(const mvae_rnn_fwd_desc* d, void* ws, size_t ws_bytes, hipSt
 bool rnn_persist_bwd_supported(const mvae_rnn_bwd_desc* d);
 size_t rnn_persist_bwd_workspace_bytes(int T);
 int rnn_persist_bwd(const mvae_rnn_bwd_desc* d, void* ws, size_t ws_bytes, hipStream_t st);
-size_t rnn_rowres_fwd_pipe_workspace(const mvae_rnn_fwd_desc* d);     // rnn_rowres.hip: layer-concurrent row-resident LSTM forward
+// rnn_rowres.hip: row-resident schedules (narrow f32 LSTM stacks; the one-layer bf16 GRU(256)); MVAE_ERR_UNSUPPORTED = not their shape
+size_t rnn_rowres_fwd_pipe_workspace(const mvae_rnn_fwd_desc* d);     // layer-concurrent LSTM forward: 0 = shape / device not served
+int rnn_rowres_fwd(const mvae_rnn_fwd_desc* d, hipStream_t st);
+size_t rnn_rowres_bwd_workspace(int layers, int T, int B, int H);
+int rnn_rowres_bwd(const mvae_rnn_bwd_desc* d, hipStream_t st);
+int rnn_gru_rowres_fwd(const mvae_rnn_fwd_desc* d, hipStream_t st);
+int rnn_gru_rowres_bwd(const mvae_rnn_bwd_desc* d, hipStream_t st);
+// rnn.hip: argument checks, then the row-resident schedules where they serve the shape, else the layer-wavefront launches
+int rnn_fwd_impl(const mvae_rnn_fwd_desc* d, hipStream_t st);
+int rnn_bwd_impl(const mvae_rnn_bwd_desc* d, hipStream_t st);
+size_t rnn_bwd_workspace_bytes(const mvae_rnn_bwd_desc* d);

@@ -77,19 +77,6 @@ __device__ __forceinline__ bool commit_token(long b, int w, int step, int eos_id
   return open;
 }
 
-// A head above the default 64 KB dynamic-LDS limit: opt both dtypes of a kernel in, once per device (`done` is the caller's
-// static std::atomic<bool>[MVAE_MAX_DEVICES]: the attribute is per kernel function, so every instantiation pair has its own).
-static hipError_t lds_opt_in(std::atomic<bool>* done, const void* kernel_f32, const void* kernel_bf16, int cap) {
-  int dev_id = 0;
-  hipError_t e = hipGetDevice(&dev_id);
-  if (e != hipSuccess) return e;
-  const bool known = dev_id >= 0 && dev_id < MVAE_MAX_DEVICES;
-  if (known && done[dev_id].load(std::memory_order_acquire)) return hipSuccess;
-  e = hipFuncSetAttribute(kernel_f32, hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-  if (e == hipSuccess) e = hipFuncSetAttribute(kernel_bf16, hipFuncAttributeMaxDynamicSharedMemorySize, cap);
-  if (e == hipSuccess && known) done[dev_id].store(true, std::memory_order_release);
-  return e;
-}
 // the launch statement given, once for either compute dtype (the callers have refused every other value): inside it `T` is the element type
 #define DECODE_BY_DTYPE(dtype, ...) do { if ((dtype) == MVAE_BF16) { using T = bf16_t; __VA_ARGS__; } else { using T = float; __VA_ARGS__; } } while (0)
 static size_t head_lds_bytes(int dtype, int V, int H) { return (size_t)V * H * (dtype == MVAE_BF16 ? 2 : 4); }
@@ -463,11 +450,9 @@ static int sample_filtered_launch(int dtype, int B, int V, int H, const void* h_
                                   const int32_t* forced = nullptr, int64_t forced_ld = 0) {
   const size_t lds = head_lds_bytes(dtype, V, H);
   if (lds > 160 * 1024) return MVAE_ERR_UNSUPPORTED;                 // the head must fit the CU's LDS, as in mvae_moses_sample_step
-  if (lds > 64 * 1024) {
-    static std::atomic<bool> attr[MVAE_MAX_DEVICES];                 // (per instantiation)
-    MVAE_CHECK_HIP(lds_opt_in(attr, reinterpret_cast<const void*>(moses_sample_filtered_step_kernel<float, SYNTAX, FORCED>),
-                          reinterpret_cast<const void*>(moses_sample_filtered_step_kernel<bf16_t, SYNTAX, FORCED>), 160 * 1024));
-  }
+  // a head above the default 64 KB dynamic-LDS limit: both dtypes of the kernel are opted in
+  if (lds > 64 * 1024)
+    MVAE_CHECK_HIP((lds_opt_in<moses_sample_filtered_step_kernel<float, SYNTAX, FORCED>, moses_sample_filtered_step_kernel<bf16_t, SYNTAX, FORCED>>(160 * 1024)));
   if (top_p > 1.f) top_p = 1.f;                                       // larger values mean off
   int blocks = (B + 3) / 4; if (blocks > 1024) blocks = 1024;
   DECODE_BY_DTYPE(dtype, hipLaunchKernelGGL((moses_sample_filtered_step_kernel<T, SYNTAX, FORCED>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, B, V, H,
@@ -503,11 +488,8 @@ static int beam_step_launch(int dtype, int B, int K, int V, int H, int layers, v
   const size_t lds = head_lds_bytes(dtype, V, H);
   constexpr size_t lds_cap = 156 * 1024;                             // the CU's 160 KB less the kernel's static candidate arrays
   if (lds > lds_cap) return MVAE_ERR_UNSUPPORTED;
-  if (lds > 64 * 1024) {
-    static std::atomic<bool> attr[MVAE_MAX_DEVICES];                 // (per instantiation)
-    MVAE_CHECK_HIP(lds_opt_in(attr, reinterpret_cast<const void*>(moses_beam_step_kernel<float, SYNTAX, FORCED>),
-                          reinterpret_cast<const void*>(moses_beam_step_kernel<bf16_t, SYNTAX, FORCED>), (int)lds_cap));
-  }
+  if (lds > 64 * 1024)
+    MVAE_CHECK_HIP((lds_opt_in<moses_beam_step_kernel<float, SYNTAX, FORCED>, moses_beam_step_kernel<bf16_t, SYNTAX, FORCED>>((int)lds_cap)));
   const int G = K >= 4 ? 1 : 4 / K;
   int blocks = (B + G - 1) / G; if (blocks > 1024) blocks = 1024;
   DECODE_BY_DTYPE(dtype, hipLaunchKernelGGL((moses_beam_step_kernel<T, SYNTAX, FORCED>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, B, K, V, H, layers,
@@ -528,11 +510,7 @@ int mvae_moses_sample_step(int dtype, int B, int V, int H, const void* h_top, in
     return MVAE_ERR_INVALID;
   const size_t lds = head_lds_bytes(dtype, V, H);
   if (lds > 160 * 1024) return MVAE_ERR_UNSUPPORTED;                 // the head must fit the CU's LDS (fp32, H = 512: V <= 80; bf16: V <= 64 by the check above)
-  if (lds > 64 * 1024) {
-    static std::atomic<bool> attr[MVAE_MAX_DEVICES];
-    MVAE_CHECK_HIP(lds_opt_in(attr, reinterpret_cast<const void*>(moses_sample_step_kernel<float>),
-                          reinterpret_cast<const void*>(moses_sample_step_kernel<bf16_t>), 160 * 1024));
-  }
+  if (lds > 64 * 1024) MVAE_CHECK_HIP((lds_opt_in<moses_sample_step_kernel<float>, moses_sample_step_kernel<bf16_t>>(160 * 1024)));
   int blocks = (B + 3) / 4; if (blocks > 1024) blocks = 1024;
   DECODE_BY_DTYPE(dtype, hipLaunchKernelGGL((moses_sample_step_kernel<T>), dim3(blocks), dim3(256), lds, (hipStream_t)stream, B, V, H, (const T*)h_top,
                                      (long)ldh, (const T*)w_fc, (long)ldw, bias, 1.f / temp, seed, step, eos_id, table, W, base, add_out, x,

@@ -1,5 +1,6 @@
 // Helpers shared by the weights-resident dataflow kernels (rnn_persist.hip: forward, rnn_persist_bwd.hip: backward): LDS accesses the compiler's
-// waitcnt pass must not see, bounded flag polls, compile-time slot unrolling.
+// waitcnt pass must not see, bounded flag polls, compile-time slot unrolling -- and, with the layer-concurrent row-resident kernels
+// (rnn_rowres.hip), the record a bounded spin leaves when it runs out.
 #pragma once
 #include "common.hpp"
 #include "tile_pipe.hpp"
@@ -36,6 +37,19 @@ __device__ __forceinline__ bool wait_flags(const uint32_t* f, const uint32_t* st
     __builtin_amdgcn_s_sleep(2);
   }
   return false;
+}
+
+// A bounded spin ran out.  The status record of a launch is four words, all zero while nobody has given up: [code, block, layer, -].  The
+// FIRST caller of the launch writes it -- code = which wait ran out, block = its workgroup, layer = the layer that workgroup runs -- and
+// stores a NaN to the caller's poison slot when there is one; everybody else finds status[0] taken and only drains (wait_flags reads it).
+constexpr uint32_t SPIN_FLAG_WAIT = 1u;     // dataflow kernels (rnn_persist*.hip): a (layer, step) flag row did not fill
+constexpr uint32_t SPIN_ROWRES_BWD = 2u;    // row-resident backward: the layer above did not hand its dx over
+constexpr uint32_t SPIN_ROWRES_FWD = 3u;    // row-resident forward: the layer below did not hand its h over
+__device__ __forceinline__ void spin_give_up(uint32_t* status, uint32_t code, int layer, float* poison) {
+  if (atomicCAS(status, 0u, code) == 0u) {
+    status[1] = blockIdx.x; status[2] = (uint32_t)layer;
+    if (poison) *poison = __builtin_nanf("");
+  }
 }
 
 __device__ __forceinline__ void wait_vm(int n) {      // n is a compile-time constant after unrolling: the switch folds to one s_waitcnt

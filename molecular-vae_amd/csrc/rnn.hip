@@ -1156,30 +1156,20 @@ __global__ __launch_bounds__(256) void lstm_bwd_epi_kernel(StepArgsB p) {
 }
 
 // ---------------------------------------------------------------------------------------------- host drivers
-#define MVAE_STEP_LAUNCH(KERN)                                                                                     \
-  do {                                                                                                               \
-    auto kern = KERN;                                                                                                \
-    static bool attr_set = false;                                                                                    \
-    if (!attr_set) { MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr_set = true; } \
-    hipLaunchKernelGGL(kern, grid, block, lds, st, a);                                                               \
+#define MVAE_STEP_LAUNCH(KERN)                          \
+  do {                                                    \
+    MVAE_CHECK_HIP(lds_opt_in<KERN>(160 * 1024));         \
+    hipLaunchKernelGGL(KERN, grid, block, lds, st, a);    \
   } while (0)
-
-// Schedule knobs (read per call; every setting computes the same results -- the GPU tests force each tile variant through them):
-// MVAE_NBUF_FWD / MVAE_NBUF_BWD = LDS ring depth, MVAE_BM / MVAE_BJ / MVAE_FWD_GM = tile, MVAE_BWD_SPLIT.  MVAE_DBG (skip parts of a
-// kernel, results WRONG) exists only in the diagnostic build (-DMVAE_TUNING); the product library ignores it.
-static int tune_int(const char* name, int dflt) {
-  const char* v = mvae_knob(name);
-  return v ? atoi(v) : dflt;
-}
 
 static inline const char* adv(const void* p, long elems, int dtype) {
   return reinterpret_cast<const char*>(p) + elems * (dtype == MVAE_BF16 ? 2 : 4);
 }
 static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-int rnn_rowres_fwd(const mvae_rnn_fwd_desc* d, hipStream_t st);
-int rnn_gru_rowres_fwd(const mvae_rnn_fwd_desc* d, hipStream_t st);
-
+// Schedule knobs that rnn_fwd_impl / rnn_bwd_impl read (knob_int): MVAE_NBUF_FWD / MVAE_NBUF_BWD = LDS ring depth, MVAE_BM / MVAE_BJ /
+// MVAE_FWD_GM = tile, MVAE_BWD_SPLIT.  MVAE_DBG (skip parts of a kernel, results WRONG) exists only in the diagnostic build (-DMVAE_TUNING);
+// the product library ignores it.
 int rnn_fwd_impl(const mvae_rnn_fwd_desc* d, hipStream_t st) {
   if (!d) return MVAE_ERR_INVALID;
   if (d->cell != MVAE_CELL_LSTM && d->cell != MVAE_CELL_GRU) return MVAE_ERR_UNSUPPORTED;
@@ -1227,7 +1217,7 @@ int rnn_fwd_impl(const mvae_rnn_fwd_desc* d, hipStream_t st) {
   auto nblk = [&](int bm) { return (long)((B + bm - 1) / bm) * ((H + 31) / 32) * NL; };
   int BM = (nblk(128) >= 256) ? 128 : (nblk(64) >= 256 || dt == MVAE_BF16) ? 64 : 32;
   if (dt == MVAE_BF16) BM = 64;     // measured (B=512, H=1024): 64-row tiles with a 3-deep ring keep two workgroups per CU -> 53 vs 64 us/launch
-  BM = tune_int("MVAE_BM", BM);
+  BM = knob_int("MVAE_BM", BM);
   if (BM == 32 && dt == MVAE_BF16) BM = 64;
   const int sz = (dt == MVAE_BF16) ? 2 : 4, ke = KB / sz;
   // contraction length over the hidden axis: H, or H rounded up to whole K-steps when the caller guarantees zero padding
@@ -1254,13 +1244,13 @@ int rnn_fwd_impl(const mvae_rnn_fwd_desc* d, hipStream_t st) {
   // wide tile (128 rows x 64 units x 4 gates, one workgroup per CU): (128 + 256) operand rows per 32768 outputs -- half the L2->LDS
   // traffic per output of the 64 x 128 tile; used when it still gives >= 256 workgroups per full launch.  MVAE_BJ overrides.
   int BJ = (pipe && dt == MVAE_BF16 && (long)((B + 127) / 128) * ((H + 63) / 64) * NL >= 256) ? 64 : 32;
-  BJ = tune_int("MVAE_BJ", BJ);
+  BJ = knob_int("MVAE_BJ", BJ);
   if (BJ == 64 && (!pipe || dt != MVAE_BF16)) BJ = 32;
   if (BJ == 64) BM = 128;
   // gate-major tile (lstm_step_fwd_gm_kernel: LSTM, bf16, epilogue in registers): the largest of (64 units x 256 rows), (64 x 128),
   // (32 x 128), (32 x 64) that still gives about one workgroup per CU.  MVAE_FWD_GM: 0 = never, 1 = choose, 256256 / 256128 / 128128 /
   // 128064 = force that (weight rows, batch rows) tile (tests).
-  const int gm_knob = tune_int("MVAE_FWD_GM", 1);
+  const int gm_knob = knob_int("MVAE_FWD_GM", 1);
   int BMW = 0, BNB = 0;
   for (int l = 0; l < NL && drop; ++l) if (d->hdrop[l] && (!al16(d->hdrop[l]))) vec = false;
   if (gm_knob && !gru && !drop && !d->add_table && dt == MVAE_BF16 && pipe && vec && H % 64 == 0) {
@@ -1281,7 +1271,7 @@ int rnn_fwd_impl(const mvae_rnn_fwd_desc* d, hipStream_t st) {
   a.drop.seed = d->drop_seed;
   a.gru3 = gru ? 1 : 0;       // GRU: never fetch the zero gate-slot block of either segment
 #ifdef MVAE_TUNING
-  a.dbg = tune_int("MVAE_DBG", 0);
+  a.dbg = knob_int("MVAE_DBG", 0);
 #else
   a.dbg = 0;
 #endif
@@ -1290,10 +1280,10 @@ int rnn_fwd_impl(const mvae_rnn_fwd_desc* d, hipStream_t st) {
   // 768 (MOSES 7.28 -> 7.08 ms / step, models2d 10.18 -> 9.75); with 512 tiles (LSTM 4 x 1024 at B = 256) the deeper ring stays ahead.
   int nbuf_dflt = (BJ == 64) ? 3 : (dt == MVAE_BF16 && BM == 64) ? 3 : 4;
   if (dt == MVAE_BF16 && BM == 64 && BJ == 32 && !BMW) {
-    const long nb = (long)((B + BM - 1) / BM) * ((H + BJ - 1) / BJ) * NL, cus = 256;
-    if ((nb + 3 * cus - 1) / (3 * cus) < (nb + 2 * cus - 1) / (2 * cus)) nbuf_dflt = 2;
+    const long nb = (long)((B + BM - 1) / BM) * ((H + BJ - 1) / BJ) * NL, cus = device_cus();
+    if (cus > 0 && (nb + 3 * cus - 1) / (3 * cus) < (nb + 2 * cus - 1) / (2 * cus)) nbuf_dflt = 2;
   }
-  const int nbuf = pipe ? tune_int("MVAE_NBUF_FWD", nbuf_dflt) : 0;
+  const int nbuf = pipe ? knob_int("MVAE_NBUF_FWD", nbuf_dflt) : 0;
   size_t lds = (size_t)(nbuf > 0 ? nbuf : 2) * (BM + 4 * BJ) * KB;
   const size_t stage_bytes = (size_t)BM * 4 * (BJ + 4) * sizeof(float);     // epilogue staging tile
   if (lds < stage_bytes) lds = stage_bytes;
@@ -1361,10 +1351,6 @@ int rnn_fwd_impl(const mvae_rnn_fwd_desc* d, hipStream_t st) {
   return MVAE_OK;
 }
 
-int rnn_rowres_bwd(const mvae_rnn_bwd_desc* d, hipStream_t st);
-int rnn_gru_rowres_bwd(const mvae_rnn_bwd_desc* d, hipStream_t st);
-size_t rnn_rowres_bwd_workspace(int layers, int T, int B, int H);
-
 size_t rnn_bwd_workspace_bytes(const mvae_rnn_bwd_desc* d) {
   if (!d || d->layers < 1 || d->B < 1 || d->H < 1 || d->T < 1) return 0;
   const size_t split = (size_t)d->layers * 4 * d->B * d->H * sizeof(float);      // up to four fp32 partial dh tiles per cell of a wavefront launch
@@ -1411,7 +1397,7 @@ int rnn_bwd_impl(const mvae_rnn_bwd_desc* d, hipStream_t st) {
   // stack is small (MFMA-f32 bound per workgroup).  MVAE_BM overrides.
   int BM = 64, BN = 64;
   if (dt == MVAE_F32 && (long)((B + 63) / 64) * ((H + 63) / 64) * NL < 256) { BM = 32; BN = 32; }
-  if (!drop) BM = tune_int("MVAE_BM", BM);
+  if (!drop) BM = knob_int("MVAE_BM", BM);
   if (BM == 32 && dt == MVAE_BF16) BM = 64;
   if (BM != 32) BN = 64;
   const int sz = (dt == MVAE_BF16) ? 2 : 4, ke = KB / sz;
@@ -1433,7 +1419,7 @@ int rnn_bwd_impl(const mvae_rnn_bwd_desc* d, hipStream_t st) {
   // (128 x 128, 2) at B = 512, (128 x 128, 4 = half segments) at B = 256, (128 x 64, 4) at B = 128.
   // MVAE_BWD_SPLIT: 0 = never, 1 = choose, 2 = (128 x 128, 2) whenever the shape allows, 2562 / 1284 / 644 = force (tests).
   if (d->dy_a && (!pipe || dt != MVAE_BF16 || (long)B * d->dy_a_ld * sz >= (1L << 31) || (long)H * d->dy_w_ld * sz >= (1L << 31))) return MVAE_ERR_UNSUPPORTED;
-  const int split_knob = tune_int("MVAE_BWD_SPLIT", 1);
+  const int split_knob = knob_int("MVAE_BWD_SPLIT", 1);
   int nsplit = 0;
   if (split_knob && dt == MVAE_BF16 && pipe && vec && B % 128 == 0 && H % 128 == 0 && d->split_ws) {
     struct Cand { int bm, bn, ns, key; };
@@ -1479,11 +1465,11 @@ int rnn_bwd_impl(const mvae_rnn_bwd_desc* d, hipStream_t st) {
   a.gru3 = (gru && H % ke == 0 && (nsplit != 4 || (3 * H / 2) % ke == 0)) ? 1 : 0;
   a.B = B; a.H = H; a.tiles_m = (B + BM - 1) / BM; a.tiles_n = (H + BN - 1) / BN; a.vec = vec ? 1 : 0;
 #ifdef MVAE_TUNING
-  a.dbg = tune_int("MVAE_DBG", 0);
+  a.dbg = knob_int("MVAE_DBG", 0);
 #else
   a.dbg = 0;
 #endif
-  const int nbuf = pipe ? (drop ? 4 : tune_int("MVAE_NBUF_BWD", 4)) : 0;
+  const int nbuf = pipe ? (drop ? 4 : knob_int("MVAE_NBUF_BWD", 4)) : 0;
   size_t lds = (size_t)(split ? (BM == 256 ? 3 : 4) : big_fused ? (BM == 256 ? 3 : 4) : (nbuf > 0 ? nbuf : 2)) * (BM + BN) * KB;
   const size_t stage_bytes = (size_t)BM * (BN + 4) * sizeof(float);
   if (lds < stage_bytes) lds = stage_bytes;

@@ -366,9 +366,7 @@ __device__ __forceinline__ void persist_fwd_body(const PersistFwdArgs& p, char* 
   }
   if (SAVE && ok) save_half(T - 1, 1, sv);
   if (!ok) {                                      // a bounded spin ran out (or somebody else's did): record who, drain
-    if (lane == 0) {
-      if (atomicCAS(p.status, 0u, 1u) == 0u) { p.status[1] = blockIdx.x; p.status[2] = (uint32_t)layer; if (p.poison) *p.poison = __builtin_nanf(""); }
-    }
+    if (lane == 0) spin_give_up(p.status, SPIN_FLAG_WAIT, layer, p.poison);
     return;
   }
   // final cell state (fp32), slot (T - 1) & 1 of the ping-pong the wavefront kernels keep
@@ -418,9 +416,7 @@ bool rnn_persist_fwd_supported(const mvae_rnn_fwd_desc* d) {
     if (l > 0 && (reinterpret_cast<uintptr_t>(d->w_ih[l]) & 15)) return false;
     if ((d->cs[l] && (reinterpret_cast<uintptr_t>(d->cs[l]) & 15)) || (d->gates[l] && (reinterpret_cast<uintptr_t>(d->gates[l]) & 15))) return false;
   }
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
-  return cus == PWG;
+  return device_cus() == PWG;
 }
 
 // ws: rnn_persist_fwd_workspace_bytes(T) bytes of device memory, 16-byte aligned
@@ -442,22 +438,9 @@ int rnn_persist_fwd(const mvae_rnn_fwd_desc* d, void* ws, size_t ws_bytes, hipSt
 #ifdef MVAE_TUNING
   a.dbg = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + 64 + (size_t)PNL * d->T * 64 * 4);
 #endif
-  // ~0.2 s of polling rounds (2^17 x ~1.6 us): far beyond any step or any wait for a compute unit, short enough that a launch that cannot
-  // make progress costs a fifth of a second, not two (round 5: a failure is survived, so the price of one is what matters).  MVAE_PERSIST_SPIN (tests: 1 = give up at the first
-  // flag that is not there yet, which exercises the failure path) and MVAE_PERSIST_SAFE are honoured under MVAE_TUNING=1 only.
-  const char* sp = mvae_knob("MVAE_PERSIST_SPIN");
-  a.spin_limit = sp ? (uint32_t)atoi(sp) : (1u << 17);
-  const char* sf = mvae_knob("MVAE_PERSIST_SAFE");
-  a.safe = (sf && atoi(sf) != 0) ? 1 : 0;
-  // the 160 KB dynamic-LDS opt-in is a per-DEVICE function attribute: once per device, not once per process
-  static std::atomic<bool> attr[MVAE_MAX_DEVICES];
-  int dev_id = 0;
-  MVAE_CHECK_HIP(hipGetDevice(&dev_id));
-  if (dev_id < 0 || dev_id >= MVAE_MAX_DEVICES || !attr[dev_id].load(std::memory_order_acquire)) {
-    MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_persist_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, PLDS));
-    MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_persist_fwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, PLDS));
-    if (dev_id >= 0 && dev_id < MVAE_MAX_DEVICES) attr[dev_id].store(true, std::memory_order_release);
-  }
+  a.spin_limit = spin_limit("MVAE_PERSIST_SPIN");
+  a.safe = knob_on("MVAE_PERSIST_SAFE", false) ? 1 : 0;
+  MVAE_CHECK_HIP((lds_opt_in<lstm_persist_fwd_kernel<true>, lstm_persist_fwd_kernel<false>>(PLDS)));
   bool save = true;
   for (int l = 0; l < PNL; ++l) if (!d->gates[l] || !d->cs[l]) save = false;
   for (int r0 = 0; r0 < d->B; r0 += PB) {        // one pass per block of 128 rows (stream-ordered: the flags are re-zeroed in between)

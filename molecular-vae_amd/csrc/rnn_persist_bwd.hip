@@ -412,9 +412,7 @@ __device__ __forceinline__ void persist_bwd_body(const PersistBwdArgs& p, char* 
     if (tid == 0) __builtin_amdgcn_raw_buffer_store_b32(1u, r_fl, 0u, myfl + (uint32_t)(t * 256 + j * 4), 16);
   }
   if (!ok) {
-    if (lane == 0) {
-      if (atomicCAS(p.status, 0u, 1u) == 0u) { p.status[1] = blockIdx.x; p.status[2] = (uint32_t)layer; if (p.poison) *p.poison = __builtin_nanf(""); }
-    }
+    if (lane == 0) spin_give_up(p.status, SPIN_FLAG_WAIT, layer, p.poison);
   }
 }
 
@@ -451,9 +449,7 @@ bool rnn_persist_bwd_supported(const mvae_rnn_bwd_desc* d) {
     if ((reinterpret_cast<uintptr_t>(d->gates[l]) & 15) || (reinterpret_cast<uintptr_t>(d->cs[l]) & 15)) return false;
   }
   if ((long)d->T * d->B * (long)LDG * 2 >= (1L << 31)) return false;      // 32-bit byte offsets / (int) buffer-resource extents in the kernel
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return false;
-  return cus == PWG;
+  return device_cus() == PWG;
 }
 
 int rnn_persist_bwd(const mvae_rnn_bwd_desc* d, void* ws, size_t ws_bytes, hipStream_t st) {
@@ -479,17 +475,9 @@ int rnn_persist_bwd(const mvae_rnn_bwd_desc* d, void* ws, size_t ws_bytes, hipSt
 #ifdef MVAE_TUNING
   a.dbg = reinterpret_cast<unsigned long long*>(w + head + EXCH_BYTES);
 #endif
-  const char* sp = mvae_knob("MVAE_PERSIST_SPIN");
-  a.spin_limit = sp ? (uint32_t)atoi(sp) : (1u << 17);
-  const char* sf = mvae_knob("MVAE_PERSIST_SAFE");
-  a.safe = (sf && atoi(sf) != 0) ? 1 : 0;
-  static std::atomic<bool> attr[MVAE_MAX_DEVICES];       // per-device function attribute
-  int dev_id = 0;
-  MVAE_CHECK_HIP(hipGetDevice(&dev_id));
-  if (dev_id < 0 || dev_id >= MVAE_MAX_DEVICES || !attr[dev_id].load(std::memory_order_acquire)) {
-    MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_persist_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, PLDS));
-    if (dev_id >= 0 && dev_id < MVAE_MAX_DEVICES) attr[dev_id].store(true, std::memory_order_release);
-  }
+  a.spin_limit = spin_limit("MVAE_PERSIST_SPIN");
+  a.safe = knob_on("MVAE_PERSIST_SAFE", false) ? 1 : 0;
+  MVAE_CHECK_HIP(lds_opt_in<lstm_persist_bwd_kernel>(PLDS));
   for (int r0 = 0; r0 < d->B; r0 += PB) {
     a.row0 = r0;
     if (r0 == 0) MVAE_CHECK_HIP(hipMemsetAsync(ws, 0, head, st));

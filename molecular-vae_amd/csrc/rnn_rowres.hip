@@ -15,6 +15,7 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "tile_pipe.hpp"
+#include "persist_common.hpp"
 #include <stdlib.h>
 
 namespace {
@@ -66,8 +67,8 @@ constexpr int RR_TBL_ROWS = 64, RR_TBL_T = 256;      // LDS table / id capacity 
 
 // Pipeline context of the layer-concurrent forms: `above` = progress word of the workgroup that produces our input (same batch rows, the
 // neighbouring layer; nullptr: the input is complete), `mine` = our own progress word (nullptr: nobody consumes our output inside the launch).
-// Forward: progress = number of completed time steps; hs[t] is visible once progress >= t + 1.
-struct RowPipe { const uint32_t* above; uint32_t* mine; uint32_t* status; uint32_t spin_limit; float* poison; };
+// Forward: progress = number of completed time steps; hs[t] is visible once progress >= t + 1.  `layer` goes into the record of a spin that ran out.
+struct RowPipe { const uint32_t* above; uint32_t* mine; uint32_t* status; uint32_t spin_limit; float* poison; int layer; };
 
 template <int H, bool HASX, int NTHR, bool TBL = false, bool PIPE = false>
 __device__ __forceinline__ void lstm_rowres_fwd_body(const RowResF& p, int rowgroup, RowPipe pp) {
@@ -90,7 +91,7 @@ __device__ __forceinline__ void lstm_rowres_fwd_body(const RowResF& p, int rowgr
       if (known >= need) return;
       __builtin_amdgcn_s_sleep(4);
     }
-    if (pp.status && atomicCAS(pp.status, 0u, 3u) == 0u && pp.poison) *pp.poison = __builtin_nanf("");
+    if (pp.status) spin_give_up(pp.status, SPIN_ROWRES_FWD, pp.layer, pp.poison);
     known = 0xffffffffu;
   };
   auto load_x = [&](const float* src) -> float4 {  // the layer below's h: agent-scope loads in the pipelined form (not through this CU's L1)
@@ -246,7 +247,7 @@ __global__ __launch_bounds__(320) void lstm_rowres_fwd_pipe_kernel(RowResFAll a,
   RowPipe pp;
   pp.above = (l > 0) ? flags + (l - 1) * nblk + g : nullptr;
   pp.mine = (l + 1 < a.nl) ? flags + l * nblk + g : nullptr;
-  pp.status = status; pp.spin_limit = spin_limit; pp.poison = poison;
+  pp.status = status; pp.spin_limit = spin_limit; pp.poison = poison; pp.layer = l;
   if (l == 0) lstm_rowres_fwd_body<H, false, 320, TBL0, true>(a.l[0], g, pp);
   else lstm_rowres_fwd_body<H, true, 320, false, true>(a.l[l], g, pp);
 }
@@ -291,7 +292,7 @@ __device__ __forceinline__ void rowres_bwd_layer(const RowResB& p, float (&gbuf)
       if (known >= need) return;
       __builtin_amdgcn_s_sleep(4);
     }
-    if (pp.status && atomicCAS(pp.status, 0u, 2u) == 0u && pp.poison) *pp.poison = __builtin_nanf("");          // gave up: the results are invalid, the launch still ends
+    if (pp.status) spin_give_up(pp.status, SPIN_ROWRES_BWD, pp.layer, pp.poison);          // gave up: the results are invalid, the launch still ends
     known = 0xffffffffu;
   };
   float W[NG][KW];
@@ -440,7 +441,7 @@ __global__ __launch_bounds__(256) void lstm_rowres_bwd_pipe_kernel(RowResBAll a,
   RowPipe pp;
   pp.above = (l + 1 < a.nl) ? flags + (l + 1) * nblk + g : nullptr;
   pp.mine = (l > 0) ? flags + l * nblk + g : nullptr;
-  pp.status = status; pp.spin_limit = spin_limit; pp.poison = poison;
+  pp.status = status; pp.spin_limit = spin_limit; pp.poison = poison; pp.layer = l;
   if (l > 0) rowres_bwd_layer<H, 256, true, true>(a.l[l], gbuf, red, g, pp);
   else rowres_bwd_layer<H, 256, false, true>(a.l[l], gbuf, red, g, pp);
 }
@@ -814,16 +815,40 @@ __global__ __launch_bounds__(512) void gru_rowres_bwd_kernel(GruRowB p) {
 
 }  // namespace
 
-// layers of one pass, sequentially; returns MVAE_ERR_UNSUPPORTED when the shape is not the one this schedule is built for
-// scratch of the layer-concurrent forward (0: the shape / device is not served by it): [status 16 words | layers x ceil(B / 4) progress words]
-size_t rnn_rowres_fwd_pipe_workspace(const mvae_rnn_fwd_desc* d) {
-  if (d->cell != MVAE_CELL_LSTM || d->dtype != MVAE_F32 || d->H != 72 || d->x0 || d->lengths || d->layers < 2 || !d->gates[0]) return 0;
-  const int nblk = (d->B + RR_ROWS - 1) / RR_ROWS;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || d->layers * nblk > cus) return 0;
-  return ((size_t)d->layers * nblk + 16) * sizeof(uint32_t);
+// ---- the layer-concurrent forms (one launch, the layers as a pipeline over progress words): grid = layers x nblk workgroups
+static int rowres_nblk(int B) { return (B + RR_ROWS - 1) / RR_ROWS; }
+// their scratch words: one progress word per workgroup + the 16 words that hold the status record
+static size_t rowres_pipe_words(int NL, int nblk) { return (size_t)NL * nblk + 16; }
+// EVERY workgroup of the grid must be resident at once (one per CU is what is assumed; device_cus() = 0, no device: never), 2 .. max_layers layers
+static bool rowres_pipe_fits(int NL, int max_layers, int nblk) { return NL >= 2 && NL <= max_layers && NL * nblk <= device_cus(); }
+// may a pass take that form: it fits, and neither MVAE_ROWRES_PIPE=0 nor the caller (no_spin) has switched it off
+static bool rowres_pipe_ok(int NL, int max_layers, int nblk, int no_spin) {
+  return knob_on("MVAE_ROWRES_PIPE", true) && !no_spin && rowres_pipe_fits(NL, max_layers, nblk);
 }
 
+// layer l of the stack as the forward kernels take it
+static RowResF rowres_fwd_layer(const mvae_rnn_fwd_desc* d, int l) {
+  RowResF a;
+  a.x = l ? reinterpret_cast<const float*>(d->hs[l - 1]) : nullptr; a.ldx = d->ldh;
+  a.add = l ? nullptr : d->add0; a.add_ts = d->add0_tstride;
+  a.tbl = d->add_table; a.tbl_rows = d->add_table_rows; a.idx = d->add_index; a.idx_ld = d->add_index_ld;
+  a.w_ih = l ? reinterpret_cast<const float*>(d->w_ih[l]) : nullptr; a.ldw_ih = d->ldw_ih[l];
+  a.w_hh = reinterpret_cast<const float*>(d->w_hh[l]); a.ldw_hh = d->ldw_hh[l];
+  a.bias = d->bias[l];
+  a.hs = reinterpret_cast<float*>(d->hs[l]); a.ldh = d->ldh;
+  a.cs = reinterpret_cast<float*>(d->cs[l]); a.gates = reinterpret_cast<float*>(d->gates[l]);
+  a.T = d->T; a.B = d->B;
+  return a;
+}
+
+// scratch of the layer-concurrent forward (0: the shape / device is not served by it): [status 16 words | layers x ceil(B / 4) progress words]
+size_t rnn_rowres_fwd_pipe_workspace(const mvae_rnn_fwd_desc* d) {
+  if (d->cell != MVAE_CELL_LSTM || d->dtype != MVAE_F32 || d->H != 72 || d->x0 || d->lengths || !d->gates[0]) return 0;
+  const int nblk = rowres_nblk(d->B);
+  return rowres_pipe_fits(d->layers, MVAE_MAX_LAYERS, nblk) ? rowres_pipe_words(d->layers, nblk) * sizeof(uint32_t) : 0;
+}
+
+// layers of one pass, sequentially; returns MVAE_ERR_UNSUPPORTED when the shape is not the one this schedule is built for
 int rnn_rowres_fwd(const mvae_rnn_fwd_desc* d, hipStream_t st) {
   constexpr int H = 72;
   if (d->cell != MVAE_CELL_LSTM || d->dtype != MVAE_F32 || d->H != H || d->x0 || d->lengths) return MVAE_ERR_UNSUPPORTED;
@@ -837,38 +862,23 @@ int rnn_rowres_fwd(const mvae_rnn_fwd_desc* d, hipStream_t st) {
   const int T = d->T, B = d->B;
   // hoisting the upper layers' input projection pays while its GEMM is small (measured, encoder forward per step: b = 128: 0.478 -> 0.427 ms;
   // B = 1024: 0.575 -> 0.790 ms, the two [T*B, 72] x [72, 288] GEMMs then cost more than the halved contraction saves)
-  const char* hv = mvae_knob("MVAE_ROWRES_HOIST");
-  const bool hoist = hv ? atoi(hv) != 0 : (long)T * B <= 16384;
+  const bool hoist = knob_on("MVAE_ROWRES_HOIST", (long)T * B <= 16384);
   // Layer-concurrent form (one launch, the layers as a pipeline over progress words): when every workgroup of the grid is resident at once
   // (one per CU is what is assumed) and the caller gave scratch for the progress words (persist_ws: layers x ceil(B / 4) + 16 words).  It
   // replaces the hoisted form too: 0.427 ms (hoisted, layer after layer) -> see DESIGN.md at b = 128.
   {
-    const int nblk = (B + RR_ROWS - 1) / RR_ROWS, NL = d->layers;
-    int dev = 0, cus = 0;
-    const char* pk = mvae_knob("MVAE_ROWRES_PIPE");
-    bool pipe = (pk ? atoi(pk) != 0 : true) && !d->no_spin && NL >= 2 && d->persist_ws && d->persist_ws_bytes >= ((size_t)NL * nblk + 16) * sizeof(uint32_t);
-    if (pipe && (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || NL * nblk > cus)) pipe = false;
+    const int nblk = rowres_nblk(B), NL = d->layers;
+    const size_t ws_bytes = rowres_pipe_words(NL, nblk) * sizeof(uint32_t);
+    bool pipe = d->persist_ws && d->persist_ws_bytes >= ws_bytes && rowres_pipe_ok(NL, MVAE_MAX_LAYERS, nblk, d->no_spin);
     for (int l = 1; l < NL && pipe; ++l) if (reinterpret_cast<uintptr_t>(d->hs[l - 1]) & 15) pipe = false;
     if (pipe) {
       RowResFAll all;
       all.nl = NL;
-      for (int l = 0; l < NL; ++l) {
-        RowResF& a = all.l[l];
-        a.x = l ? reinterpret_cast<const float*>(d->hs[l - 1]) : nullptr; a.ldx = d->ldh;
-        a.add = l ? nullptr : d->add0; a.add_ts = d->add0_tstride;
-        a.tbl = d->add_table; a.tbl_rows = d->add_table_rows; a.idx = d->add_index; a.idx_ld = d->add_index_ld;
-        a.w_ih = l ? reinterpret_cast<const float*>(d->w_ih[l]) : nullptr; a.ldw_ih = d->ldw_ih[l];
-        a.w_hh = reinterpret_cast<const float*>(d->w_hh[l]); a.ldw_hh = d->ldw_hh[l];
-        a.bias = d->bias[l];
-        a.hs = reinterpret_cast<float*>(d->hs[l]); a.ldh = d->ldh;
-        a.cs = reinterpret_cast<float*>(d->cs[l]); a.gates = reinterpret_cast<float*>(d->gates[l]);
-        a.T = T; a.B = B;
-      }
+      for (int l = 0; l < NL; ++l) all.l[l] = rowres_fwd_layer(d, l);
       uint32_t* status = reinterpret_cast<uint32_t*>(d->persist_ws);       // [status 16 words | progress words]: the host reads the first 16 bytes
       uint32_t* flags = status + 16;
-      MVAE_CHECK_HIP(hipMemsetAsync(status, 0, ((size_t)NL * nblk + 16) * sizeof(uint32_t), st));
-      const char* sp = mvae_knob("MVAE_ROWRES_SPIN");          // tests: 1 = give up at the first hand-off that is not there yet
-      const uint32_t spin = sp ? (uint32_t)atoi(sp) : (1u << 17);
+      MVAE_CHECK_HIP(hipMemsetAsync(status, 0, ws_bytes, st));
+      const uint32_t spin = spin_limit("MVAE_ROWRES_SPIN");
       if (tbl) hipLaunchKernelGGL((lstm_rowres_fwd_pipe_kernel<H, true>), dim3(NL * nblk), dim3(320), 0, st, all, flags, status, spin, d->poison);
       else hipLaunchKernelGGL((lstm_rowres_fwd_pipe_kernel<H, false>), dim3(NL * nblk), dim3(320), 0, st, all, flags, status, spin, d->poison);
       mvae_tls_status = status;
@@ -877,18 +887,9 @@ int rnn_rowres_fwd(const mvae_rnn_fwd_desc* d, hipStream_t st) {
     }
   }
   for (int l = 0; l < d->layers; ++l) {
-    RowResF a;
-    a.x = l ? reinterpret_cast<const float*>(d->hs[l - 1]) : nullptr; a.ldx = d->ldh;
-    a.add = l ? nullptr : d->add0; a.add_ts = d->add0_tstride;
-    a.tbl = d->add_table; a.tbl_rows = d->add_table_rows; a.idx = d->add_index; a.idx_ld = d->add_index_ld;
-    a.w_ih = l ? reinterpret_cast<const float*>(d->w_ih[l]) : nullptr; a.ldw_ih = d->ldw_ih[l];
-    a.w_hh = reinterpret_cast<const float*>(d->w_hh[l]); a.ldw_hh = d->ldw_hh[l];
-    a.bias = d->bias[l];
-    a.hs = reinterpret_cast<float*>(d->hs[l]); a.ldh = d->ldh;
-    a.cs = reinterpret_cast<float*>(d->cs[l]); a.gates = reinterpret_cast<float*>(d->gates[l]);
-    a.T = T; a.B = B;
+    RowResF a = rowres_fwd_layer(d, l);
     if (l && (reinterpret_cast<uintptr_t>(d->hs[l - 1]) & 15)) return MVAE_ERR_UNSUPPORTED;
-    dim3 grid((B + RR_ROWS - 1) / RR_ROWS);
+    dim3 grid(rowres_nblk(B));
     if (l && hoist) {
       // The input part of an upper layer does not depend on its own recurrence: x_t . W_ih^T for ALL t is one exact-f32 GEMM over the
       // layer below's finished outputs, written into this layer's `gates` buffer; the recurrent kernel then takes it as its addend
@@ -909,7 +910,7 @@ int rnn_rowres_fwd(const mvae_rnn_fwd_desc* d, hipStream_t st) {
 
 // [dx ping | dx pong | progress words layers x ceil(B / 4) + status (pipelined form)]
 size_t rnn_rowres_bwd_workspace(int layers, int T, int B, int H) {
-  return (H == 72 && layers > 1) ? (size_t)2 * T * B * H * sizeof(float) + ((size_t)layers * ((B + RR_ROWS - 1) / RR_ROWS) + 16) * sizeof(uint32_t) : 0;
+  return (H == 72 && layers > 1) ? (size_t)2 * T * B * H * sizeof(float) + rowres_pipe_words(layers, rowres_nblk(B)) * sizeof(uint32_t) : 0;
 }
 
 // top layer first; layer l's input gradient (dx, scratch ping-pong) is layer l-1's dy
@@ -938,17 +939,13 @@ int rnn_rowres_bwd(const mvae_rnn_bwd_desc* d, hipStream_t st) {
   }
   // layer-concurrent form: every workgroup of the grid must be resident at once (one per CU is what is assumed), 2 or 3 layers (the dx
   // ping-pong has two buffers: layer l writes l & 1 while layer l + 2 writes the same one only when there are four)
-  const int nblk = (B + RR_ROWS - 1) / RR_ROWS;
-  int dev = 0, cus = 0;
-  const char* pk = mvae_knob("MVAE_ROWRES_PIPE");
-  bool pipe = (pk ? atoi(pk) != 0 : true) && !d->no_spin && NL >= 2 && NL <= 3;
-  if (pipe && (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || NL * nblk > cus)) pipe = false;
+  const int nblk = rowres_nblk(B);
+  const bool pipe = rowres_pipe_ok(NL, 3, nblk, d->no_spin);
   uint32_t* flags = need ? reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(d->split_ws) + (size_t)2 * T * B * H * sizeof(float)) : nullptr;
   uint32_t* status = flags ? flags + (size_t)NL * nblk : nullptr;
   if (pipe && flags) {
-    MVAE_CHECK_HIP(hipMemsetAsync(flags, 0, ((size_t)NL * nblk + 16) * sizeof(uint32_t), st));     // progress words + status
-    const char* sp = mvae_knob("MVAE_ROWRES_SPIN");
-    hipLaunchKernelGGL((lstm_rowres_bwd_pipe_kernel<H>), dim3(NL * nblk), dim3(256), 0, st, all, flags, status, sp ? (uint32_t)atoi(sp) : (1u << 17), d->poison);
+    MVAE_CHECK_HIP(hipMemsetAsync(flags, 0, rowres_pipe_words(NL, nblk) * sizeof(uint32_t), st));     // progress words + status
+    hipLaunchKernelGGL((lstm_rowres_bwd_pipe_kernel<H>), dim3(NL * nblk), dim3(256), 0, st, all, flags, status, spin_limit("MVAE_ROWRES_SPIN"), d->poison);
     mvae_tls_status = status;              // (the layer-by-layer form has no spins: no status to report, no memset)
   } else {
     hipLaunchKernelGGL((lstm_rowres_bwd_all_kernel<H>), dim3(nblk), dim3(256), 0, st, all);
@@ -966,7 +963,7 @@ int rnn_gru_rowres_fwd(const mvae_rnn_fwd_desc* d, hipStream_t st) {
   if ((long)d->T * d->B * 4 * H >= (1L << 31) || (long)d->T * d->B * d->ldh >= (1L << 31)) return MVAE_ERR_UNSUPPORTED;      // 32-bit element offsets in the kernel
   if (d->ldw_hh[0] % 8 || (reinterpret_cast<uintptr_t>(d->w_hh[0]) & 15)) return MVAE_ERR_UNSUPPORTED;
   GruRowF a;
-  { const char* sf = mvae_knob("MVAE_GRU_ROWRES_SAFE"); a.safe = (sf && atoi(sf) != 0) ? 1 : 0; }
+  a.safe = knob_on("MVAE_GRU_ROWRES_SAFE", false) ? 1 : 0;
   a.w_hh = reinterpret_cast<const bf16_t*>(d->w_hh[0]); a.ldw = d->ldw_hh[0];
   a.bias = d->bias[0];
   a.tbl = d->add_table; a.idx = reinterpret_cast<const long*>(d->add_index); a.idx_ld = d->add_index_ld; a.tbl_rows = d->add_table_rows;
@@ -978,12 +975,7 @@ int rnn_gru_rowres_fwd(const mvae_rnn_fwd_desc* d, hipStream_t st) {
   a.T = d->T; a.B = d->B;
   const size_t lds = (size_t)(H / 16) * (H / 32) * 1024 + 2 * GR_ROWS * (H + 8) * sizeof(bf16_t) + 4 * H * sizeof(float) + (size_t)4 * GR_RPL * d->T * sizeof(int);      // W_hn fragments + the double-buffered A rows + bias + token ids
   if (lds > 160 * 1024) return MVAE_ERR_UNSUPPORTED;
-  static bool attr_set = false;
-  if (!attr_set) {
-    MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gru_rowres_fwd_kernel<H, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gru_rowres_fwd_kernel<H, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
+  MVAE_CHECK_HIP((lds_opt_in<gru_rowres_fwd_kernel<H, true>, gru_rowres_fwd_kernel<H, false>>(160 * 1024)));
   if (a.gates) hipLaunchKernelGGL((gru_rowres_fwd_kernel<H, true>), dim3(d->B / (4 * GR_RPL)), dim3(512), lds, st, a);
   else hipLaunchKernelGGL((gru_rowres_fwd_kernel<H, false>), dim3(d->B / (4 * GR_RPL)), dim3(512), lds, st, a);
   MVAE_CHECK_HIP(hipGetLastError());
@@ -997,7 +989,7 @@ int rnn_gru_rowres_bwd(const mvae_rnn_bwd_desc* d, hipStream_t st) {
   if (d->dh0[0] || !d->gates[0] || !d->hs[0] || !d->dG[0] || !d->w_hhT[0] || d->T < 1 || d->B % (4 * GR_RPL)) return MVAE_ERR_UNSUPPORTED;
   if (d->ldw_hhT[0] % 8 || (reinterpret_cast<uintptr_t>(d->w_hhT[0]) & 15) || d->ldg < 4L * H) return MVAE_ERR_UNSUPPORTED;
   GruRowB a;
-  { const char* sf = mvae_knob("MVAE_GRU_ROWRES_SAFE"); a.safe = (sf && atoi(sf) != 0) ? 1 : 0; }
+  a.safe = knob_on("MVAE_GRU_ROWRES_SAFE", false) ? 1 : 0;
   a.w_hhT = reinterpret_cast<const bf16_t*>(d->w_hhT[0]); a.ldwT = d->ldw_hhT[0];
   a.gates = reinterpret_cast<const bf16_t*>(d->gates[0]);
   a.hs = reinterpret_cast<const bf16_t*>(d->hs[0]); a.ldh = d->ldh;
@@ -1007,8 +999,7 @@ int rnn_gru_rowres_bwd(const mvae_rnn_bwd_desc* d, hipStream_t st) {
   a.dG = reinterpret_cast<bf16_t*>(d->dG[0]); a.ldg = d->ldg;
   a.T = d->T; a.B = d->B;
   constexpr size_t lds = (size_t)(H / 16) * (H / 32) * 1024 + 2 * (4 * GR_RPL) * GRB_LDG * sizeof(bf16_t);
-  static bool attr_set = false;
-  if (!attr_set) { MVAE_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gru_rowres_bwd_kernel<H>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr_set = true; }
+  MVAE_CHECK_HIP(lds_opt_in<gru_rowres_bwd_kernel<H>>(160 * 1024));
   hipLaunchKernelGGL((gru_rowres_bwd_kernel<H>), dim3(d->B / (4 * GR_RPL)), dim3(512), lds, st, a);
   MVAE_CHECK_HIP(hipGetLastError());
   return MVAE_OK;

@@ -1614,10 +1614,12 @@ PERSIST_MAX_FAILURES = 3
 PERSIST_STATS = {"launches": 0, "rowres_pipe": 0, "bwd_launches": 0, "failures": 0, "reruns": 0, "disabled": False}     # passes that took a spinning schedule; what went wrong (tests / logs / bench line)
 _PERSIST_PENDING = []      # [(pinned int32[4], event, what)]
 _PERSIST_WARNED = [False]
+PERSIST_LAST_FAILURE = [None]     # (what, [code, block, layer, 0]) of the latest launch that gave up
 
 
 def _spin_failure(what, rec):
     PERSIST_STATS["failures"] += 1
+    PERSIST_LAST_FAILURE[0] = (what, list(rec))
     if PERSIST_STATS["failures"] >= PERSIST_MAX_FAILURES and not PERSIST_STATS["disabled"]:
         PERSIST_STATS["disabled"] = True
     if not _PERSIST_WARNED[0] or PERSIST_STATS["disabled"]:

@@ -201,10 +201,17 @@ def test_training_step_whose_persistent_launch_gave_up_is_skipped_on_the_device(
     assert n0["launches"] >= 1 and n0["bwd_launches"] >= 1 and n0["rowres_pipe"] >= 2         # the schedules under test are the ones running
     p0, m0 = f["p"].clone(), f["m"].clone()
     monkeypatch.setenv(knob, "1")
+    ops.PERSIST_LAST_FAILURE[0] = None
     with pytest.warns(RuntimeWarning, match="gave up"):
         mv.train_step(model, opt, lf, idx, ohe, eps=eps)
         torch.cuda.synchronize()
         ops.persist_check(sync=True)
+    if knob == "MVAE_ROWRES_SPIN":
+        # the status record of the latest launch that gave up: (code, block, layer) of its first workgroup to do so -- a row-resident
+        # hand-off (2 = backward, 3 = forward) in a grid of layers x ceil(B / 4) workgroups
+        NL, B = model.encoder.gru.num_layers, idx.shape[0]
+        code, block, layer = ops.PERSIST_LAST_FAILURE[0][1][:3]
+        assert code in (2, 3) and 0 <= block < NL * ((B + 3) // 4) and 0 <= layer < NL, (code, block, layer)
     assert torch.equal(f["p"], p0) and torch.equal(f["m"], m0)                                 # the update did not happen
     assert float(opt.skipped_steps) == 1 and float(f["poison"]) == 0.0 and not np.isfinite(float(opt.last_grad_norm))
     assert ops.PERSIST_STATS["failures"] >= 1 and ops.PERSIST_STATS["reruns"] == 0             # nothing waited, nothing was re-run
