@@ -43,7 +43,13 @@ that alone, and with ``--novel_against`` audits the corpus once (``MosesDeviceDa
 under the SMILES graph walk, written from a random root in a random neighbour order -- not canonical, not rdkit's doRandom).
 ``--canonical`` prints, for each round, the distinct canonical spellings among its samples (``mv.moses_generate(canonical=True)``:
 this library's canonical SMILES -- two spellings of one graph count once, compared on tokens; no aromaticity perception, no stereo, not
-rdkit's) and, with ``--novel_against``, how many of them are in no row of the canonicalised corpus (``MosesDeviceDataset.canonical``).
+rdkit's) and, with ``--novel_against``, how many of them are in no row of the canonicalised corpus (``MosesDeviceDataset.canonical``).  It has no
+aromaticity perception: for a figure that counts ``C1=CC=CC=C1`` and ``c1ccccc1`` once, see ``--normal``.
+``--normal`` prints, for each round, the distinct aromatic normal forms among its samples (``mv.moses_generate(normal=True)``:
+aromaticity perceived by this library's own rule -- cycles of 5 - 7 candidate atoms with 4 k + 2 electrons --, then the canonical
+spelling, so a Kekule spelling, an aromatic spelling and every respelling of one molecule count once, compared on tokens; no stereo, not
+rdkit's aromaticity model) and, with ``--novel_against``, how many of them are in no row of the corpus in normal form
+(``MosesDeviceDataset.normal_form``).  With ``--canonical`` both figures stand side by side.
 ``--filters FILE`` (one SMILES fragment per line, at most 64, each of at most 32 atoms) prints, for each round, the MOSES "Filters"
 figure on them (``mv.moses_generate(filters=)``): the share of the valence-consistent samples that contain none of the fragments, and
 the hits per fragment.  Fragments are matched as graphs (element, aromatic flag, charge, bond class) -- not SMARTS, so MOSES' own MCF
@@ -103,6 +109,9 @@ ap.add_argument("--top_scaffolds", type=int, default=0, help="with --scaffolds: 
                                                              "(this library's scaffold SMILES, not rdkit's MurckoScaffoldSmiles)")
 ap.add_argument("--canonical", action="store_true", help="print each round's distinct canonical spellings (unique@k on graphs) and, with "
                                                          "--novel_against, those absent from the canonicalised corpus")
+ap.add_argument("--normal", action="store_true", help="print each round's distinct aromatic normal forms (unique@k on molecules: a Kekule and "
+                                                      "an aromatic spelling count once) and, with --novel_against, those absent from the "
+                                                      "corpus in normal form")
 ap.add_argument("--filters", default=None, metavar="FILE", help="SMILES fragments, one per line: print each round's share of valence-consistent "
                                                                    "samples that contain none of them, and the hits per fragment")
 ap.add_argument("--reconstruct", default=None, metavar="FILE", help="strings, one per line: report exact-match reconstruction at z = mu "
@@ -176,7 +185,7 @@ with open(args.log, "w", buffering=1) as f:
                                 top_p=args.top_p, seed=args.seed + r * args.batches_per_round, syntax=args.syntax, count_valid=True,
                                 novel_against=corpus, prefix=args.prefix, nearest=args.nearest, valence=args.valence,
                                 int_div=args.int_div, snn=args.snn, scaffolds=args.scaffolds, kekule=args.kekule, canonical=args.canonical,
-                                filters=filters, top_scaffolds=args.top_scaffolds if args.scaffolds else 0, fragments=args.fragments)
+                                filters=filters, top_scaffolds=args.top_scaffolds if args.scaffolds else 0, fragments=args.fragments, normal=args.normal)
         total += res["total"]
         if args.kekule:
             kekule_valid += res["kekule_valid"]
@@ -220,6 +229,9 @@ with open(args.log, "w", buffering=1) as f:
               + (f", this round's distinct canonical spellings {res['unique_canonical']} of {res['canonical_status_counts'][0]} written"
                  if args.canonical else "")
               + (f", of which in no corpus row {res['novel_canonical']}" if args.canonical and corpus is not None else "")
+              + (f", this round's distinct aromatic normal forms {res['unique_normal']} of {res['normal_status_counts'][0]} written"
+                 if args.normal else "")
+              + (f", of which in no corpus row {res['novel_normal']}" if args.normal and corpus is not None else "")
               + (f", Filters {res['filters']:.4f} (hits " + ", ".join(f"{p} {h}" for p, h in zip(filters.patterns, res["filter_hits"]))
                  + f"; undecided {sum(res['filter_undecided'])})" if filters is not None else "")
               + (f", valid unique {valid}" if Chem is not None else "")

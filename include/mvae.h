@@ -942,7 +942,8 @@ int mvae_smiles_scaffold_host(int B, int T, int V, const int64_t* x, int64_t x_l
  * tighter necessary condition for chemical validity than "valence-consistent", and still no sufficient one.
  * What this is NOT: it is not rdkit's Kekulize or SanitizeMol, and agreement with either is neither tested nor claimed.  No aromaticity
  *   perception is done (no Hueckel count: c1ccc1 and c1ccccccc1 pass); radicals are not diagnosed (a bracket [c] with two ring bonds
- *   passes); no Kekule form is written and no other entry sees the bond orders found.
+ *   passes); no Kekule form is written and no other entry sees the bond orders found.  (The entries of "Aromatic normal form" below do
+ *   perceive aromaticity, and refuse c1ccc1 and c1ccccccc1 with MVAE_SMILES_NOT_AROMATIC.)
  * It is defined on the graph exactly as the walk builds it, with the walk's own valence table ("SMILES graph").
  *   U(a): the atom's final used valence, as the atom word holds it at <eos>: the sum of bond contributions (aromatic bonds count 1) plus
  *     bracket hydrogens.
@@ -1095,7 +1096,8 @@ int mvae_smiles_rewrite_host(int B, int T, int V, const int64_t* x, int64_t x_ld
  *   A known instance where it fails: C1CCC(CC1)CCCCCC1CCCCC1 (1,5-dicyclohexylpentane).  The equitable partition ties ring atoms with
  *   chain atoms, following every choice at every tie reaches two strings, and the spelling depends on the order of the input.
  * What this is NOT: not rdkit's canonical SMILES.  No aromaticity perception (C1=CC=CC=C1 and c1ccccc1 stay two strings), no stereo
- *   (STEREO refuses such rows), [CH4] is not unbracketed.
+ *   (STEREO refuses such rows), [CH4] is not unbracketed.  (mvae_smiles_aromatize_*, "Aromatic normal form" below, is this spelling
+ *   behind an aromaticity perception: there the two are one string.)
  * mvae_smiles_canon_rows / _corpus / _host take the arguments of mvae_smiles_rewrite_rows / _corpus / _host without seed and draw, and
  *   two more outputs, both optional (may be NULL):
  *   info int32 [B, 4] = atoms, classes after the first refinement, refinement rounds in all, ties broken -- for every row whose ranks
@@ -1211,7 +1213,7 @@ int mvae_smiles_substruct_host(int B, int T, int V, const int64_t* x, int64_t x_
  * read, written to a file, passed on as substructure queries, and compared exactly by comparing tokens.
  * What this is NOT: not rdkit's MurckoScaffoldSmiles.  Nothing is sanitised, no aromaticity is perceived (C1=CC=CC=C1 and c1ccccc1 have
  *   two scaffolds), and there is no stereo: a row with a stereo token gets status STEREO and no scaffold.  There is no generic
- *   (all-carbon) framework mode.
+ *   (all-carbon) framework mode.  (Rows put through mvae_smiles_aromatize_* first, "Aromatic normal form" below, have one.)
  * The scaffold graph G_S.  S = Core u Exo, exactly as "Murcko scaffold" defines them.  The atoms of G_S are the atoms of S, numbered in
  *   string order among themselves; its bonds are the row's bonds between two atoms of S, with their orders.
  * Hydrogens.  Every kept atom keeps its total valence, and the bonds it loses become hydrogens.
@@ -1343,6 +1345,75 @@ int mvae_smiles_fragment_smiles_host(int B, int T, int V, const int64_t* x, int6
                                      const int32_t* chem_info /* [V] */, const int32_t* emit /* [48] */, int bos_id, int eos_id, int pad_id,
                                      int max_content, int T_out, int64_t* out /* [B, T_out] */, int32_t* out_len /* [B] */,
                                      int32_t* status /* [B] */, int frag, int32_t* info /* [B, 4] or NULL */);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Aromatic normal form (an addition: a tenth consumer of the "SMILES graph" walk above, and the fifth family that writes a string).  A
+ * token row is read into its graph, aromaticity is PERCEIVED on that graph by the rule below, and the row is written back in the
+ * spelling of "SMILES canon" of the perceived graph: C1=CC=CC=C1, c1ccccc1 and every respelling of either come out as one token row.
+ * What this is NOT: the rule is this library's own.  It is not rdkit's aromaticity model and the output is not rdkit's canonical SMILES;
+ *   agreement with a toolkit is neither tested nor claimed.  There are no envelope cycles, so azulene stays Kekule (and azulene written
+ *   in lower case is refused).  There are no rings of 3, 4, 8 or more atoms.  There is no P, B, Se.  There is no stereo: a row with a
+ *   stereo token gets status STEREO.  The caveat of "SMILES canon" about ties ("NOT proved in general") carries over.
+ * Kekule graph of a row.  The walk's graph, in which every atom of the set N of "Kekulisation" has one more ring double bond; which
+ *   bond that is belongs to the matching, and nothing below depends on it.  U(a) is the used valence (bonds and bracket hydrogens).
+ *   K(a) = U(a) + [a in N] + the implicit hydrogens of an unbracketed atom ("SMILES graph"): the true valence, hydrogens included.
+ *   dbl(a) = the bonds of order 2 of a, plus one for a in N.  A row with lower-case atoms must kekulise ((N, E) has a perfect matching),
+ *   otherwise its status is MVAE_SMILES_KEKULE, as the kekule entries give it.
+ * Electrons.  An atom is a candidate iff it is a ring member and one of three cases holds:
+ *   e = 1: dbl(a) = 1, no triple bond, the double bond is a ring bond (for an atom of N by construction), K(a) <= 4, and (element,
+ *          charge) is C0, N0, N+, O+ or S+.  K <= 4 leaves out N and S+ of valence 5, so that a candidate has at most three bonds.
+ *   e = 0: C0 with dbl(a) = 1 whose double bond is a non-ring bond to O, S or N: c(=O), C(=O).
+ *   e = 2: dbl(a) = 0 and N0 with K = 3, O0 or S0 with K = 2, N- with K = 2, or C- with K = 3.
+ *   Everything else is no candidate: sp3 atoms, B, P, an exocyclic C=C, S(=O), cations without a double bond.
+ * Aromatic cycles.  Every simple cycle of 5, 6 or 7 atoms, all of them candidates (its bonds are ring bonds, being on a cycle), is
+ *   aromatic iff the sum of e over its atoms is 2 (mod 4).  An atom is aromatic iff it lies on an aromatic cycle: a function of the
+ *   graph alone, independent of the atom numbering and of which Kekule structure was written.  The cycles are enumerated by a path
+ *   search from every start atom over candidate neighbours numbered above it, to 7 atoms: a candidate has at most 3 neighbours, so a
+ *   start costs a few hundred steps at most, and no budget is needed.
+ * Refusal.  17 MVAE_SMILES_NOT_AROMATIC: a row the walk accepts, without a stereo token, that kekulises, in which some lower-case atom
+ *   is not aromatic by the rule: c1ccc1, c1ccccccc1, O=c1ccc(=O)cc1, c1cc2cccccc2c1, c1ccpcc1.  Precedence: the walk's status, STEREO
+ *   (8), KEKULE (7), NOT_AROMATIC (17), the writer's 9 - 13.  A refused row is copied through unchanged, as the rewrite copies one.
+ * Output graph.  The aromatic atoms get the aromatic flag, whatever case they were written in.  Every bond between two aromatic atoms
+ *   gets order 1, and a former double bond lowers the used valence of both its ends by one.  Every atom keeps its true hydrogen count:
+ *   a bracket atom stays a bracket atom (as in canon); an unbracketed atom stays unbracketed iff the implicit-hydrogen rule of "SMILES
+ *   graph" on its new flag and new bond sum gives that count, and otherwise becomes a bracket atom with it: N1C=CC=C1 -> c1cc[nH]c1.
+ *   Then the ranks and the writer of "SMILES canon" run on that graph unchanged.
+ *   C1=CC=CC=C1 -> c1ccccc1; O=C1C=CC=CN1 -> O=c1cccc[nH]1; C1C=CC2=CC=CC=C12 -> C1=Cc2ccccc2C1 (the five-ring double bond stays);
+ *   O=C1C=CC(=O)C=C1, C1=CC=CC=CC=C1, C1=CC=C1 and azulene C1=CC2=CC=CC=CC2=C1 have no aromatic atom and come out as canon writes them.
+ * mvae_smiles_aromatize_rows / _corpus / _host take the arguments of mvae_smiles_canon_rows / _corpus / _host with arom in the place
+ *   of rank, and write out / out_len / status (tokens_out / offsets_out / status / err) in the same layouts.  counts, where given, is
+ *   int32 [MVAE_AROMATIZE_COUNTS = 32], the histogram of the statuses (17 must fit).
+ *   info int32 [B, MVAE_AROMATIZE_INFO = 4] (optional, may be NULL) = atoms, aromatic atoms in the output, atoms written in upper case
+ *     that came out aromatic, bonds of order 2 that became aromatic -- for status 0 and 9 - 13, zeros for a row whose output graph was
+ *     not made (1 - 8, 17, a corpus id outside [0, N)).
+ *   arom uint8 [B, 128] (optional, may be NULL) = 1 / 0 per atom in the string order of the input, 0xFF beyond the atoms, and 0xFF
+ *     everywhere where info is zeros.
+ *   Every element of every given output is written, nothing else is; two runs are bit-identical; the three entries are one source.
+ * One thread per row; MVAE_AROMATIZE_LDS_BYTES = 81920 B (80 KiB) of LDS per 64-row block, the rewrite's block with nothing added:
+ *   the matching's four byte arrays are the two halves of the half-edge list and two of the writer's byte arrays, which the adjacency
+ *   fills only afterwards; the candidate neighbours (<= 3 per atom) stand in the three byte arrays; candidates, electrons and aromatic
+ *   atoms are 64-bit masks in registers, the search path is one 64-bit register.  No recursion, no private array.
+ * Refused before anything is enqueued: exactly what the canon entries refuse of these arguments.
+ */
+#define MVAE_SMILES_NOT_AROMATIC 17
+#define MVAE_AROMATIZE_INFO 4
+#define MVAE_AROMATIZE_COUNTS 32
+#define MVAE_AROMATIZE_LDS_BYTES 81920
+int mvae_smiles_aromatize_rows(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */,
+                               const int32_t* chem_info /* [V] */, const int32_t* emit /* [48] */, int bos_id, int eos_id, int pad_id,
+                               int max_content, int T_out, int64_t* out /* [B, T_out] */, int32_t* out_len /* [B] */,
+                               int32_t* status /* [B] */, int32_t* counts /* [32] or NULL */, int32_t* info /* [B, 4] or NULL */,
+                               uint8_t* arom /* [B, 128] or NULL */, void* stream);
+int mvae_smiles_aromatize_corpus(const uint8_t* tokens, const int64_t* offsets /* [N + 1] */, int64_t N, const int64_t* rows /* [B] */,
+                                 int B, int V, const int32_t* tok_info /* [V] */, const int32_t* chem_info /* [V] */,
+                                 const int32_t* emit /* [48] */, int max_content, int stride, uint8_t* tokens_out /* [B, stride] */,
+                                 int64_t* offsets_out /* [2 B + 1] */, int32_t* status /* [B] */, int32_t* counts /* [32] or NULL */,
+                                 int32_t* err /* [1] or NULL */, int32_t* info /* [B, 4] or NULL */, uint8_t* arom /* [B, 128] or NULL */,
+                                 void* stream);
+int mvae_smiles_aromatize_host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */,
+                               const int32_t* chem_info /* [V] */, const int32_t* emit /* [48] */, int bos_id, int eos_id, int pad_id,
+                               int max_content, int T_out, int64_t* out /* [B, T_out] */, int32_t* out_len /* [B] */,
+                               int32_t* status /* [B] */, int32_t* info /* [B, 4] or NULL */, uint8_t* arom /* [B, 128] or NULL */);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Tanimoto similarity of fingerprints (an addition: the structure-aware counterpart of mvae_latent_knn and mvae_edit_knn).  Fingerprints

@@ -231,6 +231,7 @@ class MosesDeviceDataset:
         self._scaffolds = self._scaffold_hist = self._scaffold_order = self._mol_keys = None     # scaffolds() and what is derived from it
         self._kekule = None
         self._canonical = None                                         # canonical(): (dataset, status, counts), computed on first use
+        self._normal = None                                            # normal_form(): (dataset, status, counts), likewise
         self._fragments = self._fragment_hist = self._fragment_order = None      # fragments() and what is derived from it
         self._scaffold_smiles = None                                   # scaffold_smiles(): (dataset, rows, status, counts), likewise
 
@@ -512,6 +513,38 @@ class MosesDeviceDataset:
         """How many corpus rows have each ``canonical_status``: int32 [16] on the device, kept by the kernel's integer atomic adds."""
         self.canonical()
         return self._canonical[2]
+
+    def normal_form(self):
+        """The corpus in aromatic normal form: a ``MosesDeviceDataset`` on the same device whose row r is the normal form of this one's
+        row r (include/mvae.h, "Aromatic normal form": aromaticity perceived by this library's own rule, then the canonical spelling; a
+        row that cannot be written -- ``normal_status()`` != 0 -- keeps its own spelling), from ONE ``mvae_smiles_aromatize_corpus``
+        launch over all rows, its gapped CSR compacted on the device.  Asked with ``VAE.normal_form`` rows, its ``lookup`` / ``contains`` /
+        ``n_distinct`` count a Kekule and an aromatic spelling of one molecule once, which ``canonical()`` does not.  NOT rdkit's
+        aromaticity model or canonical SMILES; no stereo.  Cached; the host waits once, for the row lengths.  ValueError for a
+        vocabulary of more than 64 ids."""
+        if self._normal is None:
+            from . import ops
+            from .vocab import smiles_emit_table
+            tok, chem = self._fp_tables("normal_form")
+            dev, n, stride = self.device, self.n, max(127, self.max_len)          # a row that is copied through fits
+            counts = torch.zeros(ops.AROMATIZE_COUNTS, dtype=torch.int32, device=dev)
+            tokens_out, offsets_out, status, _, _ = ops.smiles_aromatize_corpus(
+                self.tokens, self.offsets, n, torch.arange(n, dtype=torch.long, device=dev), tok, chem, smiles_emit_table(self.vocab).to(dev),
+                127, stride, info=False, arom=False, counts=counts)
+            ds = self._compacted(tokens_out, offsets_out, None)
+            self._normal = (ds, status, counts)
+        return self._normal[0]
+
+    def normal_status(self):
+        """The status of every corpus row under ``normal_form()``: int32 [N] on the device, the codes of ``ops.AROMATIZE_STATUS_NAMES``
+        (0: row r of ``normal_form()`` is the normal form; anything else: it is this corpus' own row r)."""
+        self.normal_form()
+        return self._normal[1]
+
+    def normal_counts(self):
+        """How many corpus rows have each ``normal_status()``: int32 [32] on the device, kept by the kernel's integer atomic adds."""
+        self.normal_form()
+        return self._normal[2]
 
     def scaffold_smiles(self):
         """The Murcko scaffolds of the corpus as token rows (include/mvae.h, "Scaffold SMILES"): (ds_scaf, rows) -- a
@@ -931,6 +964,39 @@ def canonical_smiles(strings, vocab, device="cuda", return_status=False):
         _require_cuda(dev, "data.canonical_smiles")
         out, out_len, status, _, _ = ops.smiles_canon_rows(x.to(dev), *(t.to(dev) for t in tables), vocab.bos, vocab.eos, vocab.pad, info=False,
                                                            rank=False)
+    out, out_len, status = out.cpu().numpy(), out_len.cpu().numpy(), status.cpu().numpy()
+    table = np.array([vocab.i2c[i] for i in range(len(vocab))], dtype=object)
+    res = [s if st else "".join(table[row[1:k - 1]]) for s, row, k, st in zip(strings, out, out_len, status)]
+    return (res, status) if return_status else res
+
+
+def normal_smiles(strings, vocab, device="cuda", return_status=False):
+    """The aromatic normal form of every string (include/mvae.h, "Aromatic normal form"): a list of strings, equal for a Kekule spelling,
+    an aromatic spelling and every respelling of one molecule -- aromaticity perceived by this library's own rule, then the spelling of
+    ``canonical_smiles``; NOT rdkit's aromaticity model or canonical SMILES, no stereo.  A string that cannot be written comes back as it
+    is; ``return_status=True`` also returns the int32 [len(strings)] statuses (ops.AROMATIZE_STATUS_NAMES: 7 = does not kekulise, 17 = a
+    lower-case atom the rule does not find aromatic).  One mvae_smiles_aromatize_rows launch on ``device``; ``device="cpu"`` asks for the
+    host entry instead (the same source compiled for the CPU).  ValueError for a vocabulary of more than 64 ids or no strings."""
+    from . import ops
+    from .vocab import smiles_token_table, smiles_chem_table, smiles_emit_table
+    strings = list(strings)
+    if not strings:
+        raise ValueError("normal_smiles: needs at least one string")
+    if len(vocab) > 64:
+        raise ValueError(f"normal_smiles: the vocabulary has {len(vocab)} ids, at most 64 are supported")
+    dev = torch.device(device)
+    ids = [vocab.string2ids(s, add_bos=True, add_eos=True) for s in strings]
+    x = torch.full((len(ids), max(map(len, ids))), vocab.pad, dtype=torch.long)
+    for b, row in enumerate(ids):
+        x[b, :len(row)] = torch.as_tensor(row)
+    tables = (smiles_token_table(vocab), smiles_chem_table(vocab), smiles_emit_table(vocab))
+    if dev.type == "cpu":
+        out, out_len, status, _, _ = ops.smiles_aromatize_host(x, *tables, vocab.bos, vocab.eos, vocab.pad, info=False, arom=False)
+    else:
+        from .models import _require_cuda
+        _require_cuda(dev, "data.normal_smiles")
+        out, out_len, status, _, _ = ops.smiles_aromatize_rows(x.to(dev), *(t.to(dev) for t in tables), vocab.bos, vocab.eos, vocab.pad, info=False,
+                                                           arom=False)
     out, out_len, status = out.cpu().numpy(), out_len.cpu().numpy(), status.cpu().numpy()
     table = np.array([vocab.i2c[i] for i in range(len(vocab))], dtype=object)
     res = [s if st else "".join(table[row[1:k - 1]]) for s, row, k, st in zip(strings, out, out_len, status)]

@@ -566,6 +566,32 @@ class VAE(_SavedState, nn.Module):
         return rows, status, extra
 
     @torch.no_grad()
+    def normal_form(self, x, max_content=127, info=False):
+        """The aromatic normal form of token rows x (what ``syntax_valid`` takes) on the device, one mvae_smiles_aromatize_rows launch,
+        no host wait: (rows int64 [B, max(T, max_content + 2)] -- <bos>, the new tokens, <eos>, <pad> --, status int32 [B],
+        ops.AROMATIZE_STATUS_NAMES).  ``canonical`` behind an aromaticity perception: the row's graph is read, the atoms on a cycle of
+        5 - 7 candidate atoms with 4 k + 2 electrons get the aromatic flag, the bonds between them become aromatic bonds, and that graph
+        is written in the canonical spelling, so that a Kekule spelling, an aromatic spelling and every respelling of one molecule are one
+        row (include/mvae.h, "Aromatic normal form": this library's own rule, NOT rdkit's aromaticity model or canonical SMILES; no
+        envelope cycles, no stereo).  A row that cannot be written (status != 0: ``canonical``'s reasons, 7: it does not kekulise, 17: a
+        lower-case atom that the rule does not find aromatic) comes back unchanged.  ``info=True`` also returns {"atoms", "aromatic",
+        "raised", "lowered_bonds": int32 [B], "arom": uint8 [B, 128]}.  ValueError for a vocabulary of more than 64 ids."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.normal_form")
+        if len(self.vocabulary) > 64:
+            raise ValueError(f"normal_form: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
+        x = self._rows(x, "normal_form", dev)
+        want = None if info else False
+        rows, _, status, inf, arom = ops.smiles_aromatize_rows(x, self._smiles_table(dev), self._smiles_chem_table(dev),
+                                                               self._smiles_emit_table(dev), self.bos, self.eos, self.pad, max_content,
+                                                               info=want, arom=want)
+        if not info:
+            return rows, status
+        extra = {name: inf[:, i] for i, name in enumerate(ops.AROMATIZE_INFO)}
+        extra["arom"] = arom
+        return rows, status, extra
+
+    @torch.no_grad()
     def scaffold_smiles(self, x, max_content=127):
         """The Murcko scaffold of token rows x (what ``syntax_valid`` takes) as token rows on the device, one
         mvae_smiles_scaffold_smiles_rows launch, no host wait: (out int64 [B, max(T, max_content + 2)] -- <bos>, the scaffold's tokens,

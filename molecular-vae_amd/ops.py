@@ -1187,6 +1187,45 @@ def smiles_fragment_smiles_corpus(tokens, offsets, N, rows, tok_info, chem_info,
                           _FRAGMENT_SMILES_OUT, (tokens_out, offsets_out, status, info), counts, err, _frag(frag), FRAGMENT_SMILES_COUNTS)
 
 
+SMILES_STATUS_NOT_AROMATIC = 17               # include/mvae.h: MVAE_SMILES_NOT_AROMATIC, given by the aromatize entries only
+AROMATIZE_STATUS_NAMES = FRAGMENT_SMILES_STATUS_NAMES + ("not_aromatic",)               # index = status; 14 - 16 are never given here
+AROMATIZE_INFO = ("atoms", "aromatic", "raised", "lowered_bonds")   # the columns of info [*, 4] (MVAE_AROMATIZE_INFO)
+AROMATIZE_COUNTS = 32                                               # MVAE_AROMATIZE_COUNTS: the per-status histogram has a slot 17
+_AROMATIZE_OUT = ((torch.int32, (len(AROMATIZE_INFO),), True), (torch.uint8, (128,), True))        # info, arom
+
+
+def smiles_aromatize_rows(x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content=127, T_out=None, out=None, out_len=None, status=None,
+                          info=None, arom=None, counts=None):
+    """The aromatic normal form of token rows x (int64 [B, T], bos first) on the device: (out int64 [B, T_out], out_len int32 [B], status
+    int32 [B], info int32 [B, 4], arom uint8 [B, 128]) -- every row read into its graph, aromaticity perceived on it by this library's
+    own rule (include/mvae.h, "Aromatic normal form": candidates by electrons, simple cycles of 5 - 7 atoms with 4 k + 2 of them), and
+    the perceived graph written in the spelling of ``smiles_canon_rows``, so that C1=CC=CC=C1 and c1ccccc1 give one row.  A refused row
+    (status != 0, ``AROMATIZE_STATUS_NAMES``: the canon entries' reasons, 7 "kekule", or 17 "not_aromatic" for a lower-case atom the
+    rule does not find aromatic) is copied through.  info = atoms, aromatic atoms, atoms raised from upper case, double bonds lowered
+    (``AROMATIZE_INFO``); arom[k] = 1 / 0 for atom k of the input, 0xFF beyond the atoms and for a refused row; ``info=False`` /
+    ``arom=False``: not written (None in its place).  counts: int32 [32].  NOT rdkit's aromaticity model or canonical SMILES; no stereo.
+    One launch (mvae_smiles_aromatize_rows)."""
+    return _writer_rows("mvae_smiles_aromatize_rows", False, x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, (), max_content, T_out,
+                        _AROMATIZE_OUT, (out, out_len, status, info, arom), counts, (), AROMATIZE_COUNTS)
+
+
+def smiles_aromatize_host(x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content=127, T_out=None, out=None, out_len=None, status=None,
+                          info=None, arom=None):
+    """smiles_aromatize_rows on HOST tensors: the same source compiled for the CPU, a plain loop over the rows
+    (mvae_smiles_aromatize_host) -- for tests and for machines without a device; not a fallback of the device entries."""
+    return _writer_rows("mvae_smiles_aromatize_host", True, x, tok_info, chem_info, emit, bos_id, eos_id, pad_id, (), max_content, T_out,
+                        _AROMATIZE_OUT, (out, out_len, status, info, arom), None, (), AROMATIZE_COUNTS)
+
+
+def smiles_aromatize_corpus(tokens, offsets, N, rows, tok_info, chem_info, emit, max_content=127, stride=None, tokens_out=None, offsets_out=None,
+                            status=None, info=None, arom=None, counts=None, err=None):
+    """smiles_aromatize_rows over the rows `rows` (int64 [B]) of the CSR corpus, one launch (mvae_smiles_aromatize_corpus): (tokens_out
+    uint8 [B, stride], offsets_out int64 [2 B + 1], status int32 [B], info int32 [B, 4], arom uint8 [B, 128]) in the gapped CSR layout of
+    ``smiles_rewrite_corpus``, with its err and counts (int32 [32]); ``info=False`` / ``arom=False``: not written (None in its place)."""
+    return _writer_corpus("mvae_smiles_aromatize_corpus", tokens, offsets, N, rows, tok_info, chem_info, emit, (), max_content, stride,
+                          _AROMATIZE_OUT, (tokens_out, offsets_out, status, info, arom), counts, err, (), AROMATIZE_COUNTS)
+
+
 SUBSTRUCT_QATOMS = 32                         # include/mvae.h: MVAE_SUBSTRUCT_QATOMS, the atoms of a query and the columns of `map`
 SUBSTRUCT_QUERIES = 64                        # MVAE_SUBSTRUCT_QUERIES, the queries of one launch: one bit of an int64 each
 SUBSTRUCT_WORDS = 100                         # MVAE_SUBSTRUCT_WORDS, the int32 words of one compiled query

@@ -802,7 +802,7 @@ def moses_reconstruction(model, batches, beam_width=1, max_len=100, syntax=False
 def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top_k=None, top_p=None, seed=0, z=None, syntax=False,
                    count_valid=False, novel_against=None, prefix=None, nearest=False, valence=False,
                    int_div=False, snn=False, scaffolds=False, kekule=False, canonical=False, filters=None, filter_steps=65536,
-                   top_scaffolds=0, fragments=False):
+                   top_scaffolds=0, fragments=False, normal=False):
     """The reference's generation pipeline (``hugesample.py``: sample in batches, hash the strings, count unique / total) with the hashing
     and the deduplication on the device: ``n_samples`` sequences from a ``mosesvae.VAE`` in batches of ``batch_size`` (the last one shorter),
     batch j with seed ``seed + j`` and ``temp`` / ``top_k`` / ``top_p`` as ``VAE.sample`` takes them.  ``z`` None draws each batch's latents
@@ -914,7 +914,19 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     have one, every drawn sample counting (each distinct sample weighted by its "counts"), by descending count; equal counts by the
     smaller token row (<bos>, the ids, <eos>, <pad>, compared left to right).  Scaffolds are compared on tokens, exactly: two keys of
     "n_scaffolds" are never merged here and one key may be several strings.  The default 0 leaves the launches and the keys of the
-    result what they were."""
+    result what they were.
+    ``normal=True`` (ValueError for a vocabulary of more than 64 ids or max_len > 129, before any device work): what ``canonical=True``
+    reports, on the aromatic normal form -- ``VAE.normal_form`` (include/mvae.h, "Aromatic normal form"): aromaticity is perceived by
+    this library's own rule before the canonical spelling, so a sample written ``C1=CC=CC=C1`` and one written ``c1ccccc1`` are one
+    molecule here and two under ``canonical``.  NOT rdkit's aromaticity model or canonical SMILES; no stereo.  Each batch's NEW rows go
+    through one ``mvae_smiles_aromatize_rows`` launch, no further host wait.  The result gains the lists "normal_status" (the codes of
+    ``ops.AROMATIZE_STATUS_NAMES``) and "normal_strings" (the normal form; the sample's own string where the status is not 0), aligned
+    with "strings"; "normal_status_counts" ({status: count} over the distinct samples); and "unique_normal", the distinct normal-form
+    token rows among the samples of status 0.  With ``novel_against`` it further gains "normal_corpus_row", aligned with "strings": the
+    lowest row of ``novel_against.normal_form()`` that equals the sample's normal form, -1 for none (one exact ``lookup`` per batch in
+    the device index ``canonical=True`` uses; the corpus is put into normal form once, by one launch, and cached), and "novel_normal",
+    the distinct normal-form rows of status 0 that equal no corpus row's.  Without the flag the launches and the keys of the result are
+    what they were."""
     n_samples, batch_size, max_len = int(n_samples), int(batch_size), int(max_len)
     if n_samples < 1 or batch_size < 1 or max_len < 1:
         raise ValueError(f"moses_generate: n_samples, batch_size and max_len must be >= 1, got {n_samples}, {batch_size}, {max_len}")
@@ -967,6 +979,11 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
             raise ValueError(f"moses_generate: canonical=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
         if max_len > 129:
             raise ValueError(f"moses_generate: canonical=True supports max_len <= 129, got {max_len}")
+    if normal:
+        if len(model.vocabulary) > 64:
+            raise ValueError(f"moses_generate: normal=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
+        if max_len > 129:
+            raise ValueError(f"moses_generate: normal=True supports max_len <= 129, got {max_len}")
     if filters is not None:
         from .data import compile_substructures
         filters = compile_substructures(filters, model.vocabulary)
@@ -1001,6 +1018,8 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     kek_codes = torch.arange(8, dtype=torch.int32, device=dev) if kekule else None
     canons = []                                                 # (canonical row [*, 129], status, corpus row or None) of each new sample, likewise
     canon_corpus = novel_against.canonical() if canonical and novel_against is not None else None       # one launch, cached by the dataset
+    normals = []                                                # (normal-form row [*, 129], status, corpus row or None) of each new sample, likewise
+    normal_corpus = novel_against.normal_form() if normal and novel_against is not None else None       # one launch, cached by the dataset
     filt = torch.zeros(2 + 2 * len(filters), dtype=i64, device=dev) if filters is not None else None      # _filter_counts, summed over the batches
     stage = [None, None]                                       # pinned staging rows [batch_size, max_len + 1] (ids, end), alternating
     pending = None
@@ -1097,6 +1116,9 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
             if canonical:
                 c_rows, c_status = model.canonical(x[sel])          # 129 columns: 127 content tokens at the most, and max_len <= 129
                 canons.append((c_rows, c_status, canon_corpus.lookup(c_rows) if canon_corpus is not None else None))
+            if normal:
+                a_rows, a_status = model.normal_form(x[sel])        # 129 columns, as the canonical rows
+                normals.append((a_rows, a_status, normal_corpus.lookup(a_rows) if normal_corpus is not None else None))
             g0 = counts.numel()
             counts = torch.cat([counts, cnt[src]])
             seen_h, perm = torch.sort(torch.cat([seen_h, hs[src]]))
@@ -1186,6 +1208,19 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         if novel_against is not None:
             res["canonical_corpus_row"] = torch.cat([c[2] for c in canons]).tolist() if canons else []
             res["novel_canonical"] = int((canon_corpus.lookup(distinct) < 0).sum()) if distinct.shape[0] else 0
+    if normal:
+        a_rows = torch.cat([c[0] for c in normals]) if normals else torch.empty((0, 129), dtype=i64, device=dev)
+        a_status = torch.cat([c[1] for c in normals]) if normals else torch.empty(0, dtype=torch.int32, device=dev)
+        res["normal_status"] = a_status.tolist()
+        res["normal_status_counts"] = dict(enumerate(torch.bincount(a_status.cpu(), minlength=len(ops.AROMATIZE_STATUS_NAMES)).tolist()))
+        v = model.vocabulary
+        res["normal_strings"] = [s if st else v.ids2string(r[:r.index(v.eos) + 1], rem_bos=True, rem_eos=True)
+                                 for s, st, r in zip(strings, res["normal_status"], a_rows.tolist())]
+        distinct = torch.unique(a_rows[a_status == 0], dim=0)
+        res["unique_normal"] = distinct.shape[0]
+        if novel_against is not None:
+            res["normal_corpus_row"] = torch.cat([c[2] for c in normals]).tolist() if normals else []
+            res["novel_normal"] = int((normal_corpus.lookup(distinct) < 0).sum()) if distinct.shape[0] else 0
     if filters is not None:
         res.update(_filter_result(filt.tolist(), len(filters)))
     return res
