@@ -982,6 +982,10 @@ __global__ __launch_bounds__(256) void ce_rows_fwd_kernel(int B, int T_, int V, 
 
 // ------------------------------------------------------------------------------------------- grad-norm + Adam
 constexpr int SUMSQ_CHUNK = 1 << 16;   // elements per partial
+// x^2 + y^2 + z^2 + w^2 of one 16-byte piece.  Explicit fmaf: the whole-chunk loop and the short-chunk loop below must round alike, which
+// implicit contraction does not promise (left to the compiler, one loop fused x and z into the sums, the other y and w: a short chunk and
+// its zero-padded form then differed in the last bits).
+__device__ __forceinline__ float sumsq4(const float4& v) { return fmaf(v.x, v.x, v.y * v.y) + fmaf(v.z, v.z, v.w * v.w); }
 __global__ __launch_bounds__(256) void sumsq_kernel(long n, const float* g, float* partial) {
   __shared__ float red[4];
   const long beg = (long)blockIdx.x * SUMSQ_CHUNK;
@@ -995,7 +999,7 @@ __global__ __launch_bounds__(256) void sumsq_kernel(long n, const float* g, floa
   if (cnt == SUMSQ_CHUNK) {
     for (long i = threadIdx.x; i < SUMSQ_CHUNK / 4; i += 1024) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) { const float4 v = g4[i + 256 * k]; acc[k] += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w); }
+      for (int k = 0; k < 4; ++k) acc[k] += sumsq4(g4[i + 256 * k]);
     }
   } else {
     for (long i = threadIdx.x; i <= n4; i += 1024) {
@@ -1005,7 +1009,7 @@ __global__ __launch_bounds__(256) void sumsq_kernel(long n, const float* g, floa
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (idx < n4) v = g4[idx];
         else if (idx == n4 && rem) { const float* t = g + beg + 4 * n4; v.x = t[0]; if (rem > 1) v.y = t[1]; if (rem > 2) v.z = t[2]; }
-        acc[k] += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+        acc[k] += sumsq4(v);
       }
     }
   }
