@@ -112,6 +112,9 @@ ap.add_argument("--canonical", action="store_true", help="print each round's dis
 ap.add_argument("--normal", action="store_true", help="print each round's distinct aromatic normal forms (unique@k on molecules: a Kekule and "
                                                       "an aromatic spelling count once) and, with --novel_against, those absent from the "
                                                       "corpus in normal form")
+ap.add_argument("--selfies", action="store_true", help="the model's vocabulary is a vocab.SelfiesVocab (--vocab, else SelfiesVocab.default()): "
+                                                       "every batch is decoded to SMILES on the device (this library's own SELFIES rules, not "
+                                                       "the selfies package's) and every figure is computed on the decoded rows")
 ap.add_argument("--filters", default=None, metavar="FILE", help="SMILES fragments, one per line: print each round's share of valence-consistent "
                                                                    "samples that contain none of them, and the hits per fragment")
 ap.add_argument("--reconstruct", default=None, metavar="FILE", help="strings, one per line: report exact-match reconstruction at z = mu "
@@ -133,6 +136,18 @@ if args.vocab:
         vocab = pickle.load(f)
 else:
     vocab = VC.OneHotVocab.from_data(D.synthetic_smiles(2048, seed=0))
+smiles_vocab = vocab                                      # the vocabulary of the molecules: the corpus, the filters, the figures
+if args.selfies:                                          # ... and `vocab`, the model's, spells SELFIES symbols
+    if args.reconstruct:
+        sys.exit("--selfies excludes --reconstruct: the file holds SMILES and the model reads SELFIES (encode it with data.selfies_from_smiles)")
+    if not isinstance(vocab, VC.SelfiesVocab):
+        vocab = VC.SelfiesVocab.default()
+    writes = set("BCNOPSFIHclrnos=#()[]+-0123456789")     # every character the decoder can write
+    lines = D.load_smiles(args.novel_against) if args.novel_against else []
+    foreign = sorted(set().union(*map(set, lines)) - writes) if lines else []
+    if foreign:                                           # they get ids, so that the corpus rows stay what they are; no sample can equal such a row
+        print(f"--selfies: the corpus uses characters no decoded row holds: {' '.join(foreign)}", flush=True)
+    smiles_vocab = VC.OneHotVocab(writes | set(foreign))
 torch.manual_seed(42)
 model = MV.VAE(vocab)
 if args.ckpt:
@@ -140,7 +155,7 @@ if args.ckpt:
 model = model.to(dev).eval()
 model.prior = args.prior
 model.seed_noise(args.seed)
-corpus = mv.MosesDeviceDataset(D.load_smiles(args.novel_against), vocab, device=dev) if args.novel_against else None
+corpus = mv.MosesDeviceDataset(D.load_smiles(args.novel_against), smiles_vocab, device=dev) if args.novel_against else None
 
 if args.reconstruct:
     collate = VC.get_collate_fn(vocab)
@@ -169,7 +184,7 @@ if args.snn and corpus is None:
 filters = None
 if args.filters:
     with open(args.filters) as ff:
-        filters = mv.compile_substructures([line.strip() for line in ff if line.strip()], model.vocabulary)
+        filters = mv.compile_substructures([line.strip() for line in ff if line.strip()], smiles_vocab)
 seen, total, valid, syntax_valid = {}, 0, 0, 0
 chem_valid, reasons, props = 0, [0] * 7, {}               # unique valence-consistent string -> (weight, heavy atoms)
 near = {}                                                 # unique string -> (distance, corpus row) of its nearest training string
@@ -185,8 +200,11 @@ with open(args.log, "w", buffering=1) as f:
                                 top_p=args.top_p, seed=args.seed + r * args.batches_per_round, syntax=args.syntax, count_valid=True,
                                 novel_against=corpus, prefix=args.prefix, nearest=args.nearest, valence=args.valence,
                                 int_div=args.int_div, snn=args.snn, scaffolds=args.scaffolds, kekule=args.kekule, canonical=args.canonical,
-                                filters=filters, top_scaffolds=args.top_scaffolds if args.scaffolds else 0, fragments=args.fragments, normal=args.normal)
+                                filters=filters, top_scaffolds=args.top_scaffolds if args.scaffolds else 0, fragments=args.fragments, normal=args.normal,
+                                selfies=smiles_vocab if args.selfies else None)
         total += res["total"]
+        if args.selfies:
+            print(f"round {r}: {res['decoded']} of {res['total']} SELFIES samples decoded to a SMILES row", flush=True)
         if args.kekule:
             kekule_valid += res["kekule_valid"]
             kekule_failed += res["kekule_status_counts"][7]

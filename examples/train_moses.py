@@ -41,12 +41,16 @@ ap.add_argument("--bucket", default=0, type=int, help="with --device-data: group
 ap.add_argument("--augment", action="store_true", help="with --device-data: SMILES enumeration -- every molecule goes in under another randomised "
                                                        "spelling each epoch (one more launch per batch, no host work)")
 ap.add_argument("--augment-slack", default=0, type=int, help="with --augment: extra columns per batch for spellings longer than the original")
+ap.add_argument("--selfies", action="store_true", help="with --device-data: train on the corpus encoded as SELFIES on the device "
+                                                       "(MosesDeviceDataset.selfies(): this library's own encoding, not the selfies package's)")
 ap.add_argument("--report", default=None, help="write a JSON summary (the per-epoch postfix dictionaries + samples) here")
 args = ap.parse_args()
 if args.bucket and not args.device_data:
     ap.error("--bucket needs --device-data")
 if args.augment and not args.device_data:
     ap.error("--augment needs --device-data")
+if args.selfies and (not args.device_data or args.augment):
+    ap.error("--selfies needs --device-data and excludes --augment (the rewrite respells SMILES rows)")
 
 rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
 torch.cuda.set_device(args.local_rank)
@@ -65,6 +69,11 @@ collate = VC.get_padded_collate_fn(vocab, pin_memory=True)
 sampler = mv.ShardedSampler(len(smiles), rank=rank, world=world, seed=0)
 loader = torch.utils.data.DataLoader(smiles, batch_size=args.batch_size, sampler=sampler, collate_fn=collate, drop_last=True)
 device_data = D.MosesDeviceDataset(smiles, vocab, device=dev) if args.device_data else None
+if args.selfies:                                         # one encode launch; the model is built on the SELFIES vocabulary
+    device_data = device_data.selfies()
+    print(f"--selfies: {len(device_data)} of {len(smiles)} rows encoded", flush=True)
+    vocab = device_data.vocab
+    sampler = mv.ShardedSampler(len(device_data), rank=rank, world=world, seed=0)
 
 torch.manual_seed(42)
 model = MV.VAE(vocab).to(dev)

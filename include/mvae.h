@@ -1416,6 +1416,108 @@ int mvae_smiles_aromatize_host(int B, int T, int V, const int64_t* x, int64_t x_
                                int32_t* status /* [B] */, int32_t* info /* [B, 4] or NULL */, uint8_t* arom /* [B, 128] or NULL */);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * SELFIES (an addition: decoding is an eleventh producer of the "SMILES graph" walk's graph and the sixth family that writes a string;
+ * encoding is the seventh).  mvae_selfies_decode_* turn rows of SELFIES tokens into the canonical Kekule SMILES rows of "SMILES canon";
+ * mvae_selfies_encode_* turn SMILES rows into SELFIES rows.
+ * What this is NOT: the derivation below is this library's own, stated here in full.  The symbol spelling and the derivation follow
+ *   SELFIES 2.x so that strings interchange in the ordinary case, but this is NOT the selfies package's decoder or encoder: agreement
+ *   with the package is neither tested nor claimed.  No stereo, no isotopes, no elements beyond the eleven of "SMILES graph", charges in
+ *   {-1, 0, +1}, at most 127 symbols and 127 atoms per row.
+ * Symbols.  A SELFIES vocabulary maps token ids to symbols.  The kernels see one int32 [V] info table; a word holds
+ *     bits 0-2   the kind: 0 other, 1 atom, 2 branch, 3 ring, 4 nop, 5 <eos>
+ *     bits 3-4   beta, the requested bond order 1 - 3: [=X] is 2, [#X] is 3
+ *     atom:      bits 5-8 the element (index into H B C N O F P S Cl Br I), 9-10 the charge + 1, 11 bracket atom, 12-14 stated hydrogens 0 - 4
+ *     branch / ring:  bits 16-17 L, the number of index symbols that follow, 1 - 3
+ *     bits 20-23 the index value 0 - 15 of the symbol read as a digit
+ *   Atom symbols are spelled [bE], [bEHn], [bE+1], [bE-1], [bEHn+1], [bEHn-1] with b one of "", "=", "#": [C], [=N], [NH1], [=N+1], [O-1],
+ *   [NH2+1].  A symbol with neither hydrogens nor charge is written as an unbracketed atom ([H] excepted); every other atom symbol is
+ *   written as a bracket atom with exactly the stated hydrogens.  Index values: [C] 0, [Ring1] 1, [Ring2] 2, [Branch1] 3, [=Branch1] 4,
+ *   [#Branch1] 5, [Branch2] 6, [=Branch2] 7, [#Branch2] 8, [O] 9, [N] 10, [=N] 11, [=C] 12, [#C] 13, [S] 14, [P] 15; every other symbol,
+ *   and a symbol missing because the row or the enclosing branch ended, reads as 0.  An index of L symbols is read in base 16, most
+ *   significant first.
+ * Capacity.  cap(atom) = the largest valence of (element, charge) in "SMILES graph" minus the stated hydrogens; neutral I has 1 minus
+ *   them.  A pair without an entry is no symbol, and neither is one whose capacity is below 1 (it could not be bonded to anything).
+ *   Every capacity is at most the walk's largest valence, so every decoded row is valence-consistent under the walk by construction.
+ * Derivation (decode).  The state: s, the bonds the previous atom can still make (0 before the first atom); prev, the atom the chain
+ *   hangs from; a list of deferred ring bonds; a stack of (resume state, root atom, end of the branch).  Symbols in order:
+ *   atom (beta, cap)   o = 0 if s == 0 (the first atom only), else min(beta, s, cap).  The atom is added with predecessor prev and bond
+ *                      order o; prev = it, s = cap - o.  If s is 0 the chain ends: the symbols left in the current branch are consumed
+ *                      without effect, at top level the rest of the row.
+ *   branch (beta, L)   if s <= 1 the symbol is skipped and its index symbols are read as ordinary symbols.  Else b = min(s - 1, beta), Q
+ *                      is read from the next L symbols, the next Q + 1 symbols (or what the enclosing branch has left) are derived with
+ *                      start state b from root prev, and the chain resumes at the same prev with s - b.
+ *   ring (beta, L)     if s == 0 it is skipped.  Else o = min(beta, s), Q is read, (l = max(0, prev - (Q + 1)), r = prev, o) is
+ *                      recorded, s -= o, and if s is 0 the chain ends as above.
+ *   nop                nothing.   <eos>, or the row end for a corpus row, ends the row.
+ *   Any other token (<bos>, <pad>, <unk>, an id >= V) anywhere in the content, consumed or not, gives status 1 with its column in info,
+ *   and so does a 128th symbol.  A row that adds no atom is status 1.
+ *   After the last symbol the recorded ring bonds are applied in order: skip if l == r; o = min(o, cap(l) - bondsum(l), cap(r) -
+ *   bondsum(r)) at that moment, skip if 0; if l and r are bonded already, by a tree bond or an earlier ring bond, that bond is raised by
+ *   min(o, 3 - its order); else the ring bond is added.  A bracket atom has its stated hydrogens and unused capacity stays unused; an
+ *   unbracketed atom gets the implicit hydrogens of "SMILES graph" on its bond sum.  The molecule a SELFIES row denotes is, by
+ *   definition, the graph of the SMILES row written.
+ * Into the writer.  The writer keeps ring closures as single bonds, so a ring bond of order >= 2 between l < r is made a tree bond: if
+ *   r's tree bond is single and l does not hang below r, r's predecessor becomes l with the ring bond's order and (old predecessor, r)
+ *   becomes the single closure; otherwise the same is tried at l; otherwise the row is MVAE_SMILES_RING_MULTI (9).  Then the adjacency,
+ *   the ranks and the writer of "SMILES canon" run unchanged.  Statuses: 0, 1, and the writer's 9 - 13; 2 - 8 never occur.  A row that
+ *   is not written gives the EMPTY row (<bos> <eos>; a corpus row of length 0), never a copy: its source is another language.
+ * Encode.  rew::read (statuses 1 - 6, 8); with aromatic atoms the matching of "Kekulisation" (7 without a perfect one), the bonds (a,
+ *   mate[a]) become double and the flags are dropped; a bracket atom gives the symbol with its hydrogens and charge, an unbracketed atom
+ *   the plain one; an atom whose bonds exceed the capacity of its symbol is MVAE_SELFIES_CAPACITY (18): hypervalent iodine.  The atoms
+ *   are emitted in increasing number, the SMILES string order.  For atom k: if k is a child of its predecessor but not the last one,
+ *   [bBranchL] with b its bond order, Q = size(k) - 1 and the smallest L that holds it; then its atom symbol with its bond order; then
+ *   for every ring closure whose later end is k, in increasing earlier end l, [RingL] or, for a closure that is double after
+ *   kekulisation, [=RingL], with Q = k - l - 1.  size(k) = the symbols of k's subtree.  A symbol the vocabulary lacks (emit table entry
+ *   -1), a bracket atom with neither hydrogens nor charge ([C]: its symbol would be read as the plain atom), or one with more than four
+ *   hydrogens, is 13; output longer
+ *   than max_content is 12.  The derivation of an encoded row skips no branch and ends no chain early.
+ * The emit table of the encode side, int32 [MVAE_SELFIES_EMIT = 529], role -> id, -1 = missing: atom symbols at (((beta - 1) * 11 +
+ *   element) * 3 + charge + 1) * 5 + hydrogens; [bBranchL] at 495 + (beta - 1) * 3 + L - 1; [bRingL] at 504 + the same; the symbol of
+ *   index value v at 513 + v.
+ * Entries.  Layouts of out / out_len / status, tokens_out / offsets_out / err and counts (int32 [MVAE_SELFIES_COUNTS = 32]) as in
+ *   mvae_smiles_canon_*.  decode: V and sinfo describe the SELFIES vocabulary (its <eos> is the word of kind 5), emit is the SMILES
+ *   emit table, bos_id / eos_id / pad_id are the SMILES ids written.  info int32 [B, 4] (may be NULL) = atoms, ring bonds kept, ring
+ *   bonds re-parented, the column of the token behind status 1 (else -1).  encode: V, tok_info, chem_info, emit and eos_in describe the
+ *   SMILES rows read, semit is the SELFIES emit table, bos_id / eos_id / pad_id are the SELFIES ids written.  info = atoms, branch
+ *   symbols, ring symbols, the atom behind status 18 (else -1).  A corpus id outside [0, N) gives status 1, err 2 and info 0 0 0 -1.
+ *   Every element of every given output is written; two runs are bit-identical; the three entries of a direction are one source.
+ * One thread per row; MVAE_SELFIES_LDS_BYTES = 81920 B of LDS per 64-row block, the rewrite's block with nothing added.
+ * Refused before anything is enqueued.  MVAE_ERR_UNSUPPORTED: V > 64.  MVAE_ERR_INVALID: a NULL pointer other than counts, err, info;
+ *   V, B, T or N < 1; x_ld < T; max_content outside [1, 127]; T_out < 2; stride < max_content; an output id outside [0, 255]; eos_in
+ *   outside [0, V).
+ */
+#define MVAE_SELFIES_CAPACITY 18
+#define MVAE_SELFIES_EMIT 529
+#define MVAE_SELFIES_COUNTS 32
+#define MVAE_SELFIES_LDS_BYTES 81920
+int mvae_selfies_decode_rows(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* sinfo /* [V] */, const int32_t* emit /* [48] */,
+                             int bos_id, int eos_id, int pad_id, int max_content, int T_out, int64_t* out /* [B, T_out] */,
+                             int32_t* out_len /* [B] */, int32_t* status /* [B] */, int32_t* counts /* [32] or NULL */,
+                             int32_t* info /* [B, 4] or NULL */, void* stream);
+int mvae_selfies_decode_corpus(const uint8_t* tokens, const int64_t* offsets /* [N + 1] */, int64_t N, const int64_t* rows /* [B] */, int B,
+                               int V, const int32_t* sinfo /* [V] */, const int32_t* emit /* [48] */, int max_content, int stride,
+                               uint8_t* tokens_out /* [B, stride] */, int64_t* offsets_out /* [2 B + 1] */, int32_t* status /* [B] */,
+                               int32_t* counts /* [32] or NULL */, int32_t* err /* [1] or NULL */, int32_t* info /* [B, 4] or NULL */,
+                               void* stream);
+int mvae_selfies_decode_host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* sinfo /* [V] */, const int32_t* emit /* [48] */,
+                             int bos_id, int eos_id, int pad_id, int max_content, int T_out, int64_t* out /* [B, T_out] */,
+                             int32_t* out_len /* [B] */, int32_t* status /* [B] */, int32_t* info /* [B, 4] or NULL */);
+int mvae_selfies_encode_rows(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */,
+                             const int32_t* chem_info /* [V] */, const int32_t* emit /* [48] */, int eos_in, const int32_t* semit /* [529] */,
+                             int bos_id, int eos_id, int pad_id, int max_content, int T_out, int64_t* out /* [B, T_out] */,
+                             int32_t* out_len /* [B] */, int32_t* status /* [B] */, int32_t* counts /* [32] or NULL */,
+                             int32_t* info /* [B, 4] or NULL */, void* stream);
+int mvae_selfies_encode_corpus(const uint8_t* tokens, const int64_t* offsets /* [N + 1] */, int64_t N, const int64_t* rows /* [B] */, int B,
+                               int V, const int32_t* tok_info /* [V] */, const int32_t* chem_info /* [V] */, const int32_t* emit /* [48] */,
+                               const int32_t* semit /* [529] */, int max_content, int stride, uint8_t* tokens_out /* [B, stride] */,
+                               int64_t* offsets_out /* [2 B + 1] */, int32_t* status /* [B] */, int32_t* counts /* [32] or NULL */,
+                               int32_t* err /* [1] or NULL */, int32_t* info /* [B, 4] or NULL */, void* stream);
+int mvae_selfies_encode_host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info /* [V] */,
+                             const int32_t* chem_info /* [V] */, const int32_t* emit /* [48] */, int eos_in, const int32_t* semit /* [529] */,
+                             int bos_id, int eos_id, int pad_id, int max_content, int T_out, int64_t* out /* [B, T_out] */,
+                             int32_t* out_len /* [B] */, int32_t* status /* [B] */, int32_t* info /* [B, 4] or NULL */);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Tanimoto similarity of fingerprints (an addition: the structure-aware counterpart of mvae_latent_knn and mvae_edit_knn).  Fingerprints
  * are dense rows of MVAE_FP_WORDS int64 words, 16-byte aligned (else MVAE_ERR_INVALID); any 1024-bit rows will do.
  * Similarity.  T(a, b) = c / (p_a + p_b - c), with p the popcounts and c the popcount of a AND b; T is 0 when the union is empty.  T is

@@ -8,8 +8,8 @@ from .models import (MolecularVAE, MolEncoder, MolDecoder, Lambda, ConvSELU, SEL
                      Flatten)
 from .functional import bce_kl_loss, make_loss_function, decoder_elbo  # noqa: F401
 from . import mosesvae, models2d, vocab, data  # noqa: F401
-from .data import MoleLoader, DeviceDataset, MosesDeviceDataset, MosesLatentIndex, tokenize_corpus, moses_epoch_plan, build_vocab, encode_smiles, synthetic_smiles, indices_to_smiles, randomized_smiles, canonical_smiles, normal_smiles, scaffold_smiles, fragment_smiles, compile_substructures, SubstructureTable  # noqa: F401
-from .vocab import CharVocab, OneHotVocab, PaddedBatch, pad_batch, get_collate_fn, get_padded_collate_fn  # noqa: F401
+from .data import MoleLoader, DeviceDataset, MosesDeviceDataset, MosesLatentIndex, tokenize_corpus, moses_epoch_plan, build_vocab, encode_smiles, synthetic_smiles, indices_to_smiles, randomized_smiles, canonical_smiles, normal_smiles, selfies_from_smiles, smiles_from_selfies, scaffold_smiles, fragment_smiles, compile_substructures, SubstructureTable  # noqa: F401
+from .vocab import CharVocab, OneHotVocab, SelfiesVocab, PaddedBatch, pad_batch, get_collate_fn, get_padded_collate_fn  # noqa: F401
 from .train import (FusedAdam, FusedSGD, GradSync, ShardedSampler, shard_batch, train_step, elbo_train_step, exact_match_accuracy,  # noqa: F401
                     evaluate, evaluate_elbo, save_checkpoint, load_checkpoint, strip_module_prefix, KLAnnealer, CyclicalKLAnnealer, CosineAnnealingLRWithRestart, cosine_lr_with_restart,
                     moses_train_step, moses_train_epoch, moses_reconstruction, moses_generate, moses_latent_diagnostics, generate_from_latent)

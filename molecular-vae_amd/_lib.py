@@ -223,6 +223,12 @@ SIGNATURES = {
     "mvae_smiles_aromatize_rows": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvae_smiles_aromatize_corpus": (_i, [_vp, _vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvae_smiles_aromatize_host": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mvae_selfies_decode_rows": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvae_selfies_decode_corpus": (_i, [_vp, _vp, _i64, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvae_selfies_decode_host": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "mvae_selfies_encode_rows": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvae_selfies_encode_corpus": (_i, [_vp, _vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvae_selfies_encode_host": (_i, [_i, _i, _i, _vp, _i64, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "mvae_tanimoto_knn_workspace": (_sz, [_i, _i64, _i]),
     "mvae_tanimoto_knn": (_i, [_i, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mvae_tanimoto_sum_workspace": (_sz, [_i64, _i64]),

@@ -472,12 +472,11 @@ int corpus(K kernel, const uint8_t* tokens, const int64_t* offsets, int64_t N, c
   return MVAE_OK;
 }
 
+// The host loop behind the checks.  selfies.hip, whose input and output vocabularies differ, states its own checks and calls this and the
+// two block bodies above: to them V, the tables and emit are whatever R::row reads, and bos_id, eos_id, pad_id are the output's.
 template <class R, class... F>
-int host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info, const int32_t* emit, int bos_id,
-         int eos_id, int pad_id, int max_content, int T_out, int64_t* out, int32_t* out_len, int32_t* status, F... family) {
-  if (V > 64) return MVAE_ERR_UNSUPPORTED;
-  if (!rows_args_ok(B, T, V, x, x_ld, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content, T_out, out, out_len, status))
-    return MVAE_ERR_INVALID;
+int host_rows(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info, const int32_t* emit,
+              int bos_id, int eos_id, int pad_id, int max_content, int T_out, int64_t* out, int32_t* out_len, int32_t* status, F... family) {
   const typename R::Args args{family...};
   Host store;
   for (long b = 0; b < B; ++b) {
@@ -497,6 +496,15 @@ int host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok
     }
   }
   return MVAE_OK;
+}
+
+template <class R, class... F>
+int host(int B, int T, int V, const int64_t* x, int64_t x_ld, const int32_t* tok_info, const int32_t* chem_info, const int32_t* emit, int bos_id,
+         int eos_id, int pad_id, int max_content, int T_out, int64_t* out, int32_t* out_len, int32_t* status, F... family) {
+  if (V > 64) return MVAE_ERR_UNSUPPORTED;
+  if (!rows_args_ok(B, T, V, x, x_ld, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content, T_out, out, out_len, status))
+    return MVAE_ERR_INVALID;
+  return host_rows<R>(B, T, V, x, x_ld, tok_info, chem_info, emit, bos_id, eos_id, pad_id, max_content, T_out, out, out_len, status, family...);
 }
 
 }  // namespace rew

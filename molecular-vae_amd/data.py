@@ -234,6 +234,7 @@ class MosesDeviceDataset:
         self._normal = None                                            # normal_form(): (dataset, status, counts), likewise
         self._fragments = self._fragment_hist = self._fragment_order = None      # fragments() and what is derived from it
         self._scaffold_smiles = None                                   # scaffold_smiles(): (dataset, rows, status, counts), likewise
+        self._selfies = None                                           # selfies(): (dataset, status, counts), likewise
 
     def __len__(self):
         return self.n
@@ -545,6 +546,36 @@ class MosesDeviceDataset:
         """How many corpus rows have each ``normal_status()``: int32 [32] on the device, kept by the kernel's integer atomic adds."""
         self.normal_form()
         return self._normal[2]
+
+    def selfies(self, svocab=None):
+        """The encodable rows of the corpus as a SELFIES training corpus: a ``MosesDeviceDataset`` in the tokens of `svocab` (a
+        ``vocab.SelfiesVocab``; None: ``SelfiesVocab.default()``) on the same device, from ONE ``mvae_selfies_encode_corpus`` launch over
+        all rows, its gapped CSR compacted on the device.  Row i of the result encodes corpus row ``source_rows[i]`` (int64 on the
+        device, ascending): the rows whose ``selfies_status()`` is 0.  The encoding keeps the atoms in their string order (include/mvae.h,
+        "SELFIES": Encode) and is this library's own, NOT the selfies package's encoder.  Cached per call with the same vocabulary
+        object; the host waits once, for the row lengths.  ValueError for a vocabulary of more than 64 ids."""
+        from .vocab import SelfiesVocab
+        if self._selfies is None or (svocab is not None and svocab is not self._selfies[0].vocab):
+            from . import ops
+            from .vocab import smiles_emit_table, selfies_emit_table
+            svocab = SelfiesVocab.default() if svocab is None else svocab
+            tok, chem = self._fp_tables("selfies")
+            dev, n = self.device, self.n
+            counts = torch.zeros(ops.SELFIES_COUNTS, dtype=torch.int32, device=dev)
+            tokens_out, offsets_out, status, _ = ops.selfies_encode_corpus(
+                self.tokens, self.offsets, n, torch.arange(n, dtype=torch.long, device=dev), tok, chem, smiles_emit_table(self.vocab).to(dev),
+                selfies_emit_table(svocab).to(dev), 127, 127, info=False, counts=counts)
+            rows = torch.nonzero(status == 0).view(-1)
+            ds = self._compacted(tokens_out, offsets_out, rows)
+            ds.vocab, ds.source_rows = svocab, rows
+            self._selfies = (ds, status, counts)
+        return self._selfies[0]
+
+    def selfies_status(self):
+        """The status of every corpus row under ``selfies()``: int32 [N] on the device, the codes of ``ops.SELFIES_STATUS_NAMES`` (0: the
+        row is in ``selfies()``; 13: a symbol the vocabulary lacks; 18: an atom over the capacity of its symbol)."""
+        self.selfies()
+        return self._selfies[1]
 
     def scaffold_smiles(self):
         """The Murcko scaffolds of the corpus as token rows (include/mvae.h, "Scaffold SMILES"): (ds_scaf, rows) -- a
@@ -1001,6 +1032,40 @@ def normal_smiles(strings, vocab, device="cuda", return_status=False):
     table = np.array([vocab.i2c[i] for i in range(len(vocab))], dtype=object)
     res = [s if st else "".join(table[row[1:k - 1]]) for s, row, k, st in zip(strings, out, out_len, status)]
     return (res, status) if return_status else res
+
+
+def selfies_from_smiles(strings, vocab, svocab, return_status=False):
+    """Every SMILES string as SELFIES text in the symbols of `svocab` (a ``vocab.SelfiesVocab``), by the host entry
+    mvae_selfies_encode_host (include/mvae.h, "SELFIES": Encode): "" for a string that cannot be encoded; ``return_status=True`` also
+    returns the int32 statuses (ops.SELFIES_STATUS_NAMES).  This library's own encoding, NOT the selfies package's.  ValueError for a
+    vocabulary of more than 64 ids or no strings."""
+    from . import ops
+    from .vocab import smiles_token_table, smiles_chem_table, smiles_emit_table, selfies_emit_table, token_rows
+    strings = list(strings)
+    if len(vocab) > 64 or len(svocab) > 64:
+        raise ValueError("selfies_from_smiles: at most 64 ids are supported")
+    x = token_rows(strings, lambda s: vocab.string2ids(s, add_bos=True, add_eos=True), vocab.pad, "selfies_from_smiles")
+    out, out_len, status, _ = ops.selfies_encode_host(x, smiles_token_table(vocab), smiles_chem_table(vocab), smiles_emit_table(vocab), vocab.eos,
+                                                      selfies_emit_table(svocab), svocab.bos, svocab.eos, svocab.pad, info=False)
+    res = [svocab.ids2string(row[:k].tolist()) for row, k in zip(out, out_len.tolist())]
+    return (res, status.numpy()) if return_status else res
+
+
+def smiles_from_selfies(strings, svocab, vocab, return_status=False):
+    """Every SELFIES text (symbols of `svocab`) as the canonical Kekule SMILES string of the molecule it denotes, by the host entry
+    mvae_selfies_decode_host (include/mvae.h, "SELFIES"): "" for a row that cannot be written; ``return_status=True`` also returns the
+    int32 statuses (ops.SELFIES_STATUS_NAMES).  This library's own derivation, NOT the selfies package's decoder.  ValueError for a
+    vocabulary of more than 64 ids or no strings."""
+    from . import ops
+    from .vocab import smiles_emit_table, selfies_info_table, token_rows
+    strings = list(strings)
+    if len(vocab) > 64 or len(svocab) > 64:
+        raise ValueError("smiles_from_selfies: at most 64 ids are supported")
+    x = token_rows(strings, lambda s: svocab.string2ids(s, add_bos=True, add_eos=True), svocab.pad, "smiles_from_selfies")
+    out, out_len, status, _ = ops.selfies_decode_host(x, selfies_info_table(svocab), smiles_emit_table(vocab), vocab.bos, vocab.eos, vocab.pad,
+                                                      info=False)
+    res = [vocab.ids2string(row[:k].tolist()) for row, k in zip(out, out_len.tolist())]
+    return (res, status.numpy()) if return_status else res
 
 
 def scaffold_smiles(strings, vocab, device="cuda", return_status=False):

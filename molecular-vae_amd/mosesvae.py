@@ -33,7 +33,7 @@ from . import _lib as L
 from . import ops
 from .models import (LinearWeights, EmbeddingWeights, RNNWeights, _Workspace, _SavedState, _pad, _require_cuda, _LDPAD, _dyk, _grad_views, _kmajor_gemm,
                      _pack_rnn_stack, _gru_param_grads)
-from .vocab import PaddedBatch, pad_batch, token_rows, length_order, smiles_token_table, smiles_chem_table, smiles_emit_table
+from .vocab import PaddedBatch, pad_batch, token_rows, length_order, smiles_token_table, smiles_chem_table, smiles_emit_table, SelfiesVocab, selfies_info_table
 
 
 class _RowsWorkspace(_Workspace):
@@ -57,7 +57,309 @@ class ReLU(nn.Module):
     """Marker (fused into the producing GEMM's epilogue)."""
 
 
-class VAE(_SavedState, nn.Module):
+class SmilesReaders:
+    """The methods that read token rows as SMILES molecules under ONE vocabulary: the syntax check, the graph walk and everything built on
+    it.  ``VAE`` inherits them for its own vocabulary; ``SmilesView`` inherits them for another one (the SMILES rows a SELFIES model's
+    samples decode to).  They ask of ``self`` exactly this: ``vocabulary``, ``bos`` / ``eos`` / ``pad``, ``device``, ``_rows(x, who, dev)``
+    (the row intake) and ``_vocab_table(key, build, dev)`` (build(vocabulary), cached per device) -- and nothing else of a model, which
+    is what lets the view stand in for one."""
+
+    def _smiles_table(self, dev):
+        return self._vocab_table("smi_tok", smiles_token_table, dev)
+
+    _SMI_START = 0xFF << 16                  # the automaton's initial state word 0: mode START, depth 0, no previous token
+
+    @torch.no_grad()
+    def syntax_valid(self, x, bad_pos=False):
+        """Which token rows are well-formed SMILES strings ending in <eos> (the automaton of sample(syntax=True), run over finished rows by
+        mvae_smiles_syntax_check; syntax only, no chemistry).  x: padded ids [B, T] (bos first) on the device, or a list of id tensors
+        (bos first) or strings.  Returns a bool [B] device tensor; bad_pos=True also returns int32 [B]: the index of the first refused
+        token, T for a row without <eos>, -1 for a valid row."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.syntax_valid")
+        x = self._rows(x, "syntax_valid", dev)
+        B = x.shape[0]
+        valid = torch.empty(B, dtype=torch.uint8, device=dev)
+        bad = torch.empty(B, dtype=torch.int32, device=dev) if bad_pos else None
+        ops.smiles_syntax_check(x, self._smiles_table(dev), self.eos, valid, bad)
+        return (valid.bool(), bad) if bad_pos else valid.bool()
+
+    def _smiles_chem_table(self, dev):
+        return self._vocab_table("smi_chem", smiles_chem_table, dev)
+
+    def _graph_rows(self, x, who):
+        """syntax_valid's input handling, then one mvae_smiles_graph_rows launch: (status, bad_pos, desc, formula), int32, on the device."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE." + who)
+        if len(self.vocabulary) > 64:
+            raise ValueError(f"{who}: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
+        return ops.smiles_graph_rows(self._rows(x, who, dev), self._smiles_table(dev), self._smiles_chem_table(dev), self.eos)
+
+    @torch.no_grad()
+    def chem_valid(self, x, return_status=False, kekule=False):
+        """Which token rows are well-formed AND valence-consistent SMILES strings (the graph walk of include/mvae.h, "SMILES graph", one
+        mvae_smiles_graph_rows launch, no host wait): every atom within the largest valence its element and charge allow, no ring bond
+        doubling an existing bond, every aromatic atom in a ring.  A necessary condition for chemical validity, not a sufficient one:
+        nothing is kekulised.  x: what ``syntax_valid`` takes.  Returns a bool [B] device tensor; return_status=True also returns the
+        int32 [B] status (ops.SMILES_STATUS_NAMES) and the int32 [B] bad_pos (the column of the first error, -1 for a row that is ok).
+        ``kekule=True``: the answer is "status 0 under ``kekule``" instead -- valence-consistent and kekulisable, one
+        mvae_smiles_kekule_rows launch; return_status=True then returns the status of ops.KEKULE_STATUS_NAMES alone, the kekule entry
+        having no bad_pos.  Still a necessary condition only, and not rdkit's verdict."""
+        if kekule:
+            status = self.kekule(x, mate=False)["status"]
+            return (status == 0, status) if return_status else status == 0
+        status, bad, _, _ = self._graph_rows(x, "chem_valid")
+        return (status == 0, status, bad) if return_status else status == 0
+
+    @torch.no_grad()
+    def kekule(self, x, mate=True):
+        """The kekulisation test of token rows x (what ``syntax_valid`` takes), on the device, one mvae_smiles_kekule_rows launch, no
+        host wait: {"status": int32 [B] (ops.KEKULE_STATUS_NAMES: ``chem_valid``'s status, or 7 where a valence-consistent row's aromatic
+        atoms cannot all take their one ring double bond), "n_atoms", "n_bonds", "pairs", "deficiency": int32 [B] (the aromatic atoms
+        that need a double bond, the aromatic ring bonds among them, the size of a maximum matching, the atoms it leaves over; zeros
+        unless the status is 0 or 7), "mate": uint8 [B, 128] (the partner of atom a, in string order, in the matching found; 255: none),
+        None with ``mate=False``}.  Status 0 is "kekulisable": tighter than valence-consistent, still necessary and not sufficient, with
+        no aromaticity perception -- NOT rdkit's Kekulize or SanitizeMol (include/mvae.h, "Kekulisation").  ValueError for a vocabulary
+        of more than 64 ids."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.kekule")
+        if len(self.vocabulary) > 64:
+            raise ValueError(f"kekule: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
+        return ops.kekule_dict(*ops.smiles_kekule_rows(self._rows(x, "kekule", dev), self._smiles_table(dev), self._smiles_chem_table(dev),
+                                                       self.eos, mate=None if mate else False))
+
+    def _smiles_emit_table(self, dev):
+        return self._vocab_table("smi_emit", smiles_emit_table, dev)
+
+    @torch.no_grad()
+    def respell(self, x, seed=0, draw=None, max_content=127):
+        """A randomised respelling of token rows x (what ``syntax_valid`` takes) on the device, one mvae_smiles_rewrite_rows launch, no
+        host wait: (rows int64 [B, max(T, max_content + 2)] -- <bos>, the new tokens, <eos>, <pad> --, status int32 [B],
+        ops.REWRITE_STATUS_NAMES).  Row b is read into the walk's graph and written back from a random root in a random neighbour order,
+        a pure function of (the row, seed, draw[b]); draw: integers [B] taken mod 2^32, None for the row numbers.  A row that cannot be
+        respelled (status != 0: not well-formed or not valence-consistent, stereo tokens, a multiple bond that would close a ring, no
+        free ring digit, more than 15 open branches, more than max_content tokens, a token the vocabulary lacks) comes back unchanged.
+        The same graph under this library's walk; NOT a canonical SMILES and not rdkit's doRandom (include/mvae.h, "SMILES rewrite").
+        ValueError for a vocabulary of more than 64 ids."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.respell")
+        if len(self.vocabulary) > 64:
+            raise ValueError(f"respell: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
+        x = self._rows(x, "respell", dev)
+        if draw is not None:
+            draw = ops.draw_words(torch.as_tensor(draw).to(dev).reshape(-1))
+            if draw.numel() != x.shape[0]:
+                raise ValueError(f"respell: draw has {draw.numel()} entries, x has {x.shape[0]} rows")
+        rows, _, status = ops.smiles_rewrite_rows(x, self._smiles_table(dev), self._smiles_chem_table(dev), self._smiles_emit_table(dev),
+                                                  self.bos, self.eos, self.pad, seed, draw, max_content)
+        return rows, status
+
+    @torch.no_grad()
+    def canonical(self, x, max_content=127, info=False):
+        """The canonical spelling of token rows x (what ``syntax_valid`` takes) on the device, one mvae_smiles_canon_rows launch, no host
+        wait: (rows int64 [B, max(T, max_content + 2)] -- <bos>, the new tokens, <eos>, <pad> --, status int32 [B],
+        ops.REWRITE_STATUS_NAMES).  ``respell`` with the atoms ordered by a canonical rank instead of a hash: two spellings of one graph
+        give one row, so rows can be compared as molecules by comparing tokens (include/mvae.h, "SMILES canon": equal rows always mean
+        equal graphs; the converse is tested on every tie of the test corpus, not proved).  No aromaticity perception, no stereo, NOT
+        rdkit's canonical SMILES.  A row that cannot be written (status != 0, ``respell``'s reasons) comes back unchanged.
+        ``info=True`` also returns {"atoms", "first_classes", "rounds", "ties": int32 [B], "rank": uint8 [B, 128]}.  ValueError for a
+        vocabulary of more than 64 ids."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.canonical")
+        if len(self.vocabulary) > 64:
+            raise ValueError(f"canonical: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
+        x = self._rows(x, "canonical", dev)
+        want = None if info else False
+        rows, _, status, inf, rank = ops.smiles_canon_rows(x, self._smiles_table(dev), self._smiles_chem_table(dev), self._smiles_emit_table(dev),
+                                                           self.bos, self.eos, self.pad, max_content, info=want, rank=want)
+        if not info:
+            return rows, status
+        extra = {name: inf[:, i] for i, name in enumerate(ops.CANON_INFO)}
+        extra["rank"] = rank
+        return rows, status, extra
+
+    @torch.no_grad()
+    def normal_form(self, x, max_content=127, info=False):
+        """The aromatic normal form of token rows x (what ``syntax_valid`` takes) on the device, one mvae_smiles_aromatize_rows launch,
+        no host wait: (rows int64 [B, max(T, max_content + 2)] -- <bos>, the new tokens, <eos>, <pad> --, status int32 [B],
+        ops.AROMATIZE_STATUS_NAMES).  ``canonical`` behind an aromaticity perception: the row's graph is read, the atoms on a cycle of
+        5 - 7 candidate atoms with 4 k + 2 electrons get the aromatic flag, the bonds between them become aromatic bonds, and that graph
+        is written in the canonical spelling, so that a Kekule spelling, an aromatic spelling and every respelling of one molecule are one
+        row (include/mvae.h, "Aromatic normal form": this library's own rule, NOT rdkit's aromaticity model or canonical SMILES; no
+        envelope cycles, no stereo).  A row that cannot be written (status != 0: ``canonical``'s reasons, 7: it does not kekulise, 17: a
+        lower-case atom that the rule does not find aromatic) comes back unchanged.  ``info=True`` also returns {"atoms", "aromatic",
+        "raised", "lowered_bonds": int32 [B], "arom": uint8 [B, 128]}.  ValueError for a vocabulary of more than 64 ids."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.normal_form")
+        if len(self.vocabulary) > 64:
+            raise ValueError(f"normal_form: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
+        x = self._rows(x, "normal_form", dev)
+        want = None if info else False
+        rows, _, status, inf, arom = ops.smiles_aromatize_rows(x, self._smiles_table(dev), self._smiles_chem_table(dev),
+                                                               self._smiles_emit_table(dev), self.bos, self.eos, self.pad, max_content,
+                                                               info=want, arom=want)
+        if not info:
+            return rows, status
+        extra = {name: inf[:, i] for i, name in enumerate(ops.AROMATIZE_INFO)}
+        extra["arom"] = arom
+        return rows, status, extra
+
+    @torch.no_grad()
+    def scaffold_smiles(self, x, max_content=127):
+        """The Murcko scaffold of token rows x (what ``syntax_valid`` takes) as token rows on the device, one
+        mvae_smiles_scaffold_smiles_rows launch, no host wait: (out int64 [B, max(T, max_content + 2)] -- <bos>, the scaffold's tokens,
+        <eos>, <pad> --, out_len int32 [B], status int32 [B], ops.SCAFFOLD_SMILES_STATUS_NAMES).  The scaffold atoms of ``scaffolds``
+        with every lost bond turned into hydrogens, in the spelling of ``canonical`` (include/mvae.h, "Scaffold SMILES"): rows that can
+        be shown, handed to ``data.compile_substructures`` once decoded, and compared exactly.  A row without a scaffold (status != 0:
+        ``canonical``'s reasons, or 14: no ring) is the EMPTY row <bos> <eos> with out_len 2, never a copy.  NOT rdkit's
+        MurckoScaffoldSmiles: nothing is sanitised, no aromaticity perception, no stereo.  ValueError for a vocabulary of more than 64 ids."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.scaffold_smiles")
+        if len(self.vocabulary) > 64:
+            raise ValueError(f"scaffold_smiles: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
+        x = self._rows(x, "scaffold_smiles", dev)
+        out, out_len, status, _ = ops.smiles_scaffold_smiles_rows(x, self._smiles_table(dev), self._smiles_chem_table(dev),
+                                                                  self._smiles_emit_table(dev), self.bos, self.eos, self.pad, max_content,
+                                                                  info=False)
+        return out, out_len, status
+
+    def _substructure_words(self, x, table, max_steps=65536, map_query=None):
+        """(status, hit, undecided[, map]) of one mvae_smiles_substruct_rows launch over token rows x on the device; table: a
+        ``data.SubstructureTable``."""
+        dev = self.device
+        status, hit, undecided, emb, _ = ops.smiles_substruct_rows(x, self._smiles_table(dev), self._smiles_chem_table(dev), self.eos, table.on(dev),
+                                                                   max_steps, map_query, steps=False)
+        return (status, hit, undecided) if map_query is None else (status, hit, undecided, emb)
+
+    @torch.no_grad()
+    def has_substructure(self, x, patterns, max_steps=65536, return_map=None):
+        """Which of the patterns (``data.compile_substructures``: 1 to 64 SMILES fragments, or a ``SubstructureTable`` to compile them
+        once) the token rows x (what ``syntax_valid`` takes) contain, on the device, one mvae_smiles_substruct_rows launch, no host
+        wait: (hit bool [B, Q], undecided bool [B, Q]).  hit[b, q]: the graph of row b contains pattern q -- an injective map of the
+        pattern's atoms that keeps element, aromatic flag and charge of every atom and the class of every bond (include/mvae.h, "SMILES
+        substructure"): graph containment, NOT SMARTS and not rdkit's HasSubstructMatch.  undecided[b, q]: the backtracking search
+        examined ``max_steps`` candidates (1 to 2^20) without an answer; such a pair is neither hit nor miss.  A row the SMILES walk
+        refuses contains nothing.  ``return_map=q`` also returns uint8 [B, 32]: the first (lexicographically smallest) embedding of
+        pattern q, atom numbers of the row in the pattern's atom order, 0xFF beyond its atoms and where there is no hit.  ValueError
+        for a refused pattern, a vocabulary of more than 64 ids, max_steps or return_map out of range."""
+        from .data import compile_substructures
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.has_substructure")
+        table = compile_substructures(patterns, self.vocabulary)
+        x = self._rows(x, "has_substructure", dev)
+        out = self._substructure_words(x, table, max_steps, return_map)
+        hit, undecided = ops.substruct_bits(out[1], len(table)), ops.substruct_bits(out[2], len(table))
+        return (hit, undecided) if return_map is None else (hit, undecided, out[3])
+
+    @torch.no_grad()
+    def descriptors(self, x):
+        """The graph walk's figures for token rows x (what ``syntax_valid`` takes), a dict of device tensors -- one graph-walk launch, one matrix-vector product for the weight, no host wait:
+        "status" and "bad_pos" as ``chem_valid`` returns them; "heavy_atoms", "bonds", "rings", "ring_atoms", "aromatic_atoms",
+        "hydrogens", "charge", "hetero_atoms" (int32 [B]); "formula" (int32 [B, 11]: atoms per element of vocab.SMI_ELEMENTS, hydrogens
+        first; ``data.formula_strings`` spells it); "weight" (float32 [B]: formula . vocab.ATOMIC_WEIGHTS).  Rows whose status is not 0
+        have zeros everywhere."""
+        return ops.graph_descriptors(*self._graph_rows(x, "descriptors"))
+
+    @torch.no_grad()
+    def fingerprints(self, x):
+        """The circular fingerprint of token rows x (what ``syntax_valid`` takes): {"status": int32 [B], "fp": int64 [B, 16]} on the
+        device, one mvae_smiles_fp_rows launch, no host wait.  1024 bits per row, radius 2, built like ECFP4 on the graph of the SMILES
+        graph walk but NOT rdkit's Morgan fingerprint (include/mvae.h, "Circular fingerprint": nothing is kekulised, the bits are
+        comparable within this library only); "status" is ``chem_valid``'s, and a row whose status is not 0 has an all-zero
+        fingerprint.  ValueError for a vocabulary of more than 64 ids."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.fingerprints")
+        if len(self.vocabulary) > 64:
+            raise ValueError(f"fingerprints: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
+        status, fp = ops.smiles_fp_rows(self._rows(x, "fingerprints", dev), self._smiles_table(dev), self._smiles_chem_table(dev), self.eos)
+        return {"status": status, "fp": fp}
+
+    @torch.no_grad()
+    def tanimoto(self, x, y):
+        """The Tanimoto similarity of the fingerprints of two batches, pair by pair: float32 [B] on the device, |a & b| / |a | b| as one
+        f32 division, 0 where the union is empty (so 0 wherever a row is not ok).  x, y: what ``fingerprints`` takes, equally many
+        rows (ValueError otherwise).  Two fingerprint launches and a few torch ops; the search over a corpus is
+        ``MosesDeviceDataset.nearest_fingerprints``."""
+        a, b = self.fingerprints(x)["fp"], self.fingerprints(y)["fp"]
+        if a.shape[0] != b.shape[0]:
+            raise ValueError(f"tanimoto: {a.shape[0]} rows against {b.shape[0]}")
+        count = lambda t: ((t.view(torch.uint8)[:, :, None] >> torch.arange(8, device=t.device, dtype=torch.uint8)) & 1).sum((1, 2))
+        c = count(a & b)
+        u = count(a) + count(b) - c
+        return torch.where(u > 0, c.float() / u.clamp(min=1).float(), torch.zeros((), device=a.device))
+
+    @torch.no_grad()
+    def scaffolds(self, x):
+        """The Murcko scaffold and the graph keys of token rows x (what ``fingerprints`` takes), on the device, one
+        mvae_smiles_scaffold_rows launch, no host wait: {"status": int32 [B], "mask": int64 [B, 2] (bit a of word a >> 6: atom a, in
+        string order, is in the scaffold), "atoms", "bonds", "linker_atoms", "exo_atoms": int32 [B] (of the scaffold), "mol_key",
+        "scaffold_key": int64 [B]}.  The scaffold is the ring atoms, the linkers between rings and the atoms double-bonded to either, on
+        the graph of the SMILES graph walk -- NOT rdkit's MurckoScaffold; the keys are equal for equal graphs however the string spells
+        them, ignore stereochemistry, and are no canonical SMILES (include/mvae.h, "Murcko scaffold", "Graph key").  A key of 0 means
+        none: the row's status is not 0, or (scaffold key) it has no ring.  ValueError for a vocabulary of more than 64 ids."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.scaffolds")
+        if len(self.vocabulary) > 64:
+            raise ValueError(f"scaffolds: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
+        return ops.scaffold_dict(*ops.smiles_scaffold_rows(self._rows(x, "scaffolds", dev), self._smiles_table(dev),
+                                                           self._smiles_chem_table(dev), self.eos))
+
+    @torch.no_grad()
+    def fragments(self, x):
+        """The fragments of token rows x (what ``fingerprints`` takes) and their graph keys, on the device, one
+        mvae_smiles_fragment_rows launch, no host wait: {"status": int32 [B], "mask": int64 [B, 16, 2] (bit a of word a >> 6 of slot f:
+        atom a, in string order, is in fragment f), "fragments", "cuts", "acyl_cuts", "largest": int32 [B], "keys": int64 [B, 16] (0 in
+        unused slots)}.  A row is cut at the bonds between a ring and its substituents and at acyl-heteroatom bonds (amide, ester, ...),
+        never at a terminal atom; the fragments are numbered by their lowest atom and keyed as ``scaffolds`` keys a scaffold
+        (include/mvae.h, "Fragments").  This library's own rule: NOT BRICS, not RECAP, no agreement with a toolkit is claimed.  A row
+        whose status is not 0 has zeros; one with more than 16 fragments has status ops.SMILES_STATUS_FRAG_MANY (15), zero mask and
+        keys, and its true counts.  ValueError for a vocabulary of more than 64 ids."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.fragments")
+        if len(self.vocabulary) > 64:
+            raise ValueError(f"fragments: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
+        return ops.fragment_dict(*ops.smiles_fragment_rows(self._rows(x, "fragments", dev), self._smiles_table(dev),
+                                                           self._smiles_chem_table(dev), self.eos))
+
+    @torch.no_grad()
+    def fragment_smiles(self, x, frag=0, max_content=127):
+        """Fragment number ``frag`` of token rows x (what ``syntax_valid`` takes) as token rows on the device, one
+        mvae_smiles_fragment_smiles_rows launch, no host wait: (out int64 [B, max(T, max_content + 2)], out_len int32 [B], status int32
+        [B], ops.FRAGMENT_SMILES_STATUS_NAMES).  The atoms of fragment ``frag`` of ``fragments`` with every lost bond turned into
+        hydrogens, in the spelling of ``canonical`` (include/mvae.h, "Fragments"): rows that can be shown and handed to
+        ``data.compile_substructures`` once decoded.  A row without that fragment (status != 0: ``canonical``'s reasons, or 16: fewer
+        fragments) is the EMPTY row <bos> <eos> with out_len 2, never a copy.  NOT BRICS, not RECAP.  ValueError for a vocabulary of
+        more than 64 ids or frag < 0."""
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.fragment_smiles")
+        if len(self.vocabulary) > 64:
+            raise ValueError(f"fragment_smiles: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
+        x = self._rows(x, "fragment_smiles", dev)
+        out, out_len, status, _ = ops.smiles_fragment_smiles_rows(x, self._smiles_table(dev), self._smiles_chem_table(dev),
+                                                                  self._smiles_emit_table(dev), self.bos, self.eos, self.pad, frag, max_content,
+                                                                  info=False)
+        return out, out_len, status
+
+    def edit_distance(self, x, y):
+        """The token-level Levenshtein distance (unit costs for insert, delete and substitute, no transposition) between the rows of two
+        batches, pair by pair: int32 [B] on the device, one launch (mvae_edit_distance_rows), no host wait.  x, y: padded ids [B, T] (bos
+        first), or a list of id tensors (bos first) or of strings, under the model's vocabulary.  A row's content is what stands between
+        <bos> and its first <eos> (or its last column); ids outside the vocabulary equal nothing.  ValueError, before any device work:
+        batches of different sizes, a vocabulary of more than 64 ids, both sides wider than 129 columns."""
+        x, y = self._rows(x, "edit_distance"), self._rows(y, "edit_distance")          # on the host: the checks come before any device work
+        if x.shape[0] != y.shape[0]:
+            raise ValueError(f"edit_distance: {x.shape[0]} rows against {y.shape[0]}")
+        V = len(self.vocabulary)
+        if V > ops.EDIT_V_MAX:
+            raise ValueError(f"edit_distance: the vocabulary has {V} ids, at most {ops.EDIT_V_MAX} are supported")
+        if min(x.shape[1], y.shape[1]) - 1 > ops.EDIT_PATTERN_MAX:
+            raise ValueError(f"edit_distance: one side must have at most {ops.EDIT_PATTERN_MAX + 1} columns, got {x.shape[1]} and {y.shape[1]}")
+        dev = self.device
+        _require_cuda(dev, "mosesvae.VAE.edit_distance")
+        return ops.edit_distance_rows(x.to(dev), y.to(dev), self.eos, V)
+
+
+class VAE(_SavedState, SmilesReaders, nn.Module):
     def __init__(self, vocab, dtype=torch.bfloat16):
         super().__init__()
         q_d_h, q_n_layers, d_n_layers, d_dropout, d_z, d_d_h = 256, 1, 3, 0.2, 160, 512     # mosesvae.py:31-40
@@ -370,6 +672,9 @@ class VAE(_SavedState, nn.Module):
         otherwise, before any device work (a CPU model reports it too)."""
         if int(max_len) < 3:
             raise ValueError(f"sample / decode: syntax=True needs max_len >= 3 (<bos>, an atom, <eos>), got {max_len}")
+        if isinstance(self.vocabulary, SelfiesVocab):
+            raise ValueError("sample / decode: syntax=True constrains SMILES tokens and this model's vocabulary is a SelfiesVocab: every "
+                             "SELFIES row is a molecule already; sample without syntax= and turn the rows into SMILES with VAE.to_smiles")
         self._smiles_table(None)
 
     def _prefix_table(self, prefix, n, max_len, what):
@@ -390,7 +695,10 @@ class VAE(_SavedState, nn.Module):
         lens = torch.zeros(len(entries), dtype=torch.int32)
         for b, e in enumerate(entries):
             if isinstance(e, str):
-                bad = [ch for ch in e if ch not in self.vocabulary.c2i]
+                if isinstance(self.vocabulary, SelfiesVocab):
+                    bad = [sym for sym in self.vocabulary.split(e) if sym not in self.vocabulary.sym2char]
+                else:
+                    bad = [ch for ch in e if ch not in self.vocabulary.c2i]
                 if bad:
                     raise ValueError(f"{what}: prefix of row {b}: character {bad[0]!r} is not in the vocabulary")
                 ids = self.vocabulary.string2ids(e)
@@ -451,299 +759,39 @@ class VAE(_SavedState, nn.Module):
             P[key] = host.to(dev)
         return P[key]
 
-    def _smiles_table(self, dev):
-        return self._vocab_table("smi_tok", smiles_token_table, dev)
-
-    _SMI_START = 0xFF << 16                  # the automaton's initial state word 0: mode START, depth 0, no previous token
-
     @torch.no_grad()
-    def syntax_valid(self, x, bad_pos=False):
-        """Which token rows are well-formed SMILES strings ending in <eos> (the automaton of sample(syntax=True), run over finished rows by
-        mvae_smiles_syntax_check; syntax only, no chemistry).  x: padded ids [B, T] (bos first) on the device, or a list of id tensors
-        (bos first) or strings.  Returns a bool [B] device tensor; bad_pos=True also returns int32 [B]: the index of the first refused
-        token, T for a row without <eos>, -1 for a valid row."""
+    def to_smiles(self, x, smiles_vocab, normal=False, max_content=127, info=False):
+        """SELFIES token rows x of a model built on a ``vocab.SelfiesVocab`` (padded ids [B, T], bos first, or a list of id tensors or
+        SELFIES texts) as SMILES token rows in `smiles_vocab`, on the device, one mvae_selfies_decode_rows launch, no host wait: (rows
+        int64 [B, max(T, max_content + 2)] -- <bos>, the tokens, <eos>, <pad> --, status int32 [B], ops.SELFIES_STATUS_NAMES).  Every row
+        is derived into a graph by this library's own SELFIES rules (include/mvae.h, "SELFIES"; NOT the selfies package's decoder:
+        agreement with it is neither tested nor claimed) and written in the canonical Kekule spelling of ``canonical``; a row that cannot
+        be written (status 1: a token that is no symbol, or no atom; 9 - 13: the writer's reasons) gives the EMPTY row.  ``normal=True``
+        runs mvae_smiles_aromatize_rows behind it: the rows are the aromatic normal form (``normal_form``), and the status of a decoded
+        row that launch refuses is the launch's.  ``info=True`` also returns {"atoms", "ring_bonds", "reparented", "bad_column": int32
+        [B]}.  ValueError for a model whose vocabulary is no SelfiesVocab and for a vocabulary of more than 64 ids."""
+        if not isinstance(self.vocabulary, SelfiesVocab):
+            raise ValueError("to_smiles: the model's vocabulary is no SelfiesVocab; its rows are SMILES rows already")
+        if len(self.vocabulary) > 64 or len(smiles_vocab) > 64:
+            raise ValueError(f"to_smiles: the vocabularies have {len(self.vocabulary)} and {len(smiles_vocab)} ids, at most 64 are supported")
         dev = self.device
-        _require_cuda(dev, "mosesvae.VAE.syntax_valid")
-        x = self._rows(x, "syntax_valid", dev)
-        B = x.shape[0]
-        valid = torch.empty(B, dtype=torch.uint8, device=dev)
-        bad = torch.empty(B, dtype=torch.int32, device=dev) if bad_pos else None
-        ops.smiles_syntax_check(x, self._smiles_table(dev), self.eos, valid, bad)
-        return (valid.bool(), bad) if bad_pos else valid.bool()
-
-    def _smiles_chem_table(self, dev):
-        return self._vocab_table("smi_chem", smiles_chem_table, dev)
-
-    def _graph_rows(self, x, who):
-        """syntax_valid's input handling, then one mvae_smiles_graph_rows launch: (status, bad_pos, desc, formula), int32, on the device."""
-        dev = self.device
-        _require_cuda(dev, "mosesvae.VAE." + who)
-        if len(self.vocabulary) > 64:
-            raise ValueError(f"{who}: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
-        return ops.smiles_graph_rows(self._rows(x, who, dev), self._smiles_table(dev), self._smiles_chem_table(dev), self.eos)
-
-    @torch.no_grad()
-    def chem_valid(self, x, return_status=False, kekule=False):
-        """Which token rows are well-formed AND valence-consistent SMILES strings (the graph walk of include/mvae.h, "SMILES graph", one
-        mvae_smiles_graph_rows launch, no host wait): every atom within the largest valence its element and charge allow, no ring bond
-        doubling an existing bond, every aromatic atom in a ring.  A necessary condition for chemical validity, not a sufficient one:
-        nothing is kekulised.  x: what ``syntax_valid`` takes.  Returns a bool [B] device tensor; return_status=True also returns the
-        int32 [B] status (ops.SMILES_STATUS_NAMES) and the int32 [B] bad_pos (the column of the first error, -1 for a row that is ok).
-        ``kekule=True``: the answer is "status 0 under ``kekule``" instead -- valence-consistent and kekulisable, one
-        mvae_smiles_kekule_rows launch; return_status=True then returns the status of ops.KEKULE_STATUS_NAMES alone, the kekule entry
-        having no bad_pos.  Still a necessary condition only, and not rdkit's verdict."""
-        if kekule:
-            status = self.kekule(x, mate=False)["status"]
-            return (status == 0, status) if return_status else status == 0
-        status, bad, _, _ = self._graph_rows(x, "chem_valid")
-        return (status == 0, status, bad) if return_status else status == 0
-
-    @torch.no_grad()
-    def kekule(self, x, mate=True):
-        """The kekulisation test of token rows x (what ``syntax_valid`` takes), on the device, one mvae_smiles_kekule_rows launch, no
-        host wait: {"status": int32 [B] (ops.KEKULE_STATUS_NAMES: ``chem_valid``'s status, or 7 where a valence-consistent row's aromatic
-        atoms cannot all take their one ring double bond), "n_atoms", "n_bonds", "pairs", "deficiency": int32 [B] (the aromatic atoms
-        that need a double bond, the aromatic ring bonds among them, the size of a maximum matching, the atoms it leaves over; zeros
-        unless the status is 0 or 7), "mate": uint8 [B, 128] (the partner of atom a, in string order, in the matching found; 255: none),
-        None with ``mate=False``}.  Status 0 is "kekulisable": tighter than valence-consistent, still necessary and not sufficient, with
-        no aromaticity perception -- NOT rdkit's Kekulize or SanitizeMol (include/mvae.h, "Kekulisation").  ValueError for a vocabulary
-        of more than 64 ids."""
-        dev = self.device
-        _require_cuda(dev, "mosesvae.VAE.kekule")
-        if len(self.vocabulary) > 64:
-            raise ValueError(f"kekule: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
-        return ops.kekule_dict(*ops.smiles_kekule_rows(self._rows(x, "kekule", dev), self._smiles_table(dev), self._smiles_chem_table(dev),
-                                                       self.eos, mate=None if mate else False))
-
-    def _smiles_emit_table(self, dev):
-        return self._vocab_table("smi_emit", smiles_emit_table, dev)
-
-    @torch.no_grad()
-    def respell(self, x, seed=0, draw=None, max_content=127):
-        """A randomised respelling of token rows x (what ``syntax_valid`` takes) on the device, one mvae_smiles_rewrite_rows launch, no
-        host wait: (rows int64 [B, max(T, max_content + 2)] -- <bos>, the new tokens, <eos>, <pad> --, status int32 [B],
-        ops.REWRITE_STATUS_NAMES).  Row b is read into the walk's graph and written back from a random root in a random neighbour order,
-        a pure function of (the row, seed, draw[b]); draw: integers [B] taken mod 2^32, None for the row numbers.  A row that cannot be
-        respelled (status != 0: not well-formed or not valence-consistent, stereo tokens, a multiple bond that would close a ring, no
-        free ring digit, more than 15 open branches, more than max_content tokens, a token the vocabulary lacks) comes back unchanged.
-        The same graph under this library's walk; NOT a canonical SMILES and not rdkit's doRandom (include/mvae.h, "SMILES rewrite").
-        ValueError for a vocabulary of more than 64 ids."""
-        dev = self.device
-        _require_cuda(dev, "mosesvae.VAE.respell")
-        if len(self.vocabulary) > 64:
-            raise ValueError(f"respell: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
-        x = self._rows(x, "respell", dev)
-        if draw is not None:
-            draw = ops.draw_words(torch.as_tensor(draw).to(dev).reshape(-1))
-            if draw.numel() != x.shape[0]:
-                raise ValueError(f"respell: draw has {draw.numel()} entries, x has {x.shape[0]} rows")
-        rows, _, status = ops.smiles_rewrite_rows(x, self._smiles_table(dev), self._smiles_chem_table(dev), self._smiles_emit_table(dev),
-                                                  self.bos, self.eos, self.pad, seed, draw, max_content)
-        return rows, status
-
-    @torch.no_grad()
-    def canonical(self, x, max_content=127, info=False):
-        """The canonical spelling of token rows x (what ``syntax_valid`` takes) on the device, one mvae_smiles_canon_rows launch, no host
-        wait: (rows int64 [B, max(T, max_content + 2)] -- <bos>, the new tokens, <eos>, <pad> --, status int32 [B],
-        ops.REWRITE_STATUS_NAMES).  ``respell`` with the atoms ordered by a canonical rank instead of a hash: two spellings of one graph
-        give one row, so rows can be compared as molecules by comparing tokens (include/mvae.h, "SMILES canon": equal rows always mean
-        equal graphs; the converse is tested on every tie of the test corpus, not proved).  No aromaticity perception, no stereo, NOT
-        rdkit's canonical SMILES.  A row that cannot be written (status != 0, ``respell``'s reasons) comes back unchanged.
-        ``info=True`` also returns {"atoms", "first_classes", "rounds", "ties": int32 [B], "rank": uint8 [B, 128]}.  ValueError for a
-        vocabulary of more than 64 ids."""
-        dev = self.device
-        _require_cuda(dev, "mosesvae.VAE.canonical")
-        if len(self.vocabulary) > 64:
-            raise ValueError(f"canonical: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
-        x = self._rows(x, "canonical", dev)
-        want = None if info else False
-        rows, _, status, inf, rank = ops.smiles_canon_rows(x, self._smiles_table(dev), self._smiles_chem_table(dev), self._smiles_emit_table(dev),
-                                                           self.bos, self.eos, self.pad, max_content, info=want, rank=want)
+        _require_cuda(dev, "mosesvae.VAE.to_smiles")
+        x = self._rows(x, "to_smiles", dev)
+        P = self._pack(dev)
+        key = ("to_smiles", id(smiles_vocab))
+        if key not in P:
+            P[key] = (smiles_vocab, smiles_token_table(smiles_vocab).to(dev), smiles_chem_table(smiles_vocab).to(dev),
+                      smiles_emit_table(smiles_vocab).to(dev))
+        _, tok, chem, emit = P[key]
+        v = smiles_vocab
+        rows, _, status, inf = ops.selfies_decode_rows(x, self._vocab_table("selfies_info", selfies_info_table, dev), emit, v.bos, v.eos, v.pad,
+                                                       max_content, info=None if info else False)
+        if normal:
+            rows, _, st2, _, _ = ops.smiles_aromatize_rows(rows, tok, chem, emit, v.bos, v.eos, v.pad, max_content, info=False, arom=False)
+            status = torch.where(status == 0, st2, status)
         if not info:
             return rows, status
-        extra = {name: inf[:, i] for i, name in enumerate(ops.CANON_INFO)}
-        extra["rank"] = rank
-        return rows, status, extra
-
-    @torch.no_grad()
-    def normal_form(self, x, max_content=127, info=False):
-        """The aromatic normal form of token rows x (what ``syntax_valid`` takes) on the device, one mvae_smiles_aromatize_rows launch,
-        no host wait: (rows int64 [B, max(T, max_content + 2)] -- <bos>, the new tokens, <eos>, <pad> --, status int32 [B],
-        ops.AROMATIZE_STATUS_NAMES).  ``canonical`` behind an aromaticity perception: the row's graph is read, the atoms on a cycle of
-        5 - 7 candidate atoms with 4 k + 2 electrons get the aromatic flag, the bonds between them become aromatic bonds, and that graph
-        is written in the canonical spelling, so that a Kekule spelling, an aromatic spelling and every respelling of one molecule are one
-        row (include/mvae.h, "Aromatic normal form": this library's own rule, NOT rdkit's aromaticity model or canonical SMILES; no
-        envelope cycles, no stereo).  A row that cannot be written (status != 0: ``canonical``'s reasons, 7: it does not kekulise, 17: a
-        lower-case atom that the rule does not find aromatic) comes back unchanged.  ``info=True`` also returns {"atoms", "aromatic",
-        "raised", "lowered_bonds": int32 [B], "arom": uint8 [B, 128]}.  ValueError for a vocabulary of more than 64 ids."""
-        dev = self.device
-        _require_cuda(dev, "mosesvae.VAE.normal_form")
-        if len(self.vocabulary) > 64:
-            raise ValueError(f"normal_form: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
-        x = self._rows(x, "normal_form", dev)
-        want = None if info else False
-        rows, _, status, inf, arom = ops.smiles_aromatize_rows(x, self._smiles_table(dev), self._smiles_chem_table(dev),
-                                                               self._smiles_emit_table(dev), self.bos, self.eos, self.pad, max_content,
-                                                               info=want, arom=want)
-        if not info:
-            return rows, status
-        extra = {name: inf[:, i] for i, name in enumerate(ops.AROMATIZE_INFO)}
-        extra["arom"] = arom
-        return rows, status, extra
-
-    @torch.no_grad()
-    def scaffold_smiles(self, x, max_content=127):
-        """The Murcko scaffold of token rows x (what ``syntax_valid`` takes) as token rows on the device, one
-        mvae_smiles_scaffold_smiles_rows launch, no host wait: (out int64 [B, max(T, max_content + 2)] -- <bos>, the scaffold's tokens,
-        <eos>, <pad> --, out_len int32 [B], status int32 [B], ops.SCAFFOLD_SMILES_STATUS_NAMES).  The scaffold atoms of ``scaffolds``
-        with every lost bond turned into hydrogens, in the spelling of ``canonical`` (include/mvae.h, "Scaffold SMILES"): rows that can
-        be shown, handed to ``data.compile_substructures`` once decoded, and compared exactly.  A row without a scaffold (status != 0:
-        ``canonical``'s reasons, or 14: no ring) is the EMPTY row <bos> <eos> with out_len 2, never a copy.  NOT rdkit's
-        MurckoScaffoldSmiles: nothing is sanitised, no aromaticity perception, no stereo.  ValueError for a vocabulary of more than 64 ids."""
-        dev = self.device
-        _require_cuda(dev, "mosesvae.VAE.scaffold_smiles")
-        if len(self.vocabulary) > 64:
-            raise ValueError(f"scaffold_smiles: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
-        x = self._rows(x, "scaffold_smiles", dev)
-        out, out_len, status, _ = ops.smiles_scaffold_smiles_rows(x, self._smiles_table(dev), self._smiles_chem_table(dev),
-                                                                  self._smiles_emit_table(dev), self.bos, self.eos, self.pad, max_content,
-                                                                  info=False)
-        return out, out_len, status
-
-    def _substructure_words(self, x, table, max_steps=65536, map_query=None):
-        """(status, hit, undecided[, map]) of one mvae_smiles_substruct_rows launch over token rows x on the device; table: a
-        ``data.SubstructureTable``."""
-        dev = self.device
-        status, hit, undecided, emb, _ = ops.smiles_substruct_rows(x, self._smiles_table(dev), self._smiles_chem_table(dev), self.eos, table.on(dev),
-                                                                   max_steps, map_query, steps=False)
-        return (status, hit, undecided) if map_query is None else (status, hit, undecided, emb)
-
-    @torch.no_grad()
-    def has_substructure(self, x, patterns, max_steps=65536, return_map=None):
-        """Which of the patterns (``data.compile_substructures``: 1 to 64 SMILES fragments, or a ``SubstructureTable`` to compile them
-        once) the token rows x (what ``syntax_valid`` takes) contain, on the device, one mvae_smiles_substruct_rows launch, no host
-        wait: (hit bool [B, Q], undecided bool [B, Q]).  hit[b, q]: the graph of row b contains pattern q -- an injective map of the
-        pattern's atoms that keeps element, aromatic flag and charge of every atom and the class of every bond (include/mvae.h, "SMILES
-        substructure"): graph containment, NOT SMARTS and not rdkit's HasSubstructMatch.  undecided[b, q]: the backtracking search
-        examined ``max_steps`` candidates (1 to 2^20) without an answer; such a pair is neither hit nor miss.  A row the SMILES walk
-        refuses contains nothing.  ``return_map=q`` also returns uint8 [B, 32]: the first (lexicographically smallest) embedding of
-        pattern q, atom numbers of the row in the pattern's atom order, 0xFF beyond its atoms and where there is no hit.  ValueError
-        for a refused pattern, a vocabulary of more than 64 ids, max_steps or return_map out of range."""
-        from .data import compile_substructures
-        dev = self.device
-        _require_cuda(dev, "mosesvae.VAE.has_substructure")
-        table = compile_substructures(patterns, self.vocabulary)
-        x = self._rows(x, "has_substructure", dev)
-        out = self._substructure_words(x, table, max_steps, return_map)
-        hit, undecided = ops.substruct_bits(out[1], len(table)), ops.substruct_bits(out[2], len(table))
-        return (hit, undecided) if return_map is None else (hit, undecided, out[3])
-
-    @torch.no_grad()
-    def descriptors(self, x):
-        """The graph walk's figures for token rows x (what ``syntax_valid`` takes), a dict of device tensors -- one graph-walk launch, one matrix-vector product for the weight, no host wait:
-        "status" and "bad_pos" as ``chem_valid`` returns them; "heavy_atoms", "bonds", "rings", "ring_atoms", "aromatic_atoms",
-        "hydrogens", "charge", "hetero_atoms" (int32 [B]); "formula" (int32 [B, 11]: atoms per element of vocab.SMI_ELEMENTS, hydrogens
-        first; ``data.formula_strings`` spells it); "weight" (float32 [B]: formula . vocab.ATOMIC_WEIGHTS).  Rows whose status is not 0
-        have zeros everywhere."""
-        return ops.graph_descriptors(*self._graph_rows(x, "descriptors"))
-
-    @torch.no_grad()
-    def fingerprints(self, x):
-        """The circular fingerprint of token rows x (what ``syntax_valid`` takes): {"status": int32 [B], "fp": int64 [B, 16]} on the
-        device, one mvae_smiles_fp_rows launch, no host wait.  1024 bits per row, radius 2, built like ECFP4 on the graph of the SMILES
-        graph walk but NOT rdkit's Morgan fingerprint (include/mvae.h, "Circular fingerprint": nothing is kekulised, the bits are
-        comparable within this library only); "status" is ``chem_valid``'s, and a row whose status is not 0 has an all-zero
-        fingerprint.  ValueError for a vocabulary of more than 64 ids."""
-        dev = self.device
-        _require_cuda(dev, "mosesvae.VAE.fingerprints")
-        if len(self.vocabulary) > 64:
-            raise ValueError(f"fingerprints: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
-        status, fp = ops.smiles_fp_rows(self._rows(x, "fingerprints", dev), self._smiles_table(dev), self._smiles_chem_table(dev), self.eos)
-        return {"status": status, "fp": fp}
-
-    @torch.no_grad()
-    def tanimoto(self, x, y):
-        """The Tanimoto similarity of the fingerprints of two batches, pair by pair: float32 [B] on the device, |a & b| / |a | b| as one
-        f32 division, 0 where the union is empty (so 0 wherever a row is not ok).  x, y: what ``fingerprints`` takes, equally many
-        rows (ValueError otherwise).  Two fingerprint launches and a few torch ops; the search over a corpus is
-        ``MosesDeviceDataset.nearest_fingerprints``."""
-        a, b = self.fingerprints(x)["fp"], self.fingerprints(y)["fp"]
-        if a.shape[0] != b.shape[0]:
-            raise ValueError(f"tanimoto: {a.shape[0]} rows against {b.shape[0]}")
-        count = lambda t: ((t.view(torch.uint8)[:, :, None] >> torch.arange(8, device=t.device, dtype=torch.uint8)) & 1).sum((1, 2))
-        c = count(a & b)
-        u = count(a) + count(b) - c
-        return torch.where(u > 0, c.float() / u.clamp(min=1).float(), torch.zeros((), device=a.device))
-
-    @torch.no_grad()
-    def scaffolds(self, x):
-        """The Murcko scaffold and the graph keys of token rows x (what ``fingerprints`` takes), on the device, one
-        mvae_smiles_scaffold_rows launch, no host wait: {"status": int32 [B], "mask": int64 [B, 2] (bit a of word a >> 6: atom a, in
-        string order, is in the scaffold), "atoms", "bonds", "linker_atoms", "exo_atoms": int32 [B] (of the scaffold), "mol_key",
-        "scaffold_key": int64 [B]}.  The scaffold is the ring atoms, the linkers between rings and the atoms double-bonded to either, on
-        the graph of the SMILES graph walk -- NOT rdkit's MurckoScaffold; the keys are equal for equal graphs however the string spells
-        them, ignore stereochemistry, and are no canonical SMILES (include/mvae.h, "Murcko scaffold", "Graph key").  A key of 0 means
-        none: the row's status is not 0, or (scaffold key) it has no ring.  ValueError for a vocabulary of more than 64 ids."""
-        dev = self.device
-        _require_cuda(dev, "mosesvae.VAE.scaffolds")
-        if len(self.vocabulary) > 64:
-            raise ValueError(f"scaffolds: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
-        return ops.scaffold_dict(*ops.smiles_scaffold_rows(self._rows(x, "scaffolds", dev), self._smiles_table(dev),
-                                                           self._smiles_chem_table(dev), self.eos))
-
-    @torch.no_grad()
-    def fragments(self, x):
-        """The fragments of token rows x (what ``fingerprints`` takes) and their graph keys, on the device, one
-        mvae_smiles_fragment_rows launch, no host wait: {"status": int32 [B], "mask": int64 [B, 16, 2] (bit a of word a >> 6 of slot f:
-        atom a, in string order, is in fragment f), "fragments", "cuts", "acyl_cuts", "largest": int32 [B], "keys": int64 [B, 16] (0 in
-        unused slots)}.  A row is cut at the bonds between a ring and its substituents and at acyl-heteroatom bonds (amide, ester, ...),
-        never at a terminal atom; the fragments are numbered by their lowest atom and keyed as ``scaffolds`` keys a scaffold
-        (include/mvae.h, "Fragments").  This library's own rule: NOT BRICS, not RECAP, no agreement with a toolkit is claimed.  A row
-        whose status is not 0 has zeros; one with more than 16 fragments has status ops.SMILES_STATUS_FRAG_MANY (15), zero mask and
-        keys, and its true counts.  ValueError for a vocabulary of more than 64 ids."""
-        dev = self.device
-        _require_cuda(dev, "mosesvae.VAE.fragments")
-        if len(self.vocabulary) > 64:
-            raise ValueError(f"fragments: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
-        return ops.fragment_dict(*ops.smiles_fragment_rows(self._rows(x, "fragments", dev), self._smiles_table(dev),
-                                                           self._smiles_chem_table(dev), self.eos))
-
-    @torch.no_grad()
-    def fragment_smiles(self, x, frag=0, max_content=127):
-        """Fragment number ``frag`` of token rows x (what ``syntax_valid`` takes) as token rows on the device, one
-        mvae_smiles_fragment_smiles_rows launch, no host wait: (out int64 [B, max(T, max_content + 2)], out_len int32 [B], status int32
-        [B], ops.FRAGMENT_SMILES_STATUS_NAMES).  The atoms of fragment ``frag`` of ``fragments`` with every lost bond turned into
-        hydrogens, in the spelling of ``canonical`` (include/mvae.h, "Fragments"): rows that can be shown and handed to
-        ``data.compile_substructures`` once decoded.  A row without that fragment (status != 0: ``canonical``'s reasons, or 16: fewer
-        fragments) is the EMPTY row <bos> <eos> with out_len 2, never a copy.  NOT BRICS, not RECAP.  ValueError for a vocabulary of
-        more than 64 ids or frag < 0."""
-        dev = self.device
-        _require_cuda(dev, "mosesvae.VAE.fragment_smiles")
-        if len(self.vocabulary) > 64:
-            raise ValueError(f"fragment_smiles: the vocabulary has {len(self.vocabulary)} ids, at most 64 are supported")
-        x = self._rows(x, "fragment_smiles", dev)
-        out, out_len, status, _ = ops.smiles_fragment_smiles_rows(x, self._smiles_table(dev), self._smiles_chem_table(dev),
-                                                                  self._smiles_emit_table(dev), self.bos, self.eos, self.pad, frag, max_content,
-                                                                  info=False)
-        return out, out_len, status
-
-    def edit_distance(self, x, y):
-        """The token-level Levenshtein distance (unit costs for insert, delete and substitute, no transposition) between the rows of two
-        batches, pair by pair: int32 [B] on the device, one launch (mvae_edit_distance_rows), no host wait.  x, y: padded ids [B, T] (bos
-        first), or a list of id tensors (bos first) or of strings, under the model's vocabulary.  A row's content is what stands between
-        <bos> and its first <eos> (or its last column); ids outside the vocabulary equal nothing.  ValueError, before any device work:
-        batches of different sizes, a vocabulary of more than 64 ids, both sides wider than 129 columns."""
-        x, y = self._rows(x, "edit_distance"), self._rows(y, "edit_distance")          # on the host: the checks come before any device work
-        if x.shape[0] != y.shape[0]:
-            raise ValueError(f"edit_distance: {x.shape[0]} rows against {y.shape[0]}")
-        V = len(self.vocabulary)
-        if V > ops.EDIT_V_MAX:
-            raise ValueError(f"edit_distance: the vocabulary has {V} ids, at most {ops.EDIT_V_MAX} are supported")
-        if min(x.shape[1], y.shape[1]) - 1 > ops.EDIT_PATTERN_MAX:
-            raise ValueError(f"edit_distance: one side must have at most {ops.EDIT_PATTERN_MAX + 1} columns, got {x.shape[1]} and {y.shape[1]}")
-        dev = self.device
-        _require_cuda(dev, "mosesvae.VAE.edit_distance")
-        return ops.edit_distance_rows(x.to(dev), y.to(dev), self.eos, V)
+        return rows, status, {name: inf[:, i] for i, name in enumerate(ops.SELFIES_DECODE_INFO)}
 
     def _decode_setup(self, z, n_mol, pre, max_len, syntax, forced, who, check_prefix=True):
         """What _sample_tokens and _beam_search do in front of their token loops, for the rows of z (fp32 [rows, d_z] on the device: one
@@ -1043,6 +1091,31 @@ class VAE(_SavedState, nn.Module):
 # the encoder's backward), _MosesEncFn (`forward_encoder`: the encoder half alone) and _MosesDecFn (`forward_decoder(x, z)`: the decoder half
 # on a latent the caller supplies, with a gradient w.r.t. that latent).  The halves use disjoint buffer names and keep a generation count
 # each (`_SavedState._next_saved_ws(half)`), so `forward_encoder` followed by `forward_decoder` (the reference's composition) overwrites nothing.
+class SmilesView(SmilesReaders):
+    """``SmilesReaders`` under ANOTHER vocabulary than the model's: what ``moses_generate(selfies=)`` runs on the SMILES rows a SELFIES
+    model's samples decode to.  It supplies what the readers ask of ``self``: the vocabulary and its ids, the model's device, the
+    per-vocabulary tables (cached here) and the row intake."""
+
+    def __init__(self, model, vocab):
+        self.model, self.vocabulary = model, vocab
+        self.bos, self.eos, self.pad = vocab.bos, vocab.eos, vocab.pad
+        self._tables = {}
+
+    device = property(lambda self: self.model.device)
+
+    def _vocab_table(self, key, build, dev):
+        if (key, None) not in self._tables:
+            self._tables[key, None] = build(self.vocabulary)
+        if dev is None:
+            return self._tables[key, None]
+        if (key, dev) not in self._tables:
+            self._tables[key, dev] = self._tables[key, None].to(dev)
+        return self._tables[key, dev]
+
+    def _rows(self, x, who, dev=None):
+        return token_rows(x, lambda s: self.vocabulary.string2ids(s, add_bos=True, add_eos=True), self.pad, who, dev)
+
+
 def _opts(x_in, free_bits):
     """The collapse remedies of one forward as the autograd nodes carry them: None when both are off (the default path), else
     dict(x_in = the decoder's word-dropped input tokens | None, fb = None | dict(lam = free bits; the encoder half adds kl2, kl_dim))."""

@@ -1226,6 +1226,117 @@ def smiles_aromatize_corpus(tokens, offsets, N, rows, tok_info, chem_info, emit,
                           _AROMATIZE_OUT, (tokens_out, offsets_out, status, info, arom), counts, err, (), AROMATIZE_COUNTS)
 
 
+SELFIES_STATUS_CAPACITY = 18                  # include/mvae.h: MVAE_SELFIES_CAPACITY, given by the SELFIES encode entries only
+SELFIES_STATUS_NAMES = AROMATIZE_STATUS_NAMES + ("selfies_capacity",)                   # index = status; 14 - 17 are never given here
+SELFIES_DECODE_INFO = ("atoms", "ring_bonds", "reparented", "bad_column")      # the columns of info [*, 4] of the decode entries
+SELFIES_ENCODE_INFO = ("atoms", "branch_symbols", "ring_symbols", "capacity_atom")      # ... of the encode entries
+SELFIES_COUNTS = 32                                                  # MVAE_SELFIES_COUNTS
+SELFIES_EMIT = 529                                                   # MVAE_SELFIES_EMIT
+_SELFIES_OUT = ((torch.int32, (4,), True),)
+
+
+def _selfies_tables(dev, tables, counts, max_content):
+    for t, n in tables:
+        assert t.dtype == torch.int32 and t.dim() == 1 and (n is None or t.numel() == n) and t.is_contiguous() and t.device == dev, (t.dtype, t.shape)
+    if not 1 <= int(max_content) <= 127:
+        raise ValueError(f"selfies: max_content must be in [1, 127], got {max_content}")
+    assert counts is None or (counts.dtype == torch.int32 and counts.shape == (SELFIES_COUNTS,) and counts.is_contiguous() and counts.device == dev)
+
+
+def _selfies_rows(name, host, x, front, tables, ids, max_content, T_out, given, counts):
+    """What the mvae_selfies_*_rows and _host entries share.  front: the arguments between x_ld and the output ids; tables: (tensor,
+    length or None) of every table among them; ids: the output's (bos, eos, pad)."""
+    x, ldx = _token_rows(x, "x")
+    assert not host or x.device.type == "cpu", x.device
+    B, T = x.shape
+    _selfies_tables(x.device, tables, counts, max_content)
+    T_out = max(T, int(max_content) + 2) if T_out is None else int(T_out)
+    res = _outputs(B, x.device, ((torch.int64, (T_out,), False), (torch.int32, (), False), (torch.int32, (), False)) + _SELFIES_OUT, given)
+    check(getattr(L.load(), name)(B, T, tables[0][0].numel(), ptr(x), ldx, *front, *map(int, ids), int(max_content), T_out, *map(ptr, res[:3]),
+                                  *(() if host else (ptr(counts),)), ptr(res[3]), *(() if host else (stream_ptr(),))), name)
+    return res
+
+
+def _selfies_corpus(name, tokens, offsets, N, rows, front, tables, max_content, stride, given, counts, err):
+    """The same for the _corpus entries; given = (tokens_out, offsets_out, status, info)."""
+    N, B = int(N), rows.numel()
+    dev = tokens.device
+    _csr(tokens, offsets, N)
+    assert rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_contiguous() and rows.device == dev and B >= 1
+    _selfies_tables(dev, tables, counts, max_content)
+    stride = int(max_content) if stride is None else int(stride)
+    offsets_out, = _outputs(2 * B + 1, dev, ((torch.int64, (), False),), given[1:2])
+    tokens_out, status, info = _outputs(B, dev, ((torch.uint8, (stride,), False), (torch.int32, (), False)) + _SELFIES_OUT, given[:1] + given[2:])
+    assert err is None or (err.dtype == torch.int32 and err.numel() == 1 and err.device == dev)
+    check(getattr(L.load(), name)(ptr(tokens), ptr(offsets), N, ptr(rows), B, tables[0][0].numel(), *front, int(max_content), stride,
+                                  ptr(tokens_out), ptr(offsets_out), ptr(status), ptr(counts), ptr(err), ptr(info), stream_ptr()), name)
+    return tokens_out, offsets_out, status, info
+
+
+def selfies_decode_rows(x, sinfo, emit, bos_id, eos_id, pad_id, max_content=127, T_out=None, out=None, out_len=None, status=None, info=None,
+                        counts=None):
+    """SELFIES token rows x (int64 [B, T], bos first; sinfo = ``vocab.selfies_info_table`` of their vocabulary) decoded on the device to
+    SMILES token rows: (out int64 [B, T_out], out_len int32 [B], status int32 [B], info int32 [B, 4]) -- every row derived into a graph by
+    this library's own SELFIES rules (include/mvae.h, "SELFIES") and written in the canonical Kekule spelling of ``smiles_canon_rows``
+    in the SMILES vocabulary that emit (``vocab.smiles_emit_table``) and bos_id / eos_id / pad_id describe.  status
+    (``SELFIES_STATUS_NAMES``): 0, 1 (a token that is no symbol, or no atom), or the writer's 9 - 13; a row that is not written gives
+    the EMPTY row, never a copy.  info = ``SELFIES_DECODE_INFO``; ``info=False``: not written.  counts: int32 [32].  NOT the selfies
+    package's decoder: agreement with it is neither tested nor claimed.  One launch (mvae_selfies_decode_rows)."""
+    return _selfies_rows("mvae_selfies_decode_rows", False, x, (ptr(sinfo), ptr(emit)), ((sinfo, None), (emit, REWRITE_EMIT)),
+                         (bos_id, eos_id, pad_id), max_content, T_out, (out, out_len, status, info), counts)
+
+
+def selfies_decode_host(x, sinfo, emit, bos_id, eos_id, pad_id, max_content=127, T_out=None, out=None, out_len=None, status=None, info=None):
+    """selfies_decode_rows on HOST tensors: the same source compiled for the CPU, a plain loop over the rows (mvae_selfies_decode_host) --
+    for tests and for machines without a device; not a fallback of the device entries."""
+    return _selfies_rows("mvae_selfies_decode_host", True, x, (ptr(sinfo), ptr(emit)), ((sinfo, None), (emit, REWRITE_EMIT)),
+                         (bos_id, eos_id, pad_id), max_content, T_out, (out, out_len, status, info), None)
+
+
+def selfies_decode_corpus(tokens, offsets, N, rows, sinfo, emit, max_content=127, stride=None, tokens_out=None, offsets_out=None, status=None,
+                          info=None, counts=None, err=None):
+    """selfies_decode_rows over the rows `rows` (int64 [B]) of a CSR corpus of SELFIES tokens, one launch (mvae_selfies_decode_corpus):
+    (tokens_out uint8 [B, stride], offsets_out int64 [2 B + 1], status int32 [B], info int32 [B, 4]) in the gapped CSR layout of
+    ``smiles_rewrite_corpus``; a row id outside [0, N) gives status 1 and err 2."""
+    return _selfies_corpus("mvae_selfies_decode_corpus", tokens, offsets, N, rows, (ptr(sinfo), ptr(emit)), ((sinfo, None), (emit, REWRITE_EMIT)),
+                           max_content, stride, (tokens_out, offsets_out, status, info), counts, err)
+
+
+def selfies_encode_rows(x, tok_info, chem_info, emit, eos_in, semit, bos_id, eos_id, pad_id, max_content=127, T_out=None, out=None, out_len=None,
+                        status=None, info=None, counts=None):
+    """SMILES token rows x (int64 [B, T], bos first; tok_info, chem_info, emit and eos_in describe their vocabulary) encoded on the device
+    to SELFIES token rows: (out, out_len, status, info) -- the atoms in their string order, parentheses as branch symbols with a length,
+    the second ring digit as a ring symbol with a distance, bond orders from the matching of ``smiles_kekule_rows`` (include/mvae.h,
+    "SELFIES": Encode), in the SELFIES vocabulary that semit (``vocab.selfies_emit_table``) and bos_id / eos_id / pad_id describe.
+    status: the walk's 1 - 6, 7 "kekule", 8 "stereo", 12 "long", 13 for a symbol the vocabulary lacks, 18 "selfies_capacity" for an atom
+    over the capacity of its symbol; a refused row gives the EMPTY row.  info = ``SELFIES_ENCODE_INFO``.  NOT the selfies package's
+    encoder.  One launch (mvae_selfies_encode_rows)."""
+    _graph_tables(tok_info, chem_info, x.device)
+    return _selfies_rows("mvae_selfies_encode_rows", False, x, (ptr(tok_info), ptr(chem_info), ptr(emit), int(eos_in), ptr(semit)),
+                         ((tok_info, None), (chem_info, None), (emit, REWRITE_EMIT), (semit, SELFIES_EMIT)), (bos_id, eos_id, pad_id), max_content,
+                         T_out, (out, out_len, status, info), counts)
+
+
+def selfies_encode_host(x, tok_info, chem_info, emit, eos_in, semit, bos_id, eos_id, pad_id, max_content=127, T_out=None, out=None, out_len=None,
+                        status=None, info=None):
+    """selfies_encode_rows on HOST tensors (mvae_selfies_encode_host) -- for tests and for machines without a device; not a fallback."""
+    _graph_tables(tok_info, chem_info, x.device)
+    return _selfies_rows("mvae_selfies_encode_host", True, x, (ptr(tok_info), ptr(chem_info), ptr(emit), int(eos_in), ptr(semit)),
+                         ((tok_info, None), (chem_info, None), (emit, REWRITE_EMIT), (semit, SELFIES_EMIT)), (bos_id, eos_id, pad_id), max_content,
+                         T_out, (out, out_len, status, info), None)
+
+
+def selfies_encode_corpus(tokens, offsets, N, rows, tok_info, chem_info, emit, semit, max_content=127, stride=None, tokens_out=None,
+                          offsets_out=None, status=None, info=None, counts=None, err=None):
+    """selfies_encode_rows over the rows `rows` (int64 [B]) of the CSR corpus of SMILES tokens, one launch (mvae_selfies_encode_corpus):
+    (tokens_out uint8 [B, stride], offsets_out int64 [2 B + 1], status int32 [B], info int32 [B, 4]) in the gapped CSR layout of
+    ``smiles_rewrite_corpus``; a row id outside [0, N) gives status 1 and err 2."""
+    _graph_tables(tok_info, chem_info, tokens.device)
+    return _selfies_corpus("mvae_selfies_encode_corpus", tokens, offsets, N, rows, (ptr(tok_info), ptr(chem_info), ptr(emit), ptr(semit)),
+                           ((tok_info, None), (chem_info, None), (emit, REWRITE_EMIT), (semit, SELFIES_EMIT)), max_content, stride,
+                           (tokens_out, offsets_out, status, info), counts, err)
+
+
 SUBSTRUCT_QATOMS = 32                         # include/mvae.h: MVAE_SUBSTRUCT_QATOMS, the atoms of a query and the columns of `map`
 SUBSTRUCT_QUERIES = 64                        # MVAE_SUBSTRUCT_QUERIES, the queries of one launch: one bit of an int64 each
 SUBSTRUCT_WORDS = 100                         # MVAE_SUBSTRUCT_WORDS, the int32 words of one compiled query

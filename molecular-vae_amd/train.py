@@ -802,7 +802,7 @@ def moses_reconstruction(model, batches, beam_width=1, max_len=100, syntax=False
 def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top_k=None, top_p=None, seed=0, z=None, syntax=False,
                    count_valid=False, novel_against=None, prefix=None, nearest=False, valence=False,
                    int_div=False, snn=False, scaffolds=False, kekule=False, canonical=False, filters=None, filter_steps=65536,
-                   top_scaffolds=0, fragments=False, normal=False):
+                   top_scaffolds=0, fragments=False, normal=False, selfies=None):
     """The reference's generation pipeline (``hugesample.py``: sample in batches, hash the strings, count unique / total) with the hashing
     and the deduplication on the device: ``n_samples`` sequences from a ``mosesvae.VAE`` in batches of ``batch_size`` (the last one shorter),
     batch j with seed ``seed + j`` and ``temp`` / ``top_k`` / ``top_p`` as ``VAE.sample`` takes them.  ``z`` None draws each batch's latents
@@ -926,7 +926,17 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     lowest row of ``novel_against.normal_form()`` that equals the sample's normal form, -1 for none (one exact ``lookup`` per batch in
     the device index ``canonical=True`` uses; the corpus is put into normal form once, by one launch, and cached), and "novel_normal",
     the distinct normal-form rows of status 0 that equal no corpus row's.  Without the flag the launches and the keys of the result are
-    what they were."""
+    what they were.
+    ``selfies=smiles_vocab`` (a model built on a ``vocab.SelfiesVocab``; ValueError otherwise, and for a vocabulary of more than 64 ids
+    or max_len > 129, before any device work): the reference's own pipeline, whose samples are SELFIES rows.  Each batch's sampled
+    rows go through one ``mvae_selfies_decode_rows`` launch (``VAE.to_smiles``: this library's own derivation, include/mvae.h, "SELFIES",
+    NOT the selfies package's decoder), and every figure above that reads a molecule -- ``count_valid``, ``valence``, ``kekule``,
+    ``canonical``, ``normal``, ``novel_against`` (a corpus in `smiles_vocab`), ``nearest``, ``scaffolds``, ``fragments``, ``int_div``,
+    ``snn``, ``filters`` -- is computed on the decoded SMILES rows by the same code under `smiles_vocab`.  "unique", "strings", "counts"
+    and "logq" stay on the sampled SELFIES rows, so two SELFIES rows of one molecule are two of "unique" and one of
+    "unique_canonical".  The result gains "decoded", the samples whose decode status is 0 (duplicates included), and "decode_status",
+    aligned with "strings".  ``syntax=True`` is refused: every SELFIES row is a molecule.  Without ``selfies`` nothing changes and no new
+    launch happens."""
     n_samples, batch_size, max_len = int(n_samples), int(batch_size), int(max_len)
     if n_samples < 1 or batch_size < 1 or max_len < 1:
         raise ValueError(f"moses_generate: n_samples, batch_size and max_len must be >= 1, got {n_samples}, {batch_size}, {max_len}")
@@ -937,11 +947,22 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         raise ValueError(f"moses_generate: z must be [{n_samples}, {model.d_z}], got {tuple(z.shape)}")
     forced = model._prefix_table(prefix, n_samples, max_len, "moses_generate")
     dev = model.device
+    cm = model                                                  # what reads molecules: the model, or its SMILES side under `selfies`
+    if selfies is not None:
+        from .mosesvae import SmilesView
+        from .vocab import SelfiesVocab
+        if not isinstance(model.vocabulary, SelfiesVocab):
+            raise ValueError("moses_generate: selfies= needs a model built on a vocab.SelfiesVocab")
+        if len(model.vocabulary) > 64 or len(selfies) > 64:
+            raise ValueError(f"moses_generate: selfies= supports at most 64 ids, the vocabularies have {len(model.vocabulary)} and {len(selfies)}")
+        if max_len > 129:
+            raise ValueError(f"moses_generate: selfies= supports max_len <= 129, got {max_len}")
+        cm = SmilesView(model, selfies)
     if novel_against is not None:
         from .data import MosesDeviceDataset
         if not isinstance(novel_against, MosesDeviceDataset):
             raise ValueError(f"moses_generate: novel_against must be a MosesDeviceDataset, got {type(novel_against).__name__}")
-        if novel_against.vocab.c2i != model.vocabulary.c2i:
+        if novel_against.vocab.c2i != cm.vocabulary.c2i:
             raise ValueError("moses_generate: novel_against was tokenised with another vocabulary than the model's")
         d = novel_against.device
         if d.type != dev.type or (d.type == "cuda" and (torch.cuda.current_device() if d.index is None else d.index)
@@ -950,22 +971,22 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     if nearest:
         if novel_against is None:
             raise ValueError("moses_generate: nearest=True needs novel_against, the corpus to search")
-        if len(model.vocabulary) > ops.EDIT_V_MAX:
-            raise ValueError(f"moses_generate: nearest=True supports at most {ops.EDIT_V_MAX} ids, the vocabulary has {len(model.vocabulary)}")
+        if len(cm.vocabulary) > ops.EDIT_V_MAX:
+            raise ValueError(f"moses_generate: nearest=True supports at most {ops.EDIT_V_MAX} ids, the vocabulary has {len(cm.vocabulary)}")
         if max_len - 1 > ops.EDIT_PATTERN_MAX:
             raise ValueError(f"moses_generate: nearest=True supports max_len <= {ops.EDIT_PATTERN_MAX + 1}, got {max_len}")
-    if valence and len(model.vocabulary) > 64:
-        raise ValueError(f"moses_generate: valence=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
-    if (int_div or snn) and len(model.vocabulary) > 64:
-        raise ValueError(f"moses_generate: int_div / snn support at most 64 ids, the vocabulary has {len(model.vocabulary)}")
+    if valence and len(cm.vocabulary) > 64:
+        raise ValueError(f"moses_generate: valence=True supports at most 64 ids, the vocabulary has {len(cm.vocabulary)}")
+    if (int_div or snn) and len(cm.vocabulary) > 64:
+        raise ValueError(f"moses_generate: int_div / snn support at most 64 ids, the vocabulary has {len(cm.vocabulary)}")
     if snn and novel_against is None:
         raise ValueError("moses_generate: snn=True needs novel_against, the corpus to search")
-    if scaffolds and len(model.vocabulary) > 64:
-        raise ValueError(f"moses_generate: scaffolds=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
-    if fragments and len(model.vocabulary) > 64:
-        raise ValueError(f"moses_generate: fragments=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
-    if kekule and len(model.vocabulary) > 64:
-        raise ValueError(f"moses_generate: kekule=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
+    if scaffolds and len(cm.vocabulary) > 64:
+        raise ValueError(f"moses_generate: scaffolds=True supports at most 64 ids, the vocabulary has {len(cm.vocabulary)}")
+    if fragments and len(cm.vocabulary) > 64:
+        raise ValueError(f"moses_generate: fragments=True supports at most 64 ids, the vocabulary has {len(cm.vocabulary)}")
+    if kekule and len(cm.vocabulary) > 64:
+        raise ValueError(f"moses_generate: kekule=True supports at most 64 ids, the vocabulary has {len(cm.vocabulary)}")
     top_scaffolds = int(top_scaffolds)
     if top_scaffolds < 0:
         raise ValueError(f"moses_generate: top_scaffolds must be >= 0, got {top_scaffolds}")
@@ -975,18 +996,18 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         if max_len > 129:
             raise ValueError(f"moses_generate: top_scaffolds supports max_len <= 129, got {max_len}")
     if canonical:
-        if len(model.vocabulary) > 64:
-            raise ValueError(f"moses_generate: canonical=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
+        if len(cm.vocabulary) > 64:
+            raise ValueError(f"moses_generate: canonical=True supports at most 64 ids, the vocabulary has {len(cm.vocabulary)}")
         if max_len > 129:
             raise ValueError(f"moses_generate: canonical=True supports max_len <= 129, got {max_len}")
     if normal:
-        if len(model.vocabulary) > 64:
-            raise ValueError(f"moses_generate: normal=True supports at most 64 ids, the vocabulary has {len(model.vocabulary)}")
+        if len(cm.vocabulary) > 64:
+            raise ValueError(f"moses_generate: normal=True supports at most 64 ids, the vocabulary has {len(cm.vocabulary)}")
         if max_len > 129:
             raise ValueError(f"moses_generate: normal=True supports max_len <= 129, got {max_len}")
     if filters is not None:
         from .data import compile_substructures
-        filters = compile_substructures(filters, model.vocabulary)
+        filters = compile_substructures(filters, cm.vocabulary)
         if int(filter_steps) != filter_steps or not 1 <= filter_steps <= ops.SUBSTRUCT_MAX_STEPS:
             raise ValueError(f"moses_generate: filter_steps must be an integer in [1, {ops.SUBSTRUCT_MAX_STEPS}], got {filter_steps!r}")
     if forced is not None and syntax:
@@ -1020,6 +1041,8 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
     canon_corpus = novel_against.canonical() if canonical and novel_against is not None else None       # one launch, cached by the dataset
     normals = []                                                # (normal-form row [*, 129], status, corpus row or None) of each new sample, likewise
     normal_corpus = novel_against.normal_form() if normal and novel_against is not None else None       # one launch, cached by the dataset
+    decs = []                                                   # the decode status of each new sample, likewise
+    n_dec = torch.zeros((), dtype=i64, device=dev) if selfies is not None else None
     filt = torch.zeros(2 + 2 * len(filters), dtype=i64, device=dev) if filters is not None else None      # _filter_counts, summed over the batches
     stage = [None, None]                                       # pinned staging rows [batch_size, max_len + 1] (ids, end), alternating
     pending = None
@@ -1035,12 +1058,16 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         zb = model.sample_z_prior(n) if z is None else z[b0:b0 + n]
         fb = None if forced is None else forced if forced[0].shape[0] == 1 else (forced[0][b0:b0 + n], forced[1][b0:b0 + n])
         x, ends, logq, h = model._sample_tokens(zb, max_len, temp, int(seed) + j, k, p, syntax=bool(syntax), forced=fb, check_prefix=False)
-        ok = model.syntax_valid(x) if count_valid else None
-        match = novel_against.lookup(x) if novel_against is not None else None
-        graph = model.descriptors(x) if valence else None
-        kek = model.kekule(x, mate=False) if kekule else None
+        xc = x                                                  # the rows that spell molecules
+        if selfies is not None:
+            xc, dec = model.to_smiles(x, selfies)               # 129 columns; the empty row where dec != 0
+            n_dec += (dec == 0).sum()
+        ok = cm.syntax_valid(xc) if count_valid else None
+        match = novel_against.lookup(xc) if novel_against is not None else None
+        graph = cm.descriptors(xc) if valence else None
+        kek = cm.kekule(xc, mate=False) if kekule else None
         if filters is not None:
-            filt += _filter_counts(*model._substructure_words(x, filters, filter_steps), len(filters))
+            filt += _filter_counts(*cm._substructure_words(xc, filters, filter_steps), len(filters))
         hs, order = torch.sort(h, stable=True)                  # equal hashes: ascending row, so a run starts at its first occurrence
         first = torch.ones(n, dtype=torch.bool, device=dev)
         first[1:] = hs[1:] != hs[:-1]
@@ -1085,14 +1112,16 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
             rows[:n_new].copy_(torch.cat([x[sel], ends[sel, None]], 1), non_blocking=True)
             pending = (rows, n_new)
             logqs.append(logq[sel])
+            if selfies is not None:
+                decs.append(dec[sel])
             if match is not None:
                 matches.append(match[sel])
             if nearest:
-                near.append(novel_against.nearest_strings(x[sel], k=1))
+                near.append(novel_against.nearest_strings(xc[sel], k=1))
             if valence:
                 chem.append(tuple(graph[name][sel] for name in ("status", "weight", "heavy_atoms", "rings")))
             if int_div or snn:
-                f = model.fingerprints(x[sel])
+                f = cm.fingerprints(xc[sel])
                 fine = f["status"] == 0
                 n_fp += fine.sum()
                 if int_div:
@@ -1103,21 +1132,21 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
                     snns.append((s_sim, torch.where(fine, s_row[:, 0], torch.full_like(s_row[:, 0], -1))))
                     snn_sum += torch.where(fine, s_sim, torch.zeros_like(s_sim)).double().sum()
             if scaffolds:
-                sc = model.scaffolds(x[sel])
+                sc = cm.scaffolds(xc[sel])
                 scafs.append((sc["mol_key"], sc["scaffold_key"], sc["atoms"]))
                 if top_scaffolds:
-                    s_rows, _, s_status = model.scaffold_smiles(x[sel])      # 129 columns, as the canonical rows below
+                    s_rows, _, s_status = cm.scaffold_smiles(xc[sel])      # 129 columns, as the canonical rows below
                     scaf_rows.append((s_rows, s_status))
             if fragments:
-                fr = model.fragments(x[sel])
+                fr = cm.fragments(xc[sel])
                 frags.append((fr["keys"], fr["status"]))
             if kekule:
                 keks.append((kek["status"][sel], kek["deficiency"][sel]))
             if canonical:
-                c_rows, c_status = model.canonical(x[sel])          # 129 columns: 127 content tokens at the most, and max_len <= 129
+                c_rows, c_status = cm.canonical(xc[sel])          # 129 columns: 127 content tokens at the most, and max_len <= 129
                 canons.append((c_rows, c_status, canon_corpus.lookup(c_rows) if canon_corpus is not None else None))
             if normal:
-                a_rows, a_status = model.normal_form(x[sel])        # 129 columns, as the canonical rows
+                a_rows, a_status = cm.normal_form(xc[sel])        # 129 columns, as the canonical rows
                 normals.append((a_rows, a_status, normal_corpus.lookup(a_rows) if normal_corpus is not None else None))
             g0 = counts.numel()
             counts = torch.cat([counts, cnt[src]])
@@ -1128,6 +1157,9 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         convert(pending)
     res = {"total": n_samples, "unique": len(strings), "strings": strings, "counts": counts.tolist(),
            "logq": torch.cat(logqs).tolist() if logqs else []}
+    if selfies is not None:
+        res["decoded"] = int(n_dec)
+        res["decode_status"] = torch.cat(decs).tolist() if decs else []
     if count_valid:
         res["valid"], res["valid_unique"] = int(n_valid), int(n_valid_new)
     if novel_against is not None:
@@ -1176,7 +1208,7 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
             distinct, inverse = torch.unique(s_rows[fine], dim=0, return_inverse=True)
             drawn = torch.zeros(distinct.shape[0], dtype=i64, device=dev).index_add_(0, inverse, counts[fine])
             best = torch.sort(drawn, descending=True, stable=True)[1][:top_scaffolds]
-            v = model.vocabulary
+            v = cm.vocabulary
             res["top_scaffolds"] = [(v.ids2string(r[:r.index(v.eos) + 1], rem_bos=True, rem_eos=True), c)
                                     for r, c in zip(distinct[best].tolist(), drawn[best].tolist())]
     if fragments:
@@ -1199,7 +1231,7 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         c_status = torch.cat([c[1] for c in canons]) if canons else torch.empty(0, dtype=torch.int32, device=dev)
         res["canonical_status"] = c_status.tolist()
         res["canonical_status_counts"] = dict(enumerate(torch.bincount(c_status.cpu(), minlength=len(ops.REWRITE_STATUS_NAMES)).tolist()))
-        v = model.vocabulary
+        v = cm.vocabulary
         res["canonical_strings"] = [s if st else v.ids2string(r[:r.index(v.eos) + 1], rem_bos=True, rem_eos=True)
                                     for s, st, r in zip(strings, res["canonical_status"], c_rows.tolist())]
         fine = c_status == 0
@@ -1213,7 +1245,7 @@ def moses_generate(model, n_samples, batch_size=4096, max_len=100, temp=1.0, top
         a_status = torch.cat([c[1] for c in normals]) if normals else torch.empty(0, dtype=torch.int32, device=dev)
         res["normal_status"] = a_status.tolist()
         res["normal_status_counts"] = dict(enumerate(torch.bincount(a_status.cpu(), minlength=len(ops.AROMATIZE_STATUS_NAMES)).tolist()))
-        v = model.vocabulary
+        v = cm.vocabulary
         res["normal_strings"] = [s if st else v.ids2string(r[:r.index(v.eos) + 1], rem_bos=True, rem_eos=True)
                                  for s, st, r in zip(strings, res["normal_status"], a_rows.tolist())]
         distinct = torch.unique(a_rows[a_status == 0], dim=0)

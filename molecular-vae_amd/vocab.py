@@ -3,6 +3,8 @@
 Symbols are the sorted characters of the corpus followed by the four specials <bos>, <eos>, <pad>, <unk> (in that
 order), so ids are reproducible.  ``OneHotVocab.vectors`` is the identity that initialises ``VAE.x_emb`` (mosesvae.py:48-50).
 """
+import re
+
 import torch
 
 
@@ -229,4 +231,145 @@ def smiles_emit_table(vocab):
     for k in range(2):
         half = (mask >> (32 * k)) & 0xFFFFFFFF
         table[SMI_EMIT_STEREO + k] = half - (1 << 32) if half >= 1 << 31 else half
+    return torch.tensor(table, dtype=torch.int32)
+
+
+# SELFIES (include/mvae.h, "SELFIES"; csrc/selfies.hpp): the symbol kinds of the info table and the roles of the emit table
+(SELFIES_OTHER, SELFIES_ATOM, SELFIES_BRANCH, SELFIES_RING, SELFIES_NOP, SELFIES_EOS) = range(6)
+SELFIES_EMIT_WORDS = 529
+SELFIES_EMIT_BRANCH, SELFIES_EMIT_RING, SELFIES_EMIT_INDEX = 495, 504, 513
+SELFIES_MAX_SYMBOLS = 60                                          # + the four specials = the 64 ids the sampling launches take
+SELFIES_INDEX_SYMBOLS = ("[C]", "[Ring1]", "[Ring2]", "[Branch1]", "[=Branch1]", "[#Branch1]", "[Branch2]", "[=Branch2]", "[#Branch2]",
+                         "[O]", "[N]", "[=N]", "[=C]", "[#C]", "[S]", "[P]")
+_SELFIES_DEFAULT = SELFIES_INDEX_SYMBOLS + (
+    "[=Ring1]", "[=Ring2]", "[nop]", "[F]", "[Cl]", "[Br]", "[I]", "[B]", "[=O]", "[=S]", "[#N]", "[=P]", "[=B]",
+    "[N+1]", "[=N+1]", "[#N+1]", "[NH1+1]", "[=NH1+1]", "[NH2+1]", "[=NH2+1]", "[NH3+1]", "[N-1]", "[=N-1]", "[NH1-1]", "[NH1]", "[O-1]",
+    "[O+1]", "[=O+1]", "[OH1+1]", "[S-1]", "[S+1]", "[=S+1]", "[SH1]", "[C-1]", "[#C-1]", "[CH1-1]", "[CH1]", "[=CH1]", "[CH2]", "[B-1]",
+    "[PH1]", "[P+1]", "[=P+1]", "[H]")
+_SELFIES_ATOM = re.compile(r"\[(=|#)?(Cl|Br|[HBCNOFPSI])(?:H([1-4]))?(?:([+-])1)?\]")
+_SELFIES_STRUCT = re.compile(r"\[(=|#)?(Branch|Ring)([1-3])\]")
+_SELFIES_SYMBOL = re.compile(r"\[[^\[\]]*\]")
+# the largest valence by charge -1 / 0 / +1 (csrc/smiles_graph.hpp: VMAX_NEG, VMAX_0, VMAX_POS; None: no entry)
+_SELFIES_VMAX = {"H": (0, 1, 0), "B": (4, 3, None), "C": (3, 4, 3), "N": (2, 3, 4), "O": (1, 2, 3), "F": (0, 1, None), "P": (2, 5, 4),
+                 "S": (1, 6, 5), "Cl": (0, 1, None), "Br": (0, 1, None), "I": (0, 5, None)}
+
+
+def selfies_symbol(symbol):
+    """One SELFIES symbol as the definition reads it: a dict with kind and beta, for an atom element / charge / h / bracket / cap, for a
+    branch or ring symbol L.  ValueError for a symbol that does not parse, whose (element, charge) has no valence entry, or whose
+    capacity is below 1 (include/mvae.h, "SELFIES": Symbols, Capacity)."""
+    if symbol == "[nop]":
+        return {"kind": SELFIES_NOP, "beta": 1}
+    m = _SELFIES_STRUCT.fullmatch(symbol)
+    if m:
+        return {"kind": SELFIES_BRANCH if m.group(2) == "Branch" else SELFIES_RING, "beta": {None: 1, "=": 2, "#": 3}[m.group(1)],
+                "L": int(m.group(3))}
+    m = _SELFIES_ATOM.fullmatch(symbol)
+    if not m:
+        raise ValueError(f"SelfiesVocab: {symbol!r} is no SELFIES symbol this library reads")
+    el, h, chg = m.group(2), int(m.group(3) or 0), {None: 0, "+": 1, "-": -1}[m.group(4)]
+    vmax = _SELFIES_VMAX[el][chg + 1]
+    if vmax is None:
+        raise ValueError(f"SelfiesVocab: {symbol!r}: no valence entry for {el} with charge {chg:+d}")
+    cap = (1 if el == "I" and chg == 0 else vmax) - h
+    if cap < 1:
+        raise ValueError(f"SelfiesVocab: {symbol!r} has capacity {cap}: it could not be bonded to anything")
+    return {"kind": SELFIES_ATOM, "beta": {None: 1, "=": 2, "#": 3}[m.group(1)], "element": SMI_ELEMENTS.index(el), "charge": chg, "h": h,
+            "bracket": int(h > 0 or chg != 0 or el == "H"), "cap": cap}
+
+
+class SelfiesVocab(OneHotVocab):
+    """A vocabulary of SELFIES symbols: a CharVocab whose characters are private characters, one per symbol (U+00A1 onwards, in the sorted
+    order of the symbols: single latin-1 bytes that no SMILES uses, so that ``tokenize_corpus`` takes ``encode_chars`` text), so that
+    everything written for a CharVocab -- the models, the collate, the device corpus -- takes it as it is.
+    ``string2ids`` takes SELFIES text and splits it at the brackets, ``ids2string`` returns SELFIES text; ``symbols`` is the sorted list.
+    At most 60 symbols.  The reading of the symbols is this library's (include/mvae.h, "SELFIES"), NOT the selfies package's."""
+
+    def __init__(self, symbols, ss=SS):
+        symbols = sorted(set(symbols))
+        if len(symbols) > SELFIES_MAX_SYMBOLS:
+            raise ValueError(f"SelfiesVocab: {len(symbols)} symbols, at most {SELFIES_MAX_SYMBOLS} are supported")
+        self.parsed = {s: selfies_symbol(s) for s in symbols}
+        self.symbols = symbols
+        self.sym2char = {s: chr(0xA1 + k) for k, s in enumerate(symbols)}
+        self.char2sym = {c: s for s, c in self.sym2char.items()}
+        super().__init__(set(self.sym2char.values()), ss)
+
+    @classmethod
+    def from_data(cls, data, *args, **kwargs):
+        return cls({s for row in data for s in split_selfies(row)}, *args, **kwargs)
+
+    @classmethod
+    def default(cls):
+        """A fixed alphabet: the 16 index symbols, [=Ring1], [=Ring2], [nop], and C N O F S P Cl Br I B with the common charged and
+        hydrogen forms."""
+        return cls(_SELFIES_DEFAULT)
+
+    @staticmethod
+    def split(string):
+        return split_selfies(string)
+
+    def symbol2id(self, symbol):
+        return self.c2i.get(self.sym2char.get(symbol), self.unk)
+
+    def id2symbol(self, id):
+        ch = self.i2c.get(id, self.ss.unk)
+        return self.char2sym.get(ch, ch)
+
+    def encode_chars(self, string):
+        """SELFIES text as the string of private characters a CharVocab-based corpus holds."""
+        return "".join(self.sym2char.get(s, "\xa0") for s in split_selfies(string))
+
+    def string2ids(self, string, add_bos=False, add_eos=False):
+        ids = [self.symbol2id(s) for s in split_selfies(string)]
+        return ([self.bos] if add_bos else []) + ids + ([self.eos] if add_eos else [])
+
+    def ids2string(self, ids, rem_bos=True, rem_eos=True):
+        ids = list(ids)
+        if ids and rem_bos and ids[0] == self.bos:
+            ids = ids[1:]
+        if ids and rem_eos and ids[-1] == self.eos:
+            ids = ids[:-1]
+        return "".join(self.id2symbol(int(i)) for i in ids)
+
+
+def split_selfies(string):
+    """The symbols of SELFIES text.  ValueError for text outside brackets."""
+    symbols = _SELFIES_SYMBOL.findall(string)
+    if sum(map(len, symbols)) != len(string):
+        raise ValueError(f"split_selfies: {string!r} has text outside [...]")
+    return symbols
+
+
+def selfies_info_table(vocab):
+    """The decode table of a SelfiesVocab: int32 [V], one word per id -- bits 0-2 the kind (SELFIES_*), 3-4 beta; an atom: 5-8 the element
+    (index into SMI_ELEMENTS), 9-10 the charge + 1, 11 bracket atom, 12-14 the stated hydrogens; a branch or ring symbol: 16-17 L; bits
+    20-23 the index value of the symbol.  <eos> is SELFIES_EOS, the other specials SELFIES_OTHER."""
+    table = [SELFIES_OTHER] * len(vocab)
+    for sym, p in vocab.parsed.items():
+        word = p["kind"] | p["beta"] << 3
+        if p["kind"] == SELFIES_ATOM:
+            word |= p["element"] << 5 | (p["charge"] + 1) << 9 | p["bracket"] << 11 | p["h"] << 12
+        elif p["kind"] in (SELFIES_BRANCH, SELFIES_RING):
+            word |= p["L"] << 16
+        if sym in SELFIES_INDEX_SYMBOLS:
+            word |= SELFIES_INDEX_SYMBOLS.index(sym) << 20
+        table[vocab.symbol2id(sym)] = word
+    table[vocab.eos] = SELFIES_EOS
+    return torch.tensor(table, dtype=torch.int32)
+
+
+def selfies_emit_table(vocab):
+    """The encode table of a SelfiesVocab: int32 [529], role -> id, -1 where the vocabulary lacks the symbol -- the atom symbol of (beta,
+    element, charge, hydrogens) at (((beta - 1) * 11 + element) * 3 + charge + 1) * 5 + hydrogens, [bBranchL] at 495 + (beta - 1) * 3 +
+    L - 1, [bRingL] at 504 + the same, the symbol of index value v at 513 + v."""
+    table = [-1] * SELFIES_EMIT_WORDS
+    for sym, p in vocab.parsed.items():
+        i = vocab.symbol2id(sym)
+        if p["kind"] == SELFIES_ATOM:
+            table[(((p["beta"] - 1) * 11 + p["element"]) * 3 + p["charge"] + 1) * 5 + p["h"]] = i
+        elif p["kind"] in (SELFIES_BRANCH, SELFIES_RING):
+            table[(SELFIES_EMIT_BRANCH if p["kind"] == SELFIES_BRANCH else SELFIES_EMIT_RING) + (p["beta"] - 1) * 3 + p["L"] - 1] = i
+        if sym in SELFIES_INDEX_SYMBOLS:
+            table[SELFIES_EMIT_INDEX + SELFIES_INDEX_SYMBOLS.index(sym)] = i
     return torch.tensor(table, dtype=torch.int32)
